@@ -19,9 +19,18 @@ GPU) and relays rank 0's line.  Two records are measured:
           ONE N=4096 posterior replicated on every rank (the single Cholesky does not shard: replicas only), the 8192
           candidates split M/G per rank, 16-byte arg-max exchange.
 
-Prints ONE JSON line on rank 0.  `roofline` is for the dominant kernel (the fused prediction kernel), measured live
-with HIP events on the library's stream; `cpu_baseline` times the CPU oracle (oracle/gp_oracle.py, BLAS-3 Gram +
-LAPACK) on this host, rank 0, N=1.
+Prints ONE JSON line on rank 0.  A plain run measures the headline figure alone: set-up, W warm-up steps, the K timed
+steps of the weak record, and the line (`value`, `ms_per_step`, ...; the keys of what it did not measure are null).
+`--full` adds everything else, each in passes of its own after the weak record: the strong record, per-kernel event
+timing (`roofline`: the dominant kernel, the fused prediction kernel, measured live with HIP events on the library's
+stream), the update latency distribution, the rows beyond the headline path, the batched / config-4 / config-5 blocks,
+the one-process multi-device child and `cpu_baseline` (the CPU oracle, oracle/gp_oracle.py, BLAS-3 Gram + LAPACK, on
+this host, rank 0, N=1).
+
+`--dump-outputs DIR` writes what the last timed step handed its caller (rank 0), float64 .npy files of about 0.6 MB in all:
+logpdf, acq (EI over the 8192 candidates), acq_argmax, acq_max, factor_z (z = L\\(y-m)) and factor_L_sample (a fixed,
+seeded sample of the lower triangle of the Cholesky factor: the whole factor is 128 MB).  The inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -56,6 +65,23 @@ def problem(seed):
     y = np.sin(2 * np.pi * X).sum(0) / np.sqrt(D) + 0.05 * rng.standard_normal(N_OBS)
     Xs = np.random.default_rng(seed + 1).uniform(0, 1, (D, M_CAND))
     return X, y, Xs
+
+
+def factor_sample_index(N, k=1 << 16):
+    """(row, column) of the factor entries --dump-outputs keeps: k fixed, seeded positions in the lower triangle."""
+    rng = np.random.default_rng(2024)
+    a, b = rng.integers(0, N, k), rng.integers(0, N, k)
+    return np.maximum(a, b), np.minimum(a, b)
+
+
+def dump_outputs(path, gp, last):
+    """--dump-outputs: the arrays the last timed step returned to its caller, and the posterior it left resident."""
+    os.makedirs(path, exist_ok=True)
+    L, z = gp.factor()
+    arrays = {"logpdf": [last["logpdf"]], "acq": last["acq"], "acq_argmax": [last["argmax"]], "acq_max": [last["max"]],
+              "factor_z": z, "factor_L_sample": L[factor_sample_index(gp.N)]}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.asarray(a, dtype=np.float64))
 
 
 def flops_update(N, d):
@@ -351,9 +377,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the next_rows measurements (counter-collection passes)")
-    ap.add_argument("--with-config5", action="store_true", help="with --no-extras: still run the batched / config-5 block (counter passes of its kernels)")
+    ap.add_argument("--full", action="store_true", help="also measure everything beyond the headline figure (see the module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs to DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the next_rows measurements (counter-collection passes)")
+    ap.add_argument("--with-config5", action="store_true", help="with --full --no-extras: still run the batched / config-5 block (counter passes of its kernels)")
     ap.add_argument("--inproc-child", type=int, default=0, help=argparse.SUPPRESS)
     args = ap.parse_args()
 
@@ -434,75 +462,89 @@ def main():
     gp = api.GP(X, y, KERNEL, device=dev)
     cand = api.Candidates(Xs, device=dev)
     best = float(y.max())
+    last = {}
+    dump_at = args.steps - 1 if args.dump_outputs is not None and rank == 0 else -1
 
     def step(i, exchange=True):
+        # with --dump-outputs, the step numbered as the last timed one also copies the acquisition values back (the same
+        # launches; a warm-up step with that number runs before it and is overwritten)
+        keep = i == dump_at
         t0 = time.perf_counter()
         # a different noise level each step so no step can reuse the previous factorisation
-        gp.update(lam, 1.0, 0.05 + 1e-4 * (i % 7))
+        lp = gp.update(lam, 1.0, 0.05 + 1e-4 * (i % 7))
         t1 = time.perf_counter()
-        _, am, mx = api.acq_ei([[gp]], cand, [1.0], None, best, want_acq=False)
+        acq, am, mx = api.acq_ei([[gp]], cand, [1.0], None, best, want_acq=keep)
         if world > 1 and exchange:
             mx, am = dist_util.argmax_exchange(mx, am + rank * M_CAND)
         t2 = time.perf_counter()
+        if keep:
+            last.update(logpdf=lp, acq=acq, argmax=am, max=mx)
         return t1 - t0, t2 - t1
 
     note("weak record: posterior update + 8192-candidate acquisition per step")
     elapsed, t_upd, t_acq = timed(step, args.steps, args.warmup)
-    note(f"  {args.steps * 1e3 / 1e3 / t_upd * world:.0f} updates/s, {elapsed / args.steps * 1e3:.3f} ms per step; strong record")
+    note(f"  {args.steps * 1e3 / 1e3 / t_upd * world:.0f} updates/s, {elapsed / args.steps * 1e3:.3f} ms per step")
+    if dump_at >= 0:
+        dump_outputs(args.dump_outputs, gp, last)
+        dump_at = -1                                   # (the later passes of --full that call step() keep nothing)
 
+    # everything below measures beyond the headline figure: --full only
     # ------------------------------------------------------------------ strong: one posterior replicated, candidates M/G
-    Xr, yr, Xsr = problem(1)                      # the same problem on every rank
-    lo, hi = dist_util.shard_range(M_CAND, rank, world)
-    gps = gp if world == 1 else api.GP(Xr, yr, KERNEL, device=dev)
-    cand_s = cand if world == 1 else api.Candidates(Xsr[:, lo:hi], device=dev)
-    best_s = float(yr.max())
-    winner = {}
+    strong = None
+    if args.full:
+        note("strong record")
+        Xr, yr, Xsr = problem(1)                      # the same problem on every rank
+        lo, hi = dist_util.shard_range(M_CAND, rank, world)
+        gps = gp if world == 1 else api.GP(Xr, yr, KERNEL, device=dev)
+        cand_s = cand if world == 1 else api.Candidates(Xsr[:, lo:hi], device=dev)
+        best_s = float(yr.max())
+        winner = {}
 
-    def step_strong(i):
-        t0 = time.perf_counter()
-        gps.update(lam, 1.0, 0.05 + 1e-4 * (i % 7))
-        t1 = time.perf_counter()
-        _, am, mx = api.acq_ei([[gps]], cand_s, [1.0], None, best_s, want_acq=False)
-        if world > 1:
-            mx, am = dist_util.argmax_exchange(mx, am + lo)
-        t2 = time.perf_counter()
-        winner[i % 7] = (am, mx)
-        return t1 - t0, t2 - t1
-
-    s_elapsed, s_upd, s_acq = timed(step_strong, args.steps, args.warmup)
-    # the same step as ONE call per rank where the shard is small enough for the substitution to ride along the replicated update
-    # (boss_gp_update_acq, csrc/rider.hpp): at G = 8 every rank holds 1024 candidates
-    fused_strong = None
-    if hi - lo <= 4096:
-        rode = []
-
-        def step_fused(i):
+        def step_strong(i):
             t0 = time.perf_counter()
-            r = gps.update_acq(lam, 1.0, 0.05 + 1e-4 * (i % 7), cand_s, best=best_s)
-            am, mx = r["argmax"], r["max"]
+            gps.update(lam, 1.0, 0.05 + 1e-4 * (i % 7))
+            t1 = time.perf_counter()
+            _, am, mx = api.acq_ei([[gps]], cand_s, [1.0], None, best_s, want_acq=False)
             if world > 1:
                 mx, am = dist_util.argmax_exchange(mx, am + lo)
-            rode.append(r["fused"])
-            return time.perf_counter() - t0, 0.0
-        f_elapsed, _, _ = timed(step_fused, args.steps, args.warmup)
-        fused_strong = {"ms_per_step": f_elapsed / args.steps * 1e3, "steps_per_sec": args.steps / f_elapsed,
-                        "rode_along": bool(all(rode)), "speedup_over_two_calls": s_elapsed / f_elapsed}
-    strong = {
-        "scaling": "strong", "metric": "acq_evals_per_sec, 8192 candidates of ONE N=4096 posterior sharded M/G (+ replicated update)",
-        "value": args.steps * M_CAND / s_acq, "unit": "evals/s", "n_gpus": world, "M_per_gpu": hi - lo,
-        "ms_acq_shard_incl_exchange": s_acq / args.steps * 1e3, "ms_update_replicated": s_upd / args.steps * 1e3,
-        "ms_per_step": s_elapsed / args.steps * 1e3, "steps_per_sec": args.steps / s_elapsed,
-        "prediction_path": "fused kernel (one workgroup per 32 candidates)" if hi - lo > 4096 else
-                           "256-row substitution steps spread over the chip (few-candidates path, first call on a factorisation)",
-        "argmax": [int(winner[0][0]), float(winner[0][1])],
-        "exchange": "none" if world == 1 else f"16-byte all-gather over {backend}",
-        "one_call_per_step": fused_strong,
-    }
+            t2 = time.perf_counter()
+            winner[i % 7] = (am, mx)
+            return t1 - t0, t2 - t1
+
+        s_elapsed, s_upd, s_acq = timed(step_strong, args.steps, args.warmup)
+        # the same step as ONE call per rank where the shard is small enough for the substitution to ride along the replicated update
+        # (boss_gp_update_acq, csrc/rider.hpp): at G = 8 every rank holds 1024 candidates
+        fused_strong = None
+        if hi - lo <= 4096:
+            rode = []
+
+            def step_fused(i):
+                t0 = time.perf_counter()
+                r = gps.update_acq(lam, 1.0, 0.05 + 1e-4 * (i % 7), cand_s, best=best_s)
+                am, mx = r["argmax"], r["max"]
+                if world > 1:
+                    mx, am = dist_util.argmax_exchange(mx, am + lo)
+                rode.append(r["fused"])
+                return time.perf_counter() - t0, 0.0
+            f_elapsed, _, _ = timed(step_fused, args.steps, args.warmup)
+            fused_strong = {"ms_per_step": f_elapsed / args.steps * 1e3, "steps_per_sec": args.steps / f_elapsed,
+                            "rode_along": bool(all(rode)), "speedup_over_two_calls": s_elapsed / f_elapsed}
+        strong = {
+            "scaling": "strong", "metric": "acq_evals_per_sec, 8192 candidates of ONE N=4096 posterior sharded M/G (+ replicated update)",
+            "value": args.steps * M_CAND / s_acq, "unit": "evals/s", "n_gpus": world, "M_per_gpu": hi - lo,
+            "ms_acq_shard_incl_exchange": s_acq / args.steps * 1e3, "ms_update_replicated": s_upd / args.steps * 1e3,
+            "ms_per_step": s_elapsed / args.steps * 1e3, "steps_per_sec": args.steps / s_elapsed,
+            "prediction_path": "fused kernel (one workgroup per 32 candidates)" if hi - lo > 4096 else
+                               "256-row substitution steps spread over the chip (few-candidates path, first call on a factorisation)",
+            "argmax": [int(winner[0][0]), float(winner[0][1])],
+            "exchange": "none" if world == 1 else f"16-byte all-gather over {backend}",
+            "one_call_per_step": fused_strong,
+        }
 
     # ---- per-kernel HIP-event timing of the dominant kernels (separate pass, events on the library's stream)
     roof = roof_potrf = None
-    note("per-kernel event timing")
-    if rank == 0:
+    if rank == 0 and args.full:
+        note("per-kernel event timing")
         # (a) the dominant kernel inside the UNSERIALISED step: the update runs as always (resident chain, side stream), the event
         # pair is switched on for the acquisition call alone — two hipEventRecord around predict_kernel on the library's stream
         api.prof_reset(dev)
@@ -557,8 +599,8 @@ def main():
     # ---- latency distribution of the posterior update (the resident chain's tail latency): 2000 back-to-back updates, every launch
     # of each stamped on the host (csrc/host_factor.inc, LaunchStamps): an update beyond 2 ms reports where its submission stood still
     upd_dist = None
-    note("update latency distribution")
-    if rank == 0:
+    if rank == 0 and args.full:
+        note("update latency distribution")
         import ctypes as C
         lib = api.load_library()
         lib.boss_debug_launch_stamps.argtypes = [C.c_int, C.c_double]
@@ -584,7 +626,7 @@ def main():
 
     # ---- SURVEY §8f rows built beyond the headline path (rank 0, N=1 only; a fraction of a second)
     extras = None
-    if rank == 0 and world == 1 and not args.no_extras:
+    if rank == 0 and world == 1 and args.full and not args.no_extras:
         note("next rows (gradients, appends, small sizes, gradient observations)")
         gp.update(lam, 1.0, 0.05)
         gp.predict_grad(Xs)                                          # first gradient call on a handle: lazy allocations (transposed factor, 138 MB)
@@ -673,7 +715,7 @@ def main():
 
     # ---- what DESIGN.md claims beyond the single-matrix chain, in the driver's own record (rank 0; N=1 only for the device work)
     batched = acq_by_m = None
-    if rank == 0 and world == 1 and (not args.no_extras or args.with_config5):
+    if rank == 0 and world == 1 and args.full and (not args.no_extras or args.with_config5):
         note("batched updates, config 5, acquisition by call size")
         batched = {}
         rs = np.random.default_rng(4)
@@ -772,7 +814,7 @@ def main():
 
     # ---- BASELINE configs[3]: semiparametric model (parametric mean + GP), 2 constrained outputs, N = 2048, d = 6, 8192 candidates
     config4 = None
-    if rank == 0 and world == 1 and not args.no_extras:
+    if rank == 0 and world == 1 and args.full and not args.no_extras:
         note("config 4 (two outputs, semiparametric)")
         N4, D4, P4 = 2048, 6, 2
         r4 = np.random.default_rng(3)
@@ -823,7 +865,7 @@ def main():
 
     # ---- configs[2] through the one-process multi-GPU entry points (a fresh child process: this one stays alive and idle meanwhile)
     inproc = None
-    if rank == 0 and not args.no_extras:
+    if rank == 0 and args.full and not args.no_extras:
         note("one-process multi-device entry points (child process)")
         try:
             env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
@@ -834,7 +876,7 @@ def main():
             inproc = {"error": repr(e)}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         note("CPU baseline (oracle on the host cores)")
         cpu = cpu_baseline(X, y, Xs, lam)
 

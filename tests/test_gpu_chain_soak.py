@@ -188,7 +188,7 @@ def test_updates_beside_foreign_kernels_are_bit_identical(api, N):
     print(f"N={N}: foreign loops {loops}, fallbacks {fallbacks}, chain switched off {chain_off}")
 
 
-def test_cu_masked_streams_are_bit_identical():
+def test_cu_masked_streams_are_bit_identical(tmp_path):
     """The round-3 experiment that once gave wrong factors: chain and strips on reserved CUs, the update's other kernels on the
     complement (hipExtStreamCreateWithCUMask, BOSS_CU_MASK=1), i.e. every hand-off of the protocol crosses hardware queues AND CU
     sets.  A run with masked streams must reproduce the unmasked run bit for bit — logpdf of every update, the factor of the first and
@@ -198,7 +198,7 @@ def test_cu_masked_streams_are_bit_identical():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, NS="1408,4096", NHASH="2", LONG="90")
+    env = dict(os.environ, NS="1408,4096", NHASH="2", LONG="90", CUMASK_DIR=str(tmp_path))
     env.pop("BOSS_CU_MASK", None)
     tool = os.path.join(root, "tools", "cumask_check.py")
     rec = subprocess.run([sys.executable, tool, "record", "12"], env=env, capture_output=True, text=True, timeout=300)

@@ -44,9 +44,9 @@ def test_two_ranks_on_one_gpu_through_the_library():
 @pytest.mark.timeout(900)
 def test_bench_launches_its_own_ranks():
     """`python bench.py --gpus 2` (no torchrun): the launcher spawns the ranks itself; on a 1-GPU box they share the
-    device and exchange over gloo (`rehearsal`).  The line carries a weak and a strong record."""
+    device and exchange over gloo (`rehearsal`).  With --full the line carries a weak and a strong record."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--no-extras"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--full", "--no-extras"],
                        env=env, capture_output=True, text=True, timeout=800)
     assert r.returncode == 0, r.stderr[-4000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]

@@ -2,13 +2,14 @@
 other kernels on the complement.  `record` (unmasked) stores logpdf and a hash of the whole factor for a cycle of updates; `check`
 (run with BOSS_CU_MASK=1 or 2) repeats them and compares bit for bit.
 python tools/cumask_check.py record|check [reps]"""
-import os, sys, json, hashlib, time, ctypes as C
+import os, sys, json, hashlib, tempfile, time, ctypes as C
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from boss_jl_amd import api
 mode = sys.argv[1]
 reps = int(sys.argv[2]) if len(sys.argv) > 2 else 70
-REF = "/tmp/cumask_ref.json"
+OUT = os.environ.get("CUMASK_DIR", tempfile.gettempdir())      # where `record` leaves what `check` reads
+REF = os.path.join(OUT, "cumask_ref.json")
 NH = int(os.environ.get("NHASH", 7))
 LONG = int(os.environ.get("LONG", 300))
 lib = api.load_library()
@@ -31,9 +32,9 @@ for N in [int(v) for v in os.environ.get("NS", "1408,4096").split(",")]:
             L, z = g.factor()
             h = hashlib.sha256(np.ascontiguousarray(L).tobytes() + np.ascontiguousarray(z).tobytes()).hexdigest()
             if mode == "record" and i == 0:
-                np.save(f"/tmp/cumask_L_{N}.npy", L)
+                np.save(os.path.join(OUT, f"cumask_L_{N}.npy"), L)
             if mode == "check" and i == 0:
-                L0 = np.load(f"/tmp/cumask_L_{N}.npy")
+                L0 = np.load(os.path.join(OUT, f"cumask_L_{N}.npy"))
                 print(f"N {N}: max |L - L_unmasked| at the first update {np.abs(L - L0).max():.3e}, finite {np.isfinite(L).all()}", flush=True)
         rec.append([float(lp).hex(), h])
         if ref is not None:

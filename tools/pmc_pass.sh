@@ -4,7 +4,7 @@ tag=$1; ctrs=$2
 out=gpurun_out/pmc_$tag
 mkdir -p $out
 export TMPDIR=/tmp
-rocprofv3 --pmc $ctrs --kernel-trace --output-format csv -d $out -o p -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras > $out/bench.json 2> $out/err.log
+rocprofv3 --pmc $ctrs --kernel-trace --output-format csv -d $out -o p -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-extras > $out/bench.json 2> $out/err.log
 python3 - "$out" <<'PY'
 import csv, sys, glob, collections
 f = glob.glob(sys.argv[1] + "/**/p_counter_collection.csv", recursive=True)[0]
