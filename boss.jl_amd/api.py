@@ -62,6 +62,8 @@ SIGNATURES = {
     "boss_gp_predict_grad": (C.c_int, [C.c_void_p, C.c_int, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp,
                                        C.POINTER(C.c_long)]),
     "boss_gp_predict_cov": (C.c_int, [C.c_void_p, C.c_int, _c_dp, _c_dp, _c_dp, _c_dp, C.POINTER(C.c_long)]),
+    "boss_ggp_predict_cov": (C.c_int, [C.c_void_p, C.c_int, _c_dp, _c_dp, _c_dp]),
+    "boss_ngp_predict_cov": (C.c_int, [C.c_void_p, C.c_int, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, C.POINTER(C.c_long)]),
     "boss_cand_create": (C.c_int, [C.c_int, C.c_int, C.c_int, _c_dp, C.POINTER(C.c_void_p)]),
     "boss_cand_free": (None, [C.c_void_p]),
     "boss_acq_ei": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, _c_dp, _c_dp, _c_dp, C.c_int,
@@ -442,6 +444,20 @@ class GradGP(GP):
         self.logpdf = out.value
         return out.value
 
+    def predict_value_cov(self, Xs):
+        """mean_and_cov of the value posterior (gradient_gp.jl:368-373, boss_ggp_predict_cov): returns (mu[M], cov[M,M]),
+        cov exactly symmetric, neither jittered nor clipped."""
+        Xs = _f64(Xs)
+        if Xs.ndim == 1:
+            Xs = _f64(Xs.reshape(-1, 1))
+        if Xs.shape[0] != self.d:
+            raise ValueError("candidates must be d×M")
+        M = Xs.shape[1]
+        mu = np.zeros(M)
+        cov = np.zeros((M, M), order="F")
+        _check(load_library().boss_ggp_predict_cov(self._h, M, _dp(Xs), _dp(mu), _dp(cov)))
+        return mu, cov
+
 
 class GibbsGP(GP):
     """One output slice's posterior under the NonstationaryGP's Gibbs kernel (nonstationary_gp.jl:61-107): the
@@ -527,6 +543,31 @@ class GibbsGP(GP):
             raise e
         _check(rc)
         return mu, var
+
+    def predict_cov(self, Xs, lam_Xs=None, amp_Xs=None, mean_Xs=None):
+        """mean_and_cov with the diagonal through _clip_var (boss_ngp_predict_cov): returns (mu[M], cov[M,M]); lam_Xs d×M and
+        amp_Xs M are λ(x*), α(x*) at the (rounded) candidates.  Without them the library refuses the call (BossError)."""
+        Xs = _f64(Xs)
+        if Xs.ndim == 1:
+            Xs = _f64(Xs.reshape(-1, 1))
+        if Xs.shape[0] != self.d:
+            raise ValueError("candidates must be d×M")
+        M = Xs.shape[1]
+        lam = None if lam_Xs is None else _f64(np.asarray(lam_Xs, dtype=np.float64).reshape(self.d, M), 2)
+        amp = None if amp_Xs is None else _f64(np.asarray(amp_Xs).reshape(-1), 1)
+        if amp is not None and amp.shape[0] != M:
+            raise ValueError("amp_Xs must have M entries")
+        ms = None if mean_Xs is None else _f64(np.asarray(mean_Xs).reshape(-1), 1)
+        mu = np.zeros(M)
+        cov = np.zeros((M, M), order="F")
+        bad = C.c_long(-1)
+        rc = load_library().boss_ngp_predict_cov(self._h, M, _dp(Xs), _dp(lam), _dp(amp), _dp(ms), _dp(mu), _dp(cov), C.byref(bad))
+        if rc == BOSS_E_NEG_VAR:
+            e = DomainError(rc, load_library().boss_last_error().decode())
+            e.bad_index = bad.value
+            raise e
+        _check(rc)
+        return mu, cov
 
     def predict_grad(self, Xs, lam_Xs, amp_Xs, dlam_Xs=None, damp_Xs=None, mean_Xs=None, mean_grad=None):
         """mean_and_var and its gradient w.r.t. the candidates (boss_ngp_predict_grad): dlam_Xs d×d×M with [l, m, j] = ∂λ_l/∂x_m at

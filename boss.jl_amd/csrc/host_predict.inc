@@ -624,6 +624,48 @@ extern "C" int boss_gp_predict(boss_gp_t* g, int M, const double* Xs, const doub
 // mean_and_var of a NonstationaryGP posterior (GaussianProcessPosterior over the Gibbs kernel,
 // nonstationary_gp.jl:153-157 -> gaussian_process.jl:143-194): lam_Xs d×M and amp_Xs M are the caller's latent
 // models at the candidates (evaluated at the ROUNDED candidate where dims are discrete, as DiscreteKernel does).
+// The candidates of a nonstationary call with the caller's λ(x*) (d×M) and α(x*) (M), checked and packed on the host (no device
+// work): points rounded where dims are discrete, all three column-padded to Mp.
+struct NgpCand {
+    int Mp = 0;
+    std::vector<double> x, lam, amp;
+};
+static int ngp_pack(const boss_gp* g, int M, const double* Xs, const double* lam_Xs, const double* amp_Xs, NgpCand& p) {
+    const int d = g->d, Mp = round_up(M, 64);
+    p.Mp = Mp;
+    p.lam.assign((size_t)d * Mp, 1.0);
+    p.amp.assign(Mp, 0.0);
+    for (int j = 0; j < M; ++j) {
+        for (int k = 0; k < d; ++k) {
+            const double v = lam_Xs[(size_t)j * d + k];
+            if (!(v > 0.0) || !std::isfinite(v)) return fail(BOSS_E_INVALID, "lengthscales must be finite and > 0");
+            p.lam[(size_t)k * Mp + j] = v;
+        }
+        if (!(amp_Xs[j] >= 0.0) || !std::isfinite(amp_Xs[j])) return fail(BOSS_E_INVALID, "amplitudes must be finite and >= 0");
+        p.amp[j] = amp_Xs[j];
+    }
+    pack_points(p.x, Xs, d, M, Mp, g->discrete.empty() ? nullptr : g->discrete.data());
+    return BOSS_OK;
+}
+// ... and uploaded into the per-device candidate workspace (Craw | λ | α).  Caller holds the context lock.
+static int ngp_upload(Ctx* c, int d, int M, const NgpCand& p, boss_cand& cd, double*& clam, double*& camp) {
+    const int Mp = p.Mp;
+    hipStream_t s = c->stream;
+    int rc = ws_reserve(c->craw, sizeof(double) * ((size_t)2 * d * Mp + Mp));
+    if (rc) return rc;
+    cd.ctx = c;
+    cd.d = d;
+    cd.M = M;
+    cd.Mp = Mp;
+    cd.Craw = (double*)c->craw.p;
+    clam = cd.Craw + (size_t)d * Mp;
+    camp = clam + (size_t)d * Mp;
+    HIPCHK(hipMemcpyAsync(cd.Craw, p.x.data(), sizeof(double) * d * Mp, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(clam, p.lam.data(), sizeof(double) * d * Mp, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(camp, p.amp.data(), sizeof(double) * Mp, hipMemcpyHostToDevice, s));
+    return BOSS_OK;
+}
+
 extern "C" int boss_ngp_predict(boss_gp_t* g, int M, const double* Xs, const double* lam_Xs, const double* amp_Xs,
                                 const double* mean_Xs, double* mu, double* var, long* bad_index) {
     if (!g || !Xs || !lam_Xs || !amp_Xs || !mu || !var) return fail(BOSS_E_INVALID, "NULL argument");
@@ -631,35 +673,17 @@ extern "C" int boss_ngp_predict(boss_gp_t* g, int M, const double* Xs, const dou
     if (M < 1) return fail(BOSS_E_INVALID, "M must be >= 1");
     if (bad_index) *bad_index = -1;
     if (!g->fitted) return fail(BOSS_E_NOT_FITTED, "handle has no valid factorisation");
-    const int d = g->d, Mp = round_up(M, 64);
-    std::vector<double> buf, lam((size_t)d * Mp, 1.0), amp(Mp, 0.0);
-    pack_points(buf, Xs, d, M, Mp, g->discrete.empty() ? nullptr : g->discrete.data());
-    for (int j = 0; j < M; ++j) {
-        for (int k = 0; k < d; ++k) {
-            const double v = lam_Xs[(size_t)j * d + k];
-            if (!(v > 0.0) || !std::isfinite(v)) return fail(BOSS_E_INVALID, "lengthscales must be finite and > 0");
-            lam[(size_t)k * Mp + j] = v;
-        }
-        if (!(amp_Xs[j] >= 0.0) || !std::isfinite(amp_Xs[j])) return fail(BOSS_E_INVALID, "amplitudes must be finite and >= 0");
-        amp[j] = amp_Xs[j];
-    }
+    NgpCand pk;
+    int rc = ngp_pack(g, M, Xs, lam_Xs, amp_Xs, pk);
+    if (rc) return rc;
     Ctx* c = g->ctx;
     HIPCHK(hipSetDevice(c->device));
     std::lock_guard<std::mutex> lk(c->mtx);
     hipStream_t s = c->stream;
-    int rc = ws_reserve(c->craw, sizeof(double) * ((size_t)2 * d * Mp + Mp));
-    if (rc) return rc;
     boss_cand cd;
-    cd.ctx = c;
-    cd.d = d;
-    cd.M = M;
-    cd.Mp = Mp;
-    cd.Craw = (double*)c->craw.p;
-    double* clam = cd.Craw + (size_t)d * Mp;
-    double* camp = clam + (size_t)d * Mp;
-    HIPCHK(hipMemcpyAsync(cd.Craw, buf.data(), sizeof(double) * d * Mp, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(clam, lam.data(), sizeof(double) * d * Mp, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(camp, amp.data(), sizeof(double) * Mp, hipMemcpyHostToDevice, s));
+    double *clam, *camp;
+    rc = ngp_upload(c, g->d, M, pk, cd, clam, camp);
+    if (rc) return rc;
     rc = ws_reserve(c->pred, sizeof(double) * (3 * (size_t)M + 2));   // mu | var | mean | bad
     if (rc) {
         (void)hipStreamSynchronize(s);
@@ -1180,6 +1204,149 @@ extern "C" int boss_gp_predict_cov(boss_gp_t* g, int M, const double* Xs, const 
         if (bad_index) *bad_index = (long)bad;
         char msg[160];
         std::snprintf(msg, sizeof msg, "The posterior GP predicted variance %g but only values above -1e-08 are tolerated. (DomainError)", cov[bad * (size_t)M + bad]);
+        return fail(BOSS_E_NEG_VAR, msg);
+    }
+    return BOSS_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// mean_and_cov / cov of the gradient-observation and nonstationary posteriors: V = L⁻¹K* from predict_enqueue(need_v), then
+// VᵀV on the fp64 MFMA in 64×64 lower-triangle block pairs × chunks of the n range (cov_syrk_partial_kernel) and the fixed-order
+// sum with K** (cov_finish_kernel).  (The plain handles' boss_gp_predict_cov keeps its VALU predict_cov_kernel.)
+// ------------------------------------------------------------------------------------------
+constexpr int COV_MAX_M = 32768;                // M×M doubles = 8 GiB on the device and on the host
+constexpr int COV_TARGET_WG = 512;              // (block pair, chunk) workgroups wanted: two per CU
+constexpr size_t COV_PART_MIN_CAP = 64ull << 20;
+
+// Block pairs P, chunks C of `rows` training rows each.  The partial slabs (C·P blocks of 64×64 doubles) are bounded by the larger
+// of the M×M output and 64 MiB: small M gets up to Np/256 chunks (M = 64: 3 block pairs), large M one chunk (P·32 KiB ≈ 4 M² bytes).
+static void cov_plan(int Np, int M, int& P, int& C, int& rows) {
+    const int nbk = (M + COV_T - 1) / COV_T;
+    P = nbk * (nbk + 1) / 2;
+    const int nrb = Np / PRED_RB;
+    const size_t slab = (size_t)P * COV_T * COV_T * sizeof(double);
+    const size_t cap = std::max((size_t)M * M * sizeof(double), COV_PART_MIN_CAP);
+    int want = (COV_TARGET_WG + P - 1) / P;
+    want = (int)std::min<size_t>((size_t)want, std::max<size_t>(1, cap / slab));
+    want = std::max(1, std::min(want, nrb));
+    const int per = (nrb + want - 1) / want;              // 256-row blocks per chunk
+    rows = per * PRED_RB;
+    C = (nrb + per - 1) / per;
+}
+
+// enqueue Σ into dcov (M×M) from the V slabs predict_enqueue(need_v = true) just left; part has room for cov_plan's C·P blocks
+static void cov_enqueue(boss_gp* g, int M, int form, const double* X, const double* Lam, const double* Amp, int ldx, double* part,
+                        double* dcov, unsigned long long* dbad) {
+    Ctx* c = g->ctx;
+    hipStream_t s = c->stream;
+    static const bool force64 = getenv("BOSS_FORCE_BN64") && atoi(getenv("BOSS_FORCE_BN64"));
+    const int BN = (M >= 64 * 256 || force64) ? 64 : 32;     // must mirror predict_enqueue's choice (V slab layout)
+    int P, C, rows;
+    cov_plan(g->Np, M, P, C, rows);
+    ProfScope ps(c, "cov");
+    hipLaunchKernelGGL(cov_syrk_partial_kernel, dim3(P, C), dim3(256), 0, s, (const double*)c->vscratch.p, g->Np, BN, M, rows, part);
+    if (form == COV_FORM_GIBBS)
+        hipLaunchKernelGGL(cov_finish_kernel<COV_FORM_GIBBS>, dim3(P), dim3(256), 0, s, (const double*)part, C, X, Lam, Amp, g->d, ldx,
+                           g->kernel, g->amp2, M, dcov, dbad);
+    else
+        hipLaunchKernelGGL(cov_finish_kernel<COV_FORM_VALUE>, dim3(P), dim3(256), 0, s, (const double*)part, C, X, Lam, Amp, g->d, ldx,
+                           g->kernel, g->amp2, M, dcov, dbad);
+}
+
+static size_t cov_part_doubles(const boss_gp* g, int M) {
+    int P, C, rows;
+    cov_plan(g->Np, M, P, C, rows);
+    return (size_t)C * P * COV_T * COV_T;
+}
+
+extern "C" int boss_ggp_predict_cov(boss_gp_t* g, int M, const double* Xs, double* mu, double* cov) {
+    if (!g || !Xs || !mu || !cov) return fail(BOSS_E_INVALID, "NULL argument");
+    if (!g->aug) return fail(BOSS_E_INVALID, "handle was not created by boss_ggp_create");
+    if (M < 1) return fail(BOSS_E_INVALID, "M must be >= 1");
+    if (M > COV_MAX_M) return fail(BOSS_E_INVALID, "M above the covariance limit of 32768 candidates");
+    if (!g->fitted) return fail(BOSS_E_NOT_FITTED, "handle has no valid factorisation");
+    Ctx* c = g->ctx;
+    HIPCHK(hipSetDevice(c->device));
+    std::lock_guard<std::mutex> lk(c->mtx);                 // the V slabs live in the shared scratch
+    hipStream_t s = c->stream;
+    boss_cand cd;
+    int rc = temp_cand(c, g->d, M, Xs, &cd);
+    if (rc) return rc;
+    double* dev = nullptr;   // mu | var | cov | partials
+    const size_t MM = (size_t)M * M;
+    if (dev_malloc((void**)&dev, sizeof(double) * (2 * (size_t)M + MM + cov_part_doubles(g, M))) != hipSuccess) {
+        (void)hipStreamSynchronize(s);
+        return fail(BOSS_E_ALLOC, "device allocation failed");
+    }
+    double *dmu = dev, *dvar = dev + M, *dcov = dev + 2 * (size_t)M, *part = dcov + MM;
+    rc = predict_enqueue(g, &cd, nullptr, dmu, dvar, false, nullptr, nullptr, true);   // V in the slab scratch, Csc scaled
+    if (rc) {
+        (void)hipStreamSynchronize(s);
+        (void)hipFree(dev);
+        return rc;
+    }
+    cov_enqueue(g, M, COV_FORM_VALUE, (const double*)c->csc.p, nullptr, nullptr, cd.Mp, part, dcov, nullptr);
+    (void)hipMemcpyAsync(mu, dmu, sizeof(double) * M, hipMemcpyDeviceToHost, s);
+    (void)hipMemcpyAsync(cov, dcov, sizeof(double) * MM, hipMemcpyDeviceToHost, s);
+    hipError_t e = hipStreamSynchronize(s);
+    hipError_t e2 = hipGetLastError();
+    (void)hipFree(dev);
+    if (e != hipSuccess) return fail(BOSS_E_NO_DEVICE, hipGetErrorString(e));
+    if (e2 != hipSuccess) return fail(BOSS_E_NO_DEVICE, hipGetErrorString(e2));
+    return BOSS_OK;
+}
+
+extern "C" int boss_ngp_predict_cov(boss_gp_t* g, int M, const double* Xs, const double* lam_Xs, const double* amp_Xs,
+                                    const double* mean_Xs, double* mu, double* cov, long* bad_index) {
+    if (!g || !Xs || !lam_Xs || !amp_Xs || !mu || !cov) return fail(BOSS_E_INVALID, "NULL argument");
+    if (!g->gibbs) return fail(BOSS_E_INVALID, "handle was not created by boss_ngp_create");
+    if (M < 1) return fail(BOSS_E_INVALID, "M must be >= 1");
+    if (M > COV_MAX_M) return fail(BOSS_E_INVALID, "M above the covariance limit of 32768 candidates");
+    if (bad_index) *bad_index = -1;
+    if (!g->fitted) return fail(BOSS_E_NOT_FITTED, "handle has no valid factorisation");
+    NgpCand pk;
+    int rc = ngp_pack(g, M, Xs, lam_Xs, amp_Xs, pk);
+    if (rc) return rc;
+    Ctx* c = g->ctx;
+    HIPCHK(hipSetDevice(c->device));
+    std::lock_guard<std::mutex> lk(c->mtx);                 // the V slabs live in the shared scratch
+    hipStream_t s = c->stream;
+    boss_cand cd;
+    double *clam, *camp;
+    rc = ngp_upload(c, g->d, M, pk, cd, clam, camp);
+    if (rc) return rc;
+    double* dev = nullptr;   // mu | var | mean | bad | cov | partials
+    const size_t MM = (size_t)M * M;
+    if (dev_malloc((void**)&dev, sizeof(double) * (3 * (size_t)M + 2 + MM + cov_part_doubles(g, M))) != hipSuccess) {
+        (void)hipStreamSynchronize(s);
+        return fail(BOSS_E_ALLOC, "device allocation failed");
+    }
+    double *dmu = dev, *dvar = dev + M, *dmean = dev + 2 * (size_t)M;
+    unsigned long long* dbad = (unsigned long long*)(dev + 3 * (size_t)M);
+    double *dcov = dev + 3 * (size_t)M + 2, *part = dcov + MM;
+    if (mean_Xs) (void)hipMemcpyAsync(dmean, mean_Xs, sizeof(double) * M, hipMemcpyHostToDevice, s);
+    (void)hipMemsetAsync(dbad, 0xff, sizeof(unsigned long long), s);
+    rc = predict_enqueue(g, &cd, mean_Xs ? dmean : nullptr, dmu, dvar, false, clam, camp, true);   // V in the slab scratch
+    if (rc) {
+        (void)hipStreamSynchronize(s);
+        (void)hipFree(dev);
+        return rc;
+    }
+    cov_enqueue(g, M, COV_FORM_GIBBS, (const double*)cd.Craw, clam, camp, cd.Mp, part, dcov, dbad);
+    unsigned long long bad = 0;
+    (void)hipMemcpyAsync(mu, dmu, sizeof(double) * M, hipMemcpyDeviceToHost, s);
+    (void)hipMemcpyAsync(cov, dcov, sizeof(double) * MM, hipMemcpyDeviceToHost, s);
+    (void)hipMemcpyAsync(&bad, dbad, sizeof bad, hipMemcpyDeviceToHost, s);
+    hipError_t e = hipStreamSynchronize(s);
+    hipError_t e2 = hipGetLastError();
+    (void)hipFree(dev);
+    if (e != hipSuccess) return fail(BOSS_E_NO_DEVICE, hipGetErrorString(e));
+    if (e2 != hipSuccess) return fail(BOSS_E_NO_DEVICE, hipGetErrorString(e2));
+    if (bad != ~0ULL) {
+        if (bad_index) *bad_index = (long)bad;
+        char msg[160];
+        std::snprintf(msg, sizeof msg, "The posterior GP predicted variance %g but only values above -1e-08 are tolerated. (DomainError)",
+                      cov[bad * (size_t)M + bad]);
         return fail(BOSS_E_NEG_VAR, msg);
     }
     return BOSS_OK;

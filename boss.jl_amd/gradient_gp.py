@@ -4,8 +4,9 @@
 Every evaluated point contributes its value and its gradient, so n points give an n(1+x_dim) system per output:
   model_posterior_slice / data_loglike   -> boss_ggp_create + boss_ggp_update (augmented Gram, Cholesky, α-solve, logpdf)
   mean / var / mean_and_var              -> boss_gp_predict on the augmented factor
-The acquisition maximizers (HipBatchAM, …) take these posteriors unchanged; the entry points that assume
-value-only observations (append, gradients w.r.t. candidates, covariance) are not available for this model.
+  mean_and_cov / cov                     -> boss_ggp_predict_cov
+The acquisition maximizers (HipBatchAM, …) take these posteriors unchanged; append has its own entry point
+(boss_ggp_append).
 """
 from __future__ import annotations
 
@@ -71,15 +72,19 @@ def join_gradient_slices(ps: Sequence[HipGradientGPParams]) -> HipGradientGPPara
 
 
 class HipGradientGPPosteriorSlice(HipGaussianProcessPosteriorSlice):
-    """GradientGPPosteriorSlice (gradient_gp.jl:57-64): μ = k*·α, σ² = max(0, k(x,x) − ‖L⁻¹k*‖²)  (:334-361)."""
+    """GradientGPPosteriorSlice (gradient_gp.jl:57-64): μ = k*·α, σ² = max(0, k(x,x) − ‖L⁻¹k*‖²)  (:334-361).
+    mean_and_var_grad is inherited: boss_gp_predict_grad takes these posteriors."""
 
     def _mean_s(self, X):
         return None                                             # the model's mean is not used (:334-337)
 
-    def _unavailable(self, *a, **k):
-        raise NotImplementedError("not defined for gradient-observation posteriors")
+    def mean_and_cov(self, X):
+        """cov(post::GradientGPPosteriorSlice, X) with its mean (:368-373, boss_ggp_predict_cov) -> (mu[M], Σ[M,M]): neither
+        jittered nor clipped."""
+        return self.gp.predict_value_cov(np.asarray(X, float))
 
-    mean_and_cov = cov = _unavailable                        # (mean_and_var_grad: inherited — boss_gp_predict_grad takes these posteriors)
+    def cov(self, X):
+        return self.mean_and_cov(X)[1]
 
     def append(self, x, y, dy) -> float:
         """augment_dataset! (src/types/problem.jl:191-198) on the fitted slice: new points with values and gradients, hyper-parameters

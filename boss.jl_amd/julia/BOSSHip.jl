@@ -80,7 +80,9 @@ Base.unsafe_convert(::Type{Ptr{Cvoid}}, o::Handle) = o.h
 struct HipPosteriorSlice <: BOSS.ModelPosteriorSlice{HipGaussianProcess}
     h::Handle
     mean                                                           # prior mean of this output: nothing, a Real or x -> Real
+    aug::Bool                                                      # a gradient-observation slice (boss_ggp_create)
 end
+HipPosteriorSlice(h::Handle, mean) = HipPosteriorSlice(h, mean, false)
 mean_vals(::Nothing, X) = C_NULL
 mean_vals(m::Real, X) = fill(Float64(m), size(X, 2))
 mean_vals(m::Function, X) = Float64[m(x) for x in eachcol(X)]
@@ -114,6 +116,8 @@ var(post::HipPosteriorSlice, x) = mean_and_var(post, x)[2]
 function BOSS.mean_and_cov(post::HipPosteriorSlice, X::AbstractMatrix{<:Real})
     Xs = Matrix{Float64}(X); M = size(Xs, 2)
     μ = Vector{Float64}(undef, M); Σ = Matrix{Float64}(undef, M, M); bad = Ref{Clong}(-1)
+    post.aug && (GC.@preserve post check(ccall((:boss_ggp_predict_cov, lib), Cint,   # gradient_gp.jl:368-373
+        (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}), post.h.h, M, Xs, μ, Σ)); return μ, Σ)
     GC.@preserve post check(ccall((:boss_gp_predict_cov, lib), Cint,
         (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Clong}),
         post.h.h, M, Xs, mean_vals(post.mean, Xs), μ, Σ, bad))
@@ -700,7 +704,7 @@ ggp_update(h, p::BOSS.GradientGaussianProcessParams, i::Int) = (lp = Ref{Cdouble
           h, Vector{Float64}(p.λ[:, i]), p.α[i], p.σ[i], p.σ_∂[i], 0, lp)); lp[])
 function model_posterior_slice(m::HipGradientGaussianProcess, p::BOSS.GradientGaussianProcessParams, data::BOSS.GradientData, i::Int)
     h = ggp_create(m, data, i); ggp_update(h, p, i)
-    return HipPosteriorSlice(Handle(h), nothing)  # mean / var / mean_and_var above apply (gradient_gp.jl:334-361)
+    return HipPosteriorSlice(Handle(h), nothing, true)  # mean / var / mean_and_var / mean_and_cov above apply (gradient_gp.jl:334-373)
 end
 function data_loglike(m::HipGradientGaussianProcess, data::BOSS.GradientData)
     h = Handle(ggp_create(m, data, 1))            # per-output likelihood of the sliced model (gradient_gp.jl:367-397)
@@ -775,6 +779,15 @@ function mean_and_var(p::HipNonstationaryPosterior, X::AbstractMatrix{<:Real})
         p.post.h.h, M, Xs, reduce(hcat, p.f_λ.(eachcol(Xr))), Float64.(p.f_α.(eachcol(Xr))), mean_vals(p.post.mean, Xs), μ, σ2, bad))
     return μ, σ2
 end
+function BOSS.mean_and_cov(p::HipNonstationaryPosterior, X::AbstractMatrix{<:Real})   # gaussian_process.jl:180-184, Gibbs kernel
+    Xs = Matrix{Float64}(X); Xr = rounded(Xs, p.discrete); M = size(Xs, 2)
+    μ = Vector{Float64}(undef, M); Σ = Matrix{Float64}(undef, M, M); bad = Ref{Clong}(-1)
+    check(ccall((:boss_ngp_predict_cov, lib), Cint,
+        (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Clong}),
+        p.post.h.h, M, Xs, reduce(hcat, p.f_λ.(eachcol(Xr))), Float64.(p.f_α.(eachcol(Xr))), mean_vals(p.post.mean, Xs), μ, Σ, bad))
+    return μ, Σ
+end
+BOSS.cov(p::HipNonstationaryPosterior, X::AbstractMatrix{<:Real}) = BOSS.mean_and_cov(p, X)[2]
 # ---------------------------------------------------------------- moments with gradients, moments-only acquisition
 "mean_and_var(post, X) with their analytic gradients w.r.t. the columns of X: (μ, σ², ∂μ/∂x (d×M), ∂σ²/∂x (d×M))."
 function mean_and_var_grad(post::HipPosteriorSlice, X::AbstractMatrix{<:Real}; mean_grad = C_NULL)

@@ -194,6 +194,19 @@ class HipNonstationaryPosteriorSlice:
         ms = None if self.mean_fn is None else np.array([float(self.mean_fn(X[:, j])) for j in range(M)])
         return self.gp.predict_grad(X, _cols(self.f_lam, Xr).T, _cols(self.f_amp, Xr).reshape(-1), Dl, Da, ms, mean_grad)
 
+    def mean_and_cov(self, X):
+        """mean_and_cov(post, X::Matrix) (gaussian_process.jl:180-184) over the Gibbs kernel -> (mu[M], Σ[M,M]) with the diagonal
+        through _clip_var (boss_ngp_predict_cov); the latent models are evaluated at the rounded candidates, as in mean_and_var."""
+        X = np.asarray(X, float)
+        if X.ndim == 1:
+            X = X[:, None]
+        Xr = self._round(X)
+        ms = None if self.mean_fn is None else np.array([float(self.mean_fn(X[:, j])) for j in range(X.shape[1])])
+        return self.gp.predict_cov(X, _cols(self.f_lam, Xr).T, _cols(self.f_amp, Xr).reshape(-1), ms)
+
+    def cov(self, X):
+        return self.mean_and_cov(X)[1]
+
     def mean(self, x):
         return self.mean_and_var(x)[0]
 

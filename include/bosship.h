@@ -149,7 +149,7 @@ int boss_gp_get_factor(const boss_gp_t* gp, double* L_out, double* z_out);
  * the unclipped expression) and boss_gp_free work on it; boss_ggp_loglike_grad and boss_ggp_append are its own forms of the
  * likelihood gradient and of augment_dataset!; the entry points that assume value-only observations (boss_gp_update,
  * boss_gp_set_y, boss_gp_append, boss_gp_reserve, boss_gp_predict_cov, boss_gp_loglike_grad, boss_track_create) return
- * BOSS_E_INVALID.
+ * BOSS_E_INVALID; the posterior covariance of these handles is boss_ggp_predict_cov.
  * Limits: d <= 16, n(1+d) <= 46080. */
 int boss_ggp_create(int device, int kernel, int d, int n, const double* X, const double* y, const double* dY,
                     boss_gp_t** out);
@@ -180,8 +180,8 @@ int boss_ggp_append(boss_gp_t* gp, int n_new, const double* X_new, const double*
  * boss_ngp_update factorises and returns logpdf(FiniteGP, y); boss_ngp_predict is mean_and_var with _clip_var
  * (k(x*,x*) = a(x*)^2, +1e-18 jitter as for the plain model).  boss_gp_sync, boss_gp_set_y, boss_gp_get_factor,
  * boss_gp_free, boss_acq_ei_moments (EI on the predicted moments), boss_ngp_predict_grad and boss_acq_ei_grad_moments (their
- * gradients w.r.t. the candidates) work with these handles; the other
- * boss_gp_* / boss_acq_* / boss_track_* entry points return BOSS_E_INVALID for them. */
+ * gradients w.r.t. the candidates) work with these handles, boss_ngp_predict_cov is their mean_and_cov; the other
+ * boss_gp_* / boss_acq_* / boss_track_* entry points (boss_gp_predict_cov included) return BOSS_E_INVALID for them. */
 int boss_ngp_create(int device, int d, int N, const double* X, const double* y, const unsigned char* discrete,
                     boss_gp_t** out);
 int boss_ngp_update(boss_gp_t* gp, const double* lam_X, const double* amp_X, const double* noise_X,
@@ -279,6 +279,21 @@ int boss_gp_predict_grad(boss_gp_t* gp, int M, const double* Xs, const double* m
  * of the plugin is served from the device-resident factor. */
 int boss_gp_predict_cov(boss_gp_t* gp, int M, const double* Xs, const double* mean_Xs,
                         double* mu, double* cov, long* bad_index);
+
+/* mean_and_cov of a gradient-observation posterior (boss_ggp_create handles).
+ * Replaces: cov(post::GradientGPPosteriorSlice, X) (gradient_gp.jl:368-373) with its mean:
+ *   Sigma_ij = (a+1e-8)^2 k(|(x_i - x_j) / (l+1e-8)|) - v_i'v_j,  v = L^-1 k*(x) (value-to-(values; gradients) cross-covariance),
+ *   mu = k*' alpha.  No jitter, no clipping (the reference's cov does neither; its var clips to max(0, .)).
+ * Sigma is M×M column-major, exactly symmetric (Sigma[i,j] and Sigma[j,i] are the same double).  1 <= M <= 32768.
+ * Other handle kinds: BOSS_E_INVALID. */
+int boss_ggp_predict_cov(boss_gp_t* gp, int M, const double* Xs, double* mu, double* cov);
+/* mean_and_cov of a nonstationary posterior (boss_ngp_create handles), gaussian_process.jl:163-167,180-184 over the Gibbs kernel:
+ *   Sigma = K**_Gibbs - V'V + 1e-18 I, diagonal through _clip_var (values from -1e-8 up to 0 become 0; below: BOSS_E_NEG_VAR,
+ *   first such index in bad_index).  lam_Xs d×M, amp_Xs M are l(x*), a(x*) at the (rounded) candidates as for boss_ngp_predict,
+ *   mean_Xs M the prior mean at the candidates or NULL; mu = m(x*) + K*'a.  Sigma M×M column-major, exactly symmetric.
+ *   1 <= M <= 32768.  Other handle kinds: BOSS_E_INVALID. */
+int boss_ngp_predict_cov(boss_gp_t* gp, int M, const double* Xs, const double* lam_Xs, const double* amp_Xs,
+                         const double* mean_Xs, double* mu, double* cov, long* bad_index);
 
 /* resident candidates (one upload, many acquisition passes / many posteriors) */
 int boss_cand_create(int device, int d, int M, const double* Xs, boss_cand_t** out);
