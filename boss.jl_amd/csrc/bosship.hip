@@ -134,6 +134,14 @@ struct Ctx {
     hipEvent_t llg_join[LLG_BANKS - 1] = {nullptr, nullptr, nullptr};
     //   // lg*: log-likelihood gradient (LinvT, K⁻¹, partials)   // craw: raw candidates of one-shot calls
     void* pinned = nullptr;   // small host-pinned result area
+    // work tables of the deferred trailing update under the chain (BOSS_CHAIN_TRAIL=4), one per block-column count: planned and
+    // uploaded by the first factorisation of that size (trail_table, host_factor.inc)
+    struct TrailTab {
+        TrailWork* dev = nullptr;
+        std::vector<TrailWork> host;
+        std::vector<int> off;                   // off[k] = first entry of step k; off[nblk-1] = end
+    };
+    TrailTab trail[65];
     std::mutex mtx;
 };
 
@@ -191,6 +199,8 @@ static void ctx_destroy(Ctx* c) {
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     if (c->sig_panel && !c->sig_panel_host) (void)hipFree(c->sig_panel);   // (watch mode: the detached watcher thread keeps reading the block — it stays)
     if (c->few_done) (void)hipFree(c->few_done);
+    for (auto& t : c->trail)
+        if (t.dev) (void)hipFree(t.dev);
     if (c->slab_cache) (void)hipFree(c->slab_cache);
     if (c->hostblk_cache) (void)hipHostFree(c->hostblk_cache);
     if (c->ev_up) (void)hipEventDestroy(c->ev_up);
@@ -693,6 +703,31 @@ extern "C" int boss_debug_colupd_decode(int G, int k, int m, int ncols, int jfir
         R0[t] = w.R0;
         C0[t] = w.C0;
         crit[t] = w.crit;
+    }
+    return BOSS_OK;
+}
+
+// Host-side copy of the deferred trailing-update plan (BOSS_CHAIN_TRAIL=4, trail_plan in host_factor.inc) for nblk block columns,
+// `panels` panels per far batch and at most `lag` panels left for the near pass: off[k] (nblk entries) = first entry of step k, off[nblk-1] = their number; items (5 ints each, up
+// to cap entries, may be null to ask for the count): R0, C0, first panel, panel count, critical.  No device work:
+// tests/test_trail_plan.py replays the table.
+extern "C" int boss_debug_trail_plan(int nblk, int panels, int lag, int* n_items, int* off, int* items, int cap) {
+    if (nblk < 2 || nblk > 64 || panels < 1 || panels > 8 || lag < 1 || lag > 8 || !n_items || !off) return fail(BOSS_E_INVALID, "bad argument");
+    std::vector<TrailWork> plan;
+    std::vector<int> o;
+    trail_plan(nblk, panels, lag, plan, o);
+    *n_items = (int)plan.size();
+    for (int k = 0; k < nblk; ++k) off[k] = o[k];
+    if (!items) return BOSS_OK;
+    if (cap < (int)plan.size()) return fail(BOSS_E_INVALID, "cap too small");
+    for (size_t t = 0; t < plan.size(); ++t) {
+        const TrailWork& w = plan[t];
+        int* it = items + 5 * t;
+        it[0] = w.R0;
+        it[1] = w.C0;
+        it[2] = w.k0;
+        it[3] = w.npc & 255;
+        it[4] = w.npc >> 8;
     }
     return BOSS_OK;
 }

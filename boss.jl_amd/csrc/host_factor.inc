@@ -92,6 +92,8 @@ struct ChainPlan {
     bool on = false;
     unsigned long long cbase = 0, critbase = 0;
     unsigned long long up_want = 0;                          // sig[SIGW_UP] when every resident workgroup of this factorisation has started
+    const TrailWork* tab = nullptr;                          // BOSS_CHAIN_TRAIL=4: the size's work table on the device (null: per-step launches)
+    const int* tab_off = nullptr;                            // ... and where each step's entries start
 };
 // Time budget of every wait inside the factorisation's kernels (PollTimer, potrf.hpp), in ticks of the 100 MHz device clock:
 // ≈ 20× what an update of this size takes (a chain step of ≈ 45 µs per block column plus the trailing updates at 30 TFLOP/s), at
@@ -128,15 +130,128 @@ static bool chain_applies(const Ctx* c, int Np, int batch, bool gates) {
            c->stream == c->own_stream && virtual_devices() == 0 && !g_chain_off[c->device & 63].load(std::memory_order_relaxed);
 }
 // Trailing update under the chain (BOSS_CHAIN_TRAIL, see potrf_enqueue): 0 = one main-stream launch per step, 1 = main-stream pairs,
-// 2 = the two-stream gated schedule (the only one that uses the side stream while the chain runs)
+// 2 = the two-stream gated schedule (the only one that uses the side stream while the chain runs), 4 = deferred (trail_plan).
+// Measured on MI355X (ms per update, p50, mode 0 / 1 / 4 with its default P, Q): N = 1024: 0.253 / 0.268 / 0.251 (P = 1; 0.259 with
+// P = 2), 2048: 0.490–0.495 / 0.512 / 0.479, 4096: 1.102–1.107 / — / 1.067–1.073, 8192: 5.04 / 4.68 / 4.44 — the deferred schedule
+// from 16 block columns on, the plain per-step update below.
 static int chain_trail_mode(int nblk) {
     static const int env = getenv("BOSS_CHAIN_TRAIL") ? atoi(getenv("BOSS_CHAIN_TRAIL")) : -1;
-    return env >= 0 ? env : (nblk <= 44 ? 0 : 1);
+    return env >= 0 ? env : (nblk < 16 ? 0 : 4);
+}
+// Panels per far batch of the deferred schedule (BOSS_TRAIL_PANELS, 1 … 8), and how many a unit may still lack when it becomes
+// near work (BOSS_TRAIL_LAG, 1 … 8).  Defaults by size (measured, N = 4096: P, Q = 2, 1: 1.067–1.073 ms; 3, 1: 1.085; 2, 2: 1.090;
+// 4, 2: 1.130; 1, 1: 1.135; 8, 3: 1.370.  N = 8192: 4, 3: 4.44; 4, 2: 4.47; 3, 1: 4.53; 2, 1: 4.57): short batches where the chain
+// period bounds every step, longer ones where the trailing work does.
+static int trail_panels(int nblk) {
+    static const int v = getenv("BOSS_TRAIL_PANELS") ? atoi(getenv("BOSS_TRAIL_PANELS")) : 0;
+    return v > 0 ? std::min(8, v) : (nblk <= 44 ? 2 : 4);
+}
+static int trail_lag(int nblk) {
+    static const int v = getenv("BOSS_TRAIL_LAG") ? atoi(getenv("BOSS_TRAIL_LAG")) : 0;
+    return v > 0 ? std::min(8, v) : (nblk <= 44 ? 1 : 3);
+}
+// Deferred trailing update under the chain (BOSS_CHAIN_TRAIL=4): the work of every step as a table of 32×128 strips, each with the
+// run of panels it receives in one pass (TrailWork, potrf_colupd_tab_kernel).  Units: tile (i, j) of block column j = 1 … nblk-1
+// (j <= i < nblk) and the δ^T strip of column j (i = nblk).  Tile (j, j) receives panels 0 … j-2 here and panel j-1 from the chain
+// kernel, so it must be complete by the end of step j-2; every other unit receives panels 0 … j-1 and must be complete by the end of
+// step j-1, before the panel solve of step j reads it.  Step k:
+//   near   what the chain and the next panel solve need — tiles (k+2, k+1), (k+2, k+2) first (the eight critical strips, counted
+//          into sig[CRIT] as before), then the rest of column k+1 and its δ^T strip — receive every panel they still lack;
+//   ahead  tiles (k+3, k+2), (k+3, k+3), critical one step later, are brought up to panel k, so that their critical pass is K = 128;
+//   far    the other units of columns >= k+2 receive batches of P pending panels (K = 128·P: C is read and written once per P
+//          panels instead of once per panel), least slack first, until the step holds its share of what is left: the remaining
+//          work (cost model: P panels of one strip = P + C0 units) spread evenly over the remaining steps.  A unit's slack counts
+//          the far steps it has left against the batches it still needs to reach its near step lacking at most Q panels; at no
+//          slack it goes out whatever the share (with fewer than P panels if that is all it lacks).  Steps 0 … P-2 have no
+//          complete batch yet and carry little far work; the middle steps catch up.
+// Panels are applied in ascending order, every (unit, panel) pair exactly once, and the table depends on nblk and P only, so each
+// strip's accumulation order is fixed (tests/test_trail_plan.py replays it).
+static void trail_plan(int nblk, int P, int Q, std::vector<TrailWork>& out, std::vector<int>& off) {
+    constexpr double C0 = 0.7;                               // a strip's C traffic and start-up, in panels (K = 128 strip: 46 µs for 2080 of
+                                                             // them at k = 0 against 27.7 µs of MFMA work)
+    out.clear();
+    off.assign(std::max(nblk, 1), 0);
+    if (nblk < 2) return;
+    std::vector<int> have((size_t)(nblk + 1) * (nblk + 1), 0);   // have[j*(nblk+1)+i]: panels 0 … have-1 applied to unit (i, j)
+    auto H = [&](int i, int j) -> int& { return have[(size_t)j * (nblk + 1) + i]; };
+    auto target = [](int i, int j) { return i == j ? j - 1 : j; };
+    auto strips = [&](int i) { return i == nblk ? 1 : 4; };
+    double cost = 0.0;
+    auto emit = [&](int i, int j, int n, bool crit) {
+        int& h = H(i, j);
+        for (int s = 0; s < strips(i); ++s) out.push_back(TrailWork{i * BLK + 32 * s, j * BLK, h, n | (crit ? 256 : 0)});
+        h += n;
+        cost += strips(i) * (n + C0);
+    };
+    for (int k = 0; k + 1 < nblk; ++k) {
+        off[k] = (int)out.size();
+        double left = 0.0;                                   // what this and the later steps still have to do
+        for (int j = k + 1; j < nblk; ++j)
+            for (int i = j; i <= nblk; ++i) {
+                const int n = target(i, j) - H(i, j);
+                if (n > 0) left += strips(i) * (n + C0 * ((n + P - 1) / P));
+            }
+        const double share = left / (nblk - 1 - k);
+        cost = 0.0;
+        if (k + 2 < nblk) {
+            emit(k + 2, k + 1, k + 1 - H(k + 2, k + 1), true);
+            emit(k + 2, k + 2, k + 1 - H(k + 2, k + 2), true);
+        }
+        for (int i = (k + 2 < nblk ? k + 3 : k + 2); i <= nblk; ++i) emit(i, k + 1, k + 1 - H(i, k + 1), false);
+        if (k + 3 < nblk) {
+            emit(k + 3, k + 2, k + 1 - H(k + 3, k + 2), false);
+            emit(k + 3, k + 3, k + 1 - H(k + 3, k + 3), false);
+        }
+        // far candidates by slack: the steps left before the unit becomes near work, less the batches it still needs so that it
+        // then lacks at most Q panels (the near pass of a late step has few strips: its longest strip is its duration)
+        struct Cand {
+            int slack, j, i, n;
+        };
+        std::vector<Cand> cand;
+        for (int j = k + 2; j < nblk; ++j)
+            for (int i = j; i <= nblk; ++i) {
+                if ((i == k + 2 && j == k + 2) || (i == k + 3 && j <= k + 3)) continue;   // near / ahead above
+                const int b = k + 1 - H(i, j);                                          // pending panels
+                const int steps = (i == j ? j - 2 : j - 1) - k;                         // far steps left, this one included
+                const int slack = steps - std::max(0, (b + steps - Q + P - 1) / P);
+                if (b >= P || (b > 0 && slack <= 0)) cand.push_back(Cand{slack, j, i, std::min(b, P)});
+            }
+        std::stable_sort(cand.begin(), cand.end(), [](const Cand& x, const Cand& y) { return x.slack < y.slack; });
+        for (const Cand& w : cand) {
+            if (w.slack > 0 && cost >= share) break;          // what has no slack left goes out whatever the step's share
+            emit(w.i, w.j, w.n, false);
+        }
+    }
+    off[nblk - 1] = (int)out.size();
+}
+// The size's table on the device, planned and uploaded (behind the main stream's earlier work) on first use; null if it cannot be
+// allocated — the update then takes the per-step launches of mode 0
+static const TrailWork* trail_table(Ctx* c, int nblk, const int** off) {
+    if (nblk < 3 || nblk > 64) return nullptr;
+    Ctx::TrailTab& t = c->trail[nblk];
+    if (!t.dev) {
+        trail_plan(nblk, trail_panels(nblk), trail_lag(nblk), t.host, t.off);
+        const size_t bytes = t.host.size() * sizeof(TrailWork);
+        if (hipMalloc((void**)&t.dev, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            t.dev = nullptr;
+            return nullptr;
+        }
+        if (hipMemcpyAsync(t.dev, t.host.data(), bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) {
+            (void)hipGetLastError();
+            (void)hipFree(t.dev);
+            t.dev = nullptr;
+            return nullptr;
+        }
+    }
+    *off = t.off.data();
+    return t.dev;
 }
 static ChainPlan chain_begin(Ctx* c, double* A, int ld, int Np, double* inv16, int* info) {
     ChainPlan p;
     if (!chain_applies(c, Np, 1, true)) return p;
     const int nblk = Np / BLK;
+    if (chain_trail_mode(nblk) == 4) p.tab = trail_table(c, nblk, &p.tab_off);   // (before the resident kernels: the upload is a first-use copy)
     p.on = true;
     p.cbase = c->chain_seq;
     c->chain_seq += 8ull * nblk + 16;
@@ -437,8 +552,12 @@ static void potrf_enqueue(Ctx* c, double* A, int ld, int Np, int batch, size_t b
             const bool poll = last_rest >= 0 && last_rest == tail_join && bulk_pub != 0;   // the paired phase's last bulk update: its end is published
             if (last_rest >= 0 && !poll) (void)hipStreamWaitEvent(s, c->ev_rest[last_rest], 0);
             last_rest = -1;
-            hipLaunchKernelGGL(potrf_colupd_kernel, dim3(2 * m * (m + 1) + m, 1, batch), dim3(256), 0, s, A, ld, bstride, k,
-                               m, m, 0, 1, poll ? c->sig_panel + bulk_pub_word : (unsigned long long*)nullptr, bulk_pub, info, chain ? 1 : 0, -1, critw, budget);
+            if (chain_inline && plan->tab) {                 // deferred schedule: the step's entries of the work table
+                const int* off = plan->tab_off;
+                hipLaunchKernelGGL(potrf_colupd_tab_kernel, dim3(off[k + 1] - off[k]), dim3(256), 0, s, A, ld, plan->tab + off[k], k, critw);
+            } else
+                hipLaunchKernelGGL(potrf_colupd_kernel, dim3(2 * m * (m + 1) + m, 1, batch), dim3(256), 0, s, A, ld, bstride, k,
+                                   m, m, 0, 1, poll ? c->sig_panel + bulk_pub_word : (unsigned long long*)nullptr, bulk_pub, info, chain ? 1 : 0, -1, critw, budget);
             BOSS_STAMP(2000 + k);
             if (step_hook && chain_inline) (*step_hook)(k);
             continue;

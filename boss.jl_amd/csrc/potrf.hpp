@@ -1425,6 +1425,34 @@ __global__ __launch_bounds__(256, 2) void potrf_colupd_kernel(double* __restrict
     else syrk_tile<RhsG>(A, ld, k, w.R0, w.C0);
 }
 
+// One workgroup of the deferred trailing update (BOSS_CHAIN_TRAIL=4): the 32×128 strip at (R0, C0) receives the panels
+// k0 .. k0+npan-1 in ONE pass, C -= [P_k0 … P_k0+npan-1][…]^T with K = 128·npan.  The host plans the table once per size
+// (trail_plan, host_factor.inc); crit marks the eight critical strips of the step, which come first in its list.
+struct TrailWork {
+    int R0, C0, k0, npc;                                      // npc = npan | crit << 8
+};
+// One launch per step k, grid = the step's entries of the table.  Same GEMM as potrf_colupd_kernel (exact ring tail: K/4 is a
+// multiple of the ring depth for every panel count), so a strip's MFMA sequence is the same whichever passes its panels are grouped
+// into: the factor is bit-identical to that of the per-step schedule.
+__global__ __launch_bounds__(256, 2) void potrf_colupd_tab_kernel(double* __restrict__ A, int ld, const TrailWork* __restrict__ tab, int k,
+                                                                  unsigned long long* critw) {
+#ifdef BOSS_CHAIN_TRACE
+    if (threadIdx.x == 0) atomicMin(&g_cutrace[(k & 63) * 4 + 0], (unsigned long long)__builtin_amdgcn_s_memrealtime());
+    struct TraceEnd { int k; __device__ ~TraceEnd() { if (threadIdx.x == 0) atomicMax(&g_cutrace[(k & 63) * 4 + 1], (unsigned long long)__builtin_amdgcn_s_memrealtime()); } } trace_end_{k};
+#endif
+    __builtin_amdgcn_s_setprio(3);
+    const TrailWork w = tab[blockIdx.x];
+    const int K = (w.npc & 255) * BLK;
+    if (w.npc >> 8) {
+        syrk_tile<RhsG, true>(A, ld, w.k0, w.R0, w.C0, K);
+        drain_stores();
+        __syncthreads();
+        if (threadIdx.x == 0) __hip_atomic_fetch_add(as_global(critw), 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return;
+    }
+    syrk_tile<RhsG>(A, ld, w.k0, w.R0, w.C0, K);
+}
+
 // Block-row variant for boss_gp_append: behind panel k update ONLY block row kb (4 strips of
 // 32×128 per column block k+1..kb, the last one being the diagonal block of the rebuilt rows) and
 // the δ^T entries of block column kb:  C_{kb,c} -= W_k L_ck^T ,  δ^T_kb -= z_k W_k^T.
