@@ -1061,3 +1061,28 @@ def prof_get(device: int, kernel_class: str):
     n = C.c_long(0)
     _check(load_library().boss_prof_get(device, kernel_class.encode(), C.byref(ms), C.byref(n)))
     return ms.value, n.value
+
+
+def _update_path(g: GP):
+    """(chained, trail_mode, fell_back) of the handle's last completed update (boss_debug_update_path; tests): whether it ran
+    under the resident panel chain, the trailing schedule it used there (4: the deferred schedule's work table; -1: no chain),
+    and whether it was repeated on a simpler schedule."""
+    lib = load_library()
+    fn = lib.boss_debug_update_path
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    ch, tm, fb = C.c_int(0), C.c_int(0), C.c_int(0)
+    _check(fn(g._h, C.byref(ch), C.byref(tm), C.byref(fb)))
+    return ch.value, tm.value, fb.value
+
+
+def _fallbacks(device: int = 0):
+    """(updates repeated on a simpler schedule so far in this process, whether the resident chain is off on `device`)
+    (boss_debug_fallbacks; tests)."""
+    lib = load_library()
+    fn = lib.boss_debug_fallbacks
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_int, C.POINTER(C.c_long), C.POINTER(C.c_int)]
+    n, off = C.c_long(0), C.c_int(0)
+    _check(fn(device, C.byref(n), C.byref(off)))
+    return n.value, off.value

@@ -499,6 +499,7 @@ struct boss_gp {
     bool gated = false;                        // the pending update was enqueued with gate kernels
     bool chained = false;                      // ... and under the resident panel chain (chain.hpp)
     bool fell_back = false;                    // gp_finish repeated the pending update on a simpler schedule
+    int trail_used = -1;                       // trailing schedule the last factorisation ran under the chain (boss_debug_update_path), -1: no chain
     double* host_res = nullptr;                // pinned: scal[2], info
     double* host_res_dev = nullptr;            // the same memory through its device address (written by small_fit_kernel / potrf_logdet_kernel)
     bool par_in_args = false;                  // this update's hyper-parameters travel in the first kernel's arguments
@@ -729,6 +730,17 @@ extern "C" int boss_debug_trail_plan(int nblk, int panels, int lag, int* n_items
         it[3] = w.npc & 255;
         it[4] = w.npc >> 8;
     }
+    return BOSS_OK;
+}
+
+// What the handle's last completed update did (tests/test_gpu_factor_schedules.py): whether it ran under the resident chain, the
+// trailing schedule it used there (0, 1, 2, or 4 when the deferred schedule's work table was in place; -1 without the chain), and
+// whether gp_finish repeated it on a simpler schedule.  No device work.
+extern "C" int boss_debug_update_path(const boss_gp* g, int* chained, int* trail_mode, int* fell_back) {
+    if (!g || !chained || !trail_mode || !fell_back) return fail(BOSS_E_INVALID, "bad argument");
+    *chained = g->chained ? 1 : 0;
+    *trail_mode = g->chained ? g->trail_used : -1;
+    *fell_back = g->fell_back ? 1 : 0;
     return BOSS_OK;
 }
 

@@ -303,7 +303,8 @@ __device__ __forceinline__ void follow_strip(double* __restrict__ A, int ld, int
     auto ival = [&](int jb, int s) { return ld_sc1(inv16k + jb * 256 + (4 * s + (lane >> 4)) * 16 + (lane & 15)); };
     bool dead = false;                                           // a wait gave up: finish without waiting (the update is marked failed)
     // CRIT: the resident strips do not wait for the chain's panel word before they fetch the inverse of diagonal tile jb — they poll
-    // the DATA: inv16 is filled with an all-ones pattern before the factorisation (factor_enqueue), no computed value has it, and
+    // the DATA: inv16 is filled with an all-ones pattern before the factorisation (factor_enqueue), no stored value has it (a NaN
+    // goes out as the canonical quiet NaN, inv16_entry in potrf.hpp — the all-ones word is a NaN whose payload arithmetic keeps), and
     // an 8-byte word is stored whole, so a lane that sees four real values has the final ones.  One round trip instead of two on
     // the path from the chain's last panel to the next diagonal block; the row tiles of the panel (they overwrite live matrix
     // entries: no pattern possible) are still taken behind the word.

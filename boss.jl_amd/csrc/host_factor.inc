@@ -1050,6 +1050,8 @@ static int factor_enqueue(boss_gp* g, RiderReq* rider) {
     // patterns); likelihood-only loops (fitters) never pay for them, a first prediction builds them itself
     g->gated = c->sig_panel != nullptr;                      // this update may contain gate kernels (gp_finish: fallback on their timeout)
     g->chained = plan.on;                                    // ... and ran under the resident chain
+    const int trail = chain_trail_mode(g->nblk);             // (mode 4 without its work table runs the per-step launches of mode 0)
+    g->trail_used = !plan.on ? -1 : trail == 4 ? (plan.tab ? 4 : 0) : (trail == 1 || trail == 2) ? trail : 0;
     // (with a rider the side stream is busy with the candidates' substitution, which needs no block inverses: a later prediction
     // builds them itself)
     const bool eager = g->dinv_used && !c->prof_on && !rider;
@@ -1131,6 +1133,8 @@ static int gp_update_enqueue(boss_gp* g, const double* lengthscale, double ampli
                            (const double*)g->y, (const double*)g->mean, g->A, g->inv16, g->invlam, g->scal, g->info, g->host_res_dev,
                            ++g->res_seq);
         g->res_polled = true;
+        g->chained = false;
+        g->trail_used = -1;
         if (g->dinv_used) dinv_eager(g);
         g->dinv_used = false;
     } else {

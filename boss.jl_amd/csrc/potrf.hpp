@@ -256,6 +256,13 @@ constexpr int DIAG_TILES = 36;
 constexpr int DIAG_STAGE = 2 * 256 + 2;                // doubles: unscaled E' and S' of the current panel (lane-private layout) + a flag word
 constexpr int DIAG_LDS_BYTES = (DIAG_TILES * 256 + DIAG_STAGE) * 8;
 __device__ __forceinline__ int dtile(int i, int j) { return (i * (i + 1) / 2 + j) * 256; }   // LDS offset of lower tile (i, j)
+// An entry of inv16 as stored: any NaN becomes the canonical quiet NaN.  The resident strips take the all-ones bit pattern for "not
+// written yet" (follow_strip, chain.hpp), and a NaN in the data can reach this store with that very pattern (NaN arithmetic keeps
+// the payload of a NaN operand): one integer compare and select per value (bit operations, which no NaN-payload folding touches).
+__device__ __forceinline__ double inv16_entry(double v) {
+    const long long b = __double_as_longlong(v);
+    return (b & 0x7fffffffffffffffll) > 0x7ff0000000000000ll ? __longlong_as_double(0x7ff8000000000000ll) : v;
+}
 
 // nsub: number of leading 16-column panels that hold observations (8 = the whole block); the panels behind them are
 // identity padding and are neither factored nor touched.
@@ -393,10 +400,10 @@ __device__ __forceinline__ void diag_block_factor(double* __restrict__ smem, dou
                 const int c = q + 4 * i;
                 if constexpr (PUB) {
                     if (r16 >= c) st_sc1(At + (size_t)c * ld + r16, Sv[i] * rs);
-                    st_sc1(inv16 + jb * 256 + r16 * 16 + c, Ev[i] * rs);
+                    st_sc1(inv16 + jb * 256 + r16 * 16 + c, inv16_entry(Ev[i] * rs));
                 } else {
                     if (r16 >= c) At[(size_t)c * ld + r16] = Sv[i] * rs;
-                    inv16[jb * 256 + r16 * 16 + c] = Ev[i] * rs;        // inv(L16)(c, r16) = E(r16, c), stored at r16*16 + c
+                    inv16[jb * 256 + r16 * 16 + c] = inv16_entry(Ev[i] * rs);   // inv(L16)(c, r16) = E(r16, c), stored at r16*16 + c
                 }
                 if constexpr (KEEP) {
                     D[dtile(jb, jb) + oel[i]] = (r16 >= c) ? Sv[i] * rs : 0.0;

@@ -687,7 +687,46 @@ def _kernel_and_derivs(kernel: int, lam: np.ndarray, amp2: float, xi: np.ndarray
 def augmented_kernel_matrix(kernel: int, X, lengthscale, amplitude: float, noise_std: float, grad_noise_std: float):
     """gradient_gp.jl:175-210 `_build_augmented_kernel`: the n(1+d) square matrix over the observation
     ordering [f(x_1..n), ∂f/∂x_1(x_1..n), …, ∂f/∂x_d(x_1..n)], noise σ² on the function block's diagonal
-    and σ_∂² on the gradient blocks' (+1e-8 on every parameter, :128-131,:200-204)."""
+    and σ_∂² on the gradient blocks' (+1e-8 on every parameter, :128-131,:200-204).
+    All pairs at once, with the per-pair arithmetic of `_kernel_and_derivs` (same operations in the same order, the
+    sums over the d coordinates along a contiguous last axis as in the per-pair vector sums): bit-identical to the
+    pair loop `_augmented_kernel_matrix_pairs` (tests/test_oracle_crosscheck.py), fast enough for several thousand rows."""
+    kernel = KERNEL_NAMES.get(kernel, kernel) if isinstance(kernel, str) else kernel
+    X = np.asarray(X, dtype=np.float64)
+    d, n = X.shape
+    lam = np.asarray(lengthscale, dtype=np.float64) + MIN_PARAM_VALUE
+    amp2 = (float(amplitude) + MIN_PARAM_VALUE) ** 2
+    N = n * (1 + d)
+    P = np.ascontiguousarray(X.T)                                       # n × d: point i's coordinates contiguous
+    U = P[:, None, :] - P[None, :, :]                                   # U[i, j] = xi − xj
+    Kv = amp2 * kappa(kernel, np.sqrt(np.sum((U / lam) ** 2, axis=-1)))
+    # _isapprox(xi, xj): ‖xi − xj‖ <= rtol · max(‖xi‖, ‖xj‖)
+    nrm = np.sqrt(np.einsum("ik,ik->i", P, P))
+    near = np.sqrt(np.sum(U * U, axis=-1)) <= _ISAPPROX_RTOL * np.maximum(nrm[:, None], nrm[None, :])
+    if near.any():
+        U = np.where(near[:, :, None], P[:, None, :] - (P[None, :, :] + MIN_PARAM_VALUE), U)
+    r = np.sqrt(np.sum((U / lam) ** 2, axis=-1))
+    h = kappa_prime_over_r(kernel, r)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        g = kappa_second(kernel, r)
+    S = U / lam ** 2
+    dxi = (amp2 * h)[:, :, None] * S                                    # n × n × d
+    d2 = -amp2 * (h[:, :, None, None] * np.diag(1.0 / lam ** 2) + g[:, :, None, None] * (S[:, :, :, None] * S[:, :, None, :]))
+    K = np.zeros((N, N))
+    K[:n, :n] = Kv
+    for l in range(d):
+        K[:n, n + l * n:n + (l + 1) * n] = -dxi[:, :, l]
+        K[n + l * n:n + (l + 1) * n, :n] = dxi[:, :, l]
+        for m in range(d):
+            K[n + l * n:n + (l + 1) * n, n + m * n:n + (m + 1) * n] = d2[:, :, l, m]
+    K[np.arange(n), np.arange(n)] += (float(noise_std) + MIN_PARAM_VALUE) ** 2
+    K[np.arange(n, N), np.arange(n, N)] += (float(grad_noise_std) + MIN_PARAM_VALUE) ** 2
+    return np.triu(K) + np.triu(K, 1).T
+
+
+def _augmented_kernel_matrix_pairs(kernel: int, X, lengthscale, amplitude: float, noise_std: float, grad_noise_std: float):
+    """`augmented_kernel_matrix` one pair at a time through `_kernel_and_derivs` (the literal transcription of the
+    reference's double loop; the pin of the vectorised form)."""
     kernel = KERNEL_NAMES.get(kernel, kernel) if isinstance(kernel, str) else kernel
     X = np.asarray(X, dtype=np.float64)
     d, n = X.shape

@@ -368,3 +368,24 @@ def test_chain_schedules_apply_every_panel_once_in_order():
                 for r in list(range(4 * j, 4 * nblk)) + [4 * nblk]:
                     assert applied.get((r, j)) == list(range(j)), (mode, nblk, r, j, applied.get((r, j)))
             assert all(j >= 1 and r >= 4 * j for (r, j) in applied)
+
+
+def test_update_path_report_validates_its_arguments():
+    """boss_debug_update_path (what a handle's last update did: chain, trailing schedule, fallback; the GPU tests of the factor
+    schedules assert it on every update) is exported, and a NULL handle or a NULL output is BOSS_E_INVALID — no device needed."""
+    import ctypes as C
+    from boss_jl_amd import api
+    lib = api.load_library()
+    assert hasattr(lib, "boss_debug_update_path") and hasattr(lib, "boss_debug_fallbacks")
+    fn = lib.boss_debug_update_path
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    a, b, c = C.c_int(7), C.c_int(7), C.c_int(7)
+    assert fn(None, C.byref(a), C.byref(b), C.byref(c)) == api.BOSS_E_INVALID
+    assert (a.value, b.value, c.value) == (7, 7, 7)
+    fake = C.create_string_buffer(4096)                       # (never dereferenced: the outputs are checked first)
+    for outs in ((None, C.byref(b), C.byref(c)), (C.byref(a), None, C.byref(c)), (C.byref(a), C.byref(b), None)):
+        assert fn(C.cast(fake, C.c_void_p), *outs) == api.BOSS_E_INVALID
+    assert "bad argument" in lib.boss_last_error().decode()
+    n, off = api._fallbacks(0)                               # (host counters only)
+    assert n >= 0 and off in (0, 1)

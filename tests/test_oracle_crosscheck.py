@@ -423,3 +423,20 @@ def test_nonstationary_likelihood_gradient_matches_finite_differences(disc):
         assert abs(fd(amp, i, "amp") - da[i]) <= 1e-6 * (1 + abs(da[i]))
         assert abs(fd(noi, i, "noi") - dn[i]) <= 1e-6 * (1 + abs(dn[i]))
         assert abs(fd(m, i, "m") - dm[i]) <= 1e-6 * (1 + abs(dm[i]))
+
+
+@pytest.mark.parametrize("kernel", ["matern32", "matern52", "sqexp"])
+@pytest.mark.parametrize("d,n,dup", [(1, 5, False), (3, 40, True), (8, 33, True), (8, 60, False), (16, 20, True)])
+def test_vectorised_augmented_matrix_is_the_pair_loop_bit_for_bit(kernel, d, n, dup):
+    """augmented_kernel_matrix (all pairs at once: the GPU tests at several thousand augmented rows) against the literal
+    per-pair transcription of the reference's loop, bit for bit — coincident and nearly coincident points included (the
+    entries the reference evaluates at x_j + 1e-8)."""
+    rng = np.random.default_rng(d * n)
+    X = rng.uniform(0, 1, (d, n))
+    if dup:
+        X[:, 1] = X[:, 0]
+        X[:, 3] = X[:, 2] + 1e-12
+    lam = np.linspace(0.3, 0.6, d)
+    a = O.augmented_kernel_matrix(kernel, X, lam, 1.2, 0.05, 0.1)
+    b = O._augmented_kernel_matrix_pairs(kernel, X, lam, 1.2, 0.05, 0.1)
+    assert a.shape == b.shape and np.array_equal(a.view(np.int64), b.view(np.int64))
