@@ -27,9 +27,62 @@ extern "C" int boss_cand_create(int device, int d, int M, const double* Xs, boss
     return BOSS_OK;
 }
 
-// One-shot entry points (predict / predict_cov / predict_grad / acq_ei_grad) upload their candidates into a
-// grow-only per-device workspace instead of allocating: hipMalloc/hipFree synchronise the device and cost
-// a few hundred microseconds per call.  Caller holds the context lock.
+// One-shot entry points (predict / predict_cov / predict_grad / acq_ei_grad) share one staging and one finish:
+//  - candidates go into a grow-only per-device workspace instead of an allocation (hipMalloc/hipFree synchronise the device and
+//    cost a few hundred microseconds per call): temp_cand, or ngp_pack + ngp_upload for the nonstationary calls;
+//  - the outputs lie first and together in the c->pred workspace, inputs (prior means) behind them, and finish() copies them back;
+//  - an error that follows enqueued work synchronises the stream before the call returns (drain), and the call frees what it
+//    allocated: the next call reuses the workspaces right away.
+// Caller holds the context lock.
+static int drain(Ctx* c, int rc) {
+    (void)hipStreamSynchronize(c->stream);
+    return rc;
+}
+
+// the error _clip_var raises (gaussian_process.jl:165,182): bad is the first offending candidate, v its variance
+static int neg_var_error(long* bad_index, unsigned long long bad, double v) {
+    if (bad_index) *bad_index = (long)bad;
+    char msg[160];
+    std::snprintf(msg, sizeof msg, "The posterior GP predicted variance %g but only values above -1e-08 are tolerated. (DomainError)", v);
+    return fail(BOSS_E_NEG_VAR, msg);
+}
+
+struct DownCopy {
+    void* host;
+    const void* dev;
+    size_t bytes;
+};
+// Copy the outputs back, synchronise, report a failed launch.  Outputs that lie together on the device and fit the pinned area come
+// back in ONE copy (five copies into the caller's pageable arrays cost ≈60 µs of a ≈100 µs call), others one copy each.
+static int finish(Ctx* c, std::initializer_list<DownCopy> outs) {
+    hipStream_t s = c->stream;
+    const char* next = (const char*)outs.begin()->dev;
+    size_t total = 0;
+    bool together = true;
+    for (const DownCopy& o : outs) {
+        together = together && o.dev == next;
+        next = (const char*)o.dev + o.bytes;
+        total += o.bytes;
+    }
+    hipError_t e;
+    if (together && total <= PINNED_DOWN_BYTES) {
+        char* stage = (char*)c->pinned + PINNED_DOWN_OFF;
+        (void)hipMemcpyAsync(stage, outs.begin()->dev, total, hipMemcpyDeviceToHost, s);
+        e = hipStreamSynchronize(s);
+        for (const DownCopy& o : outs) {
+            std::memcpy(o.host, stage, o.bytes);
+            stage += o.bytes;
+        }
+    } else {
+        for (const DownCopy& o : outs) (void)hipMemcpyAsync(o.host, o.dev, o.bytes, hipMemcpyDeviceToHost, s);
+        e = hipStreamSynchronize(s);
+    }
+    const hipError_t e2 = hipGetLastError();                 // (read either way: it also clears the error)
+    if (e == hipSuccess) e = e2;
+    if (e != hipSuccess) return fail(BOSS_E_NO_DEVICE, hipGetErrorString(e));
+    return BOSS_OK;
+}
+
 static int temp_cand(Ctx* c, int d, int M, const double* Xs, boss_cand* cd) {
     cd->ctx = c;
     cd->d = d;
@@ -83,6 +136,13 @@ __global__ void scale_cand_kernel(const double* __restrict__ Craw, double* __res
 static int invgemm_max_tiles() {
     static const int v = getenv("BOSS_INVGEMM_MAX_TILES") ? atoi(getenv("BOSS_INVGEMM_MAX_TILES")) : 128;
     return v;
+}
+
+// width of the V slabs predict_enqueue leaves (and the covariances read): 64 candidates per workgroup once that still fills the
+// machine (BOSS_FORCE_BN64=1: tests); the gradient pass (adjoint substitution) runs on 32-candidate slabs
+static int slab_bn(int M, bool for_grad) {
+    static const bool force64 = getenv("BOSS_FORCE_BN64") && atoi(getenv("BOSS_FORCE_BN64"));
+    return !for_grad && (M >= 64 * 256 || force64) ? 64 : 32;
 }
 
 
@@ -167,10 +227,7 @@ static int predict_enqueue(boss_gp* g, const boss_cand* cd, const double* mean_s
     }
     g->dinv_used = true;
     const int Mp = cd->Mp;
-    // 64 candidates per workgroup once that still fills the machine (BOSS_FORCE_BN64=1: tests)
-    static const bool force64 = getenv("BOSS_FORCE_BN64") && atoi(getenv("BOSS_FORCE_BN64"));
-    // the gradient pass (adjoint substitution) runs on 32-candidate slabs
-    const int BN = for_grad ? 32 : ((cd->M >= 64 * 256 || force64) ? 64 : 32);
+    const int BN = slab_bn(cd->M, for_grad);
     const int tiles = (cd->M + BN - 1) / BN;
     int rc = ws_reserve(c->csc, sizeof(double) * (size_t)g->d * Mp);
     if (rc) return rc;
@@ -565,60 +622,27 @@ extern "C" int boss_gp_predict(boss_gp_t* g, int M, const double* Xs, const doub
             }
             long long bad;
             std::memcpy(&bad, &hres[8], sizeof bad);
-            if (bad >= 0) {
-                if (bad_index) *bad_index = (long)bad;
-                char msg[160];
-                std::snprintf(msg, sizeof msg, "The posterior GP predicted variance %g but only values above -1e-08 are tolerated. (DomainError)", var[bad]);
-                return fail(BOSS_E_NEG_VAR, msg);
-            }
-            return BOSS_OK;
+            return bad >= 0 ? neg_var_error(bad_index, (unsigned long long)bad, var[bad]) : BOSS_OK;
         }
     }
-    boss_cand cand_tmp;
-    boss_cand* cd = &cand_tmp;
-    int rc = temp_cand(c, g->d, M, Xs, cd);
-    if (rc) return rc;
+    boss_cand cd;
+    int rc = temp_cand(c, g->d, M, Xs, &cd);
+    if (rc) return drain(c, rc);
     rc = ws_reserve(c->pred, sizeof(double) * (3 * (size_t)M + 2));   // mu | var | bad | mean
-    if (rc) return rc;
+    if (rc) return drain(c, rc);
     double* dev = (double*)c->pred.p;
     double *dmu = dev, *dvar = dev + M, *dmean = dev + 2 * (size_t)M + 1;
     unsigned long long* dbad = (unsigned long long*)(dev + 2 * (size_t)M);
     hipStream_t s = c->stream;
-    auto cleanup = [&]() {
-        (void)hipStreamSynchronize(s);
-    };
     if (mean_Xs) (void)hipMemcpyAsync(dmean, mean_Xs, sizeof(double) * M, hipMemcpyHostToDevice, s);
     (void)hipMemsetAsync(dbad, 0xff, sizeof(unsigned long long), s);
-    rc = predict_enqueue(g, cd, mean_Xs ? dmean : nullptr, dmu, dvar);
-    if (rc) {
-        cleanup();
-        return rc;
-    }
+    rc = predict_enqueue(g, &cd, mean_Xs ? dmean : nullptr, dmu, dvar);
+    if (rc) return drain(c, rc);
     hipLaunchKernelGGL(clip_var_kernel, dim3((M + 255) / 256), dim3(256), 0, s, dvar, M, dbad);
     unsigned long long bad = 0;
-    const size_t down = sizeof(double) * (2 * (size_t)M + 1);
-    hipError_t e;
-    if (down <= PINNED_DOWN_BYTES) {                         // few candidates: one copy into pinned memory
-        double* stage = (double*)((char*)c->pinned + PINNED_DOWN_OFF);
-        (void)hipMemcpyAsync(stage, dev, down, hipMemcpyDeviceToHost, s);
-        e = hipStreamSynchronize(s);
-        std::memcpy(mu, stage, sizeof(double) * M);
-        std::memcpy(var, stage + M, sizeof(double) * M);
-        std::memcpy(&bad, stage + 2 * (size_t)M, sizeof bad);
-    } else {
-        (void)hipMemcpyAsync(mu, dmu, sizeof(double) * M, hipMemcpyDeviceToHost, s);
-        (void)hipMemcpyAsync(var, dvar, sizeof(double) * M, hipMemcpyDeviceToHost, s);
-        (void)hipMemcpyAsync(&bad, dbad, sizeof bad, hipMemcpyDeviceToHost, s);
-        e = hipStreamSynchronize(s);
-    }
-    if (e != hipSuccess) return fail(BOSS_E_NO_DEVICE, hipGetErrorString(e));
-    if (bad != ~0ULL) {
-        if (bad_index) *bad_index = (long)bad;
-        char msg[160];
-        std::snprintf(msg, sizeof msg, "The posterior GP predicted variance %g but only values above -1e-08 are tolerated. (DomainError)", var[bad]);
-        return fail(BOSS_E_NEG_VAR, msg);
-    }
-    return BOSS_OK;
+    rc = finish(c, {{mu, dmu, sizeof(double) * M}, {var, dvar, sizeof(double) * M}, {&bad, dbad, sizeof bad}});
+    if (rc) return rc;
+    return bad != ~0ULL ? neg_var_error(bad_index, bad, var[bad]) : BOSS_OK;
 }
 
 // mean_and_var of a NonstationaryGP posterior (GaussianProcessPosterior over the Gibbs kernel,
@@ -683,36 +707,21 @@ extern "C" int boss_ngp_predict(boss_gp_t* g, int M, const double* Xs, const dou
     boss_cand cd;
     double *clam, *camp;
     rc = ngp_upload(c, g->d, M, pk, cd, clam, camp);
-    if (rc) return rc;
-    rc = ws_reserve(c->pred, sizeof(double) * (3 * (size_t)M + 2));   // mu | var | mean | bad
-    if (rc) {
-        (void)hipStreamSynchronize(s);
-        return rc;
-    }
+    if (rc) return drain(c, rc);
+    rc = ws_reserve(c->pred, sizeof(double) * (3 * (size_t)M + 2));   // mu | var | bad | mean
+    if (rc) return drain(c, rc);
     double* dev = (double*)c->pred.p;
-    double *dmu = dev, *dvar = dev + M, *dmean = dev + 2 * (size_t)M;
-    unsigned long long* dbad = (unsigned long long*)(dev + 3 * (size_t)M);
+    double *dmu = dev, *dvar = dev + M, *dmean = dev + 2 * (size_t)M + 1;
+    unsigned long long* dbad = (unsigned long long*)(dev + 2 * (size_t)M);
     if (mean_Xs) (void)hipMemcpyAsync(dmean, mean_Xs, sizeof(double) * M, hipMemcpyHostToDevice, s);
     (void)hipMemsetAsync(dbad, 0xff, sizeof(unsigned long long), s);
     rc = predict_enqueue(g, &cd, mean_Xs ? dmean : nullptr, dmu, dvar, false, clam, camp);
-    if (rc) {
-        (void)hipStreamSynchronize(s);
-        return rc;
-    }
+    if (rc) return drain(c, rc);
     hipLaunchKernelGGL(clip_var_kernel, dim3((M + 255) / 256), dim3(256), 0, s, dvar, M, dbad);
     unsigned long long bad = 0;
-    (void)hipMemcpyAsync(mu, dmu, sizeof(double) * M, hipMemcpyDeviceToHost, s);
-    (void)hipMemcpyAsync(var, dvar, sizeof(double) * M, hipMemcpyDeviceToHost, s);
-    (void)hipMemcpyAsync(&bad, dbad, sizeof bad, hipMemcpyDeviceToHost, s);
-    hipError_t e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return fail(BOSS_E_NO_DEVICE, hipGetErrorString(e));
-    if (bad != ~0ULL) {
-        if (bad_index) *bad_index = (long)bad;
-        char msg[160];
-        std::snprintf(msg, sizeof msg, "The posterior GP predicted variance %g but only values above -1e-08 are tolerated. (DomainError)", var[bad]);
-        return fail(BOSS_E_NEG_VAR, msg);
-    }
-    return BOSS_OK;
+    rc = finish(c, {{mu, dmu, sizeof(double) * M}, {var, dvar, sizeof(double) * M}, {&bad, dbad, sizeof bad}});
+    if (rc) return rc;
+    return bad != ~0ULL ? neg_var_error(bad_index, bad, var[bad]) : BOSS_OK;
 }
 
 static int grad_enqueue(boss_gp* g, const boss_cand* cd, const double* mean_s_dev, const double* mean_grad_dev, double* mu,
@@ -733,61 +742,34 @@ extern "C" int boss_ngp_predict_grad(boss_gp_t* g, int M, const double* Xs, cons
     if (g->d > GIBBS_GRAD_MAX_D) return fail(BOSS_E_INVALID, "x_dim above 16 is not supported by the nonstationary gradient kernel");
     if (bad_index) *bad_index = -1;
     if (!g->fitted) return fail(BOSS_E_NOT_FITTED, "handle has no valid factorisation");
-    const int d = g->d, Mp = round_up(M, 64), nslot = 2 * (2 * d + 1);
-    std::vector<double> buf, lam((size_t)d * Mp, 1.0), amp(Mp, 1.0);
-    pack_points(buf, Xs, d, M, Mp, g->discrete.empty() ? nullptr : g->discrete.data());
-    for (int j = 0; j < M; ++j) {
-        for (int k = 0; k < d; ++k) {
-            const double v = lam_Xs[(size_t)j * d + k];
-            if (!(v > 0.0) || !std::isfinite(v)) return fail(BOSS_E_INVALID, "lengthscales must be finite and > 0");
-            lam[(size_t)k * Mp + j] = v;
-        }
-        if (!(amp_Xs[j] >= 0.0) || !std::isfinite(amp_Xs[j])) return fail(BOSS_E_INVALID, "amplitudes must be finite and >= 0");
-        amp[j] = amp_Xs[j];
-    }
+    NgpCand pk;
+    int rc = ngp_pack(g, M, Xs, lam_Xs, amp_Xs, pk);
+    if (rc) return rc;
     Ctx* c = g->ctx;
     HIPCHK(hipSetDevice(c->device));
     std::lock_guard<std::mutex> lk(c->mtx);
     hipStream_t s = c->stream;
-    int rc = ws_reserve(c->craw, sizeof(double) * ((size_t)2 * d * Mp + Mp));
-    if (rc) return rc;
     boss_cand cd;
-    cd.ctx = c;
-    cd.d = d;
-    cd.M = M;
-    cd.Mp = Mp;
-    cd.Craw = (double*)c->craw.p;
-    double* clam = cd.Craw + (size_t)d * Mp;
-    double* camp = clam + (size_t)d * Mp;
-    HIPCHK(hipMemcpyAsync(cd.Craw, buf.data(), sizeof(double) * d * Mp, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(clam, lam.data(), sizeof(double) * d * Mp, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(camp, amp.data(), sizeof(double) * Mp, hipMemcpyHostToDevice, s));
-    rc = ws_reserve(c->pred, sizeof(double) * (3 * (size_t)M + 2 + (size_t)nslot * Mp));   // mu | var | mean | bad | sums
-    if (rc) {
-        (void)hipStreamSynchronize(s);
-        return rc;
-    }
+    double *clam, *camp;
+    rc = ngp_upload(c, g->d, M, pk, cd, clam, camp);
+    if (rc) return drain(c, rc);
+    const int d = g->d, Mp = pk.Mp, nslot = 2 * (2 * d + 1);
+    const size_t nsums = (size_t)nslot * Mp;
+    rc = ws_reserve(c->pred, sizeof(double) * (3 * (size_t)M + 2 + nsums));   // mu | var | sums | bad | mean
+    if (rc) return drain(c, rc);
     double* dev = (double*)c->pred.p;
-    double *dmu_ = dev, *dvar_ = dev + M, *dmean = dev + 2 * (size_t)M;
-    unsigned long long* dbad = (unsigned long long*)(dev + 3 * (size_t)M);
-    double* dsums = dev + 3 * (size_t)M + 2;
+    double *dmu_ = dev, *dvar_ = dev + M, *dsums = dev + 2 * (size_t)M, *dmean = dsums + nsums + 1;
+    unsigned long long* dbad = (unsigned long long*)(dsums + nsums);
     if (mean_Xs) (void)hipMemcpyAsync(dmean, mean_Xs, sizeof(double) * M, hipMemcpyHostToDevice, s);
     (void)hipMemsetAsync(dbad, 0xff, sizeof(unsigned long long), s);
     rc = grad_enqueue(g, &cd, mean_Xs ? dmean : nullptr, nullptr, dmu_, dvar_, nullptr, nullptr, clam, camp, dsums);
-    if (rc) {
-        (void)hipStreamSynchronize(s);
-        return rc;
-    }
+    if (rc) return drain(c, rc);
     hipLaunchKernelGGL(clip_var_kernel, dim3((M + 255) / 256), dim3(256), 0, s, dvar_, M, dbad);
     unsigned long long bad = 0;
-    std::vector<double> sums((size_t)nslot * Mp);
-    (void)hipMemcpyAsync(mu, dmu_, sizeof(double) * M, hipMemcpyDeviceToHost, s);
-    (void)hipMemcpyAsync(var, dvar_, sizeof(double) * M, hipMemcpyDeviceToHost, s);
-    (void)hipMemcpyAsync(sums.data(), dsums, sizeof(double) * nslot * Mp, hipMemcpyDeviceToHost, s);
-    (void)hipMemcpyAsync(&bad, dbad, sizeof bad, hipMemcpyDeviceToHost, s);
-    hipError_t e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return fail(BOSS_E_NO_DEVICE, hipGetErrorString(e));
-    HIPCHK(hipGetLastError());
+    std::vector<double> sums(nsums);
+    rc = finish(c, {{mu, dmu_, sizeof(double) * M}, {var, dvar_, sizeof(double) * M}, {sums.data(), dsums, sizeof(double) * nsums},
+                    {&bad, dbad, sizeof bad}});
+    if (rc) return rc;
     const int ns1 = 2 * d + 1;
     for (int j = 0; j < M; ++j) {
         const double* Dl = dlam_Xs ? dlam_Xs + (size_t)j * d * d : nullptr;
@@ -809,13 +791,7 @@ extern "C" int boss_ngp_predict_grad(boss_gp_t* g, int M, const double* Xs, cons
             dvar[(size_t)j * d + m] = av - 2.0 * gw;
         }
     }
-    if (bad != ~0ULL) {
-        if (bad_index) *bad_index = (long)bad;
-        char msg[160];
-        std::snprintf(msg, sizeof msg, "The posterior GP predicted variance %g but only values above -1e-08 are tolerated. (DomainError)", var[bad]);
-        return fail(BOSS_E_NEG_VAR, msg);
-    }
-    return BOSS_OK;
+    return bad != ~0ULL ? neg_var_error(bad_index, bad, var[bad]) : BOSS_OK;
 }
 
 static int ei_params(Ctx* c, hipStream_t s, int P, const double* fit_coefs, const double* y_max, int has_best, double best,
@@ -965,63 +941,29 @@ extern "C" int boss_gp_predict_grad(boss_gp_t* g, int M, const double* Xs, const
     Ctx* c = g->ctx;
     HIPCHK(hipSetDevice(c->device));
     std::lock_guard<std::mutex> lk(c->mtx);
-    boss_cand cand_tmp;
-    boss_cand* cd = &cand_tmp;
-    int rc = temp_cand(c, g->d, M, Xs, cd);
-    if (rc) return rc;
+    boss_cand cd;
+    int rc = temp_cand(c, g->d, M, Xs, &cd);
+    if (rc) return drain(c, rc);
     const int d = g->d;
     const size_t dm = (size_t)d * M;
     rc = ws_reserve(c->pred, sizeof(double) * (3 * (size_t)M + 3 * dm + 2));   // mu | var | dmu | dvar | bad | mean | mean_grad
-    if (rc) return rc;
-    double* dev = (double*)c->pred.p;                        // (the outputs lie together: few candidates come back in ONE copy)
+    if (rc) return drain(c, rc);
+    double* dev = (double*)c->pred.p;
     double *dmu_ = dev, *dvar_ = dev + M, *dgm = dev + 2 * (size_t)M, *dgv = dgm + dm;
     unsigned long long* dbad = (unsigned long long*)(dgv + dm);
     double *dmean = dgv + dm + 1, *dmg = dmean + M;
     hipStream_t s = c->stream;
-    auto cleanup = [&]() {
-        (void)hipStreamSynchronize(s);
-    };
     if (mean_Xs) (void)hipMemcpyAsync(dmean, mean_Xs, sizeof(double) * M, hipMemcpyHostToDevice, s);
     if (mean_grad) (void)hipMemcpyAsync(dmg, mean_grad, sizeof(double) * dm, hipMemcpyHostToDevice, s);
     (void)hipMemsetAsync(dbad, 0xff, sizeof(unsigned long long), s);
-    rc = grad_enqueue(g, cd, mean_Xs ? dmean : nullptr, mean_grad ? dmg : nullptr, dmu_, dvar_, dgm, dgv);
-    if (rc) {
-        cleanup();
-        return rc;
-    }
+    rc = grad_enqueue(g, &cd, mean_Xs ? dmean : nullptr, mean_grad ? dmg : nullptr, dmu_, dvar_, dgm, dgv);
+    if (rc) return drain(c, rc);
     hipLaunchKernelGGL(clip_var_kernel, dim3((M + 255) / 256), dim3(256), 0, s, dvar_, M, dbad);
     unsigned long long bad = 0;
-    const size_t down = sizeof(double) * (2 * (size_t)M + 2 * dm + 1);
-    hipError_t e;
-    if (down <= PINNED_DOWN_BYTES) {
-        // few candidates: one copy into pinned memory (five copies into the caller's pageable arrays cost ≈60 µs of a ≈100 µs call)
-        double* stage = (double*)((char*)c->pinned + PINNED_DOWN_OFF);
-        (void)hipMemcpyAsync(stage, dev, down, hipMemcpyDeviceToHost, s);
-        e = hipStreamSynchronize(s);
-        std::memcpy(mu, stage, sizeof(double) * M);
-        std::memcpy(var, stage + M, sizeof(double) * M);
-        std::memcpy(dmu, stage + 2 * (size_t)M, sizeof(double) * dm);
-        std::memcpy(dvar, stage + 2 * (size_t)M + dm, sizeof(double) * dm);
-        std::memcpy(&bad, stage + 2 * (size_t)M + 2 * dm, sizeof bad);
-    } else {
-        (void)hipMemcpyAsync(mu, dmu_, sizeof(double) * M, hipMemcpyDeviceToHost, s);
-        (void)hipMemcpyAsync(var, dvar_, sizeof(double) * M, hipMemcpyDeviceToHost, s);
-        (void)hipMemcpyAsync(dmu, dgm, sizeof(double) * dm, hipMemcpyDeviceToHost, s);
-        (void)hipMemcpyAsync(dvar, dgv, sizeof(double) * dm, hipMemcpyDeviceToHost, s);
-        (void)hipMemcpyAsync(&bad, dbad, sizeof bad, hipMemcpyDeviceToHost, s);
-        e = hipStreamSynchronize(s);
-    }
-    hipError_t e2 = hipGetLastError();
-    cleanup();
-    if (e != hipSuccess) return fail(BOSS_E_NO_DEVICE, hipGetErrorString(e));
-    if (e2 != hipSuccess) return fail(BOSS_E_NO_DEVICE, hipGetErrorString(e2));
-    if (bad != ~0ULL) {
-        if (bad_index) *bad_index = (long)bad;
-        char msg[160];
-        std::snprintf(msg, sizeof msg, "The posterior GP predicted variance %g but only values above -1e-08 are tolerated. (DomainError)", var[bad]);
-        return fail(BOSS_E_NEG_VAR, msg);
-    }
-    return BOSS_OK;
+    rc = finish(c, {{mu, dmu_, sizeof(double) * M}, {var, dvar_, sizeof(double) * M}, {dmu, dgm, sizeof(double) * dm},
+                    {dvar, dgv, sizeof(double) * dm}, {&bad, dbad, sizeof bad}});
+    if (rc) return rc;
+    return bad != ~0ULL ? neg_var_error(bad_index, bad, var[bad]) : BOSS_OK;
 }
 
 // Acquisition value AND gradient w.r.t. the candidates for one hyper-parameter sample (MAP): the EI x feasibility
@@ -1041,16 +983,15 @@ extern "C" int boss_acq_ei_grad(int P, boss_gp_t* const* gps, int M, const doubl
     HIPCHK(hipSetDevice(c->device));
     std::lock_guard<std::mutex> lk(c->mtx);
     const int d = gps[0]->d;
-    boss_cand cand_tmp;
-    boss_cand* cd = &cand_tmp;
-    int rc = temp_cand(c, d, M, Xs, cd);
-    if (rc) return rc;
+    boss_cand cd;
+    int rc = temp_cand(c, d, M, Xs, &cd);
+    if (rc) return drain(c, rc);
     hipStream_t s = c->stream;
     const size_t dm = (size_t)d * M;
     // device scratch: mu[P][M] | var[P][M] | mean[P][M] | mean_grad[P][dM] | dmu[P][dM] | dvar[P][dM] | acq[M] | dacq[dM] | coefs[P] | ymax[P] | mask
     const size_t nd = (size_t)3 * P * M + (size_t)3 * P * dm + M + dm + 2 * P;
     rc = ws_reserve(c->pred, sizeof(double) * nd + M);
-    if (rc) return rc;
+    if (rc) return drain(c, rc);
     double* dev = (double*)c->pred.p;
     double* dmu = dev;
     double* dvar = dmu + (size_t)P * M;
@@ -1063,48 +1004,23 @@ extern "C" int boss_acq_ei_grad(int P, boss_gp_t* const* gps, int M, const doubl
     double* dcoef = ddacq + dm;
     double* dymax = dcoef + P;
     unsigned char* dmask = (unsigned char*)(dev + nd);
-    auto cleanup = [&]() {
-        (void)hipStreamSynchronize(s);
-    };
     EiPar par;
     rc = ei_params(c, s, P, fit_coefs, y_max, has_best, best, &par, dcoef, dymax);
-    if (rc) {
-        cleanup();
-        return rc;
-    }
+    if (rc) return drain(c, rc);
     if (mean_Xs) (void)hipMemcpyAsync(dmean, mean_Xs, sizeof(double) * P * M, hipMemcpyHostToDevice, s);
     if (mean_grad) (void)hipMemcpyAsync(dmg, mean_grad, sizeof(double) * P * dm, hipMemcpyHostToDevice, s);
     if (valid_mask) (void)hipMemcpyAsync(dmask, valid_mask, M, hipMemcpyHostToDevice, s);
     if (par.mode != 0) {
         for (int p = 0; p < P; ++p) {
-            rc = grad_enqueue(gps[p], cd, mean_Xs ? dmean + (size_t)p * M : nullptr, mean_grad ? dmg + (size_t)p * dm : nullptr,
+            rc = grad_enqueue(gps[p], &cd, mean_Xs ? dmean + (size_t)p * M : nullptr, mean_grad ? dmg + (size_t)p * dm : nullptr,
                               dmu + (size_t)p * M, dvar + (size_t)p * M, dgm + (size_t)p * dm, dgv + (size_t)p * dm);
-            if (rc) {
-                cleanup();
-                return rc;
-            }
+            if (rc) return drain(c, rc);
         }
     }
     hipLaunchKernelGGL(ei_grad_kernel, dim3((M + 127) / 128), dim3(128), 0, s, (const double*)dmu, (const double*)dvar,
                        (const double*)dgm, (const double*)dgv, M, d, par, (const double*)dcoef, (const double*)dymax,
                        valid_mask ? (const unsigned char*)dmask : nullptr, dacq, ddacq);
-    hipError_t e;
-    if (ddacq == dacq + M && sizeof(double) * (M + dm) <= PINNED_DOWN_BYTES) {
-        double* stage = (double*)((char*)c->pinned + PINNED_DOWN_OFF);          // one copy into pinned memory, then the caller's arrays
-        (void)hipMemcpyAsync(stage, dacq, sizeof(double) * (M + dm), hipMemcpyDeviceToHost, s);
-        e = hipStreamSynchronize(s);
-        std::memcpy(acq_out, stage, sizeof(double) * M);
-        std::memcpy(dacq_out, stage + M, sizeof(double) * dm);
-    } else {
-        (void)hipMemcpyAsync(acq_out, dacq, sizeof(double) * M, hipMemcpyDeviceToHost, s);
-        (void)hipMemcpyAsync(dacq_out, ddacq, sizeof(double) * dm, hipMemcpyDeviceToHost, s);
-        e = hipStreamSynchronize(s);
-    }
-    hipError_t e2 = hipGetLastError();
-    cleanup();
-    if (e != hipSuccess) return fail(BOSS_E_NO_DEVICE, hipGetErrorString(e));
-    if (e2 != hipSuccess) return fail(BOSS_E_NO_DEVICE, hipGetErrorString(e2));
-    return BOSS_OK;
+    return finish(c, {{acq_out, dacq, sizeof(double) * M}, {dacq_out, ddacq, sizeof(double) * dm}});
 }
 
 // The same chain rule from moments and moment gradients the caller already holds (nonstationary posteriors: boss_ngp_predict_grad per
@@ -1135,7 +1051,7 @@ extern "C" int boss_acq_ei_grad_moments(int device, int P, int M, int d, const d
     unsigned char* dmask = (unsigned char*)(dev + nd);
     EiPar par;
     rc = ei_params(c, s, P, fit_coefs, y_max, has_best, best, &par, dcoef, dymax);
-    if (rc) return rc;
+    if (rc) return drain(c, rc);
     (void)hipMemcpyAsync(d_mu, mu, sizeof(double) * P * M, hipMemcpyHostToDevice, s);
     (void)hipMemcpyAsync(d_var, var, sizeof(double) * P * M, hipMemcpyHostToDevice, s);
     (void)hipMemcpyAsync(d_gm, dmu, sizeof(double) * P * dm, hipMemcpyHostToDevice, s);
@@ -1144,75 +1060,13 @@ extern "C" int boss_acq_ei_grad_moments(int device, int P, int M, int d, const d
     hipLaunchKernelGGL(ei_grad_kernel, dim3((M + 127) / 128), dim3(128), 0, s, (const double*)d_mu, (const double*)d_var, (const double*)d_gm,
                        (const double*)d_gv, M, d, par, (const double*)dcoef, (const double*)dymax,
                        valid_mask ? (const unsigned char*)dmask : nullptr, dacq, ddacq);
-    (void)hipMemcpyAsync(acq_out, dacq, sizeof(double) * M, hipMemcpyDeviceToHost, s);
-    (void)hipMemcpyAsync(dacq_out, ddacq, sizeof(double) * dm, hipMemcpyDeviceToHost, s);
-    hipError_t e = hipStreamSynchronize(s);
-    hipError_t e2 = hipGetLastError();
-    if (e != hipSuccess) return fail(BOSS_E_NO_DEVICE, hipGetErrorString(e));
-    if (e2 != hipSuccess) return fail(BOSS_E_NO_DEVICE, hipGetErrorString(e2));
-    return BOSS_OK;
-}
-
-extern "C" int boss_gp_predict_cov(boss_gp_t* g, int M, const double* Xs, const double* mean_Xs, double* mu,
-                                   double* cov, long* bad_index) {
-    if (!g || !Xs || !mu || !cov) return fail(BOSS_E_INVALID, "NULL argument");
-    NOT_FOR_AUG(g);
-    if (M < 1) return fail(BOSS_E_INVALID, "M must be >= 1");
-    if (bad_index) *bad_index = -1;
-    if (!g->fitted) return fail(BOSS_E_NOT_FITTED, "handle has no valid factorisation");
-    Ctx* c = g->ctx;
-    HIPCHK(hipSetDevice(c->device));
-    std::lock_guard<std::mutex> lk(c->mtx);                 // the per-device scratch areas are shared
-    boss_cand_t* cd = nullptr;
-    int rc = boss_cand_create(c->device, g->d, M, Xs, &cd);
-    if (rc) return rc;
-    double* dev = nullptr;   // mu | var | mean | bad | cov
-    if (dev_malloc((void**)&dev, sizeof(double) * (3 * (size_t)M + 2 + (size_t)M * M)) != hipSuccess) {
-        boss_cand_free(cd);
-        return fail(BOSS_E_ALLOC, "device allocation failed");
-    }
-    double *dmu = dev, *dvar = dev + M, *dmean = dev + 2 * (size_t)M;
-    unsigned long long* dbad = (unsigned long long*)(dev + 3 * (size_t)M);
-    double* dcov = dev + 3 * (size_t)M + 2;
-    hipStream_t s = c->stream;
-    auto cleanup = [&]() {
-        (void)hipStreamSynchronize(s);
-        (void)hipFree(dev);
-        boss_cand_free(cd);
-    };
-    if (mean_Xs) (void)hipMemcpyAsync(dmean, mean_Xs, sizeof(double) * M, hipMemcpyHostToDevice, s);
-    (void)hipMemsetAsync(dbad, 0xff, sizeof(unsigned long long), s);
-    rc = predict_enqueue(g, cd, mean_Xs ? dmean : nullptr, dmu, dvar, false, nullptr, nullptr, true);   // leaves V in the slab scratch, Csc scaled
-    if (rc) {
-        cleanup();
-        return rc;
-    }
-    static const bool force64 = getenv("BOSS_FORCE_BN64") && atoi(getenv("BOSS_FORCE_BN64"));
-    const int BN = (M >= 64 * 256 || force64) ? 64 : 32;     // must mirror predict_enqueue's choice (V slab layout)
-    const int gb = (M + 15) / 16;
-    hipLaunchKernelGGL(predict_cov_kernel, dim3(gb, gb), dim3(256), 0, s, (const double*)c->vscratch.p, g->Np, BN,
-                       (const double*)c->csc.p, g->d, cd->Mp, M, g->kernel, g->amp2, dcov);
-    hipLaunchKernelGGL(clip_cov_diag_kernel, dim3((M + 255) / 256), dim3(256), 0, s, dcov, M, dbad);
-    unsigned long long bad = 0;
-    (void)hipMemcpyAsync(mu, dmu, sizeof(double) * M, hipMemcpyDeviceToHost, s);
-    (void)hipMemcpyAsync(cov, dcov, sizeof(double) * (size_t)M * M, hipMemcpyDeviceToHost, s);
-    (void)hipMemcpyAsync(&bad, dbad, sizeof bad, hipMemcpyDeviceToHost, s);
-    hipError_t e = hipStreamSynchronize(s);
-    cleanup();
-    if (e != hipSuccess) return fail(BOSS_E_NO_DEVICE, hipGetErrorString(e));
-    if (bad != ~0ULL) {
-        if (bad_index) *bad_index = (long)bad;
-        char msg[160];
-        std::snprintf(msg, sizeof msg, "The posterior GP predicted variance %g but only values above -1e-08 are tolerated. (DomainError)", cov[bad * (size_t)M + bad]);
-        return fail(BOSS_E_NEG_VAR, msg);
-    }
-    return BOSS_OK;
+    return finish(c, {{acq_out, dacq, sizeof(double) * M}, {dacq_out, ddacq, sizeof(double) * dm}});
 }
 
 // ------------------------------------------------------------------------------------------
-// mean_and_cov / cov of the gradient-observation and nonstationary posteriors: V = L⁻¹K* from predict_enqueue(need_v), then
-// VᵀV on the fp64 MFMA in 64×64 lower-triangle block pairs × chunks of the n range (cov_syrk_partial_kernel) and the fixed-order
-// sum with K** (cov_finish_kernel).  (The plain handles' boss_gp_predict_cov keeps its VALU predict_cov_kernel.)
+// mean_and_cov / cov: V = L⁻¹K* from predict_enqueue(need_v), then Σ = K** − VᵀV.  Gradient-observation and nonstationary
+// posteriors: VᵀV on the fp64 MFMA in 64×64 lower-triangle block pairs × chunks of the n range (cov_syrk_partial_kernel) and the
+// fixed-order sum with K** (cov_finish_kernel).  Plain posteriors: the VALU predict_cov_kernel + clip_cov_diag_kernel.
 // ------------------------------------------------------------------------------------------
 constexpr int COV_MAX_M = 32768;                // M×M doubles = 8 GiB on the device and on the host
 constexpr int COV_TARGET_WG = 512;              // (block pair, chunk) workgroups wanted: two per CU
@@ -1239,12 +1093,11 @@ static void cov_enqueue(boss_gp* g, int M, int form, const double* X, const doub
                         double* dcov, unsigned long long* dbad) {
     Ctx* c = g->ctx;
     hipStream_t s = c->stream;
-    static const bool force64 = getenv("BOSS_FORCE_BN64") && atoi(getenv("BOSS_FORCE_BN64"));
-    const int BN = (M >= 64 * 256 || force64) ? 64 : 32;     // must mirror predict_enqueue's choice (V slab layout)
     int P, C, rows;
     cov_plan(g->Np, M, P, C, rows);
     ProfScope ps(c, "cov");
-    hipLaunchKernelGGL(cov_syrk_partial_kernel, dim3(P, C), dim3(256), 0, s, (const double*)c->vscratch.p, g->Np, BN, M, rows, part);
+    hipLaunchKernelGGL(cov_syrk_partial_kernel, dim3(P, C), dim3(256), 0, s, (const double*)c->vscratch.p, g->Np, slab_bn(M, false), M,
+                       rows, part);
     if (form == COV_FORM_GIBBS)
         hipLaunchKernelGGL(cov_finish_kernel<COV_FORM_GIBBS>, dim3(P), dim3(256), 0, s, (const double*)part, C, X, Lam, Amp, g->d, ldx,
                            g->kernel, g->amp2, M, dcov, dbad);
@@ -1259,41 +1112,68 @@ static size_t cov_part_doubles(const boss_gp* g, int M) {
     return (size_t)C * P * COV_T * COV_T;
 }
 
+// The three covariance entry points behind their argument checks: candidates staged (pk: packed by ngp_pack, else Xs through
+// temp_cand), μ and V, Σ, copied back, the clipping error of Σ's diagonal (none for gradient observations: their Σ is not clipped).
+// Σ and the partial slabs are a per-call allocation: up to 8 GiB must not stay resident in a grow-only workspace.
+static int predict_cov(boss_gp* g, int M, const double* Xs, const NgpCand* pk, const double* mean_Xs, double* mu, double* cov,
+                       long* bad_index) {
+    Ctx* c = g->ctx;
+    HIPCHK(hipSetDevice(c->device));
+    std::lock_guard<std::mutex> lk(c->mtx);                 // the V slabs live in the shared scratch
+    hipStream_t s = c->stream;
+    boss_cand cd;
+    double *clam = nullptr, *camp = nullptr;
+    int rc = pk ? ngp_upload(c, g->d, M, *pk, cd, clam, camp) : temp_cand(c, g->d, M, Xs, &cd);
+    if (rc) return drain(c, rc);
+    const size_t MM = (size_t)M * M;
+    double* dev = nullptr;   // mu | cov | bad | var | mean | partials
+    if (dev_malloc((void**)&dev, sizeof(double) * (3 * (size_t)M + 2 + MM + (g->aug || g->gibbs ? cov_part_doubles(g, M) : 0))) != hipSuccess)
+        return drain(c, fail(BOSS_E_ALLOC, "device allocation failed"));
+    double *dmu = dev, *dcov = dev + M, *dvar = dcov + MM + 1, *dmean = dvar + M, *part = dmean + M;
+    unsigned long long* dbad = g->aug ? nullptr : (unsigned long long*)(dcov + MM);
+    if (mean_Xs) (void)hipMemcpyAsync(dmean, mean_Xs, sizeof(double) * M, hipMemcpyHostToDevice, s);
+    if (dbad) (void)hipMemsetAsync(dbad, 0xff, sizeof(unsigned long long), s);
+    rc = predict_enqueue(g, &cd, mean_Xs ? dmean : nullptr, dmu, dvar, false, clam, camp, true);   // V in the slab scratch, Csc scaled
+    if (rc) {
+        (void)drain(c, rc);
+        (void)hipFree(dev);
+        return rc;
+    }
+    if (g->gibbs) {
+        cov_enqueue(g, M, COV_FORM_GIBBS, (const double*)cd.Craw, clam, camp, cd.Mp, part, dcov, dbad);
+    } else if (g->aug) {
+        cov_enqueue(g, M, COV_FORM_VALUE, (const double*)c->csc.p, nullptr, nullptr, cd.Mp, part, dcov, nullptr);
+    } else {
+        const int gb = (M + 15) / 16;
+        hipLaunchKernelGGL(predict_cov_kernel, dim3(gb, gb), dim3(256), 0, s, (const double*)c->vscratch.p, g->Np, slab_bn(M, false),
+                           (const double*)c->csc.p, g->d, cd.Mp, M, g->kernel, g->amp2, dcov);
+        hipLaunchKernelGGL(clip_cov_diag_kernel, dim3((M + 255) / 256), dim3(256), 0, s, dcov, M, dbad);
+    }
+    unsigned long long bad = ~0ULL;
+    rc = dbad ? finish(c, {{mu, dmu, sizeof(double) * M}, {cov, dcov, sizeof(double) * MM}, {&bad, dbad, sizeof bad}})
+              : finish(c, {{mu, dmu, sizeof(double) * M}, {cov, dcov, sizeof(double) * MM}});
+    (void)hipFree(dev);
+    if (rc) return rc;
+    return bad != ~0ULL ? neg_var_error(bad_index, bad, cov[bad * (size_t)M + bad]) : BOSS_OK;
+}
+
+extern "C" int boss_gp_predict_cov(boss_gp_t* g, int M, const double* Xs, const double* mean_Xs, double* mu,
+                                   double* cov, long* bad_index) {
+    if (!g || !Xs || !mu || !cov) return fail(BOSS_E_INVALID, "NULL argument");
+    NOT_FOR_AUG(g);
+    if (M < 1) return fail(BOSS_E_INVALID, "M must be >= 1");
+    if (bad_index) *bad_index = -1;
+    if (!g->fitted) return fail(BOSS_E_NOT_FITTED, "handle has no valid factorisation");
+    return predict_cov(g, M, Xs, nullptr, mean_Xs, mu, cov, bad_index);
+}
+
 extern "C" int boss_ggp_predict_cov(boss_gp_t* g, int M, const double* Xs, double* mu, double* cov) {
     if (!g || !Xs || !mu || !cov) return fail(BOSS_E_INVALID, "NULL argument");
     if (!g->aug) return fail(BOSS_E_INVALID, "handle was not created by boss_ggp_create");
     if (M < 1) return fail(BOSS_E_INVALID, "M must be >= 1");
     if (M > COV_MAX_M) return fail(BOSS_E_INVALID, "M above the covariance limit of 32768 candidates");
     if (!g->fitted) return fail(BOSS_E_NOT_FITTED, "handle has no valid factorisation");
-    Ctx* c = g->ctx;
-    HIPCHK(hipSetDevice(c->device));
-    std::lock_guard<std::mutex> lk(c->mtx);                 // the V slabs live in the shared scratch
-    hipStream_t s = c->stream;
-    boss_cand cd;
-    int rc = temp_cand(c, g->d, M, Xs, &cd);
-    if (rc) return rc;
-    double* dev = nullptr;   // mu | var | cov | partials
-    const size_t MM = (size_t)M * M;
-    if (dev_malloc((void**)&dev, sizeof(double) * (2 * (size_t)M + MM + cov_part_doubles(g, M))) != hipSuccess) {
-        (void)hipStreamSynchronize(s);
-        return fail(BOSS_E_ALLOC, "device allocation failed");
-    }
-    double *dmu = dev, *dvar = dev + M, *dcov = dev + 2 * (size_t)M, *part = dcov + MM;
-    rc = predict_enqueue(g, &cd, nullptr, dmu, dvar, false, nullptr, nullptr, true);   // V in the slab scratch, Csc scaled
-    if (rc) {
-        (void)hipStreamSynchronize(s);
-        (void)hipFree(dev);
-        return rc;
-    }
-    cov_enqueue(g, M, COV_FORM_VALUE, (const double*)c->csc.p, nullptr, nullptr, cd.Mp, part, dcov, nullptr);
-    (void)hipMemcpyAsync(mu, dmu, sizeof(double) * M, hipMemcpyDeviceToHost, s);
-    (void)hipMemcpyAsync(cov, dcov, sizeof(double) * MM, hipMemcpyDeviceToHost, s);
-    hipError_t e = hipStreamSynchronize(s);
-    hipError_t e2 = hipGetLastError();
-    (void)hipFree(dev);
-    if (e != hipSuccess) return fail(BOSS_E_NO_DEVICE, hipGetErrorString(e));
-    if (e2 != hipSuccess) return fail(BOSS_E_NO_DEVICE, hipGetErrorString(e2));
-    return BOSS_OK;
+    return predict_cov(g, M, Xs, nullptr, nullptr, mu, cov, nullptr);
 }
 
 extern "C" int boss_ngp_predict_cov(boss_gp_t* g, int M, const double* Xs, const double* lam_Xs, const double* amp_Xs,
@@ -1307,47 +1187,5 @@ extern "C" int boss_ngp_predict_cov(boss_gp_t* g, int M, const double* Xs, const
     NgpCand pk;
     int rc = ngp_pack(g, M, Xs, lam_Xs, amp_Xs, pk);
     if (rc) return rc;
-    Ctx* c = g->ctx;
-    HIPCHK(hipSetDevice(c->device));
-    std::lock_guard<std::mutex> lk(c->mtx);                 // the V slabs live in the shared scratch
-    hipStream_t s = c->stream;
-    boss_cand cd;
-    double *clam, *camp;
-    rc = ngp_upload(c, g->d, M, pk, cd, clam, camp);
-    if (rc) return rc;
-    double* dev = nullptr;   // mu | var | mean | bad | cov | partials
-    const size_t MM = (size_t)M * M;
-    if (dev_malloc((void**)&dev, sizeof(double) * (3 * (size_t)M + 2 + MM + cov_part_doubles(g, M))) != hipSuccess) {
-        (void)hipStreamSynchronize(s);
-        return fail(BOSS_E_ALLOC, "device allocation failed");
-    }
-    double *dmu = dev, *dvar = dev + M, *dmean = dev + 2 * (size_t)M;
-    unsigned long long* dbad = (unsigned long long*)(dev + 3 * (size_t)M);
-    double *dcov = dev + 3 * (size_t)M + 2, *part = dcov + MM;
-    if (mean_Xs) (void)hipMemcpyAsync(dmean, mean_Xs, sizeof(double) * M, hipMemcpyHostToDevice, s);
-    (void)hipMemsetAsync(dbad, 0xff, sizeof(unsigned long long), s);
-    rc = predict_enqueue(g, &cd, mean_Xs ? dmean : nullptr, dmu, dvar, false, clam, camp, true);   // V in the slab scratch
-    if (rc) {
-        (void)hipStreamSynchronize(s);
-        (void)hipFree(dev);
-        return rc;
-    }
-    cov_enqueue(g, M, COV_FORM_GIBBS, (const double*)cd.Craw, clam, camp, cd.Mp, part, dcov, dbad);
-    unsigned long long bad = 0;
-    (void)hipMemcpyAsync(mu, dmu, sizeof(double) * M, hipMemcpyDeviceToHost, s);
-    (void)hipMemcpyAsync(cov, dcov, sizeof(double) * MM, hipMemcpyDeviceToHost, s);
-    (void)hipMemcpyAsync(&bad, dbad, sizeof bad, hipMemcpyDeviceToHost, s);
-    hipError_t e = hipStreamSynchronize(s);
-    hipError_t e2 = hipGetLastError();
-    (void)hipFree(dev);
-    if (e != hipSuccess) return fail(BOSS_E_NO_DEVICE, hipGetErrorString(e));
-    if (e2 != hipSuccess) return fail(BOSS_E_NO_DEVICE, hipGetErrorString(e2));
-    if (bad != ~0ULL) {
-        if (bad_index) *bad_index = (long)bad;
-        char msg[160];
-        std::snprintf(msg, sizeof msg, "The posterior GP predicted variance %g but only values above -1e-08 are tolerated. (DomainError)",
-                      cov[bad * (size_t)M + bad]);
-        return fail(BOSS_E_NEG_VAR, msg);
-    }
-    return BOSS_OK;
+    return predict_cov(g, M, Xs, &pk, mean_Xs, mu, cov, bad_index);
 }
