@@ -56,6 +56,10 @@ SIGNATURES = {
                                         C.c_int, _c_dp, _c_dp, _c_dp, _c_dp, C.POINTER(C.c_int)]),
     "boss_gp_loglike_grad_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _c_dp, _c_dp, _c_dp, C.c_int, _c_ucp,
                                              C.c_int, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, C.POINTER(C.c_int)]),
+    "boss_ggp_loglike_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _c_dp, _c_dp, _c_dp, C.c_int, _c_dp, _c_dp, _c_dp,
+                                         _c_dp, _c_dp, C.POINTER(C.c_int)]),
+    "boss_ngp_loglike_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, _c_dp, _c_dp, _c_ucp, C.c_int, _c_dp, _c_dp, _c_dp, _c_dp,
+                                         C.c_int, _c_dp, C.POINTER(C.c_int)]),
     "boss_gp_fit_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _c_dp, _c_dp, _c_dp, C.c_int, _c_ucp,
                                     C.c_int, _c_dp, _c_dp, _c_dp, C.POINTER(C.c_void_p), _c_dp, C.POINTER(C.c_int)]),
     "boss_gp_predict": (C.c_int, [C.c_void_p, C.c_int, _c_dp, _c_dp, _c_dp, _c_dp, C.POINTER(C.c_long)]),
@@ -729,6 +733,89 @@ def loglike_batch(X, y, kernel, lengthscales, amplitudes, noise_stds, mean_X=Non
     _check(load_library().boss_gp_loglike_batch(device, _kernel_id(kernel), d, N, _dp(X), _dp(y), _dp(m), stride,
                                                 _ucp(disc), S, _dp(lam), _dp(amp), _dp(sig), _dp(ll),
                                                 st.ctypes.data_as(C.POINTER(C.c_int))))
+    return ll, st
+
+
+def _ggp_batch_args(X, y, dY, lengthscales, amplitudes, noise_stds, grad_noise_stds):
+    """The arrays boss_ggp_loglike_batch reads, converted and checked (no device is touched): X d×n, y n, dY d×n, lengthscales d×S,
+    the other parameters S each — all float64, matrices column-major."""
+    X = _f64(X, 2)
+    d, n = X.shape
+    y = _f64(np.asarray(y).reshape(-1), 1)
+    dY = _f64(dY, 2)
+    if y.shape[0] != n or dY.shape != (d, n):
+        raise ValueError("y must have n entries and dY must be d×n")
+    lam = _f64(lengthscales, 2)
+    if lam.shape[0] != d:
+        raise BossError(BOSS_E_INVALID, "lengthscales must be d×S")
+    S = lam.shape[1]
+    amp, sig, sgd = (_f64(np.asarray(a).reshape(-1), 1) for a in (amplitudes, noise_stds, grad_noise_stds))
+    if amp.shape[0] != S or sig.shape[0] != S or sgd.shape[0] != S:
+        raise BossError(BOSS_E_INVALID, "amplitudes, noise_stds and grad_noise_stds must have one entry per column of lengthscales")
+    return X, y, dY, lam, amp, sig, sgd
+
+
+def ggp_loglike_batch(X, y, dY, kernel, lengthscales, amplitudes, noise_stds, grad_noise_stds, device: int = 0):
+    """S log marginal likelihoods of the gradient-observation model on one (X, y, dY) slice in one device call
+    (boss_ggp_loglike_batch); lengthscales is d×S.  Returns (ll[S], status[S]); ll = -Inf where the augmented matrix is not PD
+    or a parameter is negative."""
+    X, y, dY, lam, amp, sig, sgd = _ggp_batch_args(X, y, dY, lengthscales, amplitudes, noise_stds, grad_noise_stds)
+    d, n = X.shape
+    S = lam.shape[1]
+    ll = np.zeros(S)
+    st = np.zeros(S, dtype=np.int32)
+    _check(load_library().boss_ggp_loglike_batch(device, _kernel_id(kernel), d, n, _dp(X), _dp(y), _dp(dY), S, _dp(lam), _dp(amp),
+                                                 _dp(sig), _dp(sgd), _dp(ll), st.ctypes.data_as(C.POINTER(C.c_int))))
+    return ll, st
+
+
+def _ngp_batch_args(X, y, lam_X, amp_X, noise_X, mean_X=None, discrete=None):
+    """The arrays boss_ngp_loglike_batch reads, converted and checked (no device is touched): X d×N, y N, lam_X d×N×S, amp_X and
+    noise_X N×S (column s = set s), mean_X None, N values shared by the sets, or S×N (row s = set s).  Returns them with the
+    mean stride (0 or N) and the uint8 discrete flags."""
+    X = _f64(X, 2)
+    d, N = X.shape
+    y = _f64(np.asarray(y).reshape(-1), 1)
+    if y.shape[0] != N:
+        raise ValueError("y must have one entry per column of X")
+    lam = _f64(lam_X, 3)
+    if lam.shape[:2] != (d, N):
+        raise BossError(BOSS_E_INVALID, "lam_X must be d×N×S")
+    S = lam.shape[2]
+    amp = _f64(amp_X, 2)
+    noi = _f64(noise_X, 2)
+    if amp.shape != (N, S) or noi.shape != (N, S):
+        raise BossError(BOSS_E_INVALID, "amp_X and noise_X must be N×S")
+    stride = 0
+    m = None
+    if mean_X is not None:
+        m = np.asarray(mean_X, dtype=np.float64)
+        if m.ndim == 2:          # S×N, row s = mean of set s  → contiguous rows
+            if m.shape != (S, N):
+                raise BossError(BOSS_E_INVALID, "a per-set mean_X must be S×N")
+            m = np.ascontiguousarray(m)
+            stride = N
+        else:
+            m = np.ascontiguousarray(m.reshape(-1))
+            if m.shape[0] != N:
+                raise BossError(BOSS_E_INVALID, "a shared mean_X must have N entries")
+    disc = None if discrete is None else np.ascontiguousarray(np.asarray(discrete, dtype=bool).astype(np.uint8))
+    if disc is not None and disc.shape != (d,):
+        raise BossError(BOSS_E_INVALID, "discrete must have one flag per dimension")
+    return X, y, lam, amp, noi, m, stride, disc
+
+
+def ngp_loglike_batch(X, y, lam_X, amp_X, noise_X, mean_X=None, discrete=None, device: int = 0):
+    """S log marginal likelihoods of the nonstationary model on one (X, y) slice in one device call (boss_ngp_loglike_batch): the
+    latent models' values at the (rounded) data for every set, lam_X d×N×S, amp_X N×S, noise_X N×S.  Returns (ll[S], status[S]);
+    ll = -Inf where the matrix is not PD or a latent value is negative, NaN or infinite."""
+    X, y, lam, amp, noi, m, stride, disc = _ngp_batch_args(X, y, lam_X, amp_X, noise_X, mean_X, discrete)
+    d, N = X.shape
+    S = lam.shape[2]
+    ll = np.zeros(S)
+    st = np.zeros(S, dtype=np.int32)
+    _check(load_library().boss_ngp_loglike_batch(device, d, N, _dp(X), _dp(y), _ucp(disc), S, _dp(lam), _dp(amp), _dp(noi), _dp(m),
+                                                 stride, _dp(ll), st.ctypes.data_as(C.POINTER(C.c_int))))
     return ll, st
 
 

@@ -168,9 +168,17 @@ __device__ __forceinline__ double aug_entry(int kern, double amp2, int d, const 
 // Lower 64×64 tiles of the augmented matrix.  `cholesky(Symmetric(K))` (:209,:325) reads the UPPER
 // triangle, so the stored entry (a, b), a ≥ b, is the reference's K[b, a].  hyp = {α², σ², σ_∂²};
 // padding rows/columns = identity.
+// blockIdx.z = parameter set (boss_ggp_loglike_batch): the raw points are shared, set z reads its 1/λ and hyp at
+// z·par_bstride and writes its matrix at z·bstride.  A single handle's update is the one-set case (grid.z = 1, strides 0),
+// so both paths build every entry with the same instructions.  The set's α², σ², σ_∂² are wave-uniform (scalar registers),
+// its 1/λ sit in LDS beside the staged points.
 __global__ __launch_bounds__(256) void aug_gram_kernel(const double* __restrict__ Xraw, int ldx, int d, int n, int N, int Np,
                                                        int kern, const double* __restrict__ hyp,
-                                                       const double* __restrict__ invlam, double* __restrict__ A, int ld) {
+                                                       const double* __restrict__ invlam, size_t par_bstride,
+                                                       double* __restrict__ A, int ld, size_t bstride) {
+    hyp += (size_t)blockIdx.z * par_bstride;
+    invlam += (size_t)blockIdx.z * par_bstride;
+    A += (size_t)blockIdx.z * bstride;
     __shared__ double xa[AUG_MAX_D][64], xb[AUG_MAX_D][64], il[AUG_MAX_D];
     __shared__ int la[64], lb[64];
     const int tid = threadIdx.x, t = blockIdx.x;
@@ -367,9 +375,17 @@ __device__ __forceinline__ void gibbs_dim(double x, double lx, double y, double 
     esum = __builtin_fma(df * df, q, esum);
 }
 
+// blockIdx.z = parameter set (boss_ngp_loglike_batch): the rounded points are shared, set z reads λ(x_j) [d][Np] at
+// z·lam_bstride, α(x_j) and σ(x_j) [Np] at z·vec_bstride and writes its matrix at z·bstride; a single handle's update is the
+// one-set case (grid.z = 1, strides 0).
 __global__ __launch_bounds__(256) void gibbs_gram_kernel(const double* __restrict__ X, const double* __restrict__ Lam,
                                                          const double* __restrict__ amp, const double* __restrict__ noise,
-                                                         int d, int N, int Np, double* __restrict__ A, int ld) {
+                                                         size_t lam_bstride, size_t vec_bstride, int d, int N, int Np,
+                                                         double* __restrict__ A, int ld, size_t bstride) {
+    Lam += (size_t)blockIdx.z * lam_bstride;
+    amp += (size_t)blockIdx.z * vec_bstride;
+    noise += (size_t)blockIdx.z * vec_bstride;
+    A += (size_t)blockIdx.z * bstride;
     __shared__ double xj[16][64], lj[16][64];
     const int tid = threadIdx.x, t = blockIdx.x;
     int bi = (int)((sqrt(8.0 * t + 1.0) - 1.0) * 0.5);

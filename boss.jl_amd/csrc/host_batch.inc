@@ -1,4 +1,5 @@
-// host_batch.inc — boss_gp_loglike_batch: S hyper-parameter sets on one data slice (included by bosship.hip).
+// host_batch.inc — boss_gp_loglike_batch, boss_ggp_loglike_batch, boss_ngp_loglike_batch, boss_gp_fit_batch: S hyper-parameter
+// sets on one data slice (included by bosship.hip).
 
 // ------------------------------------------------------------------------------------------
 // batched log-likelihood
@@ -16,9 +17,12 @@ static void llgrad_finalize(int d, int N, const double* invlam, double amp2, dou
 // streams against 6.5-6.9 ms in one batch — a chunk costs the same ≈ 50 launches as the whole batch, and 25 chunks make the call
 // launch-bound on the host.  Where the one batch spends its 6.6 ms (rocprofv3, per call): trailing updates 3.0 ms (K = 256 tiles at
 // 48 TFLOP/s, 3.5 TB/s of C-tile traffic), panel solves 1.3 ms, column updates 0.95 ms, Gram 0.9 ms, diagonal blocks 0.4 ms.
-static void batch_factor_enqueue(Ctx* c, int kernel, int d, int N, int Np, int nb, const double* Xraw, const double* ydev,
-                                 const double* mean_arg, size_t mean_b, const double* invlam, const double* hyp, double* Xsc,
-                                 size_t xs_bstride, double* A, int ld, size_t bstride, double* inv16, size_t inv16_b, double* scal, int* info) {
+// What the models do differently is handed in: prep (may be empty) runs in front of the right-hand-side rows of a chunk, gram
+// builds the chunk's matrices; both launch on c->stream for sets b0 .. b0+cnt-1.
+using BatchStage = std::function<void(int b0, int cnt)>;
+static void batch_middle_enqueue(Ctx* c, int N, int Np, int nb, const double* ydev, const double* mean_arg, size_t mean_b, double* A,
+                                 int ld, size_t bstride, double* inv16, size_t inv16_b, double* scal, int* info, const BatchStage& prep,
+                                 const BatchStage& gram) {
     hipStream_t main_s = c->stream;
     static const double cache_mb = getenv("BOSS_BATCH_CHUNK_MB") ? atof(getenv("BOSS_BATCH_CHUNK_MB")) : 1e12;
     static const int max_streams = getenv("BOSS_BATCH_STREAMS") ? std::max(1, std::min(3, atoi(getenv("BOSS_BATCH_STREAMS")))) : 3;
@@ -41,12 +45,11 @@ static void batch_factor_enqueue(Ctx* c, int kernel, int d, int N, int Np, int n
         c->stream = s;                                       // (the enqueue helpers launch on the context's current stream)
         {
             ProfScope ps(c, "prep");
-            hipLaunchKernelGGL(scale_points_kernel, dim3((Np + 255) / 256, 1, cnt), dim3(256), 0, s, Xraw, Xsc + (size_t)b0 * xs_bstride, xs_bstride,
-                               invlam + (size_t)b0 * d, d, Np);
+            if (prep) prep(b0, cnt);
             hipLaunchKernelGGL(rhs_rows_kernel, dim3((Np + 255) / 256, 1, cnt), dim3(256), 0, s, A + (size_t)b0 * bstride, ld, bstride, N, Np,
                                ydev, mean_arg ? mean_arg + (size_t)b0 * mean_b : nullptr, mean_b, 0, (int*)nullptr);
         }
-        gram_enqueue(c, Xsc + (size_t)b0 * xs_bstride, xs_bstride, d, N, Np, kernel, hyp + 2 * (size_t)b0, A + (size_t)b0 * bstride, ld, bstride, cnt);
+        gram(b0, cnt);
         potrf_enqueue(c, A + (size_t)b0 * bstride, ld, Np, cnt, bstride, inv16 + (size_t)b0 * inv16_b, inv16_b, info + b0, /*gates=*/false);
         {
             ProfScope ps(c, "logdet");
@@ -59,6 +62,32 @@ static void batch_factor_enqueue(Ctx* c, int kernel, int d, int N, int Np, int n
         (void)hipEventRecord(c->llg_join[j - 1], c->llg_stream[j - 1]);
         (void)hipStreamWaitEvent(main_s, c->llg_join[j - 1], 0);
     }
+}
+
+// The plain model's stages: scaled points per set, then the stationary Gram kernel.
+static void batch_factor_enqueue(Ctx* c, int kernel, int d, int N, int Np, int nb, const double* Xraw, const double* ydev,
+                                 const double* mean_arg, size_t mean_b, const double* invlam, const double* hyp, double* Xsc,
+                                 size_t xs_bstride, double* A, int ld, size_t bstride, double* inv16, size_t inv16_b, double* scal, int* info) {
+    batch_middle_enqueue(
+        c, N, Np, nb, ydev, mean_arg, mean_b, A, ld, bstride, inv16, inv16_b, scal, info,
+        [&](int b0, int cnt) {
+            hipLaunchKernelGGL(scale_points_kernel, dim3((Np + 255) / 256, 1, cnt), dim3(256), 0, c->stream, Xraw, Xsc + (size_t)b0 * xs_bstride,
+                               xs_bstride, invlam + (size_t)b0 * d, d, Np);
+        },
+        [&](int b0, int cnt) {
+            gram_enqueue(c, Xsc + (size_t)b0 * xs_bstride, xs_bstride, d, N, Np, kernel, hyp + 2 * (size_t)b0, A + (size_t)b0 * bstride, ld, bstride,
+                         cnt);
+        });
+}
+
+// What the device left of set b as the caller sees it (shared by the three models' batched likelihoods): an invalid parameter set,
+// a failed pivot or a non-finite result give -Inf and their status, the others the log marginal likelihood of N observations.
+static int batch_set_result(int N, bool valid, int info, double logdet, double zz, double* ll) {
+    *ll = -std::numeric_limits<double>::infinity();
+    if (!valid) return BOSS_E_INVALID;
+    if (info != 0 || !std::isfinite(logdet) || !std::isfinite(zz)) return BOSS_E_NOT_PD;   // safe_data_loglike: exception → -Inf
+    *ll = -0.5 * (N * 1.8378770664093453 + logdet + zz);
+    return BOSS_OK;
 }
 
 // grad_out: null, or (d+2)×S — ∂logpdf/∂(λ_1..λ_d, α, σ) of every set (the factorisations run batched, the gradient passes set
@@ -272,17 +301,8 @@ static int loglike_batch_impl(int device, int kernel, int d, int N, const double
         HIPCHK(hipGetLastError());
         for (int b = 0; b < nb; ++b) {
             const double logdet = h_scal[2 * b], zz = h_scal[2 * b + 1];
-            int st = BOSS_OK;
             double ll;
-            if (!valid[b]) {
-                st = BOSS_E_INVALID;
-                ll = -std::numeric_limits<double>::infinity();
-            } else if (h_info[b] != 0 || !std::isfinite(logdet) || !std::isfinite(zz)) {
-                st = BOSS_E_NOT_PD;
-                ll = -std::numeric_limits<double>::infinity();   // safe_data_loglike: exception → -Inf
-            } else {
-                ll = -0.5 * (N * 1.8378770664093453 + logdet + zz);
-            }
+            const int st = batch_set_result(N, valid[b], h_info[b], logdet, zz, &ll);
             ll_out[s0 + b] = ll;
             if (status_out) status_out[s0 + b] = st;
             if (grad_out) {
@@ -314,6 +334,176 @@ extern "C" int boss_gp_loglike_grad_batch(int device, int kernel, int d, int N, 
     if (!grad_out) return fail(BOSS_E_INVALID, "grad_out is NULL");
     return loglike_batch_impl(device, kernel, d, N, X, y, mean_X, mean_stride, discrete, S, lengthscales, amplitudes, noise_stds,
                               ll_out, status_out, grad_out);
+}
+
+// ------------------------------------------------------------------------------------------
+// Batched likelihoods of the gradient-observation and the nonstationary model (boss_ggp_loglike_batch, boss_ngp_loglike_batch):
+// `loglike.(samples)` of src/model_fitters/sampling.jl:59-78 over gradient_gp.jl:367-397 / nonstationary_gp.jl:237-245.  The
+// structure is loglike_batch_impl's: chunks of at most 12 GiB of matrices on the workspaces batchA / batchX / batchMisc, the shared
+// middle (batch_middle_enqueue), one copy back and one synchronisation per chunk.  The models differ in their resident points, in
+// the per-set parameter block (par_doubles doubles per set, written by fill, which also says whether the set is valid) and in the
+// Gram launch.  Rows are padded to 128 (the one-workgroup small path knows the plain kernel only).
+// BOSS_MODEL_BATCH_CHUNK_MB=<MB> (tests) lowers the 12 GiB limit so that a small batch spans several chunks.
+// ------------------------------------------------------------------------------------------
+struct ModelBatchGramArgs {
+    const double* pts;                                       // the model's points, shared by all sets
+    const double* par;                                       // first set of the chunk, par_doubles apart
+    double* A;
+    int ld, cnt;
+    size_t bstride;
+};
+
+static int model_loglike_batch_run(Ctx* c, int N, int Np, int S, const std::vector<double>& pts, const std::vector<double>& yb,
+                                   const double* mean_X, int mean_stride, size_t par_doubles,
+                                   const std::function<bool(int, double*)>& fill,
+                                   const std::function<void(const ModelBatchGramArgs&)>& gram, double* ll_out, int* status_out) {
+    hipStream_t s = c->stream;
+    const int nblk = Np / BLK, ld = Np + RHS_ROWS;
+    const size_t bstride = (size_t)ld * Np, per = bstride * sizeof(double);
+    static const double chunk_mb = getenv("BOSS_MODEL_BATCH_CHUNK_MB") ? atof(getenv("BOSS_MODEL_BATCH_CHUNK_MB")) : 12288.0;
+    const size_t limit = (size_t)(std::max(chunk_mb, 0.0) * 1048576.0);
+    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)S, limit / per));
+    const size_t inv16_b = (size_t)nblk * 8 * 256, mean_doubles = mean_X ? (mean_stride == 0 ? (size_t)Np : (size_t)Np * chunk) : 0;
+    int rc = ws_reserve(c->batchA, per * chunk);
+    if (rc) return rc;
+    rc = ws_reserve(c->batchX, sizeof(double) * (pts.size() + Np + mean_doubles + par_doubles * chunk));
+    if (rc) return rc;
+    rc = ws_reserve(c->batchMisc, sizeof(double) * ((size_t)chunk * (inv16_b + 2)) + sizeof(int) * chunk + 64);
+    if (rc) return rc;
+    double* A = (double*)c->batchA.p;
+    double* pts_dev = (double*)c->batchX.p;                  // points | observations | prior means | parameter blocks
+    double* ydev = pts_dev + pts.size();
+    double* meandev = ydev + Np;
+    double* par_dev = meandev + mean_doubles;
+    double* inv16 = (double*)c->batchMisc.p;
+    double* scal = inv16 + inv16_b * chunk;
+    int* info = (int*)(scal + 2 * (size_t)chunk);
+    // (the host vectors outlive the copies: every chunk ends with a synchronisation)
+    HIPCHK(hipMemcpyAsync(pts_dev, pts.data(), sizeof(double) * pts.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(ydev, yb.data(), sizeof(double) * Np, hipMemcpyHostToDevice, s));
+    std::vector<double> h_par(par_doubles * chunk), h_scal(2 * (size_t)chunk), h_mean;
+    std::vector<int> h_info(chunk), valid(chunk);
+    const int Nm = mean_X ? mean_stride : 0;                 // (mean_stride is 0 or the number of observations)
+    if (mean_X && mean_stride == 0) {
+        h_mean.assign(Np, 0.0);
+        std::copy(mean_X, mean_X + N, h_mean.begin());
+        HIPCHK(hipMemcpyAsync(meandev, h_mean.data(), sizeof(double) * Np, hipMemcpyHostToDevice, s));
+    }
+    for (int s0 = 0; s0 < S; s0 += chunk) {
+        const int nb = std::min(chunk, S - s0);
+        for (int b = 0; b < nb; ++b) valid[b] = fill(s0 + b, h_par.data() + (size_t)b * par_doubles);
+        HIPCHK(hipMemcpyAsync(par_dev, h_par.data(), sizeof(double) * par_doubles * nb, hipMemcpyHostToDevice, s));
+        if (Nm) {
+            h_mean.assign((size_t)Np * nb, 0.0);
+            for (int b = 0; b < nb; ++b)
+                std::copy(mean_X + (size_t)(s0 + b) * Nm, mean_X + (size_t)(s0 + b + 1) * Nm, h_mean.begin() + (size_t)b * Np);
+            HIPCHK(hipMemcpyAsync(meandev, h_mean.data(), sizeof(double) * Np * nb, hipMemcpyHostToDevice, s));
+        }
+        batch_middle_enqueue(c, N, Np, nb, ydev, mean_X ? meandev : nullptr, Nm ? (size_t)Np : 0, A, ld, bstride, inv16, inv16_b, scal, info,
+                             BatchStage(), [&](int b0, int cnt) {
+                                 ProfScope ps(c, "gram");
+                                 gram(ModelBatchGramArgs{pts_dev, par_dev + (size_t)b0 * par_doubles, A + (size_t)b0 * bstride, ld, cnt, bstride});
+                             });
+        HIPCHK(hipMemcpyAsync(h_scal.data(), scal, sizeof(double) * 2 * nb, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(h_info.data(), info, sizeof(int) * nb, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        HIPCHK(hipGetLastError());
+        for (int b = 0; b < nb; ++b) {
+            const int st = batch_set_result(N, valid[b], h_info[b], h_scal[2 * b], h_scal[2 * b + 1], &ll_out[s0 + b]);
+            if (status_out) status_out[s0 + b] = st;
+        }
+    }
+    return BOSS_OK;
+}
+
+// S parameter sets (λ[d], α, σ, σ_∂) of a GradientGaussianProcess on one output slice; X d×n, dY d×n column-major as in
+// boss_ggp_create, lengthscales d×S.  Every parameter gets +1e-8 (gradient_gp.jl:128-131, :200-204) as in boss_ggp_update.
+extern "C" int boss_ggp_loglike_batch(int device, int kernel, int d, int n, const double* X, const double* y, const double* dY, int S,
+                                      const double* lengthscales, const double* amplitudes, const double* noise_stds,
+                                      const double* grad_noise_stds, double* ll_out, int* status_out) {
+    if (kernel < 0 || kernel > 2) return fail(BOSS_E_INVALID, "unknown kernel id");
+    if (d < 1 || n < 1 || S < 0 || !X || !y || !dY || !ll_out) return fail(BOSS_E_INVALID, "bad arguments");
+    if (d > AUG_MAX_D) return fail(BOSS_E_INVALID, "gradient observations: x_dim above 16 is not supported");
+    if ((long long)n * (1 + d) > MAX_ROWS) return fail(BOSS_E_INVALID, "augmented system too large (n (1 + d) > 46080)");
+    if (S == 0) return BOSS_OK;
+    if (!lengthscales || !amplitudes || !noise_stds || !grad_noise_stds) return fail(BOSS_E_INVALID, "NULL hyper-parameter array");
+    Ctx* c;
+    int rc = get_ctx(device, &c);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(c->mtx);
+    const int N = n * (1 + d), Np = round_up(N, BLK), ldx = round_up(n, 64);
+    std::vector<double> pts, yb(Np, 0.0);
+    pack_points(pts, X, d, n, ldx, nullptr);
+    for (int j = 0; j < n; ++j) {                            // `_build_obs_vector` (gradient_gp.jl:288-302), built once for all sets
+        yb[j] = y[j];
+        for (int l = 0; l < d; ++l) yb[(size_t)n * (1 + l) + j] = dY[(size_t)j * d + l];
+    }
+    const size_t par_doubles = (size_t)d + 4;               // 1/λ (d) | α², σ², σ_∂², -: the layout of a handle's resident parameters
+    auto fill = [&](int b, double* p) {
+        const double* lam = lengthscales + (size_t)b * d;
+        bool ok = amplitudes[b] >= 0.0 && noise_stds[b] >= 0.0 && grad_noise_stds[b] >= 0.0;
+        for (int k = 0; k < d; ++k) ok = ok && lam[k] >= 0.0;
+        for (int k = 0; k < d; ++k) p[k] = 1.0 / ((ok ? lam[k] : 1.0) + MIN_PARAM_VALUE);
+        const double amp = (ok ? amplitudes[b] : 1.0) + MIN_PARAM_VALUE, sig = (ok ? noise_stds[b] : 1.0) + MIN_PARAM_VALUE,
+                     sgd = (ok ? grad_noise_stds[b] : 1.0) + MIN_PARAM_VALUE;
+        p[d] = amp * amp;
+        p[d + 1] = sig * sig;
+        p[d + 2] = sgd * sgd;
+        p[d + 3] = 0.0;
+        return ok;
+    };
+    auto gram = [&](const ModelBatchGramArgs& a) {
+        const long long t64 = Np / 64;
+        hipLaunchKernelGGL(aug_gram_kernel, dim3((unsigned)(t64 * (t64 + 1) / 2), 1, a.cnt), dim3(256), 0, c->stream, a.pts, ldx, d, n, N, Np,
+                           kernel, a.par + d, a.par, par_doubles, a.A, a.ld, a.bstride);
+    };
+    return model_loglike_batch_run(c, N, Np, S, pts, yb, nullptr, 0, par_doubles, fill, gram, ll_out, status_out);
+}
+
+// S sets of latent values (λ(x_j) d×N, α(x_j) N, σ(x_j) N; set after set) of a NonstationaryGP on one output slice.  The values
+// are taken as given (nothing is added), and checked as boss_ngp_update checks them: a set with a lengthscale that is not finite
+// and positive, or an amplitude or noise that is not finite and non-negative, is reported and the others are computed.
+extern "C" int boss_ngp_loglike_batch(int device, int d, int N, const double* X, const double* y, const unsigned char* discrete, int S,
+                                      const double* lam_X, const double* amp_X, const double* noise_X, const double* mean_X,
+                                      int mean_stride, double* ll_out, int* status_out) {
+    if (d < 1 || N < 1 || S < 0 || !X || !y || !ll_out) return fail(BOSS_E_INVALID, "bad arguments");
+    if (N > MAX_ROWS) return fail(BOSS_E_INVALID, "more than 46080 observations are not supported");
+    if (S == 0) return BOSS_OK;
+    if (!lam_X || !amp_X || !noise_X) return fail(BOSS_E_INVALID, "NULL latent-value array");
+    if (mean_X && mean_stride != 0 && mean_stride != N) return fail(BOSS_E_INVALID, "mean_stride must be 0 or N");
+    Ctx* c;
+    int rc = get_ctx(device, &c);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(c->mtx);
+    const int Np = round_up(N, BLK);
+    std::vector<double> pts, yb(Np, 0.0);
+    pack_points(pts, X, d, N, Np, discrete);
+    std::copy(y, y + N, yb.begin());
+    const size_t par_doubles = ((size_t)d + 2) * Np;        // λ [d][Np] | α [Np] | σ [Np]; padding λ = 1, α = σ = 0 as in boss_ngp_update
+    auto fill = [&](int b, double* p) {
+        const double* lam = lam_X + (size_t)b * d * N;
+        const double* amp = amp_X + (size_t)b * N;
+        const double* noi = noise_X + (size_t)b * N;
+        bool ok = true;
+        for (int j = 0; j < N && ok; ++j) {
+            for (int k = 0; k < d; ++k) ok = ok && lam[(size_t)j * d + k] > 0.0 && std::isfinite(lam[(size_t)j * d + k]);
+            ok = ok && amp[j] >= 0.0 && std::isfinite(amp[j]) && noi[j] >= 0.0 && std::isfinite(noi[j]);
+        }
+        std::fill(p, p + (size_t)d * Np, 1.0);
+        std::fill(p + (size_t)d * Np, p + par_doubles, 0.0);
+        for (int j = 0; j < N; ++j) {
+            for (int k = 0; k < d; ++k) p[(size_t)k * Np + j] = ok ? lam[(size_t)j * d + k] : 1.0;
+            p[(size_t)d * Np + j] = ok ? amp[j] : 1.0;
+            p[(size_t)(d + 1) * Np + j] = ok ? noi[j] : 1.0;
+        }
+        return ok;
+    };
+    auto gram = [&](const ModelBatchGramArgs& a) {
+        const int t64 = Np / 64;
+        hipLaunchKernelGGL(gibbs_gram_kernel, dim3(t64 * (t64 + 1) / 2, 1, a.cnt), dim3(256), 0, c->stream, a.pts, a.par,
+                           a.par + (size_t)d * Np, a.par + (size_t)(d + 1) * Np, par_doubles, par_doubles, d, N, Np, a.A, a.ld, a.bstride);
+    };
+    return model_loglike_batch_run(c, N, Np, S, pts, yb, mean_X, mean_stride, par_doubles, fill, gram, ll_out, status_out);
 }
 
 // ------------------------------------------------------------------------------------------

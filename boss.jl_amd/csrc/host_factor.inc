@@ -1032,12 +1032,14 @@ static int factor_enqueue(boss_gp* g, RiderReq* rider) {
         ProfScope ps(c, "gram");
         const long long t64 = g->Np / 64;
         hipLaunchKernelGGL(aug_gram_kernel, dim3((unsigned)(t64 * (t64 + 1) / 2)), dim3(256), 0, s, (const double*)g->Xraw, g->ldx,
-                           g->d, g->npts, g->N, g->Np, g->kernel, (const double*)g->hyp, (const double*)g->invlam, g->A, g->ld);
+                           g->d, g->npts, g->N, g->Np, g->kernel, (const double*)g->hyp, (const double*)g->invlam, (size_t)0, g->A,
+                           g->ld, (size_t)0);
     } else if (g->gibbs) {
         ProfScope ps(c, "gram");
         const int t64 = g->Np / 64;
         hipLaunchKernelGGL(gibbs_gram_kernel, dim3(t64 * (t64 + 1) / 2), dim3(256), 0, s, (const double*)g->Xraw,
-                           (const double*)g->lamX, (const double*)g->ampX, (const double*)g->noiseX, g->d, g->N, g->Np, g->A, g->ld);
+                           (const double*)g->lamX, (const double*)g->ampX, (const double*)g->noiseX, (size_t)0, (size_t)0, g->d, g->N,
+                           g->Np, g->A, g->ld, (size_t)0);
     } else {
         gram_enqueue(c, g->Xsc, 0, g->d, g->N, g->Np, g->kernel, g->hyp, g->A, g->ld, 0, 1);
     }

@@ -5,6 +5,7 @@ Every evaluated point contributes its value and its gradient, so n points give a
   model_posterior_slice / data_loglike   -> boss_ggp_create + boss_ggp_update (augmented Gram, Cholesky, α-solve, logpdf)
   mean / var / mean_and_var              -> boss_gp_predict on the augmented factor
   mean_and_cov / cov                     -> boss_ggp_predict_cov
+  data_loglike_batch (`loglike.(samples)`) -> boss_ggp_loglike_batch (all samples of an output in one call)
 The acquisition maximizers (HipBatchAM, …) take these posteriors unchanged; append has its own entry point
 (boss_ggp_append).
 """
@@ -92,6 +93,26 @@ class HipGradientGPPosteriorSlice(HipGaussianProcessPosteriorSlice):
         return self.gp.append(x, y, dy)
 
 
+# Where data_loglike_batch switches from the loop of boss_ggp_update calls on one resident handle to one boss_ggp_loglike_batch
+# call.  Measured on an MI355X (tools/model_batch_time.py, p50 of 20 calls, range of three runs, ms; DESIGN.md §4.2,
+# profiles/model_batch_times.jsonl):
+#   rows   S = 2: batched | loop        S = 8: batched | loop        S = 64: batched | loop
+#     60   0.117-0.121 | 0.229-0.230    0.115-0.119 | 0.932-0.942    0.120-0.122 | 7.37-7.51
+#   1017   0.382-0.402 | 0.567-0.591    0.462-0.478 | 2.27-2.36      1.22-1.24   | 17.4-18.8
+#   4095   2.12-2.17   | 2.24-2.26      4.87-4.97   | 8.96-9.06      32.0        | 71.9-72.4
+#   8190   8.94-9.02   | 9.13-9.17      29.2-29.4   | 36.5-36.6      225-226     | 293
+# The batched call wins at every measured shape, by less and less as the system grows (the resident chain of a single update is
+# at its best there); beyond 8190 rows nothing is measured and the loop stays.  One set is an update.
+BATCH_MIN_SETS = 2
+BATCH_MAX_ROWS = 8192
+
+
+def batched_call_pays(rows: int, n_sets: int) -> bool:
+    """True where one batched call scores `n_sets` parameter sets of an augmented system of `rows` = n(1+d) rows faster than
+    the loop on resident handles (the measured region above)."""
+    return n_sets >= BATCH_MIN_SETS and rows <= BATCH_MAX_ROWS
+
+
 @dataclass
 class HipGradientGaussianProcess:
     """GradientGaussianProcess(mean, kernel, lengthscale_priors, amplitude_priors, noise_std_priors,
@@ -168,14 +189,29 @@ class HipGradientGaussianProcess:
         return llg
 
     def data_loglike_batch(self, data: GradientData, samples: Sequence[HipGradientGPParams]) -> np.ndarray:
-        """`loglike.(samples)` (src/model_fitters/sampling.jl:64,77) — what HipBatchedMAP calls; the augmented
-        factorisations are large enough to fill the device one at a time, so this is a loop on resident handles."""
-        ll = self.data_loglike(data)
-        try:
-            return np.array([ll(p) for p in samples])
-        finally:
-            for g in ll.handles:
-                g.close()
+        """`loglike.(samples)` (src/model_fitters/sampling.jl:64,77) — what HipBatchedMAP and HipSampleOptMAP's scoring phase call:
+        one boss_ggp_loglike_batch call per output (every launch covers all samples), summed over the outputs, -Inf where any
+        output's augmented matrix is not PD.  Few samples of a large system stay a loop of boss_ggp_update calls on resident
+        handles (`batched_call_pays`)."""
+        samples = list(samples)
+        S = len(samples)
+        if S == 0:
+            return np.zeros(0)
+        d, n = data.X.shape
+        if not batched_call_pays(n * (1 + d), S):
+            ll = self.data_loglike(data)
+            try:
+                return np.array([ll(p) for p in samples])
+            finally:
+                for g in ll.handles:
+                    g.close()
+        tot = np.zeros(S)
+        for i in range(data.Y.shape[0]):
+            lam = np.stack([p.lengthscales[:, i] for p in samples], axis=1)
+            amp, sig, sgd = (np.array([getattr(p, name)[i] for p in samples]) for name in ("amplitudes", "noise_std", "grad_noise_std"))
+            ll_i, st = api.ggp_loglike_batch(data.X, data.Y[i], data.dY[i], self.kernel, lam, amp, sig, sgd, self.device)
+            tot += np.where(st == api.BOSS_OK, ll_i, -math.inf)
+        return tot
 
     def model_posterior_slice(self, params: HipGradientGPParams, data: GradientData, i: int) -> HipGradientGPPosteriorSlice:
         """model_posterior_slice (gradient_gp.jl:307-329)."""

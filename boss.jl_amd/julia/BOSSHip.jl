@@ -301,10 +301,11 @@ function batched_data_loglike(m::Union{HipGaussianProcess, HipSemiparametric}, d
     return ll
 end
 function estimate_parameters(f::HipBatchedMAP, problem::BOSS.BossProblem, options::BOSS.BossOptions; return_all=false)
-    m = problem.model::Union{HipGaussianProcess, HipSemiparametric}; data = problem.data
+    m = problem.model::Union{HipGaussianProcess, HipSemiparametric, HipGradientGaussianProcess}; data = problem.data
     sampler = BOSS.params_sampler(m, data); prior = params_loglike(m)
     ps = [sampler() for _ in 1:f.samples]
-    ll = batched_data_loglike(m, data, ps; devices = f.devices) .+ prior.(ps)     # model_loglike = data + prior (src/surrogate_model.jl)
+    # (the gradient-observation model scores its samples on one device: boss_ggp_loglike_batch, method below)
+    ll = (m isa HipGradientGaussianProcess ? batched_data_loglike(m, data, ps) : batched_data_loglike(m, data, ps; devices = f.devices)) .+ prior.(ps)     # model_loglike = data + prior (src/surrogate_model.jl)
     return_all && return BOSS.MAPParams.(ps, ll)
     b = argmax(ll); return BOSS.MAPParams(ps[b], ll[b])
 end
@@ -723,6 +724,25 @@ function data_loglike_grad(m::HipGradientGaussianProcess, data::BOSS.GradientDat
         return lp[], (g[1:d], g[d + 1], g[d + 2], g[d + 3])
     end
 end
+"""
+Data log-likelihood of every parameter set of `ps` (summed over the outputs) for the gradient-observation model: one batched device
+call per output (`boss_ggp_loglike_batch`: the observation vector is built once, every launch covers all sets); -Inf where the
+augmented matrix is not PD.  `estimate_parameters(f::HipBatchedMAP, …)` takes it like the plain model's method.
+"""
+function batched_data_loglike(m::HipGradientGaussianProcess, data::BOSS.GradientData, ps::AbstractVector)
+    X = Matrix{Float64}(data.X); S = length(ps); ll = zeros(S)
+    for i in 1:size(data.Y, 1)
+        dY = ndims(data.dY) == 3 ? Matrix{Float64}(data.dY[i, :, :]) : Matrix{Float64}(data.dY)     # x_dim × n
+        λ = Matrix{Float64}(reduce(hcat, (p.λ[:, i] for p in ps))); lli = zeros(S); st = zeros(Cint, S)
+        α = Float64[p.α[i] for p in ps]; σ = Float64[p.σ[i] for p in ps]; σ∂ = Float64[p.σ_∂[i] for p in ps]
+        check(ccall((:boss_ggp_loglike_batch, lib), Cint,
+            (Cint, Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint,
+             Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}),
+            m.device, kernel_id(m.gp.kernel), size(X, 1), size(X, 2), X, Vector{Float64}(data.Y[i, :]), dY, S, λ, α, σ, σ∂, lli, st))
+        ll .+= lli
+    end
+    return ll
+end
 "augment_dataset! (src/types/problem.jl:191-198) for a fitted gradient-observation slice: new points with values and gradients, same hyper-parameters."
 function augment!(post::HipPosteriorSlice, X_new::AbstractMatrix{<:Real}, y_new::AbstractVector{<:Real}, dY_new::AbstractMatrix{<:Real})
     lp = Ref{Cdouble}()
@@ -749,6 +769,29 @@ function hip_posterior_slice(model::BOSS.NonstationaryGP, params::BOSS.Nonstatio
     check(ccall((:boss_ngp_update, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ref{Cdouble}),
           h[], reduce(hcat, f_λ.(eachcol(Xr))), Float64.(f_α.(eachcol(Xr))), Float64.(f_σ.(eachcol(X))), mean_vals(mu, X), 0, lp))
     return HipNonstationaryPosterior(HipPosteriorSlice(Handle(h[]), mu), f_λ, f_α, model.discrete, f_σ), lp[]   # lp = data_loglike_slice
+end
+"""
+`data_loglike_slice` (nonstationary_gp.jl:237-245) of output `i` for every parameter set of `ps` in one device call
+(`boss_ngp_loglike_batch`): the latent models of every set are evaluated at the (rounded) data on the host, their values cross the
+ABI set after set (λ x_dim × N × S, α and σ N × S).  Returns the S log-likelihoods, -Inf where not PD or a latent value is invalid.
+"""
+function batched_data_loglike_slice(model::BOSS.NonstationaryGP, ps::AbstractVector{<:BOSS.NonstationaryGPParams},
+                                    data::BOSS.ExperimentData, i::Int; device = 0)
+    X = Matrix{Float64}(data.X); Xr = rounded(X, model.discrete); d, N = size(X); S = length(ps)
+    Λ = Array{Float64}(undef, d, N, S); A = Matrix{Float64}(undef, N, S); Σ = Matrix{Float64}(undef, N, S)
+    for (s, p) in enumerate(ps)
+        f_λ = BOSS._param_posterior_slice(model.lengthscale_model, p.λ, data, i)
+        f_α = BOSS._param_posterior_slice(model.amplitude_model, p.α, data, i)
+        f_σ = BOSS._param_posterior_slice(model.noise_std_model, p.σ, data, i)
+        Λ[:, :, s] .= reduce(hcat, f_λ.(eachcol(Xr))); A[:, s] .= f_α.(eachcol(Xr)); Σ[:, s] .= f_σ.(eachcol(X))
+    end
+    ll = zeros(S); st = zeros(Cint, S)
+    check(ccall((:boss_ngp_loglike_batch, lib), Cint,
+        (Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{UInt8}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint,
+         Ptr{Cdouble}, Ptr{Cint}),
+        device, d, N, X, Vector{Float64}(data.Y[i, :]), isnothing(model.discrete) ? C_NULL : UInt8.(model.discrete), S, Λ, A, Σ,
+        mean_vals(BOSS.mean_getindex(model.mean, i), X), 0, ll, st))
+    return ll
 end
 """
 Log-likelihood of a fitted nonstationary slice with its partial derivatives w.r.t. the latent models' values at the training points:

@@ -265,3 +265,36 @@ class HipNonstationaryGP:
             finally:
                 g.close()
         return tot
+
+
+def data_loglike_batch(models: Sequence[HipNonstationaryGP], data: ExperimentData) -> np.ndarray:
+    """`loglike.(samples)` (src/model_fitters/sampling.jl:59-78) for S nonstationary models that differ in their latent closures
+    only (same `discrete`, same `device`): every model's closures are evaluated at the data exactly as `data_loglike` evaluates them
+    (λ, α at the rounded points, σ and the prior mean at the points as given), then ONE boss_ngp_loglike_batch call per output
+    scores all of them.  Returns the S log-likelihoods summed over the outputs; -Inf where an output's matrix is not PD (or a
+    latent value is invalid)."""
+    models = list(models)
+    S = len(models)
+    if S == 0:
+        return np.zeros(0)
+    first = models[0]
+    disc0 = None if first.discrete is None else np.asarray(first.discrete, bool)
+    for m in models[1:]:
+        disc = None if m.discrete is None else np.asarray(m.discrete, bool)
+        if m.device != first.device or (disc is None) != (disc0 is None) or (disc is not None and not np.array_equal(disc, disc0)):
+            raise ValueError("the models of a batch must share `discrete` and `device`")
+    d, N = data.X.shape
+    tot = np.zeros(S)
+    for i in range(data.Y.shape[0]):
+        lam = np.empty((d, N, S), order="F")
+        amp = np.empty((N, S), order="F")
+        noi = np.empty((N, S), order="F")
+        means = []
+        for s, m in enumerate(models):
+            lam[:, :, s], amp[:, s], noi[:, s], mu, _ = m._latent_at_data(data.X, i)
+            means.append(mu)
+        mean_X = None if all(mu is None for mu in means) else np.stack([np.zeros(N) if mu is None else mu for mu in means])
+        ll, st = api.ngp_loglike_batch(data.X, data.Y[i], lam, amp, noi, mean_X, disc0, first.device)
+        tot += np.where(st == api.BOSS_OK, ll, -np.inf)
+    return tot
+

@@ -233,6 +233,26 @@ int boss_gp_loglike_grad_batch(int device, int kernel, int d, int N, const doubl
                                const double* mean_X, int mean_stride, const unsigned char* discrete,
                                int S, const double* lengthscales, const double* amplitudes,
                                const double* noise_stds, double* ll_out, double* grad_out, int* status_out);
+/* The batched likelihood of the gradient-observation model: S parameter sets on one (X, y, dY) slice, arguments as in
+ * boss_ggp_create (X d×n, y n, dY d×n column-major) and boss_ggp_update (every parameter gets +1e-8):
+ *   lengthscales d×S (column s = set s), amplitudes S, noise_stds S, grad_noise_stds S;
+ *   ll_out S (-Inf where not PD or invalid), status_out S (BOSS_OK / BOSS_E_NOT_PD / BOSS_E_INVALID for a negative parameter) or NULL.
+ * The observation vector [y; dy/dx_1; ...; dy/dx_d] is built once; every launch covers the batch (grid.z = parameter set); the
+ * augmented matrix of a set is bit for bit the one boss_ggp_update builds at those parameters.  S = 0 is a no-op.
+ * Limits: d <= 16, n(1+d) <= 46080. */
+int boss_ggp_loglike_batch(int device, int kernel, int d, int n, const double* X, const double* y, const double* dY,
+                           int S, const double* lengthscales, const double* amplitudes, const double* noise_stds,
+                           const double* grad_noise_stds, double* ll_out, int* status_out);
+/* The batched likelihood of the nonstationary model: S sets of latent values at the N training points, set after set:
+ *   lam_X d×N×S (set s, column j = l(x_j)), amp_X N×S, noise_X N×S, taken as given (no 1e-8) and checked as boss_ngp_update
+ *   checks them: a set holding a lengthscale that is not finite and > 0, or an amplitude or noise that is not finite and >= 0
+ *   (negative, NaN, infinite), gets -Inf and BOSS_E_INVALID, the other sets are computed;
+ *   mean_X NULL, or N values shared by all sets (mean_stride = 0), or S×N with mean_stride = N;
+ *   discrete as in boss_ngp_create (the latent models are evaluated at the rounded points by the caller).
+ *   ll_out S (-Inf where not PD or invalid), status_out S or NULL.  S = 0 is a no-op. */
+int boss_ngp_loglike_batch(int device, int d, int N, const double* X, const double* y, const unsigned char* discrete,
+                           int S, const double* lam_X, const double* amp_X, const double* noise_X,
+                           const double* mean_X, int mean_stride, double* ll_out, int* status_out);
 /* S RESIDENT posteriors of one output slice out of ONE batched factorisation.
  * Replaces: the broadcast `model_posterior.(Ref(model), params, Ref(data))` over the S parameter samples of a Bayesian-inference
  * fit (src/posterior.jl:15-19; samples from ext/TuringExt.jl:88-107), i.e. S calls of posterior_gp (gaussian_process.jl:199-211)
