@@ -3,25 +3,6 @@
 // ------------------------------------------------------------------------------------------
 // acquisition
 // ------------------------------------------------------------------------------------------
-// EI parameters: by value in the kernel arguments for P <= EI_MAXP, else in device arrays.
-static int ei_params(Ctx* c, hipStream_t s, int P, const double* fit_coefs, const double* y_max, int has_best, double best,
-                     EiPar* par, double* dcoef, double* dymax) {
-    par->P = P;
-    par->mode = (has_best ? 1 : 0) | (y_max ? 2 : 0);
-    par->best = best;
-    if (P <= EI_MAXP) {
-        for (int p = 0; p < P; ++p) {
-            par->coefs[p] = fit_coefs[p];
-            par->ymax[p] = y_max ? y_max[p] : std::numeric_limits<double>::infinity();
-        }
-    } else {
-        HIPCHK(hipMemcpyAsync(dcoef, fit_coefs, sizeof(double) * P, hipMemcpyHostToDevice, s));
-        if (y_max) HIPCHK(hipMemcpyAsync(dymax, y_max, sizeof(double) * P, hipMemcpyHostToDevice, s));
-        HIPCHK(hipStreamSynchronize(s));
-    }
-    return BOSS_OK;
-}
-
 // dpair / idx_off / defer: one shard of a multi-device call (host_multi.inc) — the epilogue also leaves (max, global index) in the
 // device buffer dpair, and with defer the call returns right behind the enqueue (the caller runs the exchange on the same stream and
 // waits once); the shard's own (max, index) are then read from the context's pinned block by acq_shard_result.
@@ -281,22 +262,34 @@ static void llgrad_finalize(int d, int N, const double* invlam, double amp2, dou
     grad_out[d + 1] = sig * (aa - trK);
 }
 
+// The sums of one fitted handle on the host (h.size() doubles, see llgrad_enqueue): through the context's prediction workspace, one
+// copy back, one synchronisation.  Caller holds the context's lock.
+static int llgrad_download(boss_gp* g, std::vector<double>& h) {
+    Ctx* c = g->ctx;
+    hipStream_t s = c->stream;
+    int rc = ws_reserve(c->pred, sizeof(double) * h.size());
+    if (rc) return rc;
+    double* sums = (double*)c->pred.p;
+    rc = llgrad_enqueue(g, s, sums, 0, SetBatch(), g->gibbs ? (const double*)nullptr : (const double*)g->hyp, 0);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(h.data(), sums, sizeof(double) * h.size(), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipGetLastError());
+    return BOSS_OK;
+}
+
 extern "C" int boss_gp_loglike_grad(boss_gp_t* g, double* logpdf_out, double* grad_out) {
     if (!g || !grad_out) return fail(BOSS_E_INVALID, "NULL argument");
     NOT_FOR_AUG(g);
     Ctx* c = g->ctx;
     HIPCHK(hipSetDevice(c->device));
     std::lock_guard<std::mutex> lk(c->mtx);
-    if (g->pending) {
-        int rc0 = gp_finish(g, nullptr);
-        if (rc0) return rc0;
-    }
-    if (!g->fitted) return fail(BOSS_E_NOT_FITTED, "handle has no valid factorisation");
+    int rc = gp_settle(g);
+    if (rc) return rc;
     const int d = g->d, nv = d + 2;
     if (d > LLG_MAX_D) return fail(BOSS_E_INVALID, "x_dim too large for the likelihood-gradient kernel");
     hipStream_t s = c->stream;
-    static const bool small_off = getenv("BOSS_NO_SMALL_FIT") && atoi(getenv("BOSS_NO_SMALL_FIT"));
-    if (g->N <= SMALL_MAX_N && d <= SMALL_MAX_D && !g->gibbs && !c->prof_on && !small_off) {
+    if (small_fit_ok(c, g->N, d) && !g->gibbs) {
         // N <= 128: one workgroup, one launch, the Σ-vector lands in mapped host memory (small_llgrad_kernel)
         dinv_join(g);
         hipLaunchKernelGGL(small_llgrad_kernel, dim3(1), dim3(DIAG_THREADS), SMALL_LLG_LDS_BYTES, s, (const double*)g->A, g->ld, g->Np,
@@ -318,21 +311,15 @@ extern "C" int boss_gp_loglike_grad(boss_gp_t* g, double* logpdf_out, double* gr
             if (!got) HIPCHK(hipStreamSynchronize(s));
         }
         llgrad_finalize(d, g->N, g->host_par, g->host_par[d], g->host_par[d + 1], g->host_res[1], g->host_res + 8, grad_out);
-        if (logpdf_out) *logpdf_out = -0.5 * (g->N * 1.8378770664093453 + g->host_res[0] + g->host_res[1]);
+        if (logpdf_out) *logpdf_out = loglik(g->N, g->host_res[0], g->host_res[1]);
         return BOSS_OK;
     }
-    int rc = ws_reserve(c->pred, sizeof(double) * nv);
-    if (rc) return rc;
-    double* sums = (double*)c->pred.p;
-    rc = llgrad_enqueue(g, s, sums, 0, SetBatch(), (const double*)g->hyp, 0);
-    if (rc) return rc;
     std::vector<double> h(nv);
-    HIPCHK(hipMemcpyAsync(h.data(), sums, sizeof(double) * nv, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(hipGetLastError());
+    rc = llgrad_download(g, h);
+    if (rc) return rc;
     // host_par still holds the staged parameters of the last update: 1/(λ+1e-8), (α+1e-8)², (σ+1e-8)²
     llgrad_finalize(d, g->N, g->host_par, g->host_par[d], g->host_par[d + 1], g->host_res[1], h.data(), grad_out);
-    if (logpdf_out) *logpdf_out = -0.5 * (g->N * 1.8378770664093453 + g->host_res[0] + g->host_res[1]);
+    if (logpdf_out) *logpdf_out = loglik(g->N, g->host_res[0], g->host_res[1]);
     return BOSS_OK;
 }
 
@@ -346,23 +333,13 @@ extern "C" int boss_ngp_loglike_grad(boss_gp_t* g, double* logpdf_out, double* d
     Ctx* c = g->ctx;
     HIPCHK(hipSetDevice(c->device));
     std::lock_guard<std::mutex> lk(c->mtx);
-    if (g->pending) {
-        int rc0 = gp_finish(g, nullptr);
-        if (rc0) return rc0;
-    }
-    if (!g->fitted) return fail(BOSS_E_NOT_FITTED, "handle has no valid factorisation");
+    int rc = gp_settle(g);
+    if (rc) return rc;
     const int d = g->d, N = g->N, Np = g->Np;
     if (d > GIBBS_GRAD_MAX_D) return fail(BOSS_E_INVALID, "x_dim above 16 is not supported by the nonstationary gradient kernels");
-    hipStream_t s = c->stream;
-    int rc = ws_reserve(c->pred, sizeof(double) * (size_t)(d + 3) * Np);
-    if (rc) return rc;
-    double* sums = (double*)c->pred.p;
-    rc = llgrad_enqueue(g, s, sums, 0, SetBatch(), (const double*)nullptr, 0);
-    if (rc) return rc;
     std::vector<double> h((size_t)(d + 3) * Np);
-    HIPCHK(hipMemcpyAsync(h.data(), sums, sizeof(double) * h.size(), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(hipGetLastError());
+    rc = llgrad_download(g, h);
+    if (rc) return rc;
     for (int j = 0; j < N; ++j) {
         if (dlam_out)
             for (int k = 0; k < d; ++k) dlam_out[(size_t)j * d + k] = h[(size_t)k * Np + j];
@@ -370,7 +347,7 @@ extern "C" int boss_ngp_loglike_grad(boss_gp_t* g, double* logpdf_out, double* d
         if (dnoise_out) dnoise_out[j] = h[(size_t)(d + 1) * Np + j];
         if (dmean_out) dmean_out[j] = h[(size_t)(d + 2) * Np + j];
     }
-    if (logpdf_out) *logpdf_out = -0.5 * (g->N * 1.8378770664093453 + g->host_res[0] + g->host_res[1]);
+    if (logpdf_out) *logpdf_out = loglik(g->N, g->host_res[0], g->host_res[1]);
     return BOSS_OK;
 }
 
@@ -382,29 +359,19 @@ extern "C" int boss_ggp_loglike_grad(boss_gp_t* g, double* logpdf_out, double* g
     Ctx* c = g->ctx;
     HIPCHK(hipSetDevice(c->device));
     std::lock_guard<std::mutex> lk(c->mtx);
-    if (g->pending) {
-        int rc0 = gp_finish(g, nullptr);
-        if (rc0) return rc0;
-    }
-    if (!g->fitted) return fail(BOSS_E_NOT_FITTED, "handle has no valid factorisation");
+    int rc = gp_settle(g);
+    if (rc) return rc;
     const int d = g->d, nv = d + 3;
     if (d > AUG_MAX_D) return fail(BOSS_E_INVALID, "x_dim too large for the gradient-observation kernels");
-    hipStream_t s = c->stream;
-    int rc = ws_reserve(c->pred, sizeof(double) * nv);
-    if (rc) return rc;
-    double* sums = (double*)c->pred.p;
-    rc = llgrad_enqueue(g, s, sums, 0, SetBatch(), (const double*)g->hyp, 0);
-    if (rc) return rc;
     std::vector<double> h(nv);
-    HIPCHK(hipMemcpyAsync(h.data(), sums, sizeof(double) * nv, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(hipGetLastError());
+    rc = llgrad_download(g, h);
+    if (rc) return rc;
     // host_par holds the staged parameters of the last update: 1/(λ+1e-8), (α+1e-8)², (σ+1e-8)², (σ_∂+1e-8)²
     const double* hp = g->host_par;
     for (int m = 0; m < d; ++m) grad_out[m] = h[m];
     grad_out[d] = 2.0 * h[d] / std::sqrt(hp[d]);
     grad_out[d + 1] = std::sqrt(hp[d + 1]) * h[d + 1];
     grad_out[d + 2] = std::sqrt(hp[d + 2]) * h[d + 2];
-    if (logpdf_out) *logpdf_out = -0.5 * (g->N * 1.8378770664093453 + g->host_res[0] + g->host_res[1]);
+    if (logpdf_out) *logpdf_out = loglik(g->N, g->host_res[0], g->host_res[1]);
     return BOSS_OK;
 }

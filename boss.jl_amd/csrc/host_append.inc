@@ -171,11 +171,8 @@ extern "C" int boss_gp_append(boss_gp_t* g, int n, const double* X_new, const do
 // caller holds the context lock
 static int append_locked(boss_gp* g, int n, const double* X_new, const double* y_new, const double* mean_new, double* logpdf_out) {
     Ctx* c = g->ctx;
-    if (g->pending) {
-        int rc0 = gp_finish(g, nullptr);
-        if (rc0) return rc0;
-    }
-    if (!g->fitted) return fail(BOSS_E_NOT_FITTED, "append needs a fitted handle (its hyper-parameters are reused)");
+    int rc = gp_settle(g, "append needs a fitted handle (its hyper-parameters are reused)");
+    if (rc) return rc;
     if (g->has_mean && !mean_new)
         return fail(BOSS_E_INVALID, "the posterior has a prior mean: mean_new (its values at the new points) is required");
     hipStream_t s = c->stream;
@@ -205,7 +202,7 @@ static int append_locked(boss_gp* g, int n, const double* X_new, const double* y
         }
         fast = g->have_winv;
     }
-    int rc = gp_grow(g, N1);
+    rc = gp_grow(g, N1);
     if (rc) return rc;
     g->fitted = false;
     g->have_lt = false;
@@ -364,9 +361,7 @@ static int append_locked(boss_gp* g, int n, const double* X_new, const double* y
         HIPCHK(hipMemcpyAsync(g->host_res, g->scal, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
         HIPCHK(hipMemcpyAsync(&g->host_res[2], g->info, sizeof(int), hipMemcpyDeviceToHost, s));
     }
-    HIPCHK(hipGetLastError());
-    g->pending = true;
-    return gp_finish(g, logpdf_out);
+    return update_finish(g, 0, logpdf_out);
 }
 
 extern "C" int boss_gp_fit(int device, int kernel, int d, int N, const double* X, const double* y,

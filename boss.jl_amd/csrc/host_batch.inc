@@ -86,8 +86,26 @@ static int batch_set_result(int N, bool valid, int info, double logdet, double z
     *ll = -std::numeric_limits<double>::infinity();
     if (!valid) return BOSS_E_INVALID;
     if (info != 0 || !std::isfinite(logdet) || !std::isfinite(zz)) return BOSS_E_NOT_PD;   // safe_data_loglike: exception → -Inf
-    *ll = -0.5 * (N * 1.8378770664093453 + logdet + zz);
+    *ll = loglik(N, logdet, zz);
     return BOSS_OK;
+}
+
+// Set b of a batch — or a member of a fitted set — seen as a handle: the shape and the arrays every reader of a factor takes from
+// it (block columns and leading dimension follow from the padded row count as in gp_create_common)
+static void set_view(boss_gp* v, Ctx* c, int kernel, int d, int N, int Np, double* A, double* inv16, double* Xsc, double* Dinv,
+                     double* Dinv2) {
+    v->ctx = c;
+    v->kernel = kernel;
+    v->d = d;
+    v->N = N;
+    v->Np = Np;
+    v->nblk = Np / BLK;
+    v->ld = Np + RHS_ROWS;
+    v->A = A;
+    v->inv16 = inv16;
+    v->Xsc = Xsc;
+    v->Dinv = Dinv;
+    v->Dinv2 = Dinv2;
 }
 
 // grad_out: null, or (d+2)×S — ∂logpdf/∂(λ_1..λ_d, α, σ) of every set (the factorisations run batched, the gradient passes set
@@ -166,17 +184,9 @@ static int loglike_batch_impl(int device, int kernel, int d, int N, const double
     std::vector<double> h_sums;
     for (int s0 = 0; s0 < S; s0 += chunk) {
         const int nb = std::min(chunk, S - s0);
-        for (int b = 0; b < nb; ++b) {
-            const double* lam = lengthscales + (size_t)(s0 + b) * d;
-            bool ok = amplitudes[s0 + b] >= 0.0 && noise_stds[s0 + b] >= 0.0;
-            for (int k = 0; k < d; ++k) ok = ok && lam[k] >= 0.0;
-            valid[b] = ok;
-            const double amp = (ok ? amplitudes[s0 + b] : 1.0) + MIN_PARAM_VALUE;
-            const double sig = (ok ? noise_stds[s0 + b] : 1.0) + MIN_PARAM_VALUE;
-            for (int k = 0; k < d; ++k) h_invlam[(size_t)b * d + k] = 1.0 / ((ok ? lam[k] : 1.0) + MIN_PARAM_VALUE);
-            h_hyp[2 * b] = amp * amp;
-            h_hyp[2 * b + 1] = sig * sig;
-        }
+        for (int b = 0; b < nb; ++b)
+            valid[b] = stage_hyper(d, lengthscales + (size_t)(s0 + b) * d, amplitudes[s0 + b], noise_stds[s0 + b], &h_invlam[(size_t)b * d],
+                                   &h_hyp[2 * b]);
         if (!staged) {
             HIPCHK(hipMemcpy(invlam, h_invlam.data(), sizeof(double) * d * nb, hipMemcpyHostToDevice));
             HIPCHK(hipMemcpy(hyp, h_hyp.data(), sizeof(double) * 2 * nb, hipMemcpyHostToDevice));
@@ -207,9 +217,7 @@ static int loglike_batch_impl(int device, int kernel, int d, int N, const double
             HIPCHK(hipMemcpyAsync(hyp, st2, sizeof(double) * (4 * (size_t)chunk + (size_t)d * nb), hipMemcpyHostToDevice, s));
             HIPCHK(hipEventRecord(c->ev_up, s));
         }
-        static const bool small_off = getenv("BOSS_NO_SMALL_FIT") && atoi(getenv("BOSS_NO_SMALL_FIT"));
-        const bool small = N <= SMALL_MAX_N && d <= SMALL_MAX_D && !c->prof_on && !small_off;
-        if (small) {
+        if (small_fit_ok(c, N, d)) {
             // the reference's own sizes: one workgroup per set does scaled points, Gram, factorisation, z, logdet (small_fit_batch_kernel),
             // a second launch the Σ-vectors of the gradients (small_llgrad_kernel) — two launches per chunk instead of a dozen per group
             hipLaunchKernelGGL(small_fit_batch_kernel, dim3(nb), dim3(DIAG_THREADS), SMALL_LDS_BYTES, s, d, N, Np, ld, kernel,
@@ -232,18 +240,8 @@ static int loglike_batch_impl(int device, int kernel, int d, int N, const double
                 for (int b0 = 0; b0 < nb; b0 += group) {
                     const int cnt = std::min(group, nb - b0);
                     boss_gp v;                              // a view of sets b0 .. b0+cnt-1 as fitted handles with constant strides
-                    v.ctx = c;
-                    v.kernel = kernel;
-                    v.d = d;
-                    v.N = N;
-                    v.Np = Np;
-                    v.nblk = nblk;
-                    v.ld = ld;
-                    v.A = A + (size_t)b0 * bstride;
-                    v.inv16 = inv16 + (size_t)b0 * inv16_b;
-                    v.Xsc = Xsc + (size_t)b0 * xs_bstride;
-                    v.Dinv = dinv_scratch;
-                    v.Dinv2 = dinv_scratch + (size_t)group * nblk * BLK * BLK;
+                    set_view(&v, c, kernel, d, N, Np, A + (size_t)b0 * bstride, inv16 + (size_t)b0 * inv16_b, Xsc + (size_t)b0 * xs_bstride,
+                             dinv_scratch, dinv_scratch + (size_t)group * nblk * BLK * BLK);
                     SetBatch B;
                     B.nb = cnt;
                     B.sA = bstride;
@@ -268,18 +266,9 @@ static int loglike_batch_impl(int device, int kernel, int d, int N, const double
                 const int bank = b % nbanks;
                 hipStream_t sb = bank ? c->llg_stream[bank - 1] : s;
                 boss_gp v;
-                v.ctx = c;
-                v.kernel = kernel;
-                v.d = d;
-                v.N = N;
-                v.Np = Np;
-                v.nblk = nblk;
-                v.ld = ld;
-                v.A = A + (size_t)b * bstride;
-                v.inv16 = inv16 + (size_t)b * inv16_b;
-                v.Xsc = Xsc + (size_t)b * xs_bstride;
-                v.Dinv = dinv_scratch + (size_t)bank * dinv_one;
-                v.Dinv2 = v.Dinv + (size_t)nblk * BLK * BLK;
+                double* const dinv = dinv_scratch + (size_t)bank * dinv_one;
+                set_view(&v, c, kernel, d, N, Np, A + (size_t)b * bstride, inv16 + (size_t)b * inv16_b, Xsc + (size_t)b * xs_bstride, dinv,
+                         dinv + (size_t)nblk * BLK * BLK);
                 rc = llgrad_enqueue(&v, sb, sums + (size_t)b * nv, bank, SetBatch(), hyp + 2 * (size_t)b, 0);
                 if (rc) {
                     (void)hipDeviceSynchronize();
@@ -440,14 +429,8 @@ extern "C" int boss_ggp_loglike_batch(int device, int kernel, int d, int n, cons
     }
     const size_t par_doubles = (size_t)d + 4;               // 1/λ (d) | α², σ², σ_∂², -: the layout of a handle's resident parameters
     auto fill = [&](int b, double* p) {
-        const double* lam = lengthscales + (size_t)b * d;
-        bool ok = amplitudes[b] >= 0.0 && noise_stds[b] >= 0.0 && grad_noise_stds[b] >= 0.0;
-        for (int k = 0; k < d; ++k) ok = ok && lam[k] >= 0.0;
-        for (int k = 0; k < d; ++k) p[k] = 1.0 / ((ok ? lam[k] : 1.0) + MIN_PARAM_VALUE);
-        const double amp = (ok ? amplitudes[b] : 1.0) + MIN_PARAM_VALUE, sig = (ok ? noise_stds[b] : 1.0) + MIN_PARAM_VALUE,
-                     sgd = (ok ? grad_noise_stds[b] : 1.0) + MIN_PARAM_VALUE;
-        p[d] = amp * amp;
-        p[d + 1] = sig * sig;
+        const bool ok = stage_hyper(d, lengthscales + (size_t)b * d, amplitudes[b], noise_stds[b], p, p + d) && grad_noise_stds[b] >= 0.0;
+        const double sgd = (ok ? grad_noise_stds[b] : 1.0) + MIN_PARAM_VALUE;
         p[d + 2] = sgd * sgd;
         p[d + 3] = 0.0;
         return ok;
@@ -620,22 +603,13 @@ extern "C" int boss_gp_fit_batch(int device, int kernel, int d, int N, const dou
     double* scalB = hypB + 2 * (size_t)S;
     int* infoB = (int*)(scalB + 2 * (size_t)S);
 
-    static const bool small_off = getenv("BOSS_NO_SMALL_FIT") && atoi(getenv("BOSS_NO_SMALL_FIT"));
-    const bool small = N <= SMALL_MAX_N && d <= SMALL_MAX_D && !c->prof_on && !small_off;
+    const bool small = small_fit_ok(c, N, d);
     std::vector<double> buf, yb(Np, 0.0), h_invlam((size_t)d * S), h_hyp(2 * (size_t)S), h_mean;
     std::vector<int> valid(S);
     pack_points(buf, X, d, N, Np, discrete);
     std::copy(y, y + N, yb.begin());
-    for (int b = 0; b < S; ++b) {
-        const double* lam = lengthscales + (size_t)b * d;
-        bool ok = amplitudes[b] >= 0.0 && noise_stds[b] >= 0.0;     // gaussian_process.jl:227-229 (a failed set is reported, the others are built)
-        for (int k = 0; k < d; ++k) ok = ok && lam[k] >= 0.0;
-        valid[b] = ok;
-        const double amp = (ok ? amplitudes[b] : 1.0) + MIN_PARAM_VALUE, sig = (ok ? noise_stds[b] : 1.0) + MIN_PARAM_VALUE;
-        for (int k = 0; k < d; ++k) h_invlam[(size_t)b * d + k] = 1.0 / ((ok ? lam[k] : 1.0) + MIN_PARAM_VALUE);
-        h_hyp[2 * b] = amp * amp;
-        h_hyp[2 * b + 1] = sig * sig;
-    }
+    for (int b = 0; b < S; ++b)   // (a failed set is reported, the others are built)
+        valid[b] = stage_hyper(d, lengthscales + (size_t)b * d, amplitudes[b], noise_stds[b], &h_invlam[(size_t)b * d], &h_hyp[2 * b]);
     hipError_t e = hipSuccess;
     // small problems (one identity-padded block row beyond the data): everything the kernels do not write reads as zero
     if (small) e = hipMemsetAsync(st->slab, 0, sizeof(double) * total, s);
@@ -679,23 +653,13 @@ extern "C" int boss_gp_fit_batch(int device, int kernel, int d, int N, const dou
     for (int b = 0; b < S; ++b) {
         boss_gp* g = new boss_gp();
         hs.push_back(g);
-        g->ctx = c;
+        set_view(g, c, kernel, d, N, Np, A + (size_t)b * sA, inv16 + (size_t)b * sInv, Xsc + (size_t)b * sX, Dinv + (size_t)b * sDinv,
+                 Dinv2 + (size_t)b * sDinv2);
         g->set = st;
-        g->kernel = kernel;
-        g->d = d;
-        g->N = N;
-        g->Np = Np;
-        g->nblk = nblk;
-        g->ld = ld;
         g->npts = N;
         g->ldx = Np;
         g->Xraw = Xraw;
         g->y = ydev;
-        g->A = A + (size_t)b * sA;
-        g->inv16 = inv16 + (size_t)b * sInv;
-        g->Dinv = Dinv + (size_t)b * sDinv;
-        g->Dinv2 = Dinv2 + (size_t)b * sDinv2;
-        g->Xsc = Xsc + (size_t)b * sX;
         g->mean = meandev + (size_t)b * sMean;
         g->invlam = par + (size_t)b * sPar;
         g->hyp = g->invlam + d;
@@ -717,11 +681,8 @@ extern "C" int boss_gp_fit_batch(int device, int kernel, int d, int N, const dou
         g->host_par[d] = h_hyp[2 * b];
         g->host_par[d + 1] = h_hyp[2 * b + 1];
         const double logdet = h_scal[2 * b], zz = h_scal[2 * b + 1];
-        int stt = BOSS_OK;
-        double ll = -std::numeric_limits<double>::infinity();
-        if (!valid[b]) stt = BOSS_E_INVALID;
-        else if (h_info[b] != 0 || !std::isfinite(logdet) || !std::isfinite(zz)) stt = BOSS_E_NOT_PD;   // PosDefException of this sample's cholesky
-        else ll = -0.5 * (N * 1.8378770664093453 + logdet + zz);
+        double ll;
+        const int stt = batch_set_result(N, valid[b], h_info[b], logdet, zz, &ll);   // (BOSS_E_NOT_PD: PosDefException of this sample's cholesky)
         g->host_res[0] = logdet;
         g->host_res[1] = zz;
         g->fitted = stt == BOSS_OK;

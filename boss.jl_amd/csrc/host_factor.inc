@@ -805,6 +805,49 @@ static int gp_finish(boss_gp* g, double* logpdf_out);
 static int factor_enqueue(boss_gp* g, RiderReq* rider = nullptr);
 static int gp_own(boss_gp* g);
 
+// log marginal likelihood of N observations from log|K| and zᵀz
+constexpr double LOG_2PI = 1.8378770664093453;
+static double loglik(int N, double logdet, double zz) { return -0.5 * (N * LOG_2PI + logdet + zz); }
+
+// N <= 128 and few dimensions: the one-workgroup kernels (small_calls.hpp) take the plain model's fit, likelihood gradient and
+// prediction in one launch each.  BOSS_NO_SMALL_FIT=1 sends them through the tiled kernels; profiling wants its scopes.
+static bool small_fit_ok(const Ctx* c, int N, int d) {
+    static const bool small_off = getenv("BOSS_NO_SMALL_FIT") && atoi(getenv("BOSS_NO_SMALL_FIT"));
+    return N <= SMALL_MAX_N && d <= SMALL_MAX_D && !c->prof_on && !small_off;
+}
+
+// What a new factorisation of the handle's data under new hyper-parameters makes stale (every model's update).  The appends
+// (gp_grow, append_locked) keep part of it on purpose — have_winv survives a rank-one append — and clear their own lists.
+static void gp_invalidate(boss_gp* g) {
+    g->fitted = false;
+    g->have_dinv = false;
+    g->have_winv = false;
+    g->few_calls = 0;
+    g->have_lt = false;
+    g->fell_back = false;
+    ++g->epoch;
+    g->append_calls = 0;
+}
+
+// A pending update is finished (its error is the caller's), then the handle must hold a valid factorisation.  Caller holds the
+// context's lock.
+static int gp_settle(boss_gp* g, const char* unfitted = "handle has no valid factorisation") {
+    if (g->pending) {
+        int rc = gp_finish(g, nullptr);
+        if (rc) return rc;
+    }
+    if (!g->fitted) return fail(BOSS_E_NOT_FITTED, unfitted);
+    return BOSS_OK;
+}
+
+// What was just enqueued becomes the handle's pending update; waited for unless the caller defers that (boss_gp_sync)
+static int update_finish(boss_gp* g, int flags, double* logpdf_out) {
+    HIPCHK(hipGetLastError());
+    g->pending = true;
+    if (flags & BOSS_FIT_NO_SYNC) return BOSS_OK;
+    return gp_finish(g, logpdf_out);
+}
+
 extern "C" int boss_gp_set_y(boss_gp_t* g, const double* y) {
     if (!g || !y) return fail(BOSS_E_INVALID, "NULL argument");
     if (g->aug) return fail(BOSS_E_INVALID, "not available for gradient-observation posteriors (boss_ggp_*)");
@@ -821,14 +864,29 @@ extern "C" int boss_gp_set_y(boss_gp_t* g, const double* y) {
     return BOSS_OK;
 }
 
-static int validate_hyper(int d, const double* lam, double amp, double sig) {
-    // gaussian_process.jl:227-229: negative values signal an error (zero is lifted to 1e-8)
-    if (!lam) return fail(BOSS_E_INVALID, "lengthscale is NULL");
+// gaussian_process.jl:227-229: negative values signal an error (zero is lifted to 1e-8), and so does a NaN.  Null: the set is valid.
+static const char* hyper_fault(int d, const double* lam, double amp, double sig) {
     for (int k = 0; k < d; ++k)
-        if (!(lam[k] >= 0.0)) return fail(BOSS_E_INVALID, "lengthscales must be >= 0");
-    if (!(amp >= 0.0)) return fail(BOSS_E_INVALID, "amplitude must be >= 0");
-    if (!(sig >= 0.0)) return fail(BOSS_E_INVALID, "noise_std must be >= 0");
-    return BOSS_OK;
+        if (!(lam[k] >= 0.0)) return "lengthscales must be >= 0";
+    if (!(amp >= 0.0)) return "amplitude must be >= 0";
+    if (!(sig >= 0.0)) return "noise_std must be >= 0";
+    return nullptr;
+}
+static int validate_hyper(int d, const double* lam, double amp, double sig) {
+    if (!lam) return fail(BOSS_E_INVALID, "lengthscale is NULL");
+    const char* why = hyper_fault(d, lam, amp, sig);
+    return why ? fail(BOSS_E_INVALID, why) : BOSS_OK;
+}
+// The parameters as the kernels take them, +1e-8 on each (gaussian_process.jl:239-241): invlam[k] = 1/(λ_k + 1e-8),
+// hyp = {(α + 1e-8)², (σ + 1e-8)²}.  False: the set is invalid (hyper_fault) and staged as all-ones — a batch factorises it with
+// the others and reports it.
+static bool stage_hyper(int d, const double* lam, double amplitude, double noise_std, double* invlam, double* hyp) {
+    const bool ok = !hyper_fault(d, lam, amplitude, noise_std);
+    for (int k = 0; k < d; ++k) invlam[k] = 1.0 / ((ok ? lam[k] : 1.0) + MIN_PARAM_VALUE);
+    const double amp = (ok ? amplitude : 1.0) + MIN_PARAM_VALUE, sig = (ok ? noise_std : 1.0) + MIN_PARAM_VALUE;
+    hyp[0] = amp * amp;
+    hyp[1] = sig * sig;
+    return ok;
 }
 
 static int gp_finish(boss_gp* g, double* logpdf_out) {
@@ -933,7 +991,7 @@ static int gp_finish(boss_gp* g, double* logpdf_out) {
         return fail(BOSS_E_NOT_PD, msg);
     }
     g->fitted = true;
-    if (logpdf_out) *logpdf_out = -0.5 * (g->N * 1.8378770664093453 + logdet + zz);
+    if (logpdf_out) *logpdf_out = loglik(g->N, logdet, zz);
     launch_stamps_report("an update");
     return BOSS_OK;
 }
@@ -1081,17 +1139,8 @@ static int gp_update_enqueue(boss_gp* g, const double* lengthscale, double ampli
                              RiderReq* rider) {
     Ctx* c = g->ctx;
     hipStream_t s = c->stream;
-    g->fitted = false;
-    g->have_dinv = false;
-    g->have_winv = false;
-    g->few_calls = 0;
-    g->have_lt = false;
-    g->fell_back = false;
-    ++g->epoch;
-    g->append_calls = 0;
-    // +1e-8 on every parameter (gaussian_process.jl:239-241)
-    static const bool small_off = getenv("BOSS_NO_SMALL_FIT") && atoi(getenv("BOSS_NO_SMALL_FIT"));
-    const bool small = g->N <= SMALL_MAX_N && g->d <= SMALL_MAX_D && !c->prof_on && !small_off;   // one launch does it all
+    gp_invalidate(g);
+    const bool small = small_fit_ok(c, g->N, g->d);          // one launch does it all
     if (!g->par_ev) {                         // a member of a batch-fitted set: created here, on its first update (boss_gp_fit_batch)
         HIPCHK(hipEventCreateWithFlags(&g->par_ev, hipEventDisableTiming));
         if (!g->dinv_ev) HIPCHK(hipEventCreateWithFlags(&g->dinv_ev, hipEventDisableTiming));
@@ -1099,10 +1148,7 @@ static int gp_update_enqueue(boss_gp* g, const double* lengthscale, double ampli
     HIPCHK(hipEventSynchronize(g->par_ev));   // previous update's staging copies have been consumed
     double* invlam = g->host_par;
     double* hyp = g->host_par + g->d;
-    for (int k = 0; k < g->d; ++k) invlam[k] = 1.0 / (lengthscale[k] + MIN_PARAM_VALUE);
-    const double amp = amplitude + MIN_PARAM_VALUE, sig = noise_std + MIN_PARAM_VALUE;
-    hyp[0] = amp * amp;
-    hyp[1] = sig * sig;
+    (void)stage_hyper(g->d, lengthscale, amplitude, noise_std, invlam, hyp);   // (validated by the caller)
     g->amp2 = hyp[0];
     g->par_in_args = !small && g->d <= HYP_ARGS_MAX_D;          // the first kernel of the update deposits them on the device
     if (!small && !g->par_in_args) {
@@ -1176,29 +1222,30 @@ extern "C" int boss_ggp_update(boss_gp_t* g, const double* lengthscale, double a
     HIPCHK(hipSetDevice(c->device));
     std::lock_guard<std::mutex> lk(c->mtx);
     hipStream_t s = c->stream;
-    g->fitted = false;
-    g->have_dinv = false;
-    g->have_winv = false;
-    g->few_calls = 0;
-    ++g->epoch;
-    g->append_calls = 0;
+    gp_invalidate(g);
     HIPCHK(hipEventSynchronize(g->par_ev));
     double* invlam = g->host_par;
     double* hyp = g->host_par + g->d;
-    for (int k = 0; k < g->d; ++k) invlam[k] = 1.0 / (lengthscale[k] + MIN_PARAM_VALUE);   // gradient_gp.jl:128-131
-    const double amp = amplitude + MIN_PARAM_VALUE, sig = noise_std + MIN_PARAM_VALUE, sgd = grad_noise_std + MIN_PARAM_VALUE;
-    hyp[0] = amp * amp;
-    hyp[1] = sig * sig;                                      // :200-204
+    (void)stage_hyper(g->d, lengthscale, amplitude, noise_std, invlam, hyp);   // gradient_gp.jl:128-131, :200-204 (validated above)
+    const double sgd = grad_noise_std + MIN_PARAM_VALUE;
     hyp[2] = sgd * sgd;
     g->amp2 = hyp[0];
     HIPCHK(hipMemcpyAsync(g->invlam, invlam, sizeof(double) * (g->d + 3), hipMemcpyHostToDevice, s));
     HIPCHK(hipEventRecord(g->par_ev, s));
     rc = factor_enqueue(g);
     if (rc) return rc;
-    HIPCHK(hipGetLastError());
-    g->pending = true;
-    if (flags & BOSS_FIT_NO_SYNC) return BOSS_OK;
-    return gp_finish(g, logpdf_out);
+    return update_finish(g, flags, logpdf_out);
+}
+
+// The end of the two rebuild-appends: g2, a fresh handle on the joined data whose update returned rc, gives its contents to g when
+// that update succeeded (the caller's pointer stays valid) and goes either way.
+static int replace_with_rebuilt(boss_gp* g, boss_gp* g2, int rc) {
+    if (!rc) {
+        std::lock_guard<std::mutex> lk(g->ctx->mtx);
+        std::swap(*g, *g2);
+    }
+    boss_gp_free(g2);
+    return rc;
 }
 
 // augment_dataset! (src/types/problem.jl:191-198) followed by the posterior at unchanged hyper-parameters for a gradient-observation
@@ -1217,11 +1264,8 @@ extern "C" int boss_ggp_append(boss_gp_t* g, int n_new, const double* X_new, con
     {
         HIPCHK(hipSetDevice(c->device));
         std::lock_guard<std::mutex> lk(c->mtx);
-        if (g->pending) {
-            int rc0 = gp_finish(g, nullptr);
-            if (rc0) return rc0;
-        }
-        if (!g->fitted) return fail(BOSS_E_NOT_FITTED, "handle has no valid factorisation (its hyper-parameters are the ones re-used)");
+        int rc0 = gp_settle(g, "handle has no valid factorisation (its hyper-parameters are the ones re-used)");
+        if (rc0) return rc0;
         HIPCHK(hipMemcpyAsync(Xd.data(), g->Xraw, sizeof(double) * Xd.size(), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipMemcpyAsync(yt.data(), g->y, sizeof(double) * yt.size(), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
@@ -1252,16 +1296,7 @@ extern "C" int boss_ggp_append(boss_gp_t* g, int n_new, const double* X_new, con
     int rc = boss_ggp_create(c->logical, g->kernel, d, nt, X.data(), y.data(), dY.data(), &g2);
     if (rc) return rc;
     rc = boss_ggp_update(g2, lam.data(), std::max(amp, 0.0), std::max(sig, 0.0), std::max(sgd, 0.0), 0, logpdf_out);
-    if (rc) {
-        boss_gp_free(g2);
-        return rc;
-    }
-    {
-        std::lock_guard<std::mutex> lk(c->mtx);
-        std::swap(*g, *g2);
-    }
-    boss_gp_free(g2);
-    return BOSS_OK;
+    return replace_with_rebuilt(g, g2, rc);
 }
 
 // finite_nongp + logpdf / posterior (nonstationary_gp.jl:153-196, :237-245): the caller evaluates its latent
@@ -1287,12 +1322,7 @@ extern "C" int boss_ngp_update(boss_gp_t* g, const double* lam_X, const double* 
     HIPCHK(hipSetDevice(c->device));
     std::lock_guard<std::mutex> lk(c->mtx);
     hipStream_t s = c->stream;
-    g->fitted = false;
-    g->have_dinv = false;
-    g->have_winv = false;
-    g->few_calls = 0;
-    ++g->epoch;
-    g->append_calls = 0;
+    gp_invalidate(g);
     HIPCHK(hipMemcpyAsync(g->lamX, lam.data(), sizeof(double) * d * Np, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(g->ampX, amp.data(), sizeof(double) * Np, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(g->noiseX, noi.data(), sizeof(double) * Np, hipMemcpyHostToDevice, s));
@@ -1306,10 +1336,7 @@ extern "C" int boss_ngp_update(boss_gp_t* g, const double* lam_X, const double* 
     HIPCHK(hipStreamSynchronize(s));                         // the staging vectors go out of scope
     int rc = factor_enqueue(g);
     if (rc) return rc;
-    HIPCHK(hipGetLastError());
-    g->pending = true;
-    if (flags & BOSS_FIT_NO_SYNC) return BOSS_OK;
-    return gp_finish(g, logpdf_out);
+    return update_finish(g, flags, logpdf_out);
 }
 
 // augment_dataset! (src/types/problem.jl:191-198) + the posterior with the latent models re-evaluated by the caller AT THE NEW POINTS
@@ -1327,11 +1354,8 @@ extern "C" int boss_ngp_append(boss_gp_t* g, int n_new, const double* X_new, con
     {
         HIPCHK(hipSetDevice(c->device));
         std::lock_guard<std::mutex> lk(c->mtx);
-        if (g->pending) {
-            int rc0 = gp_finish(g, nullptr);
-            if (rc0) return rc0;
-        }
-        if (!g->fitted) return fail(BOSS_E_NOT_FITTED, "handle has no valid factorisation (its per-point hyper-parameters are the ones re-used)");
+        int rc0 = gp_settle(g, "handle has no valid factorisation (its per-point hyper-parameters are the ones re-used)");
+        if (rc0) return rc0;
         has_mean = g->has_mean;
         if (has_mean && !mean_new) return fail(BOSS_E_INVALID, "the posterior has a prior mean: mean_new (its values at the new points) is required");
         hipStream_t s = c->stream;
@@ -1370,16 +1394,7 @@ extern "C" int boss_ngp_append(boss_gp_t* g, int n_new, const double* X_new, con
     int rc = boss_ngp_create(c->logical, d, Nt, X.data(), y.data(), g->discrete.empty() ? nullptr : g->discrete.data(), &g2);
     if (rc) return rc;
     rc = boss_ngp_update(g2, lam.data(), amp.data(), noi.data(), meand.empty() ? nullptr : meand.data(), 0, logpdf_out);
-    if (rc) {
-        boss_gp_free(g2);
-        return rc;
-    }
-    {
-        std::lock_guard<std::mutex> lk(c->mtx);
-        std::swap(*g, *g2);
-    }
-    boss_gp_free(g2);
-    return BOSS_OK;
+    return replace_with_rebuilt(g, g2, rc);
 }
 
 extern "C" int boss_gp_sync(boss_gp_t* g, double* logpdf_out) {
@@ -1388,7 +1403,7 @@ extern "C" int boss_gp_sync(boss_gp_t* g, double* logpdf_out) {
     std::lock_guard<std::mutex> lk(g->ctx->mtx);
     if (!g->pending) {
         if (!g->fitted) return fail(BOSS_E_NOT_FITTED, "no update pending and handle is not fitted");
-        if (logpdf_out) *logpdf_out = -0.5 * (g->N * 1.8378770664093453 + g->host_res[0] + g->host_res[1]);
+        if (logpdf_out) *logpdf_out = loglik(g->N, g->host_res[0], g->host_res[1]);
         return BOSS_OK;
     }
     return gp_finish(g, logpdf_out);

@@ -183,11 +183,10 @@ static void small_dinv(boss_gp* g, hipStream_t s) {
     g->dinv0_gen = g->factor_gen;
 }
 static bool small_predict_ok(const boss_gp* g, int M) {
-    static const bool small_off = getenv("BOSS_NO_SMALL_FIT") && atoi(getenv("BOSS_NO_SMALL_FIT"));
     // one wave per candidate costs ∝ N² per candidate: up to 1024 candidates at N = 128, proportionally more below (the tiled
     // kernels take over where they are faster: 251 against 367 µs at N = 100, M = 8192)
     const long long cap = std::min<long long>(16384, 1024LL * SMALL_MAX_N * SMALL_MAX_N / ((long long)g->N * g->N));
-    return g->N <= SMALL_MAX_N && g->d <= SMALL_MAX_D && M <= cap && !g->aug && !g->gibbs && !g->ctx->prof_on && !small_off;
+    return small_fit_ok(g->ctx, g->N, g->d) && M <= cap && !g->aug && !g->gibbs;
 }
 
 static int predict_enqueue(boss_gp* g, const boss_cand* cd, const double* mean_s_dev, double* mu, double* var,
@@ -724,78 +723,24 @@ extern "C" int boss_ngp_predict(boss_gp_t* g, int M, const double* Xs, const dou
     return bad != ~0ULL ? neg_var_error(bad_index, bad, var[bad]) : BOSS_OK;
 }
 
-static int grad_enqueue(boss_gp* g, const boss_cand* cd, const double* mean_s_dev, const double* mean_grad_dev, double* mu,
-                        double* var, double* dmu, double* dvar, const double* clam_dev, const double* camp_dev, double* gibbs_sums);
-
-// mean_and_var of a NonstationaryGP posterior AND its gradient w.r.t. the candidates: what ForwardDiff pushes through
-// nonstationary_gp.jl:153-196 inside OptimizationAM (src/acquisition_maximizers/optimization.jl:36,89-118).  The candidate enters the
-// Gibbs kernel directly and through the latent λ(x*), α(x*): their Jacobians arrive evaluated, like their values —
-//   dlam_Xs d×d×M, dlam_Xs[l + d (m + d j)] = ∂λ_l/∂x_m at candidate j (NULL: constant λ);  damp_Xs d×M (NULL: constant α).
-// The device accumulates Σ_i a_i k_i ∇ln k_i and Σ_i w_i k_i ∇ln k_i in their three parts (explicit, through λ*, through α*:
-// gibbs_grad_accum_kernel), the Jacobians are folded in here (M d² multiply-adds).
-extern "C" int boss_ngp_predict_grad(boss_gp_t* g, int M, const double* Xs, const double* lam_Xs, const double* amp_Xs,
-                                     const double* dlam_Xs, const double* damp_Xs, const double* mean_Xs, const double* mean_grad,
-                                     double* mu, double* var, double* dmu, double* dvar, long* bad_index) {
-    if (!g || !Xs || !lam_Xs || !amp_Xs || !mu || !var || !dmu || !dvar) return fail(BOSS_E_INVALID, "NULL argument");
-    if (!g->gibbs) return fail(BOSS_E_INVALID, "handle was not created by boss_ngp_create");
-    if (M < 1) return fail(BOSS_E_INVALID, "M must be >= 1");
-    if (g->d > GIBBS_GRAD_MAX_D) return fail(BOSS_E_INVALID, "x_dim above 16 is not supported by the nonstationary gradient kernel");
-    if (bad_index) *bad_index = -1;
-    if (!g->fitted) return fail(BOSS_E_NOT_FITTED, "handle has no valid factorisation");
-    NgpCand pk;
-    int rc = ngp_pack(g, M, Xs, lam_Xs, amp_Xs, pk);
-    if (rc) return rc;
-    Ctx* c = g->ctx;
-    HIPCHK(hipSetDevice(c->device));
-    std::lock_guard<std::mutex> lk(c->mtx);
-    hipStream_t s = c->stream;
-    boss_cand cd;
-    double *clam, *camp;
-    rc = ngp_upload(c, g->d, M, pk, cd, clam, camp);
-    if (rc) return drain(c, rc);
-    const int d = g->d, Mp = pk.Mp, nslot = 2 * (2 * d + 1);
-    const size_t nsums = (size_t)nslot * Mp;
-    rc = ws_reserve(c->pred, sizeof(double) * (3 * (size_t)M + 2 + nsums));   // mu | var | sums | bad | mean
-    if (rc) return drain(c, rc);
-    double* dev = (double*)c->pred.p;
-    double *dmu_ = dev, *dvar_ = dev + M, *dsums = dev + 2 * (size_t)M, *dmean = dsums + nsums + 1;
-    unsigned long long* dbad = (unsigned long long*)(dsums + nsums);
-    if (mean_Xs) (void)hipMemcpyAsync(dmean, mean_Xs, sizeof(double) * M, hipMemcpyHostToDevice, s);
-    (void)hipMemsetAsync(dbad, 0xff, sizeof(unsigned long long), s);
-    rc = grad_enqueue(g, &cd, mean_Xs ? dmean : nullptr, nullptr, dmu_, dvar_, nullptr, nullptr, clam, camp, dsums);
-    if (rc) return drain(c, rc);
-    hipLaunchKernelGGL(clip_var_kernel, dim3((M + 255) / 256), dim3(256), 0, s, dvar_, M, dbad);
-    unsigned long long bad = 0;
-    std::vector<double> sums(nsums);
-    rc = finish(c, {{mu, dmu_, sizeof(double) * M}, {var, dvar_, sizeof(double) * M}, {sums.data(), dsums, sizeof(double) * nsums},
-                    {&bad, dbad, sizeof bad}});
-    if (rc) return rc;
-    const int ns1 = 2 * d + 1;
-    for (int j = 0; j < M; ++j) {
-        const double* Dl = dlam_Xs ? dlam_Xs + (size_t)j * d * d : nullptr;
-        const double* Da = damp_Xs ? damp_Xs + (size_t)j * d : nullptr;
-        for (int m = 0; m < d; ++m) {
-            double ga = sums[(size_t)(1 + m) * Mp + j], gw = sums[(size_t)(ns1 + 1 + m) * Mp + j];
-            if (Dl)
-                for (int l = 0; l < d; ++l) {
-                    ga += Dl[l + (size_t)d * m] * sums[(size_t)(1 + d + l) * Mp + j];
-                    gw += Dl[l + (size_t)d * m] * sums[(size_t)(ns1 + 1 + d + l) * Mp + j];
-                }
-            double av = 0.0;
-            if (Da) {
-                ga += Da[m] * sums[j];
-                gw += Da[m] * sums[(size_t)ns1 * Mp + j];
-                av = 2.0 * amp_Xs[j] * Da[m];
-            }
-            dmu[(size_t)j * d + m] = ga + (mean_grad ? mean_grad[(size_t)j * d + m] : 0.0);
-            dvar[(size_t)j * d + m] = av - 2.0 * gw;
-        }
-    }
-    return bad != ~0ULL ? neg_var_error(bad_index, bad, var[bad]) : BOSS_OK;
-}
-
+// EI parameters: by value in the kernel arguments for P <= EI_MAXP, else in device arrays.
 static int ei_params(Ctx* c, hipStream_t s, int P, const double* fit_coefs, const double* y_max, int has_best, double best,
-                     EiPar* par, double* dcoef, double* dymax);
+                     EiPar* par, double* dcoef, double* dymax) {
+    par->P = P;
+    par->mode = (has_best ? 1 : 0) | (y_max ? 2 : 0);
+    par->best = best;
+    if (P <= EI_MAXP) {
+        for (int p = 0; p < P; ++p) {
+            par->coefs[p] = fit_coefs[p];
+            par->ymax[p] = y_max ? y_max[p] : std::numeric_limits<double>::infinity();
+        }
+    } else {
+        HIPCHK(hipMemcpyAsync(dcoef, fit_coefs, sizeof(double) * P, hipMemcpyHostToDevice, s));
+        if (y_max) HIPCHK(hipMemcpyAsync(dymax, y_max, sizeof(double) * P, hipMemcpyHostToDevice, s));
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    return BOSS_OK;
+}
 
 // SURVEY §8f3.  Enqueue μ, σ² (unclipped) and ∇μ, ∇σ² of one posterior at resident candidates:
 // forward substitution (prediction kernel, 32-wide V slabs), adjoint substitution in place, gradient
@@ -963,6 +908,73 @@ extern "C" int boss_gp_predict_grad(boss_gp_t* g, int M, const double* Xs, const
     rc = finish(c, {{mu, dmu_, sizeof(double) * M}, {var, dvar_, sizeof(double) * M}, {dmu, dgm, sizeof(double) * dm},
                     {dvar, dgv, sizeof(double) * dm}, {&bad, dbad, sizeof bad}});
     if (rc) return rc;
+    return bad != ~0ULL ? neg_var_error(bad_index, bad, var[bad]) : BOSS_OK;
+}
+
+// mean_and_var of a NonstationaryGP posterior AND its gradient w.r.t. the candidates: what ForwardDiff pushes through
+// nonstationary_gp.jl:153-196 inside OptimizationAM (src/acquisition_maximizers/optimization.jl:36,89-118).  The candidate enters the
+// Gibbs kernel directly and through the latent λ(x*), α(x*): their Jacobians arrive evaluated, like their values —
+//   dlam_Xs d×d×M, dlam_Xs[l + d (m + d j)] = ∂λ_l/∂x_m at candidate j (NULL: constant λ);  damp_Xs d×M (NULL: constant α).
+// The device accumulates Σ_i a_i k_i ∇ln k_i and Σ_i w_i k_i ∇ln k_i in their three parts (explicit, through λ*, through α*:
+// gibbs_grad_accum_kernel), the Jacobians are folded in here (M d² multiply-adds).
+extern "C" int boss_ngp_predict_grad(boss_gp_t* g, int M, const double* Xs, const double* lam_Xs, const double* amp_Xs,
+                                     const double* dlam_Xs, const double* damp_Xs, const double* mean_Xs, const double* mean_grad,
+                                     double* mu, double* var, double* dmu, double* dvar, long* bad_index) {
+    if (!g || !Xs || !lam_Xs || !amp_Xs || !mu || !var || !dmu || !dvar) return fail(BOSS_E_INVALID, "NULL argument");
+    if (!g->gibbs) return fail(BOSS_E_INVALID, "handle was not created by boss_ngp_create");
+    if (M < 1) return fail(BOSS_E_INVALID, "M must be >= 1");
+    if (g->d > GIBBS_GRAD_MAX_D) return fail(BOSS_E_INVALID, "x_dim above 16 is not supported by the nonstationary gradient kernel");
+    if (bad_index) *bad_index = -1;
+    if (!g->fitted) return fail(BOSS_E_NOT_FITTED, "handle has no valid factorisation");
+    NgpCand pk;
+    int rc = ngp_pack(g, M, Xs, lam_Xs, amp_Xs, pk);
+    if (rc) return rc;
+    Ctx* c = g->ctx;
+    HIPCHK(hipSetDevice(c->device));
+    std::lock_guard<std::mutex> lk(c->mtx);
+    hipStream_t s = c->stream;
+    boss_cand cd;
+    double *clam, *camp;
+    rc = ngp_upload(c, g->d, M, pk, cd, clam, camp);
+    if (rc) return drain(c, rc);
+    const int d = g->d, Mp = pk.Mp, nslot = 2 * (2 * d + 1);
+    const size_t nsums = (size_t)nslot * Mp;
+    rc = ws_reserve(c->pred, sizeof(double) * (3 * (size_t)M + 2 + nsums));   // mu | var | sums | bad | mean
+    if (rc) return drain(c, rc);
+    double* dev = (double*)c->pred.p;
+    double *dmu_ = dev, *dvar_ = dev + M, *dsums = dev + 2 * (size_t)M, *dmean = dsums + nsums + 1;
+    unsigned long long* dbad = (unsigned long long*)(dsums + nsums);
+    if (mean_Xs) (void)hipMemcpyAsync(dmean, mean_Xs, sizeof(double) * M, hipMemcpyHostToDevice, s);
+    (void)hipMemsetAsync(dbad, 0xff, sizeof(unsigned long long), s);
+    rc = grad_enqueue(g, &cd, mean_Xs ? dmean : nullptr, nullptr, dmu_, dvar_, nullptr, nullptr, clam, camp, dsums);
+    if (rc) return drain(c, rc);
+    hipLaunchKernelGGL(clip_var_kernel, dim3((M + 255) / 256), dim3(256), 0, s, dvar_, M, dbad);
+    unsigned long long bad = 0;
+    std::vector<double> sums(nsums);
+    rc = finish(c, {{mu, dmu_, sizeof(double) * M}, {var, dvar_, sizeof(double) * M}, {sums.data(), dsums, sizeof(double) * nsums},
+                    {&bad, dbad, sizeof bad}});
+    if (rc) return rc;
+    const int ns1 = 2 * d + 1;
+    for (int j = 0; j < M; ++j) {
+        const double* Dl = dlam_Xs ? dlam_Xs + (size_t)j * d * d : nullptr;
+        const double* Da = damp_Xs ? damp_Xs + (size_t)j * d : nullptr;
+        for (int m = 0; m < d; ++m) {
+            double ga = sums[(size_t)(1 + m) * Mp + j], gw = sums[(size_t)(ns1 + 1 + m) * Mp + j];
+            if (Dl)
+                for (int l = 0; l < d; ++l) {
+                    ga += Dl[l + (size_t)d * m] * sums[(size_t)(1 + d + l) * Mp + j];
+                    gw += Dl[l + (size_t)d * m] * sums[(size_t)(ns1 + 1 + d + l) * Mp + j];
+                }
+            double av = 0.0;
+            if (Da) {
+                ga += Da[m] * sums[j];
+                gw += Da[m] * sums[(size_t)ns1 * Mp + j];
+                av = 2.0 * amp_Xs[j] * Da[m];
+            }
+            dmu[(size_t)j * d + m] = ga + (mean_grad ? mean_grad[(size_t)j * d + m] : 0.0);
+            dvar[(size_t)j * d + m] = av - 2.0 * gw;
+        }
+    }
     return bad != ~0ULL ? neg_var_error(bad_index, bad, var[bad]) : BOSS_OK;
 }
 

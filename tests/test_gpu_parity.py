@@ -1715,6 +1715,34 @@ def test_gradient_gp_candidate_gradients(api, O, kernel, d, n, M):
 
 
 @pytest.mark.parametrize("kernel", ["matern32", "matern52", "sqexp"])
+@pytest.mark.parametrize("d,n,M", [(3, 40, 70), (8, 150, 40)])
+def test_gradient_gp_candidate_gradients_after_a_refit(api, O, kernel, d, n, M):
+    """One handle: update(A), predict_grad, update(B), predict_grad — the second gradients belong to B's factorisation (the transposed
+    factor, the transposed block inverses and a = L⁻ᵀz are built once per factorisation, so every update has to void them).  The two
+    parameter sets are far enough apart for the bounds to tell them from each other (asserted on the oracle alone)."""
+    X, y, dY = make_grad(d, n, seed=d + n)
+    lam = np.linspace(0.35, 0.6, d)
+    par_a, par_b = (lam, 1.1, 1e-2, 3e-2), (1.5 * lam, 0.7, 3e-2, 5e-2)
+    Xs = np.random.default_rng(M).uniform(0.05, 0.95, (d, M))
+    _, _, dmu_a, dvar_a = O.gradient_gp_mean_and_var_grad(O.gradient_gp_fit(X, y, dY, kernel, *par_a), Xs)
+    mu_o, var_o, dmu_o, dvar_o = O.gradient_gp_mean_and_var_grad(O.gradient_gp_fit(X, y, dY, kernel, *par_b), Xs)
+    K = O.augmented_kernel_matrix(kernel, X, *par_b)
+    tol = max(1e-9, np.linalg.cond(K) * K.shape[0] * 2.0 ** -53 * 8)
+    bound_dmu, bound_dvar = tol * (1 + np.abs(dmu_o).max()) * 10, tol * (1 + np.abs(dvar_o).max()) * 10
+    assert np.abs(dmu_a - dmu_o).max() >= 1000 * bound_dmu and np.abs(dvar_a - dvar_o).max() >= 1000 * bound_dvar
+    g = api.GradGP(X, y, dY, kernel)
+    g.update(*par_a)
+    g.predict_grad(Xs)
+    g.update(*par_b)
+    mu, var, dmu, dvar = g.predict_grad(Xs)
+    assert np.all(np.abs(mu - mu_o) <= tol * (1 + np.abs(mu_o)))
+    assert np.all(np.abs(var - np.maximum(var_o, 0.0)) <= tol * 0.7 ** 2)
+    assert np.abs(dmu - dmu_o).max() <= bound_dmu, np.abs(dmu - dmu_o).max()
+    assert np.abs(dvar - dvar_o).max() <= bound_dvar, np.abs(dvar - dvar_o).max()
+    g.close()
+
+
+@pytest.mark.parametrize("kernel", ["matern32", "matern52", "sqexp"])
 @pytest.mark.parametrize("d,n,dup", [(1, 6, False), (3, 40, False), (2, 30, True), (8, 150, False), (16, 40, True)])
 def test_gradient_gp_likelihood_gradient(api, O, kernel, d, n, dup):
     """SURVEY §8f3 over §8f4: ∂ℓ/∂(λ, α, σ, σ_∂) of the gradient-observation model's data_loglike (gradient_gp.jl:367-397) — what
@@ -2053,6 +2081,46 @@ def test_nonstationary_gp_candidate_gradients(api, O, d, N, M):
     acq_o, dacq_o = O.expected_improvement_lin_grad([1.0], mu_o[None], vo[None], dmu_o[None], np.where(vo > 0, dvar_o, 0.0)[None], best)
     acq, dacq = api.acq_ei_grad_moments(mu[None], var[None], dmu[None], dvar[None], [1.0], None, best)
     assert np.abs(acq - acq_o).max() <= tol * 10 and np.abs(dacq - dacq_o).max() <= tol * (1 + np.abs(dacq_o).max()) * 100
+    g.close()
+
+
+def test_nonstationary_gp_candidate_gradients_after_a_refit(api, O):
+    """One handle: update(A), predict_grad, update(B), predict_grad with the latent models of B = (1.5 λ, 0.7 α, σ) of A — the second
+    gradients belong to B's factorisation (see test_gradient_gp_candidate_gradients_after_a_refit).  A and B are far enough apart
+    for the bounds to tell them from each other (asserted on the oracle alone)."""
+    d, N, M = 3, 300, 70
+    X, y, Xs = make(d, N, M, seed=14)
+    Xs = np.asfortranarray(0.05 + 0.9 * Xs)
+    w = np.linspace(0.5, 1.5, d)
+    f_lam = lambda x: 0.3 + 0.4 * np.asarray(x) ** 2 + 0.05 * np.arange(1, d + 1) + 0.1 * np.sin(w @ np.asarray(x))    # noqa: E731
+    J_lam = lambda x: np.diag(0.8 * np.asarray(x)) + 0.1 * np.cos(w @ np.asarray(x)) * np.tile(w, (d, 1))               # noqa: E731
+    f_amp = lambda x: 1.0 + 0.4 * np.sin(3 * x[0]) + 0.1 * x[-1]                                                        # noqa: E731
+    J_amp = lambda x: np.concatenate(([1.2 * np.cos(3 * x[0])], np.zeros(d - 2), [0.1]))                                # noqa: E731
+    f_noise = lambda x: 0.05 + 0.02 * x[0]                                                                               # noqa: E731
+    ev = lambda f, Z: np.array([f(Z[:, j]) for j in range(Z.shape[1])])                                                  # noqa: E731
+    noiX = ev(f_noise, X)
+    mX, mS = 0.3 * X[0], 0.3 * Xs[0]
+    mg = np.zeros((d, M))
+    mg[0] = 0.3
+    def case(sl, sa):                                         # latent models (sl λ, sa α): values at X, values and Jacobians at Xs
+        return (sl * ev(f_lam, X).T, sa * ev(f_amp, X)), (sl * ev(f_lam, Xs).T, sa * ev(f_amp, Xs), sl * np.stack([J_lam(Xs[:, j]) for j in range(M)], axis=2),
+                                                           sa * np.stack([J_amp(Xs[:, j]) for j in range(M)], axis=1))
+    (fit_a, cand_a), (fit_b, cand_b) = case(1.0, 1.0), case(1.5, 0.7)
+    _, _, dmu_a, dvar_a = O.nonstationary_mean_and_var_grad(O.nonstationary_fit(X, y, *fit_a, noiX, mean=mX), Xs, *cand_a, mS, mg)
+    post = O.nonstationary_fit(X, y, *fit_b, noiX, mean=mX)
+    mu_o, var_o, dmu_o, dvar_o = O.nonstationary_mean_and_var_grad(post, Xs, *cand_b, mS, mg)
+    tol = max(1e-9, np.linalg.cond(post.L @ post.L.T) * N * 2.0 ** -53 * 8)
+    bound_dmu, bound_dvar = tol * (1 + np.abs(dmu_o).max()) * 10, tol * (1 + np.abs(dvar_o).max()) * 10
+    assert np.abs(dmu_a - dmu_o).max() >= 1000 * bound_dmu and np.abs(dvar_a - dvar_o).max() >= 1000 * bound_dvar
+    g = api.GibbsGP(X, y)
+    g.update(*fit_a, noiX, mX)
+    g.predict_grad(Xs, *cand_a, mS, mg)
+    g.update(*fit_b, noiX, mX)
+    mu, var, dmu, dvar = g.predict_grad(Xs, *cand_b, mS, mg)
+    assert np.abs(mu - mu_o).max() <= tol * (1 + np.abs(mu_o).max())
+    assert np.abs(var - np.maximum(var_o, 0.0)).max() <= tol * cand_b[1].max() ** 2
+    assert np.abs(dmu - dmu_o).max() <= bound_dmu, np.abs(dmu - dmu_o).max()
+    assert np.abs(dvar - dvar_o).max() <= bound_dvar, np.abs(dvar - dvar_o).max()
     g.close()
 
 
