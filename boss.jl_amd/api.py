@@ -62,6 +62,12 @@ SIGNATURES = {
                                          C.c_int, _c_dp, C.POINTER(C.c_int)]),
     "boss_gp_fit_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _c_dp, _c_dp, _c_dp, C.c_int, _c_ucp,
                                     C.c_int, _c_dp, _c_dp, _c_dp, C.POINTER(C.c_void_p), _c_dp, C.POINTER(C.c_int)]),
+    "boss_ggp_fit_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _c_dp, _c_dp, _c_dp, C.c_int, _c_dp, _c_dp, _c_dp,
+                                     _c_dp, C.POINTER(C.c_void_p), _c_dp, C.POINTER(C.c_int)]),
+    "boss_ngp_fit_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, _c_dp, _c_dp, _c_ucp, C.c_int, _c_dp, _c_dp, _c_dp, _c_dp,
+                                     C.c_int, C.POINTER(C.c_void_p), _c_dp, C.POINTER(C.c_int)]),
+    "boss_ngp_predict_set": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.c_int, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp,
+                                       C.POINTER(C.c_long)]),
     "boss_gp_predict": (C.c_int, [C.c_void_p, C.c_int, _c_dp, _c_dp, _c_dp, _c_dp, C.POINTER(C.c_long)]),
     "boss_gp_predict_grad": (C.c_int, [C.c_void_p, C.c_int, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp,
                                        C.POINTER(C.c_long)]),
@@ -819,6 +825,96 @@ def ngp_loglike_batch(X, y, lam_X, amp_X, noise_X, mean_X=None, discrete=None, d
     return ll, st
 
 
+def ggp_fit_batch(X, y, dY, kernel, lengthscales, amplitudes, noise_stds, grad_noise_stds, device: int = 0):
+    """S resident posteriors of the gradient-observation model on one (X, y, dY) slice from ONE batched factorisation
+    (boss_ggp_fit_batch): what model_posterior builds per sample of a BI fit (src/posterior.jl:15-19).  Arguments as
+    ggp_loglike_batch.  Returns (gps[S] of GradGP, logpdf[S], status[S]); members with status != 0 are unfitted handles."""
+    X, y, dY, lam, amp, sig, sgd = _ggp_batch_args(X, y, dY, lengthscales, amplitudes, noise_stds, grad_noise_stds)
+    d, n = X.shape
+    S = lam.shape[1]
+    if S < 1:
+        raise BossError(BOSS_E_INVALID, "at least one parameter set is needed")
+    hs = (C.c_void_p * S)()
+    ll = np.zeros(S)
+    st = np.zeros(S, dtype=np.int32)
+    _check(load_library().boss_ggp_fit_batch(device, _kernel_id(kernel), d, n, _dp(X), _dp(y), _dp(dY), S, _dp(lam), _dp(amp),
+                                             _dp(sig), _dp(sgd), hs, _dp(ll), st.ctypes.data_as(C.POINTER(C.c_int))))
+    gps = []
+    for s in range(S):
+        g = GradGP.__new__(GradGP)
+        g.d, g.n, g.N, g.device, g.kernel, g._h = d, n, n * (1 + d), device, _kernel_id(kernel), C.c_void_p(hs[s])
+        g.logpdf = float(ll[s]) if st[s] == 0 else None
+        gps.append(g)
+    return gps, ll, st
+
+
+def ngp_fit_batch(X, y, lam_X, amp_X, noise_X, mean_X=None, discrete=None, device: int = 0):
+    """S resident posteriors of the nonstationary model on one (X, y) slice from ONE batched factorisation (boss_ngp_fit_batch).
+    Arguments as ngp_loglike_batch.  Returns (gps[S] of GibbsGP, logpdf[S], status[S]); members with status != 0 are unfitted."""
+    X, y, lam, amp, noi, m, stride, disc = _ngp_batch_args(X, y, lam_X, amp_X, noise_X, mean_X, discrete)
+    d, N = X.shape
+    S = lam.shape[2]
+    if S < 1:
+        raise BossError(BOSS_E_INVALID, "at least one parameter set is needed")
+    hs = (C.c_void_p * S)()
+    ll = np.zeros(S)
+    st = np.zeros(S, dtype=np.int32)
+    _check(load_library().boss_ngp_fit_batch(device, d, N, _dp(X), _dp(y), _ucp(disc), S, _dp(lam), _dp(amp), _dp(noi), _dp(m),
+                                             stride, hs, _dp(ll), st.ctypes.data_as(C.POINTER(C.c_int))))
+    gps = []
+    for s in range(S):
+        g = GibbsGP.__new__(GibbsGP)
+        g.d, g.N, g.device, g.kernel, g._h = d, N, device, None, C.c_void_p(hs[s])
+        g.logpdf = float(ll[s]) if st[s] == 0 else None
+        gps.append(g)
+    return gps, ll, st
+
+
+def _ngp_set_args(n, d, Xs, lam_Xs, amp_Xs, mean_Xs):
+    """The arrays boss_ngp_predict_set reads, converted and checked (no device is touched): Xs d×M, lam_Xs d×M×n, amp_Xs M×n (column i =
+    member i), mean_Xs None or n×M (row i = member i)."""
+    Xs = _f64(Xs)
+    if Xs.ndim == 1:
+        Xs = _f64(Xs.reshape(-1, 1))
+    if Xs.ndim != 2 or Xs.shape[0] != d:
+        raise ValueError("candidates must be d×M")
+    M = Xs.shape[1]
+    lam = _f64(lam_Xs, 3)
+    amp = _f64(amp_Xs, 2)
+    if lam.shape != (d, M, n) or amp.shape != (M, n):
+        raise BossError(BOSS_E_INVALID, "lam_Xs must be d×M×n and amp_Xs M×n (n = number of posteriors)")
+    ms = None
+    if mean_Xs is not None:
+        ms = np.ascontiguousarray(np.asarray(mean_Xs, dtype=np.float64))
+        if ms.shape != (n, M):
+            raise BossError(BOSS_E_INVALID, "mean_Xs must be n×M (one row per posterior)")
+    return Xs, lam, amp, ms
+
+
+def ngp_predict_set(gps: Sequence["GibbsGP"], Xs, lam_Xs, amp_Xs, mean_Xs=None):
+    """mean_and_var of n nonstationary posteriors at the same candidates in one call (boss_ngp_predict_set): lam_Xs d×M×n and
+    amp_Xs M×n are every member's λ(x*), α(x*).  Returns (mu[n, M], var[n, M]) — what acq_ei_moments takes as mu[S][1][M].
+    Equally shaped handles (the members of an ngp_fit_batch) are predicted in one launch.  DomainError (with .bad_index) as
+    GibbsGP.predict."""
+    n = len(gps)
+    if n < 1:
+        raise BossError(BOSS_E_INVALID, "at least one posterior is needed")
+    d = gps[0].d
+    Xs, lam, amp, ms = _ngp_set_args(n, d, Xs, lam_Xs, amp_Xs, mean_Xs)
+    M = Xs.shape[1]
+    arr = (C.c_void_p * n)(*[g._h.value for g in gps])
+    mu = np.zeros((n, M))
+    var = np.zeros((n, M))
+    bad = C.c_long(-1)
+    rc = load_library().boss_ngp_predict_set(n, arr, M, _dp(Xs), _dp(lam), _dp(amp), _dp(ms), _dp(mu), _dp(var), C.byref(bad))
+    if rc == BOSS_E_NEG_VAR:
+        e = DomainError(rc, load_library().boss_last_error().decode())
+        e.bad_index = bad.value
+        raise e
+    _check(rc)
+    return mu, var
+
+
 def acq_ei(gps: Sequence[Sequence[GP]], cand: Candidates, fit_coefs, y_max=None, best=None, valid_mask=None,
            mean_Xs=None, want_acq: bool = True):
     """EI·feas over resident candidates.  gps[s][p] = output p of hyper-parameter sample s.
@@ -1173,3 +1269,14 @@ def _fallbacks(device: int = 0):
     n, off = C.c_long(0), C.c_int(0)
     _check(fn(device, C.byref(n), C.byref(off)))
     return n.value, off.value
+
+
+def _set_launches(device: int = 0):
+    """(all, on precomputed K*) launches of the one-launch set prediction on the device so far (boss_debug_set_launches; tests)."""
+    lib = load_library()
+    fn = lib.boss_debug_set_launches
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_int, C.POINTER(C.c_long), C.POINTER(C.c_long)]
+    a, b = C.c_long(0), C.c_long(0)
+    fn(device, C.byref(a), C.byref(b))
+    return a.value, b.value

@@ -121,6 +121,7 @@ struct Ctx {
     size_t hostblk_cache_bytes = 0;
     unsigned long long* few_done = nullptr;    // device counter of finished workgroups (winv_args_kernel) and its value on the host
     unsigned long long few_done_cnt = 0;
+    long set_launches = 0, set_pre_launches = 0;   // predict_kernel_set launches: all, and those on K* written beforehand (boss_debug_set_launches)
     bool lookahead = true;
     bool prof_on = false;
     std::map<std::string, std::vector<std::pair<hipEvent_t, hipEvent_t>>> prof;
@@ -187,6 +188,14 @@ extern "C" int boss_debug_slab_cache_bytes(int device, size_t* bytes_out) {   //
         std::lock_guard<std::mutex> sl(it->second->slab_mtx);
         *bytes_out = it->second->slab_cache_bytes;
     }
+    return BOSS_OK;
+}
+
+extern "C" int boss_debug_set_launches(int device, long* all_out, long* pre_out) {   // (tests: did a call take the one-launch set prediction?)
+    std::lock_guard<std::mutex> lk(g_ctx_mtx);
+    auto it = g_ctx.find(device);
+    if (all_out) *all_out = it != g_ctx.end() ? it->second->set_launches : 0;
+    if (pre_out) *pre_out = it != g_ctx.end() ? it->second->set_pre_launches : 0;
     return BOSS_OK;
 }
 
@@ -483,7 +492,7 @@ static void gpset_release_storage(boss_gpset* st) {
 struct boss_gp {
     Ctx* ctx = nullptr;
     boss_gpset* set = nullptr;                 // member of a batch-fitted set: Xraw, y (shared with its siblings), Xsc, mean, A, inv16, Dinv, Dinv2, invlam, scal,
-                                               // host_res, host_par are views — never freed one by one, detached (gp_own) before anything grows or rewrites the data
+                                               // lamX, ampX, noiseX, host_res, host_par are views — never freed one by one, detached (gp_own) before anything grows or rewrites the data
     int kernel = 0, d = 0, N = 0, Np = 0, nblk = 0, ld = 0;
     double *Xraw = nullptr, *Xsc = nullptr, *y = nullptr, *mean = nullptr, *A = nullptr;
     double *LT = nullptr, *DT2 = nullptr, *avec = nullptr;   // gradients: transposed factor, transposed 256×256 inverses, a = L⁻ᵀz (lazily)

@@ -341,15 +341,16 @@ __global__ __launch_bounds__(256) void aug_llgrad_tile_kernel(const double* __re
 // Cross-covariances of `_build_cross_cov` for every candidate, written where the substitution kernels
 // expect their right-hand side: out[tile][row][BN] (the V slabs of predict_kernel<G, true>, or the residual
 // array of the few-candidates path).  One training observation per thread; padding rows = 0.
-__global__ __launch_bounds__(256) void aug_kstar_kernel(const double* __restrict__ Xraw, int ldx, int d, int n, int N, int Np,
-                                                        const double* __restrict__ Craw, int Mp, int kern, double amp2,
-                                                        const double* __restrict__ invlam, double* __restrict__ out, int BN) {
+// aug_kstar_body: the work of one workgroup = 256 rows (blockIdx.x) of candidate tile `tile` under one parameter set; out is that
+// tile's slab.
+__device__ __forceinline__ void aug_kstar_body(const double* __restrict__ Xraw, int ldx, int d, int n, int N, int Np,
+                                               const double* __restrict__ Craw, int Mp, int kern, double amp2,
+                                               const double* __restrict__ invlam, double* __restrict__ out, int BN, int tile) {
     extern __shared__ double sm[];                           // cs[d][BN] | xt[d][256] | il[d]
     double* cs = sm;
     double* xt = cs + d * BN;
     double* il = xt + d * 256;
-    const int tid = threadIdx.x, c0 = blockIdx.y * BN;
-    out += (size_t)blockIdx.y * Np * BN;
+    const int tid = threadIdx.x, c0 = tile * BN;
     const int row = blockIdx.x * 256 + tid;
     const int l = row < N ? row / n : -1, pt = row < N ? row - l * n : 0;
     for (int idx = tid; idx < d * BN; idx += 256) cs[idx] = Craw[(size_t)(idx / BN) * Mp + c0 + (idx % BN)];
@@ -359,6 +360,11 @@ __global__ __launch_bounds__(256) void aug_kstar_kernel(const double* __restrict
 #pragma unroll 1
     for (int c = 0; c < BN; ++c)
         out[(size_t)row * BN + c] = (l >= 0) ? aug_entry(kern, amp2, d, il, cs + c, BN, xt + tid, 256, 0, l) : 0.0;
+}
+__global__ __launch_bounds__(256) void aug_kstar_kernel(const double* __restrict__ Xraw, int ldx, int d, int n, int N, int Np,
+                                                        const double* __restrict__ Craw, int Mp, int kern, double amp2,
+                                                        const double* __restrict__ invlam, double* __restrict__ out, int BN) {
+    aug_kstar_body(Xraw, ldx, d, n, N, Np, Craw, Mp, kern, amp2, invlam, out + (size_t)blockIdx.y * Np * BN, BN, (int)blockIdx.y);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -474,18 +480,19 @@ __global__ __launch_bounds__(256) void gibbs_kstar_kernel(const double* __restri
 // The same for 32-wide tiles with the lanes along the candidate columns: a wave writes two whole 256-byte rows of the
 // tile per store (one row per thread makes every store touch 64 cache lines).  Rows are staged 8 dimensions at a time.
 constexpr int GIBBS_KSTAR_MAX_D = 48;                         // LDS: (2·d·32 + 32 + 2·8·256) doubles
-__global__ __launch_bounds__(256) void gibbs_kstar_cols_kernel(const double* __restrict__ X, const double* __restrict__ Lam,
-                                                               const double* __restrict__ amp, int d, int N, int Np,
-                                                               const double* __restrict__ C, const double* __restrict__ Clam,
-                                                               const double* __restrict__ Camp, int Mp, double* __restrict__ out) {
+// gibbs_kstar_cols_body: 256 rows (blockIdx.x) of candidate tile `tile`; out is that tile's slab, Clam / Camp the latent values
+// at the candidates of the parameter set at hand.
+__device__ __forceinline__ void gibbs_kstar_cols_body(const double* __restrict__ X, const double* __restrict__ Lam,
+                                                      const double* __restrict__ amp, int d, int N, int Np,
+                                                      const double* __restrict__ C, const double* __restrict__ Clam,
+                                                      const double* __restrict__ Camp, int Mp, double* __restrict__ out, int tile) {
     extern __shared__ double sm[];                           // cx[d][32] | cl[d][32] | ca[32] | xs[8][256] | ls[8][256]
     double* cx = sm;
     double* cl = cx + d * 32;
     double* ca = cl + d * 32;
     double* xs = ca + 32;
     double* ls = xs + 8 * 256;
-    const int tid = threadIdx.x, c0 = blockIdx.y * 32, col = tid & 31, rg = tid >> 5, rbase = blockIdx.x * 256;
-    out += (size_t)blockIdx.y * Np * 32;
+    const int tid = threadIdx.x, c0 = tile * 32, col = tid & 31, rg = tid >> 5, rbase = blockIdx.x * 256;
     for (int idx = tid; idx < d * 32; idx += 256) {
         cx[idx] = C[(size_t)(idx >> 5) * Mp + c0 + (idx & 31)];
         cl[idx] = Clam[(size_t)(idx >> 5) * Mp + c0 + (idx & 31)];
@@ -518,6 +525,12 @@ __global__ __launch_bounds__(256) void gibbs_kstar_cols_kernel(const double* __r
         const double am = 0.5 * (amp[row] + ac);
         out[(size_t)row * 32 + col] = (row < N) ? am * am * sqrt(pr[i]) * exp(-es[i]) : 0.0;
     }
+}
+__global__ __launch_bounds__(256) void gibbs_kstar_cols_kernel(const double* __restrict__ X, const double* __restrict__ Lam,
+                                                               const double* __restrict__ amp, int d, int N, int Np,
+                                                               const double* __restrict__ C, const double* __restrict__ Clam,
+                                                               const double* __restrict__ Camp, int Mp, double* __restrict__ out) {
+    gibbs_kstar_cols_body(X, Lam, amp, d, N, Np, C, Clam, Camp, Mp, out + (size_t)blockIdx.y * Np * 32, (int)blockIdx.y);
 }
 
 // σ²(x*) = k(x*,x*) − Σv² + 1e-18 with k(x*,x*) = α(x*)²; the substitution kernels left −Σv² in var.

@@ -14,21 +14,24 @@ static int gp_own(boss_gp* g) {
     if (!g->set) return BOSS_OK;
     Ctx* c = g->ctx;
     hipStream_t s = c->stream;
-    const size_t Np = g->Np, d = g->d;
-    double* nw[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    double* src[10] = {g->Xraw, g->Xsc, g->y, g->mean, g->A, g->inv16, g->Dinv, g->Dinv2, g->invlam, g->scal};
-    const size_t bytes[10] = {sizeof(double) * d * Np, sizeof(double) * d * Np, sizeof(double) * Np, sizeof(double) * Np,
+    const size_t Np = g->Np, d = g->d, ldx = g->ldx;          // (ldx: Np, or the padded point count of a gradient-observation member)
+    constexpr int NA = 13;                                   // the last three: λ(X), α(X), σ(X) of a nonstationary member
+    double* nw[NA] = {};
+    double* src[NA] = {g->Xraw, g->Xsc, g->y, g->mean, g->A, g->inv16, g->Dinv, g->Dinv2, g->invlam, g->scal, g->lamX, g->ampX, g->noiseX};
+    const size_t bytes[NA] = {sizeof(double) * d * ldx, sizeof(double) * d * ldx, sizeof(double) * Np, sizeof(double) * Np,
                               sizeof(double) * (size_t)g->ld * Np, sizeof(double) * g->nblk * 8 * 256, sizeof(double) * g->nblk * BLK * BLK,
-                              sizeof(double) * Np * PRED_RB, sizeof(double) * (d + 4), sizeof(double) * 4};
+                              sizeof(double) * Np * PRED_RB, sizeof(double) * (d + 4), sizeof(double) * 4,
+                              g->gibbs ? sizeof(double) * d * Np : 0, g->gibbs ? sizeof(double) * Np : 0, g->gibbs ? sizeof(double) * Np : 0};
     double *hres = nullptr, *hpar = nullptr, *hres_dev = nullptr;
     bool ok = true;
-    for (int i = 0; i < 10 && ok; ++i) ok = dev_malloc((void**)&nw[i], bytes[i]) == hipSuccess;
+    for (int i = 0; i < NA && ok; ++i) ok = bytes[i] == 0 || dev_malloc((void**)&nw[i], bytes[i]) == hipSuccess;
     ok = ok && hipHostMalloc((void**)&hres, 512, hipHostMallocDefault) == hipSuccess &&
          hipHostMalloc((void**)&hpar, sizeof(double) * (d + 4), hipHostMallocDefault) == hipSuccess &&
          hipHostGetDevicePointer((void**)&hres_dev, hres, 0) == hipSuccess;
     dinv_join(g);
     hipError_t e = hipSuccess;
-    for (int i = 0; i < 10 && ok && e == hipSuccess; ++i) e = hipMemcpyAsync(nw[i], src[i], bytes[i], hipMemcpyDeviceToDevice, s);
+    for (int i = 0; i < NA && ok && e == hipSuccess; ++i)
+        if (bytes[i]) e = hipMemcpyAsync(nw[i], src[i], bytes[i], hipMemcpyDeviceToDevice, s);
     if (ok && e == hipSuccess) e = hipStreamSynchronize(s);
     if (!ok || e != hipSuccess) {
         (void)hipStreamSynchronize(s);
@@ -54,6 +57,7 @@ static int gp_own(boss_gp* g) {
     g->hyp = g->invlam + d;
     g->scal = nw[9];
     g->info = (int*)(g->scal + 2);
+    g->lamX = nw[10]; g->ampX = nw[11]; g->noiseX = nw[12];
     g->host_res = hres;
     g->host_res_dev = hres_dev;
     g->host_par = hpar;

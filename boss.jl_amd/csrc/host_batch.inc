@@ -1,5 +1,5 @@
-// host_batch.inc — boss_gp_loglike_batch, boss_ggp_loglike_batch, boss_ngp_loglike_batch, boss_gp_fit_batch: S hyper-parameter
-// sets on one data slice (included by bosship.hip).
+// host_batch.inc — boss_gp_loglike_batch, boss_ggp_loglike_batch, boss_ngp_loglike_batch, boss_gp_fit_batch, boss_ggp_fit_batch,
+// boss_ngp_fit_batch: S hyper-parameter sets on one data slice (included by bosship.hip).
 
 // ------------------------------------------------------------------------------------------
 // batched log-likelihood
@@ -405,6 +405,33 @@ static int model_loglike_batch_run(Ctx* c, int N, int Np, int S, const std::vect
     return BOSS_OK;
 }
 
+// The parameter block of set b of a GradientGaussianProcess batch as a handle keeps it: 1/λ (d) | α², σ², σ_∂², - ; every
+// parameter gets +1e-8 (gradient_gp.jl:128-131, :200-204) as in boss_ggp_update.  False: an invalid set, staged as all-ones.
+static bool ggp_stage_set(int d, const double* lam, double amp, double sig, double gsig, double* p) {
+    const bool ok = stage_hyper(d, lam, amp, sig, p, p + d) && gsig >= 0.0;
+    const double sgd = (ok ? gsig : 1.0) + MIN_PARAM_VALUE;
+    p[d + 2] = sgd * sgd;
+    p[d + 3] = 0.0;
+    return ok;
+}
+// ... and of a NonstationaryGP batch: λ [d][Np] | α [Np] | σ [Np], padding λ = 1, α = σ = 0 as in boss_ngp_update; the values are
+// taken as given and checked as boss_ngp_update checks them.
+static bool ngp_stage_set(int d, int N, int Np, const double* lam, const double* amp, const double* noi, double* p) {
+    bool ok = true;
+    for (int j = 0; j < N && ok; ++j) {
+        for (int k = 0; k < d; ++k) ok = ok && lam[(size_t)j * d + k] > 0.0 && std::isfinite(lam[(size_t)j * d + k]);
+        ok = ok && amp[j] >= 0.0 && std::isfinite(amp[j]) && noi[j] >= 0.0 && std::isfinite(noi[j]);
+    }
+    std::fill(p, p + (size_t)d * Np, 1.0);
+    std::fill(p + (size_t)d * Np, p + ((size_t)d + 2) * Np, 0.0);
+    for (int j = 0; j < N; ++j) {
+        for (int k = 0; k < d; ++k) p[(size_t)k * Np + j] = ok ? lam[(size_t)j * d + k] : 1.0;
+        p[(size_t)d * Np + j] = ok ? amp[j] : 1.0;
+        p[(size_t)(d + 1) * Np + j] = ok ? noi[j] : 1.0;
+    }
+    return ok;
+}
+
 // S parameter sets (λ[d], α, σ, σ_∂) of a GradientGaussianProcess on one output slice; X d×n, dY d×n column-major as in
 // boss_ggp_create, lengthscales d×S.  Every parameter gets +1e-8 (gradient_gp.jl:128-131, :200-204) as in boss_ggp_update.
 extern "C" int boss_ggp_loglike_batch(int device, int kernel, int d, int n, const double* X, const double* y, const double* dY, int S,
@@ -429,11 +456,7 @@ extern "C" int boss_ggp_loglike_batch(int device, int kernel, int d, int n, cons
     }
     const size_t par_doubles = (size_t)d + 4;               // 1/λ (d) | α², σ², σ_∂², -: the layout of a handle's resident parameters
     auto fill = [&](int b, double* p) {
-        const bool ok = stage_hyper(d, lengthscales + (size_t)b * d, amplitudes[b], noise_stds[b], p, p + d) && grad_noise_stds[b] >= 0.0;
-        const double sgd = (ok ? grad_noise_stds[b] : 1.0) + MIN_PARAM_VALUE;
-        p[d + 2] = sgd * sgd;
-        p[d + 3] = 0.0;
-        return ok;
+        return ggp_stage_set(d, lengthscales + (size_t)b * d, amplitudes[b], noise_stds[b], grad_noise_stds[b], p);
     };
     auto gram = [&](const ModelBatchGramArgs& a) {
         const long long t64 = Np / 64;
@@ -464,22 +487,7 @@ extern "C" int boss_ngp_loglike_batch(int device, int d, int N, const double* X,
     std::copy(y, y + N, yb.begin());
     const size_t par_doubles = ((size_t)d + 2) * Np;        // λ [d][Np] | α [Np] | σ [Np]; padding λ = 1, α = σ = 0 as in boss_ngp_update
     auto fill = [&](int b, double* p) {
-        const double* lam = lam_X + (size_t)b * d * N;
-        const double* amp = amp_X + (size_t)b * N;
-        const double* noi = noise_X + (size_t)b * N;
-        bool ok = true;
-        for (int j = 0; j < N && ok; ++j) {
-            for (int k = 0; k < d; ++k) ok = ok && lam[(size_t)j * d + k] > 0.0 && std::isfinite(lam[(size_t)j * d + k]);
-            ok = ok && amp[j] >= 0.0 && std::isfinite(amp[j]) && noi[j] >= 0.0 && std::isfinite(noi[j]);
-        }
-        std::fill(p, p + (size_t)d * Np, 1.0);
-        std::fill(p + (size_t)d * Np, p + par_doubles, 0.0);
-        for (int j = 0; j < N; ++j) {
-            for (int k = 0; k < d; ++k) p[(size_t)k * Np + j] = ok ? lam[(size_t)j * d + k] : 1.0;
-            p[(size_t)d * Np + j] = ok ? amp[j] : 1.0;
-            p[(size_t)(d + 1) * Np + j] = ok ? noi[j] : 1.0;
-        }
-        return ok;
+        return ngp_stage_set(d, N, Np, lam_X + (size_t)b * d * N, amp_X + (size_t)b * N, noise_X + (size_t)b * N, p);
     };
     auto gram = [&](const ModelBatchGramArgs& a) {
         const int t64 = Np / 64;
@@ -501,37 +509,61 @@ __global__ void set_scatter_kernel(int d, int S, const double* __restrict__ invl
                                    size_t sPar, double* __restrict__ scal, size_t sScal) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= S) return;
-    double* p = par + (size_t)b * sPar;                      // [1/λ (d) | α², σ², -, -]: the layout of a handle's resident hyper-parameters
-    for (int k = 0; k < d; ++k) p[k] = invlamB[(size_t)b * d + k];
-    p[d] = hypB[2 * b];
-    p[d + 1] = hypB[2 * b + 1];
+    if (invlamB) {                                           // (null: the members' parameter blocks were uploaded in place)
+        double* p = par + (size_t)b * sPar;                  // [1/λ (d) | α², σ², -, -]: the layout of a handle's resident hyper-parameters
+        for (int k = 0; k < d; ++k) p[k] = invlamB[(size_t)b * d + k];
+        p[d] = hypB[2 * b];
+        p[d + 1] = hypB[2 * b + 1];
+    }
     double* q = scal + (size_t)b * sScal;                    // [logdet, zᵀz | info]
     q[0] = scalB[2 * b];
     q[1] = scalB[2 * b + 1];
     reinterpret_cast<int*>(q + 2)[0] = infoB[b];
 }
 
-extern "C" int boss_gp_fit_batch(int device, int kernel, int d, int N, const double* X, const double* y, const double* mean_X,
-                                 int mean_stride, const unsigned char* discrete, int S, const double* lengthscales,
-                                 const double* amplitudes, const double* noise_stds, boss_gp_t** out, double* logpdf_out,
-                                 int* status_out) {
-    if (!out) return fail(BOSS_E_INVALID, "out is NULL");
-    for (int b = 0; b < S; ++b) out[b] = nullptr;
-    if (kernel < 0 || kernel > 2) return fail(BOSS_E_INVALID, "unknown kernel id");
-    if (d < 1 || N < 1 || S < 1 || !X || !y) return fail(BOSS_E_INVALID, "need d >= 1, N >= 1, S >= 1 and non-NULL X, y");
-    if (N > MAX_ROWS) return fail(BOSS_E_INVALID, "more than 46080 observations are not supported");
-    if (!lengthscales || !amplitudes || !noise_stds) return fail(BOSS_E_INVALID, "NULL hyper-parameter array");
-    if (mean_X && mean_stride != 0 && mean_stride != N) return fail(BOSS_E_INVALID, "mean_stride must be 0 or N");
-    Ctx* c;
-    int rc = get_ctx(device, &c);
-    if (rc) return rc;
-    const int Np = round_up(N, PRED_RB), nblk = Np / BLK, ld = Np + RHS_ROWS;
-    const size_t sA = (size_t)ld * Np, sInv = (size_t)nblk * 8 * 256, sDinv = (size_t)nblk * BLK * BLK, sDinv2 = (size_t)Np * PRED_RB,
-                 sX = (size_t)d * Np, sMean = (size_t)Np, sPar = (size_t)round_up(d + 4, 8), sScal = 8;
-    const size_t shared = sX + Np;                           // raw points | y
-    const size_t compact = (size_t)S * (d + 4) + (size_t)round_up(S, 2) / 2 + 8;   // 1/λ, {α², σ²}, {logdet, zᵀz}, info of the batch kernels
-    const size_t total = shared + (size_t)S * (sA + sInv + sDinv + sDinv2 + sX + sMean + sPar + sScal) + compact;
-    const size_t hstride = 64 + sPar;                        // pinned doubles per member: host_res (512 bytes) | host_par
+// What the three fit-batch entry points share (fit_batch_run): the slab out of the context's cache or fresh, its layout, the upload of
+// the shared points / observations / prior means, one synchronisation, the members as views, and the clean-up when anything fails.
+// A model describes itself by its shape (FitBatchSpec) and two hooks: `factor` uploads the parameters and enqueues Gram matrices,
+// factorisations and log-determinants of all sets on c->stream (scalB: {logdet, zᵀz} per set, infoB: failed-pivot flags), `member`
+// fills in what only the model knows of member b (host_par, amp2) and says whether its parameters were valid.
+struct FitBatchSpec {
+    int kernel = 0, d = 0, N = 0, npts = 0, ldx = 0, S = 0;  // N rows per member; npts points [d][ldx] shared by all
+    bool aug = false, gibbs = false, zero_slab = false;      // zero_slab: the one-workgroup kernels read what they do not write as zero
+    const std::vector<double>* pts = nullptr;                // packed points, d·ldx doubles
+    const std::vector<double>* yb = nullptr;                 // observations, padded to Np
+    const double* mean_X = nullptr;
+    int mean_stride = 0;
+    const unsigned char* discrete = nullptr;
+    size_t sExtra = 0;                                       // per-member doubles behind the common arrays (nonstationary: λ(X) | α(X) | σ(X))
+    size_t compact_extra = 0;                                // staging of the batch kernels behind the members (plain model: 1/λ, {α², σ²} of all sets)
+};
+struct FitBatchSlab {
+    int Np = 0, ld = 0;
+    size_t total = 0, sA = 0, sInv = 0, sDinv = 0, sDinv2 = 0, sX = 0, sMean = 0, sPar = 0, sScal = 0, sExtra = 0;
+    double *base = nullptr, *pts = nullptr, *y = nullptr, *A = nullptr, *inv16 = nullptr, *Dinv = nullptr, *Dinv2 = nullptr, *Xsc = nullptr,
+           *mean = nullptr, *par = nullptr, *scal = nullptr, *extra = nullptr, *scalB = nullptr, *cextra = nullptr;
+    int* infoB = nullptr;
+    const double *scatter_invlam = nullptr, *scatter_hyp = nullptr;   // set by `factor` when the parameter blocks are scattered from compact arrays
+};
+static int fit_batch_run(Ctx* c, const FitBatchSpec& sp, const std::function<hipError_t(FitBatchSlab&, hipStream_t)>& factor,
+                         const std::function<bool(int, boss_gp*)>& member, boss_gp_t** out, double* logpdf_out, int* status_out) {
+    const int S = sp.S, d = sp.d, N = sp.N;
+    FitBatchSlab L;
+    const int Np = L.Np = round_up(N, PRED_RB), nblk = Np / BLK;
+    L.ld = Np + RHS_ROWS;
+    L.sA = (size_t)L.ld * Np;
+    L.sInv = (size_t)nblk * 8 * 256;
+    L.sDinv = (size_t)nblk * BLK * BLK;
+    L.sDinv2 = (size_t)Np * PRED_RB;
+    L.sX = (size_t)d * sp.ldx;
+    L.sMean = (size_t)Np;
+    L.sPar = (size_t)round_up(d + 4, 8);
+    L.sScal = 8;
+    L.sExtra = sp.sExtra;
+    const size_t shared = L.sX + Np;                         // raw points | y
+    const size_t compact = 2 * (size_t)S + (size_t)round_up(S, 2) / 2 + 8 + sp.compact_extra;   // {logdet, zᵀz}, info of the batch kernels
+    const size_t total = L.total = shared + (size_t)S * (L.sA + L.sInv + L.sDinv + L.sDinv2 + L.sX + L.sMean + L.sPar + L.sScal + L.sExtra) + compact;
+    const size_t hstride = 64 + L.sPar;                      // pinned doubles per member: host_res (512 bytes) | host_par
     HIPCHK(hipSetDevice(c->device));                         // (before anything is allocated: this early return leaves nothing behind)
     boss_gpset* st = new boss_gpset();
     st->ctx = c;
@@ -588,101 +620,92 @@ extern "C" int boss_gp_fit_batch(int device, int kernel, int d, int N, const dou
     double* host_dev = nullptr;
     if (hipHostGetDevicePointer((void**)&host_dev, st->host_block, 0) != hipSuccess) return bail(BOSS_E_ALLOC, "pinned allocation failed");
     hipStream_t s = c->stream;
-    double* Xraw = (double*)st->slab;
-    double* ydev = Xraw + sX;
-    double* A = ydev + Np;
-    double* inv16 = A + (size_t)S * sA;
-    double* Dinv = inv16 + (size_t)S * sInv;
-    double* Dinv2 = Dinv + (size_t)S * sDinv;
-    double* Xsc = Dinv2 + (size_t)S * sDinv2;
-    double* meandev = Xsc + (size_t)S * sX;
-    double* par = meandev + (size_t)S * sMean;
-    double* scal = par + (size_t)S * sPar;
-    double* invlamB = scal + (size_t)S * sScal;
-    double* hypB = invlamB + (size_t)S * d;
-    double* scalB = hypB + 2 * (size_t)S;
-    int* infoB = (int*)(scalB + 2 * (size_t)S);
+    L.base = (double*)st->slab;
+    L.pts = L.base;
+    L.y = L.pts + L.sX;
+    L.A = L.y + Np;
+    L.inv16 = L.A + (size_t)S * L.sA;
+    L.Dinv = L.inv16 + (size_t)S * L.sInv;
+    L.Dinv2 = L.Dinv + (size_t)S * L.sDinv;
+    L.Xsc = L.Dinv2 + (size_t)S * L.sDinv2;
+    L.mean = L.Xsc + (size_t)S * L.sX;
+    L.par = L.mean + (size_t)S * L.sMean;
+    L.scal = L.par + (size_t)S * L.sPar;
+    L.extra = L.scal + (size_t)S * L.sScal;
+    L.scalB = L.extra + (size_t)S * L.sExtra;
+    L.infoB = (int*)(L.scalB + 2 * (size_t)S);
+    L.cextra = L.scalB + 2 * (size_t)S + (size_t)round_up(S, 2) / 2 + 8;
 
-    const bool small = small_fit_ok(c, N, d);
-    std::vector<double> buf, yb(Np, 0.0), h_invlam((size_t)d * S), h_hyp(2 * (size_t)S), h_mean;
-    std::vector<int> valid(S);
-    pack_points(buf, X, d, N, Np, discrete);
-    std::copy(y, y + N, yb.begin());
-    for (int b = 0; b < S; ++b)   // (a failed set is reported, the others are built)
-        valid[b] = stage_hyper(d, lengthscales + (size_t)b * d, amplitudes[b], noise_stds[b], &h_invlam[(size_t)b * d], &h_hyp[2 * b]);
+    std::vector<double> h_mean;
     hipError_t e = hipSuccess;
     // small problems (one identity-padded block row beyond the data): everything the kernels do not write reads as zero
-    if (small) e = hipMemsetAsync(st->slab, 0, sizeof(double) * total, s);
-    else e = hipMemsetAsync(meandev, 0, sizeof(double) * sMean * S, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(Xraw, buf.data(), sizeof(double) * sX, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(ydev, yb.data(), sizeof(double) * Np, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(invlamB, h_invlam.data(), sizeof(double) * d * S, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(hypB, h_hyp.data(), sizeof(double) * 2 * S, hipMemcpyHostToDevice, s);
-    if (mean_X && e == hipSuccess) {
-        h_mean.assign(sMean * S, 0.0);
+    if (sp.zero_slab) e = hipMemsetAsync(st->slab, 0, sizeof(double) * total, s);
+    else e = hipMemsetAsync(L.mean, 0, sizeof(double) * L.sMean * S, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(L.pts, sp.pts->data(), sizeof(double) * L.sX, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(L.y, sp.yb->data(), sizeof(double) * Np, hipMemcpyHostToDevice, s);
+    if (sp.mean_X && e == hipSuccess) {
+        h_mean.assign(L.sMean * S, 0.0);
         for (int b = 0; b < S; ++b) {
-            const double* src = mean_X + (mean_stride == 0 ? 0 : (size_t)b * N);
+            const double* src = sp.mean_X + (sp.mean_stride == 0 ? 0 : (size_t)b * N);
             std::copy(src, src + N, h_mean.begin() + (size_t)b * Np);
         }
-        e = hipMemcpyAsync(meandev, h_mean.data(), sizeof(double) * sMean * S, hipMemcpyHostToDevice, s);
+        e = hipMemcpyAsync(L.mean, h_mean.data(), sizeof(double) * L.sMean * S, hipMemcpyHostToDevice, s);
     }
     if (e != hipSuccess) return bail(BOSS_E_NO_DEVICE, std::string("uploading the observations: ") + hipGetErrorString(e));
-    if (small) {
-        hipLaunchKernelGGL(small_fit_batch_kernel, dim3(S), dim3(DIAG_THREADS), SMALL_LDS_BYTES, s, d, N, Np, ld, kernel,
-                           (const double*)invlamB, (const double*)hypB, (const double*)Xraw, Xsc, sX, (const double*)ydev,
-                           (const double*)meandev, sMean, A, sA, inv16, sInv, scalB, infoB);
-    } else {
-        batch_factor_enqueue(c, kernel, d, N, Np, S, Xraw, ydev, (const double*)meandev, sMean, invlamB, hypB, Xsc, sX, A, ld, sA, inv16, sInv,
-                             scalB, infoB);
-        // (the block inverses the prediction kernels need are built for all members in one set of launches by the first prediction over
-        // the set — predict_set_enqueue —, or member by member where a single member is used: a fit whose caller only wants the
-        // likelihoods, or a few members, does not pay the 2.9 ms they cost at 512 × N = 1024)
-    }
-    hipLaunchKernelGGL(set_scatter_kernel, dim3((S + 255) / 256), dim3(256), 0, s, d, S, (const double*)invlamB, (const double*)hypB,
-                       (const double*)scalB, (const int*)infoB, par, sPar, scal, sScal);
+    e = factor(L, s);
+    if (e != hipSuccess) return bail(BOSS_E_NO_DEVICE, std::string("uploading the hyper-parameters: ") + hipGetErrorString(e));
+    // (the block inverses the prediction kernels need are built for all members in one set of launches by the first prediction over
+    // the set — predict_set_enqueue —, or member by member where a single member is used: a fit whose caller only wants the
+    // likelihoods, or a few members, does not pay the 2.9 ms they cost at 512 × N = 1024)
+    hipLaunchKernelGGL(set_scatter_kernel, dim3((S + 255) / 256), dim3(256), 0, s, d, S, L.scatter_invlam, L.scatter_hyp,
+                       (const double*)L.scalB, (const int*)L.infoB, L.par, L.sPar, L.scal, L.sScal);
     std::vector<double> h_scal(2 * (size_t)S);
     std::vector<int> h_info(S);
-    e = hipMemcpyAsync(h_scal.data(), scalB, sizeof(double) * 2 * S, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(h_info.data(), infoB, sizeof(int) * S, hipMemcpyDeviceToHost, s);
+    e = hipMemcpyAsync(h_scal.data(), L.scalB, sizeof(double) * 2 * S, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(h_info.data(), L.infoB, sizeof(int) * S, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e == hipSuccess) e = hipGetLastError();
     if (e != hipSuccess) return bail(BOSS_E_NO_DEVICE, std::string("batched factorisation: ") + hipGetErrorString(e));
     bool any_disc = false;
-    if (discrete)
-        for (int k = 0; k < d; ++k) any_disc |= discrete[k] != 0;
+    if (sp.discrete)
+        for (int k = 0; k < d; ++k) any_disc |= sp.discrete[k] != 0;
     for (int b = 0; b < S; ++b) {
         boss_gp* g = new boss_gp();
         hs.push_back(g);
-        set_view(g, c, kernel, d, N, Np, A + (size_t)b * sA, inv16 + (size_t)b * sInv, Xsc + (size_t)b * sX, Dinv + (size_t)b * sDinv,
-                 Dinv2 + (size_t)b * sDinv2);
+        set_view(g, c, sp.kernel, d, N, Np, L.A + (size_t)b * L.sA, L.inv16 + (size_t)b * L.sInv, L.Xsc + (size_t)b * L.sX,
+                 L.Dinv + (size_t)b * L.sDinv, L.Dinv2 + (size_t)b * L.sDinv2);
         g->set = st;
-        g->npts = N;
-        g->ldx = Np;
-        g->Xraw = Xraw;
-        g->y = ydev;
-        g->mean = meandev + (size_t)b * sMean;
-        g->invlam = par + (size_t)b * sPar;
+        g->aug = sp.aug;
+        g->gibbs = sp.gibbs;
+        g->npts = sp.npts;
+        g->ldx = sp.ldx;
+        g->Xraw = L.pts;
+        g->y = L.y;
+        g->mean = L.mean + (size_t)b * L.sMean;
+        g->invlam = L.par + (size_t)b * L.sPar;
         g->hyp = g->invlam + d;
-        g->scal = scal + (size_t)b * sScal;
+        g->scal = L.scal + (size_t)b * L.sScal;
         g->info = (int*)(g->scal + 2);
+        if (sp.gibbs) {
+            g->lamX = L.extra + (size_t)b * L.sExtra;
+            g->ampX = g->lamX + (size_t)d * Np;
+            g->noiseX = g->ampX + Np;
+        }
         g->host_res = (double*)st->host_block + (size_t)b * hstride;
         g->host_res_dev = host_dev + (size_t)b * hstride;
         g->host_par = g->host_res + 64;
-        g->has_mean = mean_X != nullptr;
-        g->amp2 = h_hyp[2 * b];
+        g->has_mean = sp.mean_X != nullptr;
         // (its two events are created by the member's first update — gp_update_enqueue —: 1024 event creations per 512-member fit
         // were a good part of what the call cost beyond its batched factorisation)
         if (any_disc) {
-            g->discrete.assign(discrete, discrete + d);
+            g->discrete.assign(sp.discrete, sp.discrete + d);
             if (dev_malloc((void**)&g->discrete_dev, d) != hipSuccess) return bail(BOSS_E_ALLOC, "device allocation failed");
-            (void)hipMemcpy(g->discrete_dev, discrete, d, hipMemcpyHostToDevice);
+            (void)hipMemcpy(g->discrete_dev, sp.discrete, d, hipMemcpyHostToDevice);
         }
-        for (int k = 0; k < d; ++k) g->host_par[k] = h_invlam[(size_t)b * d + k];
-        g->host_par[d] = h_hyp[2 * b];
-        g->host_par[d + 1] = h_hyp[2 * b + 1];
+        const bool valid = member(b, g);
         const double logdet = h_scal[2 * b], zz = h_scal[2 * b + 1];
         double ll;
-        const int stt = batch_set_result(N, valid[b], h_info[b], logdet, zz, &ll);   // (BOSS_E_NOT_PD: PosDefException of this sample's cholesky)
+        const int stt = batch_set_result(N, valid, h_info[b], logdet, zz, &ll);   // (BOSS_E_NOT_PD: PosDefException of this sample's cholesky)
         g->host_res[0] = logdet;
         g->host_res[1] = zz;
         g->fitted = stt == BOSS_OK;
@@ -693,4 +716,180 @@ extern "C" int boss_gp_fit_batch(int device, int kernel, int d, int N, const dou
     st->refs.store(S);
     for (int b = 0; b < S; ++b) out[b] = hs[b];
     return BOSS_OK;
+}
+
+extern "C" int boss_gp_fit_batch(int device, int kernel, int d, int N, const double* X, const double* y, const double* mean_X,
+                                 int mean_stride, const unsigned char* discrete, int S, const double* lengthscales,
+                                 const double* amplitudes, const double* noise_stds, boss_gp_t** out, double* logpdf_out,
+                                 int* status_out) {
+    if (!out) return fail(BOSS_E_INVALID, "out is NULL");
+    for (int b = 0; b < S; ++b) out[b] = nullptr;
+    if (kernel < 0 || kernel > 2) return fail(BOSS_E_INVALID, "unknown kernel id");
+    if (d < 1 || N < 1 || S < 1 || !X || !y) return fail(BOSS_E_INVALID, "need d >= 1, N >= 1, S >= 1 and non-NULL X, y");
+    if (N > MAX_ROWS) return fail(BOSS_E_INVALID, "more than 46080 observations are not supported");
+    if (!lengthscales || !amplitudes || !noise_stds) return fail(BOSS_E_INVALID, "NULL hyper-parameter array");
+    if (mean_X && mean_stride != 0 && mean_stride != N) return fail(BOSS_E_INVALID, "mean_stride must be 0 or N");
+    Ctx* c;
+    int rc = get_ctx(device, &c);
+    if (rc) return rc;
+    const int Np = round_up(N, PRED_RB);
+    const bool small = small_fit_ok(c, N, d);
+    std::vector<double> buf, yb(Np, 0.0), h_invlam((size_t)d * S), h_hyp(2 * (size_t)S);
+    std::vector<int> valid(S);
+    pack_points(buf, X, d, N, Np, discrete);
+    std::copy(y, y + N, yb.begin());
+    for (int b = 0; b < S; ++b)   // (a failed set is reported, the others are built)
+        valid[b] = stage_hyper(d, lengthscales + (size_t)b * d, amplitudes[b], noise_stds[b], &h_invlam[(size_t)b * d], &h_hyp[2 * b]);
+    FitBatchSpec sp;
+    sp.kernel = kernel;
+    sp.d = d;
+    sp.N = sp.npts = N;
+    sp.ldx = Np;
+    sp.S = S;
+    sp.zero_slab = small;
+    sp.pts = &buf;
+    sp.yb = &yb;
+    sp.mean_X = mean_X;
+    sp.mean_stride = mean_stride;
+    sp.discrete = discrete;
+    sp.compact_extra = (size_t)S * (d + 2);                  // 1/λ | {α², σ²} of the batch kernels
+    auto factor = [&](FitBatchSlab& L, hipStream_t s) {
+        double* invlamB = L.cextra;
+        double* hypB = invlamB + (size_t)S * d;
+        hipError_t e = hipMemcpyAsync(invlamB, h_invlam.data(), sizeof(double) * d * S, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(hypB, h_hyp.data(), sizeof(double) * 2 * S, hipMemcpyHostToDevice, s);
+        if (e != hipSuccess) return e;
+        if (small)
+            hipLaunchKernelGGL(small_fit_batch_kernel, dim3(S), dim3(DIAG_THREADS), SMALL_LDS_BYTES, s, d, N, Np, L.ld, kernel,
+                               (const double*)invlamB, (const double*)hypB, (const double*)L.pts, L.Xsc, L.sX, (const double*)L.y,
+                               (const double*)L.mean, L.sMean, L.A, L.sA, L.inv16, L.sInv, L.scalB, L.infoB);
+        else
+            batch_factor_enqueue(c, kernel, d, N, Np, S, L.pts, L.y, (const double*)L.mean, L.sMean, invlamB, hypB, L.Xsc, L.sX, L.A, L.ld,
+                                 L.sA, L.inv16, L.sInv, L.scalB, L.infoB);
+        L.scatter_invlam = invlamB;
+        L.scatter_hyp = hypB;
+        return hipSuccess;
+    };
+    auto member = [&](int b, boss_gp* g) {
+        g->amp2 = h_hyp[2 * b];
+        for (int k = 0; k < d; ++k) g->host_par[k] = h_invlam[(size_t)b * d + k];
+        g->host_par[d] = h_hyp[2 * b];
+        g->host_par[d + 1] = h_hyp[2 * b + 1];
+        return valid[b] != 0;
+    };
+    return fit_batch_run(c, sp, factor, member, out, logpdf_out, status_out);
+}
+
+// boss_ggp_fit_batch: the S posteriors of a GradientGaussianProcess under S parameter sets (arguments as boss_ggp_loglike_batch) as
+// resident handles out of one batched factorisation — gradient_gp.jl:307-329 once per sample of a Bayesian-inference fit.
+extern "C" int boss_ggp_fit_batch(int device, int kernel, int d, int n, const double* X, const double* y, const double* dY, int S,
+                                  const double* lengthscales, const double* amplitudes, const double* noise_stds,
+                                  const double* grad_noise_stds, boss_gp_t** out, double* logpdf_out, int* status_out) {
+    if (!out) return fail(BOSS_E_INVALID, "out is NULL");
+    for (int b = 0; b < S; ++b) out[b] = nullptr;
+    if (kernel < 0 || kernel > 2) return fail(BOSS_E_INVALID, "unknown kernel id");
+    if (d < 1 || n < 1 || S < 1 || !X || !y || !dY) return fail(BOSS_E_INVALID, "need d >= 1, n >= 1, S >= 1 and non-NULL X, y, dY");
+    if (d > AUG_MAX_D) return fail(BOSS_E_INVALID, "gradient observations: x_dim above 16 is not supported");
+    if ((long long)n * (1 + d) > MAX_ROWS) return fail(BOSS_E_INVALID, "augmented system too large (n (1 + d) > 46080)");
+    if (!lengthscales || !amplitudes || !noise_stds || !grad_noise_stds) return fail(BOSS_E_INVALID, "NULL hyper-parameter array");
+    Ctx* c;
+    int rc = get_ctx(device, &c);
+    if (rc) return rc;
+    const int N = n * (1 + d), Np = round_up(N, PRED_RB), ldx = round_up(n, 64);
+    std::vector<double> pts, yb(Np, 0.0);
+    pack_points(pts, X, d, n, ldx, nullptr);
+    for (int j = 0; j < n; ++j) {                            // `_build_obs_vector` (gradient_gp.jl:288-302), built once for all sets
+        yb[j] = y[j];
+        for (int l = 0; l < d; ++l) yb[(size_t)n * (1 + l) + j] = dY[(size_t)j * d + l];
+    }
+    FitBatchSpec sp;
+    sp.kernel = kernel;
+    sp.d = d;
+    sp.N = N;
+    sp.npts = n;
+    sp.ldx = ldx;
+    sp.S = S;
+    sp.aug = true;
+    sp.pts = &pts;
+    sp.yb = &yb;
+    std::vector<double> h_par;
+    std::vector<int> valid(S);
+    auto factor = [&](FitBatchSlab& L, hipStream_t s) {
+        h_par.assign(L.sPar * S, 0.0);                       // the members' own blocks, uploaded in place
+        for (int b = 0; b < S; ++b)
+            valid[b] = ggp_stage_set(d, lengthscales + (size_t)b * d, amplitudes[b], noise_stds[b], grad_noise_stds[b], &h_par[(size_t)b * L.sPar]);
+        hipError_t e = hipMemcpyAsync(L.par, h_par.data(), sizeof(double) * L.sPar * S, hipMemcpyHostToDevice, s);
+        if (e != hipSuccess) return e;
+        batch_middle_enqueue(c, N, Np, S, L.y, nullptr, 0, L.A, L.ld, L.sA, L.inv16, L.sInv, L.scalB, L.infoB, BatchStage(),
+                             [&](int b0, int cnt) {
+                                 ProfScope ps(c, "gram");
+                                 const long long t64 = Np / 64;
+                                 hipLaunchKernelGGL(aug_gram_kernel, dim3((unsigned)(t64 * (t64 + 1) / 2), 1, cnt), dim3(256), 0, c->stream,
+                                                    (const double*)L.pts, ldx, d, n, N, Np, kernel, (const double*)(L.par + (size_t)b0 * L.sPar + d),
+                                                    (const double*)(L.par + (size_t)b0 * L.sPar), L.sPar, L.A + (size_t)b0 * L.sA, L.ld, L.sA);
+                             });
+        return hipSuccess;
+    };
+    auto member = [&](int b, boss_gp* g) {
+        const double* p = &h_par[(size_t)b * round_up(d + 4, 8)];
+        for (int k = 0; k < d + 3; ++k) g->host_par[k] = p[k];
+        g->amp2 = p[d];
+        return valid[b] != 0;
+    };
+    return fit_batch_run(c, sp, factor, member, out, logpdf_out, status_out);
+}
+
+// boss_ngp_fit_batch: the S posteriors of a NonstationaryGP under S sets of latent values (arguments as boss_ngp_loglike_batch) as
+// resident handles out of one batched factorisation; every member keeps its λ(X), α(X), σ(X) in the slab.
+extern "C" int boss_ngp_fit_batch(int device, int d, int N, const double* X, const double* y, const unsigned char* discrete, int S,
+                                  const double* lam_X, const double* amp_X, const double* noise_X, const double* mean_X,
+                                  int mean_stride, boss_gp_t** out, double* logpdf_out, int* status_out) {
+    if (!out) return fail(BOSS_E_INVALID, "out is NULL");
+    for (int b = 0; b < S; ++b) out[b] = nullptr;
+    if (d < 1 || N < 1 || S < 1 || !X || !y) return fail(BOSS_E_INVALID, "need d >= 1, N >= 1, S >= 1 and non-NULL X, y");
+    if (N > MAX_ROWS) return fail(BOSS_E_INVALID, "more than 46080 observations are not supported");
+    if (!lam_X || !amp_X || !noise_X) return fail(BOSS_E_INVALID, "NULL latent-value array");
+    if (mean_X && mean_stride != 0 && mean_stride != N) return fail(BOSS_E_INVALID, "mean_stride must be 0 or N");
+    Ctx* c;
+    int rc = get_ctx(device, &c);
+    if (rc) return rc;
+    const int Np = round_up(N, PRED_RB);
+    std::vector<double> pts, yb(Np, 0.0);
+    pack_points(pts, X, d, N, Np, discrete);
+    std::copy(y, y + N, yb.begin());
+    FitBatchSpec sp;
+    sp.kernel = KERN_GIBBS;
+    sp.d = d;
+    sp.N = sp.npts = N;
+    sp.ldx = Np;
+    sp.S = S;
+    sp.gibbs = true;
+    sp.pts = &pts;
+    sp.yb = &yb;
+    sp.mean_X = mean_X;
+    sp.mean_stride = mean_stride;
+    sp.discrete = discrete;
+    sp.sExtra = ((size_t)d + 2) * Np;
+    std::vector<double> h_par;
+    std::vector<int> valid(S);
+    auto factor = [&](FitBatchSlab& L, hipStream_t s) {
+        h_par.resize(L.sExtra * S);
+        for (int b = 0; b < S; ++b)
+            valid[b] = ngp_stage_set(d, N, Np, lam_X + (size_t)b * d * N, amp_X + (size_t)b * N, noise_X + (size_t)b * N, &h_par[(size_t)b * L.sExtra]);
+        hipError_t e = hipMemcpyAsync(L.extra, h_par.data(), sizeof(double) * L.sExtra * S, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemsetAsync(L.par, 0, sizeof(double) * L.sPar * S, s);   // (a nonstationary handle has no scalar parameters)
+        if (e != hipSuccess) return e;
+        batch_middle_enqueue(c, N, Np, S, L.y, (const double*)L.mean, L.sMean, L.A, L.ld, L.sA, L.inv16, L.sInv, L.scalB, L.infoB, BatchStage(),
+                             [&](int b0, int cnt) {
+                                 ProfScope ps(c, "gram");
+                                 const int t64 = Np / 64;
+                                 const double* par = L.extra + (size_t)b0 * L.sExtra;
+                                 hipLaunchKernelGGL(gibbs_gram_kernel, dim3(t64 * (t64 + 1) / 2, 1, cnt), dim3(256), 0, c->stream, (const double*)L.pts,
+                                                    par, par + (size_t)d * Np, par + (size_t)(d + 1) * Np, L.sExtra, L.sExtra, d, N, Np,
+                                                    L.A + (size_t)b0 * L.sA, L.ld, L.sA);
+                             });
+        return hipSuccess;
+    };
+    auto member = [&](int b, boss_gp*) { return valid[b] != 0; };
+    return fit_batch_run(c, sp, factor, member, out, logpdf_out, status_out);
 }

@@ -623,6 +623,7 @@ static void gp_release(boss_gp* g) {
             delete st;
         }
         g->Xraw = g->Xsc = g->y = g->mean = g->A = g->inv16 = g->Dinv = g->Dinv2 = g->invlam = g->scal = nullptr;
+        g->lamX = g->ampX = g->noiseX = nullptr;
         g->host_res = g->host_par = nullptr;
         g->set = nullptr;
     }
@@ -1223,6 +1224,7 @@ extern "C" int boss_ggp_update(boss_gp_t* g, const double* lengthscale, double a
     std::lock_guard<std::mutex> lk(c->mtx);
     hipStream_t s = c->stream;
     gp_invalidate(g);
+    if (!g->par_ev) HIPCHK(hipEventCreateWithFlags(&g->par_ev, hipEventDisableTiming));   // (a member of a batch-fitted set: its first update)
     HIPCHK(hipEventSynchronize(g->par_ev));
     double* invlam = g->host_par;
     double* hyp = g->host_par + g->d;

@@ -429,23 +429,32 @@ static int set_np_max() {
     static const int v = getenv("BOSS_SET_NP_MAX") ? atoi(getenv("BOSS_SET_NP_MAX")) : 2048;
     return v;
 }
-// may the n posteriors be predicted by one launch?  (plain stationary models of one shape on the candidates' device, fused 32-candidate kernel)
-static bool predict_set_ok(int n, boss_gp_t* const* gps, const boss_cand* cd) {
+// may the n posteriors be predicted by one launch?  (models of one kind and shape on the candidates' device, fused 32-candidate
+// kernel: plain stationary models; gradient-observation models of one point count — the members of boss_ggp_fit_batch calls on the
+// outputs of a model —; and, where the caller brings the latent values at the candidates (with_latents, boss_ngp_predict_set),
+// nonstationary models)
+static bool predict_set_ok(int n, boss_gp_t* const* gps, const boss_cand* cd, bool with_latents = false) {
     if (n < 2) return false;
     const boss_gp* g0 = gps[0];
-    if (g0->Np > set_np_max() || g0->ctx->prof_on || g0->d > 64) return false;
+    if (!g0 || g0->Np > set_np_max() || g0->ctx->prof_on || g0->d > 64) return false;
+    if (g0->gibbs && (!with_latents || g0->d > GIBBS_KSTAR_MAX_D)) return false;
+    const bool model = g0->aug || g0->gibbs;                 // K* comes from the members' raw points: one layout for all
     for (int i = 0; i < n; ++i) {
         const boss_gp* g = gps[i];
-        if (!g || g->aug || g->gibbs || !g->fitted || g->pending || g->ctx != cd->ctx || g->N != g0->N || g->Np != g0->Np || g->ld != g0->ld ||
-            g->d != g0->d || g->d != cd->d || g->kernel != g0->kernel || g->discrete != g0->discrete)
+        if (!g || g->aug != g0->aug || g->gibbs != g0->gibbs || !g->fitted || g->pending || g->ctx != cd->ctx || g->N != g0->N || g->Np != g0->Np ||
+            g->ld != g0->ld || g->d != g0->d || g->d != cd->d || g->kernel != g0->kernel || g->discrete != g0->discrete)
             return false;
+        if (model && (g->npts != g0->npts || g->ldx != g0->ldx)) return false;
     }
     return true;
 }
 // moments of posteriors gps[0..n-1] at resident candidates: mu/var of posterior i at mu_all + i·mstride (unclipped); mean_all (or
 // null): prior means at the candidates in the same layout.  Caller holds the context lock and has checked predict_set_ok.
+// Gradient-observation and nonstationary members: K* of every member goes into its V slabs first (aug_kstar_set_kernel /
+// gibbs_kstar_set_kernel), the substitution takes it from there (predict_kernel_set<G, true>); clam_all / camp_all are the
+// nonstationary members' latent values at the candidates, [n][d][Mp] and [n][Mp].
 static int predict_set_enqueue(int n, boss_gp_t* const* gps, const boss_cand* cd, const double* mean_all, double* mu_all,
-                               double* var_all, size_t mstride) {
+                               double* var_all, size_t mstride, const double* clam_all = nullptr, const double* camp_all = nullptr) {
     boss_gp* g0 = gps[0];
     Ctx* c = g0->ctx;
     hipStream_t s = c->stream;
@@ -492,7 +501,8 @@ static int predict_set_enqueue(int n, boss_gp_t* const* gps, const boss_cand* cd
         rc = ws_reserve(c->vscratch, v_one * group);
     }
     if (rc) return rc;
-    rc = ws_reserve(c->csc, sizeof(double) * (size_t)d * Mp * n);
+    const bool pre = g0->aug || g0->gibbs;
+    if (!pre) rc = ws_reserve(c->csc, sizeof(double) * (size_t)d * Mp * n);
     if (rc) return rc;
     rc = ws_reserve(c->setdesc, sizeof(PredSet) * (size_t)n);
     if (rc) return rc;
@@ -502,12 +512,19 @@ static int predict_set_enqueue(int n, boss_gp_t* const* gps, const boss_cand* cd
         desc[i].A = g->A;
         desc[i].Dinv = g->Dinv2;
         desc[i].Xsc = g->Xsc;
-        desc[i].Csc = (const double*)c->csc.p + (size_t)i * d * Mp;
+        desc[i].Csc = pre ? nullptr : (const double*)c->csc.p + (size_t)i * d * Mp;
         desc[i].mean_s = mean_all ? mean_all + (size_t)i * mstride : nullptr;
         desc[i].invlam = g->invlam;
         desc[i].mu = mu_all + (size_t)i * mstride;
         desc[i].var = var_all + (size_t)i * mstride;
         desc[i].amp2 = g->amp2;
+        desc[i].Xraw = pre ? g->Xraw : nullptr;
+        if (g->gibbs) {
+            desc[i].lamX = g->lamX;
+            desc[i].ampX = g->ampX;
+            desc[i].clam = clam_all + (size_t)i * d * Mp;
+            desc[i].camp = camp_all + (size_t)i * Mp;
+        }
     }
     const size_t bytes = sizeof(PredSet) * (size_t)n;
     if (bytes <= PINNED_UP_BYTES) {
@@ -521,13 +538,29 @@ static int predict_set_enqueue(int n, boss_gp_t* const* gps, const boss_cand* cd
         HIPCHK(hipStreamSynchronize(s));
     }
     const PredSet* dsets = (const PredSet*)c->setdesc.p;
-    for (int i0 = 0; i0 < n; i0 += 65535)
-        hipLaunchKernelGGL(scale_cand_set_kernel, dim3((Mp + 255) / 256, std::min(65535, n - i0)), dim3(256), 0, s, (const double*)cd->Craw,
-                           dsets + i0, (const unsigned char*)g0->discrete_dev, d, Mp);
+    if (!pre)
+        for (int i0 = 0; i0 < n; i0 += 65535)
+            hipLaunchKernelGGL(scale_cand_set_kernel, dim3((Mp + 255) / 256, std::min(65535, n - i0)), dim3(256), 0, s, (const double*)cd->Craw,
+                               dsets + i0, (const unsigned char*)g0->discrete_dev, d, Mp);
     for (int i0 = 0; i0 < n; i0 += group) {
         const int cnt = std::min(group, n - i0);
-        hipLaunchKernelGGL(predict_kernel_set<G>, dim3(tiles, cnt), dim3(G::NTHREADS), PredictLds<G>::BYTES, s, dsets + i0, g0->ld, Np, g0->N, d,
-                           Mp, g0->kernel, (double*)c->vscratch.p, cd->M);
+        ++c->set_launches;
+        if (!pre) {
+            hipLaunchKernelGGL(predict_kernel_set<G>, dim3(tiles, cnt), dim3(G::NTHREADS), PredictLds<G>::BYTES, s, dsets + i0, g0->ld, Np, g0->N, d,
+                               Mp, g0->kernel, (double*)c->vscratch.p, cd->M);
+            continue;
+        }
+        ++c->set_pre_launches;
+        if (g0->aug)
+            hipLaunchKernelGGL(aug_kstar_set_kernel, dim3(Np / 256, tiles, cnt), dim3(256), sizeof(double) * ((size_t)d * (G::BN + 256) + d), s,
+                               g0->ldx, d, g0->npts, g0->N, Np, (const double*)cd->Craw, Mp, g0->kernel, dsets + i0,
+                               (double*)c->vscratch.p, (int)G::BN);
+        else
+            hipLaunchKernelGGL(gibbs_kstar_set_kernel, dim3(Np / 256, tiles, cnt), dim3(256), sizeof(double) * (2 * d * 32 + 32 + 2 * 8 * 256), s,
+                               d, g0->N, Np, (const double*)cd->Craw, Mp, dsets + i0, (double*)c->vscratch.p);
+        hipLaunchKernelGGL((predict_kernel_set<G, true>), dim3(tiles, cnt), dim3(G::NTHREADS), PredictLds<G>::BYTES, s, dsets + i0, g0->ld, Np,
+                           g0->N, d, Mp, g0->kernel, (double*)c->vscratch.p, cd->M);
+        if (g0->gibbs) hipLaunchKernelGGL(gibbs_var_set_kernel, dim3((cd->M + 255) / 256, cnt), dim3(256), 0, s, dsets + i0, cd->M);
     }
     HIPCHK(hipGetLastError());
     return BOSS_OK;
@@ -721,6 +754,82 @@ extern "C" int boss_ngp_predict(boss_gp_t* g, int M, const double* Xs, const dou
     rc = finish(c, {{mu, dmu, sizeof(double) * M}, {var, dvar, sizeof(double) * M}, {&bad, dbad, sizeof bad}});
     if (rc) return rc;
     return bad != ~0ULL ? neg_var_error(bad_index, bad, var[bad]) : BOSS_OK;
+}
+
+// mean_and_var of n NonstationaryGP posteriors at the same M candidates in one call — the posteriors of the S samples of a
+// Bayesian-inference fit (src/posterior.jl:15-19), each with its own latent models: lam_Xs d×M×n, amp_Xs M×n, mean_Xs null or M×n
+// (member after member); mu, var [n][M].  Equally shaped handles (the members of a boss_ngp_fit_batch) take the one-launch set
+// prediction; any other list of nonstationary handles is predicted member by member inside the same call.  The variances are clipped as boss_ngp_predict clips
+// them; the first member with a variance below the threshold fails the call with BOSS_E_NEG_VAR, bad_index_out = the candidate.
+extern "C" int boss_ngp_predict_set(int n, boss_gp_t* const* gps, int M, const double* Xs, const double* lam_Xs, const double* amp_Xs,
+                                    const double* mean_Xs, double* mu, double* var, long* bad_index_out) {
+    if (n < 1 || !gps || !Xs || !lam_Xs || !amp_Xs || !mu || !var) return fail(BOSS_E_INVALID, "NULL argument or n < 1");
+    if (M < 1) return fail(BOSS_E_INVALID, "M must be >= 1");
+    if ((long long)n * M > (1LL << 30)) return fail(BOSS_E_INVALID, "n·M above 2^30 is not supported");
+    if (bad_index_out) *bad_index_out = -1;
+    for (int i = 0; i < n; ++i) {
+        if (!gps[i]) return fail(BOSS_E_INVALID, "NULL posterior handle");
+        if (!gps[i]->gibbs) return fail(BOSS_E_INVALID, "handle was not created by boss_ngp_create / boss_ngp_fit_batch");
+        if (gps[i]->ctx != gps[0]->ctx || gps[i]->d != gps[0]->d) return fail(BOSS_E_INVALID, "all handles must live on one device and share x_dim");
+        if (gps[i]->discrete != gps[0]->discrete) return fail(BOSS_E_INVALID, "all handles must round the same dimensions");
+        if (!gps[i]->fitted) return fail(BOSS_E_NOT_FITTED, "handle has no valid factorisation");
+    }
+    boss_gp* g0 = gps[0];
+    const int d = g0->d, Mp = round_up(M, 64);
+    std::vector<NgpCand> pk(n);
+    for (int i = 0; i < n; ++i) {
+        int rc = ngp_pack(g0, M, Xs, lam_Xs + (size_t)i * d * M, amp_Xs + (size_t)i * M, pk[i]);
+        if (rc) return rc;
+    }
+    Ctx* c = g0->ctx;
+    HIPCHK(hipSetDevice(c->device));
+    std::lock_guard<std::mutex> lk(c->mtx);
+    hipStream_t s = c->stream;
+    for (int i = 0; i < n; ++i) {
+        int rc = gp_settle(gps[i]);
+        if (rc) return rc;
+    }
+    // candidates | λ(x*) of every member | α(x*) of every member;  outputs mu | var | bad, prior means behind them
+    const size_t nm = (size_t)n * M;
+    int rc = ws_reserve(c->craw, sizeof(double) * ((size_t)d * Mp + (size_t)n * ((size_t)d * Mp + Mp)));
+    if (rc) return rc;
+    rc = ws_reserve(c->pred, sizeof(double) * (3 * nm + 2));
+    if (rc) return rc;
+    boss_cand cd;
+    cd.ctx = c;
+    cd.d = d;
+    cd.M = M;
+    cd.Mp = Mp;
+    cd.Craw = (double*)c->craw.p;
+    double* clam = cd.Craw + (size_t)d * Mp;
+    double* camp = clam + (size_t)n * d * Mp;
+    double* dev = (double*)c->pred.p;
+    double *dmu = dev, *dvar = dev + nm, *dmean = dev + 2 * nm + 1;
+    unsigned long long* dbad = (unsigned long long*)(dev + 2 * nm);
+    HIPCHK(hipMemcpyAsync(cd.Craw, pk[0].x.data(), sizeof(double) * d * Mp, hipMemcpyHostToDevice, s));
+    for (int i = 0; i < n; ++i) {
+        HIPCHK(hipMemcpyAsync(clam + (size_t)i * d * Mp, pk[i].lam.data(), sizeof(double) * d * Mp, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(camp + (size_t)i * Mp, pk[i].amp.data(), sizeof(double) * Mp, hipMemcpyHostToDevice, s));
+    }
+    if (mean_Xs) (void)hipMemcpyAsync(dmean, mean_Xs, sizeof(double) * nm, hipMemcpyHostToDevice, s);
+    (void)hipMemsetAsync(dbad, 0xff, sizeof(unsigned long long), s);
+    static const bool set_off = getenv("BOSS_NO_SET_PREDICT") && atoi(getenv("BOSS_NO_SET_PREDICT"));
+    if (!set_off && predict_set_ok(n, gps, &cd, true)) {
+        rc = predict_set_enqueue(n, gps, &cd, mean_Xs ? dmean : nullptr, dmu, dvar, (size_t)M, clam, camp);
+        if (rc) return drain(c, rc);
+    } else {
+        for (int i = 0; i < n; ++i) {
+            rc = predict_enqueue(gps[i], &cd, mean_Xs ? dmean + (size_t)i * M : nullptr, dmu + (size_t)i * M, dvar + (size_t)i * M, false,
+                                 clam + (size_t)i * d * Mp, camp + (size_t)i * Mp);
+            if (rc) return drain(c, rc);
+        }
+    }
+    // (member after member in one array: the smallest flat index is the first member's first offender)
+    hipLaunchKernelGGL(clip_var_kernel, dim3((unsigned)((nm + 255) / 256)), dim3(256), 0, s, dvar, (int)nm, dbad);
+    unsigned long long bad = 0;
+    rc = finish(c, {{mu, dmu, sizeof(double) * nm}, {var, dvar, sizeof(double) * nm}, {&bad, dbad, sizeof bad}});
+    if (rc) return rc;
+    return bad != ~0ULL ? neg_var_error(bad_index_out, bad % (unsigned long long)M, var[bad]) : BOSS_OK;
 }
 
 // EI parameters: by value in the kernel arguments for P <= EI_MAXP, else in device arrays.

@@ -243,13 +243,44 @@ struct PredSet {
     double* mu;
     double* var;
     double amp2;
+    const double* Xraw;       // gradient-observation / nonstationary members: the raw points K* is evaluated from (null otherwise)
+    // nonstationary members only (null otherwise): λ(X) [d][Np], α(X) [Np] of this posterior and its latent values at the candidates
+    const double* lamX;
+    const double* ampX;
+    const double* clam;       // λ(x*) [d][Mp]
+    const double* camp;       // α(x*) [Mp]
 };
-template <class G>
+// PRE: the members' K* tiles lie in their V slabs already (aug_kstar_set_kernel / gibbs_kstar_set_kernel, same slab indexing)
+template <class G, bool PRE = false>
 __global__ __launch_bounds__(G::NTHREADS) __attribute__((amdgpu_waves_per_eu(1, 1))) void predict_kernel_set(const PredSet* __restrict__ sets, int ld, int Np, int N,
                                                       int d, int Mp, int kern, double* __restrict__ Vscratch, int M) {
     const PredSet ps = sets[blockIdx.y];                     // (uniform: scalar loads)
-    predict_body<G, false>(ps.A, ld, Np, N, ps.Dinv, ps.Xsc, ps.Csc, d, Mp, kern, ps.amp2,
-                           Vscratch + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * Np * G::BN, ps.mean_s, M, ps.mu, ps.var, 0, (int)blockIdx.x);
+    predict_body<G, PRE>(ps.A, ld, Np, N, ps.Dinv, ps.Xsc, ps.Csc, d, Mp, kern, ps.amp2,
+                         Vscratch + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * Np * G::BN, ps.mean_s, M, ps.mu, ps.var, 0, (int)blockIdx.x);
+}
+
+// K* of a SET of equally shaped gradient-observation / nonstationary posteriors, written into the V slabs predict_kernel_set<G, true>
+// reads: grid = (256-row blocks, candidate tiles, posteriors).  The candidates are shared; the points (the members of one fit share
+// them, the outputs of a model each bring their own copy), 1/λ and α² (gradient model), λ(X), α(X) and the latent values at the
+// candidates (nonstationary model) come from the member's descriptor.
+__global__ __launch_bounds__(256) void aug_kstar_set_kernel(int ldx, int d, int n, int N, int Np,
+                                                            const double* __restrict__ Craw, int Mp, int kern,
+                                                            const PredSet* __restrict__ sets, double* __restrict__ Vscratch, int BN) {
+    const PredSet ps = sets[blockIdx.z];
+    aug_kstar_body(ps.Xraw, ldx, d, n, N, Np, Craw, Mp, kern, ps.amp2, ps.invlam,
+                   Vscratch + ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * Np * BN, BN, (int)blockIdx.y);
+}
+__global__ __launch_bounds__(256) void gibbs_kstar_set_kernel(int d, int N, int Np, const double* __restrict__ C, int Mp,
+                                                              const PredSet* __restrict__ sets, double* __restrict__ Vscratch) {
+    const PredSet ps = sets[blockIdx.z];
+    gibbs_kstar_cols_body(ps.Xraw, ps.lamX, ps.ampX, d, N, Np, C, ps.clam, ps.camp, Mp,
+                          Vscratch + ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * Np * 32, (int)blockIdx.y);
+}
+// gibbs_var_kernel for the set: grid.y = posterior
+__global__ void gibbs_var_set_kernel(const PredSet* __restrict__ sets, int M) {
+    const PredSet ps = sets[blockIdx.y];
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < M) ps.var[j] = __builtin_fma(ps.camp[j], ps.camp[j], ps.var[j]) + PREDICT_JITTER;
 }
 
 // ------------------------------------------------------------------------------------------

@@ -225,5 +225,44 @@ class HipGradientGaussianProcess:
 
     def model_posterior(self, params, data: GradientData):
         if isinstance(params, (list, tuple)):
-            return [self.model_posterior(p, data) for p in params]
+            return self.model_posterior_batch(list(params), data)
         return HipGaussianProcessPosterior([self.model_posterior_slice(params, data, i) for i in range(data.Y.shape[0])])
+
+    def model_posterior_batch(self, samples: Sequence[HipGradientGPParams], data: GradientData):
+        """`model_posterior.(Ref(model), samples, Ref(data))` (src/posterior.jl:15-19): one posterior per sample of a BI fit, built
+        by ONE boss_ggp_fit_batch call per output (the members share the points and observations and are predicted together by
+        acq_ei).  Few samples of a large system, or a batch that does not fit the device, stay the loop of create + update per sample
+        and output (`batched_call_pays`).  A sample whose matrix is not PD raises PosDefException, as the loop does."""
+        S = len(samples)
+        d, n = data.X.shape
+
+        def loop():
+            return [self.model_posterior(p, data) for p in samples]
+        if S == 0 or not batched_call_pays(n * (1 + d), S):
+            return loop()
+        rows = []                                               # rows[i][s]: handle of output i under sample s
+
+        def close_all():
+            for gps in rows:
+                for g in gps:
+                    g.close()
+        for i in range(data.Y.shape[0]):
+            lam = np.stack([p.lengthscales[:, i] for p in samples], axis=1)
+            amp, sig, sgd = (np.array([getattr(p, name)[i] for p in samples]) for name in ("amplitudes", "noise_std", "grad_noise_std"))
+            try:
+                gps, _, st = api.ggp_fit_batch(data.X, data.Y[i], data.dY[i], self.kernel, lam, amp, sig, sgd, self.device)
+            except api.BossError as e:
+                close_all()
+                if e.code == api.BOSS_E_ALLOC:                  # (a 36 864-row member is 10.9 GB: the loop holds one factor at a time per handle)
+                    return loop()
+                raise
+            rows.append(gps)
+            bad = np.flatnonzero(st != api.BOSS_OK)
+            if bad.size:
+                close_all()
+                s = int(bad[0])
+                if st[s] == api.BOSS_E_NOT_PD:
+                    raise api.PosDefException(api.BOSS_E_NOT_PD, f"sample {s}, output {i}: the augmented matrix is not positive definite")
+                raise api.BossError(int(st[s]), f"sample {s}, output {i}: invalid hyper-parameters")
+        return [HipGaussianProcessPosterior([HipGradientGPPosteriorSlice(self, p, i, rows[i][s]) for i in range(len(rows))])
+                for s, p in enumerate(samples)]

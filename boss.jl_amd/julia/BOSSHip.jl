@@ -743,6 +743,28 @@ function batched_data_loglike(m::HipGradientGaussianProcess, data::BOSS.Gradient
     end
     return ll
 end
+"""
+The posteriors of every parameter sample of `ps` for the gradient-observation model (src/posterior.jl:15-19): ONE
+`boss_ggp_fit_batch` call per output builds the S members as resident handles that share the points and observations;
+`boss_acq_ei` then predicts them in one launch.  Returns posts[s][i] (sample s, output i).
+"""
+function model_posteriors_batched(m::HipGradientGaussianProcess, ps::AbstractVector, data::BOSS.GradientData)
+    X = Matrix{Float64}(data.X); S = length(ps); P = size(data.Y, 1)
+    rows = Vector{Vector{HipPosteriorSlice}}(undef, P)
+    for i in 1:P
+        dY = ndims(data.dY) == 3 ? Matrix{Float64}(data.dY[i, :, :]) : Matrix{Float64}(data.dY)     # x_dim × n
+        λ = Matrix{Float64}(reduce(hcat, (p.λ[:, i] for p in ps))); ll = zeros(S); st = zeros(Cint, S); hs = Vector{Ptr{Cvoid}}(undef, S)
+        α = Float64[p.α[i] for p in ps]; σ = Float64[p.σ[i] for p in ps]; σ∂ = Float64[p.σ_∂[i] for p in ps]
+        check(ccall((:boss_ggp_fit_batch, lib), Cint,
+            (Cint, Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint,
+             Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Ptr{Cvoid}}, Ptr{Cdouble}, Ptr{Cint}),
+            m.device, kernel_id(m.gp.kernel), size(X, 1), size(X, 2), X, Vector{Float64}(data.Y[i, :]), dY, S, λ, α, σ, σ∂, hs, ll, st))
+        rows[i] = [HipPosteriorSlice(Handle(h), nothing, true) for h in hs]
+        bad = findfirst(!=(0), st)
+        isnothing(bad) || (st[bad] == 3 ? throw(PosDefException(bad)) : error("boss_ggp_fit_batch: invalid hyper-parameters in sample $bad"))
+    end
+    return [[rows[i][s] for i in 1:P] for s in 1:S]
+end
 "augment_dataset! (src/types/problem.jl:191-198) for a fitted gradient-observation slice: new points with values and gradients, same hyper-parameters."
 function augment!(post::HipPosteriorSlice, X_new::AbstractMatrix{<:Real}, y_new::AbstractVector{<:Real}, dY_new::AbstractMatrix{<:Real})
     lp = Ref{Cdouble}()
@@ -792,6 +814,50 @@ function batched_data_loglike_slice(model::BOSS.NonstationaryGP, ps::AbstractVec
         device, d, N, X, Vector{Float64}(data.Y[i, :]), isnothing(model.discrete) ? C_NULL : UInt8.(model.discrete), S, Λ, A, Σ,
         mean_vals(BOSS.mean_getindex(model.mean, i), X), 0, ll, st))
     return ll
+end
+"""
+The posteriors of output `i` under every parameter set of `ps` (src/posterior.jl:15-19) out of ONE `boss_ngp_fit_batch` call: the
+latent models of every set are evaluated at the (rounded) data on the host as in `batched_data_loglike_slice`; the members share
+the points and observations and keep their own λ(X), α(X), σ(X).
+"""
+function hip_posterior_slices_batched(model::BOSS.NonstationaryGP, ps::AbstractVector{<:BOSS.NonstationaryGPParams},
+                                      data::BOSS.ExperimentData, i::Int; device = 0)
+    X = Matrix{Float64}(data.X); Xr = rounded(X, model.discrete); d, N = size(X); S = length(ps)
+    Λ = Array{Float64}(undef, d, N, S); A = Matrix{Float64}(undef, N, S); Σ = Matrix{Float64}(undef, N, S); fs = Vector{Any}(undef, S)
+    for (s, p) in enumerate(ps)
+        f_λ = BOSS._param_posterior_slice(model.lengthscale_model, p.λ, data, i)
+        f_α = BOSS._param_posterior_slice(model.amplitude_model, p.α, data, i)
+        f_σ = BOSS._param_posterior_slice(model.noise_std_model, p.σ, data, i)
+        Λ[:, :, s] .= reduce(hcat, f_λ.(eachcol(Xr))); A[:, s] .= f_α.(eachcol(Xr)); Σ[:, s] .= f_σ.(eachcol(X)); fs[s] = (f_λ, f_α, f_σ)
+    end
+    ll = zeros(S); st = zeros(Cint, S); hs = Vector{Ptr{Cvoid}}(undef, S); mu = BOSS.mean_getindex(model.mean, i)
+    check(ccall((:boss_ngp_fit_batch, lib), Cint,
+        (Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{UInt8}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint,
+         Ptr{Ptr{Cvoid}}, Ptr{Cdouble}, Ptr{Cint}),
+        device, d, N, X, Vector{Float64}(data.Y[i, :]), isnothing(model.discrete) ? C_NULL : UInt8.(model.discrete), S, Λ, A, Σ,
+        mean_vals(mu, X), 0, hs, ll, st))
+    posts = [HipNonstationaryPosterior(HipPosteriorSlice(Handle(hs[s]), mu), fs[s][1], fs[s][2], model.discrete, fs[s][3]) for s in 1:S]
+    bad = findfirst(!=(0), st)
+    isnothing(bad) || (st[bad] == 3 ? throw(PosDefException(bad)) : error("boss_ngp_fit_batch: invalid latent values in sample $bad"))
+    return posts, ll
+end
+"""
+mean_and_var of the S sampled posteriors of one output at the same candidates in ONE call (`boss_ngp_predict_set`): every sample's
+latent models are evaluated at the rounded candidates; returns μ, σ² as M × S matrices (column s = sample s) — the moments
+`boss_acq_ei_moments` averages the acquisition over (src/acquisitions/expected_improvement.jl:87-90).
+"""
+function mean_and_var(ps::AbstractVector{HipNonstationaryPosterior}, X::AbstractMatrix{<:Real})
+    Xs = Matrix{Float64}(X); Xr = rounded(Xs, ps[1].discrete); d, M = size(Xs); S = length(ps)
+    Λ = Array{Float64}(undef, d, M, S); A = Matrix{Float64}(undef, M, S); mu = ps[1].post.mean
+    for (s, p) in enumerate(ps)
+        Λ[:, :, s] .= reduce(hcat, p.f_λ.(eachcol(Xr))); A[:, s] .= p.f_α.(eachcol(Xr))
+    end
+    ms = isnothing(mu) ? C_NULL : repeat(Vector{Float64}(mean_vals(mu, Xs)), S)
+    μ = Matrix{Float64}(undef, M, S); σ2 = similar(μ); bad = Ref{Clong}(-1); hs = Ptr{Cvoid}[p.post.h.h for p in ps]
+    GC.@preserve ps check(ccall((:boss_ngp_predict_set, lib), Cint,
+        (Cint, Ptr{Ptr{Cvoid}}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Clong}),
+        S, hs, M, Xs, Λ, A, ms, μ, σ2, bad))
+    return μ, σ2
 end
 """
 Log-likelihood of a fitted nonstationary slice with its partial derivatives w.r.t. the latent models' values at the training points:

@@ -277,12 +277,7 @@ def data_loglike_batch(models: Sequence[HipNonstationaryGP], data: ExperimentDat
     S = len(models)
     if S == 0:
         return np.zeros(0)
-    first = models[0]
-    disc0 = None if first.discrete is None else np.asarray(first.discrete, bool)
-    for m in models[1:]:
-        disc = None if m.discrete is None else np.asarray(m.discrete, bool)
-        if m.device != first.device or (disc is None) != (disc0 is None) or (disc is not None and not np.array_equal(disc, disc0)):
-            raise ValueError("the models of a batch must share `discrete` and `device`")
+    first, disc0 = _check_batch_models(models)
     d, N = data.X.shape
     tot = np.zeros(S)
     for i in range(data.Y.shape[0]):
@@ -298,3 +293,82 @@ def data_loglike_batch(models: Sequence[HipNonstationaryGP], data: ExperimentDat
         tot += np.where(st == api.BOSS_OK, ll, -np.inf)
     return tot
 
+
+def _check_batch_models(models):
+    first = models[0]
+    disc0 = None if first.discrete is None else np.asarray(first.discrete, bool)
+    for m in models[1:]:
+        disc = None if m.discrete is None else np.asarray(m.discrete, bool)
+        if m.device != first.device or (disc is None) != (disc0 is None) or (disc is not None and not np.array_equal(disc, disc0)):
+            raise ValueError("the models of a batch must share `discrete` and `device`")
+    return first, disc0
+
+
+def nonstationary_model_posterior_batch(models: Sequence[HipNonstationaryGP], data: ExperimentData) -> List[List[HipNonstationaryPosteriorSlice]]:
+    """`model_posterior.(samples, Ref(data))` (src/posterior.jl:15-19) for S nonstationary models that differ in their latent closures
+    only (same `discrete`, same `device`): the closures are evaluated at the data as `model_posterior_slice` evaluates them, then ONE
+    boss_ngp_fit_batch call per output builds the S posteriors as resident handles that share the points and observations.  Returns
+    posts[s][i] (sample s, output i).  A sample whose matrix is not PD raises PosDefException, as `model_posterior` does."""
+    models = list(models)
+    S = len(models)
+    if S == 0:
+        return []
+    first, disc0 = _check_batch_models(models)
+    d, N = data.X.shape
+    rows = []
+    for i in range(data.Y.shape[0]):
+        lam = np.empty((d, N, S), order="F")
+        amp = np.empty((N, S), order="F")
+        noi = np.empty((N, S), order="F")
+        means = []
+        for s, m in enumerate(models):
+            lam[:, :, s], amp[:, s], noi[:, s], mu, _ = m._latent_at_data(data.X, i)
+            means.append(mu)
+        mean_X = None if all(mu is None for mu in means) else np.stack([np.zeros(N) if mu is None else mu for mu in means])
+        try:
+            gps, _, st = api.ngp_fit_batch(data.X, data.Y[i], lam, amp, noi, mean_X, disc0, first.device)
+        except Exception:
+            for r in rows:
+                for g in r:
+                    g.close()
+            raise
+        rows.append(gps)
+        bad = np.flatnonzero(st != api.BOSS_OK)
+        if bad.size:
+            for r in rows:
+                for g in r:
+                    g.close()
+            s = int(bad[0])
+            if st[s] == api.BOSS_E_NOT_PD:
+                raise api.PosDefException(api.BOSS_E_NOT_PD, f"sample {s}, output {i}: the matrix is not positive definite")
+            raise api.BossError(int(st[s]), f"sample {s}, output {i}: invalid latent values")
+    return [[HipNonstationaryPosteriorSlice(rows[i][s], m.f_lam[i], m.f_amp[i], None if m.mean is None else m.mean[i], disc0, m.f_noise[i])
+             for i in range(len(rows))] for s, m in enumerate(models)]
+
+
+def nonstationary_acq_ei_batch(posts: Sequence[Sequence[HipNonstationaryPosteriorSlice]], Xs, fit_coefs, y_max=None, best=None,
+                               valid_mask=None):
+    """EI × feasibility averaged over the S sampled posteriors posts[s][i] (src/acquisitions/expected_improvement.jl:87-90) at the
+    candidates Xs d×M: per output ONE boss_ngp_predict_set call (every sample's latent models evaluated at the rounded candidates,
+    all samples in one prediction launch where they come from nonstationary_model_posterior_batch), then boss_acq_ei_moments.
+    Returns (acq[M], argmax, max)."""
+    Xs = np.asarray(Xs, float)
+    if Xs.ndim == 1:
+        Xs = Xs[:, None]
+    S, P = len(posts), len(posts[0])
+    d, M = Xs.shape
+    mu = np.empty((S, P, M))
+    var = np.empty((S, P, M))
+    for i in range(P):
+        sl = [posts[s][i] for s in range(S)]
+        Xr = sl[0]._round(Xs)
+        lam = np.empty((d, M, S), order="F")
+        amp = np.empty((M, S), order="F")
+        means = []
+        for s, p in enumerate(sl):
+            lam[:, :, s] = _cols(p.f_lam, Xr).T
+            amp[:, s] = _cols(p.f_amp, Xr).reshape(-1)
+            means.append(None if p.mean_fn is None else np.array([float(p.mean_fn(Xs[:, j])) for j in range(M)]))
+        ms = None if all(m is None for m in means) else np.stack([np.zeros(M) if m is None else m for m in means])
+        mu[:, i, :], var[:, i, :] = api.ngp_predict_set([p.gp for p in sl], Xs, lam, amp, ms)
+    return api.acq_ei_moments(mu, var, fit_coefs, y_max, best, valid_mask, posts[0][0].gp.device)

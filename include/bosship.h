@@ -201,6 +201,13 @@ int boss_ngp_loglike_grad(boss_gp_t* gp, double* logpdf_out, double* dlam_out, d
                           double* dmean_out);
 int boss_ngp_predict(boss_gp_t* gp, int M, const double* Xs, const double* lam_Xs, const double* amp_Xs,
                      const double* mean_Xs, double* mu, double* var, long* bad_index);
+/* mean_and_var of n nonstationary posteriors at the same M candidates in one call: the posteriors of the samples of a
+ * Bayesian-inference fit (src/posterior.jl:15-19), every one with its own latent models.  lam_Xs d×M×n, amp_Xs M×n, mean_Xs NULL
+ * or M×n (member after member); mu, var n×M (member after member) — the layout boss_acq_ei_moments takes for P = 1.  Equally
+ * shaped handles (the members of a boss_ngp_fit_batch) are predicted in one launch, other lists member by member.  _clip_var as boss_ngp_predict: the first
+ * member with a variance below -1e-8 fails the call with BOSS_E_NEG_VAR, bad_index_out = its first such candidate. */
+int boss_ngp_predict_set(int n, boss_gp_t* const* gps, int M, const double* Xs, const double* lam_Xs, const double* amp_Xs,
+                         const double* mean_Xs, double* mu, double* var, long* bad_index_out);
 /* mean_and_var of a nonstationary posterior AND its gradient w.r.t. the candidates.
  * Replaces: the derivatives ForwardDiff pushes through nonstationary_gp.jl:153-196 inside OptimizationAM
  * (src/acquisition_maximizers/optimization.jl:36,89-118).  The candidate enters the Gibbs kernel directly and through the
@@ -265,6 +272,19 @@ int boss_gp_fit_batch(int device, int kernel, int d, int N, const double* X, con
                       const double* mean_X, int mean_stride, const unsigned char* discrete,
                       int S, const double* lengthscales, const double* amplitudes,
                       const double* noise_stds, boss_gp_t** out, double* logpdf_out, int* status_out);
+/* The same for the gradient-observation model and the nonstationary model: S RESIDENT posteriors out of one batched factorisation.
+ * Replaces: model_posterior per sample of a Bayesian-inference fit (src/posterior.jl:15-19) over gradient_gp.jl:307-329 /
+ * nonstationary_gp.jl:153-196.  Arguments, the +1e-8 rule and the validity checks as boss_ggp_loglike_batch /
+ * boss_ngp_loglike_batch; out, logpdf_out, status_out as boss_gp_fit_batch (S >= 1).  The members are ordinary boss_ggp_* /
+ * boss_ngp_* handles; a nonstationary member keeps its lam_X, amp_X, noise_X.  BOSS_E_ALLOC when the S factors do not fit
+ * (nothing is left behind).  boss_acq_ei walks S > 1 gradient-model members of one fit in one prediction launch; nonstationary
+ * members are predicted together by boss_ngp_predict_set. */
+int boss_ggp_fit_batch(int device, int kernel, int d, int n, const double* X, const double* y, const double* dY,
+                       int S, const double* lengthscales, const double* amplitudes, const double* noise_stds,
+                       const double* grad_noise_stds, boss_gp_t** out, double* logpdf_out, int* status_out);
+int boss_ngp_fit_batch(int device, int d, int N, const double* X, const double* y, const unsigned char* discrete,
+                       int S, const double* lam_X, const double* amp_X, const double* noise_X,
+                       const double* mean_X, int mean_stride, boss_gp_t** out, double* logpdf_out, int* status_out);
 
 /* ---- prediction -------------------------------------------------------------------------
  * Replaces: mean_and_var(post, X::Matrix) (gaussian_process.jl:174-178) =
