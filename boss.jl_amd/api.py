@@ -89,6 +89,8 @@ SIGNATURES = {
                                            C.c_double, _c_ucp, _c_dp, _c_dp]),
     "boss_acq_ei_grad": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.c_int, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, C.c_int,
                                    C.c_double, _c_ucp, _c_dp, _c_dp]),
+    "boss_acq_ei_grad_set": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_int, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, C.c_int,
+                                   C.c_double, _c_ucp, _c_dp, _c_dp]),
     "boss_track_create": (C.c_int, [C.c_void_p, C.c_void_p, _c_dp, C.POINTER(C.c_void_p)]),
     "boss_track_free": (None, [C.c_void_p]),
     "boss_track_sync": (C.c_int, [C.c_void_p]),
@@ -1044,6 +1046,36 @@ def acq_ei_grad(gps: Sequence[GP], Xs, fit_coefs, y_max=None, best=None, valid_m
     return acq, dacq
 
 
+def acq_ei_grad_set(gps: Sequence[Sequence[GP]], Xs, fit_coefs, y_max=None, best=None, valid_mask=None, mean_Xs=None, mean_grad=None):
+    """EI·feas and its gradient w.r.t. the candidates, averaged over S hyper-parameter samples in ONE device call
+    (boss_acq_ei_grad_set).  gps[s][p] = output p of sample s.  mean_Xs: None or [S][P][M]; mean_grad: None or [S][P][d][M].
+    Returns (acq[M], dacq[d, M]) = the means over s of what acq_ei_grad returns for gps[s]."""
+    S = len(gps)
+    P = len(gps[0]) if S else 0
+    if S < 1 or P < 1 or any(len(row) != P for row in gps):
+        raise BossError(BOSS_E_INVALID, "gps must be S rows of P posteriors")
+    Xs = _f64(Xs, 2)
+    d, M = Xs.shape
+    arr = (C.c_void_p * (P * S))()
+    for s in range(S):
+        for p in range(P):
+            arr[p + P * s] = gps[s][p]._h
+    coefs = _f64(np.asarray(fit_coefs).reshape(-1), 1)
+    ym = None if y_max is None else _f64(np.asarray(y_max).reshape(-1), 1)
+    mask = None if valid_mask is None else np.ascontiguousarray(np.asarray(valid_mask, dtype=bool).astype(np.uint8))
+    ms = None if mean_Xs is None else np.ascontiguousarray(np.asarray(mean_Xs, dtype=np.float64).reshape(S, P, M))
+    mg = None
+    if mean_grad is not None:
+        a = np.asarray(mean_grad, dtype=np.float64).reshape(S, P, d, M)
+        mg = np.ascontiguousarray(a.transpose(0, 1, 3, 2))        # [s][p][j*d + m]
+    acq = np.zeros(M)
+    dacq = np.zeros((d, M), order="F")
+    _check(load_library().boss_acq_ei_grad_set(P, S, arr, M, _dp(Xs), _dp(ms), _dp(mg), _dp(coefs), _dp(ym),
+                                               0 if best is None else 1, 0.0 if best is None else float(best), _ucp(mask),
+                                               _dp(acq), _dp(dacq)))
+    return acq, dacq
+
+
 def acq_ei_moments(mu, var, fit_coefs, y_max=None, best=None, valid_mask=None, device: int = 0):
     """EI·feas + arg-max from posterior moments already on the host (outputs fitted on other
     ranks).  mu, var: [S][P][M] (or [P][M] for S = 1).  Returns (acq[M], argmax, max)."""
@@ -1280,3 +1312,15 @@ def _set_launches(device: int = 0):
     a, b = C.c_long(0), C.c_long(0)
     fn(device, C.byref(a), C.byref(b))
     return a.value, b.value
+
+
+def _set_grad_launches(device: int = 0):
+    """Launches of the set adjoint substitution (boss_acq_ei_grad_set's set path) on the device so far
+    (boss_debug_set_grad_launches; tests)."""
+    lib = load_library()
+    fn = lib.boss_debug_set_grad_launches
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_int, C.POINTER(C.c_long)]
+    a = C.c_long(0)
+    fn(device, C.byref(a))
+    return a.value

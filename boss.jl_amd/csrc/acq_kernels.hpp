@@ -156,19 +156,20 @@ __global__ __launch_bounds__(ACQ_EPI_THREADS) void acq_epilogue_kernel(const dou
 //        ∇FP = Σ_p (Π_{q≠p} Φ(t_q)) φ(t_p) ∇t_p ,  ∇t_p = −∇μ_p/s_p − (ymax_p − μ_p) ∇σ²_p / (2 s_p³)
 //   acq = EI·FP (or EI, or FP, or 0 by mode); outside the domain mask: acq = 0, ∇acq = 0 (make_safe).
 // Variances clipped to 0 (or exactly 0) contribute no σ-gradient.
-__global__ void ei_grad_kernel(const double* __restrict__ mu, const double* __restrict__ var, const double* __restrict__ dmu,
-                               const double* __restrict__ dvar, int M, int d, EiPar par,
-                               const double* __restrict__ coefs_dev, const double* __restrict__ ymax_dev,
-                               const unsigned char* __restrict__ mask, double* __restrict__ acq,
-                               double* __restrict__ dacq) {
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= M) return;
+// (ADD: the sample's value and gradient are added to what acq_j / gout hold — the Bayesian-inference sum of ei_grad_set_kernel)
+template <bool ADD>
+__device__ __forceinline__ void ei_grad_point(const double* __restrict__ mu, const double* __restrict__ var, const double* __restrict__ dmu,
+                                              const double* __restrict__ dvar, int M, int d, const EiPar& par,
+                                              const double* __restrict__ coefs_dev, const double* __restrict__ ymax_dev,
+                                              const unsigned char* __restrict__ mask, int j, double* __restrict__ acq_j,
+                                              double* __restrict__ gout) {
     const int P = par.P, mode = par.mode;
     const size_t dm = (size_t)d * M;
-    double* gout = dacq + (size_t)j * d;
     if (mode == 0 || (mask && !mask[j])) {
-        acq[j] = 0.0;
-        for (int m = 0; m < d; ++m) gout[m] = 0.0;
+        if (!ADD) {
+            *acq_j = 0.0;
+            for (int m = 0; m < d; ++m) gout[m] = 0.0;
+        }
         return;
     }
     // pass 1: scalars
@@ -205,7 +206,8 @@ __global__ void ei_grad_kernel(const double* __restrict__ mu, const double* __re
     double a;
     if (mode & 1) a = (mode & 2) ? ei * fp : ei;
     else a = fp;
-    acq[j] = poison ? -INFINITY : a;
+    if (ADD) *acq_j += poison ? -INFINITY : a;
+    else *acq_j = poison ? -INFINITY : a;
     // pass 2: gradient, one coordinate at a time
     for (int m = 0; m < d; ++m) {
         double dmuf = 0.0, dvf = 0.0, dfp = 0.0;
@@ -242,8 +244,37 @@ __global__ void ei_grad_kernel(const double* __restrict__ mu, const double* __re
         double gA;
         if (mode & 1) gA = (mode & 2) ? dei * fp + ei * dfp : dei;
         else gA = dfp;
-        gout[m] = poison ? 0.0 : gA;
+        if (ADD) gout[m] += poison ? 0.0 : gA;
+        else gout[m] = poison ? 0.0 : gA;
     }
+}
+__global__ void ei_grad_kernel(const double* __restrict__ mu, const double* __restrict__ var, const double* __restrict__ dmu,
+                               const double* __restrict__ dvar, int M, int d, EiPar par,
+                               const double* __restrict__ coefs_dev, const double* __restrict__ ymax_dev,
+                               const unsigned char* __restrict__ mask, double* __restrict__ acq,
+                               double* __restrict__ dacq) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= M) return;
+    ei_grad_point<false>(mu, var, dmu, dvar, M, d, par, coefs_dev, ymax_dev, mask, j, acq + j, dacq + (size_t)j * d);
+}
+// The Bayesian-inference average of the above over S hyper-parameter samples (expected_improvement.jl:87-90 under the ForwardDiff of
+// OptimizationAM): mu / var [s][p][M], dmu / dvar [s][p][d×M]; acq = (Σ_s acq_s)/S, ∇acq = (Σ_s ∇acq_s)/S, summed in ascending s by
+// the candidate's own thread (no atomics: the result does not depend on scheduling).
+__global__ void ei_grad_set_kernel(const double* __restrict__ mu, const double* __restrict__ var, const double* __restrict__ dmu,
+                                   const double* __restrict__ dvar, int M, int d, int S, EiPar par,
+                                   const double* __restrict__ coefs_dev, const double* __restrict__ ymax_dev,
+                                   const unsigned char* __restrict__ mask, double* __restrict__ acq,
+                                   double* __restrict__ dacq) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= M) return;
+    double* gout = dacq + (size_t)j * d;
+    acq[j] = 0.0;
+    for (int m = 0; m < d; ++m) gout[m] = 0.0;
+    const size_t pm = (size_t)par.P * M, pdm = pm * d;
+    for (int s = 0; s < S; ++s)
+        ei_grad_point<true>(mu + s * pm, var + s * pm, dmu + s * pdm, dvar + s * pdm, M, d, par, coefs_dev, ymax_dev, mask, j, acq + j, gout);
+    acq[j] /= (double)S;
+    for (int m = 0; m < d; ++m) gout[m] /= (double)S;
 }
 
 // ------------------------------------------------------------------------------------------

@@ -122,11 +122,12 @@ struct Ctx {
     unsigned long long* few_done = nullptr;    // device counter of finished workgroups (winv_args_kernel) and its value on the host
     unsigned long long few_done_cnt = 0;
     long set_launches = 0, set_pre_launches = 0;   // predict_kernel_set launches: all, and those on K* written beforehand (boss_debug_set_launches)
+    long set_grad_launches = 0;                    // backsolve_set_kernel launches (boss_debug_set_grad_launches)
     bool lookahead = true;
     bool prof_on = false;
     std::map<std::string, std::vector<std::pair<hipEvent_t, hipEvent_t>>> prof;
     std::vector<hipEvent_t> ev_pool;
-    Workspace vscratch, csc, pred, acq, batchA, batchX, batchMisc, craw, lgA, lgB, lgC, few, setdesc, setmom;
+    Workspace vscratch, csc, pred, acq, batchA, batchX, batchMisc, craw, lgA, lgB, lgC, few, setdesc, setmom, gsetdesc;
     // batched likelihood gradients: the gradient passes of consecutive sets rotate over LLG_BANKS streams, each with its
     // own bank of workspaces (bank 0 = the main stream and lgA/lgB/lgC)
     static constexpr int LLG_BANKS = 4;
@@ -196,6 +197,13 @@ extern "C" int boss_debug_set_launches(int device, long* all_out, long* pre_out)
     auto it = g_ctx.find(device);
     if (all_out) *all_out = it != g_ctx.end() ? it->second->set_launches : 0;
     if (pre_out) *pre_out = it != g_ctx.end() ? it->second->set_pre_launches : 0;
+    return BOSS_OK;
+}
+
+extern "C" int boss_debug_set_grad_launches(int device, long* out) {   // (tests: did boss_acq_ei_grad_set take the set launches?)
+    std::lock_guard<std::mutex> lk(g_ctx_mtx);
+    auto it = g_ctx.find(device);
+    if (out) *out = it != g_ctx.end() ? it->second->set_grad_launches : 0;
     return BOSS_OK;
 }
 
@@ -365,6 +373,9 @@ static int ctx_init(Ctx* c) {
                                PredictLds<PredG32>::BYTES));
     HIPCHK(hipFuncSetAttribute((const void*)backsolve_kernel<PredG32>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                PredictLds<PredG32>::BYTES));
+    HIPCHK(hipFuncSetAttribute((const void*)backsolve_set_kernel<PredG32>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               PredictLds<PredG32>::BYTES));
+    HIPCHK(hipFuncSetAttribute((const void*)grad_accum_set_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
     HIPCHK(hipFuncSetAttribute((const void*)predict_kernel<PredG64>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                PredictLds<PredG64>::BYTES));
     HIPCHK(hipFuncSetAttribute((const void*)predict_kernel<PredG32, true>, hipFuncAttributeMaxDynamicSharedMemorySize,

@@ -16,11 +16,8 @@ namespace boss {
 // factorisation by a chain of small GEMV launches.
 // ------------------------------------------------------------------------------------------
 // out[c + r*ldo] = in[r + c*ldi] for an n×n matrix (batched over blockIdx.z with the given strides)
-__global__ __launch_bounds__(256) void transpose_kernel(const double* __restrict__ in, int ldi, size_t si,
-                                                        double* __restrict__ out, int ldo, size_t so, int n) {
+__device__ __forceinline__ void transpose_body(const double* __restrict__ I, int ldi, double* __restrict__ O, int ldo, int n) {
     __shared__ double t[64][65];
-    const double* I = in + (size_t)blockIdx.z * si;
-    double* O = out + (size_t)blockIdx.z * so;
     const int r0 = blockIdx.x * 64, c0 = blockIdx.y * 64;
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
     for (int c = ty; c < 64; c += 4)
@@ -29,12 +26,44 @@ __global__ __launch_bounds__(256) void transpose_kernel(const double* __restrict
     for (int r = ty; r < 64; r += 4)
         if (c0 + tx < n && r0 + r < n) O[(size_t)(r0 + r) * ldo + c0 + tx] = t[tx][r];
 }
+__global__ __launch_bounds__(256) void transpose_kernel(const double* __restrict__ in, int ldi, size_t si,
+                                                        double* __restrict__ out, int ldo, size_t so, int n) {
+    transpose_body(in + (size_t)blockIdx.z * si, ldi, out + (size_t)blockIdx.z * so, ldo, n);
+}
+
+// What the gradient pass of a SET of equally shaped posteriors (boss_acq_ei_grad_set: the S hyper-parameter samples × P outputs of a
+// Bayesian-inference fit) needs of one member, beside its PredSet descriptor: the once-per-factorisation arrays (transposed factor,
+// transposed 256×256 inverses, a = L⁻ᵀz) and where its moment gradients go.  The members' arrays need not lie at constant strides.
+struct GradSet {
+    const double* A;          // factor (+ z row)
+    const double* Dinv2;      // 256×256 diagonal-block inverses
+    double* LT;               // Lᵀ, leading dimension ld
+    double* DT2;              // Dinv2 blocks transposed
+    double* avec;             // a = L⁻ᵀz [Np] | GEMV partials [Np]
+    const double* Xsc;        // scaled training points (plain members)
+    const double* Xraw;       // raw points (gradient-observation members)
+    const double* Csc;        // the candidates scaled by this member's lengthscales (plain members)
+    const double* invlam;
+    const double* mean_grad;  // ∇m at the candidates [d×M] or null
+    double* dmu;              // ∇μ, ∇σ² of this member [d×M]
+    double* dvar;
+    double amp2;
+};
+// the two transpositions of the once-per-factorisation preparation for a list of members: which = 0: LT = Aᵀ (grid.z = member),
+// which = 1: DT2 = the Np/256 blocks of Dinv2 transposed (grid.z = member · nb + block)
+__global__ __launch_bounds__(256) void transpose_set_kernel(const GradSet* __restrict__ sets, int which, int ld, int Np) {
+    const int nb = Np / PRED_RB;
+    const GradSet gs = sets[which ? blockIdx.z / nb : blockIdx.z];
+    const size_t off = which ? (size_t)(blockIdx.z % nb) * PRED_RB * PRED_RB : 0;
+    transpose_body(which ? gs.Dinv2 + off : gs.A, which ? PRED_RB : ld, which ? gs.DT2 + off : gs.LT, which ? PRED_RB : ld,
+                   which ? PRED_RB : Np);
+}
 
 // a = L⁻ᵀ z (= (K+σ²I)⁻¹(y−m)), once per factorisation, in 256-row steps from the last to the first:
 //     bt_gemv_partial_kernel   partial[c][r] = Σ_{k in 256-column chunk c} Lᵀ[i0+r, k] a[k]      (one workgroup per chunk)
 //     bt_finish_kernel         a[i0..i0+255] = Dinv2ᵀ_i (z_i − Σ_c partial[c])                   (fixed summation order)
-__global__ __launch_bounds__(256) void bt_gemv_partial_kernel(const double* __restrict__ LT, int ldt, int ib,
-                                                              const double* __restrict__ a, double* __restrict__ partial) {
+__device__ __forceinline__ void bt_gemv_partial_body(const double* __restrict__ LT, int ldt, int ib, const double* __restrict__ a,
+                                                     double* __restrict__ partial) {
     const int r = threadIdx.x, kc = (ib + 1 + blockIdx.x) * PRED_RB;
     const double* col = LT + (size_t)ib * PRED_RB + r + (size_t)kc * ldt;
     double s = 0.0;
@@ -42,10 +71,14 @@ __global__ __launch_bounds__(256) void bt_gemv_partial_kernel(const double* __re
     for (int k = 0; k < PRED_RB; ++k) s = __builtin_fma(col[(size_t)k * ldt], a[kc + k], s);
     partial[(size_t)blockIdx.x * PRED_RB + r] = s;
 }
+__global__ __launch_bounds__(256) void bt_gemv_partial_kernel(const double* __restrict__ LT, int ldt, int ib,
+                                                              const double* __restrict__ a, double* __restrict__ partial) {
+    bt_gemv_partial_body(LT, ldt, ib, a, partial);
+}
 
-__global__ __launch_bounds__(256) void bt_finish_kernel(const double* __restrict__ A, int ld, int Np, int N, int ib, int nchunks,
-                                                        const double* __restrict__ partial, const double* __restrict__ DT2,
-                                                        double* __restrict__ a) {
+__device__ __forceinline__ void bt_finish_body(const double* __restrict__ A, int ld, int Np, int N, int ib, int nchunks,
+                                               const double* __restrict__ partial, const double* __restrict__ DT2,
+                                               double* __restrict__ a) {
     __shared__ double rv[PRED_RB];
     const int r = threadIdx.x, i = ib * PRED_RB + r;
     double v = (i < N) ? A[(size_t)i * ld + Np] : 0.0;      // z_i sits in row Np of the factor array
@@ -58,15 +91,28 @@ __global__ __launch_bounds__(256) void bt_finish_kernel(const double* __restrict
     for (int k = 0; k < PRED_RB; ++k) s = __builtin_fma(D[r + (size_t)k * PRED_RB], rv[k], s);   // upper triangular: zeros below the diagonal
     a[i] = s;
 }
+__global__ __launch_bounds__(256) void bt_finish_kernel(const double* __restrict__ A, int ld, int Np, int N, int ib, int nchunks,
+                                                        const double* __restrict__ partial, const double* __restrict__ DT2,
+                                                        double* __restrict__ a) {
+    bt_finish_body(A, ld, Np, N, ib, nchunks, partial, DT2, a);
+}
+// the same chain for a list of members (grid.y = member): every member's partials live behind its own a
+__global__ __launch_bounds__(256) void bt_gemv_partial_set_kernel(const GradSet* __restrict__ sets, int ldt, int Np, int ib) {
+    const GradSet gs = sets[blockIdx.y];
+    bt_gemv_partial_body(gs.LT, ldt, ib, gs.avec, gs.avec + Np);
+}
+__global__ __launch_bounds__(256) void bt_finish_set_kernel(const GradSet* __restrict__ sets, int ld, int Np, int N, int ib, int nchunks) {
+    const GradSet gs = sets[blockIdx.y];
+    bt_finish_body(gs.A, ld, Np, N, ib, nchunks, gs.avec + Np, gs.DT2, gs.avec);
+}
 
 // W = L⁻ᵀ V in place on every slab: for the row steps from the last to the first,
 //     R_i = V_i − Σ_{j>i} Lᵀ_ij W_j        (GemmDirect: A = rows of LT, B = this slab's finished rows)
 //     W_i = Dinv2_iᵀ R_i                    (R in LDS; DT2 holds the transposed 256×256 inverses: upper
 //                                            triangular, a row only needs the k ≥ its own 64-row slice)
 template <class G>
-__global__ __launch_bounds__(G::NTHREADS) void backsolve_kernel(const double* __restrict__ LT, int ldt, int Np,
-                                                                const double* __restrict__ DT2,
-                                                                double* __restrict__ Vscratch) {
+__device__ __forceinline__ void backsolve_body(const double* __restrict__ LT, int ldt, int Np, const double* __restrict__ DT2,
+                                               double* __restrict__ V) {
     static_assert(G::WC == 1 && G::BM == 2 * BLK, "written for 256-row steps");
     constexpr int RB = G::BM, BN = G::BN, TM = G::TM, TN = G::TN, LDR = PredictLds<G>::LDR;
     extern __shared__ double lds[];
@@ -74,7 +120,6 @@ __global__ __launch_bounds__(G::NTHREADS) void backsolve_kernel(const double* __
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int wr = wave, wc = 0;
-    double* V = Vscratch + (size_t)blockIdx.x * Np * BN;
     const int nb = Np / RB;
     for (int ib = nb - 1; ib >= 0; --ib) {
         v4d acc[TM][TN];
@@ -113,6 +158,19 @@ __global__ __launch_bounds__(G::NTHREADS) void backsolve_kernel(const double* __
         }
         __syncthreads();                                   // W_ib visible to the workgroup; Rs reusable
     }
+}
+template <class G>
+__global__ __launch_bounds__(G::NTHREADS) void backsolve_kernel(const double* __restrict__ LT, int ldt, int Np,
+                                                                const double* __restrict__ DT2,
+                                                                double* __restrict__ Vscratch) {
+    backsolve_body<G>(LT, ldt, Np, DT2, Vscratch + (size_t)blockIdx.x * Np * G::BN);
+}
+// ... of a SET of equally shaped posteriors: grid = (candidate tiles, members), slabs indexed as predict_kernel_set leaves them
+template <class G>
+__global__ __launch_bounds__(G::NTHREADS) void backsolve_set_kernel(const GradSet* __restrict__ sets, int ldt, int Np,
+                                                                    double* __restrict__ Vscratch) {
+    const GradSet gs = sets[blockIdx.y];                     // (uniform: scalar loads)
+    backsolve_body<G>(gs.LT, ldt, Np, gs.DT2, Vscratch + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * Np * G::BN);
 }
 
 // Few candidates: the adjoint substitution W = L⁻ᵀV right-looking, from the LAST 256-row step to the first, in
@@ -188,32 +246,31 @@ __global__ __launch_bounds__(GU::NTHREADS) void few_back_update_kernel(const dou
 // loads of a chunk are issued together.  Dimensions are handled 16 at a time (registers).
 constexpr int GRAD_MAX_D = 16;
 constexpr int GRAD_CHUNK = 64;
-__global__ __launch_bounds__(256) void grad_accum_kernel(const double* __restrict__ Wslabs, const double* __restrict__ avec,
-                                                         int Np, int N, const double* __restrict__ Xsc,
-                                                         const double* __restrict__ Csc, int d, int Mp, int M, int kern,
-                                                         double amp2, const double* __restrict__ invlam,
-                                                         const unsigned char* __restrict__ discrete,
-                                                         const double* __restrict__ mean_grad,
-                                                         double* __restrict__ dmu, double* __restrict__ dvar,
-                                                         double* __restrict__ part) {
-    // gridDim.y > 1 (few tiles, d <= 16): the rows are split over gridDim.y workgroups per tile, each writes its
-    // sums to part[(tile·gridDim.y + y)][2(GRAD_MAX_D+1)][32]; grad_finalize_kernel adds them in a fixed order
+__device__ __forceinline__ void grad_accum_body(const double* __restrict__ W, const double* __restrict__ avec,
+                                                int Np, int N, const double* __restrict__ Xsc,
+                                                const double* __restrict__ Csc, int d, int Mp, int M, int kern,
+                                                double amp2, const double* __restrict__ invlam,
+                                                const unsigned char* __restrict__ discrete,
+                                                const double* __restrict__ mean_grad,
+                                                double* __restrict__ dmu, double* __restrict__ dvar,
+                                                double* __restrict__ part, int bx, int by, int ny) {
+    // W: the slab of tile bx.  ny > 1 (few tiles, d <= 16): the rows are split over ny workgroups per tile, workgroup by writes its
+    // sums to part[by][2(GRAD_MAX_D+1)][32] (part: this tile's); grad_finalize_kernel adds them in a fixed order
     constexpr int BN = 32;
     extern __shared__ double glds[];
     double* xs = glds;                                       // [d][GRAD_CHUNK] scaled coordinates of the chunk's rows
     double* as = xs + (size_t)d * GRAD_CHUNK;                // [GRAD_CHUNK]     a_i
     double* red = as + GRAD_CHUNK;                           // [8][2(GRAD_MAX_D+1)][BN]
     const int tid = threadIdx.x, c = tid & 31, rs = tid >> 5;
-    const int j = blockIdx.x * BN + c;
-    const double* W = Wslabs + (size_t)blockIdx.x * Np * BN;
+    const int j = bx * BN + c;
     for (int m0 = 0; m0 < d; m0 += GRAD_MAX_D) {            // d > 16: passes of 16 dimensions
         const int dm = (d - m0 < GRAD_MAX_D) ? (d - m0) : GRAD_MAX_D;
         double S1 = 0.0, S2 = 0.0, T1[GRAD_MAX_D], T2[GRAD_MAX_D];
 #pragma unroll
         for (int m = 0; m < GRAD_MAX_D; ++m) T1[m] = T2[m] = 0.0;
         const int nchunk = (N + GRAD_CHUNK - 1) / GRAD_CHUNK;
-        const int cpb = (nchunk + gridDim.y - 1) / gridDim.y;
-        const int rbeg = blockIdx.y * cpb * GRAD_CHUNK;
+        const int cpb = (nchunk + ny - 1) / ny;
+        const int rbeg = by * cpb * GRAD_CHUNK;
         const int rend = (rbeg + cpb * GRAD_CHUNK < N) ? rbeg + cpb * GRAD_CHUNK : N;
         for (int r0 = rbeg; r0 < rend; r0 += GRAD_CHUNK) {
             __syncthreads();
@@ -258,9 +315,9 @@ __global__ __launch_bounds__(256) void grad_accum_kernel(const double* __restric
             rd[(3 + 2 * m) * BN + c] = T2[m];
         }
         __syncthreads();
-        if (gridDim.y > 1) {
+        if (ny > 1) {
             // this workgroup's sums (over its 8 row subsets) go to global; the finalize kernel finishes
-            double* pw = part + ((size_t)blockIdx.x * gridDim.y + blockIdx.y) * (2 * (GRAD_MAX_D + 1)) * BN;
+            double* pw = part + (size_t)by * (2 * (GRAD_MAX_D + 1)) * BN;
             for (int slot = rs; slot < 2 * (GRAD_MAX_D + 1); slot += 8) {
                 double v = 0.0;
                 for (int k = 0; k < 8; ++k) v += red[((size_t)k * (2 * (GRAD_MAX_D + 1)) + slot) * BN + c];
@@ -293,6 +350,27 @@ __global__ __launch_bounds__(256) void grad_accum_kernel(const double* __restric
         }
     }
 }
+__global__ __launch_bounds__(256) void grad_accum_kernel(const double* __restrict__ Wslabs, const double* __restrict__ avec,
+                                                         int Np, int N, const double* __restrict__ Xsc,
+                                                         const double* __restrict__ Csc, int d, int Mp, int M, int kern,
+                                                         double amp2, const double* __restrict__ invlam,
+                                                         const unsigned char* __restrict__ discrete,
+                                                         const double* __restrict__ mean_grad,
+                                                         double* __restrict__ dmu, double* __restrict__ dvar,
+                                                         double* __restrict__ part) {
+    grad_accum_body(Wslabs + (size_t)blockIdx.x * Np * 32, avec, Np, N, Xsc, Csc, d, Mp, M, kern, amp2, invlam, discrete, mean_grad, dmu, dvar,
+                    part ? part + (size_t)blockIdx.x * gridDim.y * (2 * (GRAD_MAX_D + 1)) * 32 : nullptr, blockIdx.x, blockIdx.y, gridDim.y);
+}
+// ... of a SET of equally shaped plain posteriors: grid = (candidate tiles, row splits, members); every member writes ∇μ, ∇σ² (or
+// its partial sums, part[member][tile][split]) to its own slice
+__global__ __launch_bounds__(256) void grad_accum_set_kernel(const GradSet* __restrict__ sets, const double* __restrict__ Wslabs, int Np, int N,
+                                                             int d, int Mp, int M, int kern, const unsigned char* __restrict__ discrete,
+                                                             double* __restrict__ part) {
+    const GradSet gs = sets[blockIdx.z];
+    const size_t slab = (size_t)blockIdx.z * gridDim.x + blockIdx.x;
+    grad_accum_body(Wslabs + slab * Np * 32, gs.avec, Np, N, gs.Xsc, gs.Csc, d, Mp, M, kern, gs.amp2, gs.invlam, discrete, gs.mean_grad, gs.dmu,
+                    gs.dvar, part ? part + slab * gridDim.y * (2 * (GRAD_MAX_D + 1)) * 32 : nullptr, blockIdx.x, blockIdx.y, gridDim.y);
+}
 
 // ------------------------------------------------------------------------------------------
 // ∇μ, ∇σ² of a gradient-observation posterior (GradientGaussianProcess, src/models/gradient_gp.jl:334-361 under the ForwardDiff of
@@ -304,17 +382,18 @@ __global__ __launch_bounds__(256) void grad_accum_kernel(const double* __restric
 // One workgroup per 32-candidate slab and row split: lanes along the candidates, eight point subsets; the a entries come from avec
 // (row l·n + i), the w entries from the W slabs.  part (gridDim.y > 1): [tile·gridDim.y + y][2 d][32], summed by aug_grad_finalize_kernel.
 // ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void aug_grad_accum_kernel(const double* __restrict__ Wslabs, const double* __restrict__ avec, int Np,
-                                                             int n, const double* __restrict__ Xraw, int ldx,
-                                                             const double* __restrict__ Craw, int d, int Mp, int M, int kern,
-                                                             double amp2, const double* __restrict__ invlam,
-                                                             double* __restrict__ dmu, double* __restrict__ dvar,
-                                                             double* __restrict__ part) {
+__device__ __forceinline__ void aug_grad_accum_body(const double* __restrict__ Wslab, const double* __restrict__ avec, int Np,
+                                                    int n, const double* __restrict__ Xraw, int ldx,
+                                                    const double* __restrict__ Craw, int d, int Mp, int M, int kern,
+                                                    double amp2, const double* __restrict__ invlam,
+                                                    double* __restrict__ dmu, double* __restrict__ dvar,
+                                                    double* __restrict__ part, int bx, int by, int ny) {
+    // Wslab: this tile's slab; part: this tile's [ny][2 AUG_MAX_D][32] partial sums (ny > 1)
     constexpr int BN = 32, DM = AUG_MAX_D;
     __shared__ double red[8][2 * DM][BN];
     const int tid = threadIdx.x, c = tid & 31, rs = tid >> 5;
-    const int j = blockIdx.x * BN + c;
-    const double* W = Wslabs + (size_t)blockIdx.x * Np * BN + c;
+    const int j = bx * BN + c;
+    const double* W = Wslab + c;
     double xc[DM], il2[DM], il[DM], G1[DM], G2[DM];
     double nc = 0.0;
 #pragma unroll
@@ -325,8 +404,8 @@ __global__ __launch_bounds__(256) void aug_grad_accum_kernel(const double* __res
         nc = __builtin_fma(xc[m], xc[m], nc);
         G1[m] = G2[m] = 0.0;
     }
-    const int per = (n + gridDim.y - 1) / gridDim.y;
-    const int ibeg = blockIdx.y * per, iend = min(n, ibeg + per);
+    const int per = (n + ny - 1) / ny;
+    const int ibeg = by * per, iend = min(n, ibeg + per);
     for (int i = ibeg + rs; i < iend; i += 8) {
         double t[DM], du2 = 0.0, ni = 0.0, r2 = 0.0;
 #pragma unroll
@@ -380,25 +459,54 @@ __global__ __launch_bounds__(256) void aug_grad_accum_kernel(const double* __res
         double v = 0.0;
         for (int k = 0; k < 8; ++k) v += red[k][slot][c];
         const int m = slot >> 1;
-        if (gridDim.y > 1) part[(((size_t)blockIdx.x * gridDim.y + blockIdx.y) * 2 * DM + slot) * BN + c] = v;
+        if (ny > 1) part[(((size_t)by) * 2 * DM + slot) * BN + c] = v;
         else if (j < M) {
             if (slot & 1) dvar[(size_t)j * d + m] = -2.0 * amp2 * v;
             else dmu[(size_t)j * d + m] = amp2 * v;
         }
     }
 }
-__global__ __launch_bounds__(32) void aug_grad_finalize_kernel(const double* __restrict__ part, int rsplit, int d, int M, double amp2,
-                                                               double* __restrict__ dmu, double* __restrict__ dvar) {
+__global__ __launch_bounds__(256) void aug_grad_accum_kernel(const double* __restrict__ Wslabs, const double* __restrict__ avec, int Np,
+                                                             int n, const double* __restrict__ Xraw, int ldx,
+                                                             const double* __restrict__ Craw, int d, int Mp, int M, int kern,
+                                                             double amp2, const double* __restrict__ invlam,
+                                                             double* __restrict__ dmu, double* __restrict__ dvar,
+                                                             double* __restrict__ part) {
+    aug_grad_accum_body(Wslabs + (size_t)blockIdx.x * Np * 32, avec, Np, n, Xraw, ldx, Craw, d, Mp, M, kern, amp2, invlam, dmu, dvar,
+                        part ? part + (size_t)blockIdx.x * gridDim.y * 2 * AUG_MAX_D * 32 : nullptr, blockIdx.x, blockIdx.y, gridDim.y);
+}
+// ... of a SET of equally shaped gradient-observation posteriors: grid = (candidate tiles, point splits, members)
+__global__ __launch_bounds__(256) void aug_grad_accum_set_kernel(const GradSet* __restrict__ sets, const double* __restrict__ Wslabs, int Np,
+                                                                 int n, int ldx, const double* __restrict__ Craw, int d, int Mp, int M, int kern,
+                                                                 double* __restrict__ part) {
+    const GradSet gs = sets[blockIdx.z];
+    const size_t slab = (size_t)blockIdx.z * gridDim.x + blockIdx.x;
+    aug_grad_accum_body(Wslabs + slab * Np * 32, gs.avec, Np, n, gs.Xraw, ldx, Craw, d, Mp, M, kern, gs.amp2, gs.invlam, gs.dmu, gs.dvar,
+                        part ? part + slab * gridDim.y * 2 * AUG_MAX_D * 32 : nullptr, blockIdx.x, blockIdx.y, gridDim.y);
+}
+__device__ __forceinline__ void aug_grad_finalize_body(const double* __restrict__ part, int rsplit, int d, int M, double amp2,
+                                                       double* __restrict__ dmu, double* __restrict__ dvar) {
+    // part: this tile's [rsplit][2 AUG_MAX_D][32]
     constexpr int BN = 32, DM = AUG_MAX_D;
     const int c = threadIdx.x, j = blockIdx.x * BN + c;
     if (j >= M) return;
     for (int slot = 0; slot < 2 * d; ++slot) {
         double v = 0.0;
-        for (int y = 0; y < rsplit; ++y) v += part[(((size_t)blockIdx.x * rsplit + y) * 2 * DM + slot) * BN + c];
+        for (int y = 0; y < rsplit; ++y) v += part[(((size_t)y) * 2 * DM + slot) * BN + c];
         const int m = slot >> 1;
         if (slot & 1) dvar[(size_t)j * d + m] = -2.0 * amp2 * v;
         else dmu[(size_t)j * d + m] = amp2 * v;
     }
+}
+__global__ __launch_bounds__(32) void aug_grad_finalize_kernel(const double* __restrict__ part, int rsplit, int d, int M, double amp2,
+                                                               double* __restrict__ dmu, double* __restrict__ dvar) {
+    aug_grad_finalize_body(part + (size_t)blockIdx.x * rsplit * 2 * AUG_MAX_D * 32, rsplit, d, M, amp2, dmu, dvar);
+}
+__global__ __launch_bounds__(32) void aug_grad_finalize_set_kernel(const GradSet* __restrict__ sets, const double* __restrict__ part, int rsplit,
+                                                                   int d, int M) {   // grid = (tiles, members)
+    const GradSet gs = sets[blockIdx.y];
+    aug_grad_finalize_body(part + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * rsplit * 2 * AUG_MAX_D * 32, rsplit, d, M, gs.amp2, gs.dmu,
+                           gs.dvar);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -937,16 +1045,16 @@ __global__ __launch_bounds__(256) void gibbs_llgrad_reduce_kernel(const double* 
     out[(size_t)(d + 2) * Np + i] = i < N ? ai : 0.0;
 }
 
-__global__ __launch_bounds__(32) void grad_finalize_kernel(const double* __restrict__ part, int rsplit,
-                                                           const double* __restrict__ Csc, int d, int Mp, int M,
-                                                           const double* __restrict__ invlam,
-                                                           const unsigned char* __restrict__ discrete,
-                                                           const double* __restrict__ mean_grad, double* __restrict__ dmu,
-                                                           double* __restrict__ dvar) {
+__device__ __forceinline__ void grad_finalize_body(const double* __restrict__ pt, int rsplit,
+                                                   const double* __restrict__ Csc, int d, int Mp, int M,
+                                                   const double* __restrict__ invlam,
+                                                   const unsigned char* __restrict__ discrete,
+                                                   const double* __restrict__ mean_grad, double* __restrict__ dmu,
+                                                   double* __restrict__ dvar) {
+    // pt: this tile's [rsplit][2(GRAD_MAX_D+1)][32]
     constexpr int BN = 32, NS = 2 * (GRAD_MAX_D + 1);
     const int c = threadIdx.x, j = blockIdx.x * BN + c;
     if (j >= M) return;
-    const double* pt = part + (size_t)blockIdx.x * rsplit * NS * BN;
     double s1 = 0.0, s2 = 0.0;
     for (int y = 0; y < rsplit; ++y) {
         s1 += pt[((size_t)y * NS + 0) * BN + c];
@@ -965,6 +1073,21 @@ __global__ __launch_bounds__(32) void grad_finalize_kernel(const double* __restr
         dmu[(size_t)j * d + m] = g1 + (mean_grad ? mean_grad[(size_t)j * d + m] : 0.0);
         dvar[(size_t)j * d + m] = g2;
     }
+}
+__global__ __launch_bounds__(32) void grad_finalize_kernel(const double* __restrict__ part, int rsplit,
+                                                           const double* __restrict__ Csc, int d, int Mp, int M,
+                                                           const double* __restrict__ invlam,
+                                                           const unsigned char* __restrict__ discrete,
+                                                           const double* __restrict__ mean_grad, double* __restrict__ dmu,
+                                                           double* __restrict__ dvar) {
+    grad_finalize_body(part + (size_t)blockIdx.x * rsplit * 2 * (GRAD_MAX_D + 1) * 32, rsplit, Csc, d, Mp, M, invlam, discrete, mean_grad, dmu,
+                       dvar);
+}
+__global__ __launch_bounds__(32) void grad_finalize_set_kernel(const GradSet* __restrict__ sets, const double* __restrict__ part, int rsplit,
+                                                               int d, int Mp, int M, const unsigned char* __restrict__ discrete) {   // grid = (tiles, members)
+    const GradSet gs = sets[blockIdx.y];
+    grad_finalize_body(part + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * rsplit * 2 * (GRAD_MAX_D + 1) * 32, rsplit, gs.Csc, d, Mp, M,
+                       gs.invlam, discrete, gs.mean_grad, gs.dmu, gs.dvar);
 }
 
 // a5: full posterior covariance  Σ = K** − VᵀV + 1e-18·I  (mean_and_cov, gaussian_process.jl:180-184;

@@ -448,49 +448,56 @@ static bool predict_set_ok(int n, boss_gp_t* const* gps, const boss_cand* cd, bo
     }
     return true;
 }
+// The diagonal-block inverses of every member of a set, current on the stream: members of ONE batch-fitted set that still lack them
+// get them in one set of launches (grid.z = member; their arrays are views into one slab with constant strides), anything else member
+// by member.  Idempotent.
+static void set_dinv_enqueue(int n, boss_gp_t* const* gps, hipStream_t s) {
+    boss_gp* g0 = gps[0];
+    bool uniform = n >= 2 && g0->set != nullptr;
+    const ptrdiff_t sA = n >= 2 ? gps[1]->A - gps[0]->A : 0, sI = n >= 2 ? gps[1]->inv16 - gps[0]->inv16 : 0,
+                    sD = n >= 2 ? gps[1]->Dinv - gps[0]->Dinv : 0, sD2 = n >= 2 ? gps[1]->Dinv2 - gps[0]->Dinv2 : 0;
+    for (int i = 0; i < n && uniform; ++i) {
+        const boss_gp* g = gps[i];
+        uniform = g->set == g0->set && !g->have_dinv && !g->dinv_pending && g->A - g0->A == sA * i && g->inv16 - g0->inv16 == sI * i &&
+                  g->Dinv - g0->Dinv == sD * i && g->Dinv2 - g0->Dinv2 == sD2 * i && sA > 0 && sI > 0 && sD > 0 && sD2 > 0;
+    }
+    if (uniform) {
+        SetBatch B;
+        B.nb = n;
+        B.sA = (size_t)sA;
+        B.sInv16 = (size_t)sI;
+        B.sDinv = (size_t)sD;
+        B.sDinv2 = (size_t)sD2;
+        dinv_launch(gps[0], s, B);
+        for (int i = 0; i < n; ++i) gps[i]->have_dinv = true;
+    }
+    for (int i = 0; i < n; ++i) {
+        boss_gp* g = gps[i];
+        dinv_join(g);
+        if (!g->have_dinv) {
+            dinv_launch(g, s);
+            g->have_dinv = true;
+        }
+        g->dinv_used = true;
+    }
+}
 // moments of posteriors gps[0..n-1] at resident candidates: mu/var of posterior i at mu_all + i·mstride (unclipped); mean_all (or
 // null): prior means at the candidates in the same layout.  Caller holds the context lock and has checked predict_set_ok.
 // Gradient-observation and nonstationary members: K* of every member goes into its V slabs first (aug_kstar_set_kernel /
 // gibbs_kstar_set_kernel), the substitution takes it from there (predict_kernel_set<G, true>); clam_all / camp_all are the
 // nonstationary members' latent values at the candidates, [n][d][Mp] and [n][Mp].
+// after_group(i0, cnt), if given, is called behind the launches of every group of members: their V slabs (member i0 + k, tile t at
+// slab k·tiles + t of the scratch) are overwritten by the next group, so whoever needs them enqueues its work there (grad_set_enqueue).
 static int predict_set_enqueue(int n, boss_gp_t* const* gps, const boss_cand* cd, const double* mean_all, double* mu_all,
-                               double* var_all, size_t mstride, const double* clam_all = nullptr, const double* camp_all = nullptr) {
+                               double* var_all, size_t mstride, const double* clam_all = nullptr, const double* camp_all = nullptr,
+                               const std::function<int(int, int)>* after_group = nullptr) {
     boss_gp* g0 = gps[0];
     Ctx* c = g0->ctx;
     hipStream_t s = c->stream;
     typedef PredG32 G;
     const int Mp = cd->Mp, d = g0->d, Np = g0->Np;
     const int tiles = (cd->M + G::BN - 1) / G::BN;
-    {   // the diagonal-block inverses of every member: members of ONE batch-fitted set that still lack them get them in one set of
-        // launches (grid.z = member; their arrays are views into one slab with constant strides), anything else member by member
-        bool uniform = n >= 2 && g0->set != nullptr;
-        const ptrdiff_t sA = n >= 2 ? gps[1]->A - gps[0]->A : 0, sI = n >= 2 ? gps[1]->inv16 - gps[0]->inv16 : 0,
-                        sD = n >= 2 ? gps[1]->Dinv - gps[0]->Dinv : 0, sD2 = n >= 2 ? gps[1]->Dinv2 - gps[0]->Dinv2 : 0;
-        for (int i = 0; i < n && uniform; ++i) {
-            const boss_gp* g = gps[i];
-            uniform = g->set == g0->set && !g->have_dinv && !g->dinv_pending && g->A - g0->A == sA * i && g->inv16 - g0->inv16 == sI * i &&
-                      g->Dinv - g0->Dinv == sD * i && g->Dinv2 - g0->Dinv2 == sD2 * i && sA > 0 && sI > 0 && sD > 0 && sD2 > 0;
-        }
-        if (uniform) {
-            SetBatch B;
-            B.nb = n;
-            B.sA = (size_t)sA;
-            B.sInv16 = (size_t)sI;
-            B.sDinv = (size_t)sD;
-            B.sDinv2 = (size_t)sD2;
-            dinv_launch(gps[0], s, B);
-            for (int i = 0; i < n; ++i) gps[i]->have_dinv = true;
-        }
-        for (int i = 0; i < n; ++i) {
-            boss_gp* g = gps[i];
-            dinv_join(g);
-            if (!g->have_dinv) {
-                dinv_launch(g, s);
-                g->have_dinv = true;
-            }
-            g->dinv_used = true;
-        }
-    }
+    set_dinv_enqueue(n, gps, s);
     // the V slabs of the workgroups in flight: groups of posteriors per launch so that the scratch stays bounded
     static const size_t v_cap = (size_t)(getenv("BOSS_SET_V_GIB") ? atof(getenv("BOSS_SET_V_GIB")) : 8.0) * ((size_t)1 << 30);
     const size_t v_one = sizeof(double) * (size_t)tiles * G::BN * Np;
@@ -548,6 +555,7 @@ static int predict_set_enqueue(int n, boss_gp_t* const* gps, const boss_cand* cd
         if (!pre) {
             hipLaunchKernelGGL(predict_kernel_set<G>, dim3(tiles, cnt), dim3(G::NTHREADS), PredictLds<G>::BYTES, s, dsets + i0, g0->ld, Np, g0->N, d,
                                Mp, g0->kernel, (double*)c->vscratch.p, cd->M);
+            if (after_group && (rc = (*after_group)(i0, cnt)) != BOSS_OK) return rc;
             continue;
         }
         ++c->set_pre_launches;
@@ -561,6 +569,7 @@ static int predict_set_enqueue(int n, boss_gp_t* const* gps, const boss_cand* cd
         hipLaunchKernelGGL((predict_kernel_set<G, true>), dim3(tiles, cnt), dim3(G::NTHREADS), PredictLds<G>::BYTES, s, dsets + i0, g0->ld, Np,
                            g0->N, d, Mp, g0->kernel, (double*)c->vscratch.p, cd->M);
         if (g0->gibbs) hipLaunchKernelGGL(gibbs_var_set_kernel, dim3((cd->M + 255) / 256, cnt), dim3(256), 0, s, dsets + i0, cd->M);
+        if (after_group && (rc = (*after_group)(i0, cnt)) != BOSS_OK) return rc;
     }
     HIPCHK(hipGetLastError());
     return BOSS_OK;
@@ -1140,6 +1149,213 @@ extern "C" int boss_acq_ei_grad(int P, boss_gp_t* const* gps, int M, const doubl
     }
     hipLaunchKernelGGL(ei_grad_kernel, dim3((M + 127) / 128), dim3(128), 0, s, (const double*)dmu, (const double*)dvar,
                        (const double*)dgm, (const double*)dgv, M, d, par, (const double*)dcoef, (const double*)dymax,
+                       valid_mask ? (const unsigned char*)dmask : nullptr, dacq, ddacq);
+    return finish(c, {{acq_out, dacq, sizeof(double) * M}, {dacq_out, ddacq, sizeof(double) * dm}});
+}
+
+// ------------------------------------------------------------------------------------------
+// Moments AND moment gradients of a SET of equally shaped posteriors at the same candidates (boss_acq_ei_grad_set): the forward
+// substitution of all members through predict_set_enqueue, and behind every group of members the adjoint substitution
+// (backsolve_set_kernel, grid = tiles × members) and the accumulation (grad_accum_set_kernel / aug_grad_accum_set_kernel).
+// ------------------------------------------------------------------------------------------
+static bool grad_set_ok(int n, boss_gp_t* const* gps, const boss_cand* cd) {
+    if (!predict_set_ok(n, gps, cd)) return false;
+    const boss_gp* g0 = gps[0];
+    // (N <= 128 with few candidates: the one-launch small_predict_grad_kernel of grad_enqueue is the better path)
+    return !g0->gibbs && !small_predict_ok(g0, cd->M) && (!g0->aug || g0->d <= AUG_MAX_D);
+}
+
+// mu / var of member i at mu_all + i·M (unclipped), ∇μ / ∇σ² at gm_all + i·d·M; mean_all / mg_all (or null): the prior means and
+// their gradients in the same layouts.  Caller holds the context lock and has checked grad_set_ok.  BOSS_E_ALLOC: nothing the
+// caller relies on has been written (what was enqueued is overwritten by the member-by-member path the caller turns to).
+static int grad_set_enqueue(int n, boss_gp_t* const* gps, const boss_cand* cd, const double* mean_all, const double* mg_all,
+                            double* mu_all, double* var_all, double* gm_all, double* gv_all) {
+    boss_gp* g0 = gps[0];
+    Ctx* c = g0->ctx;
+    hipStream_t s = c->stream;
+    typedef PredG32 G;
+    const int d = g0->d, Np = g0->Np, ld = g0->ld, M = cd->M, Mp = cd->Mp;
+    const int tiles = (M + 31) / 32, nb = Np / PRED_RB;
+    const size_t dm = (size_t)d * M;
+    const size_t glds = sizeof(double) * ((size_t)d * GRAD_CHUNK + GRAD_CHUNK + 8 * 2 * (GRAD_MAX_D + 1) * 32);
+    if (!g0->aug && glds > 150 * 1024) return fail(BOSS_E_INVALID, "x_dim too large for the gradient kernel's LDS staging");
+    std::vector<int> prep;                                   // members whose transposed factor is not current
+    for (int i = 0; i < n; ++i) {
+        boss_gp* g = gps[i];
+        if (!g->LT) {
+            if (dev_malloc((void**)&g->LT, sizeof(double) * (size_t)ld * Np) != hipSuccess ||
+                dev_malloc((void**)&g->DT2, sizeof(double) * (size_t)Np * PRED_RB) != hipSuccess ||
+                dev_malloc((void**)&g->avec, sizeof(double) * (size_t)Np * 2) != hipSuccess) {
+                if (g->LT) (void)hipFree(g->LT);
+                if (g->DT2) (void)hipFree(g->DT2);
+                g->LT = g->DT2 = g->avec = nullptr;
+                (void)hipGetLastError();
+                return fail(BOSS_E_ALLOC, "device allocation failed (transposed factor)");
+            }
+            g->have_lt = false;
+        }
+        if (!g->have_lt) prep.push_back(i);
+    }
+    // scratch whose addresses go into the descriptors, or that a later group must not move: reserved before anything is enqueued
+    int rc = g0->aug ? BOSS_OK : ws_reserve(c->csc, sizeof(double) * (size_t)d * Mp * n);
+    if (rc) return rc;
+    const size_t part_one = (size_t)32 * (g0->aug ? 2 * AUG_MAX_D : 2 * (GRAD_MAX_D + 1));   // doubles per (member, tile, split)
+    // workgroups wanted in flight before the rows of a tile stop being split (BOSS_SET_GRAD_FILL overrides, 0: never split)
+    static const int fill_env = getenv("BOSS_SET_GRAD_FILL") ? std::max(0, atoi(getenv("BOSS_SET_GRAD_FILL"))) : -1;
+    const int fill = fill_env >= 0 ? fill_env : 2 * c->n_cus;
+    rc = ws_reserve(c->few, sizeof(double) * part_one * std::max((size_t)fill, (size_t)n * tiles));
+    if (rc) return rc;
+    const size_t ndesc = (size_t)n + prep.size();
+    rc = ws_reserve(c->gsetdesc, sizeof(GradSet) * ndesc);
+    if (rc) return rc;
+    std::vector<GradSet> desc(ndesc);
+    for (int i = 0; i < n; ++i) {
+        const boss_gp* g = gps[i];
+        GradSet& q = desc[i];
+        q.A = g->A;
+        q.Dinv2 = g->Dinv2;
+        q.LT = g->LT;
+        q.DT2 = g->DT2;
+        q.avec = g->avec;
+        q.Xsc = g->Xsc;
+        q.Xraw = g->Xraw;
+        q.Csc = g0->aug ? nullptr : (const double*)c->csc.p + (size_t)i * d * Mp;   // (where predict_set_enqueue puts them)
+        q.invlam = g->invlam;
+        q.mean_grad = mg_all ? mg_all + (size_t)i * dm : nullptr;
+        q.dmu = gm_all + (size_t)i * dm;
+        q.dvar = gv_all + (size_t)i * dm;
+        q.amp2 = g->amp2;
+    }
+    for (size_t k = 0; k < prep.size(); ++k) desc[n + k] = desc[prep[k]];
+    const size_t dbytes = sizeof(GradSet) * ndesc;
+    if (dbytes <= PINNED_UP_BYTES) {
+        void* stage = (char*)c->pinned + PINNED_UP_OFF;
+        HIPCHK(hipEventSynchronize(c->ev_up));               // (the candidates' upload out of the same area)
+        std::memcpy(stage, desc.data(), dbytes);
+        HIPCHK(hipMemcpyAsync(c->gsetdesc.p, stage, dbytes, hipMemcpyHostToDevice, s));
+        HIPCHK(hipEventRecord(c->ev_up, s));
+    } else {
+        HIPCHK(hipMemcpyAsync(c->gsetdesc.p, desc.data(), dbytes, hipMemcpyHostToDevice, s));
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    const GradSet* gsets = (const GradSet*)c->gsetdesc.p;
+    if (!prep.empty()) {
+        // once per factorisation, for all members that need it together: LT, DT2 and a = L⁻ᵀz in 256-row steps from the last to the
+        // first; grid.z of the DT2 transposition is member · nb + block, so at most 65535 / nb members per launch
+        set_dinv_enqueue(n, gps, s);
+        const int np = (int)prep.size(), chunk = 65535 / nb;
+        for (int k0 = 0; k0 < np; k0 += chunk) {
+            const int kc = std::min(chunk, np - k0);
+            const GradSet* ps = gsets + n + k0;
+            hipLaunchKernelGGL(transpose_set_kernel, dim3(Np / 64, Np / 64, kc), dim3(256), 0, s, ps, 0, ld, Np);
+            hipLaunchKernelGGL(transpose_set_kernel, dim3(PRED_RB / 64, PRED_RB / 64, nb * kc), dim3(256), 0, s, ps, 1, ld, Np);
+            for (int ib = nb - 1; ib >= 0; --ib) {
+                const int nch = nb - 1 - ib;
+                if (nch > 0) hipLaunchKernelGGL(bt_gemv_partial_set_kernel, dim3(nch, kc), dim3(256), 0, s, ps, ld, Np, ib);
+                hipLaunchKernelGGL(bt_finish_set_kernel, dim3(1, kc), dim3(256), 0, s, ps, ld, Np, g0->N, ib, nch);
+            }
+        }
+        HIPCHK(hipGetLastError());
+        // (the launches are on the stream already: an error later in this call ends in drain(), which waits for them, so the arrays
+        // are current whatever the call returns)
+        for (int i : prep) gps[i]->have_lt = true;
+    }
+    std::function<int(int, int)> after = [&](int i0, int cnt) -> int {
+        double* slabs = (double*)c->vscratch.p;
+        ++c->set_grad_launches;
+        hipLaunchKernelGGL(backsolve_set_kernel<G>, dim3(tiles, cnt), dim3(G::NTHREADS), PredictLds<G>::BYTES, s, gsets + i0, ld, Np, slabs);
+        // members × tiles fill the chip on their own from 2 workgroups per CU on; below that the rows of a tile are split as in grad_enqueue
+        const int wgs = tiles * cnt;
+        int rsplit = wgs >= fill ? 1 : std::min(32, std::max(1, fill / wgs));
+        double* part = (double*)c->few.p;
+        if (g0->aug) {
+            rsplit = std::max(1, std::min(rsplit, (g0->npts + 63) / 64));
+            hipLaunchKernelGGL(aug_grad_accum_set_kernel, dim3(tiles, rsplit, cnt), dim3(256), 0, s, gsets + i0, (const double*)slabs, Np, g0->npts,
+                               g0->ldx, (const double*)cd->Craw, d, Mp, M, g0->kernel, rsplit > 1 ? part : nullptr);
+            if (rsplit > 1)
+                hipLaunchKernelGGL(aug_grad_finalize_set_kernel, dim3(tiles, cnt), dim3(32), 0, s, gsets + i0, (const double*)part, rsplit, d, M);
+        } else {
+            if (d > GRAD_MAX_D) rsplit = 1;
+            rsplit = std::max(1, std::min(rsplit, (g0->N + GRAD_CHUNK - 1) / GRAD_CHUNK));
+            hipLaunchKernelGGL(grad_accum_set_kernel, dim3(tiles, rsplit, cnt), dim3(256), glds, s, gsets + i0, (const double*)slabs, Np, g0->N, d,
+                               Mp, M, g0->kernel, (const unsigned char*)g0->discrete_dev, rsplit > 1 ? part : nullptr);
+            if (rsplit > 1)
+                hipLaunchKernelGGL(grad_finalize_set_kernel, dim3(tiles, cnt), dim3(32), 0, s, gsets + i0, (const double*)part, rsplit, d, Mp, M,
+                                   (const unsigned char*)g0->discrete_dev);
+        }
+        HIPCHK(hipGetLastError());
+        return BOSS_OK;
+    };
+    return predict_set_enqueue(n, gps, cd, mean_all, mu_all, var_all, (size_t)M, nullptr, nullptr, &after);
+}
+
+// boss_acq_ei_grad averaged over S hyper-parameter samples in one call (expected_improvement.jl:87-90 inside the multistart
+// refinement of optimization.jl:89-118): gps[p + P·s]; the candidates are uploaded once, every member's moments and moment
+// gradients stay on the device ([s][p] slices), and ONE epilogue applies the chain rule per sample and sums in ascending s.
+// Equally shaped members take the set launches (grad_set_enqueue); any other list, BOSS_NO_SET_PREDICT=1 and a set-path
+// allocation failure go member by member through grad_enqueue into the same slices.
+extern "C" int boss_acq_ei_grad_set(int P, int S, boss_gp_t* const* gps, int M, const double* Xs, const double* mean_Xs,
+                                    const double* mean_grad, const double* fit_coefs, const double* y_max, int has_best,
+                                    double best, const unsigned char* valid_mask, double* acq_out, double* dacq_out) {
+    if (P < 1 || S < 1 || !gps || M < 1 || !Xs || !fit_coefs || !acq_out || !dacq_out) return fail(BOSS_E_INVALID, "bad arguments");
+    if ((long long)P * S * M > (1LL << 30)) return fail(BOSS_E_INVALID, "P·S·M above 2^30 is not supported");
+    const int n = P * S;
+    for (int i = 0; i < n; ++i) {
+        if (!gps[i]) return fail(BOSS_E_INVALID, "NULL posterior handle");
+        NOT_FOR_GIBBS(gps[i], mean_Xs, mean_grad);
+        if (gps[i]->ctx != gps[0]->ctx || gps[i]->d != gps[0]->d)
+            return fail(BOSS_E_INVALID, "all handles must live on one device and share x_dim");
+    }
+    for (int i = 0; i < n; ++i)
+        if (!gps[i]->fitted) return fail(BOSS_E_NOT_FITTED, "handle has no valid factorisation");
+    if (S == 1)
+        return boss_acq_ei_grad(P, gps, M, Xs, mean_Xs, mean_grad, fit_coefs, y_max, has_best, best, valid_mask, acq_out, dacq_out);
+    Ctx* c = gps[0]->ctx;
+    HIPCHK(hipSetDevice(c->device));
+    std::lock_guard<std::mutex> lk(c->mtx);
+    const int d = gps[0]->d;
+    boss_cand cd;
+    int rc = temp_cand(c, d, M, Xs, &cd);
+    if (rc) return drain(c, rc);
+    hipStream_t s = c->stream;
+    const size_t dm = (size_t)d * M, nm = (size_t)n * M, ndm = (size_t)n * dm;
+    // device scratch: acq[M] | dacq[dM] | mu[n][M] | var[n][M] | dmu[n][dM] | dvar[n][dM] | mean[n][M] | mean_grad[n][dM] | coefs[P] | ymax[P] | mask
+    const size_t nd = M + dm + 3 * nm + 3 * ndm + 2 * (size_t)P;
+    rc = ws_reserve(c->pred, sizeof(double) * nd + M);
+    if (rc) return drain(c, rc);
+    double* dacq = (double*)c->pred.p;
+    double* ddacq = dacq + M;
+    double* dmu = ddacq + dm;
+    double* dvar = dmu + nm;
+    double* dgm = dvar + nm;
+    double* dgv = dgm + ndm;
+    double* dmean = dgv + ndm;
+    double* dmg = dmean + nm;
+    double* dcoef = dmg + ndm;
+    double* dymax = dcoef + P;
+    unsigned char* dmask = (unsigned char*)(dacq + nd);
+    EiPar par;
+    rc = ei_params(c, s, P, fit_coefs, y_max, has_best, best, &par, dcoef, dymax);
+    if (rc) return drain(c, rc);
+    if (mean_Xs) (void)hipMemcpyAsync(dmean, mean_Xs, sizeof(double) * nm, hipMemcpyHostToDevice, s);
+    if (mean_grad) (void)hipMemcpyAsync(dmg, mean_grad, sizeof(double) * ndm, hipMemcpyHostToDevice, s);
+    if (valid_mask) (void)hipMemcpyAsync(dmask, valid_mask, M, hipMemcpyHostToDevice, s);
+    if (par.mode != 0) {
+        static const bool set_off = getenv("BOSS_NO_SET_PREDICT") && atoi(getenv("BOSS_NO_SET_PREDICT"));
+        bool done = false;
+        if (!set_off && grad_set_ok(n, gps, &cd)) {
+            rc = grad_set_enqueue(n, gps, &cd, mean_Xs ? dmean : nullptr, mean_grad ? dmg : nullptr, dmu, dvar, dgm, dgv);
+            if (rc != BOSS_OK && rc != BOSS_E_ALLOC) return drain(c, rc);
+            done = rc == BOSS_OK;                            // (no memory for the set launches: the call goes on member by member)
+        }
+        for (int i = 0; i < n && !done; ++i) {
+            rc = grad_enqueue(gps[i], &cd, mean_Xs ? dmean + (size_t)i * M : nullptr, mean_grad ? dmg + (size_t)i * dm : nullptr,
+                              dmu + (size_t)i * M, dvar + (size_t)i * M, dgm + (size_t)i * dm, dgv + (size_t)i * dm);
+            if (rc) return drain(c, rc);
+        }
+    }
+    hipLaunchKernelGGL(ei_grad_set_kernel, dim3((M + 127) / 128), dim3(128), 0, s, (const double*)dmu, (const double*)dvar, (const double*)dgm,
+                       (const double*)dgv, M, d, S, par, (const double*)dcoef, (const double*)dymax,
                        valid_mask ? (const unsigned char*)dmask : nullptr, dacq, ddacq);
     return finish(c, {{acq_out, dacq, sizeof(double) * M}, {dacq_out, ddacq, sizeof(double) * dm}});
 }

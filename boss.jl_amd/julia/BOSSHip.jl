@@ -553,6 +553,31 @@ function acq_value_and_grad(problem::BOSS.BossProblem, post, X::AbstractMatrix{<
         something(b, 0.0), ei.cons_safe ? mask : C_NULL, acq, dacq))
     return acq, dacq          # feed an Optimization.jl OptimizationFunction(f; grad = ...) per start, or batch the starts
 end
+# the same averaged over the S posteriors of BIParams (expected_improvement.jl:87-90) in ONE device call: handles [p + P*s], prior
+# means M×P×S, their gradients d×M×P×S; equally shaped posteriors run every substitution with grid = candidate tiles × members
+function acq_value_and_grad_set(problem::BOSS.BossProblem, posts::AbstractVector, X::AbstractMatrix{<:Real})
+    ei = problem.acquisition::BOSS.ExpectedImprovement{<:BOSS.LinFitness}
+    P = BOSS.y_dim(problem); S = length(posts); Xs = Matrix{Float64}(X); d, M = size(Xs)
+    hs = Ptr{Cvoid}[post.slices[p].h.h for post in posts for p in 1:P]
+    b = BOSS.best_so_far(problem, ei.fitness)
+    mask = UInt8[BOSS.in_bounds(x, problem.domain.bounds) && BOSS.in_cons(x, problem.domain.cons) for x in eachcol(Xs)]
+    ms, mg = C_NULL, C_NULL
+    if any(post -> any(has_mean, post.slices), posts)
+        ms = zeros(M, P, S); mg = zeros(d, M, P, S)
+        for (s, post) in enumerate(posts), (p, sl) in enumerate(post.slices)
+            isnothing(sl.mean) && continue
+            ms[:, p, s] .= mean_vals(sl.mean, Xs)
+            sl.mean isa Function && (mg[:, :, p, s] .= reduce(hcat, (BOSS.ForwardDiff.gradient(sl.mean, Vector(x)) for x in eachcol(Xs))))
+        end
+    end
+    acq = Vector{Float64}(undef, M); dacq = Matrix{Float64}(undef, d, M)
+    GC.@preserve posts check(ccall((:boss_acq_ei_grad_set, lib), Cint,
+        (Cint, Cint, Ptr{Ptr{Cvoid}}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cdouble,
+         Ptr{UInt8}, Ptr{Cdouble}, Ptr{Cdouble}),
+        P, S, hs, M, Xs, ms, mg, Float64.(ei.fitness.coefs), Float64[c for c in problem.y_max], isnothing(b) ? 0 : 1,
+        something(b, 0.0), ei.cons_safe ? mask : C_NULL, acq, dacq))
+    return acq, dacq
+end
 # ---------------------------------------------------------------- likelihood gradient for OptimizationMAP-style fitters
 # (value, gradient) of the data log-likelihood of output slice i at hyper-parameters p, on resident data:
 function loglike_and_grad!(h::Ptr{Cvoid}, λ::Vector{Float64}, α::Float64, σ::Float64, mean_X)
@@ -580,8 +605,8 @@ end
 `HipGradientAM` — OptimizationAM semantics (src/acquisition_maximizers/optimization.jl:13-118): multistart LOCAL optimisation of
 the acquisition from `multistart` starts inside the domain, the best local optimum wins (`optimize_multistart`,
 src/utils/optim_multistart.jl).  The reference differentiates the acquisition with ForwardDiff (:36) one start at a time; here
-the gradient is analytic and evaluated on the device for ALL starts in one call per iteration (`boss_acq_ei_grad`): projected
-gradient ascent with a per-start step and backtracking.  Discrete dimensions are rounded (gradient 0); `cons` is honoured through
+the gradient is analytic and evaluated on the device for ALL starts in one call per iteration (`boss_acq_ei_grad`; with
+`BIParams` `boss_acq_ei_grad_set`: all samples in the same call): projected gradient ascent with a per-start step and backtracking.  Discrete dimensions are rounded (gradient 0); `cons` is honoured through
 make_safe (acq = 0 outside) and a final in-domain filter.  Works on `HipGaussianProcess` / `HipSemiparametric` posteriors and on those of
 `HipGradientGaussianProcess` (`boss_acq_ei_grad` differentiates the augmented cross-covariances of src/models/gradient_gp.jl:221-243 as well).
 """
@@ -595,10 +620,8 @@ function maximize_acquisition(am::HipGradientAM, problem::BOSS.BossProblem, opti
     dom = problem.domain; lb, ub = Float64.(dom.bounds[1]), Float64.(dom.bounds[2])
     X = Matrix{Float64}(BOSS.get_starts(am.multistart, dom))              # LHC starts (optimization.jl:78-88) or the given ones
     posts isa AbstractVector || (posts = [posts])
-    value_and_grad(Z) = begin                                              # BI: the sample mean of acquisition and gradient (:87-90)
-        vg = [acq_value_and_grad(problem, post, Z) for post in posts]
-        sum(first.(vg)) ./ length(posts), sum(last.(vg)) ./ length(posts)
-    end
+    # BIParams: the sample mean of acquisition and gradient (:87-90) in one device call per iteration (boss_acq_ei_grad_set)
+    value_and_grad(Z) = length(posts) > 1 ? acq_value_and_grad_set(problem, posts, Z) : acq_value_and_grad(problem, posts[1], Z)
     span = map((l, u) -> isfinite(u - l) ? u - l : 1.0, lb, ub); cont = .!dom.discrete
     f, g = value_and_grad(X); step = fill(0.05, size(X, 2))                # step relative to the box, per start
     for _ in 1:am.iters

@@ -370,7 +370,8 @@ class HipGradientAM:
     optimisation of the acquisition, started from `multistart` x_prior samples inside the domain, the
     best local optimum wins (optim_multistart.jl).  The reference differentiates the acquisition with
     ForwardDiff (optimization.jl:36) one start at a time; here the gradient is analytic and evaluated
-    on the device (boss_acq_ei_grad) for ALL starts in one call per iteration: projected gradient
+    on the device (boss_acq_ei_grad; boss_acq_ei_grad_set for the S samples of a BI fit) for ALL starts in one call per
+    iteration: projected gradient
     ascent with a per-start Barzilai–Borwein step and backtracking.  Discrete dimensions are rounded
     (their gradient is zero), `cons` is honoured through make_safe (acq = 0 outside) and a final
     in-domain filter.  Multi-GPU: the starts are sharded across ranks, 16-byte arg-max exchange.
@@ -389,17 +390,30 @@ class HipGradientAM:
             raise NotImplementedError("HipGradientAM needs the analytic EI of LinFitness")
         b = best_so_far(ei.fitness, problem.data.Y, problem.y_max)
         mask = (in_bounds(X, problem.domain.bounds) & in_cons(X, problem.domain.cons)) if ei.cons_safe else None
-        acc, gacc = 0.0, 0.0
-        for post in posts:                                   # BI: the acquisition (and its gradient) is the sample mean
-            gps = [s.gp for s in post.slices]
+        M = X.shape[1]
+        mg = None                                            # P×d×M Jacobian of the prior mean: the same for every sample
+        if self.mean_grad is not None:
+            mg = np.stack([np.asarray(self.mean_grad(X[:, j]), float) for j in range(M)], axis=2)
+
+        def means(post):                                     # P×M prior means of one sample, or None when no slice has one
+            rows = [s._mean_s(X) for s in post.slices]
+            if all(r is None for r in rows):
+                return None
+            return np.stack([np.zeros(M) if r is None else np.asarray(r, float) for r in rows])
+
+        nonstat = any(isinstance(s.gp, api.GibbsGP) for post in posts for s in post.slices)
+        if len(posts) > 1 and not nonstat:
+            # BI: the sample mean of the acquisition and of its gradient in ONE device call (boss_acq_ei_grad_set)
+            mm = [means(post) for post in posts]
             ms = None
-            if post.slices[0]._mean_s(X) is not None:
-                ms = np.stack([s._mean_s(X) for s in post.slices])
-            mg = None
-            if self.mean_grad is not None:
-                J = np.stack([np.asarray(self.mean_grad(X[:, j]), float) for j in range(X.shape[1])], axis=2)   # P×d×M
-                mg = J
-            a, g = api.acq_ei_grad(gps, X, ei.fitness.coefs, problem.y_max, b, mask, ms, mg)
+            if any(m is not None for m in mm):               # samples without a prior mean travel as zeros
+                ms = np.stack([np.zeros((len(post.slices), M)) if m is None else m for m, post in zip(mm, posts)])   # S×P×M
+            mgs = None if mg is None else np.stack([mg] * len(posts))                                              # S×P×d×M
+            return api.acq_ei_grad_set([[s.gp for s in post.slices] for post in posts], X, ei.fitness.coefs, problem.y_max, b,
+                                       mask, ms, mgs)
+        acc, gacc = 0.0, 0.0
+        for post in posts:                                   # one sample (MAP), or nonstationary models: sample by sample
+            a, g = api.acq_ei_grad([s.gp for s in post.slices], X, ei.fitness.coefs, problem.y_max, b, mask, means(post), mg)
             acc, gacc = acc + a, gacc + g
         return acc / len(posts), gacc / len(posts)
 

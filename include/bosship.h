@@ -414,6 +414,26 @@ int boss_acq_ei_grad(int P, boss_gp_t* const* gps, int M, const double* Xs, cons
                      const double* mean_grad, const double* fit_coefs, const double* y_max, int has_best,
                      double best, const unsigned char* valid_mask, double* acq_out, double* dacq_out);
 
+/* boss_acq_ei_grad averaged over the S hyper-parameter samples of a Bayesian-inference fit, in ONE call: what OptimizationAM
+ * differentiates when the model parameters are BI samples (src/acquisitions/expected_improvement.jl:87-90 inside
+ * src/acquisition_maximizers/optimization.jl:89-118).
+ *   gps        S×P handles, gps[p + P*s] as boss_acq_ei: plain (also semiparametric) or gradient-observation posteriors, all on one
+ *              device with one x_dim; nonstationary handles: BOSS_E_INVALID (boss_ngp_predict_grad + boss_acq_ei_grad_moments);
+ *   mean_Xs    NULL or S×P×M, index j + M*(p + P*s);  mean_grad NULL or [s][p][d×M column-major] (both NULL for gradient observations);
+ *   the other arguments as boss_acq_ei_grad.
+ * For every sample s, (acq_s, grad acq_s) are exactly what boss_acq_ei_grad defines for its P handles; the outputs are
+ * (sum_s acq_s)/S and (sum_s grad acq_s)/S, summed in ascending s and divided once: no atomics, repeated calls agree bit for bit.
+ * S = 1 is boss_acq_ei_grad itself.  Equally shaped members (the members of boss_gp_fit_batch / boss_ggp_fit_batch calls, the
+ * shape test of boss_acq_ei's set prediction) run forward substitution, adjoint substitution and accumulation with grid =
+ * candidate tiles × members; any other list, BOSS_NO_SET_PREDICT=1 and a failed allocation of the set path go member by member
+ * inside the same call (one candidate upload, one copy back).  Either path keeps a transposed copy of every member's factor on the
+ * device (as boss_acq_ei_grad does per handle): when that cannot be allocated the call fails with BOSS_E_ALLOC; what the in-call
+ * fallback saves is a failure of the set path's own scratch (V slabs, partial sums, descriptors).  P*S*M above 2^30: BOSS_E_INVALID.
+ * After an error nothing stays enqueued. */
+int boss_acq_ei_grad_set(int P, int S, boss_gp_t* const* gps, int M, const double* Xs, const double* mean_Xs,
+                         const double* mean_grad, const double* fit_coefs, const double* y_max, int has_best,
+                         double best, const unsigned char* valid_mask, double* acq_out, double* dacq_out);
+
 /* ---- tracked candidates -----------------------------------------------------------------------
  * SequentialBatchAM (src/acquisition_maximizers/batch.jl:26-38) re-evaluates the acquisition on
  * the whole candidate set after every speculative observation; with a FIXED candidate set (GridAM
