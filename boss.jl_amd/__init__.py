@@ -16,6 +16,7 @@ from .gradient_gp import (GradientData, HipGradientGaussianProcess, HipGradientG
                           join_gradient_slices)
 from .nonstationary import HipNonstationaryGP, HipParametrizedGP, stack_latents  # noqa: F401,E402
 from .nonstationary import data_loglike_batch as nonstationary_data_loglike_batch  # noqa: F401,E402
+from .nonstationary import data_loglike_grad_batch as nonstationary_data_loglike_grad_batch  # noqa: F401,E402
 from .nonstationary import nonstationary_acq_ei_batch, nonstationary_model_posterior_batch  # noqa: F401,E402
 from .fitter import HipBatchedMAP, HipGradientMAP, HipSampleOptMAP, MAPParams  # noqa: F401,E402
 from .maximizer import HipBatchAM, HipGradientAM, HipSequentialBatchAM  # noqa: F401,E402

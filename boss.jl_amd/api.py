@@ -60,6 +60,10 @@ SIGNATURES = {
                                          _c_dp, _c_dp, C.POINTER(C.c_int)]),
     "boss_ngp_loglike_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, _c_dp, _c_dp, _c_ucp, C.c_int, _c_dp, _c_dp, _c_dp, _c_dp,
                                          C.c_int, _c_dp, C.POINTER(C.c_int)]),
+    "boss_ggp_loglike_grad_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _c_dp, _c_dp, _c_dp, C.c_int, _c_dp, _c_dp,
+                                              _c_dp, _c_dp, _c_dp, _c_dp, C.POINTER(C.c_int)]),
+    "boss_ngp_loglike_grad_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, _c_dp, _c_dp, _c_ucp, C.c_int, _c_dp, _c_dp, _c_dp, _c_dp,
+                                              C.c_int, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, C.POINTER(C.c_int)]),
     "boss_gp_fit_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _c_dp, _c_dp, _c_dp, C.c_int, _c_ucp,
                                     C.c_int, _c_dp, _c_dp, _c_dp, C.POINTER(C.c_void_p), _c_dp, C.POINTER(C.c_int)]),
     "boss_ggp_fit_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _c_dp, _c_dp, _c_dp, C.c_int, _c_dp, _c_dp, _c_dp,
@@ -825,6 +829,41 @@ def ngp_loglike_batch(X, y, lam_X, amp_X, noise_X, mean_X=None, discrete=None, d
     _check(load_library().boss_ngp_loglike_batch(device, d, N, _dp(X), _dp(y), _ucp(disc), S, _dp(lam), _dp(amp), _dp(noi), _dp(m),
                                                  stride, _dp(ll), st.ctypes.data_as(C.POINTER(C.c_int))))
     return ll, st
+
+
+def ggp_loglike_grad_batch(X, y, dY, kernel, lengthscales, amplitudes, noise_stds, grad_noise_stds, device: int = 0):
+    """ggp_loglike_batch with the gradient of every log-likelihood in the same device call (boss_ggp_loglike_grad_batch): what
+    GradGP.update + GradGP.loglike_grad give set by set.  Returns (ll[S], status[S], grad[(d+3), S]); column s of grad is
+    ∂ℓ/∂(λ_1..λ_d, α, σ, σ_∂) of set s, zeros (and ll = -Inf) where the set is not PD or holds a negative parameter."""
+    X, y, dY, lam, amp, sig, sgd = _ggp_batch_args(X, y, dY, lengthscales, amplitudes, noise_stds, grad_noise_stds)
+    d, n = X.shape
+    S = lam.shape[1]
+    ll = np.zeros(S)
+    st = np.zeros(S, dtype=np.int32)
+    grad = np.zeros((d + 3, S), order="F")
+    _check(load_library().boss_ggp_loglike_grad_batch(device, _kernel_id(kernel), d, n, _dp(X), _dp(y), _dp(dY), S, _dp(lam),
+                                                      _dp(amp), _dp(sig), _dp(sgd), _dp(ll), _dp(grad),
+                                                      st.ctypes.data_as(C.POINTER(C.c_int))))
+    return ll, st, grad
+
+
+def ngp_loglike_grad_batch(X, y, lam_X, amp_X, noise_X, mean_X=None, discrete=None, device: int = 0):
+    """ngp_loglike_batch with the partial derivatives w.r.t. the latent values of every set in the same device call
+    (boss_ngp_loglike_grad_batch): what NonstatGP.update + NonstatGP.loglike_grad give set by set.  Returns (ll[S], status[S],
+    dlam[d, N, S], damp[N, S], dnoise[N, S], dmean[N, S]); zeros (and ll = -Inf) where a set is not PD or invalid."""
+    X, y, lam, amp, noi, m, stride, disc = _ngp_batch_args(X, y, lam_X, amp_X, noise_X, mean_X, discrete)
+    d, N = X.shape
+    if d > 16:
+        raise BossError(BOSS_E_INVALID, "x_dim above 16 is not supported by the nonstationary gradient kernels")
+    S = lam.shape[2]
+    ll = np.zeros(S)
+    st = np.zeros(S, dtype=np.int32)
+    dlam = np.zeros((d, N, S), order="F")
+    damp, dnoise, dmean = (np.zeros((N, S), order="F") for _ in range(3))
+    _check(load_library().boss_ngp_loglike_grad_batch(device, d, N, _dp(X), _dp(y), _ucp(disc), S, _dp(lam), _dp(amp), _dp(noi),
+                                                      _dp(m), stride, _dp(ll), _dp(dlam), _dp(damp), _dp(dnoise), _dp(dmean),
+                                                      st.ctypes.data_as(C.POINTER(C.c_int))))
+    return ll, st, dlam, damp, dnoise, dmean
 
 
 def ggp_fit_batch(X, y, dY, kernel, lengthscales, amplitudes, noise_stds, grad_noise_stds, device: int = 0):

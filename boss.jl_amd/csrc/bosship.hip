@@ -573,6 +573,7 @@ static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 struct SetBatch {
     int nb = 1;
     size_t sA = 0, sInv16 = 0, sDinv = 0, sDinv2 = 0, sW = 0, sX = 0;
+    size_t sPar = 0;                           // the gradient / nonstationary model's parameter block (likelihood-gradient batches)
 };
 static void linv_enqueue(boss_gp* g, hipStream_t s, double* U, double* Lw, const SetBatch& B = SetBatch());
 // largest system the entry points accept: element offsets into the factor stay below 2^31 (exercised up to

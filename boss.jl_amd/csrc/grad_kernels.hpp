@@ -948,8 +948,12 @@ __global__ __launch_bounds__(256) void llgrad_reduce_kernel(const double* __rest
 //   ∂ℓ/∂σ_i = σ_i G_ii ,  ∂ℓ/∂m_i = a_i ,     G = a aᵀ − K⁻¹,  q_l = λ_il² + λ_jl²,  Δ_l = x_il − x_jl.
 // K⁻¹ arrives with its lower triangle valid (kinv_syrk_kernel); mirror_lower_kernel fills the upper one so that row i of the
 // symmetric matrix is read as column i (coalesced over the 64 rows of a workgroup).
+// blockIdx.z = parameter set (boss_ngp_loglike_grad_batch) in all four kernels: the rounded points are shared, set z has its K⁻¹
+// at z·zW, its latent values λ [d][Np] | α [Np] | σ [Np] at z·zPar, its partials at z·zC and its (d + 3)·Np results at z·zO.  A
+// single handle's call is the one-set case (grid.z = 1, strides 0).
 // ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void mirror_lower_kernel(double* __restrict__ A, int ld, int Np) {
+__global__ __launch_bounds__(256) void mirror_lower_kernel(double* __restrict__ A, int ld, int Np, size_t zW) {
+    A += (size_t)blockIdx.z * zW;
     __shared__ double t[64][65];
     const int bi = blockIdx.x, bj = blockIdx.y;
     if (bj >= bi) return;                                    // (strictly lower tiles are copied into their mirror images; diagonal tiles: below)
@@ -958,7 +962,8 @@ __global__ __launch_bounds__(256) void mirror_lower_kernel(double* __restrict__ 
     __syncthreads();
     for (int c = cg; c < 64; c += 4) A[(size_t)(bi * 64 + c) * ld + bj * 64 + r] = t[r][c];   // element (row bj·64 + r, column bi·64 + c) = (bi·64 + c, bj·64 + r)
 }
-__global__ __launch_bounds__(256) void mirror_diag_kernel(double* __restrict__ A, int ld) {
+__global__ __launch_bounds__(256) void mirror_diag_kernel(double* __restrict__ A, int ld, size_t zW) {
+    A += (size_t)blockIdx.z * zW;
     const int b = blockIdx.x, r = threadIdx.x & 63, cg = threadIdx.x >> 6;
     for (int c = cg; c < 64; c += 4)
         if (c > r) A[(size_t)(b * 64 + c) * ld + b * 64 + r] = A[(size_t)(b * 64 + r) * ld + b * 64 + c];
@@ -968,7 +973,12 @@ __global__ __launch_bounds__(256) void mirror_diag_kernel(double* __restrict__ A
 __global__ __launch_bounds__(256) void gibbs_llgrad_kernel(const double* __restrict__ X, const double* __restrict__ Lam,
                                                            const double* __restrict__ amp, int d, int N, int Np,
                                                            const double* __restrict__ Kinv, int ldk, const double* __restrict__ apart,
-                                                           int nch, double* __restrict__ part) {
+                                                           int nch, double* __restrict__ part, size_t zPar, size_t zW, size_t zC) {
+    Lam += (size_t)blockIdx.z * zPar;
+    amp += (size_t)blockIdx.z * zPar;
+    Kinv += (size_t)blockIdx.z * zW;
+    apart += (size_t)blockIdx.z * zC;
+    part += (size_t)blockIdx.z * zC;
     constexpr int DM = GIBBS_GRAD_MAX_D;
     __shared__ double xj[DM][64], lj[DM][64], aj[64], mj[64];
     const int tid = threadIdx.x, r = tid & 63, cg = tid >> 6;
@@ -1031,7 +1041,13 @@ __global__ __launch_bounds__(256) void gibbs_llgrad_kernel(const double* __restr
 // out: dlam [d][Np] | damp [Np] | dnoise [Np] | dmean [Np], the parts summed in slot order
 __global__ __launch_bounds__(256) void gibbs_llgrad_reduce_kernel(const double* __restrict__ part, int nparts, int d, int N, int Np,
                                                                   const double* __restrict__ noise, const double* __restrict__ Kinv, int ldk,
-                                                                  const double* __restrict__ apart, int nch, double* __restrict__ out) {
+                                                                  const double* __restrict__ apart, int nch, double* __restrict__ out,
+                                                                  size_t zPar, size_t zW, size_t zC, size_t zO) {
+    part += (size_t)blockIdx.z * zC;
+    noise += (size_t)blockIdx.z * zPar;
+    Kinv += (size_t)blockIdx.z * zW;
+    apart += (size_t)blockIdx.z * zC;
+    out += (size_t)blockIdx.z * zO;
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= Np) return;
     for (int v = 0; v <= d; ++v) {

@@ -277,10 +277,19 @@ __device__ __forceinline__ double aug_entry_dlam(int kern, double amp2, int d, c
 //   out[tile][0..d-1] = Σ w G_ab ∂K_ab/∂λ_m ,  out[tile][d] = Σ w G_ab K⁰_ab (noise-free entries) ,
 //   out[tile][d+1] = Σ_{a value row} G_aa ,  out[tile][d+2] = Σ_{a derivative row} G_aa ,
 // w = 1 below the diagonal (the pair counts twice in ½ Σ_ab), ½ on it;  G = a aᵀ − K⁻¹ with a summed from its nch partials.
+// blockIdx.z = parameter set (boss_ggp_loglike_grad_batch): the raw points are shared, set z reads its 1/λ and hyp at
+// z·par_bstride (the block aug_gram_kernel reads), its K⁻¹ at z·zW, its partials of a at z·zC and writes its tile sums at z·zC.
+// A single handle's call is the one-set case (grid.z = 1, strides 0): a set's sums do not depend on where it stands in a batch.
 __global__ __launch_bounds__(256) void aug_llgrad_tile_kernel(const double* __restrict__ Xraw, int ldx, int d, int n, int N, int Np, int kern,
                                                               const double* __restrict__ hyp, const double* __restrict__ invlam,
-                                                              const double* __restrict__ Kinv, int ldk, const double* __restrict__ apart,
-                                                              int nch, double* __restrict__ out) {
+                                                              size_t par_bstride, const double* __restrict__ Kinv, int ldk,
+                                                              const double* __restrict__ apart, int nch, double* __restrict__ out, size_t zW,
+                                                              size_t zC) {
+    hyp += (size_t)blockIdx.z * par_bstride;
+    invlam += (size_t)blockIdx.z * par_bstride;
+    Kinv += (size_t)blockIdx.z * zW;
+    apart += (size_t)blockIdx.z * zC;
+    out += (size_t)blockIdx.z * zC;
     __shared__ double xa[AUG_MAX_D][64], xb[AUG_MAX_D][64], il[AUG_MAX_D], ab[64], red[256];
     __shared__ int la[64], lb[64];
     const int tid = threadIdx.x, t = blockIdx.x;

@@ -192,7 +192,9 @@ static int llgrad_enqueue(boss_gp* g, hipStream_t s, double* sums_out, int bank,
                           int amp2_stride) {
     // bank: which set of workspaces (the batched entry point rotates large sets over several streams);
     // B: nb equally shaped posteriors behind g's pointers (small sets: every launch covers the whole group in grid.z),
-    //    α² of set b at amp2_dev[b · amp2_stride], its Σ-vector at sums_out + b (d+2)
+    //    α² of set b at amp2_dev[b · amp2_stride], its Σ-vector at sums_out + b (d+2); the gradient-observation model's sets have
+    //    their parameter blocks B.sPar apart behind g->invlam / g->hyp and d+3 sums each, the nonstationary model's their latent
+    //    values B.sPar apart behind g->lamX / g->ampX / g->noiseX and (d+3)·Np results each
     Ctx* c = g->ctx;
     const int d = g->d, N = g->N, Np = g->Np, ld = g->ld, nb = B.nb;
     const int nt = Np / 64, ntiles = nt * (nt + 1) / 2, nv = g->aug ? d + 3 : d + 2, nch = 8;   // (gradient-observation model: λ[d], α-sum, two traces)
@@ -232,19 +234,22 @@ static int llgrad_enqueue(boss_gp* g, hipStream_t s, double* sums_out, int bank,
                        Kinv, ld, Bw.sW);
     hipLaunchKernelGGL(avec_partial_kernel, dim3(Np / 256, nch, nb), dim3(256), 0, s, (const double*)LinvT, ld, Np, N,
                        (const double*)g->A, ld, apart, Bw.sW, B.sA, nb > 1 ? sC : (size_t)0);
+    const size_t zC = nb > 1 ? sC : (size_t)0, zPar = nb > 1 ? B.sPar : (size_t)0;
     if (g->gibbs) {
-        // per-point partial derivatives (boss_ngp_loglike_grad): sums_out holds (d + 3) rows of Np
-        hipLaunchKernelGGL(mirror_lower_kernel, dim3(Np / 64, Np / 64), dim3(256), 0, s, Kinv, ld, Np);
-        hipLaunchKernelGGL(mirror_diag_kernel, dim3(Np / 64), dim3(256), 0, s, Kinv, ld);
-        hipLaunchKernelGGL(gibbs_llgrad_kernel, dim3(Np / 64, gibbs_js), dim3(256), 0, s, (const double*)g->Xraw, (const double*)g->lamX,
-                           (const double*)g->ampX, d, N, Np, (const double*)Kinv, ld, (const double*)apart, nch, parts);
-        hipLaunchKernelGGL(gibbs_llgrad_reduce_kernel, dim3((Np + 255) / 256), dim3(256), 0, s, (const double*)parts, gibbs_js * 4, d, N, Np,
-                           (const double*)g->noiseX, (const double*)Kinv, ld, (const double*)apart, nch, sums_out);
+        // per-point partial derivatives (boss_ngp_loglike_grad): sums_out holds (d + 3) rows of Np per set
+        hipLaunchKernelGGL(mirror_lower_kernel, dim3(Np / 64, Np / 64, nb), dim3(256), 0, s, Kinv, ld, Np, Bw.sW);
+        hipLaunchKernelGGL(mirror_diag_kernel, dim3(Np / 64, 1, nb), dim3(256), 0, s, Kinv, ld, Bw.sW);
+        hipLaunchKernelGGL(gibbs_llgrad_kernel, dim3(Np / 64, gibbs_js, nb), dim3(256), 0, s, (const double*)g->Xraw, (const double*)g->lamX,
+                           (const double*)g->ampX, d, N, Np, (const double*)Kinv, ld, (const double*)apart, nch, parts, zPar, Bw.sW, zC);
+        hipLaunchKernelGGL(gibbs_llgrad_reduce_kernel, dim3((Np + 255) / 256, 1, nb), dim3(256), 0, s, (const double*)parts, gibbs_js * 4, d, N,
+                           Np, (const double*)g->noiseX, (const double*)Kinv, ld, (const double*)apart, nch, sums_out, zPar, Bw.sW, zC,
+                           nb > 1 ? (size_t)(d + 3) * Np : (size_t)0);
         return BOSS_OK;
     }
     if (g->aug)
-        hipLaunchKernelGGL(aug_llgrad_tile_kernel, dim3(ntiles), dim3(256), 0, s, (const double*)g->Xraw, g->ldx, d, g->npts, N, Np, g->kernel,
-                           (const double*)g->hyp, (const double*)g->invlam, (const double*)Kinv, ld, (const double*)apart, nch, parts);
+        hipLaunchKernelGGL(aug_llgrad_tile_kernel, dim3(ntiles, 1, nb), dim3(256), 0, s, (const double*)g->Xraw, g->ldx, d, g->npts, N, Np,
+                           g->kernel, (const double*)g->hyp, (const double*)g->invlam, zPar, (const double*)Kinv, ld, (const double*)apart, nch,
+                           parts, Bw.sW, zC);
     else
     hipLaunchKernelGGL(llgrad_tile_kernel, dim3(ntiles, 1, nb), dim3(256), 0, s, (const double*)g->Xsc, d, N, Np, g->kernel, amp2_dev,
                        amp2_stride, (const double*)Kinv, ld, (const double*)apart, nch, parts, B.sX, Bw.sW, nb > 1 ? sC : (size_t)0,
@@ -351,6 +356,15 @@ extern "C" int boss_ngp_loglike_grad(boss_gp_t* g, double* logpdf_out, double* d
     return BOSS_OK;
 }
 
+// ∂ℓ/∂(λ_1..λ_d, α, σ, σ_∂) of the gradient-observation model from its d+3 sums h; hp = [1/(λ+1e-8) (d) | (α+1e-8)², (σ+1e-8)²,
+// (σ_∂+1e-8)²], the staged parameters (a handle's host_par, a batch's parameter block)
+static void ggp_llgrad_finalize(int d, const double* hp, const double* h, double* grad_out) {
+    for (int m = 0; m < d; ++m) grad_out[m] = h[m];
+    grad_out[d] = 2.0 * h[d] / std::sqrt(hp[d]);
+    grad_out[d + 1] = std::sqrt(hp[d + 1]) * h[d + 1];
+    grad_out[d + 2] = std::sqrt(hp[d + 2]) * h[d + 2];
+}
+
 // data_loglike of a GradientGaussianProcess and its gradient (gradient_gp.jl:367-397 under ForwardDiff, as OptimizationMAP takes it,
 // src/model_fitters/optimization.jl:146-164): grad_out[d + 3] = ∂ℓ/∂(λ_1..λ_d, α, σ, σ_∂) at the parameters of the last boss_ggp_update.
 extern "C" int boss_ggp_loglike_grad(boss_gp_t* g, double* logpdf_out, double* grad_out) {
@@ -366,12 +380,7 @@ extern "C" int boss_ggp_loglike_grad(boss_gp_t* g, double* logpdf_out, double* g
     std::vector<double> h(nv);
     rc = llgrad_download(g, h);
     if (rc) return rc;
-    // host_par holds the staged parameters of the last update: 1/(λ+1e-8), (α+1e-8)², (σ+1e-8)², (σ_∂+1e-8)²
-    const double* hp = g->host_par;
-    for (int m = 0; m < d; ++m) grad_out[m] = h[m];
-    grad_out[d] = 2.0 * h[d] / std::sqrt(hp[d]);
-    grad_out[d + 1] = std::sqrt(hp[d + 1]) * h[d + 1];
-    grad_out[d + 2] = std::sqrt(hp[d + 2]) * h[d + 2];
+    ggp_llgrad_finalize(d, g->host_par, h.data(), grad_out);   // (host_par: the staged parameters of the last update)
     if (logpdf_out) *logpdf_out = loglik(g->N, g->host_res[0], g->host_res[1]);
     return BOSS_OK;
 }

@@ -1,4 +1,4 @@
-// host_batch.inc — boss_gp_loglike_batch, boss_ggp_loglike_batch, boss_ngp_loglike_batch, boss_gp_fit_batch, boss_ggp_fit_batch,
+// host_batch.inc — boss_gp_loglike_batch, boss_ggp_loglike_batch, boss_ngp_loglike_batch and their _grad_batch forms, boss_gp_fit_batch, boss_ggp_fit_batch,
 // boss_ngp_fit_batch: S hyper-parameter sets on one data slice (included by bosship.hip).
 
 // ------------------------------------------------------------------------------------------
@@ -7,6 +7,7 @@
 static int llgrad_enqueue(boss_gp* g, hipStream_t s, double* sums_out, int bank, const SetBatch& B, const double* amp2_dev,
                           int amp2_stride);
 static void llgrad_finalize(int d, int N, const double* invlam, double amp2, double sig2, double zz, const double* h, double* grad_out);
+static void ggp_llgrad_finalize(int d, const double* hp, const double* h, double* grad_out);
 
 // Scaled points, right-hand sides, Gram matrices, factors and log-determinants of nb hyper-parameter sets laid out with constant strides
 // (shared by boss_gp_loglike_batch and boss_gp_fit_batch).  Replaces the S likelihood / posterior evaluations of
@@ -108,6 +109,74 @@ static void set_view(boss_gp* v, Ctx* c, int kernel, int d, int N, int Np, doubl
     v->Dinv2 = Dinv2;
 }
 
+// Padded rows up to which the gradient passes of a batch run in groups (BOSS_LLGRAD_GROUP_NP, read once per process)
+static int llgrad_group_np_max() {
+    static const int v = getenv("BOSS_LLGRAD_GROUP_NP") ? atoi(getenv("BOSS_LLGRAD_GROUP_NP")) : 2048;
+    return v;
+}
+// How many sets of a chunk share one gradient pass (0: no gradients): small sets run in groups (every launch covers the group in
+// grid.z, bounded by 2 GiB of work matrices), large ones set after set
+static int llgrad_group_size(bool grads, int Np, int ld, int chunk) {
+    if (!grads) return 0;
+    const size_t per_set_w = 2 * (size_t)ld * Np * sizeof(double);
+    return Np <= llgrad_group_np_max() ? (int)std::max<size_t>(1, std::min<size_t>((size_t)chunk, ((size_t)2 << 30) / per_set_w)) : 1;
+}
+// one set's Dinv + Dinv2, and what the gradient passes of a chunk need of them: one per bank / per member of a group
+static size_t llgrad_dinv_one(int Np) { return (size_t)(Np / BLK) * BLK * BLK + (size_t)Np * PRED_RB; }
+static size_t llgrad_dinv_doubles(int group, int Np) { return group ? (size_t)std::max(group, (int)Ctx::LLG_BANKS) * llgrad_dinv_one(Np) : 0; }
+
+// The gradient passes of the nb factorised sets of a chunk (shared by the three models' batched likelihood gradients): in groups of
+// `group` sets, or — group = 1 — set after set over up to four streams, each on its own bank of workspaces, so that their small
+// kernels (low levels of the triangular inverse, reductions) overlap the other sets' large ones.  view(v, b, Dinv, Dinv2) makes v a
+// view of set b as a fitted handle; St holds the constant strides between sets; set b's results go to sums + b·sum_stride and its
+// α² (plain model) is read at amp2_dev[2 b].  Everything is complete on s's timeline when the function returns.
+static int llgrad_sets_enqueue(Ctx* c, hipStream_t s, int nb, int group, int Np, double* dinv_scratch, double* sums, size_t sum_stride,
+                               const SetBatch& St, const double* amp2_dev,
+                               const std::function<void(boss_gp*, int, double*, double*)>& view) {
+    const int nblk = Np / BLK;
+    const size_t dinv_one = llgrad_dinv_one(Np);
+    int rc = BOSS_OK;
+    if (group > 1) {
+        for (int b0 = 0; b0 < nb; b0 += group) {
+            boss_gp v;                                       // a view of sets b0 .. b0+cnt-1 as fitted handles with constant strides
+            view(&v, b0, dinv_scratch, dinv_scratch + (size_t)group * nblk * BLK * BLK);
+            SetBatch B = St;
+            B.nb = std::min(group, nb - b0);
+            B.sDinv = (size_t)nblk * BLK * BLK;
+            B.sDinv2 = (size_t)Np * PRED_RB;
+            rc = llgrad_enqueue(&v, s, sums + (size_t)b0 * sum_stride, 0, B, amp2_dev ? amp2_dev + 2 * (size_t)b0 : nullptr, 2);
+            if (rc) {
+                (void)hipDeviceSynchronize();
+                return rc;
+            }
+        }
+        return BOSS_OK;
+    }
+    static const int nbanks_env = getenv("BOSS_LLGRAD_STREAMS") ? atoi(getenv("BOSS_LLGRAD_STREAMS")) : Ctx::LLG_BANKS;
+    const int nbanks = std::max(1, std::min(std::min(nbanks_env, (int)Ctx::LLG_BANKS), nb));
+    if (nbanks > 1) {
+        (void)hipEventRecord(c->ev_fork, s);
+        for (int i = 0; i < nbanks - 1; ++i) (void)hipStreamWaitEvent(c->llg_stream[i], c->ev_fork, 0);
+    }
+    for (int b = 0; b < nb; ++b) {                           // a view of set b as a fitted handle
+        const int bank = b % nbanks;
+        hipStream_t sb = bank ? c->llg_stream[bank - 1] : s;
+        boss_gp v;
+        double* const dinv = dinv_scratch + (size_t)bank * dinv_one;
+        view(&v, b, dinv, dinv + (size_t)nblk * BLK * BLK);
+        rc = llgrad_enqueue(&v, sb, sums + (size_t)b * sum_stride, bank, SetBatch(), amp2_dev ? amp2_dev + 2 * (size_t)b : nullptr, 0);
+        if (rc) {
+            (void)hipDeviceSynchronize();
+            return rc;
+        }
+    }
+    for (int i = 0; i < nbanks - 1; ++i) {
+        (void)hipEventRecord(c->llg_join[i], c->llg_stream[i]);
+        (void)hipStreamWaitEvent(s, c->llg_join[i], 0);
+    }
+    return BOSS_OK;
+}
+
 // grad_out: null, or (d+2)×S — ∂logpdf/∂(λ_1..λ_d, α, σ) of every set (the factorisations run batched, the gradient passes set
 // after set on the shared workspaces)
 static int loglike_batch_impl(int device, int kernel, int d, int N, const double* X, const double* y,
@@ -138,12 +207,9 @@ static int loglike_batch_impl(int device, int kernel, int d, int N, const double
     if (rc) return rc;
     const size_t inv16_b = (size_t)nblk * 8 * 256;
     const int nv = d + 2;
-    const size_t dinv_one = (size_t)nblk * BLK * BLK + (size_t)Np * PRED_RB;                        // one set's Dinv + Dinv2
     // small sets run their gradient passes in groups (every launch covers the group in grid.z), large ones set after set
-    const size_t per_set_w = 2 * (size_t)ld * Np * sizeof(double);
-    static const int group_np_max = getenv("BOSS_LLGRAD_GROUP_NP") ? atoi(getenv("BOSS_LLGRAD_GROUP_NP")) : 2048;
-    const int group = (grad_out && Np <= group_np_max) ? (int)std::max<size_t>(1, std::min<size_t>((size_t)chunk, ((size_t)2 << 30) / per_set_w)) : 1;
-    const size_t dinv_doubles = grad_out ? (size_t)std::max(group, (int)Ctx::LLG_BANKS) * dinv_one : 0;   // one per bank / per member of a group
+    const int group = llgrad_group_size(grad_out != nullptr, Np, ld, chunk);
+    const size_t dinv_doubles = llgrad_dinv_doubles(group, Np);
     rc = ws_reserve(c->batchMisc, sizeof(double) * ((size_t)chunk * (inv16_b + 2 + 2 + d + nv) + dinv_doubles) + sizeof(int) * chunk + 64);
     if (rc) return rc;
     double* A = (double*)c->batchA.p;
@@ -234,52 +300,14 @@ static int loglike_batch_impl(int device, int kernel, int d, int N, const double
         batch_factor_enqueue(c, kernel, d, N, Np, nb, Xraw, ydev, mean_arg, mean_b, invlam, hyp, Xsc, xs_bstride, A, ld, bstride, inv16, inv16_b,
                              scal, info);
         if (grad_out) {
-            // the gradient passes of consecutive sets rotate over up to four streams (each on its own bank of workspaces):
-            // their small kernels (low levels of the triangular inverse, reductions) overlap the other set's large ones
-            if (group > 1) {
-                for (int b0 = 0; b0 < nb; b0 += group) {
-                    const int cnt = std::min(group, nb - b0);
-                    boss_gp v;                              // a view of sets b0 .. b0+cnt-1 as fitted handles with constant strides
-                    set_view(&v, c, kernel, d, N, Np, A + (size_t)b0 * bstride, inv16 + (size_t)b0 * inv16_b, Xsc + (size_t)b0 * xs_bstride,
-                             dinv_scratch, dinv_scratch + (size_t)group * nblk * BLK * BLK);
-                    SetBatch B;
-                    B.nb = cnt;
-                    B.sA = bstride;
-                    B.sInv16 = inv16_b;
-                    B.sDinv = (size_t)nblk * BLK * BLK;
-                    B.sDinv2 = (size_t)Np * PRED_RB;
-                    B.sX = xs_bstride;
-                    rc = llgrad_enqueue(&v, s, sums + (size_t)b0 * nv, 0, B, hyp + 2 * (size_t)b0, 2);
-                    if (rc) {
-                        (void)hipDeviceSynchronize();
-                        return rc;
-                    }
-                }
-            } else {
-            static const int nbanks_env = getenv("BOSS_LLGRAD_STREAMS") ? atoi(getenv("BOSS_LLGRAD_STREAMS")) : Ctx::LLG_BANKS;
-            const int nbanks = std::max(1, std::min(std::min(nbanks_env, (int)Ctx::LLG_BANKS), nb));
-            if (nbanks > 1) {
-                (void)hipEventRecord(c->ev_fork, s);
-                for (int i = 0; i < nbanks - 1; ++i) (void)hipStreamWaitEvent(c->llg_stream[i], c->ev_fork, 0);
-            }
-            for (int b = 0; b < nb; ++b) {                  // a view of set b as a fitted handle
-                const int bank = b % nbanks;
-                hipStream_t sb = bank ? c->llg_stream[bank - 1] : s;
-                boss_gp v;
-                double* const dinv = dinv_scratch + (size_t)bank * dinv_one;
-                set_view(&v, c, kernel, d, N, Np, A + (size_t)b * bstride, inv16 + (size_t)b * inv16_b, Xsc + (size_t)b * xs_bstride, dinv,
-                         dinv + (size_t)nblk * BLK * BLK);
-                rc = llgrad_enqueue(&v, sb, sums + (size_t)b * nv, bank, SetBatch(), hyp + 2 * (size_t)b, 0);
-                if (rc) {
-                    (void)hipDeviceSynchronize();
-                    return rc;
-                }
-            }
-            for (int i = 0; i < nbanks - 1; ++i) {
-                (void)hipEventRecord(c->llg_join[i], c->llg_stream[i]);
-                (void)hipStreamWaitEvent(s, c->llg_join[i], 0);
-            }
-            }
+            SetBatch St;
+            St.sA = bstride;
+            St.sInv16 = inv16_b;
+            St.sX = xs_bstride;
+            rc = llgrad_sets_enqueue(c, s, nb, group, Np, dinv_scratch, sums, nv, St, hyp, [&](boss_gp* v, int b, double* Dinv, double* Dinv2) {
+                set_view(v, c, kernel, d, N, Np, A + (size_t)b * bstride, inv16 + (size_t)b * inv16_b, Xsc + (size_t)b * xs_bstride, Dinv, Dinv2);
+            });
+            if (rc) return rc;
             h_sums.resize((size_t)nv * nb);
             HIPCHK(hipMemcpyAsync(h_sums.data(), sums, sizeof(double) * nv * nb, hipMemcpyDeviceToHost, s));
         }
@@ -333,6 +361,10 @@ extern "C" int boss_gp_loglike_grad_batch(int device, int kernel, int d, int N, 
 // the per-set parameter block (par_doubles doubles per set, written by fill, which also says whether the set is valid) and in the
 // Gram launch.  Rows are padded to 128 (the one-workgroup small path knows the plain kernel only).
 // BOSS_MODEL_BATCH_CHUNK_MB=<MB> (tests) lowers the 12 GiB limit so that a small batch spans several chunks.
+// With gradients (boss_ggp_loglike_grad_batch, boss_ngp_loglike_grad_batch; ModelBatchGrad) the caller pads the rows to 256, since
+// the gradient pass works in 256-row steps — the extra identity block changes no sum, the likelihoods stay those of the 128-padded
+// call in every bit —, and the gradient passes of a chunk follow its factorisations under the plain model's grouping policy
+// (llgrad_sets_enqueue); their results come back in the chunk's one copy and one synchronisation.
 // ------------------------------------------------------------------------------------------
 struct ModelBatchGramArgs {
     const double* pts;                                       // the model's points, shared by all sets
@@ -341,11 +373,17 @@ struct ModelBatchGramArgs {
     int ld, cnt;
     size_t bstride;
 };
+struct ModelBatchGrad {
+    size_t out_doubles;                                      // results per set on the device: d+3 sums, or (d+3)·Np per-point values
+    std::function<void(boss_gp*, const double* pts_dev, double* par_dev)> view;   // what llgrad_enqueue reads of the model in a view of one set
+    std::function<void(int s, const double* par, const double* h)> finish;       // set s's outputs from its staged parameters and results; h null: zeros
+};
 
 static int model_loglike_batch_run(Ctx* c, int N, int Np, int S, const std::vector<double>& pts, const std::vector<double>& yb,
                                    const double* mean_X, int mean_stride, size_t par_doubles,
                                    const std::function<bool(int, double*)>& fill,
-                                   const std::function<void(const ModelBatchGramArgs&)>& gram, double* ll_out, int* status_out) {
+                                   const std::function<void(const ModelBatchGramArgs&)>& gram, double* ll_out, int* status_out,
+                                   const ModelBatchGrad* G = nullptr) {
     hipStream_t s = c->stream;
     const int nblk = Np / BLK, ld = Np + RHS_ROWS;
     const size_t bstride = (size_t)ld * Np, per = bstride * sizeof(double);
@@ -357,7 +395,9 @@ static int model_loglike_batch_run(Ctx* c, int N, int Np, int S, const std::vect
     if (rc) return rc;
     rc = ws_reserve(c->batchX, sizeof(double) * (pts.size() + Np + mean_doubles + par_doubles * chunk));
     if (rc) return rc;
-    rc = ws_reserve(c->batchMisc, sizeof(double) * ((size_t)chunk * (inv16_b + 2)) + sizeof(int) * chunk + 64);
+    const int group = llgrad_group_size(G != nullptr, Np, ld, chunk);
+    const size_t dinv_doubles = llgrad_dinv_doubles(group, Np), out_doubles = G ? G->out_doubles : 0;
+    rc = ws_reserve(c->batchMisc, sizeof(double) * ((size_t)chunk * (inv16_b + 2 + out_doubles) + dinv_doubles) + sizeof(int) * chunk + 64);
     if (rc) return rc;
     double* A = (double*)c->batchA.p;
     double* pts_dev = (double*)c->batchX.p;                  // points | observations | prior means | parameter blocks
@@ -366,7 +406,10 @@ static int model_loglike_batch_run(Ctx* c, int N, int Np, int S, const std::vect
     double* par_dev = meandev + mean_doubles;
     double* inv16 = (double*)c->batchMisc.p;
     double* scal = inv16 + inv16_b * chunk;
-    int* info = (int*)(scal + 2 * (size_t)chunk);
+    double* sums = scal + 2 * (size_t)chunk;                 // chunk × out_doubles
+    double* dinv_scratch = sums + out_doubles * chunk;
+    int* info = (int*)(dinv_scratch + dinv_doubles);
+    std::vector<double> h_sums(out_doubles * chunk);
     // (the host vectors outlive the copies: every chunk ends with a synchronisation)
     HIPCHK(hipMemcpyAsync(pts_dev, pts.data(), sizeof(double) * pts.size(), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(ydev, yb.data(), sizeof(double) * Np, hipMemcpyHostToDevice, s));
@@ -393,6 +436,19 @@ static int model_loglike_batch_run(Ctx* c, int N, int Np, int S, const std::vect
                                  ProfScope ps(c, "gram");
                                  gram(ModelBatchGramArgs{pts_dev, par_dev + (size_t)b0 * par_doubles, A + (size_t)b0 * bstride, ld, cnt, bstride});
                              });
+        if (G) {
+            SetBatch St;
+            St.sA = bstride;
+            St.sInv16 = inv16_b;
+            St.sPar = par_doubles;
+            rc = llgrad_sets_enqueue(c, s, nb, group, Np, dinv_scratch, sums, out_doubles, St, nullptr,
+                                     [&](boss_gp* v, int b, double* Dinv, double* Dinv2) {
+                                         set_view(v, c, 0, 0, N, Np, A + (size_t)b * bstride, inv16 + (size_t)b * inv16_b, nullptr, Dinv, Dinv2);
+                                         G->view(v, pts_dev, par_dev + (size_t)b * par_doubles);
+                                     });
+            if (rc) return rc;
+            HIPCHK(hipMemcpyAsync(h_sums.data(), sums, sizeof(double) * out_doubles * nb, hipMemcpyDeviceToHost, s));
+        }
         HIPCHK(hipMemcpyAsync(h_scal.data(), scal, sizeof(double) * 2 * nb, hipMemcpyDeviceToHost, s));
         HIPCHK(hipMemcpyAsync(h_info.data(), info, sizeof(int) * nb, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
@@ -400,6 +456,7 @@ static int model_loglike_batch_run(Ctx* c, int N, int Np, int S, const std::vect
         for (int b = 0; b < nb; ++b) {
             const int st = batch_set_result(N, valid[b], h_info[b], h_scal[2 * b], h_scal[2 * b + 1], &ll_out[s0 + b]);
             if (status_out) status_out[s0 + b] = st;
+            if (G) G->finish(s0 + b, h_par.data() + (size_t)b * par_doubles, st == BOSS_OK ? h_sums.data() + (size_t)b * out_doubles : nullptr);
         }
     }
     return BOSS_OK;
@@ -434,9 +491,10 @@ static bool ngp_stage_set(int d, int N, int Np, const double* lam, const double*
 
 // S parameter sets (λ[d], α, σ, σ_∂) of a GradientGaussianProcess on one output slice; X d×n, dY d×n column-major as in
 // boss_ggp_create, lengthscales d×S.  Every parameter gets +1e-8 (gradient_gp.jl:128-131, :200-204) as in boss_ggp_update.
-extern "C" int boss_ggp_loglike_batch(int device, int kernel, int d, int n, const double* X, const double* y, const double* dY, int S,
-                                      const double* lengthscales, const double* amplitudes, const double* noise_stds,
-                                      const double* grad_noise_stds, double* ll_out, int* status_out) {
+// grad_out: null, or (d+3)×S — ∂ℓ/∂(λ_1..λ_d, α, σ, σ_∂) of every set.
+static int ggp_loglike_batch_impl(int device, int kernel, int d, int n, const double* X, const double* y, const double* dY, int S,
+                                  const double* lengthscales, const double* amplitudes, const double* noise_stds,
+                                  const double* grad_noise_stds, double* ll_out, int* status_out, double* grad_out) {
     if (kernel < 0 || kernel > 2) return fail(BOSS_E_INVALID, "unknown kernel id");
     if (d < 1 || n < 1 || S < 0 || !X || !y || !dY || !ll_out) return fail(BOSS_E_INVALID, "bad arguments");
     if (d > AUG_MAX_D) return fail(BOSS_E_INVALID, "gradient observations: x_dim above 16 is not supported");
@@ -447,7 +505,7 @@ extern "C" int boss_ggp_loglike_batch(int device, int kernel, int d, int n, cons
     int rc = get_ctx(device, &c);
     if (rc) return rc;
     std::lock_guard<std::mutex> lk(c->mtx);
-    const int N = n * (1 + d), Np = round_up(N, BLK), ldx = round_up(n, 64);
+    const int N = n * (1 + d), Np = round_up(N, grad_out ? PRED_RB : BLK), ldx = round_up(n, 64);
     std::vector<double> pts, yb(Np, 0.0);
     pack_points(pts, X, d, n, ldx, nullptr);
     for (int j = 0; j < n; ++j) {                            // `_build_obs_vector` (gradient_gp.jl:288-302), built once for all sets
@@ -463,17 +521,55 @@ extern "C" int boss_ggp_loglike_batch(int device, int kernel, int d, int n, cons
         hipLaunchKernelGGL(aug_gram_kernel, dim3((unsigned)(t64 * (t64 + 1) / 2), 1, a.cnt), dim3(256), 0, c->stream, a.pts, ldx, d, n, N, Np,
                            kernel, a.par + d, a.par, par_doubles, a.A, a.ld, a.bstride);
     };
-    return model_loglike_batch_run(c, N, Np, S, pts, yb, nullptr, 0, par_doubles, fill, gram, ll_out, status_out);
+    ModelBatchGrad G;
+    G.out_doubles = (size_t)d + 3;
+    G.view = [&](boss_gp* v, const double* pts_dev, double* par) {
+        v->kernel = kernel;
+        v->d = d;
+        v->aug = true;
+        v->npts = n;
+        v->ldx = ldx;
+        v->Xraw = const_cast<double*>(pts_dev);
+        v->invlam = par;
+        v->hyp = par + d;
+    };
+    G.finish = [&](int b, const double* par, const double* h) {
+        double* gr = grad_out + (size_t)b * (d + 3);
+        if (h) ggp_llgrad_finalize(d, par, h, gr);
+        else std::fill(gr, gr + d + 3, 0.0);
+    };
+    return model_loglike_batch_run(c, N, Np, S, pts, yb, nullptr, 0, par_doubles, fill, gram, ll_out, status_out, grad_out ? &G : nullptr);
+}
+
+extern "C" int boss_ggp_loglike_batch(int device, int kernel, int d, int n, const double* X, const double* y, const double* dY, int S,
+                                      const double* lengthscales, const double* amplitudes, const double* noise_stds,
+                                      const double* grad_noise_stds, double* ll_out, int* status_out) {
+    return ggp_loglike_batch_impl(device, kernel, d, n, X, y, dY, S, lengthscales, amplitudes, noise_stds, grad_noise_stds, ll_out, status_out,
+                                  nullptr);
+}
+
+// ... AND their gradients w.r.t. (lengthscale[d], amplitude, noise_std, grad_noise_std): what a multistart OptimizationMAP over a
+// GradientGaussianProcess evaluates per round (src/model_fitters/optimization.jl:146-164 over gradient_gp.jl:367-397), all starts in
+// one call.  Column s of grad_out is what boss_ggp_loglike_grad returns after boss_ggp_update at the parameters of set s.
+extern "C" int boss_ggp_loglike_grad_batch(int device, int kernel, int d, int n, const double* X, const double* y, const double* dY,
+                                           int S, const double* lengthscales, const double* amplitudes, const double* noise_stds,
+                                           const double* grad_noise_stds, double* ll_out, double* grad_out, int* status_out) {
+    if (!grad_out) return fail(BOSS_E_INVALID, "grad_out is NULL");
+    return ggp_loglike_batch_impl(device, kernel, d, n, X, y, dY, S, lengthscales, amplitudes, noise_stds, grad_noise_stds, ll_out, status_out,
+                                  grad_out);
 }
 
 // S sets of latent values (λ(x_j) d×N, α(x_j) N, σ(x_j) N; set after set) of a NonstationaryGP on one output slice.  The values
 // are taken as given (nothing is added), and checked as boss_ngp_update checks them: a set with a lengthscale that is not finite
 // and positive, or an amplitude or noise that is not finite and non-negative, is reported and the others are computed.
-extern "C" int boss_ngp_loglike_batch(int device, int d, int N, const double* X, const double* y, const unsigned char* discrete, int S,
-                                      const double* lam_X, const double* amp_X, const double* noise_X, const double* mean_X,
-                                      int mean_stride, double* ll_out, int* status_out) {
+// grads: the partial derivatives w.r.t. the latent values are wanted (each of the four outputs may still be null).
+static int ngp_loglike_batch_impl(int device, int d, int N, const double* X, const double* y, const unsigned char* discrete, int S,
+                                  const double* lam_X, const double* amp_X, const double* noise_X, const double* mean_X, int mean_stride,
+                                  double* ll_out, int* status_out, bool grads, double* dlam_out, double* damp_out, double* dnoise_out,
+                                  double* dmean_out) {
     if (d < 1 || N < 1 || S < 0 || !X || !y || !ll_out) return fail(BOSS_E_INVALID, "bad arguments");
     if (N > MAX_ROWS) return fail(BOSS_E_INVALID, "more than 46080 observations are not supported");
+    if (grads && d > GIBBS_GRAD_MAX_D) return fail(BOSS_E_INVALID, "x_dim above 16 is not supported by the nonstationary gradient kernels");
     if (S == 0) return BOSS_OK;
     if (!lam_X || !amp_X || !noise_X) return fail(BOSS_E_INVALID, "NULL latent-value array");
     if (mean_X && mean_stride != 0 && mean_stride != N) return fail(BOSS_E_INVALID, "mean_stride must be 0 or N");
@@ -481,7 +577,7 @@ extern "C" int boss_ngp_loglike_batch(int device, int d, int N, const double* X,
     int rc = get_ctx(device, &c);
     if (rc) return rc;
     std::lock_guard<std::mutex> lk(c->mtx);
-    const int Np = round_up(N, BLK);
+    const int Np = round_up(N, grads ? PRED_RB : BLK);
     std::vector<double> pts, yb(Np, 0.0);
     pack_points(pts, X, d, N, Np, discrete);
     std::copy(y, y + N, yb.begin());
@@ -494,7 +590,44 @@ extern "C" int boss_ngp_loglike_batch(int device, int d, int N, const double* X,
         hipLaunchKernelGGL(gibbs_gram_kernel, dim3(t64 * (t64 + 1) / 2, 1, a.cnt), dim3(256), 0, c->stream, a.pts, a.par,
                            a.par + (size_t)d * Np, a.par + (size_t)(d + 1) * Np, par_doubles, par_doubles, d, N, Np, a.A, a.ld, a.bstride);
     };
-    return model_loglike_batch_run(c, N, Np, S, pts, yb, mean_X, mean_stride, par_doubles, fill, gram, ll_out, status_out);
+    ModelBatchGrad G;
+    G.out_doubles = ((size_t)d + 3) * Np;                    // dlam [d][Np] | damp [Np] | dnoise [Np] | dmean [Np]
+    G.view = [&](boss_gp* v, const double* pts_dev, double* par) {
+        v->d = d;
+        v->gibbs = true;
+        v->Xraw = const_cast<double*>(pts_dev);
+        v->lamX = par;
+        v->ampX = par + (size_t)d * Np;
+        v->noiseX = par + (size_t)(d + 1) * Np;
+    };
+    G.finish = [&](int b, const double*, const double* h) {
+        double* dl = dlam_out ? dlam_out + (size_t)b * d * N : nullptr;
+        for (int j = 0; j < N; ++j) {
+            if (dl)
+                for (int k = 0; k < d; ++k) dl[(size_t)j * d + k] = h ? h[(size_t)k * Np + j] : 0.0;
+            if (damp_out) damp_out[(size_t)b * N + j] = h ? h[(size_t)d * Np + j] : 0.0;
+            if (dnoise_out) dnoise_out[(size_t)b * N + j] = h ? h[(size_t)(d + 1) * Np + j] : 0.0;
+            if (dmean_out) dmean_out[(size_t)b * N + j] = h ? h[(size_t)(d + 2) * Np + j] : 0.0;
+        }
+    };
+    return model_loglike_batch_run(c, N, Np, S, pts, yb, mean_X, mean_stride, par_doubles, fill, gram, ll_out, status_out, grads ? &G : nullptr);
+}
+
+extern "C" int boss_ngp_loglike_batch(int device, int d, int N, const double* X, const double* y, const unsigned char* discrete, int S,
+                                      const double* lam_X, const double* amp_X, const double* noise_X, const double* mean_X,
+                                      int mean_stride, double* ll_out, int* status_out) {
+    return ngp_loglike_batch_impl(device, d, N, X, y, discrete, S, lam_X, amp_X, noise_X, mean_X, mean_stride, ll_out, status_out, false,
+                                  nullptr, nullptr, nullptr, nullptr);
+}
+
+// ... AND their partial derivatives w.r.t. the latent models' values at the training points (boss_ngp_loglike_grad per set):
+// dlam_out d×N×S (set after set, each in lam_X's layout), damp_out, dnoise_out, dmean_out N×S; each may be NULL.
+extern "C" int boss_ngp_loglike_grad_batch(int device, int d, int N, const double* X, const double* y, const unsigned char* discrete,
+                                           int S, const double* lam_X, const double* amp_X, const double* noise_X,
+                                           const double* mean_X, int mean_stride, double* ll_out, double* dlam_out, double* damp_out,
+                                           double* dnoise_out, double* dmean_out, int* status_out) {
+    return ngp_loglike_batch_impl(device, d, N, X, y, discrete, S, lam_X, amp_X, noise_X, mean_X, mean_stride, ll_out, status_out, true,
+                                  dlam_out, damp_out, dnoise_out, dmean_out);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -100,29 +100,26 @@ class HipGradientMAP:
         return tot, gl, ga, gs
 
     def _objective_gradient_model(self, model, prior_ll, data, plist):
-        """The same for a HipGradientGaussianProcess (values + gradients): per start and output one boss_ggp_update and one
-        boss_ggp_loglike_grad on resident handles (an augmented factorisation fills the device on its own); a fourth parameter group,
-        the gradient noise σ_∂ (what ForwardDiff yields through gradient_gp.jl:367-397 inside OptimizationMAP)."""
+        """The same for a HipGradientGaussianProcess (values + gradients): one batched device call per output
+        (data_loglike_grad_batch -> boss_ggp_loglike_grad_batch; where that call does not pay, per start and output one
+        boss_ggp_update and one boss_ggp_loglike_grad on resident handles); a fourth parameter group, the gradient noise σ_∂ (what
+        ForwardDiff yields through gradient_gp.jl:367-397 inside OptimizationMAP)."""
         S = len(plist)
         d, P = plist[0].lengthscales.shape
         tot = np.array([prior_ll(p) for p in plist], dtype=float)
         gl, ga, gs, gd = np.zeros((S, d, P)), np.zeros((S, P)), np.zeros((S, P)), np.zeros((S, P))
-        llg = model.data_loglike_grad(data)
-        try:
-            for k, p in enumerate(plist):
-                ll, g = llg(p)
-                tot[k] += ll
-                if not np.isfinite(ll):
-                    continue
-                gl[k], ga[k], gs[k], gd[k] = g.lengthscales, g.amplitudes, g.noise_std, g.grad_noise_std
-                for i in range(P):
-                    gl[k, :, i] += np.atleast_1d(model.lengthscale_priors[i].grad_logpdf(p.lengthscales[:, i]))
-                    ga[k, i] += model.amplitude_priors[i].grad_logpdf(p.amplitudes[i])
-                    gs[k, i] += model.noise_std_priors[i].grad_logpdf(p.noise_std[i])
-                    gd[k, i] += model.grad_noise_std_priors[i].grad_logpdf(p.grad_noise_std[i])
-        finally:
-            for h in llg.handles:
-                h.close()
+        lls, gparams = model.data_loglike_grad_batch(data, plist)
+        for k, p in enumerate(plist):
+            ll, g = lls[k], gparams[k]
+            tot[k] += ll
+            if not np.isfinite(ll):
+                continue
+            gl[k], ga[k], gs[k], gd[k] = g.lengthscales, g.amplitudes, g.noise_std, g.grad_noise_std
+            for i in range(P):
+                gl[k, :, i] += np.atleast_1d(model.lengthscale_priors[i].grad_logpdf(p.lengthscales[:, i]))
+                ga[k, i] += model.amplitude_priors[i].grad_logpdf(p.amplitudes[i])
+                gs[k, i] += model.noise_std_priors[i].grad_logpdf(p.noise_std[i])
+                gd[k, i] += model.grad_noise_std_priors[i].grad_logpdf(p.grad_noise_std[i])
         tot = np.where(np.isfinite(tot), tot, -np.inf)
         return tot, gl, ga, gs, gd
 

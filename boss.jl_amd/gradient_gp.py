@@ -6,6 +6,7 @@ Every evaluated point contributes its value and its gradient, so n points give a
   mean / var / mean_and_var              -> boss_gp_predict on the augmented factor
   mean_and_cov / cov                     -> boss_ggp_predict_cov
   data_loglike_batch (`loglike.(samples)`) -> boss_ggp_loglike_batch (all samples of an output in one call)
+  data_loglike_grad_batch (a round of OptimizationMAP) -> boss_ggp_loglike_grad_batch (values and gradients, one call per output)
 The acquisition maximizers (HipBatchAM, …) take these posteriors unchanged; append has its own entry point
 (boss_ggp_append).
 """
@@ -113,6 +114,28 @@ def batched_call_pays(rows: int, n_sets: int) -> bool:
     return n_sets >= BATCH_MIN_SETS and rows <= BATCH_MAX_ROWS
 
 
+# Where data_loglike_grad_batch switches from the loop of boss_ggp_update + boss_ggp_loglike_grad on one resident handle to one
+# boss_ggp_loglike_grad_batch call.  Measured on an MI355X (tools/model_llgrad_batch_time.py, one process per shape, p50 of 20 calls,
+# range of three runs, ms; the loop timed on the previous commit's library; DESIGN.md §4.2, profiles/model_llgrad_batch_times.jsonl):
+#   rows   S = 8: batched | loop          S = 64: batched | loop
+#     60   0.334-0.346 | 2.15-2.28        0.438-0.454 | 17.1-19.0
+#    240   0.340-0.365 | 2.30-2.37        0.497-0.543 | 18.3-19.0
+#   1017   1.15-1.18   | 6.00-6.07        3.91-4.18   | 47.8-52.2
+#   2043   3.15-3.21   | 11.1-11.3        19.0-19.2   | 88.8-93.5
+#   4095   18.9-19.3   | 24.5-25.0        124-125     | 196-199
+# The batched call's slowest run is below the loop's fastest at every measured shape (1.27× at the least, at 4095 rows and 8 sets).
+# Fewer than 8 sets and more than 4095 rows are not measured: they keep the loop.
+GRAD_BATCH_MIN_SETS = 8
+GRAD_BATCH_MAX_ROWS = 4095
+
+
+def batched_grad_call_pays(rows: int, n_sets: int) -> bool:
+    """True where one batched call evaluates value and gradient of `n_sets` parameter sets of an augmented system of `rows` =
+    n(1+d) rows faster than the loop on a resident handle: the measured region above, where the batched call's slowest run stays
+    below the loop's fastest.  Unmeasured shapes keep the loop."""
+    return n_sets >= GRAD_BATCH_MIN_SETS and rows <= GRAD_BATCH_MAX_ROWS
+
+
 @dataclass
 class HipGradientGaussianProcess:
     """GradientGaussianProcess(mean, kernel, lengthscale_priors, amplitude_priors, noise_std_priors,
@@ -212,6 +235,40 @@ class HipGradientGaussianProcess:
             ll_i, st = api.ggp_loglike_batch(data.X, data.Y[i], data.dY[i], self.kernel, lam, amp, sig, sgd, self.device)
             tot += np.where(st == api.BOSS_OK, ll_i, -math.inf)
         return tot
+
+    def data_loglike_grad_batch(self, data: GradientData, samples: Sequence[HipGradientGPParams]):
+        """Value and gradient of data_loglike at every parameter set of `samples` — one round of a multistart OptimizationMAP
+        (src/model_fitters/optimization.jl:146-164): (ℓ[S], [HipGradientGPParams of partial derivatives] × S), summed over the
+        outputs, by ONE boss_ggp_loglike_grad_batch call per output; (-Inf, zeros) where any output's augmented matrix is not PD.
+        Where the batched call does not pay (`batched_grad_call_pays`) the sets go through data_loglike_grad's loop on resident
+        handles; both ways give the same numbers bit for bit."""
+        samples = list(samples)
+        S = len(samples)
+        if S == 0:
+            return np.zeros(0), []
+        d, n = data.X.shape
+        P = data.Y.shape[0]
+        if not batched_grad_call_pays(n * (1 + d), S):
+            llg = self.data_loglike_grad(data)
+            try:
+                res = [llg(p) for p in samples]
+            finally:
+                for g in llg.handles:
+                    g.close()
+            return np.array([r[0] for r in res]), [r[1] for r in res]
+        tot = np.zeros(S)
+        gl, ga, gs, gd = np.zeros((S, d, P)), np.zeros((S, P)), np.zeros((S, P)), np.zeros((S, P))
+        for i in range(P):
+            lam = np.stack([p.lengthscales[:, i] for p in samples], axis=1)
+            amp, sig, sgd = (np.array([getattr(p, name)[i] for p in samples]) for name in ("amplitudes", "noise_std", "grad_noise_std"))
+            ll_i, st, gr = api.ggp_loglike_grad_batch(data.X, data.Y[i], data.dY[i], self.kernel, lam, amp, sig, sgd, self.device)
+            tot += np.where(st == api.BOSS_OK, ll_i, -math.inf)
+            gl[:, :, i], ga[:, i], gs[:, i], gd[:, i] = gr[:d].T, gr[d], gr[d + 1], gr[d + 2]
+        bad = ~np.isfinite(tot)
+        tot[bad] = -math.inf
+        for arr in (gl, ga, gs, gd):
+            arr[bad] = 0.0
+        return tot, [HipGradientGPParams(gl[k], ga[k], gs[k], gd[k]) for k in range(S)]
 
     def model_posterior_slice(self, params: HipGradientGPParams, data: GradientData, i: int) -> HipGradientGPPosteriorSlice:
         """model_posterior_slice (gradient_gp.jl:307-329)."""

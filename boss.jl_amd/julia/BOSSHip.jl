@@ -748,6 +748,34 @@ function data_loglike_grad(m::HipGradientGaussianProcess, data::BOSS.GradientDat
     end
 end
 """
+`data_loglike_grad` at every parameter set of `ps` — one round of a multistart gradient fitter (OptimizationMAP semantics,
+src/model_fitters/optimization.jl:146-164; the lockstep ascent of `estimate_parameters(fit::HipGradientMAP, …)` over this model):
+ONE `boss_ggp_loglike_grad_batch` ccall per output evaluates the value and the analytic gradient of every trial point, instead of
+one `boss_ggp_update` + `boss_ggp_loglike_grad` per start.  Returns (ℓ (S), [(∂ℓ/∂λ (x_dim × y_dim), ∂ℓ/∂α, ∂ℓ/∂σ, ∂ℓ/∂σ_∂ (y_dim))] × S),
+summed over the outputs; -Inf and zeros where an output's augmented matrix is not PD.  (Not run here: no Julia toolchain.)
+"""
+function data_loglike_grad_batch(m::HipGradientGaussianProcess, data::BOSS.GradientData, ps::AbstractVector)
+    X = Matrix{Float64}(data.X); S = length(ps); d = size(X, 1); P = size(data.Y, 1); ll = zeros(S)
+    G = [(zeros(d, P), zeros(P), zeros(P), zeros(P)) for _ in 1:S]
+    for i in 1:P
+        dY = ndims(data.dY) == 3 ? Matrix{Float64}(data.dY[i, :, :]) : Matrix{Float64}(data.dY)     # x_dim × n
+        λ = Matrix{Float64}(reduce(hcat, (p.λ[:, i] for p in ps))); lli = zeros(S); st = zeros(Cint, S); g = zeros(d + 3, S)
+        α = Float64[p.α[i] for p in ps]; σ = Float64[p.σ[i] for p in ps]; σ∂ = Float64[p.σ_∂[i] for p in ps]
+        check(ccall((:boss_ggp_loglike_grad_batch, lib), Cint,
+            (Cint, Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint,
+             Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}),
+            m.device, kernel_id(m.gp.kernel), d, size(X, 2), X, Vector{Float64}(data.Y[i, :]), dY, S, λ, α, σ, σ∂, lli, g, st))
+        ll .+= lli
+        for s in 1:S
+            G[s][1][:, i] .= g[1:d, s]; G[s][2][i] = g[d + 1, s]; G[s][3][i] = g[d + 2, s]; G[s][4][i] = g[d + 3, s]
+        end
+    end
+    for s in findall(!isfinite, ll), a in G[s]
+        a .= 0.0
+    end
+    return ll, G
+end
+"""
 Data log-likelihood of every parameter set of `ps` (summed over the outputs) for the gradient-observation model: one batched device
 call per output (`boss_ggp_loglike_batch`: the observation vector is built once, every launch covers all sets); -Inf where the
 augmented matrix is not PD.  `estimate_parameters(f::HipBatchedMAP, …)` takes it like the plain model's method.
@@ -893,6 +921,30 @@ function loglike_grad_values(p::HipNonstationaryPosterior, N::Int, d::Int)
     GC.@preserve p check(ccall((:boss_ngp_loglike_grad, lib), Cint, (Ptr{Cvoid}, Ref{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
         p.post.h.h, lp, dλ, dα, dσ, dm))
     return lp[], dλ, dα, dσ, dm
+end
+"""
+`loglike_grad_values` of output `i` for every parameter set of `ps` in ONE device call (`boss_ngp_loglike_grad_batch`): the latent
+models of every set are evaluated at the (rounded) data on the host as in `batched_data_loglike_slice`; returns
+(ℓ (S), ∂ℓ/∂λ(x_j) (x_dim × N × S), ∂ℓ/∂α(x_j), ∂ℓ/∂σ(x_j), ∂ℓ/∂m(x_j) (N × S)) — -Inf and zeros where a set is not PD or holds
+an invalid latent value.  (Not run here: no Julia toolchain.)
+"""
+function loglike_grad_values_batch(model::BOSS.NonstationaryGP, ps::AbstractVector{<:BOSS.NonstationaryGPParams},
+                                   data::BOSS.ExperimentData, i::Int; device = 0)
+    X = Matrix{Float64}(data.X); Xr = rounded(X, model.discrete); d, N = size(X); S = length(ps)
+    Λ = Array{Float64}(undef, d, N, S); A = Matrix{Float64}(undef, N, S); Σ = Matrix{Float64}(undef, N, S)
+    for (s, p) in enumerate(ps)
+        f_λ = BOSS._param_posterior_slice(model.lengthscale_model, p.λ, data, i)
+        f_α = BOSS._param_posterior_slice(model.amplitude_model, p.α, data, i)
+        f_σ = BOSS._param_posterior_slice(model.noise_std_model, p.σ, data, i)
+        Λ[:, :, s] .= reduce(hcat, f_λ.(eachcol(Xr))); A[:, s] .= f_α.(eachcol(Xr)); Σ[:, s] .= f_σ.(eachcol(X))
+    end
+    ll = zeros(S); st = zeros(Cint, S); dλ = zeros(d, N, S); dα = zeros(N, S); dσ = zeros(N, S); dm = zeros(N, S)
+    check(ccall((:boss_ngp_loglike_grad_batch, lib), Cint,
+        (Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{UInt8}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint,
+         Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}),
+        device, d, N, X, Vector{Float64}(data.Y[i, :]), isnothing(model.discrete) ? C_NULL : UInt8.(model.discrete), S, Λ, A, Σ,
+        mean_vals(BOSS.mean_getindex(model.mean, i), X), 0, ll, dλ, dα, dσ, dm, st))
+    return ll, dλ, dα, dσ, dm
 end
 "augment_dataset! (src/types/problem.jl:191-198) for a fitted nonstationary slice: the latent models are evaluated at the new points only."
 function augment!(p::HipNonstationaryPosterior, X_new::AbstractMatrix{<:Real}, y_new::AbstractVector{<:Real})

@@ -294,6 +294,42 @@ def data_loglike_batch(models: Sequence[HipNonstationaryGP], data: ExperimentDat
     return tot
 
 
+def data_loglike_grad_batch(models: Sequence[HipNonstationaryGP], data: ExperimentData):
+    """data_loglike_batch with the cotangents a gradient-based fitter chains back through its latent models: for S nonstationary
+    models that differ in their latent closures only (same `discrete`, same `device`) the closures are evaluated at the data as
+    `_latent_at_data` evaluates them (λ, α at the rounded points, σ and the prior mean at the points as given), then ONE
+    boss_ngp_loglike_grad_batch call per output gives every model's log-likelihood and its partial derivatives w.r.t. those values.
+    Returns (ℓ[S] summed over the outputs, grads) with grads[s][i] = (dlam[d, N], damp[N], dnoise[N], dmean[N]) of model s and
+    output i — what HipNonstationaryPosteriorSlice.loglike_grad returns for that slice; -Inf and zeros throughout a model's
+    cotangents where one of its outputs is not PD (or holds an invalid latent value)."""
+    models = list(models)
+    S = len(models)
+    if S == 0:
+        return np.zeros(0), []
+    first, disc0 = _check_batch_models(models)
+    d, N = data.X.shape
+    P = data.Y.shape[0]
+    tot = np.zeros(S)
+    grads = [[None] * P for _ in range(S)]
+    for i in range(P):
+        lam = np.empty((d, N, S), order="F")
+        amp = np.empty((N, S), order="F")
+        noi = np.empty((N, S), order="F")
+        means = []
+        for s, m in enumerate(models):
+            lam[:, :, s], amp[:, s], noi[:, s], mu, _ = m._latent_at_data(data.X, i)
+            means.append(mu)
+        mean_X = None if all(mu is None for mu in means) else np.stack([np.zeros(N) if mu is None else mu for mu in means])
+        ll, st, dlam, damp, dnoise, dmean = api.ngp_loglike_grad_batch(data.X, data.Y[i], lam, amp, noi, mean_X, disc0, first.device)
+        tot += np.where(st == api.BOSS_OK, ll, -np.inf)
+        for s in range(S):
+            grads[s][i] = (np.array(dlam[:, :, s]), np.array(damp[:, s]), np.array(dnoise[:, s]), np.array(dmean[:, s]))
+    for s in np.flatnonzero(~np.isfinite(tot)):
+        tot[s] = -np.inf
+        grads[s] = [tuple(np.zeros_like(a) for a in g) for g in grads[s]]
+    return tot, grads
+
+
 def _check_batch_models(models):
     first = models[0]
     disc0 = None if first.discrete is None else np.asarray(first.discrete, bool)

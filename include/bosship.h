@@ -260,6 +260,26 @@ int boss_ggp_loglike_batch(int device, int kernel, int d, int n, const double* X
 int boss_ngp_loglike_batch(int device, int d, int N, const double* X, const double* y, const unsigned char* discrete,
                            int S, const double* lam_X, const double* amp_X, const double* noise_X,
                            const double* mean_X, int mean_stride, double* ll_out, int* status_out);
+/* The two models' batched likelihoods WITH their gradients: what a gradient-based fitter evaluates per round (one round of a
+ * multistart OptimizationMAP, src/model_fitters/optimization.jl:146-164), all trial points of an output in one call.
+ * boss_ggp_loglike_grad_batch: arguments, the +1e-8 rule, limits and validity checks of boss_ggp_loglike_batch; grad_out is
+ *   (d+3)×S, column s = dl/d(lengthscale[d], amplitude, noise_std, grad_noise_std) of set s — what boss_ggp_loglike_grad returns
+ *   after boss_ggp_update at those parameters, bit for bit.  A NULL grad_out is BOSS_E_INVALID.
+ * boss_ngp_loglike_grad_batch: arguments and checks of boss_ngp_loglike_batch; the partial derivatives w.r.t. the latent values of
+ *   every set as boss_ngp_loglike_grad returns them: dlam_out d×N×S (set after set, each in lam_X's layout), damp_out, dnoise_out,
+ *   dmean_out N×S; each may be NULL.  d <= 16.
+ * Both: ll_out and status_out as in the likelihood batches (the likelihoods are theirs bit for bit); a set that is invalid or not
+ * positive definite gets -Inf, its status and zeros in every gradient output, the other sets are unaffected; S = 0 is a no-op.
+ * The factorisations run batched, the gradient passes in groups of sets (grid.z = set) up to 2048 padded rows and set after set
+ * over four streams above; one copy back and one synchronisation per chunk of sets.  A set's results do not depend on its position
+ * in the batch or on its neighbours. */
+int boss_ggp_loglike_grad_batch(int device, int kernel, int d, int n, const double* X, const double* y, const double* dY,
+                                int S, const double* lengthscales, const double* amplitudes, const double* noise_stds,
+                                const double* grad_noise_stds, double* ll_out, double* grad_out, int* status_out);
+int boss_ngp_loglike_grad_batch(int device, int d, int N, const double* X, const double* y, const unsigned char* discrete,
+                                int S, const double* lam_X, const double* amp_X, const double* noise_X,
+                                const double* mean_X, int mean_stride, double* ll_out,
+                                double* dlam_out, double* damp_out, double* dnoise_out, double* dmean_out, int* status_out);
 /* S RESIDENT posteriors of one output slice out of ONE batched factorisation.
  * Replaces: the broadcast `model_posterior.(Ref(model), params, Ref(data))` over the S parameter samples of a Bayesian-inference
  * fit (src/posterior.jl:15-19; samples from ext/TuringExt.jl:88-107), i.e. S calls of posterior_gp (gaussian_process.jl:199-211)
