@@ -95,6 +95,10 @@ SIGNATURES = {
                                    C.c_double, _c_ucp, _c_dp, _c_dp]),
     "boss_acq_ei_grad_set": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_int, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, C.c_int,
                                    C.c_double, _c_ucp, _c_dp, _c_dp]),
+    "boss_ngp_predict_grad_set": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.c_int, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp,
+                                            _c_dp, _c_dp, _c_dp, _c_dp, C.POINTER(C.c_long)]),
+    "boss_ngp_acq_ei_grad_set": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_int, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp,
+                                           _c_dp, _c_dp, _c_dp, C.c_int, C.c_double, _c_ucp, _c_dp, _c_dp]),
     "boss_track_create": (C.c_int, [C.c_void_p, C.c_void_p, _c_dp, C.POINTER(C.c_void_p)]),
     "boss_track_free": (None, [C.c_void_p]),
     "boss_track_sync": (C.c_int, [C.c_void_p]),
@@ -986,8 +990,10 @@ def acq_ei(gps: Sequence[Sequence[GP]], cand: Candidates, fit_coefs, y_max=None,
 def acq_ei_grad_moments(mu, var, dmu, dvar, fit_coefs, y_max=None, best=None, valid_mask=None, device: int = 0):
     """EI × feasibility and its gradient w.r.t. the candidates from moments and moment gradients already on the host
     (boss_acq_ei_grad_moments): mu / var [P][M], dmu / dvar [P][d][M].  Returns (acq[M], dacq[d, M])."""
-    mu = _f64(np.atleast_2d(mu), 2)
-    var = _f64(np.atleast_2d(var), 2)
+    mu = np.ascontiguousarray(np.atleast_2d(np.asarray(mu, dtype=np.float64)))       # row p at p*M
+    var = np.ascontiguousarray(np.atleast_2d(np.asarray(var, dtype=np.float64)))
+    if mu.ndim != 2 or var.shape != mu.shape:
+        raise ValueError("mu and var must both be P×M")
     P, M = mu.shape
     gm = np.asarray(dmu, dtype=np.float64).reshape(P, -1, M)
     gv = np.asarray(dvar, dtype=np.float64).reshape(P, -1, M)
@@ -1112,6 +1118,91 @@ def acq_ei_grad_set(gps: Sequence[Sequence[GP]], Xs, fit_coefs, y_max=None, best
     _check(load_library().boss_acq_ei_grad_set(P, S, arr, M, _dp(Xs), _dp(ms), _dp(mg), _dp(coefs), _dp(ym),
                                                0 if best is None else 1, 0.0 if best is None else float(best), _ucp(mask),
                                                _dp(acq), _dp(dacq)))
+    return acq, dacq
+
+
+def _ngp_grad_set_args(n, d, Xs, lam_Xs, amp_Xs, dlam_Xs, damp_Xs, mean_Xs, mean_grad):
+    """The arrays boss_ngp_predict_grad_set / boss_ngp_acq_ei_grad_set read beside those of _ngp_set_args, converted and checked (no
+    device is touched): dlam_Xs None or d×d×M×n ([l, m, j, i] = ∂λ_l/∂x_m of member i at candidate j), damp_Xs None or d×M×n,
+    mean_Xs None or n×M, mean_grad None or n×d×M (-> [i][j*d + m])."""
+    Xs, lam, amp, ms = _ngp_set_args(n, d, Xs, lam_Xs, amp_Xs, mean_Xs)
+    M = Xs.shape[1]
+    dl = da = mg = None
+    if dlam_Xs is not None:
+        dl = _f64(dlam_Xs, 4)
+        if dl.shape != (d, d, M, n):
+            raise BossError(BOSS_E_INVALID, "dlam_Xs must be d×d×M×n")
+    if damp_Xs is not None:
+        da = _f64(damp_Xs, 3)
+        if da.shape != (d, M, n):
+            raise BossError(BOSS_E_INVALID, "damp_Xs must be d×M×n")
+    if mean_grad is not None:
+        a = np.asarray(mean_grad, dtype=np.float64)
+        if a.shape != (n, d, M):
+            raise BossError(BOSS_E_INVALID, "mean_grad must be n×d×M (one block per posterior)")
+        mg = np.ascontiguousarray(a.transpose(0, 2, 1))
+    return Xs, lam, amp, dl, da, ms, mg
+
+
+def ngp_predict_grad_set(gps: Sequence["GibbsGP"], Xs, lam_Xs, amp_Xs, dlam_Xs=None, damp_Xs=None, mean_Xs=None, mean_grad=None):
+    """GibbsGP.predict_grad of n nonstationary posteriors at the same candidates in one call (boss_ngp_predict_grad_set): lam_Xs
+    d×M×n, amp_Xs M×n, dlam_Xs d×d×M×n, damp_Xs d×M×n (None: constant latent models), mean_Xs n×M, mean_grad n×d×M.
+    Returns (mu[n, M], var[n, M], dmu[n, d, M], dvar[n, d, M]).  DomainError (with .bad_index) as GibbsGP.predict_grad."""
+    gps = list(gps)
+    n = len(gps)
+    if n < 1:
+        raise BossError(BOSS_E_INVALID, "at least one posterior is needed")
+    d = gps[0].d
+    Xs, lam, amp, dl, da, ms, mg = _ngp_grad_set_args(n, d, Xs, lam_Xs, amp_Xs, dlam_Xs, damp_Xs, mean_Xs, mean_grad)
+    M = Xs.shape[1]
+    arr = (C.c_void_p * n)(*[g._h.value for g in gps])
+    mu, var = np.zeros((n, M)), np.zeros((n, M))
+    dmu, dvar = np.zeros((n, M, d)), np.zeros((n, M, d))
+    bad = C.c_long(-1)
+    rc = load_library().boss_ngp_predict_grad_set(n, arr, M, _dp(Xs), _dp(lam), _dp(amp), _dp(dl), _dp(da), _dp(ms), _dp(mg), _dp(mu),
+                                                  _dp(var), _dp(dmu), _dp(dvar), C.byref(bad))
+    if rc == BOSS_E_NEG_VAR:
+        e = DomainError(rc, load_library().boss_last_error().decode())
+        e.bad_index = bad.value
+        raise e
+    _check(rc)
+    return mu, var, dmu.transpose(0, 2, 1), dvar.transpose(0, 2, 1)
+
+
+def ngp_acq_ei_grad_set(gps: Sequence[Sequence["GibbsGP"]], Xs, lam_Xs, amp_Xs, dlam_Xs=None, damp_Xs=None, fit_coefs=None, y_max=None,
+                        best=None, valid_mask=None, mean_Xs=None, mean_grad=None):
+    """EI·feas and its gradient w.r.t. the candidates for nonstationary posteriors, averaged over S hyper-parameter samples in ONE
+    device call (boss_ngp_acq_ei_grad_set).  gps[s][p] = output p of sample s; the latent arrays are those of ngp_predict_grad_set
+    with member i = p + P·s.  Returns (acq[M], dacq[d, M]) = the means over s of acq_ei_grad_moments on the P members'
+    GibbsGP.predict_grad results."""
+    S = len(gps)
+    P = len(gps[0]) if S else 0
+    if S < 1 or P < 1 or any(len(row) != P for row in gps):
+        raise BossError(BOSS_E_INVALID, "gps must be S rows of P posteriors")
+    if fit_coefs is None:
+        raise BossError(BOSS_E_INVALID, "fit_coefs is needed")
+    n = P * S
+    d = gps[0][0].d
+    Xs, lam, amp, dl, da, ms, mg = _ngp_grad_set_args(n, d, Xs, lam_Xs, amp_Xs, dlam_Xs, damp_Xs, mean_Xs, mean_grad)
+    M = Xs.shape[1]
+    arr = (C.c_void_p * n)()
+    for s in range(S):
+        for p in range(P):
+            arr[p + P * s] = gps[s][p]._h
+    coefs = _f64(np.asarray(fit_coefs).reshape(-1), 1)
+    if coefs.shape[0] != P:
+        raise BossError(BOSS_E_INVALID, "fit_coefs must have one entry per output")
+    ym = None if y_max is None else _f64(np.asarray(y_max).reshape(-1), 1)
+    if ym is not None and ym.shape[0] != P:
+        raise BossError(BOSS_E_INVALID, "y_max must have one entry per output")
+    mask = None if valid_mask is None else np.ascontiguousarray(np.asarray(valid_mask, dtype=bool).astype(np.uint8))
+    if mask is not None and mask.shape != (M,):
+        raise BossError(BOSS_E_INVALID, "valid_mask must have one entry per candidate")
+    acq = np.zeros(M)
+    dacq = np.zeros((d, M), order="F")
+    _check(load_library().boss_ngp_acq_ei_grad_set(P, S, arr, M, _dp(Xs), _dp(lam), _dp(amp), _dp(dl), _dp(da), _dp(ms), _dp(mg),
+                                                   _dp(coefs), _dp(ym), 0 if best is None else 1, 0.0 if best is None else float(best),
+                                                   _ucp(mask), _dp(acq), _dp(dacq)))
     return acq, dacq
 
 

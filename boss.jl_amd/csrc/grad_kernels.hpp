@@ -48,6 +48,14 @@ struct GradSet {
     double* dmu;              // ∇μ, ∇σ² of this member [d×M]
     double* dvar;
     double amp2;
+    // nonstationary members only (null otherwise; boss_ngp_acq_ei_grad_set): λ(X) [d][Np], α(X) [Np], the latent values at the
+    // candidates λ(x*) [d][Mp], α(x*) [Mp] and their Jacobians ∂λ/∂x [M][d×d], ∂α/∂x [M][d] (either may be null: constant)
+    const double* lamX;
+    const double* ampX;
+    const double* clam;
+    const double* camp;
+    const double* dlam;
+    const double* damp;
 };
 // the two transpositions of the once-per-factorisation preparation for a list of members: which = 0: LT = Aᵀ (grid.z = member),
 // which = 1: DT2 = the Np/256 blocks of Dinv2 transposed (grid.z = member · nb + block)
@@ -590,6 +598,164 @@ __global__ __launch_bounds__(256) void gibbs_grad_accum_kernel(const double* __r
             reduce_store(nslot + 1 + d + m, Cw[m]);
         }
     }
+}
+
+// ... of a SET of equally shaped nonstationary posteriors (boss_ngp_predict_grad_set / boss_ngp_acq_ei_grad_set): grid = (candidate
+// tiles, row splits, members).  The rows of a tile are split over gridDim.y workgroups (one workgroup per tile walks all N rows alone
+// and leaves the chip idle at a few hundred candidates); every workgroup writes its 2 (2 d + 1) × 32 partial sums, no atomics:
+//     part[((member · tiles + tile) · splits + split)][slot][32],   slot as in gibbs_grad_accum_kernel,
+// and gibbs_grad_fold_set_kernel sums the splits in ascending order.  Instantiated on the padded dimension DM (4 / 8 / 16) so that
+// d = 3 does not carry 16-wide register arrays.  The per-row terms are those of gibbs_grad_accum_kernel, except that the
+// row-independent ½/λ*_l of c_l is added once per thread (× Σ_i weight) instead of once per row.  The eight row subsets of a
+// workgroup are summed in a fixed order: the two halves of each wave by a lane exchange, the four waves through LDS.
+template <int DM>
+__global__ __launch_bounds__(256) void gibbs_grad_accum_set_kernel(const GradSet* __restrict__ sets, const double* __restrict__ Wslabs,
+                                                                   int Np, int N, const double* __restrict__ C, int d, int Mp,
+                                                                   const unsigned char* __restrict__ discrete, double* __restrict__ part) {
+    static_assert(DM <= GIBBS_GRAD_MAX_D, "padded dimension above the kernel's limit");
+    constexpr int BN = 32, NS1 = 2 * DM + 1;
+    __shared__ double red[4][NS1][BN];
+    const GradSet gs = sets[blockIdx.z];                     // (uniform: scalar loads)
+    const size_t slab = (size_t)blockIdx.z * gridDim.x + blockIdx.x;
+    const int tid = threadIdx.x, c = tid & 31, rs = tid >> 5, wave = tid >> 6;
+    const int j = blockIdx.x * BN + c;                       // (< Mp: the candidate arrays are padded to a multiple of 64)
+    const double* __restrict__ W = Wslabs + slab * Np * BN + c;
+    const double* __restrict__ X = gs.Xraw;
+    const double* __restrict__ Lam = gs.lamX;
+    const double* __restrict__ amp = gs.ampX;
+    const double* __restrict__ avec = gs.avec;
+    double xc[DM], lc[DM], Ea[DM], Ca[DM], Ew[DM], Cw[DM], Sa = 0.0, Sw = 0.0, Ta = 0.0, Tw = 0.0;
+    unsigned disc = 0;
+#pragma unroll
+    for (int m = 0; m < DM; ++m) {
+        xc[m] = m < d ? C[(size_t)m * Mp + j] : 0.0;
+        lc[m] = m < d ? gs.clam[(size_t)m * Mp + j] : 1.0;
+        Ea[m] = Ca[m] = Ew[m] = Cw[m] = 0.0;
+        if (m < d && discrete && discrete[m]) disc |= 1u << m;
+    }
+    const double ac = gs.camp[j];
+    const int per = (((N + (int)gridDim.y - 1) / (int)gridDim.y + 7) / 8) * 8;
+    const int ibeg = blockIdx.y * per, iend = min(N, ibeg + per);
+    for (int i = ibeg + rs; i < iend; i += 8) {
+        double prod = 1.0, esum = 0.0, e[DM], cl[DM];
+#pragma unroll
+        for (int m = 0; m < DM; ++m) {
+            if (m < d) {
+                const double x = X[(size_t)m * Np + i], l = Lam[(size_t)m * Np + i];
+                const double rq = rcp_refined(__builtin_fma(l, l, lc[m] * lc[m]));
+                const double df = x - xc[m];
+                prod *= 2.0 * l * lc[m] * rq;
+                esum = __builtin_fma(df * df, rq, esum);
+                e[m] = 2.0 * df * rq;
+                cl[m] = 2.0 * lc[m] * df * df * rq * rq - lc[m] * rq;
+            } else {
+                e[m] = cl[m] = 0.0;
+            }
+        }
+        const double ai = amp[i], am = 0.5 * (ai + ac);
+        const double k = am * am * sqrt(prod) * exp(-esum);
+        const double wa = avec[i] * k, ww = W[(size_t)i * BN] * k, s = 1.0 / am;      // 2/(α_i + α*)
+        Sa = __builtin_fma(wa, s, Sa);
+        Sw = __builtin_fma(ww, s, Sw);
+        Ta += wa;
+        Tw += ww;
+#pragma unroll
+        for (int m = 0; m < DM; ++m) {
+            Ea[m] = __builtin_fma(wa, e[m], Ea[m]);
+            Ca[m] = __builtin_fma(wa, cl[m], Ca[m]);
+            Ew[m] = __builtin_fma(ww, e[m], Ew[m]);
+            Cw[m] = __builtin_fma(ww, cl[m], Cw[m]);
+        }
+    }
+#pragma unroll
+    for (int m = 0; m < DM; ++m) {
+        const double hl = m < d ? 0.5 / lc[m] : 0.0;
+        Ca[m] = __builtin_fma(hl, Ta, Ca[m]);
+        Cw[m] = __builtin_fma(hl, Tw, Cw[m]);
+        if (disc >> m & 1) Ea[m] = Ew[m] = 0.0;              // discrete dimensions: no explicit part
+    }
+    const int ns1 = 2 * d + 1;
+    double* __restrict__ out = part + ((slab * gridDim.y + blockIdx.y) * 2 * (size_t)ns1) * BN;
+    // lanes c and c + 32 of a wave hold row subsets 2·wave and 2·wave + 1 of the same candidate
+    auto fold_wave = [&](int slot, double v) {
+        v += __shfl_xor(v, 32);
+        if (!(tid & 32)) red[wave][slot][c] = v;
+    };
+    for (int which = 0; which < 2; ++which) {
+        if (which) __syncthreads();                          // (the first half has been read)
+        fold_wave(0, which ? Sw : Sa);
+#pragma unroll
+        for (int m = 0; m < DM; ++m) {
+            if (m < d) {                                     // (uniform)
+                fold_wave(1 + m, which ? Ew[m] : Ea[m]);
+                fold_wave(1 + d + m, which ? Cw[m] : Ca[m]);
+            }
+        }
+        __syncthreads();
+        for (int idx = tid; idx < ns1 * BN; idx += 256) {
+            const int slot = idx >> 5, cc = idx & 31;
+            out[(size_t)(which * ns1 + slot) * BN + cc] = ((red[0][slot][cc] + red[1][slot][cc]) + red[2][slot][cc]) + red[3][slot][cc];
+        }
+    }
+}
+
+// The Jacobian fold of boss_ngp_predict_grad on the device, in the host loop's operation order: with the sums S (slot 0), E_m, C_l of
+// the a-weights and of the w-weights,
+//     ∇μ_m  = E^a_m + Σ_l ∂λ_l/∂x_m C^a_l + ∂α/∂x_m S^a + ∇m_m ,      ∇σ²_m = 2 α* ∂α/∂x_m − 2 (E^w_m + Σ_l ∂λ_l/∂x_m C^w_l + ∂α/∂x_m S^w)
+// for the 32 candidates of one tile.  The sums are read as sums[split · split_stride + slot · slot_stride + c], splits added in
+// ascending order: the partial sums of gibbs_grad_accum_set_kernel ([split][slot][32]) or, with one split and slot_stride = Mp,
+// what gibbs_grad_accum_kernel leaves ([slot][Mp], at the tile's offset).
+__device__ __forceinline__ void gibbs_grad_fold_body(const double* __restrict__ sums, int nsplit, size_t split_stride, size_t slot_stride,
+                                                     const double* __restrict__ dlam, const double* __restrict__ damp,
+                                                     const double* __restrict__ camp, const double* __restrict__ mean_grad,
+                                                     double* __restrict__ dmu, double* __restrict__ dvar, int d, int M, int tile) {
+    constexpr int BN = 32;
+    __shared__ double sm[2 * (2 * GIBBS_GRAD_MAX_D + 1)][BN];
+    const int tid = threadIdx.x, ns1 = 2 * d + 1;
+    for (int idx = tid; idx < 2 * ns1 * BN; idx += blockDim.x) {
+        const int slot = idx >> 5, c = idx & 31;
+        double v = 0.0;
+        for (int y = 0; y < nsplit; ++y) v += sums[(size_t)y * split_stride + (size_t)slot * slot_stride + c];
+        sm[slot][c] = v;
+    }
+    __syncthreads();
+    for (int idx = tid; idx < d * BN; idx += blockDim.x) {
+        const int c = idx / d, m = idx - c * d;              // (m fastest: the stores of a candidate are contiguous)
+        const int j = tile * BN + c;
+        if (j >= M) continue;
+        double ga = sm[1 + m][c], gw = sm[ns1 + 1 + m][c];
+        if (dlam) {
+            const double* Dl = dlam + (size_t)j * d * d + (size_t)d * m;
+            for (int l = 0; l < d; ++l) {
+                ga += Dl[l] * sm[1 + d + l][c];
+                gw += Dl[l] * sm[ns1 + 1 + d + l][c];
+            }
+        }
+        double av = 0.0;
+        if (damp) {
+            const double da = damp[(size_t)j * d + m];
+            ga += da * sm[0][c];
+            gw += da * sm[ns1][c];
+            av = 2.0 * camp[j] * da;
+        }
+        dmu[(size_t)j * d + m] = ga + (mean_grad ? mean_grad[(size_t)j * d + m] : 0.0);
+        dvar[(size_t)j * d + m] = av - 2.0 * gw;
+    }
+}
+// one posterior behind gibbs_grad_accum_kernel (the member-by-member path): grid = tiles
+__global__ __launch_bounds__(256) void gibbs_grad_fold_kernel(const double* __restrict__ sums, int Mp, const double* __restrict__ dlam,
+                                                              const double* __restrict__ damp, const double* __restrict__ camp,
+                                                              const double* __restrict__ mean_grad, double* __restrict__ dmu,
+                                                              double* __restrict__ dvar, int d, int M) {
+    gibbs_grad_fold_body(sums + (size_t)blockIdx.x * 32, 1, 0, (size_t)Mp, dlam, damp, camp, mean_grad, dmu, dvar, d, M, blockIdx.x);
+}
+// a set behind gibbs_grad_accum_set_kernel: grid = (tiles, members), straight into the members' ∇μ / ∇σ² slices
+__global__ __launch_bounds__(256) void gibbs_grad_fold_set_kernel(const GradSet* __restrict__ sets, const double* __restrict__ part, int nsplit,
+                                                                  int d, int M) {
+    const GradSet gs = sets[blockIdx.y];
+    const size_t one = (size_t)2 * (2 * d + 1) * 32;
+    gibbs_grad_fold_body(part + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * nsplit * one, nsplit, one, 32, gs.dlam, gs.damp, gs.camp,
+                         gs.mean_grad, gs.dmu, gs.dvar, d, M, blockIdx.x);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -1168,8 +1168,12 @@ static bool grad_set_ok(int n, boss_gp_t* const* gps, const boss_cand* cd) {
 // mu / var of member i at mu_all + i·M (unclipped), ∇μ / ∇σ² at gm_all + i·d·M; mean_all / mg_all (or null): the prior means and
 // their gradients in the same layouts.  Caller holds the context lock and has checked grad_set_ok.  BOSS_E_ALLOC: nothing the
 // caller relies on has been written (what was enqueued is overwritten by the member-by-member path the caller turns to).
+// Nonstationary members (ngp_grad_set_ok): clam_all / camp_all as predict_set_enqueue takes them, dlam_all [n][M][d×d] / damp_all
+// [n][M][d] (or null) the latent models' Jacobians; the accumulation leaves partial sums and gibbs_grad_fold_set_kernel folds the
+// Jacobians in on the device.
 static int grad_set_enqueue(int n, boss_gp_t* const* gps, const boss_cand* cd, const double* mean_all, const double* mg_all,
-                            double* mu_all, double* var_all, double* gm_all, double* gv_all) {
+                            double* mu_all, double* var_all, double* gm_all, double* gv_all, const double* clam_all = nullptr,
+                            const double* camp_all = nullptr, const double* dlam_all = nullptr, const double* damp_all = nullptr) {
     boss_gp* g0 = gps[0];
     Ctx* c = g0->ctx;
     hipStream_t s = c->stream;
@@ -1197,9 +1201,9 @@ static int grad_set_enqueue(int n, boss_gp_t* const* gps, const boss_cand* cd, c
         if (!g->have_lt) prep.push_back(i);
     }
     // scratch whose addresses go into the descriptors, or that a later group must not move: reserved before anything is enqueued
-    int rc = g0->aug ? BOSS_OK : ws_reserve(c->csc, sizeof(double) * (size_t)d * Mp * n);
+    int rc = g0->aug || g0->gibbs ? BOSS_OK : ws_reserve(c->csc, sizeof(double) * (size_t)d * Mp * n);
     if (rc) return rc;
-    const size_t part_one = (size_t)32 * (g0->aug ? 2 * AUG_MAX_D : 2 * (GRAD_MAX_D + 1));   // doubles per (member, tile, split)
+    const size_t part_one = (size_t)32 * (g0->aug ? 2 * AUG_MAX_D : g0->gibbs ? 2 * (2 * d + 1) : 2 * (GRAD_MAX_D + 1));   // doubles per (member, tile, split)
     // workgroups wanted in flight before the rows of a tile stop being split (BOSS_SET_GRAD_FILL overrides, 0: never split)
     static const int fill_env = getenv("BOSS_SET_GRAD_FILL") ? std::max(0, atoi(getenv("BOSS_SET_GRAD_FILL"))) : -1;
     const int fill = fill_env >= 0 ? fill_env : 2 * c->n_cus;
@@ -1219,12 +1223,20 @@ static int grad_set_enqueue(int n, boss_gp_t* const* gps, const boss_cand* cd, c
         q.avec = g->avec;
         q.Xsc = g->Xsc;
         q.Xraw = g->Xraw;
-        q.Csc = g0->aug ? nullptr : (const double*)c->csc.p + (size_t)i * d * Mp;   // (where predict_set_enqueue puts them)
+        q.Csc = g0->aug || g0->gibbs ? nullptr : (const double*)c->csc.p + (size_t)i * d * Mp;   // (where predict_set_enqueue puts them)
         q.invlam = g->invlam;
         q.mean_grad = mg_all ? mg_all + (size_t)i * dm : nullptr;
         q.dmu = gm_all + (size_t)i * dm;
         q.dvar = gv_all + (size_t)i * dm;
         q.amp2 = g->amp2;
+        if (g->gibbs) {
+            q.lamX = g->lamX;
+            q.ampX = g->ampX;
+            q.clam = clam_all + (size_t)i * d * Mp;
+            q.camp = camp_all + (size_t)i * Mp;
+            q.dlam = dlam_all ? dlam_all + (size_t)i * d * dm : nullptr;
+            q.damp = damp_all ? damp_all + (size_t)i * dm : nullptr;
+        }
     }
     for (size_t k = 0; k < prep.size(); ++k) desc[n + k] = desc[prep[k]];
     const size_t dbytes = sizeof(GradSet) * ndesc;
@@ -1268,7 +1280,14 @@ static int grad_set_enqueue(int n, boss_gp_t* const* gps, const boss_cand* cd, c
         const int wgs = tiles * cnt;
         int rsplit = wgs >= fill ? 1 : std::min(32, std::max(1, fill / wgs));
         double* part = (double*)c->few.p;
-        if (g0->aug) {
+        if (g0->gibbs) {
+            // (always through the partial sums: the fold kernel reads them and writes the members' slices)
+            rsplit = std::max(1, std::min(rsplit, (g0->N + GRAD_CHUNK - 1) / GRAD_CHUNK));
+            auto kfn = d <= 4 ? gibbs_grad_accum_set_kernel<4> : d <= 8 ? gibbs_grad_accum_set_kernel<8> : gibbs_grad_accum_set_kernel<16>;
+            hipLaunchKernelGGL(kfn, dim3(tiles, rsplit, cnt), dim3(256), 0, s, gsets + i0, (const double*)slabs, Np, g0->N,
+                               (const double*)cd->Craw, d, Mp, (const unsigned char*)g0->discrete_dev, part);
+            hipLaunchKernelGGL(gibbs_grad_fold_set_kernel, dim3(tiles, cnt), dim3(256), 0, s, gsets + i0, (const double*)part, rsplit, d, M);
+        } else if (g0->aug) {
             rsplit = std::max(1, std::min(rsplit, (g0->npts + 63) / 64));
             hipLaunchKernelGGL(aug_grad_accum_set_kernel, dim3(tiles, rsplit, cnt), dim3(256), 0, s, gsets + i0, (const double*)slabs, Np, g0->npts,
                                g0->ldx, (const double*)cd->Craw, d, Mp, M, g0->kernel, rsplit > 1 ? part : nullptr);
@@ -1286,7 +1305,7 @@ static int grad_set_enqueue(int n, boss_gp_t* const* gps, const boss_cand* cd, c
         HIPCHK(hipGetLastError());
         return BOSS_OK;
     };
-    return predict_set_enqueue(n, gps, cd, mean_all, mu_all, var_all, (size_t)M, nullptr, nullptr, &after);
+    return predict_set_enqueue(n, gps, cd, mean_all, mu_all, var_all, (size_t)M, clam_all, camp_all, &after);
 }
 
 // boss_acq_ei_grad averaged over S hyper-parameter samples in one call (expected_improvement.jl:87-90 inside the multistart
@@ -1358,6 +1377,165 @@ extern "C" int boss_acq_ei_grad_set(int P, int S, boss_gp_t* const* gps, int M, 
                        (const double*)dgv, M, d, S, par, (const double*)dcoef, (const double*)dymax,
                        valid_mask ? (const unsigned char*)dmask : nullptr, dacq, ddacq);
     return finish(c, {{acq_out, dacq, sizeof(double) * M}, {dacq_out, ddacq, sizeof(double) * dm}});
+}
+
+// ------------------------------------------------------------------------------------------
+// boss_ngp_predict_grad over a list of nonstationary posteriors (boss_ngp_predict_grad_set), and boss_acq_ei_grad_set's counterpart
+// for them (boss_ngp_acq_ei_grad_set): one enqueue path.  Candidates, every member's λ(x*), α(x*) and Jacobians go up once; equally
+// shaped members take grad_set_enqueue (gibbs_grad_accum_set_kernel + gibbs_grad_fold_set_kernel behind every group), any other
+// list, BOSS_NO_SET_PREDICT=1 and a failed allocation of the set path's scratch go member by member through grad_enqueue's
+// nonstationary branch + gibbs_grad_fold_kernel into the same slices; one copy back.
+// ------------------------------------------------------------------------------------------
+constexpr long long NGP_GRAD_SET_MAX_JAC = 1LL << 27;       // n·M·d² doubles of ∂λ/∂x (1 GiB) per call
+
+static bool ngp_grad_set_ok(int n, boss_gp_t* const* gps, const boss_cand* cd) {
+    return predict_set_ok(n, gps, cd, true) && gps[0]->d <= GIBBS_GRAD_MAX_D;
+}
+
+struct NgpEiArgs {
+    int P, S;
+    const double *fit_coefs, *y_max;
+    int has_best;
+    double best;
+    const unsigned char* valid_mask;
+    double *acq_out, *dacq_out;
+};
+
+// ei: null (the members' moments and gradients come back: mu / var [n][M], dmu / dvar [n][d×M]) or the acquisition's arguments
+// (acq_out / dacq_out come back)
+static int ngp_grad_set_call(int n, boss_gp_t* const* gps, int M, const double* Xs, const double* lam_Xs, const double* amp_Xs,
+                             const double* dlam_Xs, const double* damp_Xs, const double* mean_Xs, const double* mean_grad,
+                             const NgpEiArgs* ei, double* mu, double* var, double* dmu, double* dvar, long* bad_index_out) {
+    if (M < 1) return fail(BOSS_E_INVALID, "M must be >= 1");
+    if ((long long)n * M > (1LL << 30)) return fail(BOSS_E_INVALID, "n·M above 2^30 is not supported");
+    if (bad_index_out) *bad_index_out = -1;
+    for (int i = 0; i < n; ++i) {
+        if (!gps[i]) return fail(BOSS_E_INVALID, "NULL posterior handle");
+        if (!gps[i]->gibbs) return fail(BOSS_E_INVALID, "handle was not created by boss_ngp_create / boss_ngp_fit_batch");
+        if (gps[i]->ctx != gps[0]->ctx || gps[i]->d != gps[0]->d) return fail(BOSS_E_INVALID, "all handles must live on one device and share x_dim");
+        if (gps[i]->discrete != gps[0]->discrete) return fail(BOSS_E_INVALID, "all handles must round the same dimensions");
+    }
+    boss_gp* g0 = gps[0];
+    const int d = g0->d, Mp = round_up(M, 64);
+    if (d > GIBBS_GRAD_MAX_D) return fail(BOSS_E_INVALID, "x_dim above 16 is not supported by the nonstationary gradient kernel");
+    if ((long long)n * M * d * d > NGP_GRAD_SET_MAX_JAC) return fail(BOSS_E_INVALID, "n·M·x_dim² above 2^27 is not supported");
+    for (int i = 0; i < n; ++i)
+        if (!gps[i]->fitted && !gps[i]->pending) return fail(BOSS_E_NOT_FITTED, "handle has no valid factorisation");
+    std::vector<NgpCand> pk(n);
+    for (int i = 0; i < n; ++i) {
+        int rc = ngp_pack(g0, M, Xs, lam_Xs + (size_t)i * d * M, amp_Xs + (size_t)i * M, pk[i]);
+        if (rc) return rc;
+    }
+    Ctx* c = g0->ctx;
+    HIPCHK(hipSetDevice(c->device));
+    std::lock_guard<std::mutex> lk(c->mtx);
+    hipStream_t s = c->stream;
+    for (int i = 0; i < n; ++i) {
+        int rc = gp_settle(gps[i]);
+        if (rc) return rc;
+    }
+    const size_t dm = (size_t)d * M, nm = (size_t)n * M, ndm = (size_t)n * dm, nsums = (size_t)2 * (2 * d + 1) * Mp;
+    const int P = ei ? ei->P : 0;
+    // candidates | λ(x*) of every member | α(x*) of every member | ∂λ/∂x | ∂α/∂x
+    int rc = ws_reserve(c->craw, sizeof(double) * ((size_t)d * Mp + (size_t)n * ((size_t)d * Mp + Mp) + (dlam_Xs ? ndm * d : 0) + (damp_Xs ? ndm : 0)));
+    if (rc) return rc;
+    // acq | dacq | mu | var | dmu | dvar | bad | mean | mean_grad | sums of one member (member-by-member path) | coefs | ymax | mask
+    const size_t nacq = ei ? M + dm : 0, nd = nacq + 3 * nm + 3 * ndm + 1 + nsums + 2 * (size_t)P;
+    rc = ws_reserve(c->pred, sizeof(double) * nd + M);
+    if (rc) return rc;
+    boss_cand cd;
+    cd.ctx = c;
+    cd.d = d;
+    cd.M = M;
+    cd.Mp = Mp;
+    cd.Craw = (double*)c->craw.p;
+    double* clam = cd.Craw + (size_t)d * Mp;
+    double* camp = clam + (size_t)n * d * Mp;
+    double* djl = camp + (size_t)n * Mp;
+    double* dja = djl + (dlam_Xs ? ndm * d : 0);
+    double* dacq = (double*)c->pred.p;
+    double* ddacq = dacq + (ei ? M : 0);
+    double* dmu_ = dacq + nacq;
+    double* dvar_ = dmu_ + nm;
+    double* dgm = dvar_ + nm;
+    double* dgv = dgm + ndm;
+    unsigned long long* dbad = (unsigned long long*)(dgv + ndm);
+    double* dmean = dgv + ndm + 1;
+    double* dmg = dmean + nm;
+    double* dsums = dmg + ndm;
+    double* dcoef = dsums + nsums;
+    double* dymax = dcoef + P;
+    unsigned char* dmask = (unsigned char*)(dacq + nd);
+    EiPar par;
+    if (ei) {
+        rc = ei_params(c, s, P, ei->fit_coefs, ei->y_max, ei->has_best, ei->best, &par, dcoef, dymax);
+        if (rc) return drain(c, rc);
+    }
+    HIPCHK(hipMemcpyAsync(cd.Craw, pk[0].x.data(), sizeof(double) * d * Mp, hipMemcpyHostToDevice, s));
+    for (int i = 0; i < n; ++i) {
+        HIPCHK(hipMemcpyAsync(clam + (size_t)i * d * Mp, pk[i].lam.data(), sizeof(double) * d * Mp, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(camp + (size_t)i * Mp, pk[i].amp.data(), sizeof(double) * Mp, hipMemcpyHostToDevice, s));
+    }
+    if (dlam_Xs) HIPCHK(hipMemcpyAsync(djl, dlam_Xs, sizeof(double) * ndm * d, hipMemcpyHostToDevice, s));
+    if (damp_Xs) HIPCHK(hipMemcpyAsync(dja, damp_Xs, sizeof(double) * ndm, hipMemcpyHostToDevice, s));
+    if (mean_Xs) (void)hipMemcpyAsync(dmean, mean_Xs, sizeof(double) * nm, hipMemcpyHostToDevice, s);
+    if (mean_grad) (void)hipMemcpyAsync(dmg, mean_grad, sizeof(double) * ndm, hipMemcpyHostToDevice, s);
+    if (ei && ei->valid_mask) (void)hipMemcpyAsync(dmask, ei->valid_mask, M, hipMemcpyHostToDevice, s);
+    if (!ei) (void)hipMemsetAsync(dbad, 0xff, sizeof(unsigned long long), s);
+    if (!ei || par.mode != 0) {
+        static const bool set_off = getenv("BOSS_NO_SET_PREDICT") && atoi(getenv("BOSS_NO_SET_PREDICT"));
+        bool done = false;
+        if (!set_off && ngp_grad_set_ok(n, gps, &cd)) {
+            rc = grad_set_enqueue(n, gps, &cd, mean_Xs ? dmean : nullptr, mean_grad ? dmg : nullptr, dmu_, dvar_, dgm, dgv, clam, camp,
+                                  dlam_Xs ? djl : nullptr, damp_Xs ? dja : nullptr);
+            if (rc != BOSS_OK && rc != BOSS_E_ALLOC) return drain(c, rc);
+            done = rc == BOSS_OK;                            // (no memory for the set launches: the call goes on member by member)
+        }
+        const int tiles = (M + 31) / 32;
+        for (int i = 0; i < n && !done; ++i) {
+            const double *cl = clam + (size_t)i * d * Mp, *ca = camp + (size_t)i * Mp;
+            rc = grad_enqueue(gps[i], &cd, mean_Xs ? dmean + (size_t)i * M : nullptr, nullptr, dmu_ + (size_t)i * M, dvar_ + (size_t)i * M,
+                              nullptr, nullptr, cl, ca, dsums);
+            if (rc) return drain(c, rc);
+            hipLaunchKernelGGL(gibbs_grad_fold_kernel, dim3(tiles), dim3(256), 0, s, (const double*)dsums, Mp,
+                               dlam_Xs ? (const double*)djl + (size_t)i * d * dm : nullptr, damp_Xs ? (const double*)dja + (size_t)i * dm : nullptr,
+                               ca, mean_grad ? (const double*)dmg + (size_t)i * dm : nullptr, dgm + (size_t)i * dm, dgv + (size_t)i * dm, d, M);
+        }
+    }
+    if (ei) {
+        hipLaunchKernelGGL(ei_grad_set_kernel, dim3((M + 127) / 128), dim3(128), 0, s, (const double*)dmu_, (const double*)dvar_,
+                           (const double*)dgm, (const double*)dgv, M, d, ei->S, par, (const double*)dcoef, (const double*)dymax,
+                           ei->valid_mask ? (const unsigned char*)dmask : nullptr, dacq, ddacq);
+        return finish(c, {{ei->acq_out, dacq, sizeof(double) * M}, {ei->dacq_out, ddacq, sizeof(double) * dm}});
+    }
+    // (member after member in one array: the smallest flat index is the first member's first offender)
+    hipLaunchKernelGGL(clip_var_kernel, dim3((unsigned)((nm + 255) / 256)), dim3(256), 0, s, dvar_, (int)nm, dbad);
+    unsigned long long bad = 0;
+    rc = finish(c, {{mu, dmu_, sizeof(double) * nm}, {var, dvar_, sizeof(double) * nm}, {dmu, dgm, sizeof(double) * ndm},
+                    {dvar, dgv, sizeof(double) * ndm}, {&bad, dbad, sizeof bad}});
+    if (rc) return rc;
+    return bad != ~0ULL ? neg_var_error(bad_index_out, bad % (unsigned long long)M, var[bad]) : BOSS_OK;
+}
+
+extern "C" int boss_ngp_predict_grad_set(int n, boss_gp_t* const* gps, int M, const double* Xs, const double* lam_Xs, const double* amp_Xs,
+                                         const double* dlam_Xs, const double* damp_Xs, const double* mean_Xs, const double* mean_grad,
+                                         double* mu, double* var, double* dmu, double* dvar, long* bad_index_out) {
+    if (n < 1 || !gps || !Xs || !lam_Xs || !amp_Xs || !mu || !var || !dmu || !dvar) return fail(BOSS_E_INVALID, "NULL argument or n < 1");
+    return ngp_grad_set_call(n, gps, M, Xs, lam_Xs, amp_Xs, dlam_Xs, damp_Xs, mean_Xs, mean_grad, nullptr, mu, var, dmu, dvar, bad_index_out);
+}
+
+// The acquisition of boss_acq_ei_grad_set for nonstationary posteriors: gps[p + P·s], every member with its own latent values and
+// Jacobians at the candidates; per sample the chain rule of boss_acq_ei_grad_moments on its P members' moments and gradients, the
+// samples summed in ascending s and divided once (ei_grad_set_kernel).  Nothing but acq / dacq leaves the device.
+extern "C" int boss_ngp_acq_ei_grad_set(int P, int S, boss_gp_t* const* gps, int M, const double* Xs, const double* lam_Xs,
+                                        const double* amp_Xs, const double* dlam_Xs, const double* damp_Xs, const double* mean_Xs,
+                                        const double* mean_grad, const double* fit_coefs, const double* y_max, int has_best, double best,
+                                        const unsigned char* valid_mask, double* acq_out, double* dacq_out) {
+    if (P < 1 || S < 1 || !gps || !Xs || !lam_Xs || !amp_Xs || !fit_coefs || !acq_out || !dacq_out) return fail(BOSS_E_INVALID, "bad arguments");
+    if ((long long)P * S > (1LL << 30)) return fail(BOSS_E_INVALID, "P·S·M above 2^30 is not supported");
+    const NgpEiArgs ei{P, S, fit_coefs, y_max, has_best, best, valid_mask, acq_out, dacq_out};
+    return ngp_grad_set_call(P * S, gps, M, Xs, lam_Xs, amp_Xs, dlam_Xs, damp_Xs, mean_Xs, mean_grad, &ei, nullptr, nullptr, nullptr, nullptr,
+                             nullptr);
 }
 
 // The same chain rule from moments and moment gradients the caller already holds (nonstationary posteriors: boss_ngp_predict_grad per

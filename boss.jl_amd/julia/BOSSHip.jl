@@ -1002,6 +1002,53 @@ function mean_and_var_grad(p::HipNonstationaryPosterior, X::AbstractMatrix{<:Rea
         p.post.h.h, M, Xs, λ, α, Dλ, Dα, mean_vals(p.post.mean, Xs), mean_grad, μ, σ2, dμ, dσ2, bad))
     return μ, σ2, dμ, dσ2
 end
+# the arrays the two set calls below read: every member's λ(x*), α(x*) and ForwardDiff Jacobians at the rounded candidates, member after member
+function latent_set_args(ps::AbstractVector{HipNonstationaryPosterior}, Xs::Matrix{Float64})
+    Xr = rounded(Xs, ps[1].discrete); d, M = size(Xs); n = length(ps)
+    Λ = Array{Float64}(undef, d, M, n); A = Matrix{Float64}(undef, M, n)
+    Dλ = Array{Float64}(undef, d, d, M, n); Dα = Array{Float64}(undef, d, M, n)
+    for (i, p) in enumerate(ps)
+        Λ[:, :, i] .= reduce(hcat, p.f_λ.(eachcol(Xr))); A[:, i] .= p.f_α.(eachcol(Xr))
+        for (j, x) in enumerate(eachcol(Xr))
+            Dλ[:, :, j, i] .= ForwardDiff.jacobian(p.f_λ, collect(x)); Dα[:, j, i] .= ForwardDiff.gradient(p.f_α, collect(x))
+        end
+    end
+    isnothing(ps[1].discrete) || (Dλ[:, ps[1].discrete, :, :] .= 0.0; Dα[ps[1].discrete, :, :] .= 0.0)
+    ms = all(p -> isnothing(p.post.mean), ps) ? C_NULL : reduce(hcat, (Vector{Float64}(mean_vals(p.post.mean, Xs)) for p in ps))
+    return Λ, A, Dλ, Dα, ms
+end
+"""
+`mean_and_var_grad` of n nonstationary posteriors at the same candidates in ONE call (`boss_ngp_predict_grad_set`): returns
+(μ (M×n), σ² (M×n), ∂μ/∂x (d×M×n), ∂σ²/∂x (d×M×n)), member after member.  (Not run here: no Julia toolchain.)
+"""
+function mean_and_var_grad(ps::AbstractVector{HipNonstationaryPosterior}, X::AbstractMatrix{<:Real}; mean_grad = C_NULL)
+    Xs = Matrix{Float64}(X); d, M = size(Xs); n = length(ps); Λ, A, Dλ, Dα, ms = latent_set_args(ps, Xs)
+    μ = Matrix{Float64}(undef, M, n); σ2 = similar(μ); dμ = Array{Float64}(undef, d, M, n); dσ2 = similar(dμ); bad = Ref{Clong}(-1)
+    hs = Ptr{Cvoid}[p.post.h.h for p in ps]
+    GC.@preserve ps check(ccall((:boss_ngp_predict_grad_set, lib), Cint,
+        (Cint, Ptr{Ptr{Cvoid}}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+         Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Clong}),
+        n, hs, M, Xs, Λ, A, Dλ, Dα, ms, mean_grad, μ, σ2, dμ, dσ2, bad))
+    return μ, σ2, dμ, dσ2
+end
+"""
+EI × feasibility and its gradient w.r.t. the candidates averaged over the S sampled posteriors of a nonstationary model
+(`posts[s][p]`, src/acquisitions/expected_improvement.jl:87-90 under the AD of OptimizationAM, optimization.jl:89-118) in ONE device
+call (`boss_ngp_acq_ei_grad_set`): the latent Jacobians are folded in on the device, only acq (M) and ∂acq/∂x (d×M) come back.
+(Not run here: no Julia toolchain.)
+"""
+function acq_grad_samples(problem::BOSS.BossProblem, xs::AbstractMatrix{Float64}, posts::AbstractVector{<:AbstractVector{HipNonstationaryPosterior}};
+                          mean_grad = C_NULL)
+    d, M = size(xs); S = length(posts); P = length(posts[1]); coefs, ymax, hb, b, mask = ei_arguments(problem, xs)
+    ps = HipNonstationaryPosterior[posts[s][p] for s in 1:S for p in 1:P]                   # member p + P·s
+    Xs = Matrix{Float64}(xs); Λ, A, Dλ, Dα, ms = latent_set_args(ps, Xs)
+    acq = Vector{Float64}(undef, M); dacq = Matrix{Float64}(undef, d, M); hs = Ptr{Cvoid}[p.post.h.h for p in ps]
+    GC.@preserve posts check(ccall((:boss_ngp_acq_ei_grad_set, lib), Cint,
+        (Cint, Cint, Ptr{Ptr{Cvoid}}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+         Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cdouble, Ptr{UInt8}, Ptr{Cdouble}, Ptr{Cdouble}),
+        P, S, hs, M, Xs, Λ, A, Dλ, Dα, ms, mean_grad, coefs, ymax, hb, b, mask, acq, dacq))
+    return acq, dacq
+end
 "EI × feasibility and its gradient w.r.t. the candidates from per-output moments and gradients (P-vectors of what `mean_and_var_grad` returns)."
 function acq_grad_from_moments(problem::BOSS.BossProblem, xs::AbstractMatrix{Float64}, moms::AbstractVector; device = 0)
     d, M = size(xs); P = length(moms); coefs, ymax, hb, b, mask = ei_arguments(problem, xs)

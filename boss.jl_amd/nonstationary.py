@@ -408,3 +408,53 @@ def nonstationary_acq_ei_batch(posts: Sequence[Sequence[HipNonstationaryPosterio
         ms = None if all(m is None for m in means) else np.stack([np.zeros(M) if m is None else m for m in means])
         mu[:, i, :], var[:, i, :] = api.ngp_predict_set([p.gp for p in sl], Xs, lam, amp, ms)
     return api.acq_ei_moments(mu, var, fit_coefs, y_max, best, valid_mask, posts[0][0].gp.device)
+
+
+def nonstationary_acq_ei_grad_batch(posts: Sequence[Sequence[HipNonstationaryPosteriorSlice]], Xs, fit_coefs, y_max=None, best=None,
+                                    valid_mask=None, lam_jac=None, amp_jac=None, mean_grad=None, fd_step: float = 1e-6):
+    """EI × feasibility AND its gradient w.r.t. the candidates, averaged over the S sampled posteriors posts[s][i]
+    (src/acquisitions/expected_improvement.jl:87-90 under the ForwardDiff of OptimizationAM, optimization.jl:89-118) at the candidates
+    Xs d×M in ONE boss_ngp_acq_ei_grad_set call.  Every slice's latent closures are evaluated at the rounded candidates; their
+    Jacobians come from lam_jac[s][i](x) -> d×d / amp_jac[s][i](x) -> d, or by central differences of the closures (step fd_step),
+    exactly as HipNonstationaryPosteriorSlice.mean_and_var_grad takes them; discrete dimensions get zero columns.  mean_grad: None or
+    [S][P][d][M].  Returns (acq[M], dacq[d, M])."""
+    Xs = np.asarray(Xs, float)
+    if Xs.ndim == 1:
+        Xs = Xs[:, None]
+    S, P = len(posts), len(posts[0])
+    if any(len(row) != P for row in posts):
+        raise ValueError("posts must be S rows of P slices")
+    d, M = Xs.shape
+    n = S * P
+    Xr = posts[0][0]._round(Xs)
+    lam = np.empty((d, M, n), order="F")
+    amp = np.empty((M, n), order="F")
+    Dl = np.empty((d, d, M, n), order="F")
+    Da = np.empty((d, M, n), order="F")
+    means = []
+
+    def jac(f, x, n_out):
+        J = np.zeros((n_out, d))
+        for m in range(d):
+            e = np.zeros(d)
+            e[m] = fd_step
+            J[:, m] = (np.atleast_1d(np.asarray(f(x + e), float)) - np.atleast_1d(np.asarray(f(x - e), float))) / (2 * fd_step)
+        return J
+    for s in range(S):
+        for i in range(P):
+            p, k = posts[s][i], i + P * s
+            lj = None if lam_jac is None else lam_jac[s][i]
+            aj = None if amp_jac is None else amp_jac[s][i]
+            lam[:, :, k] = _cols(p.f_lam, Xr).T
+            amp[:, k] = _cols(p.f_amp, Xr).reshape(-1)
+            for j in range(M):
+                Dl[:, :, j, k] = np.asarray(lj(Xr[:, j]), float) if lj else jac(p.f_lam, Xr[:, j], d)
+                Da[:, j, k] = np.asarray(aj(Xr[:, j]), float).reshape(-1) if aj else jac(p.f_amp, Xr[:, j], 1)[0]
+            means.append(None if p.mean_fn is None else np.array([float(p.mean_fn(Xs[:, j])) for j in range(M)]))
+    disc = posts[0][0].discrete
+    if disc is not None:                                     # rounded dimensions: the latent models are piecewise constant in them
+        Dl[:, disc, :, :] = 0.0
+        Da[disc, :, :] = 0.0
+    ms = None if all(m is None for m in means) else np.stack([np.zeros(M) if m is None else m for m in means])
+    mg = None if mean_grad is None else np.asarray(mean_grad, float).reshape(n, d, M)
+    return api.ngp_acq_ei_grad_set([[p.gp for p in row] for row in posts], Xs, lam, amp, Dl, Da, fit_coefs, y_max, best, valid_mask, ms, mg)

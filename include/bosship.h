@@ -438,7 +438,7 @@ int boss_acq_ei_grad(int P, boss_gp_t* const* gps, int M, const double* Xs, cons
  * differentiates when the model parameters are BI samples (src/acquisitions/expected_improvement.jl:87-90 inside
  * src/acquisition_maximizers/optimization.jl:89-118).
  *   gps        S×P handles, gps[p + P*s] as boss_acq_ei: plain (also semiparametric) or gradient-observation posteriors, all on one
- *              device with one x_dim; nonstationary handles: BOSS_E_INVALID (boss_ngp_predict_grad + boss_acq_ei_grad_moments);
+ *              device with one x_dim; nonstationary handles: BOSS_E_INVALID (they bring latent values: boss_ngp_acq_ei_grad_set);
  *   mean_Xs    NULL or S×P×M, index j + M*(p + P*s);  mean_grad NULL or [s][p][d×M column-major] (both NULL for gradient observations);
  *   the other arguments as boss_acq_ei_grad.
  * For every sample s, (acq_s, grad acq_s) are exactly what boss_acq_ei_grad defines for its P handles; the outputs are
@@ -453,6 +453,39 @@ int boss_acq_ei_grad(int P, boss_gp_t* const* gps, int M, const double* Xs, cons
 int boss_acq_ei_grad_set(int P, int S, boss_gp_t* const* gps, int M, const double* Xs, const double* mean_Xs,
                          const double* mean_grad, const double* fit_coefs, const double* y_max, int has_best,
                          double best, const unsigned char* valid_mask, double* acq_out, double* dacq_out);
+
+/* boss_ngp_predict_grad for n nonstationary posteriors at the same M candidates in ONE call, and the sample-averaged acquisition
+ * gradient on top of it: boss_acq_ei_grad_set for NonstationaryGP posteriors (BI samples of a finite_nongp model under
+ * OptimizationAM, src/acquisitions/expected_improvement.jl:87-90 inside src/acquisition_maximizers/optimization.jl:89-118).
+ * Member after member, each member in the layout of the single-handle call (n = P*S, member i = p + P*s in the acquisition call):
+ *   lam_Xs d×M×n, amp_Xs M×n         as boss_ngp_predict_set;
+ *   dlam_Xs d×d×M×n or NULL          per member as boss_ngp_predict_grad (NULL: constant lengthscales for all members);
+ *   damp_Xs d×M×n or NULL            per member as boss_ngp_predict_grad (NULL: constant amplitude for all members);
+ *   mean_Xs M×n or NULL, mean_grad d×M×n column-major per member or NULL;
+ *   mu, var n×M (var clipped as boss_ngp_predict_grad clips it), dmu, dvar n blocks of d×M column-major (dvar: gradient of the
+ *   UNclipped variance).
+ * boss_ngp_predict_grad_set: member i's outputs are what boss_ngp_predict_grad defines for gps[i] with member i's arguments; the
+ * first member with a variance below -1e-8 fails the call with BOSS_E_NEG_VAR, bad_index_out = its first such candidate.
+ * boss_ngp_acq_ei_grad_set: for every sample s, (acq_s, grad acq_s) is what boss_acq_ei_grad_moments returns on the P members'
+ * boss_ngp_predict_grad results; the outputs are (sum_s acq_s)/S and (sum_s grad acq_s)/S, summed in ascending s and divided once
+ * (no atomics: repeated calls agree bit for bit).  S = 1 is the P-output MAP case.  A variance below -1e-8 poisons the candidate
+ * with -Inf (gradient 0) as in boss_acq_ei_grad_set.  Between the one upload and the one copy back everything stays on the device:
+ * the Jacobians are folded in there.
+ * Handles: from boss_ngp_create or boss_ngp_fit_batch (other kinds: BOSS_E_INVALID), fitted (BOSS_E_NOT_FITTED), one device, one
+ * x_dim <= 16, the same discrete dimensions; lengthscales finite and > 0, amplitudes finite and >= 0 (BOSS_E_INVALID).
+ * Limits: n*M <= 2^30 and n*M*x_dim^2 <= 2^27 (the Jacobian upload, 1 GiB), else BOSS_E_INVALID.
+ * Equally shaped members (those of one boss_ngp_fit_batch; the shape test of boss_ngp_predict_set) run forward substitution,
+ * adjoint substitution, accumulation and Jacobian fold with grid = candidate tiles x members; any other list,
+ * BOSS_NO_SET_PREDICT=1 and a failed allocation of the set path's scratch go member by member inside the same call.  As
+ * boss_acq_ei_grad_set, either path keeps a transposed copy of every member's factor (BOSS_E_ALLOC when that cannot be allocated).
+ * After an error nothing stays enqueued and every handle stays usable. */
+int boss_ngp_predict_grad_set(int n, boss_gp_t* const* gps, int M, const double* Xs, const double* lam_Xs, const double* amp_Xs,
+                              const double* dlam_Xs, const double* damp_Xs, const double* mean_Xs, const double* mean_grad,
+                              double* mu, double* var, double* dmu, double* dvar, long* bad_index_out);
+int boss_ngp_acq_ei_grad_set(int P, int S, boss_gp_t* const* gps, int M, const double* Xs, const double* lam_Xs,
+                             const double* amp_Xs, const double* dlam_Xs, const double* damp_Xs, const double* mean_Xs,
+                             const double* mean_grad, const double* fit_coefs, const double* y_max, int has_best, double best,
+                             const unsigned char* valid_mask, double* acq_out, double* dacq_out);
 
 /* ---- tracked candidates -----------------------------------------------------------------------
  * SequentialBatchAM (src/acquisition_maximizers/batch.jl:26-38) re-evaluates the acquisition on
