@@ -8,13 +8,16 @@ the repo-root shim:  `import boss_jl_amd`.
 from . import api  # noqa: F401
 from .api import (BossError, Candidates, DomainError, GP, PosDefException, acq_ei, fit,  # noqa: F401
                   ggp_fit_batch, ggp_loglike_batch, load_library, loglike_batch, ngp_fit_batch, ngp_loglike_batch,
-                  ngp_acq_ei_grad_set, ngp_predict_grad_set, ngp_predict_set)
+                  ngp_acq_ei_grad_set, ngp_predict_grad_set, ngp_predict_set, NgpLatents, ngp_acq_ei_grad_set_lat,
+                  ngp_predict_grad_set_lat, ngp_predict_set_lat)
 from .problem import (BossOptions, BossProblem, Dirac, Domain, ExperimentData, ExpectedImprovement,  # noqa: F401,E402
                       LinFitness, LogNormal, MvDirac, MvLogNormal, NonlinFitness)
 from .model import HipGaussianProcess, HipGPParams, average_mean  # noqa: F401,E402
 from .gradient_gp import (GradientData, HipGradientGaussianProcess, HipGradientGPParams,  # noqa: F401,E402
                           join_gradient_slices)
 from .nonstationary import HipNonstationaryGP, HipParametrizedGP, stack_latents  # noqa: F401,E402
+from .nonstationary import (LatentActivation, constant_latent, exp_act, identity_act, latent_transform,  # noqa: F401,E402
+                            softplus)
 from .nonstationary import data_loglike_batch as nonstationary_data_loglike_batch  # noqa: F401,E402
 from .nonstationary import data_loglike_grad_batch as nonstationary_data_loglike_grad_batch  # noqa: F401,E402
 from .nonstationary import (nonstationary_acq_ei_batch, nonstationary_acq_ei_grad_batch,  # noqa: F401,E402

@@ -99,6 +99,19 @@ SIGNATURES = {
                                             _c_dp, _c_dp, _c_dp, _c_dp, C.POINTER(C.c_long)]),
     "boss_ngp_acq_ei_grad_set": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_int, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp,
                                            _c_dp, _c_dp, _c_dp, C.c_int, C.c_double, _c_ucp, _c_dp, _c_dp]),
+    "boss_nlat_create": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_void_p), _c_dp, C.c_void_p, C.c_double, C.c_void_p, C.c_double,
+                                   C.POINTER(C.c_int), _c_dp, C.POINTER(C.c_int), _c_dp, _c_ucp, C.POINTER(C.c_void_p)]),
+    "boss_nlat_free": (None, [C.c_void_p]),
+    "boss_nlat_eval": (C.c_int, [C.c_void_p, C.c_int, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, C.POINTER(C.c_long)]),
+    "boss_ngp_predict_lat": (C.c_int, [C.c_void_p, C.c_int, _c_dp, C.c_void_p, _c_dp, _c_dp, _c_dp, C.POINTER(C.c_long)]),
+    "boss_ngp_predict_grad_lat": (C.c_int, [C.c_void_p, C.c_int, _c_dp, C.c_void_p, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp,
+                                            C.POINTER(C.c_long)]),
+    "boss_ngp_predict_set_lat": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.c_int, _c_dp, C.POINTER(C.c_void_p), _c_dp, _c_dp, _c_dp,
+                                           C.POINTER(C.c_long)]),
+    "boss_ngp_predict_grad_set_lat": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.c_int, _c_dp, C.POINTER(C.c_void_p), _c_dp, _c_dp,
+                                                _c_dp, _c_dp, _c_dp, _c_dp, C.POINTER(C.c_long)]),
+    "boss_ngp_acq_ei_grad_set_lat": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_int, _c_dp, C.POINTER(C.c_void_p), _c_dp,
+                                               _c_dp, _c_dp, _c_dp, C.c_int, C.c_double, _c_ucp, _c_dp, _c_dp]),
     "boss_track_create": (C.c_int, [C.c_void_p, C.c_void_p, _c_dp, C.POINTER(C.c_void_p)]),
     "boss_track_free": (None, [C.c_void_p]),
     "boss_track_sync": (C.c_int, [C.c_void_p]),
@@ -616,6 +629,133 @@ class GibbsGP(GP):
         _check(rc)
         return mu, var, dmu, dvar
 
+    def _lat_args(self, Xs, lat, mean_Xs, mean_grad=None):
+        Xs = _f64(Xs)
+        if Xs.ndim == 1:
+            Xs = _f64(Xs.reshape(-1, 1))
+        if Xs.ndim != 2 or Xs.shape[0] != self.d:
+            raise ValueError("candidates must be d×M")
+        if not isinstance(lat, NgpLatents) or lat._h is None:
+            raise BossError(BOSS_E_INVALID, "lat must be an open NgpLatents")
+        M = Xs.shape[1]
+        ms = None if mean_Xs is None else _f64(np.asarray(mean_Xs).reshape(-1), 1)
+        mg = None if mean_grad is None else _f64(np.asarray(mean_grad, dtype=np.float64).reshape(self.d, M), 2)
+        return Xs, M, ms, mg
+
+    def predict_lat(self, Xs, lat: "NgpLatents", mean_Xs=None):
+        """predict with λ(x*), α(x*) read from the resident latent models `lat` on the device (boss_ngp_predict_lat)."""
+        Xs, M, ms, _ = self._lat_args(Xs, lat, mean_Xs)
+        mu, var = np.zeros(M), np.zeros(M)
+        bad = C.c_long(-1)
+        rc = load_library().boss_ngp_predict_lat(self._h, M, _dp(Xs), lat._h, _dp(ms), _dp(mu), _dp(var), C.byref(bad))
+        if rc == BOSS_E_NEG_VAR:
+            e = DomainError(rc, load_library().boss_last_error().decode())
+            e.bad_index = bad.value
+            raise e
+        _check(rc)
+        return mu, var
+
+    def predict_grad_lat(self, Xs, lat: "NgpLatents", mean_Xs=None, mean_grad=None):
+        """predict_grad with the latent values and their analytic Jacobians read from `lat` on the device
+        (boss_ngp_predict_grad_lat).  Returns (mu[M], var[M], dmu[d,M], dvar[d,M])."""
+        Xs, M, ms, mg = self._lat_args(Xs, lat, mean_Xs, mean_grad)
+        mu, var = np.zeros(M), np.zeros(M)
+        dmu, dvar = np.zeros((self.d, M), order="F"), np.zeros((self.d, M), order="F")
+        bad = C.c_long(-1)
+        rc = load_library().boss_ngp_predict_grad_lat(self._h, M, _dp(Xs), lat._h, _dp(ms), _dp(mg), _dp(mu), _dp(var), _dp(dmu),
+                                                      _dp(dvar), C.byref(bad))
+        if rc == BOSS_E_NEG_VAR:
+            e = DomainError(rc, load_library().boss_last_error().decode())
+            e.bad_index = bad.value
+            raise e
+        _check(rc)
+        return mu, var, dmu, dvar
+
+
+LATENT_TARGETS = {"none": 0, "normal": 1, "lognormal": 2, "uniform": 3}       # BOSS_LT_*
+LATENT_ACTS = {"identity": 0, "softplus": 1, "exp": 2}                          # BOSS_ACT_*
+
+
+class NgpLatents:
+    """The latent models of ONE output of a NonstationaryGP, resident on the device (boss_nlat_t): d lengthscale latents, the
+    amplitude latent and optionally the noise latent.  Every latent is either a float (a constant, taken as it is) or a pair
+    (gp, spec): `gp` a fitted plain GP handle, `spec` = (target, (p0, p1), activation, par) with the names of LATENT_TARGETS /
+    LATENT_ACTS (or their codes).  create snapshots what the posterior means need: afterwards the handles may be updated or closed."""
+
+    def __init__(self, lam, amp, noise=None, discrete=None, device: int = 0):
+        lam = list(lam)
+        d = len(lam)
+        lats = lam + [amp, noise]
+        nq = d + 2
+        handles = (C.c_void_p * nq)()
+        cst = np.full(nq, np.nan)
+        tgt = (C.c_int * nq)()
+        act = (C.c_int * nq)()
+        tpar = np.zeros(2 * nq)
+        apar = np.zeros(nq)
+        for q, v in enumerate(lats):
+            if v is None:
+                if q != d + 1:
+                    raise BossError(BOSS_E_INVALID, "only the noise latent may be left out")
+                continue
+            if isinstance(v, (tuple, list)):
+                gp, (t, tp, a, ap) = v
+                if getattr(gp, "_h", None) is None:             # a NULL handle would be read as "the constant beside it"
+                    name = f"lengthscale latent {q}" if q < d else ("amplitude latent", "noise latent")[q - d]
+                    raise BossError(BOSS_E_INVALID, f"the {name}'s GP handle is closed")
+                handles[q] = gp._h
+                tgt[q] = LATENT_TARGETS[t] if isinstance(t, str) else int(t)
+                act[q] = LATENT_ACTS[a] if isinstance(a, str) else int(a)
+                tpar[2 * q:2 * q + 2] = tp
+                apar[q] = ap
+            else:
+                cst[q] = float(v)
+        self.d = d
+        self.device = device
+        self.has_noise = noise is not None
+        disc = None if discrete is None else np.ascontiguousarray(np.asarray(discrete, dtype=bool).astype(np.uint8))
+        if disc is not None and disc.shape != (d,):
+            raise BossError(BOSS_E_INVALID, "discrete must have one flag per dimension")
+        h = C.c_void_p()
+        self._h = None
+        _check(load_library().boss_nlat_create(device, d, handles, _dp(cst), handles[d], float(cst[d]), handles[d + 1], float(cst[d + 1]),
+                                               tgt, _dp(tpar), act, _dp(apar), _ucp(disc), C.byref(h)))
+        self._h = h
+
+    def eval(self, Xs, jac: bool = True, noise: bool = False):
+        """λ(x*) d×M, α(x*) M[, σ(x*) M][, ∂λ/∂x d×d×M ([l, m, j] = ∂λ_l/∂x_m at candidate j), ∂α/∂x d×M] at the candidates
+        (boss_nlat_eval): the arrays GibbsGP.predict / predict_grad take.  Returns (lam, amp, noise or None, dlam or None, damp or
+        None).  An invalid value raises BossError (BOSS_E_INVALID) with .bad_index = the first such candidate."""
+        Xs = _f64(Xs)
+        if Xs.ndim == 1:
+            Xs = _f64(Xs.reshape(-1, 1))
+        if Xs.ndim != 2 or Xs.shape[0] != self.d:
+            raise ValueError("candidates must be d×M")
+        d, M = Xs.shape
+        lam = np.zeros((d, M), order="F")
+        amp = np.zeros(M)
+        noi = np.zeros(M) if noise else None
+        dl = np.zeros((d, d, M), order="F") if jac else None
+        da = np.zeros((d, M), order="F") if jac else None
+        bad = C.c_long(-1)
+        rc = load_library().boss_nlat_eval(self._h, M, _dp(Xs), _dp(lam), _dp(amp), _dp(noi), _dp(dl), _dp(da), C.byref(bad))
+        if rc != BOSS_OK:
+            e = BossError(rc, load_library().boss_last_error().decode())
+            e.bad_index = bad.value
+            raise e
+        return lam, amp, noi, dl, da
+
+    def close(self):
+        if self._h is not None:
+            load_library().boss_nlat_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
 
 class Candidates:
     """A resident batch of candidate points (boss_cand_t)."""
@@ -958,6 +1098,96 @@ def ngp_predict_set(gps: Sequence["GibbsGP"], Xs, lam_Xs, amp_Xs, mean_Xs=None):
         raise e
     _check(rc)
     return mu, var
+
+
+def _lat_set_args(gps, lats, Xs, mean_Xs, mean_grad=None):
+    """What the _lat set calls read, converted and checked (no device is touched)."""
+    n = len(gps)
+    if n < 1 or len(lats) != n:
+        raise BossError(BOSS_E_INVALID, "one latent object per posterior is needed (at least one)")
+    if any(not isinstance(L, NgpLatents) or L._h is None for L in lats):
+        raise BossError(BOSS_E_INVALID, "lats must be open NgpLatents")
+    d = gps[0].d
+    Xs = _f64(Xs)
+    if Xs.ndim == 1:
+        Xs = _f64(Xs.reshape(-1, 1))
+    if Xs.ndim != 2 or Xs.shape[0] != d:
+        raise ValueError("candidates must be d×M")
+    M = Xs.shape[1]
+    ms = mg = None
+    if mean_Xs is not None:
+        ms = np.ascontiguousarray(np.asarray(mean_Xs, dtype=np.float64))
+        if ms.shape != (n, M):
+            raise BossError(BOSS_E_INVALID, "mean_Xs must be n×M (one row per posterior)")
+    if mean_grad is not None:
+        a = np.asarray(mean_grad, dtype=np.float64)
+        if a.shape != (n, d, M):
+            raise BossError(BOSS_E_INVALID, "mean_grad must be n×d×M (one block per posterior)")
+        mg = np.ascontiguousarray(a.transpose(0, 2, 1))
+    arr = (C.c_void_p * n)(*[g._h.value for g in gps])
+    larr = (C.c_void_p * n)(*[L._h.value for L in lats])
+    return n, d, M, Xs, ms, mg, arr, larr
+
+
+def ngp_predict_set_lat(gps: Sequence["GibbsGP"], Xs, lats: Sequence["NgpLatents"], mean_Xs=None):
+    """ngp_predict_set with every member's λ(x*), α(x*) read from its resident latent models (boss_ngp_predict_set_lat)."""
+    gps, lats = list(gps), list(lats)
+    n, d, M, Xs, ms, _, arr, larr = _lat_set_args(gps, lats, Xs, mean_Xs)
+    mu, var = np.zeros((n, M)), np.zeros((n, M))
+    bad = C.c_long(-1)
+    rc = load_library().boss_ngp_predict_set_lat(n, arr, M, _dp(Xs), larr, _dp(ms), _dp(mu), _dp(var), C.byref(bad))
+    if rc == BOSS_E_NEG_VAR:
+        e = DomainError(rc, load_library().boss_last_error().decode())
+        e.bad_index = bad.value
+        raise e
+    _check(rc)
+    return mu, var
+
+
+def ngp_predict_grad_set_lat(gps: Sequence["GibbsGP"], Xs, lats: Sequence["NgpLatents"], mean_Xs=None, mean_grad=None):
+    """ngp_predict_grad_set with every member's latent values and analytic Jacobians read from its resident latent models
+    (boss_ngp_predict_grad_set_lat).  Returns (mu[n, M], var[n, M], dmu[n, d, M], dvar[n, d, M])."""
+    gps, lats = list(gps), list(lats)
+    n, d, M, Xs, ms, mg, arr, larr = _lat_set_args(gps, lats, Xs, mean_Xs, mean_grad)
+    mu, var = np.zeros((n, M)), np.zeros((n, M))
+    dmu, dvar = np.zeros((n, M, d)), np.zeros((n, M, d))
+    bad = C.c_long(-1)
+    rc = load_library().boss_ngp_predict_grad_set_lat(n, arr, M, _dp(Xs), larr, _dp(ms), _dp(mg), _dp(mu), _dp(var), _dp(dmu), _dp(dvar),
+                                                      C.byref(bad))
+    if rc == BOSS_E_NEG_VAR:
+        e = DomainError(rc, load_library().boss_last_error().decode())
+        e.bad_index = bad.value
+        raise e
+    _check(rc)
+    return mu, var, dmu.transpose(0, 2, 1), dvar.transpose(0, 2, 1)
+
+
+def ngp_acq_ei_grad_set_lat(gps: Sequence[Sequence["GibbsGP"]], Xs, lats: Sequence[Sequence["NgpLatents"]], fit_coefs, y_max=None,
+                            best=None, valid_mask=None, mean_Xs=None, mean_grad=None):
+    """ngp_acq_ei_grad_set with the latent values and Jacobians of member gps[s][p] read from lats[s][p] on the device
+    (boss_ngp_acq_ei_grad_set_lat).  Returns (acq[M], dacq[d, M])."""
+    S = len(gps)
+    P = len(gps[0]) if S else 0
+    if S < 1 or P < 1 or any(len(row) != P for row in gps) or len(lats) != S or any(len(row) != P for row in lats):
+        raise BossError(BOSS_E_INVALID, "gps and lats must be S rows of P")
+    flat_g = [gps[s][p] for s in range(S) for p in range(P)]                 # member i = p + P·s
+    flat_l = [lats[s][p] for s in range(S) for p in range(P)]
+    n, d, M, Xs, ms, mg, arr, larr = _lat_set_args(flat_g, flat_l, Xs, mean_Xs, mean_grad)
+    coefs = _f64(np.asarray(fit_coefs).reshape(-1), 1)
+    if coefs.shape[0] != P:
+        raise BossError(BOSS_E_INVALID, "fit_coefs must have one entry per output")
+    ym = None if y_max is None else _f64(np.asarray(y_max).reshape(-1), 1)
+    if ym is not None and ym.shape[0] != P:
+        raise BossError(BOSS_E_INVALID, "y_max must have one entry per output")
+    mask = None if valid_mask is None else np.ascontiguousarray(np.asarray(valid_mask, dtype=bool).astype(np.uint8))
+    if mask is not None and mask.shape != (M,):
+        raise BossError(BOSS_E_INVALID, "valid_mask must have one entry per candidate")
+    acq = np.zeros(M)
+    dacq = np.zeros((d, M), order="F")
+    _check(load_library().boss_ngp_acq_ei_grad_set_lat(P, S, arr, M, _dp(Xs), larr, _dp(ms), _dp(mg), _dp(coefs), _dp(ym),
+                                                       0 if best is None else 1, 0.0 if best is None else float(best), _ucp(mask),
+                                                       _dp(acq), _dp(dacq)))
+    return acq, dacq
 
 
 def acq_ei(gps: Sequence[Sequence[GP]], cand: Candidates, fit_coefs, y_max=None, best=None, valid_mask=None,

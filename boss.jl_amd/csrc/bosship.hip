@@ -24,6 +24,7 @@
 #include "chain.hpp"
 #include "small_calls.hpp"
 #include "rider.hpp"
+#include "latent_kernels.hpp"
 
 using namespace boss;
 
@@ -127,7 +128,7 @@ struct Ctx {
     bool prof_on = false;
     std::map<std::string, std::vector<std::pair<hipEvent_t, hipEvent_t>>> prof;
     std::vector<hipEvent_t> ev_pool;
-    Workspace vscratch, csc, pred, acq, batchA, batchX, batchMisc, craw, lgA, lgB, lgC, few, setdesc, setmom, gsetdesc;
+    Workspace vscratch, csc, pred, acq, batchA, batchX, batchMisc, craw, lgA, lgB, lgC, few, setdesc, setmom, gsetdesc, nlatjobs;
     // batched likelihood gradients: the gradient passes of consecutive sets rotate over LLG_BANKS streams, each with its
     // own bank of workspaces (bank 0 = the main stream and lgA/lgB/lgC)
     static constexpr int LLG_BANKS = 4;
@@ -636,6 +637,7 @@ static bool few_fused() {
 #include "host_factor.inc"
 #include "host_append.inc"
 #include "host_batch.inc"
+#include "host_latent.inc"
 #include "host_predict.inc"
 #include "host_acq.inc"
 #include "host_rider.inc"

@@ -691,6 +691,7 @@ extern "C" int boss_gp_predict(boss_gp_t* g, int M, const double* Xs, const doub
 // models at the candidates (evaluated at the ROUNDED candidate where dims are discrete, as DiscreteKernel does).
 // The candidates of a nonstationary call with the caller's λ(x*) (d×M) and α(x*) (M), checked and packed on the host (no device
 // work): points rounded where dims are discrete, all three column-padded to Mp.
+constexpr long long NGP_GRAD_SET_MAX_JAC = 1LL << 27;       // n·M·d² doubles of ∂λ/∂x (1 GiB) per call
 struct NgpCand {
     int Mp = 0;
     std::vector<double> x, lam, amp;
@@ -712,12 +713,39 @@ static int ngp_pack(const boss_gp* g, int M, const double* Xs, const double* lam
     pack_points(p.x, Xs, d, M, Mp, g->discrete.empty() ? nullptr : g->discrete.data());
     return BOSS_OK;
 }
+// The _lat calls pack the points alone: λ(x*), α(x*) come from the latent kernel.
+static void ngp_pack_x(const boss_gp* g, int M, const double* Xs, NgpCand& p) {
+    p.Mp = round_up(M, 64);
+    pack_points(p.x, Xs, g->d, M, p.Mp, g->discrete.empty() ? nullptr : g->discrete.data());
+}
 // ... and uploaded into the per-device candidate workspace (Craw | λ | α).  Caller holds the context lock.
-static int ngp_upload(Ctx* c, int d, int M, const NgpCand& p, boss_cand& cd, double*& clam, double*& camp) {
+// lat: the λ and α buffers are filled by the latent kernel instead (Craw | λ | α | flag | ∂λ/∂x | ∂α/∂x; the Jacobians where djl
+// is given); the call returns once the kernel's validity flag has been read (BOSS_E_INVALID: nothing stays enqueued).
+static int ngp_upload(Ctx* c, int d, int M, const NgpCand& p, boss_cand& cd, double*& clam, double*& camp,
+                      const boss_nlat_t* lat = nullptr, double** djl = nullptr, double** dja = nullptr) {
     const int Mp = p.Mp;
     hipStream_t s = c->stream;
-    int rc = ws_reserve(c->craw, sizeof(double) * ((size_t)2 * d * Mp + Mp));
+    const size_t dm = (size_t)d * M;
+    int rc = ws_reserve(c->craw, sizeof(double) * ((size_t)2 * d * Mp + Mp + (lat ? 1 + (djl ? dm * d + dm : 0) : 0)));
     if (rc) return rc;
+    if (lat) {
+        cd.ctx = c;
+        cd.d = d;
+        cd.M = M;
+        cd.Mp = Mp;
+        cd.Craw = (double*)c->craw.p;
+        clam = cd.Craw + (size_t)d * Mp;
+        camp = clam + (size_t)d * Mp;
+        unsigned long long* dbad = (unsigned long long*)(camp + Mp);
+        if (djl) {
+            *djl = camp + Mp + 1;
+            *dja = *djl + dm * d;
+        }
+        HIPCHK(hipMemcpyAsync(cd.Craw, p.x.data(), sizeof(double) * d * Mp, hipMemcpyHostToDevice, s));
+        boss_nlat_t* one = const_cast<boss_nlat_t*>(lat);
+        rc = nlat_enqueue(c, 1, &one, cd.Craw, Mp, M, clam, 0, camp, 0, djl ? *djl : nullptr, 0, djl ? *dja : nullptr, 0, nullptr, dbad);
+        return rc ? rc : nlat_check(c, dbad, nullptr);
+    }
     cd.ctx = c;
     cd.d = d;
     cd.M = M;
@@ -731,15 +759,22 @@ static int ngp_upload(Ctx* c, int d, int M, const NgpCand& p, boss_cand& cd, dou
     return BOSS_OK;
 }
 
-extern "C" int boss_ngp_predict(boss_gp_t* g, int M, const double* Xs, const double* lam_Xs, const double* amp_Xs,
-                                const double* mean_Xs, double* mu, double* var, long* bad_index) {
-    if (!g || !Xs || !lam_Xs || !amp_Xs || !mu || !var) return fail(BOSS_E_INVALID, "NULL argument");
+// (lat: the latent values come from a resident latent object — boss_ngp_predict_lat — instead of lam_Xs / amp_Xs)
+static int ngp_predict_call(boss_gp_t* g, int M, const double* Xs, const double* lam_Xs, const double* amp_Xs, const boss_nlat_t* lat,
+                            const double* mean_Xs, double* mu, double* var, long* bad_index) {
     if (!g->gibbs) return fail(BOSS_E_INVALID, "handle was not created by boss_ngp_create");
     if (M < 1) return fail(BOSS_E_INVALID, "M must be >= 1");
     if (bad_index) *bad_index = -1;
     if (!g->fitted) return fail(BOSS_E_NOT_FITTED, "handle has no valid factorisation");
     NgpCand pk;
-    int rc = ngp_pack(g, M, Xs, lam_Xs, amp_Xs, pk);
+    int rc = BOSS_OK;
+    if (lat) {
+        boss_nlat_t* one = const_cast<boss_nlat_t*>(lat);
+        if ((rc = nlat_match(1, &g, &one)) != BOSS_OK) return rc;
+        ngp_pack_x(g, M, Xs, pk);
+    } else {
+        rc = ngp_pack(g, M, Xs, lam_Xs, amp_Xs, pk);
+    }
     if (rc) return rc;
     Ctx* c = g->ctx;
     HIPCHK(hipSetDevice(c->device));
@@ -747,7 +782,7 @@ extern "C" int boss_ngp_predict(boss_gp_t* g, int M, const double* Xs, const dou
     hipStream_t s = c->stream;
     boss_cand cd;
     double *clam, *camp;
-    rc = ngp_upload(c, g->d, M, pk, cd, clam, camp);
+    rc = ngp_upload(c, g->d, M, pk, cd, clam, camp, lat);
     if (rc) return drain(c, rc);
     rc = ws_reserve(c->pred, sizeof(double) * (3 * (size_t)M + 2));   // mu | var | bad | mean
     if (rc) return drain(c, rc);
@@ -764,15 +799,25 @@ extern "C" int boss_ngp_predict(boss_gp_t* g, int M, const double* Xs, const dou
     if (rc) return rc;
     return bad != ~0ULL ? neg_var_error(bad_index, bad, var[bad]) : BOSS_OK;
 }
+extern "C" int boss_ngp_predict(boss_gp_t* g, int M, const double* Xs, const double* lam_Xs, const double* amp_Xs,
+                                const double* mean_Xs, double* mu, double* var, long* bad_index) {
+    if (!g || !Xs || !lam_Xs || !amp_Xs || !mu || !var) return fail(BOSS_E_INVALID, "NULL argument");
+    return ngp_predict_call(g, M, Xs, lam_Xs, amp_Xs, nullptr, mean_Xs, mu, var, bad_index);
+}
+extern "C" int boss_ngp_predict_lat(boss_gp_t* g, int M, const double* Xs, const boss_nlat_t* lat, const double* mean_Xs, double* mu,
+                                    double* var, long* bad_index) {
+    if (!g || !Xs || !lat || !mu || !var) return fail(BOSS_E_INVALID, "NULL argument");
+    return ngp_predict_call(g, M, Xs, nullptr, nullptr, lat, mean_Xs, mu, var, bad_index);
+}
 
 // mean_and_var of n NonstationaryGP posteriors at the same M candidates in one call — the posteriors of the S samples of a
 // Bayesian-inference fit (src/posterior.jl:15-19), each with its own latent models: lam_Xs d×M×n, amp_Xs M×n, mean_Xs null or M×n
 // (member after member); mu, var [n][M].  Equally shaped handles (the members of a boss_ngp_fit_batch) take the one-launch set
 // prediction; any other list of nonstationary handles is predicted member by member inside the same call.  The variances are clipped as boss_ngp_predict clips
 // them; the first member with a variance below the threshold fails the call with BOSS_E_NEG_VAR, bad_index_out = the candidate.
-extern "C" int boss_ngp_predict_set(int n, boss_gp_t* const* gps, int M, const double* Xs, const double* lam_Xs, const double* amp_Xs,
-                                    const double* mean_Xs, double* mu, double* var, long* bad_index_out) {
-    if (n < 1 || !gps || !Xs || !lam_Xs || !amp_Xs || !mu || !var) return fail(BOSS_E_INVALID, "NULL argument or n < 1");
+// (lats: n resident latent objects — boss_ngp_predict_set_lat — instead of lam_Xs / amp_Xs)
+static int ngp_predict_set_call(int n, boss_gp_t* const* gps, int M, const double* Xs, const double* lam_Xs, const double* amp_Xs,
+                                boss_nlat_t* const* lats, const double* mean_Xs, double* mu, double* var, long* bad_index_out) {
     if (M < 1) return fail(BOSS_E_INVALID, "M must be >= 1");
     if ((long long)n * M > (1LL << 30)) return fail(BOSS_E_INVALID, "n·M above 2^30 is not supported");
     if (bad_index_out) *bad_index_out = -1;
@@ -785,8 +830,13 @@ extern "C" int boss_ngp_predict_set(int n, boss_gp_t* const* gps, int M, const d
     }
     boss_gp* g0 = gps[0];
     const int d = g0->d, Mp = round_up(M, 64);
-    std::vector<NgpCand> pk(n);
-    for (int i = 0; i < n; ++i) {
+    std::vector<NgpCand> pk(lats ? 1 : n);
+    if (lats) {
+        int rc = nlat_match(n, gps, lats);
+        if (rc) return rc;
+        ngp_pack_x(g0, M, Xs, pk[0]);
+    }
+    for (int i = 0; i < n && !lats; ++i) {
         int rc = ngp_pack(g0, M, Xs, lam_Xs + (size_t)i * d * M, amp_Xs + (size_t)i * M, pk[i]);
         if (rc) return rc;
     }
@@ -798,9 +848,9 @@ extern "C" int boss_ngp_predict_set(int n, boss_gp_t* const* gps, int M, const d
         int rc = gp_settle(gps[i]);
         if (rc) return rc;
     }
-    // candidates | λ(x*) of every member | α(x*) of every member;  outputs mu | var | bad, prior means behind them
+    // candidates | λ(x*) of every member | α(x*) of every member [| the latent kernel's flag];  outputs mu | var | bad, prior means behind them
     const size_t nm = (size_t)n * M;
-    int rc = ws_reserve(c->craw, sizeof(double) * ((size_t)d * Mp + (size_t)n * ((size_t)d * Mp + Mp)));
+    int rc = ws_reserve(c->craw, sizeof(double) * ((size_t)d * Mp + (size_t)n * ((size_t)d * Mp + Mp) + (lats ? 1 : 0)));
     if (rc) return rc;
     rc = ws_reserve(c->pred, sizeof(double) * (3 * nm + 2));
     if (rc) return rc;
@@ -816,9 +866,15 @@ extern "C" int boss_ngp_predict_set(int n, boss_gp_t* const* gps, int M, const d
     double *dmu = dev, *dvar = dev + nm, *dmean = dev + 2 * nm + 1;
     unsigned long long* dbad = (unsigned long long*)(dev + 2 * nm);
     HIPCHK(hipMemcpyAsync(cd.Craw, pk[0].x.data(), sizeof(double) * d * Mp, hipMemcpyHostToDevice, s));
-    for (int i = 0; i < n; ++i) {
+    for (int i = 0; i < n && !lats; ++i) {
         HIPCHK(hipMemcpyAsync(clam + (size_t)i * d * Mp, pk[i].lam.data(), sizeof(double) * d * Mp, hipMemcpyHostToDevice, s));
         HIPCHK(hipMemcpyAsync(camp + (size_t)i * Mp, pk[i].amp.data(), sizeof(double) * Mp, hipMemcpyHostToDevice, s));
+    }
+    if (lats) {
+        unsigned long long* lbad = (unsigned long long*)(camp + (size_t)n * Mp);
+        rc = nlat_enqueue(c, n, lats, cd.Craw, Mp, M, clam, (size_t)d * Mp, camp, (size_t)Mp, nullptr, 0, nullptr, 0, nullptr, lbad);
+        if (rc == BOSS_OK) rc = nlat_check(c, lbad, nullptr);
+        if (rc) return drain(c, rc);
     }
     if (mean_Xs) (void)hipMemcpyAsync(dmean, mean_Xs, sizeof(double) * nm, hipMemcpyHostToDevice, s);
     (void)hipMemsetAsync(dbad, 0xff, sizeof(unsigned long long), s);
@@ -839,6 +895,16 @@ extern "C" int boss_ngp_predict_set(int n, boss_gp_t* const* gps, int M, const d
     rc = finish(c, {{mu, dmu, sizeof(double) * nm}, {var, dvar, sizeof(double) * nm}, {&bad, dbad, sizeof bad}});
     if (rc) return rc;
     return bad != ~0ULL ? neg_var_error(bad_index_out, bad % (unsigned long long)M, var[bad]) : BOSS_OK;
+}
+extern "C" int boss_ngp_predict_set(int n, boss_gp_t* const* gps, int M, const double* Xs, const double* lam_Xs, const double* amp_Xs,
+                                    const double* mean_Xs, double* mu, double* var, long* bad_index_out) {
+    if (n < 1 || !gps || !Xs || !lam_Xs || !amp_Xs || !mu || !var) return fail(BOSS_E_INVALID, "NULL argument or n < 1");
+    return ngp_predict_set_call(n, gps, M, Xs, lam_Xs, amp_Xs, nullptr, mean_Xs, mu, var, bad_index_out);
+}
+extern "C" int boss_ngp_predict_set_lat(int n, boss_gp_t* const* gps, int M, const double* Xs, boss_nlat_t* const* lats,
+                                        const double* mean_Xs, double* mu, double* var, long* bad_index_out) {
+    if (n < 1 || !gps || !Xs || !lats || !mu || !var) return fail(BOSS_E_INVALID, "NULL argument or n < 1");
+    return ngp_predict_set_call(n, gps, M, Xs, nullptr, nullptr, lats, mean_Xs, mu, var, bad_index_out);
 }
 
 // EI parameters: by value in the kernel arguments for P <= EI_MAXP, else in device arrays.
@@ -889,39 +955,11 @@ static int grad_enqueue(boss_gp* g, const boss_cand* cd, const double* mean_s_de
     }
     const size_t glds = sizeof(double) * ((size_t)d * GRAD_CHUNK + GRAD_CHUNK + 8 * 2 * (GRAD_MAX_D + 1) * 32);
     if (glds > 150 * 1024) return fail(BOSS_E_INVALID, "x_dim too large for the gradient kernel's LDS staging");
-    if (!g->LT) {
-        if (dev_malloc((void**)&g->LT, sizeof(double) * (size_t)g->ld * Np) != hipSuccess ||
-            dev_malloc((void**)&g->DT2, sizeof(double) * (size_t)Np * PRED_RB) != hipSuccess ||
-            dev_malloc((void**)&g->avec, sizeof(double) * (size_t)Np * 2) != hipSuccess) {
-            if (g->LT) (void)hipFree(g->LT);
-            if (g->DT2) (void)hipFree(g->DT2);
-            g->LT = g->DT2 = g->avec = nullptr;
-            (void)hipGetLastError();
-            return fail(BOSS_E_ALLOC, "device allocation failed (transposed factor)");
-        }
-        g->have_lt = false;
-    }
-    int rc = predict_enqueue(g, cd, mean_s_dev, mu, var, true, clam_dev, camp_dev);    // V slabs (32 wide) + scaled candidates
+    int rc = lt_alloc(g);                                   // transposed factor, transposed inverses, a (host_latent.inc)
     if (rc) return rc;
-    if (!g->have_lt) {                                      // once per factorisation
-        hipLaunchKernelGGL(transpose_kernel, dim3(Np / 64, Np / 64, 1), dim3(256), 0, s, (const double*)g->A, g->ld, (size_t)0,
-                           g->LT, g->ld, (size_t)0, Np);            // same (non power-of-two) leading dimension as the factor
-        hipLaunchKernelGGL(transpose_kernel, dim3(PRED_RB / 64, PRED_RB / 64, Np / PRED_RB), dim3(256), 0, s,
-                           (const double*)g->Dinv2, PRED_RB, (size_t)PRED_RB * PRED_RB, g->DT2, PRED_RB,
-                           (size_t)PRED_RB * PRED_RB, PRED_RB);
-        // a = L⁻ᵀ z: 256-row steps from the last to the first (GEMV partials live in the second half of avec's buffer)
-        const int nb = Np / PRED_RB;
-        double* partial = g->avec + Np;                      // [<= nb-1][256] fits: (nb-1)*256 < Np
-        for (int ib = nb - 1; ib >= 0; --ib) {
-            const int nch = nb - 1 - ib;
-            if (nch > 0)
-                hipLaunchKernelGGL(bt_gemv_partial_kernel, dim3(nch), dim3(256), 0, s, (const double*)g->LT, g->ld, ib,
-                                   (const double*)g->avec, partial);
-            hipLaunchKernelGGL(bt_finish_kernel, dim3(1), dim3(256), 0, s, (const double*)g->A, g->ld, Np, g->N, ib, nch,
-                               (const double*)partial, (const double*)g->DT2, g->avec);
-        }
-        g->have_lt = true;
-    }
+    rc = predict_enqueue(g, cd, mean_s_dev, mu, var, true, clam_dev, camp_dev);    // V slabs (32 wide) + scaled candidates
+    if (rc) return rc;
+    lt_build(g, s);                                         // once per factorisation
     typedef PredG32 G;
     const int tiles = (M + 31) / 32;
     double* slabs = (double*)c->vscratch.p;
@@ -1035,25 +1073,34 @@ extern "C" int boss_gp_predict_grad(boss_gp_t* g, int M, const double* Xs, const
 //   dlam_Xs d×d×M, dlam_Xs[l + d (m + d j)] = ∂λ_l/∂x_m at candidate j (NULL: constant λ);  damp_Xs d×M (NULL: constant α).
 // The device accumulates Σ_i a_i k_i ∇ln k_i and Σ_i w_i k_i ∇ln k_i in their three parts (explicit, through λ*, through α*:
 // gibbs_grad_accum_kernel), the Jacobians are folded in here (M d² multiply-adds).
-extern "C" int boss_ngp_predict_grad(boss_gp_t* g, int M, const double* Xs, const double* lam_Xs, const double* amp_Xs,
-                                     const double* dlam_Xs, const double* damp_Xs, const double* mean_Xs, const double* mean_grad,
-                                     double* mu, double* var, double* dmu, double* dvar, long* bad_index) {
-    if (!g || !Xs || !lam_Xs || !amp_Xs || !mu || !var || !dmu || !dvar) return fail(BOSS_E_INVALID, "NULL argument");
+// (lat: values and Jacobians come from a resident latent object — boss_ngp_predict_grad_lat —, are folded in by the same host
+// loop and therefore come back with the sums)
+static int ngp_predict_grad_call(boss_gp_t* g, int M, const double* Xs, const double* lam_Xs, const double* amp_Xs,
+                                 const double* dlam_Xs, const double* damp_Xs, const boss_nlat_t* lat, const double* mean_Xs,
+                                 const double* mean_grad, double* mu, double* var, double* dmu, double* dvar, long* bad_index) {
     if (!g->gibbs) return fail(BOSS_E_INVALID, "handle was not created by boss_ngp_create");
     if (M < 1) return fail(BOSS_E_INVALID, "M must be >= 1");
     if (g->d > GIBBS_GRAD_MAX_D) return fail(BOSS_E_INVALID, "x_dim above 16 is not supported by the nonstationary gradient kernel");
     if (bad_index) *bad_index = -1;
     if (!g->fitted) return fail(BOSS_E_NOT_FITTED, "handle has no valid factorisation");
     NgpCand pk;
-    int rc = ngp_pack(g, M, Xs, lam_Xs, amp_Xs, pk);
+    int rc = BOSS_OK;
+    if (lat) {
+        boss_nlat_t* one = const_cast<boss_nlat_t*>(lat);
+        if ((rc = nlat_match(1, &g, &one)) != BOSS_OK) return rc;
+        if ((long long)M * g->d * g->d > NGP_GRAD_SET_MAX_JAC) return fail(BOSS_E_INVALID, "M·x_dim² above 2^27 is not supported");
+        ngp_pack_x(g, M, Xs, pk);
+    } else {
+        rc = ngp_pack(g, M, Xs, lam_Xs, amp_Xs, pk);
+    }
     if (rc) return rc;
     Ctx* c = g->ctx;
     HIPCHK(hipSetDevice(c->device));
     std::lock_guard<std::mutex> lk(c->mtx);
     hipStream_t s = c->stream;
     boss_cand cd;
-    double *clam, *camp;
-    rc = ngp_upload(c, g->d, M, pk, cd, clam, camp);
+    double *clam, *camp, *djl = nullptr, *dja = nullptr;
+    rc = ngp_upload(c, g->d, M, pk, cd, clam, camp, lat, &djl, &dja);
     if (rc) return drain(c, rc);
     const int d = g->d, Mp = pk.Mp, nslot = 2 * (2 * d + 1);
     const size_t nsums = (size_t)nslot * Mp;
@@ -1068,9 +1115,22 @@ extern "C" int boss_ngp_predict_grad(boss_gp_t* g, int M, const double* Xs, cons
     if (rc) return drain(c, rc);
     hipLaunchKernelGGL(clip_var_kernel, dim3((M + 255) / 256), dim3(256), 0, s, dvar_, M, dbad);
     unsigned long long bad = 0;
-    std::vector<double> sums(nsums);
-    rc = finish(c, {{mu, dmu_, sizeof(double) * M}, {var, dvar_, sizeof(double) * M}, {sums.data(), dsums, sizeof(double) * nsums},
-                    {&bad, dbad, sizeof bad}});
+    std::vector<double> sums(nsums), hjl, hja, hamp;
+    if (lat) {
+        const size_t dm = (size_t)d * M;
+        hjl.resize(dm * d);
+        hja.resize(dm);
+        hamp.resize(M);
+        rc = finish(c, {{mu, dmu_, sizeof(double) * M}, {var, dvar_, sizeof(double) * M}, {sums.data(), dsums, sizeof(double) * nsums},
+                        {&bad, dbad, sizeof bad}, {hjl.data(), djl, sizeof(double) * dm * d}, {hja.data(), dja, sizeof(double) * dm},
+                        {hamp.data(), camp, sizeof(double) * M}});
+        dlam_Xs = hjl.data();
+        damp_Xs = hja.data();
+        amp_Xs = hamp.data();
+    } else {
+        rc = finish(c, {{mu, dmu_, sizeof(double) * M}, {var, dvar_, sizeof(double) * M}, {sums.data(), dsums, sizeof(double) * nsums},
+                        {&bad, dbad, sizeof bad}});
+    }
     if (rc) return rc;
     const int ns1 = 2 * d + 1;
     for (int j = 0; j < M; ++j) {
@@ -1094,6 +1154,17 @@ extern "C" int boss_ngp_predict_grad(boss_gp_t* g, int M, const double* Xs, cons
         }
     }
     return bad != ~0ULL ? neg_var_error(bad_index, bad, var[bad]) : BOSS_OK;
+}
+extern "C" int boss_ngp_predict_grad(boss_gp_t* g, int M, const double* Xs, const double* lam_Xs, const double* amp_Xs,
+                                     const double* dlam_Xs, const double* damp_Xs, const double* mean_Xs, const double* mean_grad,
+                                     double* mu, double* var, double* dmu, double* dvar, long* bad_index) {
+    if (!g || !Xs || !lam_Xs || !amp_Xs || !mu || !var || !dmu || !dvar) return fail(BOSS_E_INVALID, "NULL argument");
+    return ngp_predict_grad_call(g, M, Xs, lam_Xs, amp_Xs, dlam_Xs, damp_Xs, nullptr, mean_Xs, mean_grad, mu, var, dmu, dvar, bad_index);
+}
+extern "C" int boss_ngp_predict_grad_lat(boss_gp_t* g, int M, const double* Xs, const boss_nlat_t* lat, const double* mean_Xs,
+                                         const double* mean_grad, double* mu, double* var, double* dmu, double* dvar, long* bad_index) {
+    if (!g || !Xs || !lat || !mu || !var || !dmu || !dvar) return fail(BOSS_E_INVALID, "NULL argument");
+    return ngp_predict_grad_call(g, M, Xs, nullptr, nullptr, nullptr, nullptr, lat, mean_Xs, mean_grad, mu, var, dmu, dvar, bad_index);
 }
 
 // Acquisition value AND gradient w.r.t. the candidates for one hyper-parameter sample (MAP): the EI x feasibility
@@ -1386,8 +1457,6 @@ extern "C" int boss_acq_ei_grad_set(int P, int S, boss_gp_t* const* gps, int M, 
 // list, BOSS_NO_SET_PREDICT=1 and a failed allocation of the set path's scratch go member by member through grad_enqueue's
 // nonstationary branch + gibbs_grad_fold_kernel into the same slices; one copy back.
 // ------------------------------------------------------------------------------------------
-constexpr long long NGP_GRAD_SET_MAX_JAC = 1LL << 27;       // n·M·d² doubles of ∂λ/∂x (1 GiB) per call
-
 static bool ngp_grad_set_ok(int n, boss_gp_t* const* gps, const boss_cand* cd) {
     return predict_set_ok(n, gps, cd, true) && gps[0]->d <= GIBBS_GRAD_MAX_D;
 }
@@ -1403,8 +1472,9 @@ struct NgpEiArgs {
 
 // ei: null (the members' moments and gradients come back: mu / var [n][M], dmu / dvar [n][d×M]) or the acquisition's arguments
 // (acq_out / dacq_out come back)
+// lats: n resident latent objects (the _lat calls) instead of the four host arrays — the latent kernel fills the same buffers
 static int ngp_grad_set_call(int n, boss_gp_t* const* gps, int M, const double* Xs, const double* lam_Xs, const double* amp_Xs,
-                             const double* dlam_Xs, const double* damp_Xs, const double* mean_Xs, const double* mean_grad,
+                             const double* dlam_Xs, const double* damp_Xs, boss_nlat_t* const* lats, const double* mean_Xs, const double* mean_grad,
                              const NgpEiArgs* ei, double* mu, double* var, double* dmu, double* dvar, long* bad_index_out) {
     if (M < 1) return fail(BOSS_E_INVALID, "M must be >= 1");
     if ((long long)n * M > (1LL << 30)) return fail(BOSS_E_INVALID, "n·M above 2^30 is not supported");
@@ -1421,8 +1491,13 @@ static int ngp_grad_set_call(int n, boss_gp_t* const* gps, int M, const double* 
     if ((long long)n * M * d * d > NGP_GRAD_SET_MAX_JAC) return fail(BOSS_E_INVALID, "n·M·x_dim² above 2^27 is not supported");
     for (int i = 0; i < n; ++i)
         if (!gps[i]->fitted && !gps[i]->pending) return fail(BOSS_E_NOT_FITTED, "handle has no valid factorisation");
-    std::vector<NgpCand> pk(n);
-    for (int i = 0; i < n; ++i) {
+    std::vector<NgpCand> pk(lats ? 1 : n);
+    if (lats) {
+        int rc = nlat_match(n, gps, lats);
+        if (rc) return rc;
+        ngp_pack_x(g0, M, Xs, pk[0]);
+    }
+    for (int i = 0; i < n && !lats; ++i) {
         int rc = ngp_pack(g0, M, Xs, lam_Xs + (size_t)i * d * M, amp_Xs + (size_t)i * M, pk[i]);
         if (rc) return rc;
     }
@@ -1436,8 +1511,9 @@ static int ngp_grad_set_call(int n, boss_gp_t* const* gps, int M, const double* 
     }
     const size_t dm = (size_t)d * M, nm = (size_t)n * M, ndm = (size_t)n * dm, nsums = (size_t)2 * (2 * d + 1) * Mp;
     const int P = ei ? ei->P : 0;
-    // candidates | λ(x*) of every member | α(x*) of every member | ∂λ/∂x | ∂α/∂x
-    int rc = ws_reserve(c->craw, sizeof(double) * ((size_t)d * Mp + (size_t)n * ((size_t)d * Mp + Mp) + (dlam_Xs ? ndm * d : 0) + (damp_Xs ? ndm : 0)));
+    const bool has_jl = lats || dlam_Xs, has_ja = lats || damp_Xs;
+    // candidates | λ(x*) of every member | α(x*) of every member | ∂λ/∂x | ∂α/∂x [| the latent kernel's flag]
+    int rc = ws_reserve(c->craw, sizeof(double) * ((size_t)d * Mp + (size_t)n * ((size_t)d * Mp + Mp) + (has_jl ? ndm * d : 0) + (has_ja ? ndm : 0) + (lats ? 1 : 0)));
     if (rc) return rc;
     // acq | dacq | mu | var | dmu | dvar | bad | mean | mean_grad | sums of one member (member-by-member path) | coefs | ymax | mask
     const size_t nacq = ei ? M + dm : 0, nd = nacq + 3 * nm + 3 * ndm + 1 + nsums + 2 * (size_t)P;
@@ -1452,7 +1528,7 @@ static int ngp_grad_set_call(int n, boss_gp_t* const* gps, int M, const double* 
     double* clam = cd.Craw + (size_t)d * Mp;
     double* camp = clam + (size_t)n * d * Mp;
     double* djl = camp + (size_t)n * Mp;
-    double* dja = djl + (dlam_Xs ? ndm * d : 0);
+    double* dja = djl + (has_jl ? ndm * d : 0);
     double* dacq = (double*)c->pred.p;
     double* ddacq = dacq + (ei ? M : 0);
     double* dmu_ = dacq + nacq;
@@ -1472,12 +1548,18 @@ static int ngp_grad_set_call(int n, boss_gp_t* const* gps, int M, const double* 
         if (rc) return drain(c, rc);
     }
     HIPCHK(hipMemcpyAsync(cd.Craw, pk[0].x.data(), sizeof(double) * d * Mp, hipMemcpyHostToDevice, s));
-    for (int i = 0; i < n; ++i) {
+    for (int i = 0; i < n && !lats; ++i) {
         HIPCHK(hipMemcpyAsync(clam + (size_t)i * d * Mp, pk[i].lam.data(), sizeof(double) * d * Mp, hipMemcpyHostToDevice, s));
         HIPCHK(hipMemcpyAsync(camp + (size_t)i * Mp, pk[i].amp.data(), sizeof(double) * Mp, hipMemcpyHostToDevice, s));
     }
     if (dlam_Xs) HIPCHK(hipMemcpyAsync(djl, dlam_Xs, sizeof(double) * ndm * d, hipMemcpyHostToDevice, s));
     if (damp_Xs) HIPCHK(hipMemcpyAsync(dja, damp_Xs, sizeof(double) * ndm, hipMemcpyHostToDevice, s));
+    if (lats) {
+        unsigned long long* lbad = (unsigned long long*)(dja + ndm);
+        rc = nlat_enqueue(c, n, lats, cd.Craw, Mp, M, clam, (size_t)d * Mp, camp, (size_t)Mp, djl, dm * d, dja, dm, nullptr, lbad);
+        if (rc == BOSS_OK) rc = nlat_check(c, lbad, nullptr);
+        if (rc) return drain(c, rc);
+    }
     if (mean_Xs) (void)hipMemcpyAsync(dmean, mean_Xs, sizeof(double) * nm, hipMemcpyHostToDevice, s);
     if (mean_grad) (void)hipMemcpyAsync(dmg, mean_grad, sizeof(double) * ndm, hipMemcpyHostToDevice, s);
     if (ei && ei->valid_mask) (void)hipMemcpyAsync(dmask, ei->valid_mask, M, hipMemcpyHostToDevice, s);
@@ -1487,7 +1569,7 @@ static int ngp_grad_set_call(int n, boss_gp_t* const* gps, int M, const double* 
         bool done = false;
         if (!set_off && ngp_grad_set_ok(n, gps, &cd)) {
             rc = grad_set_enqueue(n, gps, &cd, mean_Xs ? dmean : nullptr, mean_grad ? dmg : nullptr, dmu_, dvar_, dgm, dgv, clam, camp,
-                                  dlam_Xs ? djl : nullptr, damp_Xs ? dja : nullptr);
+                                  has_jl ? djl : nullptr, has_ja ? dja : nullptr);
             if (rc != BOSS_OK && rc != BOSS_E_ALLOC) return drain(c, rc);
             done = rc == BOSS_OK;                            // (no memory for the set launches: the call goes on member by member)
         }
@@ -1498,7 +1580,7 @@ static int ngp_grad_set_call(int n, boss_gp_t* const* gps, int M, const double* 
                               nullptr, nullptr, cl, ca, dsums);
             if (rc) return drain(c, rc);
             hipLaunchKernelGGL(gibbs_grad_fold_kernel, dim3(tiles), dim3(256), 0, s, (const double*)dsums, Mp,
-                               dlam_Xs ? (const double*)djl + (size_t)i * d * dm : nullptr, damp_Xs ? (const double*)dja + (size_t)i * dm : nullptr,
+                               has_jl ? (const double*)djl + (size_t)i * d * dm : nullptr, has_ja ? (const double*)dja + (size_t)i * dm : nullptr,
                                ca, mean_grad ? (const double*)dmg + (size_t)i * dm : nullptr, dgm + (size_t)i * dm, dgv + (size_t)i * dm, d, M);
         }
     }
@@ -1521,7 +1603,13 @@ extern "C" int boss_ngp_predict_grad_set(int n, boss_gp_t* const* gps, int M, co
                                          const double* dlam_Xs, const double* damp_Xs, const double* mean_Xs, const double* mean_grad,
                                          double* mu, double* var, double* dmu, double* dvar, long* bad_index_out) {
     if (n < 1 || !gps || !Xs || !lam_Xs || !amp_Xs || !mu || !var || !dmu || !dvar) return fail(BOSS_E_INVALID, "NULL argument or n < 1");
-    return ngp_grad_set_call(n, gps, M, Xs, lam_Xs, amp_Xs, dlam_Xs, damp_Xs, mean_Xs, mean_grad, nullptr, mu, var, dmu, dvar, bad_index_out);
+    return ngp_grad_set_call(n, gps, M, Xs, lam_Xs, amp_Xs, dlam_Xs, damp_Xs, nullptr, mean_Xs, mean_grad, nullptr, mu, var, dmu, dvar, bad_index_out);
+}
+extern "C" int boss_ngp_predict_grad_set_lat(int n, boss_gp_t* const* gps, int M, const double* Xs, boss_nlat_t* const* lats,
+                                             const double* mean_Xs, const double* mean_grad, double* mu, double* var, double* dmu,
+                                             double* dvar, long* bad_index_out) {
+    if (n < 1 || !gps || !Xs || !lats || !mu || !var || !dmu || !dvar) return fail(BOSS_E_INVALID, "NULL argument or n < 1");
+    return ngp_grad_set_call(n, gps, M, Xs, nullptr, nullptr, nullptr, nullptr, lats, mean_Xs, mean_grad, nullptr, mu, var, dmu, dvar, bad_index_out);
 }
 
 // The acquisition of boss_acq_ei_grad_set for nonstationary posteriors: gps[p + P·s], every member with its own latent values and
@@ -1534,7 +1622,16 @@ extern "C" int boss_ngp_acq_ei_grad_set(int P, int S, boss_gp_t* const* gps, int
     if (P < 1 || S < 1 || !gps || !Xs || !lam_Xs || !amp_Xs || !fit_coefs || !acq_out || !dacq_out) return fail(BOSS_E_INVALID, "bad arguments");
     if ((long long)P * S > (1LL << 30)) return fail(BOSS_E_INVALID, "P·S·M above 2^30 is not supported");
     const NgpEiArgs ei{P, S, fit_coefs, y_max, has_best, best, valid_mask, acq_out, dacq_out};
-    return ngp_grad_set_call(P * S, gps, M, Xs, lam_Xs, amp_Xs, dlam_Xs, damp_Xs, mean_Xs, mean_grad, &ei, nullptr, nullptr, nullptr, nullptr,
+    return ngp_grad_set_call(P * S, gps, M, Xs, lam_Xs, amp_Xs, dlam_Xs, damp_Xs, nullptr, mean_Xs, mean_grad, &ei, nullptr, nullptr, nullptr, nullptr,
+                             nullptr);
+}
+extern "C" int boss_ngp_acq_ei_grad_set_lat(int P, int S, boss_gp_t* const* gps, int M, const double* Xs, boss_nlat_t* const* lats,
+                                            const double* mean_Xs, const double* mean_grad, const double* fit_coefs, const double* y_max,
+                                            int has_best, double best, const unsigned char* valid_mask, double* acq_out, double* dacq_out) {
+    if (P < 1 || S < 1 || !gps || !Xs || !lats || !fit_coefs || !acq_out || !dacq_out) return fail(BOSS_E_INVALID, "bad arguments");
+    if ((long long)P * S > (1LL << 30)) return fail(BOSS_E_INVALID, "P·S·M above 2^30 is not supported");
+    const NgpEiArgs ei{P, S, fit_coefs, y_max, has_best, best, valid_mask, acq_out, dacq_out};
+    return ngp_grad_set_call(P * S, gps, M, Xs, nullptr, nullptr, nullptr, nullptr, lats, mean_Xs, mean_grad, &ei, nullptr, nullptr, nullptr, nullptr,
                              nullptr);
 }
 

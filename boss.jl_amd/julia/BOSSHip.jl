@@ -1071,6 +1071,134 @@ function acq_from_moments(problem::BOSS.BossProblem, xs::AbstractMatrix{Float64}
     return acq, am_idx[] + 1, mx[]
 end
 
+# ---------------------------------------------------------------- resident latent models (boss_nlat_*) and the _lat calls
+"""
+The latent models of ONE output of a NonstationaryGP resident on the device (`boss_nlat_t`): λ_1..λ_d, α and optionally σ, each a
+constant (`Real`) or a pair `(model::BOSS.ParametrizedGP, params::BOSS.ParametrizedGPParams)`.  The device evaluates their values
+and analytic Jacobians at candidates in one launch; a transform is taken when it is one of the closed forms
+`quantile(target, cdf(Normal(), m)) |> act` has for `target_dist` in (nothing, Normal, LogNormal, Uniform) and `act_func` in
+(identity, softplus, exp) — `latent_spec` throws for anything else (no silent fallback: keep such a model on the closure path).
+(Not run here: no Julia toolchain.)
+"""
+mutable struct HipLatents
+    h::Ptr{Cvoid}
+    d::Int
+    has_noise::Bool
+    function HipLatents(h::Ptr{Cvoid}, d::Int, has_noise::Bool)
+        obj = new(h, d, has_noise)
+        finalizer(close, obj)
+    end
+end
+Base.close(o::HipLatents) = (o.h == C_NULL || ccall((:boss_nlat_free, lib), Cvoid, (Ptr{Cvoid},), o.h); o.h = C_NULL; nothing)
+# (target code, p0, p1): z = m | p0 + p1 m | exp(p0 + p1 m) | p0 + (p1 - p0) Φ(m)
+target_spec(::Nothing) = (0, 0.0, 0.0)
+target_spec(t::BOSS.Normal) = (1, Float64(t.μ), Float64(t.σ))
+target_spec(t::BOSS.LogNormal) = (2, Float64(t.μ), Float64(t.σ))
+target_spec(t::BOSS.Uniform) = (3, Float64(t.a), Float64(t.b))
+target_spec(t) = error("HipLatents: target distribution $(typeof(t)) has no closed form on the device")
+# (activation code, parameter): identity | softplus (+ lower bound) | exp
+act_spec(f) = f === identity ? (0, 0.0) : f === BOSS.softplus ? (1, 0.0) : f === exp ? (2, 0.0) :
+    error("HipLatents: activation $f is not one of identity, softplus, exp")
+latent_spec(m::BOSS.ParametrizedGP) = (target_spec(m.target_dist)..., act_spec(m.act_func)...)
+"a fitted plain handle holding the latent GP of `model_posterior(::ParametrizedGP, params, data)` (parametrized_gp.jl:91-106)"
+function latent_handle(m::BOSS.ParametrizedGP, p::BOSS.ParametrizedGPParams, device::Int)
+    X = Matrix{Float64}(p.X); y = Vector{Float64}(p.L * p.yϵ + p.μ); h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:boss_gp_create, lib), Cint, (Cint, Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{UInt8}, Ref{Ptr{Cvoid}}),
+          device, kernel_id(m.kernel), size(X, 1), size(X, 2), X, y, C_NULL, h))
+    hd = Handle(h[])
+    check(ccall((:boss_gp_update, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Cdouble, Cdouble, Ptr{Cdouble}, Cint, Ptr{Cdouble}),
+          hd.h, Vector{Float64}(p.λ), 1.0, Float64(m.noise_std), C_NULL, 0, C_NULL))
+    return hd
+end
+function HipLatents(λs::AbstractVector, α, σ = nothing; discrete::Union{Nothing, AbstractVector{Bool}} = nothing, device::Int = 0)
+    d = length(λs); lats = Any[λs..., α, σ]; nq = d + 2
+    hs = Vector{Any}(nothing, nq); ptrs = fill(C_NULL, nq); cst = fill(NaN, nq)
+    tgt = zeros(Cint, nq); act = zeros(Cint, nq); tpar = zeros(2nq); apar = zeros(nq)
+    for (q, l) in enumerate(lats)
+        if l isa Real
+            cst[q] = Float64(l)
+        elseif l isa Tuple
+            t, p0, p1, a, ap = latent_spec(l[1])
+            hs[q] = latent_handle(l[1], l[2], device); ptrs[q] = hs[q].h
+            tgt[q] = t; tpar[2q - 1] = p0; tpar[2q] = p1; act[q] = a; apar[q] = ap
+        else
+            isnothing(l) && q == nq || error("HipLatents: latent $q is neither a constant nor (ParametrizedGP, ParametrizedGPParams)")
+        end
+    end
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve hs check(ccall((:boss_nlat_create, lib), Cint,
+        (Cint, Cint, Ptr{Ptr{Cvoid}}, Ptr{Cdouble}, Ptr{Cvoid}, Cdouble, Ptr{Cvoid}, Cdouble, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cint},
+         Ptr{Cdouble}, Ptr{UInt8}, Ref{Ptr{Cvoid}}),
+        device, d, ptrs, cst, ptrs[d + 1], cst[d + 1], ptrs[d + 2], cst[d + 2], tgt, tpar, act, apar,
+        isnothing(discrete) ? C_NULL : Vector{UInt8}(discrete), out))
+    foreach(h -> isnothing(h) || close(h), hs)                         # the object holds a snapshot: the latent handles may go
+    return HipLatents(out[], d, !isnothing(σ))
+end
+"(λ d×M, α M, σ M or nothing, ∂λ/∂x d×d×M, ∂α/∂x d×M) of the latent models at the columns of X (`boss_nlat_eval`)"
+function latent_values(L::HipLatents, X::AbstractMatrix{<:Real}; noise::Bool = false)
+    Xs = Matrix{Float64}(X); d, M = size(Xs); bad = Ref{Clong}(-1)
+    λ = Matrix{Float64}(undef, d, M); α = Vector{Float64}(undef, M); σ = noise ? Vector{Float64}(undef, M) : nothing
+    Dλ = Array{Float64}(undef, d, d, M); Dα = Matrix{Float64}(undef, d, M)
+    GC.@preserve L check(ccall((:boss_nlat_eval, lib), Cint,
+        (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Clong}),
+        L.h, M, Xs, λ, α, noise ? σ : C_NULL, Dλ, Dα, bad))
+    return λ, α, σ, Dλ, Dα
+end
+"mean_and_var of a nonstationary posterior with λ(x*), α(x*) read from resident latent models (`boss_ngp_predict_lat`)"
+function mean_and_var(p::HipNonstationaryPosterior, L::HipLatents, X::AbstractMatrix{<:Real})
+    Xs = Matrix{Float64}(X); M = size(Xs, 2)
+    μ = Vector{Float64}(undef, M); σ2 = similar(μ); bad = Ref{Clong}(-1)
+    GC.@preserve p L check(ccall((:boss_ngp_predict_lat, lib), Cint,
+        (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Clong}),
+        p.post.h.h, M, Xs, L.h, mean_vals(p.post.mean, Xs), μ, σ2, bad))
+    return μ, σ2
+end
+"... and with the analytic Jacobians of the latent models instead of ForwardDiff through host closures (`boss_ngp_predict_grad_lat`)"
+function mean_and_var_grad(p::HipNonstationaryPosterior, L::HipLatents, X::AbstractMatrix{<:Real}; mean_grad = C_NULL)
+    Xs = Matrix{Float64}(X); d, M = size(Xs)
+    μ = Vector{Float64}(undef, M); σ2 = similar(μ); dμ = Matrix{Float64}(undef, d, M); dσ2 = similar(dμ); bad = Ref{Clong}(-1)
+    GC.@preserve p L check(ccall((:boss_ngp_predict_grad_lat, lib), Cint,
+        (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Clong}),
+        p.post.h.h, M, Xs, L.h, mean_vals(p.post.mean, Xs), mean_grad, μ, σ2, dμ, dσ2, bad))
+    return μ, σ2, dμ, dσ2
+end
+set_means(ps, Xs) = all(p -> isnothing(p.post.mean), ps) ? C_NULL : reduce(hcat, (Vector{Float64}(mean_vals(p.post.mean, Xs)) for p in ps))
+"mean_and_var of n nonstationary posteriors, member i with the resident latent models Ls[i] (`boss_ngp_predict_set_lat`): (μ, σ²) M×n"
+function mean_and_var(ps::AbstractVector{HipNonstationaryPosterior}, Ls::AbstractVector{HipLatents}, X::AbstractMatrix{<:Real})
+    Xs = Matrix{Float64}(X); M = size(Xs, 2); n = length(ps)
+    μ = Matrix{Float64}(undef, M, n); σ2 = similar(μ); bad = Ref{Clong}(-1)
+    hs = Ptr{Cvoid}[p.post.h.h for p in ps]; ls = Ptr{Cvoid}[L.h for L in Ls]
+    GC.@preserve ps Ls check(ccall((:boss_ngp_predict_set_lat, lib), Cint,
+        (Cint, Ptr{Ptr{Cvoid}}, Cint, Ptr{Cdouble}, Ptr{Ptr{Cvoid}}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Clong}),
+        n, hs, M, Xs, ls, set_means(ps, Xs), μ, σ2, bad))
+    return μ, σ2
+end
+"... with gradients (`boss_ngp_predict_grad_set_lat`): (μ (M×n), σ² (M×n), ∂μ/∂x (d×M×n), ∂σ²/∂x (d×M×n))"
+function mean_and_var_grad(ps::AbstractVector{HipNonstationaryPosterior}, Ls::AbstractVector{HipLatents}, X::AbstractMatrix{<:Real};
+                           mean_grad = C_NULL)
+    Xs = Matrix{Float64}(X); d, M = size(Xs); n = length(ps)
+    μ = Matrix{Float64}(undef, M, n); σ2 = similar(μ); dμ = Array{Float64}(undef, d, M, n); dσ2 = similar(dμ); bad = Ref{Clong}(-1)
+    hs = Ptr{Cvoid}[p.post.h.h for p in ps]; ls = Ptr{Cvoid}[L.h for L in Ls]
+    GC.@preserve ps Ls check(ccall((:boss_ngp_predict_grad_set_lat, lib), Cint,
+        (Cint, Ptr{Ptr{Cvoid}}, Cint, Ptr{Cdouble}, Ptr{Ptr{Cvoid}}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+         Ptr{Cdouble}, Ref{Clong}),
+        n, hs, M, Xs, ls, set_means(ps, Xs), mean_grad, μ, σ2, dμ, dσ2, bad))
+    return μ, σ2, dμ, dσ2
+end
+"`acq_grad_samples` with the latent models of posts[s][p] resident as lats[s][p]: nothing but the candidates goes up (`boss_ngp_acq_ei_grad_set_lat`)"
+function acq_grad_samples(problem::BOSS.BossProblem, xs::AbstractMatrix{Float64}, posts::AbstractVector{<:AbstractVector{HipNonstationaryPosterior}},
+                          lats::AbstractVector{<:AbstractVector{HipLatents}}; mean_grad = C_NULL)
+    d, M = size(xs); S = length(posts); P = length(posts[1]); coefs, ymax, hb, b, mask = ei_arguments(problem, xs)
+    ps = HipNonstationaryPosterior[posts[s][p] for s in 1:S for p in 1:P]                   # member p + P·s
+    Xs = Matrix{Float64}(xs); hs = Ptr{Cvoid}[p.post.h.h for p in ps]; ls = Ptr{Cvoid}[lats[s][p].h for s in 1:S for p in 1:P]
+    acq = Vector{Float64}(undef, M); dacq = Matrix{Float64}(undef, d, M)
+    GC.@preserve posts lats check(ccall((:boss_ngp_acq_ei_grad_set_lat, lib), Cint,
+        (Cint, Cint, Ptr{Ptr{Cvoid}}, Cint, Ptr{Cdouble}, Ptr{Ptr{Cvoid}}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint,
+         Cdouble, Ptr{UInt8}, Ptr{Cdouble}, Ptr{Cdouble}),
+        P, S, hs, M, Xs, ls, set_means(ps, Xs), mean_grad, coefs, ymax, hb, b, mask, acq, dacq))
+    return acq, dacq
+end
+
 # ---------------------------------------------------------------- entry points of include/bosship.h this glue does not call
 # (tests/test_abi_and_host.py checks that every exported symbol is either bound above or listed here with its reason)
 # not bound: boss_set_stream — runs the library on a caller's HIP stream (torch / AMDGPU.jl interop); BOSS.jl itself owns no stream

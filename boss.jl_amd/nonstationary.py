@@ -27,6 +27,78 @@ def _cols(f: Callable, X: np.ndarray) -> np.ndarray:
 
 
 # ---------------------------------------------------------------------------------------------
+# Activation functions the device knows in closed form (BOSS_ACT_*): ordinary array functions that also carry their code, so that
+# a ParametrizedGP using them can be evaluated by the resident latent kernel (HipParametrizedGP.device_spec).
+# ---------------------------------------------------------------------------------------------
+class LatentActivation:
+    def __init__(self, name: str, par: float = 0.0):
+        self.name, self.par = name, float(par)
+
+    def __call__(self, z):
+        z = np.asarray(z, float)
+        if self.name == "softplus":                         # softplus / ScaledSoftplus (src/utils/bijectors.jl:116-158), overflow-safe
+            return np.maximum(z, 0.0) + np.log1p(np.exp(-np.abs(z))) + self.par
+        if self.name == "exp":
+            return np.exp(z)
+        return z
+
+    def with_lower_bound(self, lb: float) -> "LatentActivation":
+        """ScaledSoftplus(lb): softplus(z) + lb."""
+        if self.name != "softplus":
+            raise ValueError("only softplus takes a lower bound")
+        return LatentActivation("softplus", lb)
+
+    def __repr__(self):
+        return f"LatentActivation({self.name!r}, {self.par})"
+
+
+identity_act = LatentActivation("identity")
+softplus = LatentActivation("softplus")
+exp_act = LatentActivation("exp")
+
+
+def latent_transform(spec, m):
+    """The closed forms the device evaluates for spec = (target, (p0, p1), activation, par) (HipParametrizedGP.device_spec) at the
+    latent posterior means m: returns (value, d value / d m) — quantile(target, cdf(Normal(), m)) |> act and its derivative."""
+    from scipy.special import ndtr
+    target, (p0, p1), act, par = spec
+    m = np.asarray(m, float)
+    if target == "normal":
+        z, dz = p0 + p1 * m, np.full_like(m, p1)
+    elif target == "lognormal":
+        z = np.exp(p0 + p1 * m)
+        dz = p1 * z
+    elif target == "uniform":
+        z, dz = p0 + (p1 - p0) * ndtr(m), (p1 - p0) * np.exp(-0.5 * m * m) / math.sqrt(2.0 * math.pi)
+    elif target == "none":
+        z, dz = m, np.ones_like(m)
+    else:
+        raise ValueError(f"unknown target {target!r}")
+    if act == "softplus":
+        e = np.exp(-np.abs(z))
+        return np.maximum(z, 0.0) + np.log1p(e) + par, dz * np.where(z >= 0, 1.0 / (1.0 + e), e / (1.0 + e))
+    if act == "exp":
+        v = np.exp(z)
+        return v, dz * v
+    if act == "identity":
+        return z, dz
+    raise ValueError(f"unknown activation {act!r}")
+
+
+def constant_latent(value: float) -> Callable:
+    """A latent model that is a constant (`_param_posterior_slice` of a non-GP parameter, nonstationary_gp.jl:198-212): a vectorized
+    closure that also says so (`.constant`), which lets the resident latent kernel take it."""
+    value = float(value)
+
+    def post(x):
+        x = np.asarray(x, float)
+        return value if x.ndim == 1 else np.full(x.shape[1], value)
+    post.vectorized = True
+    post.constant = value
+    return post
+
+
+# ---------------------------------------------------------------------------------------------
 # ParametrizedGP (src/models/nonstationary_gp/parametrized_gp.jl): the latent model of one hyper-parameter
 # of the NonstationaryGP — a zero-mean, unit-amplitude GP over the data points whose (whitened) outputs are the
 # parameters; its posterior mean, pushed through Normal-cdf -> target quantile -> activation, is the value of
@@ -50,7 +122,7 @@ class HipParametrizedGP:
     lengthscale: Sequence[float]
     kernel: str = "matern32"
     target_dist: object = None
-    act_func: Callable = staticmethod(lambda z: z)
+    act_func: Callable = identity_act
     noise_std: float = 0.0
     device: int = 0
 
@@ -61,6 +133,35 @@ class HipParametrizedGP:
             from scipy.special import ndtr
             y = self.target_dist.ppf(ndtr(y))
         return self.act_func(y)
+
+    def device_spec(self):
+        """(target, (p0, p1), activation, par) — the names of api.LATENT_TARGETS / api.LATENT_ACTS — when transform() is one of the
+        closed forms the device evaluates (include/bosship.h, boss_nlat_create), else None.  Recognised: target_dist None, frozen
+        scipy.stats norm, lognorm with loc 0 and uniform; activations identity_act, softplus (optionally with a lower bound), exp_act.
+            Normal(μ, σ): z = μ + σ m;  LogNormal(μ, σ) = lognorm(s=σ, scale=e^μ): z = exp(μ + σ m);  Uniform(a, b): z = a + (b − a) Φ(m)
+        — what quantile(target, cdf(Normal(), m)) equals."""
+        act = self.act_func
+        if not isinstance(act, LatentActivation):
+            return None
+        t = self.target_dist
+        if t is None:
+            return ("none", (0.0, 0.0), act.name, act.par)
+        dist = getattr(t, "dist", None)
+        name = getattr(dist, "name", None)
+        if name not in ("norm", "lognorm", "uniform"):
+            return None
+        try:
+            shapes, loc, scale = dist._parse_args(*t.args, **t.kwds)
+            loc, scale = float(loc), float(scale)
+        except Exception:
+            return None
+        if name == "norm":
+            return ("normal", (loc, scale), act.name, act.par)
+        if name == "uniform":
+            return ("uniform", (loc, loc + scale), act.name, act.par)
+        if loc != 0.0 or not scale > 0.0:
+            return None
+        return ("lognormal", (math.log(scale), float(shapes[0])), act.name, act.par)
 
     def params_sampler(self, data: ExperimentData):
         """_params_sampler (:191-215): L = chol of the prior covariance at the data points (finite_param_gp, :136-158),
@@ -85,7 +186,8 @@ class HipParametrizedGP:
 
     def model_posterior(self, params: HipParametrizedGPParams, data: ExperimentData = None):
         """model_posterior (:90-106): x -> act(ft(mean of the GP posterior conditioned on y = L yϵ + μ)).  The returned
-        closure takes one point or a d×M matrix (one device call); `.close()` releases the handle."""
+        closure takes one point or a d×M matrix (one device call); `.close()` releases the handle; `.gp` is its api.GP handle and
+        `.model` this model (what a resident latent object is built from)."""
         y = params.L @ params.yeps + params.mu
         g = api.GP(params.X, y, self.kernel, None, self.device)
         g.update(params.lengthscale, 1.0, self.noise_std)
@@ -97,6 +199,8 @@ class HipParametrizedGP:
             return float(z[0]) if x.ndim == 1 else z
         post.vectorized = True
         post.close = g.close
+        post.gp = g
+        post.model = self
         return post
 
     def model_posterior_lookup(self, params: HipParametrizedGPParams, data: ExperimentData = None):
@@ -121,7 +225,22 @@ def stack_latents(posts: Sequence[Callable]) -> Callable:
         cols = [np.asarray(p(x), float) for p in posts]
         return np.array(cols) if x.ndim == 1 else np.stack(cols, axis=1)
     f.vectorized = all(getattr(p, "vectorized", False) for p in posts)
+    f.posts = list(posts)
     return f
+
+
+def _latent_arg(post, name: str):
+    """What api.NgpLatents takes for one latent closure: a float, or (handle, spec).  ValueError naming the latent otherwise."""
+    if hasattr(post, "constant"):
+        return float(post.constant)
+    model, gp = getattr(post, "model", None), getattr(post, "gp", None)
+    if isinstance(model, HipParametrizedGP) and gp is not None:
+        spec = model.device_spec()
+        if spec is not None:
+            return (gp, spec)
+        raise ValueError(f"resident_latents: the transform of latent {name} (target_dist {model.target_dist!r}, act_func "
+                         f"{model.act_func!r}) is not one the device evaluates")
+    raise ValueError(f"resident_latents: latent {name} is neither a constant (constant_latent) nor a HipParametrizedGP posterior")
 
 
 @dataclass
@@ -133,6 +252,7 @@ class HipNonstationaryPosteriorSlice:
     mean_fn: Optional[Callable]
     discrete: Optional[np.ndarray]
     f_noise: Optional[Callable] = None                          # σ(·): needed by append only
+    latents: Optional[api.NgpLatents] = None                    # the latent models resident on the device (resident_latents)
 
     def append(self, x, y) -> float:
         """augment_dataset! (src/types/problem.jl:191-198) on the fitted slice: the latent models are evaluated at the new points, the
@@ -142,6 +262,11 @@ class HipNonstationaryPosteriorSlice:
         X = np.asarray(x, float).reshape(self.gp.d, -1)
         Xr = self._round(X)
         ms = None if self.mean_fn is None else np.array([float(self.mean_fn(X[:, j])) for j in range(X.shape[1])])
+        if self.latents is not None:                            # (the kernel rounds for λ and α, σ sees the point as given)
+            lam, amp, noi, _, _ = self.latents.eval(X, jac=False, noise=self.latents.has_noise)
+            if noi is None:
+                noi = _cols(self.f_noise, X).reshape(-1)
+            return self.gp.append(X, np.asarray(y, float).reshape(-1), lam, amp, noi, ms)
         return self.gp.append(X, np.asarray(y, float).reshape(-1), _cols(self.f_lam, Xr).T, _cols(self.f_amp, Xr).reshape(-1),
                               _cols(self.f_noise, X).reshape(-1), ms)
 
@@ -164,6 +289,9 @@ class HipNonstationaryPosteriorSlice:
         X = x[:, None] if vec else x
         Xr = self._round(X)
         ms = None if self.mean_fn is None else np.array([float(self.mean_fn(X[:, j])) for j in range(X.shape[1])])
+        if self.latents is not None:
+            mu, var = self.gp.predict_lat(X, self.latents, ms)
+            return (float(mu[0]), float(var[0])) if vec else (mu, var)
         mu, var = self.gp.predict(X, _cols(self.f_lam, Xr).T, _cols(self.f_amp, Xr).reshape(-1), ms)
         return (float(mu[0]), float(var[0])) if vec else (mu, var)
 
@@ -172,11 +300,16 @@ class HipNonstationaryPosteriorSlice:
         """mean_and_var and its gradient w.r.t. the candidate columns (boss_ngp_predict_grad) — what ForwardDiff pushes through the
         posterior inside OptimizationAM (src/acquisition_maximizers/optimization.jl:36).  The candidate also enters through the latent
         λ(x*), α(x*): `lam_jac(x) -> d×d` ([l, m] = ∂λ_l/∂x_m) and `amp_jac(x) -> d` supply their Jacobians; without them central
-        differences of the host closures are taken (step fd_step).  Returns (mu[M], var[M], dmu[d, M], dvar[d, M])."""
+        differences of the host closures are taken (step fd_step).  With resident latents the values and analytic Jacobians are
+        evaluated on the device (boss_ngp_predict_grad_lat); lam_jac / amp_jac / fd_step are not used.
+        Returns (mu[M], var[M], dmu[d, M], dvar[d, M])."""
         X = np.asarray(X, float)
         if X.ndim == 1:
             X = X[:, None]
         d, M = X.shape
+        if self.latents is not None:
+            ms = None if self.mean_fn is None else np.array([float(self.mean_fn(X[:, j])) for j in range(M)])
+            return self.gp.predict_grad_lat(X, self.latents, ms, mean_grad)
         Xr = self._round(X)
 
         def jac(f, x, n_out):
@@ -202,6 +335,9 @@ class HipNonstationaryPosteriorSlice:
             X = X[:, None]
         Xr = self._round(X)
         ms = None if self.mean_fn is None else np.array([float(self.mean_fn(X[:, j])) for j in range(X.shape[1])])
+        if self.latents is not None:
+            lam, amp, _, _, _ = self.latents.eval(X, jac=False)
+            return self.gp.predict_cov(X, lam, amp, ms)
         return self.gp.predict_cov(X, _cols(self.f_lam, Xr).T, _cols(self.f_amp, Xr).reshape(-1), ms)
 
     def cov(self, X):
@@ -217,6 +353,8 @@ class HipNonstationaryPosteriorSlice:
         return np.sqrt(self.var(x))
 
     def close(self):
+        if self.latents is not None:
+            self.latents.close()
         self.gp.close()
 
 
@@ -230,6 +368,33 @@ class HipNonstationaryGP:
     mean: Optional[Sequence[Optional[Callable]]] = None
     discrete: Optional[Sequence[bool]] = None
     device: int = 0
+    # keep every output's latent models resident on the device (api.NgpLatents): the slices evaluate λ(x*), α(x*) and their
+    # analytic Jacobians there instead of through the host closures.  Needs f_lam[i] = stack_latents(...) of constants
+    # (constant_latent) and HipParametrizedGP posteriors whose transform device_spec() describes, f_amp[i] one of them; ValueError else.
+    resident_latents: bool = False
+
+    def __post_init__(self):
+        if self.resident_latents:
+            for i in range(len(self.f_lam)):
+                self._latent_args(i)
+
+    def _latent_args(self, i):
+        posts = getattr(self.f_lam[i], "posts", None)
+        if posts is None:
+            raise ValueError(f"resident_latents: f_lam[{i}] must be built by stack_latents from its per-dimension latent models")
+        lam = [_latent_arg(p, f"f_lam[{i}][{l}]") for l, p in enumerate(posts)]
+        amp = _latent_arg(self.f_amp[i], f"f_amp[{i}]")
+        try:                                                    # σ(·) is optional on the device: append falls back to its closure
+            noise = _latent_arg(self.f_noise[i], f"f_noise[{i}]")
+        except ValueError:
+            noise = None
+        return lam, amp, noise
+
+    def _slice_latents(self, i) -> Optional[api.NgpLatents]:
+        if not self.resident_latents:
+            return None
+        lam, amp, noise = self._latent_args(i)
+        return api.NgpLatents(lam, amp, noise, self.discrete, self.device)
 
     def _latent_at_data(self, X, i):
         disc = None if self.discrete is None else np.asarray(self.discrete, bool)
@@ -244,10 +409,12 @@ class HipNonstationaryGP:
         g = api.GibbsGP(data.X, data.Y[i], disc, self.device)
         try:
             g.update(lam, amp, noi, m)
+            lat = self._slice_latents(i)
         except Exception:
             g.close()
             raise
-        return HipNonstationaryPosteriorSlice(g, self.f_lam[i], self.f_amp[i], None if self.mean is None else self.mean[i], disc, self.f_noise[i])
+        return HipNonstationaryPosteriorSlice(g, self.f_lam[i], self.f_amp[i], None if self.mean is None else self.mean[i], disc, self.f_noise[i],
+                                              lat)
 
     def model_posterior(self, data: ExperimentData) -> List[HipNonstationaryPosteriorSlice]:
         return [self.model_posterior_slice(data, i) for i in range(data.Y.shape[0])]
@@ -378,8 +545,23 @@ def nonstationary_model_posterior_batch(models: Sequence[HipNonstationaryGP], da
             if st[s] == api.BOSS_E_NOT_PD:
                 raise api.PosDefException(api.BOSS_E_NOT_PD, f"sample {s}, output {i}: the matrix is not positive definite")
             raise api.BossError(int(st[s]), f"sample {s}, output {i}: invalid latent values")
-    return [[HipNonstationaryPosteriorSlice(rows[i][s], m.f_lam[i], m.f_amp[i], None if m.mean is None else m.mean[i], disc0, m.f_noise[i])
-             for i in range(len(rows))] for s, m in enumerate(models)]
+    lats = []
+    try:
+        for m in models:
+            for i in range(len(rows)):
+                lats.append(m._slice_latents(i))
+    except Exception:                                       # e.g. a latent handle closed since its model was built: nothing is left behind
+        for lat in lats:
+            if lat is not None:
+                lat.close()
+        for r in rows:
+            for g in r:
+                g.close()
+        raise
+    P = len(rows)
+    return [[HipNonstationaryPosteriorSlice(rows[i][s], m.f_lam[i], m.f_amp[i], None if m.mean is None else m.mean[i], disc0, m.f_noise[i],
+                                            lats[i + P * s])
+             for i in range(P)] for s, m in enumerate(models)]
 
 
 def nonstationary_acq_ei_batch(posts: Sequence[Sequence[HipNonstationaryPosteriorSlice]], Xs, fit_coefs, y_max=None, best=None,
@@ -395,8 +577,14 @@ def nonstationary_acq_ei_batch(posts: Sequence[Sequence[HipNonstationaryPosterio
     d, M = Xs.shape
     mu = np.empty((S, P, M))
     var = np.empty((S, P, M))
+    resident = all(p.latents is not None for row in posts for p in row)      # latent values read on the device (the _lat set call)
     for i in range(P):
         sl = [posts[s][i] for s in range(S)]
+        if resident:
+            means = [None if p.mean_fn is None else np.array([float(p.mean_fn(Xs[:, j])) for j in range(M)]) for p in sl]
+            ms = None if all(m is None for m in means) else np.stack([np.zeros(M) if m is None else m for m in means])
+            mu[:, i, :], var[:, i, :] = api.ngp_predict_set_lat([p.gp for p in sl], Xs, [p.latents for p in sl], ms)
+            continue
         Xr = sl[0]._round(Xs)
         lam = np.empty((d, M, S), order="F")
         amp = np.empty((M, S), order="F")
@@ -426,6 +614,13 @@ def nonstationary_acq_ei_grad_batch(posts: Sequence[Sequence[HipNonstationaryPos
         raise ValueError("posts must be S rows of P slices")
     d, M = Xs.shape
     n = S * P
+    if all(p.latents is not None for row in posts for p in row):
+        # resident latent models: values and analytic Jacobians are evaluated on the device (lam_jac / amp_jac / fd_step are not used)
+        means = [None if p.mean_fn is None else np.array([float(p.mean_fn(Xs[:, j])) for j in range(M)]) for row in posts for p in row]
+        ms = None if all(m is None for m in means) else np.stack([np.zeros(M) if m is None else m for m in means])
+        mg = None if mean_grad is None else np.asarray(mean_grad, float).reshape(n, d, M)
+        return api.ngp_acq_ei_grad_set_lat([[p.gp for p in row] for row in posts], Xs, [[p.latents for p in row] for row in posts],
+                                           fit_coefs, y_max, best, valid_mask, ms, mg)
     Xr = posts[0][0]._round(Xs)
     lam = np.empty((d, M, n), order="F")
     amp = np.empty((M, n), order="F")

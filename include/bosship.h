@@ -487,6 +487,69 @@ int boss_ngp_acq_ei_grad_set(int P, int S, boss_gp_t* const* gps, int M, const d
                              const double* mean_grad, const double* fit_coefs, const double* y_max, int has_best, double best,
                              const unsigned char* valid_mask, double* acq_out, double* dacq_out);
 
+/* ---- resident latent models of a NonstationaryGP -------------------------------------------------
+ * In the reference lam(x), alpha(x), sigma(x) of a NonstationaryGP are posteriors of latent ParametrizedGPs
+ * (src/models/nonstationary_gp/nonstationary_gp.jl:200-214): a GP posterior mean m(x) pushed through Normal-cdf -> target quantile
+ * -> activation (parametrized_gp.jl:91-134).  A boss_nlat_t holds the latent models of ONE output on the device and evaluates their
+ * values and analytic Jacobians at candidates in one launch (latent_kernels.hpp): m = sum_i a_i k(x_i, x*), grad m = sum_i a_i grad
+ * k(x_i, x*), then the transform and its chain rule in closed form.
+ *   latent order q = 0..d-1 lengthscales, d amplitude, d+1 noise;
+ *   a latent is a fitted plain handle (boss_gp_create + boss_gp_update, no prior mean, same device and d; other kinds
+ *   BOSS_E_INVALID, unfitted BOSS_E_NOT_FITTED) or NULL = the constant given beside it (finite, taken as it is: no transform);
+ *   noise is optional: noise_gp NULL and noise_const NaN = no noise model;
+ *   target[q], target_par[2q], target_par[2q+1]: z = m | p0 + p1 m | exp(p0 + p1 m) | p0 + (p1 - p0) Phi(m);
+ *   act[q], act_par[q]: z | log1p(exp z) + par (overflow-safe, derivative = sigmoid) | exp z;
+ *   discrete: d flags or NULL — the nonstationary kernel's: candidates are rounded half-to-even in flagged dimensions before the
+ *   lengthscale and amplitude latents see them and the Jacobian columns of those dimensions are zero; the noise latent sees the point
+ *   as given (finite_nongp, nonstationary_gp.jl:192).
+ * boss_nlat_create snapshots a = (K + sigma^2 I)^-1 y, the scaled training points, kernel, 1/lambda and amplitude of every latent
+ * handle: afterwards the handles may be updated or freed.  Latents may have different N.  d <= 16.
+ * Side effect on the latent handles: create forms a on each of them the way boss_gp_predict_grad does, i.e. it allocates that
+ * handle's gradient workspace (the transposed factor, the inverted diagonal blocks and a: about N² doubles per latent handle) and makes
+ * the handle's later boss_gp_update calls build the block inverses eagerly.  Nothing of it is shared with the object; a caller who
+ * keeps the handles pays that memory and work until it frees them.
+ * boss_nlat_eval: lam_out d×M, amp_out M, noise_out M or NULL, dlam_out d×d×M or NULL, damp_out d×M or NULL in the layouts
+ * boss_ngp_predict_grad takes (dlam[l + d*(m + d*j)] = d lam_l / d x_m at candidate j).  A lengthscale that is not finite and > 0,
+ * an amplitude or noise that is not finite and >= 0 fails the call with BOSS_E_INVALID, *bad_index = the first such candidate
+ * (found by a flag the kernel sets).  No floating-point atomics: repeated calls agree bit for bit. */
+#define BOSS_LT_NONE      0
+#define BOSS_LT_NORMAL    1
+#define BOSS_LT_LOGNORMAL 2
+#define BOSS_LT_UNIFORM   3
+#define BOSS_ACT_IDENTITY 0
+#define BOSS_ACT_SOFTPLUS 1
+#define BOSS_ACT_EXP      2
+typedef struct boss_nlat boss_nlat_t;
+int boss_nlat_create(int device, int d, boss_gp_t* const* lam_gps, const double* lam_const, boss_gp_t* amp_gp, double amp_const,
+                     boss_gp_t* noise_gp, double noise_const, const int* target, const double* target_par, const int* act,
+                     const double* act_par, const unsigned char* discrete, boss_nlat_t** out);
+void boss_nlat_free(boss_nlat_t* lat);
+int boss_nlat_eval(const boss_nlat_t* lat, int M, const double* Xs, double* lam_out, double* amp_out, double* noise_out,
+                   double* dlam_out, double* damp_out, long* bad_index);
+
+/* The nonstationary prediction calls with the latent values read from a boss_nlat_t on the device instead of host arrays: each
+ * takes the latent object(s) where its array twin takes lam_Xs, amp_Xs[, dlam_Xs, damp_Xs] and is otherwise identical in arguments,
+ * limits, error behaviour and outputs.  The latent kernel writes the very device buffers the array form uploads into, so a _lat
+ * call returns bit for bit what its twin returns when fed the arrays boss_nlat_eval produces for the same candidates.  Set calls:
+ * n = P*S handles and n latent objects, member i = p + P*s; the same shape test decides set path against member-by-member and
+ * BOSS_NO_SET_PREDICT=1 has the same meaning.  A latent object whose discrete flags, device or d differ from the handle's, or an
+ * invalid latent value at a candidate: BOSS_E_INVALID.  After an error nothing stays enqueued and every handle stays usable.
+ * One limit is the _lat form's own: boss_ngp_predict_grad_lat refuses M·d² > 2^27 (BOSS_E_INVALID), the size of the device Jacobian
+ * buffer the latent kernel fills, as the set calls of both forms do; boss_ngp_predict_grad, which reads its Jacobians from host
+ * memory, has no such limit. */
+int boss_ngp_predict_lat(boss_gp_t* gp, int M, const double* Xs, const boss_nlat_t* lat, const double* mean_Xs, double* mu,
+                         double* var, long* bad_index);
+int boss_ngp_predict_grad_lat(boss_gp_t* gp, int M, const double* Xs, const boss_nlat_t* lat, const double* mean_Xs,
+                              const double* mean_grad, double* mu, double* var, double* dmu, double* dvar, long* bad_index);
+int boss_ngp_predict_set_lat(int n, boss_gp_t* const* gps, int M, const double* Xs, boss_nlat_t* const* lats, const double* mean_Xs,
+                             double* mu, double* var, long* bad_index_out);
+int boss_ngp_predict_grad_set_lat(int n, boss_gp_t* const* gps, int M, const double* Xs, boss_nlat_t* const* lats,
+                                  const double* mean_Xs, const double* mean_grad, double* mu, double* var, double* dmu, double* dvar,
+                                  long* bad_index_out);
+int boss_ngp_acq_ei_grad_set_lat(int P, int S, boss_gp_t* const* gps, int M, const double* Xs, boss_nlat_t* const* lats,
+                                 const double* mean_Xs, const double* mean_grad, const double* fit_coefs, const double* y_max,
+                                 int has_best, double best, const unsigned char* valid_mask, double* acq_out, double* dacq_out);
+
 /* ---- tracked candidates -----------------------------------------------------------------------
  * SequentialBatchAM (src/acquisition_maximizers/batch.jl:26-38) re-evaluates the acquisition on
  * the whole candidate set after every speculative observation; with a FIXED candidate set (GridAM
