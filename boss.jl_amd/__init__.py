@@ -21,6 +21,6 @@ from .nonstationary import (LatentActivation, constant_latent, exp_act, identity
 from .nonstationary import data_loglike_batch as nonstationary_data_loglike_batch  # noqa: F401,E402
 from .nonstationary import data_loglike_grad_batch as nonstationary_data_loglike_grad_batch  # noqa: F401,E402
 from .nonstationary import (nonstationary_acq_ei_batch, nonstationary_acq_ei_grad_batch,  # noqa: F401,E402
-                            nonstationary_model_posterior_batch)
+                            nonstationary_model_posterior_batch, nonstationary_sequential_batch)
 from .fitter import HipBatchedMAP, HipGradientMAP, HipSampleOptMAP, MAPParams  # noqa: F401,E402
 from .maximizer import HipBatchAM, HipGradientAM, HipSequentialBatchAM  # noqa: F401,E402

@@ -41,6 +41,7 @@ SIGNATURES = {
     "boss_ggp_update": (C.c_int, [C.c_void_p, _c_dp, C.c_double, C.c_double, C.c_double, C.c_int, _c_dp]),
     "boss_ngp_loglike_grad": (C.c_int, [C.c_void_p, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
     "boss_ngp_append": (C.c_int, [C.c_void_p, C.c_int, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
+    "boss_ngp_reserve": (C.c_int, [C.c_void_p, C.c_int]),
     "boss_ggp_loglike_grad": (C.c_int, [C.c_void_p, _c_dp, _c_dp]),
     "boss_ggp_append": (C.c_int, [C.c_void_p, C.c_int, _c_dp, _c_dp, _c_dp, _c_dp]),
     "boss_gp_fit": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _c_dp, _c_dp, _c_dp, _c_dp, C.c_double, C.c_double,
@@ -113,6 +114,8 @@ SIGNATURES = {
     "boss_ngp_acq_ei_grad_set_lat": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_int, _c_dp, C.POINTER(C.c_void_p), _c_dp,
                                                _c_dp, _c_dp, _c_dp, C.c_int, C.c_double, _c_ucp, _c_dp, _c_dp]),
     "boss_track_create": (C.c_int, [C.c_void_p, C.c_void_p, _c_dp, C.POINTER(C.c_void_p)]),
+    "boss_ngp_track_create": (C.c_int, [C.c_void_p, C.c_void_p, _c_dp, _c_dp, _c_dp, C.POINTER(C.c_void_p)]),
+    "boss_ngp_track_create_lat": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _c_dp, C.POINTER(C.c_void_p)]),
     "boss_track_free": (None, [C.c_void_p]),
     "boss_track_sync": (C.c_int, [C.c_void_p]),
     "boss_track_moments": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _c_dp, _c_dp]),
@@ -537,9 +540,15 @@ class GibbsGP(GP):
         _check(load_library().boss_ngp_loglike_grad(self._h, C.byref(out), _dp(dlam), _dp(damp), _dp(dnoi), _dp(dmean)))
         return out.value, dlam, damp, dnoi, dmean
 
+    def reserve(self, N_total: int):
+        """Reserve storage for N_total observations (boss_ngp_reserve); the handle must be (re-)updated afterwards, with latent
+        arrays of N columns as before."""
+        _check(load_library().boss_ngp_reserve(self._h, int(N_total)))
+
     def append(self, X_new, y_new, lam_new, amp_new, noise_new, mean_new=None) -> float:
         """augment_dataset! + the posterior with the latent models evaluated at the new points (lam_new d×m, amp_new m, noise_new m):
-        rebuilt and factorised (boss_ngp_append).  Returns the logpdf of all N + m points."""
+        the block rows of the factor that hold the new points are rebuilt on the device (boss_ngp_append).  Returns the logpdf of
+        all N + m points."""
         X_new = _f64(np.asarray(X_new, dtype=np.float64).reshape(self.d, -1), 2)
         m = X_new.shape[1]
         y_new = _f64(np.asarray(y_new).reshape(-1), 1)
@@ -550,8 +559,11 @@ class GibbsGP(GP):
         if y_new.shape[0] != m or lam.shape != (self.d, m) or amp.shape[0] != m or noi.shape[0] != m or (mn is not None and mn.shape[0] != m):
             raise ValueError("one entry (column) per new point in y_new, lam_new, amp_new, noise_new, mean_new")
         out = C.c_double(0.0)
-        _check(load_library().boss_ngp_append(self._h, m, _dp(X_new), _dp(y_new), _dp(lam), _dp(amp), _dp(noi), _dp(mn), C.byref(out)))
-        self.N += m
+        rc = load_library().boss_ngp_append(self._h, m, _dp(X_new), _dp(y_new), _dp(lam), _dp(amp), _dp(noi), _dp(mn), C.byref(out))
+        cnt = C.c_int(self.N)                # the device's own count: the observations stay appended when the factorisation fails
+        load_library().boss_gp_n(self._h, C.byref(cnt))
+        self.N = cnt.value
+        _check(rc)
         self.logpdf = out.value
         return out.value
 
@@ -1275,6 +1287,37 @@ class Track:
             pass
 
 
+class GibbsTrack(Track):
+    """Track of a nonstationary posterior (boss_ngp_track_create[_lat]): extended in O(N·M) after GibbsGP.append.  Exactly one of
+    the arrays (lam_Xs d×M and amp_Xs M: λ(x*), α(x*) at the candidates, rounded where dims are discrete) and `latents` (an
+    NgpLatents, evaluated on the device) is given.  Has Track's methods and goes to acq_ei_tracks like one."""
+
+    def __init__(self, gp: "GibbsGP", cand: Candidates, lam_Xs=None, amp_Xs=None, mean_Xs=None, latents: Optional[NgpLatents] = None):
+        arrays = lam_Xs is not None or amp_Xs is not None
+        if arrays == (latents is not None):
+            raise ValueError("give either lam_Xs and amp_Xs or latents")
+        if arrays and (lam_Xs is None or amp_Xs is None):
+            raise ValueError("lam_Xs and amp_Xs go together")
+        d, M = cand.d, cand.M
+        ms = None if mean_Xs is None else _f64(np.asarray(mean_Xs).reshape(-1), 1)
+        if ms is not None and ms.shape[0] != M:
+            raise ValueError("mean_Xs must have one entry per candidate")
+        h = C.c_void_p()
+        if arrays:
+            lam = _f64(lam_Xs)
+            amp = _f64(np.asarray(amp_Xs).reshape(-1), 1)
+            if lam.shape != (d, M) or amp.shape[0] != M:
+                raise ValueError("lam_Xs must be d×M and amp_Xs length M")
+            _check(load_library().boss_ngp_track_create(gp._h, cand._h, _dp(lam), _dp(amp), _dp(ms), C.byref(h)))
+        else:
+            if not isinstance(latents, NgpLatents):
+                raise ValueError("latents must be an NgpLatents")
+            if latents._h is None:
+                raise BossError(BOSS_E_INVALID, "latents must be an open NgpLatents")
+            _check(load_library().boss_ngp_track_create_lat(gp._h, cand._h, latents._h, _dp(ms), C.byref(h)))
+        self._h, self.gp, self.cand, self.M = h, gp, cand, M
+
+
 def acq_ei_tracks(tracks: Sequence[Sequence[Track]], fit_coefs, y_max=None, best=None, valid_mask=None,
                   want_acq: bool = True):
     """acq_ei on tracked states: tracks[s][p] = output p of hyper-parameter sample s."""
@@ -1649,6 +1692,17 @@ def _update_path(g: GP):
     ch, tm, fb = C.c_int(0), C.c_int(0), C.c_int(0)
     _check(fn(g._h, C.byref(ch), C.byref(tm), C.byref(fb)))
     return ch.value, tm.value, fb.value
+
+
+def _append_path(g: GP) -> int:
+    """How the handle's last append ran (boss_debug_append_path; tests): 0 no append yet, 1 block rows, 2 full re-factorisation on
+    the device, 3 rank-one on resident inverses."""
+    fn = load_library().boss_debug_append_path
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+    out = C.c_int(-1)
+    _check(fn(g._h, C.byref(out)))
+    return out.value
 
 
 def _fallbacks(device: int = 0):

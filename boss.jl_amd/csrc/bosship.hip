@@ -552,6 +552,7 @@ struct boss_gp {
     bool have_winv = false;
     int few_calls = 0;
     int append_calls = 0;                      // single-observation appends since the last update (the second one builds the inverses)
+    int append_path = 0;                       // how the last append ran (boss_debug_append_path): 0 none yet, 1 block rows, 2 re-factorised, 3 rank-one
 };
 
 struct boss_cand {
@@ -567,6 +568,10 @@ struct boss_track {                            // resident predictive state of (
     unsigned long long epoch = 0;
     double *V = nullptr, *Csc = nullptr, *mu = nullptr, *var = nullptr, *mean = nullptr;
     bool has_mean = false;
+    // a nonstationary posterior's track (boss_ngp_track_create): Csc holds the ROUNDED RAW candidates, Clam [d][Mp] and
+    // Camp [Mp] the latent models' λ(x*), α(x*) there (one spare word behind Camp: the latent kernel's validity flag)
+    bool gibbs = false;
+    double *Clam = nullptr, *Camp = nullptr;
 };
 
 static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }

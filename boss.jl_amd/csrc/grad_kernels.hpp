@@ -825,6 +825,107 @@ __global__ __launch_bounds__(256) void track_append_kernel(const double* __restr
     }
 }
 
+// The same for a nonstationary posterior (boss_ngp_track_create): the right-hand side of row r is k_Gibbs(x_r, x*) from the raw
+// points, λ / α at row r of the handle and the track's resident λ(x*), α(x*) — gibbs_dim and the final expression of
+// gibbs_kstar_kernel, so an extended row starts from what a fresh K* build would put there.  The candidate tile's x, λ, α are
+// staged in LDS once ((2d + 1)·32 doubles, dynamic); thread (c, q) evaluates k(x_{N0+q}, x*_c) before the pass over V, which
+// is track_append_kernel's: 8 row subsets, summed in a fixed order, no atomics.
+__global__ __launch_bounds__(256) void gibbs_track_append_kernel(const double* __restrict__ A, int ld, int Np, int N0, int n,
+                                                                 double* __restrict__ Vslabs, int Ncap,
+                                                                 const double* __restrict__ X, const double* __restrict__ Lam,
+                                                                 const double* __restrict__ amp, int Npx,
+                                                                 const double* __restrict__ C, const double* __restrict__ Clam,
+                                                                 const double* __restrict__ Camp, int d, int Mp, int M,
+                                                                 double* __restrict__ mu, double* __restrict__ var) {
+    constexpr int BN = 32, CH = 64;
+    extern __shared__ double sm[];                           // cx[d][32] | cl[d][32] | ca[32]
+    __shared__ double Lr[TRACK_ROWS][CH];
+    __shared__ double red[8][TRACK_ROWS][BN];
+    __shared__ double ks[TRACK_ROWS][BN];
+    double* cx = sm;
+    double* cl = cx + d * BN;
+    double* ca = cl + d * BN;
+    const int tid = threadIdx.x, c = tid & 31, rs = tid >> 5;
+    const int c0 = blockIdx.x * BN;
+    double* V = Vslabs + (size_t)blockIdx.x * Ncap * BN;
+    for (int idx = tid; idx < d * BN; idx += 256) {
+        cx[idx] = C[(size_t)(idx / BN) * Mp + c0 + (idx % BN)];
+        cl[idx] = Clam[(size_t)(idx / BN) * Mp + c0 + (idx % BN)];
+    }
+    if (tid < BN) ca[tid] = Camp[c0 + tid];
+    __syncthreads();
+    {
+        const int q = rs;                                    // (8 row subsets = TRACK_ROWS new rows: one (row, candidate) pair per thread)
+        double kv = 0.0;
+        if (q < n) {
+            double pr = 1.0, es = 0.0;
+            for (int k = 0; k < d; ++k)
+                gibbs_dim(cx[k * BN + c], cl[k * BN + c], X[(size_t)k * Npx + N0 + q], Lam[(size_t)k * Npx + N0 + q], pr, es);
+            const double am = 0.5 * (amp[N0 + q] + ca[c]);
+            kv = am * am * sqrt(pr) * exp(-es);
+        }
+        ks[q][c] = kv;
+    }
+    double acc[TRACK_ROWS];
+#pragma unroll
+    for (int q = 0; q < TRACK_ROWS; ++q) acc[q] = 0.0;
+    for (int i0 = 0; i0 < N0; i0 += CH) {
+        __syncthreads();
+        for (int idx = tid; idx < TRACK_ROWS * CH; idx += 256) {
+            const int q = idx / CH, ii = idx - q * CH;
+            Lr[q][ii] = (q < n && i0 + ii < N0) ? A[(size_t)(i0 + ii) * ld + N0 + q] : 0.0;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < CH / 8; ++k) {
+            const int ii = rs + 8 * k;
+            const double v = (i0 + ii < N0) ? V[(size_t)(i0 + ii) * BN + c] : 0.0;
+#pragma unroll
+            for (int q = 0; q < TRACK_ROWS; ++q) acc[q] = __builtin_fma(Lr[q][ii], v, acc[q]);
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < TRACK_ROWS; ++q) red[rs][q][c] = acc[q];
+    __syncthreads();
+    if (rs == 0) {
+        const int j = c0 + c;
+        double vnew[TRACK_ROWS];
+        double dvar = 0.0, dmu = 0.0;
+        for (int q = 0; q < n; ++q) {
+            double dot = 0.0;
+            for (int k = 0; k < 8; ++k) dot += red[k][q][c];
+            double t = ks[q][c] - dot;
+            for (int qq = 0; qq < q; ++qq) t = __builtin_fma(-A[(size_t)(N0 + qq) * ld + N0 + q], vnew[qq], t);
+            const double v = t / A[(size_t)(N0 + q) * ld + N0 + q];
+            vnew[q] = v;
+            V[(size_t)(N0 + q) * BN + c] = v;
+            dvar = __builtin_fma(v, v, dvar);
+            dmu = __builtin_fma(v, A[(size_t)(N0 + q) * ld + Np], dmu);      // z_r sits in row Np of the factor array
+        }
+        if (j < M) {
+            var[j] -= dvar;
+            mu[j] += dmu;
+        }
+    }
+}
+
+// the candidates of a nonstationary track, rounded where the model's dims are discrete (what its latent models were evaluated at)
+__global__ void round_cand_kernel(const double* __restrict__ Craw, double* __restrict__ out, const unsigned char* __restrict__ discrete,
+                                  int d, int Mp) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= Mp) return;
+    for (int k = 0; k < d; ++k) {
+        const double v = Craw[(size_t)k * Mp + j];
+        out[(size_t)k * Mp + j] = (discrete && discrete[k]) ? rint(v) : v;
+    }
+}
+
+// constant fill (the padding of λ(X) when a nonstationary handle grows)
+__global__ void fill_kernel(double* __restrict__ p, double v, size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) p[i] = v;
+}
+
 // ------------------------------------------------------------------------------------------
 // Gradient of the log marginal likelihood w.r.t. the hyper-parameters (second half):
 //     ∂ℓ/∂θ = ½ Σ_ij G_ij ∂K_ij/∂θ ,   G = a aᵀ − K⁻¹ ,  K⁻¹ = L⁻ᵀL⁻¹

@@ -392,17 +392,18 @@ __device__ __forceinline__ void gibbs_dim(double x, double lx, double y, double 
 
 // blockIdx.z = parameter set (boss_ngp_loglike_batch): the rounded points are shared, set z reads λ(x_j) [d][Np] at
 // z·lam_bstride, α(x_j) and σ(x_j) [Np] at z·vec_bstride and writes its matrix at z·bstride; a single handle's update is the
-// one-set case (grid.z = 1, strides 0).
+// one-set case (grid.z = 1, strides 0).  t0: index of the first 64×64 tile of the lower triangle (row-major over tile rows) —
+// the block-row append builds the 4·kb + 3 tiles of block row kb alone, with the arithmetic of a full build.
 __global__ __launch_bounds__(256) void gibbs_gram_kernel(const double* __restrict__ X, const double* __restrict__ Lam,
                                                          const double* __restrict__ amp, const double* __restrict__ noise,
                                                          size_t lam_bstride, size_t vec_bstride, int d, int N, int Np,
-                                                         double* __restrict__ A, int ld, size_t bstride) {
+                                                         double* __restrict__ A, int ld, size_t bstride, int t0) {
     Lam += (size_t)blockIdx.z * lam_bstride;
     amp += (size_t)blockIdx.z * vec_bstride;
     noise += (size_t)blockIdx.z * vec_bstride;
     A += (size_t)blockIdx.z * bstride;
     __shared__ double xj[16][64], lj[16][64];
-    const int tid = threadIdx.x, t = blockIdx.x;
+    const int tid = threadIdx.x, t = blockIdx.x + t0;
     int bi = (int)((sqrt(8.0 * t + 1.0) - 1.0) * 0.5);
     while ((bi + 1) * (bi + 2) / 2 <= t) ++bi;
     while (bi * (bi + 1) / 2 > t) --bi;

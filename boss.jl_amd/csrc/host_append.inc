@@ -86,6 +86,16 @@ static int gp_grow(boss_gp* g, int Nnew) {
             for (int j = 0; j < i; ++j) (void)hipFree(nw[j]);
             return fail(BOSS_E_ALLOC, "device allocation failed while growing the posterior handle");
         }
+    // a nonstationary handle: λ(X) [d][Np2], α(X), σ(X) [Np2]; padded like boss_ngp_update pads them (λ = 1, α = σ = 0)
+    double* nlat[3] = {nullptr, nullptr, nullptr};
+    const size_t lbytes[3] = {sizeof(double) * d * Np2, sizeof(double) * Np2, sizeof(double) * Np2};
+    if (g->gibbs)
+        for (int i = 0; i < 3; ++i)
+            if (dev_malloc((void**)&nlat[i], lbytes[i]) != hipSuccess) {
+                for (int j = 0; j < 8; ++j) (void)hipFree(nw[j]);
+                for (int j = 0; j < i; ++j) (void)hipFree(nlat[j]);
+                return fail(BOSS_E_ALLOC, "device allocation failed while growing the posterior handle");
+            }
     hipError_t e = hipSuccess;
     for (int i = 0; i < 5 && e == hipSuccess; ++i) e = hipMemsetAsync(nw[i], 0, bytes[i], s);
     if (e == hipSuccess)
@@ -104,12 +114,30 @@ static int gp_grow(boss_gp* g, int Nnew) {
         e = hipMemcpy2DAsync(nw[4] + Np2, sizeof(double) * ld2, g->A + Np, sizeof(double) * g->ld,
                              sizeof(double) * RHS_ROWS, Np, hipMemcpyDeviceToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(nw[5], g->inv16, sizeof(double) * g->nblk * 8 * 256, hipMemcpyDeviceToDevice, s);
+    if (g->gibbs) {
+        const size_t nl = (size_t)d * Np2;
+        hipLaunchKernelGGL(fill_kernel, dim3((unsigned)((nl + 255) / 256)), dim3(256), 0, s, nlat[0], 1.0, nl);
+        for (int i = 1; i < 3 && e == hipSuccess; ++i) e = hipMemsetAsync(nlat[i], 0, lbytes[i], s);
+        if (e == hipSuccess)
+            e = hipMemcpy2DAsync(nlat[0], sizeof(double) * Np2, g->lamX, sizeof(double) * Np, sizeof(double) * Np, d,
+                                 hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(nlat[1], g->ampX, sizeof(double) * Np, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(nlat[2], g->noiseX, sizeof(double) * Np, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipGetLastError();
+    }
     dinv_join(g);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) {                                   // the handle keeps its old arrays; the new ones go back
         (void)hipStreamSynchronize(s);
         for (int i = 0; i < 8; ++i) (void)hipFree(nw[i]);
+        for (double* p : nlat)
+            if (p) (void)hipFree(p);
         return fail(BOSS_E_NO_DEVICE, std::string("growing the posterior handle: ") + hipGetErrorString(e));
+    }
+    if (g->gibbs) {
+        double* oldlat[3] = {g->lamX, g->ampX, g->noiseX};
+        for (double* p : oldlat) (void)hipFree(p);
+        g->lamX = nlat[0]; g->ampX = nlat[1]; g->noiseX = nlat[2];
     }
     double* old[8] = {g->Xraw, g->Xsc, g->y, g->mean, g->A, g->inv16, g->Dinv, g->Dinv2};
     for (double* p : old) (void)hipFree(p);
@@ -137,9 +165,20 @@ static int gp_grow(boss_gp* g, int Nnew) {
 // Reserve storage for observations that will be appended later (no re-allocation / re-layout when
 // they arrive).  The extra rows are identity padding of the factor: harmless, a little extra work per
 // factorisation.  The handle is left unfitted: call boss_gp_update afterwards.
+static int reserve_locked_entry(boss_gp* g, int N_total);
 extern "C" int boss_gp_reserve(boss_gp_t* g, int N_total) {
     if (!g || N_total < 1) return fail(BOSS_E_INVALID, "bad arguments");
     NOT_FOR_AUG(g);
+    return reserve_locked_entry(g, N_total);
+}
+// The same for a nonstationary handle: λ(X), α(X), σ(X) grow with the rest (gp_grow); follow with boss_ngp_update, whose latent
+// arrays still have N columns — the reserved columns are padding.
+extern "C" int boss_ngp_reserve(boss_gp_t* g, int N_total) {
+    if (!g || N_total < 1) return fail(BOSS_E_INVALID, "bad arguments");
+    if (!g->gibbs) return fail(BOSS_E_INVALID, "handle was not created by boss_ngp_create");
+    return reserve_locked_entry(g, N_total);
+}
+static int reserve_locked_entry(boss_gp* g, int N_total) {
     Ctx* c = g->ctx;
     HIPCHK(hipSetDevice(c->device));
     std::lock_guard<std::mutex> lk(c->mtx);
@@ -186,6 +225,7 @@ static int append_locked(boss_gp* g, int n, const double* X_new, const double* y
     // resident inverse factors (built here if they are not resident yet)
     static const int winv_after = getenv("BOSS_WINV_AFTER") ? atoi(getenv("BOSS_WINV_AFTER")) : 2;
     bool fast = false;
+    g->append_path = 0;
     if (n == 1 && N1 <= g->Np && winv_after > 0 && sizeof(double) * (size_t)g->Np <= 144 * 1024) {
         if (!g->have_winv && ++g->append_calls >= 2 && g->few_calls >= 0) {
             const size_t bytes = sizeof(double) * (size_t)g->ld * g->Np;
@@ -233,6 +273,7 @@ static int append_locked(boss_gp* g, int n, const double* X_new, const double* y
     }
     g->N = N1;
     if (fast) {
+        g->append_path = 3;
         const int Np = g->Np, ld = g->ld, nwg = Np / WINV_ROWS;
         dinv_join(g);
         if (!g->have_dinv) {                                 // the patched blocks must exist
@@ -336,9 +377,11 @@ static int append_locked(boss_gp* g, int n, const double* X_new, const double* y
     const int kb0 = N0 / BLK, kb1 = (g->Np != Np_before) ? g->nblk - 1 : (N1 - 1) / BLK;
     if (kb1 - kb0 + 1 > 4 || kb1 - kb0 + 1 >= g->nblk) {
         // most of the matrix is new: a plain re-factorisation is cheaper than block-row sweeps
+        g->append_path = 2;
         rc = factor_enqueue(g);
         if (rc) return rc;
     } else {
+        g->append_path = 1;
         const int Np = g->Np, ld = g->ld;
         dinv_join(g);
         HIPCHK(hipMemsetAsync(g->info, 0, sizeof(int), s));
@@ -366,6 +409,108 @@ static int append_locked(boss_gp* g, int n, const double* X_new, const double* y
         HIPCHK(hipMemcpyAsync(&g->host_res[2], g->info, sizeof(int), hipMemcpyDeviceToHost, s));
     }
     return update_finish(g, 0, logpdf_out);
+}
+
+// augment_dataset! (src/types/problem.jl:191-198) + the posterior of a nonstationary model with the latent models evaluated by
+// the caller AT THE NEW POINTS only.  k(x_i, x_j) depends on λ, α at x_i and x_j alone, and those of the old points stay resident
+// (lamX, ampX, noiseX): no entry between two old points changes, the new observations go to the end of the ordering, so the
+// leading block of the factor stays valid exactly as for a stationary kernel — the block rows that hold new observations are
+// rebuilt (append_locked's condition and sweep, the Gram tiles from gibbs_gram_kernel), or the grown arrays are factorised
+// again on the device where most of the matrix is new.  Nothing of the handle's data travels to the host.
+extern "C" int boss_ngp_append(boss_gp_t* g, int n_new, const double* X_new, const double* y_new, const double* lam_new,
+                               const double* amp_new, const double* noise_new, const double* mean_new, double* logpdf_out) {
+    if (!g || n_new < 1 || !X_new || !y_new || !lam_new || !amp_new || !noise_new) return fail(BOSS_E_INVALID, "NULL argument or n_new < 1");
+    if (!g->gibbs) return fail(BOSS_E_INVALID, "handle was not created by boss_ngp_create");
+    Ctx* c = g->ctx;
+    const int d = g->d, n = n_new;
+    std::vector<double> lb((size_t)d * n);                  // λ at the new points, [d][n] like lamX
+    for (int j = 0; j < n; ++j) {
+        for (int k = 0; k < d; ++k) {
+            const double v = lam_new[(size_t)j * d + k];
+            if (!(v > 0.0) || !std::isfinite(v)) return fail(BOSS_E_INVALID, "lengthscales must be finite and > 0");
+            lb[(size_t)k * n + j] = v;
+        }
+        if (!(amp_new[j] >= 0.0) || !std::isfinite(amp_new[j])) return fail(BOSS_E_INVALID, "amplitudes must be finite and >= 0");
+        if (!(noise_new[j] >= 0.0) || !std::isfinite(noise_new[j])) return fail(BOSS_E_INVALID, "noise stds must be finite and >= 0");
+    }
+    HIPCHK(hipSetDevice(c->device));
+    std::lock_guard<std::mutex> lk(c->mtx);
+    int rc = gp_settle(g, "handle has no valid factorisation (its per-point hyper-parameters are the ones re-used)");
+    if (rc) return rc;
+    if (g->has_mean && !mean_new)
+        return fail(BOSS_E_INVALID, "the posterior has a prior mean: mean_new (its values at the new points) is required");
+    if ((long long)g->N + n > MAX_ROWS) return fail(BOSS_E_INVALID, "more than 46080 observations are not supported");
+    hipStream_t s = c->stream;
+    const int N0 = g->N, N1 = N0 + n;
+    const int Np_before = g->Np;
+    rc = gp_grow(g, N1);
+    if (rc) return rc;
+    g->fitted = false;
+    g->have_lt = false;
+    ++g->factor_gen;
+    g->have_dinv = false;
+    g->have_winv = false;
+    g->few_calls = 0;
+    g->append_path = 0;
+    {
+        std::vector<double> xb;
+        pack_points(xb, X_new, d, n, n, g->discrete.empty() ? nullptr : g->discrete.data());
+        const size_t pitch = sizeof(double) * g->Np, row = sizeof(double) * n;
+        HIPCHK(hipMemcpy2DAsync(g->Xraw + N0, pitch, xb.data(), row, row, d, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpy2DAsync(g->lamX + N0, pitch, lb.data(), row, row, d, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(g->ampX + N0, amp_new, row, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(g->noiseX + N0, noise_new, row, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(g->y + N0, y_new, row, hipMemcpyHostToDevice, s));
+        if (mean_new) {
+            HIPCHK(hipMemcpyAsync(g->mean + N0, mean_new, row, hipMemcpyHostToDevice, s));
+            g->has_mean = true;
+        }
+        HIPCHK(hipStreamSynchronize(s));       // staging buffers go out of scope
+    }
+    g->N = N1;
+    // the block rows to (re)build and the switch to a plain re-factorisation: append_locked's
+    const int kb0 = N0 / BLK, kb1 = (g->Np != Np_before) ? g->nblk - 1 : (N1 - 1) / BLK;
+    if (kb1 - kb0 + 1 > 4 || kb1 - kb0 + 1 >= g->nblk) {
+        g->append_path = 2;
+        rc = factor_enqueue(g);
+        if (rc) return rc;
+    } else {
+        g->append_path = 1;
+        const int Np = g->Np, ld = g->ld;
+        dinv_join(g);
+        HIPCHK(hipMemsetAsync(g->info, 0, sizeof(int), s));
+        for (int kb = kb0; kb <= kb1; ++kb) {
+            hipLaunchKernelGGL(rhs_rows_kernel, dim3(1, 1, 1), dim3(BLK), 0, s, g->A, ld, (size_t)0, N1, Np, g->y, g->mean,
+                               (size_t)0, kb * BLK, (int*)nullptr);
+            // 128 rows × columns 0 … (kb+1)·128 − 1: the 4·kb + 3 tiles from triangular tile index kb (2 kb + 1), a full build's arithmetic
+            hipLaunchKernelGGL(gibbs_gram_kernel, dim3(4 * kb + 3, 1, 1), dim3(256), 0, s, (const double*)g->Xraw,
+                               (const double*)g->lamX, (const double*)g->ampX, (const double*)g->noiseX, (size_t)0, (size_t)0, d, N1,
+                               Np, g->A, ld, (size_t)0, kb * (2 * kb + 1));
+            for (int k = 0; k < kb; ++k) {
+                hipLaunchKernelGGL(potrf_trsm_kernel, dim3(8, 1, 1), dim3(TRSM_THREADS), 0, s, g->A, ld, (size_t)0, k, g->inv16, (size_t)0,
+                                   kb * BLK);
+                hipLaunchKernelGGL(potrf_rowupd_kernel, dim3(4 * (kb - k) + 1), dim3(256), 0, s, g->A, ld, k, kb, Np);
+            }
+            hipLaunchKernelGGL(potrf_diag_kernel, dim3(1, 1, 1), dim3(DIAG_THREADS), DIAG_LDS_BYTES, s, g->A, ld, (size_t)0, kb,
+                               g->inv16, (size_t)0, g->info, (unsigned long long*)nullptr, 0ull);
+            hipLaunchKernelGGL(potrf_trsm_kernel, dim3(1, 1, 1), dim3(TRSM_THREADS), 0, s, g->A, ld, (size_t)0, kb, g->inv16, (size_t)0,
+                               Np);
+        }
+        dinv_eager(g);
+        hipLaunchKernelGGL(potrf_logdet_kernel, dim3(1, 1, 1), dim3(LOGDET_THREADS), 0, s, g->A, ld, (size_t)0, N1, Np, g->scal,
+                           (double*)nullptr, (const int*)nullptr, (unsigned long long*)nullptr, 0ull, 0ull);
+        HIPCHK(hipMemcpyAsync(g->host_res, g->scal, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(&g->host_res[2], g->info, sizeof(int), hipMemcpyDeviceToHost, s));
+    }
+    return update_finish(g, 0, logpdf_out);
+}
+
+// How the handle's last append ran (tests): 0 no append yet, 1 block rows, 2 full re-factorisation on the device, 3 rank-one on
+// resident inverses.  No device work.
+extern "C" int boss_debug_append_path(const boss_gp_t* g, int* path_out) {
+    if (!g || !path_out) return fail(BOSS_E_INVALID, "bad argument");
+    *path_out = g->append_path;
+    return BOSS_OK;
 }
 
 extern "C" int boss_gp_fit(int device, int kernel, int d, int N, const double* X, const double* y,

@@ -588,7 +588,7 @@ static int ngp_loglike_batch_impl(int device, int d, int N, const double* X, con
     auto gram = [&](const ModelBatchGramArgs& a) {
         const int t64 = Np / 64;
         hipLaunchKernelGGL(gibbs_gram_kernel, dim3(t64 * (t64 + 1) / 2, 1, a.cnt), dim3(256), 0, c->stream, a.pts, a.par,
-                           a.par + (size_t)d * Np, a.par + (size_t)(d + 1) * Np, par_doubles, par_doubles, d, N, Np, a.A, a.ld, a.bstride);
+                           a.par + (size_t)d * Np, a.par + (size_t)(d + 1) * Np, par_doubles, par_doubles, d, N, Np, a.A, a.ld, a.bstride, 0);
     };
     ModelBatchGrad G;
     G.out_doubles = ((size_t)d + 3) * Np;                    // dlam [d][Np] | damp [Np] | dnoise [Np] | dmean [Np]
@@ -1019,7 +1019,7 @@ extern "C" int boss_ngp_fit_batch(int device, int d, int N, const double* X, con
                                  const double* par = L.extra + (size_t)b0 * L.sExtra;
                                  hipLaunchKernelGGL(gibbs_gram_kernel, dim3(t64 * (t64 + 1) / 2, 1, cnt), dim3(256), 0, c->stream, (const double*)L.pts,
                                                     par, par + (size_t)d * Np, par + (size_t)(d + 1) * Np, L.sExtra, L.sExtra, d, N, Np,
-                                                    L.A + (size_t)b0 * L.sA, L.ld, L.sA);
+                                                    L.A + (size_t)b0 * L.sA, L.ld, L.sA, 0);
                              });
         return hipSuccess;
     };

@@ -1098,7 +1098,7 @@ static int factor_enqueue(boss_gp* g, RiderReq* rider) {
         const int t64 = g->Np / 64;
         hipLaunchKernelGGL(gibbs_gram_kernel, dim3(t64 * (t64 + 1) / 2), dim3(256), 0, s, (const double*)g->Xraw,
                            (const double*)g->lamX, (const double*)g->ampX, (const double*)g->noiseX, (size_t)0, (size_t)0, g->d, g->N,
-                           g->Np, g->A, g->ld, (size_t)0);
+                           g->Np, g->A, g->ld, (size_t)0, 0);
     } else {
         gram_enqueue(c, g->Xsc, 0, g->d, g->N, g->Np, g->kernel, g->hyp, g->A, g->ld, 0, 1);
     }
@@ -1239,7 +1239,7 @@ extern "C" int boss_ggp_update(boss_gp_t* g, const double* lengthscale, double a
     return update_finish(g, flags, logpdf_out);
 }
 
-// The end of the two rebuild-appends: g2, a fresh handle on the joined data whose update returned rc, gives its contents to g when
+// The end of the rebuild-append (boss_ggp_append): g2, a fresh handle on the joined data whose update returned rc, gives its contents to g when
 // that update succeeded (the caller's pointer stays valid) and goes either way.
 static int replace_with_rebuilt(boss_gp* g, boss_gp* g2, int rc) {
     if (!rc) {
@@ -1339,64 +1339,6 @@ extern "C" int boss_ngp_update(boss_gp_t* g, const double* lam_X, const double* 
     int rc = factor_enqueue(g);
     if (rc) return rc;
     return update_finish(g, flags, logpdf_out);
-}
-
-// augment_dataset! (src/types/problem.jl:191-198) + the posterior with the latent models re-evaluated by the caller AT THE NEW POINTS
-// only (the values at the old points are the resident ones): the Gibbs kernel couples every pair of points through both points'
-// lengthscales, so — as in the reference — the system is rebuilt and factorised again, on a fresh handle whose contents replace gp's.
-extern "C" int boss_ngp_append(boss_gp_t* g, int n_new, const double* X_new, const double* y_new, const double* lam_new,
-                               const double* amp_new, const double* noise_new, const double* mean_new, double* logpdf_out) {
-    if (!g || n_new < 1 || !X_new || !y_new || !lam_new || !amp_new || !noise_new) return fail(BOSS_E_INVALID, "NULL argument or n_new < 1");
-    if (!g->gibbs) return fail(BOSS_E_INVALID, "handle was not created by boss_ngp_create");
-    Ctx* c = g->ctx;
-    const int d = g->d, N = g->N, Np = g->Np, Nt = N + n_new;
-    if (Nt > MAX_ROWS) return fail(BOSS_E_INVALID, "more than 46080 observations are not supported");
-    std::vector<double> Xd((size_t)d * Np), yd(N), lamd((size_t)d * Np), ampd(Np), noid(Np), meand;
-    bool has_mean = false;
-    {
-        HIPCHK(hipSetDevice(c->device));
-        std::lock_guard<std::mutex> lk(c->mtx);
-        int rc0 = gp_settle(g, "handle has no valid factorisation (its per-point hyper-parameters are the ones re-used)");
-        if (rc0) return rc0;
-        has_mean = g->has_mean;
-        if (has_mean && !mean_new) return fail(BOSS_E_INVALID, "the posterior has a prior mean: mean_new (its values at the new points) is required");
-        hipStream_t s = c->stream;
-        HIPCHK(hipMemcpyAsync(Xd.data(), g->Xraw, sizeof(double) * Xd.size(), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(yd.data(), g->y, sizeof(double) * N, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(lamd.data(), g->lamX, sizeof(double) * lamd.size(), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(ampd.data(), g->ampX, sizeof(double) * Np, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(noid.data(), g->noiseX, sizeof(double) * Np, hipMemcpyDeviceToHost, s));
-        if (has_mean || mean_new) {
-            meand.assign(Nt, 0.0);
-            if (has_mean) HIPCHK(hipMemcpyAsync(meand.data(), g->mean, sizeof(double) * N, hipMemcpyDeviceToHost, s));
-        }
-        HIPCHK(hipStreamSynchronize(s));
-    }
-    std::vector<double> X((size_t)d * Nt), y(Nt), lam((size_t)d * Nt), amp(Nt), noi(Nt);
-    for (int j = 0; j < N; ++j) {
-        y[j] = yd[j];
-        amp[j] = ampd[j];
-        noi[j] = noid[j];
-        for (int k = 0; k < d; ++k) {
-            X[(size_t)j * d + k] = Xd[(size_t)k * Np + j];
-            lam[(size_t)j * d + k] = lamd[(size_t)k * Np + j];
-        }
-    }
-    for (int j = 0; j < n_new; ++j) {
-        y[N + j] = y_new[j];
-        amp[N + j] = amp_new[j];
-        noi[N + j] = noise_new[j];
-        if (mean_new) meand[N + j] = mean_new[j];
-        for (int k = 0; k < d; ++k) {
-            X[(size_t)(N + j) * d + k] = X_new[(size_t)j * d + k];
-            lam[(size_t)(N + j) * d + k] = lam_new[(size_t)j * d + k];
-        }
-    }
-    boss_gp_t* g2 = nullptr;
-    int rc = boss_ngp_create(c->logical, d, Nt, X.data(), y.data(), g->discrete.empty() ? nullptr : g->discrete.data(), &g2);
-    if (rc) return rc;
-    rc = boss_ngp_update(g2, lam.data(), amp.data(), noi.data(), meand.empty() ? nullptr : meand.data(), 0, logpdf_out);
-    return replace_with_rebuilt(g, g2, rc);
 }
 
 extern "C" int boss_gp_sync(boss_gp_t* g, double* logpdf_out) {

@@ -6,7 +6,7 @@
 static void track_release(boss_track* t) {
     if (!t) return;
     if (t->ctx) (void)hipSetDevice(t->ctx->device);
-    void* ptrs[] = {t->V, t->Csc, t->mu, t->var, t->mean};
+    void* ptrs[] = {t->V, t->Csc, t->mu, t->var, t->mean, t->Clam, t->Camp};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     delete t;
@@ -27,11 +27,23 @@ static int track_rebuild(boss_track* t, const boss_cand* cd) {
         }
         t->Ncap = Ncap;
     }
-    int rc = predict_enqueue(g, cd, t->has_mean ? t->mean : nullptr, t->mu, t->var, true);   // 32-wide slabs in the scratch
+    int rc;
+    if (t->gibbs) {
+        // the nonstationary prediction path on the track's own rounded candidates and latent values (cd is not read)
+        boss_cand own;
+        own.ctx = c;
+        own.d = t->d;
+        own.M = t->M;
+        own.Mp = t->Mp;
+        own.Craw = t->Csc;
+        rc = predict_enqueue(g, &own, t->has_mean ? t->mean : nullptr, t->mu, t->var, true, t->Clam, t->Camp);
+    } else {
+        rc = predict_enqueue(g, cd, t->has_mean ? t->mean : nullptr, t->mu, t->var, true);   // 32-wide slabs in the scratch
+    }
     if (rc) return rc;
     HIPCHK(hipMemcpy2DAsync(t->V, sizeof(double) * (size_t)t->Ncap * 32, c->vscratch.p, sizeof(double) * (size_t)g->Np * 32,
                             sizeof(double) * (size_t)g->Np * 32, t->tiles, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(t->Csc, c->csc.p, sizeof(double) * (size_t)t->d * t->Mp, hipMemcpyDeviceToDevice, s));
+    if (!t->gibbs) HIPCHK(hipMemcpyAsync(t->Csc, c->csc.p, sizeof(double) * (size_t)t->d * t->Mp, hipMemcpyDeviceToDevice, s));
     t->N = g->N;
     t->epoch = g->epoch;
     return BOSS_OK;
@@ -78,6 +90,106 @@ extern "C" int boss_track_create(boss_gp_t* g, const boss_cand_t* cand, const do
     return BOSS_OK;
 }
 
+// Tracked candidates of a nonstationary posterior: the prediction runs once through the nonstationary path (unclipped moments);
+// the track keeps the V slabs, μ, σ², the rounded raw candidates and λ(x*), α(x*) — from the caller's arrays, or written by the
+// latent kernel into the same buffers (lat) — so gibbs_track_append_kernel can form k_Gibbs(x_r, x*) for every appended row.
+constexpr int NGP_TRACK_MAX_D = 16;
+static int ngp_track_create(boss_gp_t* g, const boss_cand_t* cand, const double* lam_Xs, const double* amp_Xs, const boss_nlat_t* lat,
+                            const double* mean_Xs, boss_track_t** out) {
+    if (!g->gibbs) return fail(BOSS_E_INVALID, "handle was not created by boss_ngp_create");
+    if (g->d > NGP_TRACK_MAX_D) return fail(BOSS_E_INVALID, "tracked candidates of nonstationary posteriors support x_dim <= 16");
+    if (cand->ctx != g->ctx || cand->d != g->d) return fail(BOSS_E_INVALID, "candidates and posterior must share device and x_dim");
+    const int d = g->d, M = cand->M, Mp = cand->Mp;
+    std::vector<double> lam, amp;
+    if (lat) {
+        boss_nlat_t* one = const_cast<boss_nlat_t*>(lat);
+        int rc = nlat_match(1, &g, &one);
+        if (rc) return rc;
+    } else {
+        lam.assign((size_t)d * Mp, 1.0);                     // (checked and padded as ngp_pack does)
+        amp.assign(Mp, 0.0);
+        for (int j = 0; j < M; ++j) {
+            for (int k = 0; k < d; ++k) {
+                const double v = lam_Xs[(size_t)j * d + k];
+                if (!(v > 0.0) || !std::isfinite(v)) return fail(BOSS_E_INVALID, "lengthscales must be finite and > 0");
+                lam[(size_t)k * Mp + j] = v;
+            }
+            if (!(amp_Xs[j] >= 0.0) || !std::isfinite(amp_Xs[j])) return fail(BOSS_E_INVALID, "amplitudes must be finite and >= 0");
+            amp[j] = amp_Xs[j];
+        }
+    }
+    Ctx* c = g->ctx;
+    HIPCHK(hipSetDevice(c->device));
+    std::lock_guard<std::mutex> lk(c->mtx);
+    int rc = gp_settle(g);
+    if (rc) return rc;
+    hipStream_t s = c->stream;
+    boss_track* t = new boss_track();
+    t->ctx = c;
+    t->gp = g;
+    t->gibbs = true;
+    t->d = d;
+    t->M = M;
+    t->Mp = Mp;
+    t->tiles = (M + 31) / 32;
+    if (dev_malloc((void**)&t->Csc, sizeof(double) * (size_t)d * Mp) != hipSuccess ||
+        dev_malloc((void**)&t->Clam, sizeof(double) * (size_t)d * Mp) != hipSuccess ||
+        dev_malloc((void**)&t->Camp, sizeof(double) * ((size_t)Mp + 1)) != hipSuccess ||
+        dev_malloc((void**)&t->mu, sizeof(double) * M) != hipSuccess ||
+        dev_malloc((void**)&t->var, sizeof(double) * M) != hipSuccess ||
+        dev_malloc((void**)&t->mean, sizeof(double) * M) != hipSuccess) {
+        (void)hipGetLastError();
+        track_release(t);
+        return fail(BOSS_E_ALLOC, "device allocation failed");
+    }
+    auto bail = [&](int code) {
+        (void)hipStreamSynchronize(s);
+        (void)hipGetLastError();
+        track_release(t);
+        return code;
+    };
+    hipLaunchKernelGGL(round_cand_kernel, dim3((Mp + 255) / 256), dim3(256), 0, s, (const double*)cand->Craw, t->Csc,
+                       (const unsigned char*)g->discrete_dev, d, Mp);
+    if (lat) {
+        boss_nlat_t* one = const_cast<boss_nlat_t*>(lat);
+        unsigned long long* dbad = (unsigned long long*)(t->Camp + Mp);
+        rc = nlat_enqueue(c, 1, &one, t->Csc, Mp, M, t->Clam, 0, t->Camp, 0, nullptr, 0, nullptr, 0, nullptr, dbad);
+        if (rc == BOSS_OK) rc = nlat_check(c, dbad, nullptr);
+        if (rc) return bail(rc);
+    } else {
+        hipError_t e = hipMemcpyAsync(t->Clam, lam.data(), sizeof(double) * (size_t)d * Mp, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(t->Camp, amp.data(), sizeof(double) * Mp, hipMemcpyHostToDevice, s);
+        if (e != hipSuccess) return bail(fail(BOSS_E_NO_DEVICE, hipGetErrorString(e)));
+    }
+    if (mean_Xs) {
+        hipError_t e = hipMemcpyAsync(t->mean, mean_Xs, sizeof(double) * M, hipMemcpyHostToDevice, s);
+        if (e != hipSuccess) return bail(fail(BOSS_E_NO_DEVICE, hipGetErrorString(e)));
+        t->has_mean = true;
+    }
+    hipError_t e = hipStreamSynchronize(s);                  // the staging vectors and the caller's mean may go
+    if (e != hipSuccess) return bail(fail(BOSS_E_NO_DEVICE, hipGetErrorString(e)));
+    rc = track_rebuild(t, cand);
+    if (rc) return bail(rc);
+    e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return bail(fail(BOSS_E_NO_DEVICE, hipGetErrorString(e)));
+    *out = t;
+    return BOSS_OK;
+}
+extern "C" int boss_ngp_track_create(boss_gp_t* g, const boss_cand_t* cand, const double* lam_Xs, const double* amp_Xs,
+                                     const double* mean_Xs, boss_track_t** out) {
+    if (!out) return fail(BOSS_E_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!g || !cand || !lam_Xs || !amp_Xs) return fail(BOSS_E_INVALID, "NULL argument");
+    return ngp_track_create(g, cand, lam_Xs, amp_Xs, nullptr, mean_Xs, out);
+}
+extern "C" int boss_ngp_track_create_lat(boss_gp_t* g, const boss_cand_t* cand, const boss_nlat_t* lat, const double* mean_Xs,
+                                         boss_track_t** out) {
+    if (!out) return fail(BOSS_E_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!g || !cand || !lat) return fail(BOSS_E_INVALID, "NULL argument");
+    return ngp_track_create(g, cand, nullptr, nullptr, lat, mean_Xs, out);
+}
+
 extern "C" void boss_track_free(boss_track_t* t) {
     if (!t) return;
     if (t->ctx) {
@@ -98,9 +210,15 @@ static int track_sync_locked(boss_track* t) {
     hipStream_t s = t->ctx->stream;
     for (int N0 = t->N; N0 < g->N; N0 += TRACK_ROWS) {
         const int n = std::min(TRACK_ROWS, g->N - N0);
-        hipLaunchKernelGGL(track_append_kernel, dim3(t->tiles), dim3(256), 0, s, (const double*)g->A, g->ld, g->Np, N0, n, t->V,
-                           t->Ncap, (const double*)g->Xsc, g->Np, (const double*)t->Csc, t->d, t->Mp, t->M, g->kernel, g->amp2,
-                           t->mu, t->var);
+        if (t->gibbs)
+            hipLaunchKernelGGL(gibbs_track_append_kernel, dim3(t->tiles), dim3(256), sizeof(double) * (2 * t->d + 1) * 32, s,
+                               (const double*)g->A, g->ld, g->Np, N0, n, t->V, t->Ncap, (const double*)g->Xraw, (const double*)g->lamX,
+                               (const double*)g->ampX, g->Np, (const double*)t->Csc, (const double*)t->Clam, (const double*)t->Camp,
+                               t->d, t->Mp, t->M, t->mu, t->var);
+        else
+            hipLaunchKernelGGL(track_append_kernel, dim3(t->tiles), dim3(256), 0, s, (const double*)g->A, g->ld, g->Np, N0, n, t->V,
+                               t->Ncap, (const double*)g->Xsc, g->Np, (const double*)t->Csc, t->d, t->Mp, t->M, g->kernel, g->amp2,
+                               t->mu, t->var);
     }
     t->N = g->N;
     HIPCHK(hipGetLastError());

@@ -955,6 +955,22 @@ function augment!(p::HipNonstationaryPosterior, X_new::AbstractMatrix{<:Real}, y
         Float64.(p.f_σ.(eachcol(Xn))), mean_vals(p.post.mean, Xn), lp))
     return lp[]
 end
+"Room for `extra` later observations (`boss_ngp_reserve`); leaves the handle unfitted: follow with the update, latent arrays of N columns as before."
+reserve!(p::HipNonstationaryPosterior, extra::Int) =
+    check(ccall((:boss_ngp_reserve, lib), Cint, (Ptr{Cvoid}, Cint), p.post.h.h, n_obs(p.post) + extra))
+"""
+Tracked candidates of a nonstationary slice (`boss_ngp_track_create`): `cand` is the `boss_cand_t` of `xs`; the latent models are
+evaluated at the rounded candidates once, `augment!` then extends the state by one row per observation.  The returned handle goes
+to `boss_track_moments` / `boss_acq_ei_tracks` / `boss_track_free` like a plain slice's (SequentialBatchAM's loop,
+src/acquisition_maximizers/batch.jl:32-38, over a NonstationaryGP).
+"""
+function track(p::HipNonstationaryPosterior, cand::Ptr{Cvoid}, xs::AbstractMatrix{<:Real})
+    Xs = Matrix{Float64}(xs); Xr = rounded(Xs, p.discrete); t = Ref{Ptr{Cvoid}}()
+    GC.@preserve p check(ccall((:boss_ngp_track_create, lib), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Ptr{Cvoid}}),
+        p.post.h.h, cand, reduce(hcat, p.f_λ.(eachcol(Xr))), Float64.(p.f_α.(eachcol(Xr))), mean_vals(p.post.mean, Xs), t))
+    return t[]
+end
 function mean_and_var(p::HipNonstationaryPosterior, X::AbstractMatrix{<:Real})
     Xs = Matrix{Float64}(X); Xr = rounded(Xs, p.discrete); M = size(Xs, 2)
     μ = Vector{Float64}(undef, M); σ2 = similar(μ); bad = Ref{Clong}(-1)
@@ -1152,6 +1168,13 @@ function mean_and_var(p::HipNonstationaryPosterior, L::HipLatents, X::AbstractMa
         (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Clong}),
         p.post.h.h, M, Xs, L.h, mean_vals(p.post.mean, Xs), μ, σ2, bad))
     return μ, σ2
+end
+"`track` with λ(x*), α(x*) written on the device by resident latent models (`boss_ngp_track_create_lat`)"
+function track(p::HipNonstationaryPosterior, L::HipLatents, cand::Ptr{Cvoid}, xs::AbstractMatrix{<:Real})
+    Xs = Matrix{Float64}(xs); t = Ref{Ptr{Cvoid}}()
+    GC.@preserve p L check(ccall((:boss_ngp_track_create_lat, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cdouble}, Ref{Ptr{Cvoid}}),
+        p.post.h.h, cand, L.h, mean_vals(p.post.mean, Xs), t))
+    return t[]
 end
 "... and with the analytic Jacobians of the latent models instead of ForwardDiff through host closures (`boss_ngp_predict_grad_lat`)"
 function mean_and_var_grad(p::HipNonstationaryPosterior, L::HipLatents, X::AbstractMatrix{<:Real}; mean_grad = C_NULL)

@@ -255,8 +255,9 @@ class HipNonstationaryPosteriorSlice:
     latents: Optional[api.NgpLatents] = None                    # the latent models resident on the device (resident_latents)
 
     def append(self, x, y) -> float:
-        """augment_dataset! (src/types/problem.jl:191-198) on the fitted slice: the latent models are evaluated at the new points, the
-        system is rebuilt and factorised (boss_ngp_append).  x: d×m (or length d), y: m.  Returns the logpdf of all points."""
+        """augment_dataset! (src/types/problem.jl:191-198) on the fitted slice: the latent models are evaluated at the new points and
+        the block rows of the factor that hold them are rebuilt on the device (boss_ngp_append).  x: d×m (or length d), y: m.
+        Returns the logpdf of all points."""
         if self.f_noise is None:
             raise ValueError("this slice was built without its noise model")
         X = np.asarray(x, float).reshape(self.gp.d, -1)
@@ -269,6 +270,16 @@ class HipNonstationaryPosteriorSlice:
             return self.gp.append(X, np.asarray(y, float).reshape(-1), lam, amp, noi, ms)
         return self.gp.append(X, np.asarray(y, float).reshape(-1), _cols(self.f_lam, Xr).T, _cols(self.f_amp, Xr).reshape(-1),
                               _cols(self.f_noise, X).reshape(-1), ms)
+
+    def track(self, cand: api.Candidates, Xs) -> api.GibbsTrack:
+        """The slice's resident predictive state at the candidates `cand` (= api.Candidates of Xs d×M): the latent closures are
+        evaluated at the rounded candidates, or the resident latents on the device; `append` then extends it in O(N·M)."""
+        Xs = np.asarray(Xs, float)
+        ms = None if self.mean_fn is None else np.array([float(self.mean_fn(Xs[:, j])) for j in range(Xs.shape[1])])
+        if self.latents is not None:
+            return api.GibbsTrack(self.gp, cand, mean_Xs=ms, latents=self.latents)
+        Xr = self._round(Xs)
+        return api.GibbsTrack(self.gp, cand, _cols(self.f_lam, Xr).T, _cols(self.f_amp, Xr).reshape(-1), ms)
 
     def loglike_grad(self):
         """(logpdf, dlam[d, N], damp[N], dnoise[N], dmean[N]): data_loglike_slice (nonstationary_gp.jl:237-245) of the fitted slice and
@@ -596,6 +607,54 @@ def nonstationary_acq_ei_batch(posts: Sequence[Sequence[HipNonstationaryPosterio
         ms = None if all(m is None for m in means) else np.stack([np.zeros(M) if m is None else m for m in means])
         mu[:, i, :], var[:, i, :] = api.ngp_predict_set([p.gp for p in sl], Xs, lam, amp, ms)
     return api.acq_ei_moments(mu, var, fit_coefs, y_max, best, valid_mask, posts[0][0].gp.device)
+
+
+def nonstationary_sequential_batch(posts: Sequence[Sequence[HipNonstationaryPosteriorSlice]], Xs, batch_size: int, fit_coefs, y_max=None,
+                                   Y=None, valid_mask=None) -> np.ndarray:
+    """SequentialBatchAM (src/acquisition_maximizers/batch.jl:26-38) over the fixed candidates Xs d×M for the S sampled nonstationary
+    posteriors posts[s][i] (nonstationary_model_posterior_batch, or [model.model_posterior(data)]): `batch_size` times the arg-max of
+    EI × feasibility is selected, the speculative observation (x, ŷ = the sample-averaged posterior mean, average_mean) is appended
+    to every slice, and the acquisition is re-evaluated.  Every slice's candidate state stays resident (slice.track): a selection
+    costs one boss_acq_ei_tracks call, an O(N²) block-row append per slice and an O(N·M) extension of its track.  Y (P×N, the
+    observations so far; None: no best-so-far yet) gives EI's incumbent through best_so_far and grows with the speculative
+    observations.  Members of a fitted set leave the set on their first append; storage grows where an append crosses a 256-row
+    boundary (nothing is reserved up front: a reserve would need the latent values at the data again, which the slices do not
+    keep).  Returns the d×batch_size selections."""
+    from .problem import LinFitness, best_so_far
+    if batch_size < 1:
+        raise ValueError("batch_size must be >= 1")
+    posts = [list(row) for row in posts]
+    if not posts or not posts[0]:
+        raise ValueError("posts must hold at least one sample with at least one output")
+    Xs = np.asarray(Xs, float)
+    if Xs.ndim == 1:
+        Xs = Xs[:, None]
+    S, P = len(posts), len(posts[0])
+    coefs = np.asarray(fit_coefs, float).reshape(-1)
+    ymax = np.full(P, np.inf) if y_max is None else np.asarray(y_max, float).reshape(-1)
+    Yrun = None if Y is None else np.asarray(Y, float).reshape(P, -1)
+    dev = posts[0][0].gp.device
+    cand = api.Candidates(Xs, dev)
+    tracks = []
+    try:
+        tracks = [[p.track(cand, Xs) for p in row] for row in posts]
+        xs = []
+        for _ in range(batch_size):
+            b = None if Yrun is None else best_so_far(LinFitness(coefs), Yrun, ymax)
+            _, am, _ = api.acq_ei_tracks(tracks, coefs, y_max, b, valid_mask, want_acq=False)
+            x = Xs[:, am].copy()
+            y = sum(np.array([t.moments(am, 1)[0][0] for t in ts]) for ts in tracks) / S       # ŷ read off the tracks: average_mean
+            for row in posts:
+                for i, p in enumerate(row):
+                    p.append(x, y[i])
+            Yrun = y[:, None] if Yrun is None else np.concatenate([Yrun, y[:, None]], axis=1)
+            xs.append(x)
+        return np.stack(xs, axis=1)
+    finally:
+        for ts in tracks:
+            for t in ts:
+                t.close()
+        cand.close()
 
 
 def nonstationary_acq_ei_grad_batch(posts: Sequence[Sequence[HipNonstationaryPosteriorSlice]], Xs, fit_coefs, y_max=None, best=None,

@@ -180,18 +180,29 @@ int boss_ggp_append(boss_gp_t* gp, int n_new, const double* X_new, const double*
  * boss_ngp_update factorises and returns logpdf(FiniteGP, y); boss_ngp_predict is mean_and_var with _clip_var
  * (k(x*,x*) = a(x*)^2, +1e-18 jitter as for the plain model).  boss_gp_sync, boss_gp_set_y, boss_gp_get_factor,
  * boss_gp_free, boss_acq_ei_moments (EI on the predicted moments), boss_ngp_predict_grad and boss_acq_ei_grad_moments (their
- * gradients w.r.t. the candidates) work with these handles, boss_ngp_predict_cov is their mean_and_cov; the other
- * boss_gp_* / boss_acq_* / boss_track_* entry points (boss_gp_predict_cov included) return BOSS_E_INVALID for them. */
+ * gradients w.r.t. the candidates) work with these handles, boss_ngp_predict_cov is their mean_and_cov, boss_ngp_append /
+ * boss_ngp_reserve / boss_ngp_track_create[_lat] their forms of append, reserve and tracked candidates; the other
+ * boss_gp_* / boss_acq_* entry points and boss_track_create (boss_gp_predict_cov included) return BOSS_E_INVALID for them. */
 int boss_ngp_create(int device, int d, int N, const double* X, const double* y, const unsigned char* discrete,
                     boss_gp_t** out);
 int boss_ngp_update(boss_gp_t* gp, const double* lam_X, const double* amp_X, const double* noise_X,
                     const double* mean_X, int flags, double* logpdf_out);
 /* augment_dataset! (src/types/problem.jl:191-198) for a fitted nonstationary posterior: n_new further observations with the latent
  * models' values AT THE NEW POINTS (lam_new d×n_new, amp_new, noise_new; mean_new when the posterior has a prior mean); the values
- * at the old points are the resident ones.  Every kernel entry couples both points' lengthscales, so — as in the reference — the
- * system is rebuilt and factorised; the handle stays the same object.  Needs a fitted handle (BOSS_E_NOT_FITTED otherwise). */
+ * at the old points are the resident ones.  k(x_i, x_j) depends on the latent values at x_i and x_j alone, so no entry between two
+ * old points changes and the new observations go to the end of the ordering: as for boss_gp_append, only the 128-row blocks that
+ * contain new observations are rebuilt on the device (O(N^2) work per block; more than four such block rows, or all of them: the
+ * grown arrays are factorised again, on the device as well), and the result — factor, z = L^{-1}(y-m), logpdf of all N+n_new
+ * observations — equals a fresh fit of the augmented data to rounding.  Nothing of the handle's data travels to the host; device
+ * storage grows as needed.  lam_new must be finite and > 0, amp_new and noise_new finite and >= 0 (BOSS_E_INVALID otherwise: the
+ * handle stays as it was, fitted).  Needs a fitted handle (BOSS_E_NOT_FITTED otherwise).  BOSS_E_NOT_PD leaves the handle unfitted
+ * (logpdf -Inf).  Tracks of the handle (boss_ngp_track_create) survive an append. */
 int boss_ngp_append(boss_gp_t* gp, int n_new, const double* X_new, const double* y_new, const double* lam_new,
                     const double* amp_new, const double* noise_new, const double* mean_new, double* logpdf_out);
+/* boss_gp_reserve for a nonstationary handle: device storage for N_total observations (the per-point latent arrays included), so
+ * appends up to that size need no re-allocation.  Leaves the handle unfitted: follow with boss_ngp_update, whose lam_X / amp_X /
+ * noise_X still have N columns (the reserved columns are padding). */
+int boss_ngp_reserve(boss_gp_t* gp, int N_total);
 /* data_loglike_slice (nonstationary_gp.jl:237-245) with its partial derivatives w.r.t. the latent models' VALUES at the training
  * points — what a gradient-based fitter's AD carries back to the latent models through finite_nongp (:183-196); the caller chains
  * them through its own latent models.  At the parameters of the last boss_ngp_update; every output may be NULL:
@@ -566,6 +577,18 @@ int boss_ngp_acq_ei_grad_set_lat(int P, int S, boss_gp_t* const* gps, int M, con
  * after another boss_gp_update every call returns BOSS_E_INVALID (create a new track).  The
  * posterior handle must outlive its tracks. */
 int boss_track_create(boss_gp_t* gp, const boss_cand_t* cand, const double* mean_Xs, boss_track_t** out);
+/* The same for a nonstationary posterior (boss_ngp_append extends the state).  lam_Xs d×M and amp_Xs M are the latent models at
+ * the candidates — evaluated by the caller at the ROUNDED candidates where dims are discrete, checked as boss_ngp_predict checks
+ * them —, or are written on the device by a resident latent object (_lat; bit for bit the array form fed boss_nlat_eval's arrays,
+ * the mismatch errors of boss_ngp_predict_lat).  The prediction runs once through the nonstationary path; the track keeps V, mu,
+ * var (unclipped), the rounded candidates and l(x*), a(x*), from which every appended row's k(x_r, x*) is formed.  The track is
+ * bound to the latent values of the boss_ngp_update that preceded its creation: after another boss_ngp_update every call returns
+ * BOSS_E_INVALID.  boss_track_sync, boss_track_moments, boss_acq_ei_tracks and boss_track_free take these tracks as they take the
+ * others.  Handles that are not nonstationary: BOSS_E_INVALID; unfitted: BOSS_E_NOT_FITTED; x_dim <= 16 (BOSS_E_INVALID beyond). */
+int boss_ngp_track_create(boss_gp_t* gp, const boss_cand_t* cand, const double* lam_Xs, const double* amp_Xs, const double* mean_Xs,
+                          boss_track_t** out);
+int boss_ngp_track_create_lat(boss_gp_t* gp, const boss_cand_t* cand, const boss_nlat_t* lat, const double* mean_Xs,
+                              boss_track_t** out);
 void boss_track_free(boss_track_t* track);
 int boss_track_sync(boss_track_t* track);
 int boss_track_moments(boss_track_t* track, int first, int count, double* mu, double* var);
