@@ -14,7 +14,7 @@ from .problem import (BossOptions, BossProblem, Dirac, Domain, ExperimentData, E
                       LinFitness, LogNormal, MvDirac, MvLogNormal, NonlinFitness)
 from .model import HipGaussianProcess, HipGPParams, average_mean  # noqa: F401,E402
 from .gradient_gp import (GradientData, HipGradientGaussianProcess, HipGradientGPParams,  # noqa: F401,E402
-                          join_gradient_slices)
+                          gradient_sequential_batch, join_gradient_slices)
 from .nonstationary import HipNonstationaryGP, HipParametrizedGP, stack_latents  # noqa: F401,E402
 from .nonstationary import (LatentActivation, constant_latent, exp_act, identity_act, latent_transform,  # noqa: F401,E402
                             softplus)

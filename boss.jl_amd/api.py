@@ -44,6 +44,7 @@ SIGNATURES = {
     "boss_ngp_reserve": (C.c_int, [C.c_void_p, C.c_int]),
     "boss_ggp_loglike_grad": (C.c_int, [C.c_void_p, _c_dp, _c_dp]),
     "boss_ggp_append": (C.c_int, [C.c_void_p, C.c_int, _c_dp, _c_dp, _c_dp, _c_dp]),
+    "boss_ggp_reserve": (C.c_int, [C.c_void_p, C.c_int]),
     "boss_gp_fit": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _c_dp, _c_dp, _c_dp, _c_dp, C.c_double, C.c_double,
                               _c_ucp, C.POINTER(C.c_void_p), _c_dp]),
     "boss_gp_set_y": (C.c_int, [C.c_void_p, _c_dp]),
@@ -116,6 +117,7 @@ SIGNATURES = {
     "boss_track_create": (C.c_int, [C.c_void_p, C.c_void_p, _c_dp, C.POINTER(C.c_void_p)]),
     "boss_ngp_track_create": (C.c_int, [C.c_void_p, C.c_void_p, _c_dp, _c_dp, _c_dp, C.POINTER(C.c_void_p)]),
     "boss_ngp_track_create_lat": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _c_dp, C.POINTER(C.c_void_p)]),
+    "boss_ggp_track_create": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     "boss_track_free": (None, [C.c_void_p]),
     "boss_track_sync": (C.c_int, [C.c_void_p]),
     "boss_track_moments": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _c_dp, _c_dp]),
@@ -464,9 +466,18 @@ class GradGP(GP):
         _check(load_library().boss_ggp_loglike_grad(self._h, C.byref(out), _dp(grad)))
         return out.value, grad
 
+    def reserve(self, N_total=None, *, points: Optional[int] = None):
+        """Reserve storage for `points` POINTS in all, points (1 + d) rows (boss_ggp_reserve); the handle must be (re-)updated
+        afterwards.  The count is named: GP.reserve's positional N_total counts observations, which this model has 1 + d of per
+        point, and stays refused as boss_gp_reserve refuses these handles."""
+        if N_total is not None or points is None:
+            raise BossError(BOSS_E_INVALID, "a gradient-observation posterior reserves in points: reserve(points=n_points_total)")
+        _check(load_library().boss_ggp_reserve(self._h, int(points)))
+
     def append(self, X_new, y_new, dY_new) -> float:
-        """augment_dataset! + the posterior at unchanged hyper-parameters (the augmented system is rebuilt and factorised, as in the
-        reference): X_new d×m (or a length-d vector), y_new m, dY_new d×m.  Returns the logpdf of all n + m points."""
+        """augment_dataset! + the posterior at unchanged hyper-parameters: X_new d×m (or a length-d vector), y_new m, dY_new d×m.
+        The 1 + d rows of every new point go to the end of the handle's own ordering and the block rows of the factor that hold
+        them are rebuilt on the device (boss_ggp_append).  Returns the logpdf of all n + m points."""
         X_new = _f64(np.asarray(X_new, dtype=np.float64).reshape(self.d, -1), 2)
         m = X_new.shape[1]
         y_new = _f64(np.asarray(y_new).reshape(-1), 1)
@@ -474,9 +485,12 @@ class GradGP(GP):
         if y_new.shape[0] != m or dY_new.shape != (self.d, m):
             raise ValueError("y_new must have one entry and dY_new one column per new point")
         out = C.c_double(0.0)
-        _check(load_library().boss_ggp_append(self._h, m, _dp(X_new), _dp(y_new), dY_new.ctypes.data_as(_c_dp), C.byref(out)))
-        self.n += m
-        self.N = self.n * (1 + self.d)
+        rc = load_library().boss_ggp_append(self._h, m, _dp(X_new), _dp(y_new), dY_new.ctypes.data_as(_c_dp), C.byref(out))
+        cnt = C.c_int(self.N)                # the device's own count: the points stay appended when the factorisation fails
+        load_library().boss_gp_n(self._h, C.byref(cnt))
+        self.N = cnt.value
+        self.n = self.N // (1 + self.d)
+        _check(rc)
         self.logpdf = out.value
         return out.value
 
@@ -1316,6 +1330,16 @@ class GibbsTrack(Track):
                 raise BossError(BOSS_E_INVALID, "latents must be an open NgpLatents")
             _check(load_library().boss_ngp_track_create_lat(gp._h, cand._h, latents._h, _dp(ms), C.byref(h)))
         self._h, self.gp, self.cand, self.M = h, gp, cand, M
+
+
+class GradTrack(Track):
+    """Track of a gradient-observation posterior (boss_ggp_track_create): extended in O(N·M) per appended row after
+    GradGP.append.  Has Track's methods and goes to acq_ei_tracks like one; `moments` returns the reference's max(0, σ²)."""
+
+    def __init__(self, gp: "GradGP", cand: Candidates):
+        h = C.c_void_p()
+        _check(load_library().boss_ggp_track_create(gp._h, cand._h, C.byref(h)))
+        self._h, self.gp, self.cand, self.M = h, gp, cand, cand.M
 
 
 def acq_ei_tracks(tracks: Sequence[Sequence[Track]], fit_coefs, y_max=None, best=None, valid_mask=None,

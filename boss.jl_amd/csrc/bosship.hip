@@ -537,7 +537,7 @@ struct boss_gp {
     // gradient-observation posterior (GradientGaussianProcess): npts points, N = npts (1 + d) observations,
     // Xraw is [d][ldx]; hyp = {α², σ², σ_∂²}
     bool aug = false;
-    int npts = 0, ldx = 0;
+    int npts = 0, ldx = 0, nhead = 0;                        // nhead: points in component-major rows (aug_row_decode, gram_kernels.hpp)
     // nonstationary posterior (NonstationaryGP, Gibbs kernel): per-point λ [d][Np], α [Np], σ [Np]; Xraw holds the
     // (rounded where discrete) training points
     bool gibbs = false;
@@ -572,6 +572,9 @@ struct boss_track {                            // resident predictive state of (
     // Camp [Mp] the latent models' λ(x*), α(x*) there (one spare word behind Camp: the latent kernel's validity flag)
     bool gibbs = false;
     double *Clam = nullptr, *Camp = nullptr;
+    // a gradient-observation posterior's track (boss_ggp_track_create): Csc holds the RAW candidates; var is the UNCLIPPED running
+    // α² − ‖v‖² (a later row subtracts from it), clipped at 0 where it is handed out
+    bool aug = false;
 };
 
 static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }

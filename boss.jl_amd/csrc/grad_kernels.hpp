@@ -389,9 +389,11 @@ __global__ __launch_bounds__(256) void grad_accum_set_kernel(const GradSet* __re
 // The derivative rows are evaluated at x_i + 1e-8 when x* ≈ x_i (aug_entry, _build_cross_cov :233).
 // One workgroup per 32-candidate slab and row split: lanes along the candidates, eight point subsets; the a entries come from avec
 // (row l·n + i), the w entries from the W slabs.  part (gridDim.y > 1): [tile·gridDim.y + y][2 d][32], summed by aug_grad_finalize_kernel.
+// Appended points (i ≥ nhead, aug_row_decode) keep their rows together, row i (1 + d) + l: the walk over a split's points runs in two
+// segments with wave-uniform row strides (pi, pl), row = i·pi + l·pl — (1, nhead) for the head, (1 + d, 1) behind it.
 // ------------------------------------------------------------------------------------------
 __device__ __forceinline__ void aug_grad_accum_body(const double* __restrict__ Wslab, const double* __restrict__ avec, int Np,
-                                                    int n, const double* __restrict__ Xraw, int ldx,
+                                                    int n, int nhead, const double* __restrict__ Xraw, int ldx,
                                                     const double* __restrict__ Craw, int d, int Mp, int M, int kern,
                                                     double amp2, const double* __restrict__ invlam,
                                                     double* __restrict__ dmu, double* __restrict__ dvar,
@@ -414,7 +416,11 @@ __device__ __forceinline__ void aug_grad_accum_body(const double* __restrict__ W
     }
     const int per = (n + ny - 1) / ny;
     const int ibeg = by * per, iend = min(n, ibeg + per);
-    for (int i = ibeg + rs; i < iend; i += 8) {
+#pragma unroll 1
+    for (int seg = 0; seg < 2; ++seg) {
+    const int sbeg = seg ? max(ibeg, nhead) : ibeg, send = seg ? iend : min(iend, nhead);
+    const int pi = seg ? 1 + d : 1, pl = seg ? 1 : nhead;
+    for (int i = sbeg + rs; i < send; i += 8) {
         double t[DM], du2 = 0.0, ni = 0.0, r2 = 0.0;
 #pragma unroll
         for (int m = 0; m < DM; ++m) {
@@ -426,7 +432,8 @@ __device__ __forceinline__ void aug_grad_accum_body(const double* __restrict__ W
         }
 #pragma unroll
         for (int m = 0; m < DM; ++m) r2 = __builtin_fma(t[m] * il[m], t[m] * il[m], r2);
-        const double a0 = avec[i], w0 = W[(size_t)i * BN];
+        const size_t r0 = (size_t)i * pi;
+        const double a0 = avec[r0], w0 = W[r0 * BN];
         const double h0 = kappa_prime_over_r_r2(kern, r2);   // the value row: at the points as given
         double rr2 = r2;
         if (du2 <= ISAPPROX_RTOL2 * fmax(nc, ni)) {          // x* ≈ x_i: the derivative rows at x_i + 1e-8
@@ -441,8 +448,8 @@ __device__ __forceinline__ void aug_grad_accum_body(const double* __restrict__ W
         double sa = 0.0, sw = 0.0, al[DM], wl[DM];
 #pragma unroll
         for (int m = 0; m < DM; ++m) {
-            al[m] = m < d ? avec[(size_t)(m + 1) * n + i] : 0.0;
-            wl[m] = m < d ? W[((size_t)(m + 1) * n + i) * BN] : 0.0;
+            al[m] = m < d ? avec[(size_t)(m + 1) * pl + r0] : 0.0;
+            wl[m] = m < d ? W[((size_t)(m + 1) * pl + r0) * BN] : 0.0;
             const double tm = t[m] * il2[m];
             sa = __builtin_fma(al[m], tm, sa);
             sw = __builtin_fma(wl[m], tm, sw);
@@ -456,6 +463,7 @@ __device__ __forceinline__ void aug_grad_accum_body(const double* __restrict__ W
             G1[m] += tm0 * h0 * a0 + tm * ka - h * al[m] * il2[m];
             G2[m] += tm0 * h0 * w0 + tm * kw - h * wl[m] * il2[m];
         }
+    }
     }
 #pragma unroll
     for (int m = 0; m < DM; ++m) {
@@ -475,21 +483,21 @@ __device__ __forceinline__ void aug_grad_accum_body(const double* __restrict__ W
     }
 }
 __global__ __launch_bounds__(256) void aug_grad_accum_kernel(const double* __restrict__ Wslabs, const double* __restrict__ avec, int Np,
-                                                             int n, const double* __restrict__ Xraw, int ldx,
+                                                             int n, int nhead, const double* __restrict__ Xraw, int ldx,
                                                              const double* __restrict__ Craw, int d, int Mp, int M, int kern,
                                                              double amp2, const double* __restrict__ invlam,
                                                              double* __restrict__ dmu, double* __restrict__ dvar,
                                                              double* __restrict__ part) {
-    aug_grad_accum_body(Wslabs + (size_t)blockIdx.x * Np * 32, avec, Np, n, Xraw, ldx, Craw, d, Mp, M, kern, amp2, invlam, dmu, dvar,
+    aug_grad_accum_body(Wslabs + (size_t)blockIdx.x * Np * 32, avec, Np, n, nhead, Xraw, ldx, Craw, d, Mp, M, kern, amp2, invlam, dmu, dvar,
                         part ? part + (size_t)blockIdx.x * gridDim.y * 2 * AUG_MAX_D * 32 : nullptr, blockIdx.x, blockIdx.y, gridDim.y);
 }
 // ... of a SET of equally shaped gradient-observation posteriors: grid = (candidate tiles, point splits, members)
 __global__ __launch_bounds__(256) void aug_grad_accum_set_kernel(const GradSet* __restrict__ sets, const double* __restrict__ Wslabs, int Np,
-                                                                 int n, int ldx, const double* __restrict__ Craw, int d, int Mp, int M, int kern,
-                                                                 double* __restrict__ part) {
+                                                                 int n, int nhead, int ldx, const double* __restrict__ Craw, int d, int Mp, int M,
+                                                                 int kern, double* __restrict__ part) {
     const GradSet gs = sets[blockIdx.z];
     const size_t slab = (size_t)blockIdx.z * gridDim.x + blockIdx.x;
-    aug_grad_accum_body(Wslabs + slab * Np * 32, gs.avec, Np, n, gs.Xraw, ldx, Craw, d, Mp, M, kern, gs.amp2, gs.invlam, gs.dmu, gs.dvar,
+    aug_grad_accum_body(Wslabs + slab * Np * 32, gs.avec, Np, n, nhead, gs.Xraw, ldx, Craw, d, Mp, M, kern, gs.amp2, gs.invlam, gs.dmu, gs.dvar,
                         part ? part + slab * gridDim.y * 2 * AUG_MAX_D * 32 : nullptr, blockIdx.x, blockIdx.y, gridDim.y);
 }
 __device__ __forceinline__ void aug_grad_finalize_body(const double* __restrict__ part, int rsplit, int d, int M, double amp2,
@@ -907,6 +915,111 @@ __global__ __launch_bounds__(256) void gibbs_track_append_kernel(const double* _
             mu[j] += dmu;
         }
     }
+}
+
+// The same for a gradient-observation posterior (boss_ggp_track_create).  The right-hand side of new row r = (l, point) is
+// aug_entry(x*, x_pt, 0, l), the expression aug_kstar_body uses, so an extended row starts from what a fresh K* build would put
+// there; the candidate tile and 1/λ are staged in LDS once ((d·32 + d) doubles, dynamic).  The pass over V is track_append_kernel's:
+// 8 row subsets, summed in a fixed order, no atomics.  var is the track's unclipped running value (aug_track_var_kernel).
+__global__ __launch_bounds__(256) void aug_track_append_kernel(const double* __restrict__ A, int ld, int Np, int N0, int n,
+                                                               double* __restrict__ Vslabs, int Ncap,
+                                                               const double* __restrict__ Xraw, int ldx, int nhead,
+                                                               const double* __restrict__ Craw, int d, int Mp, int M, int kern,
+                                                               double amp2, const double* __restrict__ invlam,
+                                                               double* __restrict__ mu, double* __restrict__ var) {
+    constexpr int BN = 32, CH = 64;
+    extern __shared__ double sm[];                           // cx[d][32] | il[d]
+    __shared__ double Lr[TRACK_ROWS][CH];
+    __shared__ double red[8][TRACK_ROWS][BN];
+    __shared__ double ks[TRACK_ROWS][BN];
+    double* cx = sm;
+    double* il = cx + d * BN;
+    const int tid = threadIdx.x, c = tid & 31, rs = tid >> 5;
+    const int c0 = blockIdx.x * BN;
+    double* V = Vslabs + (size_t)blockIdx.x * Ncap * BN;
+    for (int idx = tid; idx < d * BN; idx += 256) cx[idx] = Craw[(size_t)(idx / BN) * Mp + c0 + (idx % BN)];
+    if (tid < d) il[tid] = invlam[tid];
+    __syncthreads();
+    {
+        const int q = rs;                                    // (8 row subsets = TRACK_ROWS new rows: one (row, candidate) pair per thread)
+        double kv = 0.0;
+        if (q < n) {
+            int l, pt;
+            aug_row_decode(N0 + q, nhead, d, l, pt);
+            kv = aug_entry(kern, amp2, d, il, cx + c, BN, Xraw + pt, ldx, 0, l);
+        }
+        ks[q][c] = kv;
+    }
+    double acc[TRACK_ROWS];
+#pragma unroll
+    for (int q = 0; q < TRACK_ROWS; ++q) acc[q] = 0.0;
+    for (int i0 = 0; i0 < N0; i0 += CH) {
+        __syncthreads();
+        for (int idx = tid; idx < TRACK_ROWS * CH; idx += 256) {
+            const int q = idx / CH, ii = idx - q * CH;
+            Lr[q][ii] = (q < n && i0 + ii < N0) ? A[(size_t)(i0 + ii) * ld + N0 + q] : 0.0;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < CH / 8; ++k) {
+            const int ii = rs + 8 * k;
+            const double v = (i0 + ii < N0) ? V[(size_t)(i0 + ii) * BN + c] : 0.0;
+#pragma unroll
+            for (int q = 0; q < TRACK_ROWS; ++q) acc[q] = __builtin_fma(Lr[q][ii], v, acc[q]);
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < TRACK_ROWS; ++q) red[rs][q][c] = acc[q];
+    __syncthreads();
+    if (rs == 0) {
+        const int j = c0 + c;
+        double vnew[TRACK_ROWS];
+        double dvar = 0.0, dmu = 0.0;
+        for (int q = 0; q < n; ++q) {
+            double dot = 0.0;
+            for (int k = 0; k < 8; ++k) dot += red[k][q][c];
+            double t = ks[q][c] - dot;
+            for (int qq = 0; qq < q; ++qq) t = __builtin_fma(-A[(size_t)(N0 + qq) * ld + N0 + q], vnew[qq], t);
+            const double v = t / A[(size_t)(N0 + q) * ld + N0 + q];
+            vnew[q] = v;
+            V[(size_t)(N0 + q) * BN + c] = v;
+            dvar = __builtin_fma(v, v, dvar);
+            dmu = __builtin_fma(v, A[(size_t)(N0 + q) * ld + Np], dmu);      // z_r sits in row Np of the factor array
+        }
+        if (j < M) {
+            var[j] -= dvar;
+            mu[j] += dmu;
+        }
+    }
+}
+
+// The unclipped variance α² − ‖v‖² of a gradient-observation track from its V slabs (the prediction path hands out the reference's
+// max(0, ·), gradient_gp.jl:343-361, from which a later row could not be subtracted).  One workgroup per slab, 8 row subsets,
+// fixed summation order.
+__global__ __launch_bounds__(256) void aug_track_var_kernel(const double* __restrict__ Vslabs, int Ncap, int N, int M, double amp2,
+                                                            double* __restrict__ var) {
+    constexpr int BN = 32;
+    __shared__ double red[8][BN];
+    const int tid = threadIdx.x, c = tid & 31, rs = tid >> 5;
+    const double* V = Vslabs + (size_t)blockIdx.x * Ncap * BN;
+    double acc = 0.0;
+    for (int i = rs; i < N; i += 8) {
+        const double v = V[(size_t)i * BN + c];
+        acc = __builtin_fma(v, v, acc);
+    }
+    red[rs][c] = acc;
+    __syncthreads();
+    if (rs == 0) {
+        double ss = 0.0;
+        for (int k = 0; k < 8; ++k) ss += red[k][c];
+        const int j = blockIdx.x * BN + c;
+        if (j < M) var[j] = amp2 - ss;
+    }
+}
+// max(0, ·) of a gradient-observation track's variances where they leave the track
+__global__ void clip_nonneg_kernel(double* __restrict__ v, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) v[i] = fmax(0.0, v[i]);
 }
 
 // the candidates of a nonstationary track, rounded where the model's dims are discrete (what its latent models were evaluated at)

@@ -165,6 +165,24 @@ __device__ __forceinline__ double aug_entry(int kern, double amp2, int d, const 
     return -amp2 * v;
 }
 
+// The internal row ordering of a gradient-observation handle.  The nhead points present at boss_ggp_create keep the reference's
+// component-major rows (row l·nhead + i); every later point j ≥ nhead owns the 1 + d consecutive rows behind them,
+// nhead (1 + d) + (j − nhead)(1 + d) + l = j (1 + d) + l, so an append only adds rows at the end (boss_ggp_append).  The posterior is
+// invariant under this symmetric permutation of the system.  With nhead = all points both maps are the reference's.
+// (aug_grad_accum_body walks the points in two segments and uses the two closed forms of aug_row_of with wave-uniform strides.)
+__device__ __forceinline__ void aug_row_decode(int row, int nhead, int d, int& l, int& pt) {
+    if (row < nhead * (1 + d)) {
+        l = row / nhead;
+        pt = row - l * nhead;
+    } else {
+        pt = row / (1 + d);
+        l = row - pt * (1 + d);
+    }
+}
+__device__ __forceinline__ int aug_row_of(int l, int pt, int nhead, int d) {
+    return pt < nhead ? l * nhead + pt : pt * (1 + d) + l;
+}
+
 // Lower 64×64 tiles of the augmented matrix.  `cholesky(Symmetric(K))` (:209,:325) reads the UPPER
 // triangle, so the stored entry (a, b), a ≥ b, is the reference's K[b, a].  hyp = {α², σ², σ_∂²};
 // padding rows/columns = identity.
@@ -172,23 +190,30 @@ __device__ __forceinline__ double aug_entry(int kern, double amp2, int d, const 
 // z·par_bstride and writes its matrix at z·bstride.  A single handle's update is the one-set case (grid.z = 1, strides 0),
 // so both paths build every entry with the same instructions.  The set's α², σ², σ_∂² are wave-uniform (scalar registers),
 // its 1/λ sit in LDS beside the staged points.
-__global__ __launch_bounds__(256) void aug_gram_kernel(const double* __restrict__ Xraw, int ldx, int d, int n, int N, int Np,
+// nhead: see aug_row_decode.  The reference's stored entry has the observation with the SMALLER component index l in the row role
+// (its ordering is component-major), and the 1e-8 shift makes value × derivative entries depend on the roles: where the mixed
+// ordering puts a derivative row of a head point in front of a value row of a later point, the roles are exchanged back.  Between
+// equal l the choice changes no bit, and with nhead = all points the smaller row never has the larger l.
+// t0: index of the first 64×64 tile of the lower triangle (row-major over tile rows) — the block-row append builds the 4·kb + 3
+// tiles of block row kb alone, with the arithmetic of a full build.
+__global__ __launch_bounds__(256) void aug_gram_kernel(const double* __restrict__ Xraw, int ldx, int d, int nhead, int N, int Np,
                                                        int kern, const double* __restrict__ hyp,
                                                        const double* __restrict__ invlam, size_t par_bstride,
-                                                       double* __restrict__ A, int ld, size_t bstride) {
+                                                       double* __restrict__ A, int ld, size_t bstride, int t0) {
     hyp += (size_t)blockIdx.z * par_bstride;
     invlam += (size_t)blockIdx.z * par_bstride;
     A += (size_t)blockIdx.z * bstride;
     __shared__ double xa[AUG_MAX_D][64], xb[AUG_MAX_D][64], il[AUG_MAX_D];
     __shared__ int la[64], lb[64];
-    const int tid = threadIdx.x, t = blockIdx.x;
+    const int tid = threadIdx.x, t = blockIdx.x + t0;
     int bi = (int)((sqrt(8.0 * t + 1.0) - 1.0) * 0.5);
     while ((bi + 1) * (bi + 2) / 2 <= t) ++bi;
     while (bi * (bi + 1) / 2 > t) --bi;
     const int bj = t - bi * (bi + 1) / 2;
     if (tid < 128) {
         const int c = tid & 63, obs = (tid < 64 ? bi : bj) * 64 + c;
-        const int l = obs < N ? obs / n : -1, pt = obs < N ? obs - l * n : 0;
+        int l = -1, pt = 0;
+        if (obs < N) aug_row_decode(obs, nhead, d, l, pt);
         if (tid < 64) la[c] = l; else lb[c] = l;
         for (int k = 0; k < d; ++k) (tid < 64 ? xa : xb)[k][c] = Xraw[(size_t)k * ldx + pt];
     }
@@ -202,7 +227,9 @@ __global__ __launch_bounds__(256) void aug_gram_kernel(const double* __restrict_
         if (a < b) continue;
         double v;
         if (a < N && b < N) {
-            v = aug_entry(kern, amp2, d, il, &xb[0][cc], 64, &xa[0][r], 64, lb[cc], la[r]);
+            const bool sw = la[r] < lb[cc];                  // (never with nhead = all points)
+            v = aug_entry(kern, amp2, d, il, sw ? &xa[0][r] : &xb[0][cc], 64, sw ? &xb[0][cc] : &xa[0][r], 64, sw ? la[r] : lb[cc],
+                          sw ? lb[cc] : la[r]);
             if (a == b) v += (la[r] == 0) ? hyp[1] : hyp[2];
         } else {
             v = (a == b) ? 1.0 : 0.0;
@@ -280,7 +307,8 @@ __device__ __forceinline__ double aug_entry_dlam(int kern, double amp2, int d, c
 // blockIdx.z = parameter set (boss_ggp_loglike_grad_batch): the raw points are shared, set z reads its 1/λ and hyp at
 // z·par_bstride (the block aug_gram_kernel reads), its K⁻¹ at z·zW, its partials of a at z·zC and writes its tile sums at z·zC.
 // A single handle's call is the one-set case (grid.z = 1, strides 0): a set's sums do not depend on where it stands in a batch.
-__global__ __launch_bounds__(256) void aug_llgrad_tile_kernel(const double* __restrict__ Xraw, int ldx, int d, int n, int N, int Np, int kern,
+// nhead and the row/column roles: as in aug_gram_kernel.
+__global__ __launch_bounds__(256) void aug_llgrad_tile_kernel(const double* __restrict__ Xraw, int ldx, int d, int nhead, int N, int Np, int kern,
                                                               const double* __restrict__ hyp, const double* __restrict__ invlam,
                                                               size_t par_bstride, const double* __restrict__ Kinv, int ldk,
                                                               const double* __restrict__ apart, int nch, double* __restrict__ out, size_t zW,
@@ -299,7 +327,8 @@ __global__ __launch_bounds__(256) void aug_llgrad_tile_kernel(const double* __re
     const int bj = t - bi * (bi + 1) / 2;
     if (tid < 128) {
         const int c = tid & 63, obs = (tid < 64 ? bi : bj) * 64 + c;
-        const int l = obs < N ? obs / n : -1, pt = obs < N ? obs - l * n : 0;
+        int l = -1, pt = 0;
+        if (obs < N) aug_row_decode(obs, nhead, d, l, pt);
         if (tid < 64) la[c] = l; else lb[c] = l;
         for (int k = 0; k < d; ++k) (tid < 64 ? xa : xb)[k][c] = Xraw[(size_t)k * ldx + pt];
         if (tid >= 64) {
@@ -323,7 +352,9 @@ __global__ __launch_bounds__(256) void aug_llgrad_tile_kernel(const double* __re
         if (a < b || a >= N || b >= N) continue;
         const double G = aa * ab[cc] - Kinv[(size_t)b * ldk + a];
         double dl[AUG_MAX_D];
-        const double v = aug_entry_dlam(kern, amp2, d, il, &xb[0][cc], 64, &xa[0][r], 64, lb[cc], la[r], dl);
+        const bool sw = la[r] < lb[cc];
+        const double v = aug_entry_dlam(kern, amp2, d, il, sw ? &xa[0][r] : &xb[0][cc], 64, sw ? &xb[0][cc] : &xa[0][r], 64,
+                                        sw ? la[r] : lb[cc], sw ? lb[cc] : la[r], dl);
         const double w = (a == b) ? 0.5 * G : G;
 #pragma unroll
         for (int m = 0; m < AUG_MAX_D; ++m)
@@ -352,7 +383,7 @@ __global__ __launch_bounds__(256) void aug_llgrad_tile_kernel(const double* __re
 // array of the few-candidates path).  One training observation per thread; padding rows = 0.
 // aug_kstar_body: the work of one workgroup = 256 rows (blockIdx.x) of candidate tile `tile` under one parameter set; out is that
 // tile's slab.
-__device__ __forceinline__ void aug_kstar_body(const double* __restrict__ Xraw, int ldx, int d, int n, int N, int Np,
+__device__ __forceinline__ void aug_kstar_body(const double* __restrict__ Xraw, int ldx, int d, int nhead, int N, int Np,
                                                const double* __restrict__ Craw, int Mp, int kern, double amp2,
                                                const double* __restrict__ invlam, double* __restrict__ out, int BN, int tile) {
     extern __shared__ double sm[];                           // cs[d][BN] | xt[d][256] | il[d]
@@ -361,7 +392,8 @@ __device__ __forceinline__ void aug_kstar_body(const double* __restrict__ Xraw, 
     double* il = xt + d * 256;
     const int tid = threadIdx.x, c0 = tile * BN;
     const int row = blockIdx.x * 256 + tid;
-    const int l = row < N ? row / n : -1, pt = row < N ? row - l * n : 0;
+    int l = -1, pt = 0;
+    if (row < N) aug_row_decode(row, nhead, d, l, pt);
     for (int idx = tid; idx < d * BN; idx += 256) cs[idx] = Craw[(size_t)(idx / BN) * Mp + c0 + (idx % BN)];
     for (int k = 0; k < d; ++k) xt[k * 256 + tid] = Xraw[(size_t)k * ldx + pt];
     if (tid < d) il[tid] = invlam[tid];
@@ -370,10 +402,10 @@ __device__ __forceinline__ void aug_kstar_body(const double* __restrict__ Xraw, 
     for (int c = 0; c < BN; ++c)
         out[(size_t)row * BN + c] = (l >= 0) ? aug_entry(kern, amp2, d, il, cs + c, BN, xt + tid, 256, 0, l) : 0.0;
 }
-__global__ __launch_bounds__(256) void aug_kstar_kernel(const double* __restrict__ Xraw, int ldx, int d, int n, int N, int Np,
+__global__ __launch_bounds__(256) void aug_kstar_kernel(const double* __restrict__ Xraw, int ldx, int d, int nhead, int N, int Np,
                                                         const double* __restrict__ Craw, int Mp, int kern, double amp2,
                                                         const double* __restrict__ invlam, double* __restrict__ out, int BN) {
-    aug_kstar_body(Xraw, ldx, d, n, N, Np, Craw, Mp, kern, amp2, invlam, out + (size_t)blockIdx.y * Np * BN, BN, (int)blockIdx.y);
+    aug_kstar_body(Xraw, ldx, d, nhead, N, Np, Craw, Mp, kern, amp2, invlam, out + (size_t)blockIdx.y * Np * BN, BN, (int)blockIdx.y);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -247,7 +247,7 @@ static int llgrad_enqueue(boss_gp* g, hipStream_t s, double* sums_out, int bank,
         return BOSS_OK;
     }
     if (g->aug)
-        hipLaunchKernelGGL(aug_llgrad_tile_kernel, dim3(ntiles, 1, nb), dim3(256), 0, s, (const double*)g->Xraw, g->ldx, d, g->npts, N, Np,
+        hipLaunchKernelGGL(aug_llgrad_tile_kernel, dim3(ntiles, 1, nb), dim3(256), 0, s, (const double*)g->Xraw, g->ldx, d, g->nhead, N, Np,
                            g->kernel, (const double*)g->hyp, (const double*)g->invlam, zPar, (const double*)Kinv, ld, (const double*)apart, nch,
                            parts, Bw.sW, zC);
     else

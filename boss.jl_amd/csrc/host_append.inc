@@ -76,9 +76,11 @@ static int gp_grow(boss_gp* g, int Nnew) {
     Ctx* c = g->ctx;
     hipStream_t s = c->stream;
     const int Np = g->Np, d = g->d, nblk2 = Np2 / BLK, ld2 = Np2 + RHS_ROWS;
+    // (a gradient-observation handle keeps its points at a pitch of their own, which ggp_grow_points grows: copied as they are)
+    const int ldx1 = g->aug ? g->ldx : Np, ldx2 = g->aug ? g->ldx : Np2;
     const size_t szA = sizeof(double) * (size_t)ld2 * Np2;
     double* nw[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    const size_t bytes[8] = {sizeof(double) * d * Np2, sizeof(double) * d * Np2, sizeof(double) * Np2, sizeof(double) * Np2,
+    const size_t bytes[8] = {sizeof(double) * d * ldx2, sizeof(double) * d * ldx2, sizeof(double) * Np2, sizeof(double) * Np2,
                              szA, sizeof(double) * nblk2 * 8 * 256, sizeof(double) * nblk2 * BLK * BLK,
                              sizeof(double) * (size_t)Np2 * PRED_RB};
     for (int i = 0; i < 8; ++i)
@@ -99,10 +101,10 @@ static int gp_grow(boss_gp* g, int Nnew) {
     hipError_t e = hipSuccess;
     for (int i = 0; i < 5 && e == hipSuccess; ++i) e = hipMemsetAsync(nw[i], 0, bytes[i], s);
     if (e == hipSuccess)
-        e = hipMemcpy2DAsync(nw[0], sizeof(double) * Np2, g->Xraw, sizeof(double) * Np, sizeof(double) * Np, d,
+        e = hipMemcpy2DAsync(nw[0], sizeof(double) * ldx2, g->Xraw, sizeof(double) * ldx1, sizeof(double) * ldx1, d,
                              hipMemcpyDeviceToDevice, s);
     if (e == hipSuccess)
-        e = hipMemcpy2DAsync(nw[1], sizeof(double) * Np2, g->Xsc, sizeof(double) * Np, sizeof(double) * Np, d,
+        e = hipMemcpy2DAsync(nw[1], sizeof(double) * ldx2, g->Xsc, sizeof(double) * ldx1, sizeof(double) * ldx1, d,
                              hipMemcpyDeviceToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(nw[2], g->y, sizeof(double) * Np, hipMemcpyDeviceToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(nw[3], g->mean, sizeof(double) * Np, hipMemcpyDeviceToDevice, s);
@@ -178,6 +180,49 @@ extern "C" int boss_ngp_reserve(boss_gp_t* g, int N_total) {
     if (!g->gibbs) return fail(BOSS_E_INVALID, "handle was not created by boss_ngp_create");
     return reserve_locked_entry(g, N_total);
 }
+// The points of a gradient-observation handle, Xraw / Xsc [d][ldx]: their pitch grows in steps of 64 points (the Gram and K*
+// kernels read whole 64-point groups).  Caller holds the context lock; the handle owns its arrays (gp_own).
+static int ggp_grow_points(boss_gp* g, int npts_new) {
+    const int ldx2 = round_up(npts_new, 64);
+    if (ldx2 <= g->ldx) return BOSS_OK;
+    hipStream_t s = g->ctx->stream;
+    const int d = g->d, ldx = g->ldx;
+    const size_t bytes = sizeof(double) * d * ldx2;
+    double* nw[2] = {nullptr, nullptr};
+    if (dev_malloc((void**)&nw[0], bytes) != hipSuccess || dev_malloc((void**)&nw[1], bytes) != hipSuccess) {
+        if (nw[0]) (void)hipFree(nw[0]);
+        return fail(BOSS_E_ALLOC, "device allocation failed while growing the posterior handle");
+    }
+    double* old[2] = {g->Xraw, g->Xsc};
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < 2 && e == hipSuccess; ++i) {
+        e = hipMemsetAsync(nw[i], 0, bytes, s);
+        if (e == hipSuccess)
+            e = hipMemcpy2DAsync(nw[i], sizeof(double) * ldx2, old[i], sizeof(double) * ldx, sizeof(double) * ldx, d, hipMemcpyDeviceToDevice, s);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {                                   // the handle keeps its old arrays
+        (void)hipStreamSynchronize(s);
+        (void)hipFree(nw[0]);
+        (void)hipFree(nw[1]);
+        return fail(BOSS_E_NO_DEVICE, std::string("growing the posterior handle: ") + hipGetErrorString(e));
+    }
+    (void)hipFree(old[0]);
+    (void)hipFree(old[1]);
+    g->Xraw = nw[0];
+    g->Xsc = nw[1];
+    g->ldx = ldx2;
+    return BOSS_OK;
+}
+
+// The same for a gradient-observation handle, counted in POINTS: n_points_total (1 + d) rows and the points' own pitch; follow with
+// boss_ggp_update.
+extern "C" int boss_ggp_reserve(boss_gp_t* g, int n_points_total) {
+    if (!g || n_points_total < 1) return fail(BOSS_E_INVALID, "bad arguments");
+    if (!g->aug) return fail(BOSS_E_INVALID, "handle was not created by boss_ggp_create");
+    if ((long long)n_points_total * (1 + g->d) > MAX_ROWS) return fail(BOSS_E_INVALID, "augmented system too large (n (1 + d) > 46080)");
+    return reserve_locked_entry(g, n_points_total * (1 + g->d));
+}
 static int reserve_locked_entry(boss_gp* g, int N_total) {
     Ctx* c = g->ctx;
     HIPCHK(hipSetDevice(c->device));
@@ -185,6 +230,10 @@ static int reserve_locked_entry(boss_gp* g, int N_total) {
     if (g->pending) (void)gp_finish(g, nullptr);
     int rc = gp_grow(g, N_total);
     if (rc) return rc;
+    if (g->aug) {
+        rc = ggp_grow_points(g, N_total / (1 + g->d));
+        if (rc) return rc;
+    }
     g->fitted = false;
     ++g->epoch;
     g->append_calls = 0;
@@ -486,6 +535,89 @@ extern "C" int boss_ngp_append(boss_gp_t* g, int n_new, const double* X_new, con
             hipLaunchKernelGGL(gibbs_gram_kernel, dim3(4 * kb + 3, 1, 1), dim3(256), 0, s, (const double*)g->Xraw,
                                (const double*)g->lamX, (const double*)g->ampX, (const double*)g->noiseX, (size_t)0, (size_t)0, d, N1,
                                Np, g->A, ld, (size_t)0, kb * (2 * kb + 1));
+            for (int k = 0; k < kb; ++k) {
+                hipLaunchKernelGGL(potrf_trsm_kernel, dim3(8, 1, 1), dim3(TRSM_THREADS), 0, s, g->A, ld, (size_t)0, k, g->inv16, (size_t)0,
+                                   kb * BLK);
+                hipLaunchKernelGGL(potrf_rowupd_kernel, dim3(4 * (kb - k) + 1), dim3(256), 0, s, g->A, ld, k, kb, Np);
+            }
+            hipLaunchKernelGGL(potrf_diag_kernel, dim3(1, 1, 1), dim3(DIAG_THREADS), DIAG_LDS_BYTES, s, g->A, ld, (size_t)0, kb,
+                               g->inv16, (size_t)0, g->info, (unsigned long long*)nullptr, 0ull);
+            hipLaunchKernelGGL(potrf_trsm_kernel, dim3(1, 1, 1), dim3(TRSM_THREADS), 0, s, g->A, ld, (size_t)0, kb, g->inv16, (size_t)0,
+                               Np);
+        }
+        dinv_eager(g);
+        hipLaunchKernelGGL(potrf_logdet_kernel, dim3(1, 1, 1), dim3(LOGDET_THREADS), 0, s, g->A, ld, (size_t)0, N1, Np, g->scal,
+                           (double*)nullptr, (const int*)nullptr, (unsigned long long*)nullptr, 0ull, 0ull);
+        HIPCHK(hipMemcpyAsync(g->host_res, g->scal, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(&g->host_res[2], g->info, sizeof(int), hipMemcpyDeviceToHost, s));
+    }
+    return update_finish(g, 0, logpdf_out);
+}
+
+// augment_dataset! (src/types/problem.jl:191-198) followed by the posterior at unchanged hyper-parameters for a gradient-observation
+// model.  X_new d×n_new, y_new n_new, dY_new d×n_new column-major.  The reference's ordering [y; ∂_1 y; …; ∂_d y] would put new rows
+// inside every block; the handle's own ordering (aug_row_decode, gram_kernels.hpp) puts the 1 + d rows of every appended point at
+// the end instead, a symmetric permutation the posterior does not see.  The leading block of the factor then survives, and the
+// append runs as the other models' does: the block rows that hold new rows are rebuilt (append_locked's condition and sweep, the
+// Gram tiles from aug_gram_kernel), or the grown arrays are factorised again on the device where most of the matrix is new.
+// Nothing of the handle's data travels to the host and the hyper-parameters staged on the device by the last update are the ones
+// used, verbatim.
+extern "C" int boss_ggp_append(boss_gp_t* g, int n_new, const double* X_new, const double* y_new, const double* dY_new, double* logpdf_out) {
+    if (!g || !X_new || !y_new || !dY_new || n_new < 1) return fail(BOSS_E_INVALID, "need a handle, n_new >= 1 and non-NULL X_new, y_new, dY_new");
+    if (!g->aug) return fail(BOSS_E_INVALID, "handle was not created by boss_ggp_create");
+    Ctx* c = g->ctx;
+    const int d = g->d, n = n_new;
+    if ((long long)(g->npts + n) * (1 + d) > MAX_ROWS) return fail(BOSS_E_INVALID, "augmented system too large (n (1 + d) > 46080)");
+    HIPCHK(hipSetDevice(c->device));
+    std::lock_guard<std::mutex> lk(c->mtx);
+    int rc = gp_settle(g, "handle has no valid factorisation (its hyper-parameters are the ones re-used)");
+    if (rc) return rc;
+    hipStream_t s = c->stream;
+    const int N0 = g->N, N1 = N0 + n * (1 + d), n0 = g->npts;
+    const int Np_before = g->Np;
+    rc = gp_grow(g, N1);                                     // (a member of a batch-fitted set leaves it here: gp_own)
+    if (rc) return rc;
+    rc = ggp_grow_points(g, n0 + n);
+    if (rc) return rc;
+    g->fitted = false;
+    g->have_lt = false;
+    ++g->factor_gen;
+    g->have_dinv = false;
+    g->have_winv = false;
+    g->few_calls = 0;
+    g->append_path = 0;
+    {
+        std::vector<double> xb, yb((size_t)n * (1 + d));
+        pack_points(xb, X_new, d, n, n, nullptr);
+        for (int j = 0; j < n; ++j) {                        // the rows of an appended point: [y_j, ∂y_j/∂x_1 … ∂y_j/∂x_d]
+            yb[(size_t)j * (1 + d)] = y_new[j];
+            for (int l = 0; l < d; ++l) yb[(size_t)j * (1 + d) + 1 + l] = dY_new[(size_t)j * d + l];
+        }
+        HIPCHK(hipMemcpy2DAsync(g->Xraw + n0, sizeof(double) * g->ldx, xb.data(), sizeof(double) * n, sizeof(double) * n, d,
+                                hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(g->y + N0, yb.data(), sizeof(double) * yb.size(), hipMemcpyHostToDevice, s));
+        HIPCHK(hipStreamSynchronize(s));       // staging buffers go out of scope
+    }
+    g->N = N1;
+    g->npts = n0 + n;
+    // the block rows to (re)build and the switch to a plain re-factorisation: append_locked's
+    const int kb0 = N0 / BLK, kb1 = (g->Np != Np_before) ? g->nblk - 1 : (N1 - 1) / BLK;
+    if (kb1 - kb0 + 1 > 4 || kb1 - kb0 + 1 >= g->nblk) {
+        g->append_path = 2;
+        rc = factor_enqueue(g);
+        if (rc) return rc;
+    } else {
+        g->append_path = 1;
+        const int Np = g->Np, ld = g->ld;
+        dinv_join(g);
+        HIPCHK(hipMemsetAsync(g->info, 0, sizeof(int), s));
+        for (int kb = kb0; kb <= kb1; ++kb) {
+            hipLaunchKernelGGL(rhs_rows_kernel, dim3(1, 1, 1), dim3(BLK), 0, s, g->A, ld, (size_t)0, N1, Np, g->y, g->mean,
+                               (size_t)0, kb * BLK, (int*)nullptr);
+            // 128 rows × columns 0 … (kb+1)·128 − 1: the 4·kb + 3 tiles from triangular tile index kb (2 kb + 1), a full build's arithmetic
+            hipLaunchKernelGGL(aug_gram_kernel, dim3(4 * kb + 3, 1, 1), dim3(256), 0, s, (const double*)g->Xraw, g->ldx, d, g->nhead, N1,
+                               Np, g->kernel, (const double*)g->hyp, (const double*)g->invlam, (size_t)0, g->A, ld, (size_t)0,
+                               kb * (2 * kb + 1));
             for (int k = 0; k < kb; ++k) {
                 hipLaunchKernelGGL(potrf_trsm_kernel, dim3(8, 1, 1), dim3(TRSM_THREADS), 0, s, g->A, ld, (size_t)0, k, g->inv16, (size_t)0,
                                    kb * BLK);

@@ -519,7 +519,7 @@ static int ggp_loglike_batch_impl(int device, int kernel, int d, int n, const do
     auto gram = [&](const ModelBatchGramArgs& a) {
         const long long t64 = Np / 64;
         hipLaunchKernelGGL(aug_gram_kernel, dim3((unsigned)(t64 * (t64 + 1) / 2), 1, a.cnt), dim3(256), 0, c->stream, a.pts, ldx, d, n, N, Np,
-                           kernel, a.par + d, a.par, par_doubles, a.A, a.ld, a.bstride);
+                           kernel, a.par + d, a.par, par_doubles, a.A, a.ld, a.bstride, 0);
     };
     ModelBatchGrad G;
     G.out_doubles = (size_t)d + 3;
@@ -528,6 +528,7 @@ static int ggp_loglike_batch_impl(int device, int kernel, int d, int n, const do
         v->d = d;
         v->aug = true;
         v->npts = n;
+        v->nhead = n;
         v->ldx = ldx;
         v->Xraw = const_cast<double*>(pts_dev);
         v->invlam = par;
@@ -811,6 +812,7 @@ static int fit_batch_run(Ctx* c, const FitBatchSpec& sp, const std::function<hip
         g->aug = sp.aug;
         g->gibbs = sp.gibbs;
         g->npts = sp.npts;
+        g->nhead = sp.npts;
         g->ldx = sp.ldx;
         g->Xraw = L.pts;
         g->y = L.y;
@@ -959,7 +961,7 @@ extern "C" int boss_ggp_fit_batch(int device, int kernel, int d, int n, const do
                                  const long long t64 = Np / 64;
                                  hipLaunchKernelGGL(aug_gram_kernel, dim3((unsigned)(t64 * (t64 + 1) / 2), 1, cnt), dim3(256), 0, c->stream,
                                                     (const double*)L.pts, ldx, d, n, N, Np, kernel, (const double*)(L.par + (size_t)b0 * L.sPar + d),
-                                                    (const double*)(L.par + (size_t)b0 * L.sPar), L.sPar, L.A + (size_t)b0 * L.sA, L.ld, L.sA);
+                                                    (const double*)(L.par + (size_t)b0 * L.sPar), L.sPar, L.A + (size_t)b0 * L.sA, L.ld, L.sA, 0);
                              });
         return hipSuccess;
     };

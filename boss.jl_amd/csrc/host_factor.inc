@@ -677,6 +677,7 @@ static int gp_create_common(int device, int kernel, int d, int npts, int N, cons
     g->ld = g->Np + RHS_ROWS;
     g->aug = aug;
     g->npts = npts;
+    g->nhead = npts;
     g->ldx = aug ? round_up(npts, 64) : g->Np;
     const size_t Np = g->Np, ldx = g->ldx;
 #define GALLOC(ptr, bytes)                                        \
@@ -1091,8 +1092,8 @@ static int factor_enqueue(boss_gp* g, RiderReq* rider) {
         ProfScope ps(c, "gram");
         const long long t64 = g->Np / 64;
         hipLaunchKernelGGL(aug_gram_kernel, dim3((unsigned)(t64 * (t64 + 1) / 2)), dim3(256), 0, s, (const double*)g->Xraw, g->ldx,
-                           g->d, g->npts, g->N, g->Np, g->kernel, (const double*)g->hyp, (const double*)g->invlam, (size_t)0, g->A,
-                           g->ld, (size_t)0);
+                           g->d, g->nhead, g->N, g->Np, g->kernel, (const double*)g->hyp, (const double*)g->invlam, (size_t)0, g->A,
+                           g->ld, (size_t)0, 0);
     } else if (g->gibbs) {
         ProfScope ps(c, "gram");
         const int t64 = g->Np / 64;
@@ -1237,68 +1238,6 @@ extern "C" int boss_ggp_update(boss_gp_t* g, const double* lengthscale, double a
     rc = factor_enqueue(g);
     if (rc) return rc;
     return update_finish(g, flags, logpdf_out);
-}
-
-// The end of the rebuild-append (boss_ggp_append): g2, a fresh handle on the joined data whose update returned rc, gives its contents to g when
-// that update succeeded (the caller's pointer stays valid) and goes either way.
-static int replace_with_rebuilt(boss_gp* g, boss_gp* g2, int rc) {
-    if (!rc) {
-        std::lock_guard<std::mutex> lk(g->ctx->mtx);
-        std::swap(*g, *g2);
-    }
-    boss_gp_free(g2);
-    return rc;
-}
-
-// augment_dataset! (src/types/problem.jl:191-198) followed by the posterior at unchanged hyper-parameters for a gradient-observation
-// model.  New points land in the MIDDLE of every block of the observation ordering [y; ∂_1 y; …; ∂_d y], so nothing of the factor
-// survives: like the reference, the augmented system is rebuilt and factorised — on a fresh handle whose contents then replace gp's
-// (the caller's pointer stays valid).  X_new d×n_new, y_new n_new, dY_new d×n_new column-major.
-extern "C" int boss_ggp_append(boss_gp_t* g, int n_new, const double* X_new, const double* y_new, const double* dY_new, double* logpdf_out) {
-    if (!g || !X_new || !y_new || !dY_new || n_new < 1) return fail(BOSS_E_INVALID, "need a handle, n_new >= 1 and non-NULL X_new, y_new, dY_new");
-    if (!g->aug) return fail(BOSS_E_INVALID, "handle was not created by boss_ggp_create");
-    Ctx* c = g->ctx;
-    const int d = g->d, n = g->npts, ldx = g->ldx;
-    if ((long long)(n + n_new) * (1 + d) > MAX_ROWS) return fail(BOSS_E_INVALID, "augmented system too large (n (1 + d) > 46080)");
-    std::vector<double> Xd((size_t)d * ldx), yt((size_t)g->N);
-    std::vector<double> lam(d);
-    double amp, sig, sgd;
-    {
-        HIPCHK(hipSetDevice(c->device));
-        std::lock_guard<std::mutex> lk(c->mtx);
-        int rc0 = gp_settle(g, "handle has no valid factorisation (its hyper-parameters are the ones re-used)");
-        if (rc0) return rc0;
-        HIPCHK(hipMemcpyAsync(Xd.data(), g->Xraw, sizeof(double) * Xd.size(), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipMemcpyAsync(yt.data(), g->y, sizeof(double) * yt.size(), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        for (int k = 0; k < d; ++k) lam[k] = 1.0 / g->host_par[k] - MIN_PARAM_VALUE;
-        amp = std::sqrt(g->host_par[d]) - MIN_PARAM_VALUE;
-        sig = std::sqrt(g->host_par[d + 1]) - MIN_PARAM_VALUE;
-        sgd = std::sqrt(g->host_par[d + 2]) - MIN_PARAM_VALUE;
-    }
-    const int nt = n + n_new;
-    std::vector<double> X((size_t)d * nt), y(nt), dY((size_t)d * nt);
-    for (int j = 0; j < n; ++j) {
-        y[j] = yt[j];
-        for (int k = 0; k < d; ++k) {
-            X[(size_t)j * d + k] = Xd[(size_t)k * ldx + j];
-            dY[(size_t)j * d + k] = yt[(size_t)n * (1 + k) + j];
-        }
-    }
-    for (int j = 0; j < n_new; ++j) {
-        y[n + j] = y_new[j];
-        for (int k = 0; k < d; ++k) {
-            X[(size_t)(n + j) * d + k] = X_new[(size_t)j * d + k];
-            dY[(size_t)(n + j) * d + k] = dY_new[(size_t)j * d + k];
-        }
-    }
-    // (the 1e-8 the update adds to every parameter was taken off above: up to rounding the same staged values come out again)
-    for (int k = 0; k < d; ++k) lam[k] = std::max(lam[k], 0.0);
-    boss_gp_t* g2 = nullptr;
-    int rc = boss_ggp_create(c->logical, g->kernel, d, nt, X.data(), y.data(), dY.data(), &g2);
-    if (rc) return rc;
-    rc = boss_ggp_update(g2, lam.data(), std::max(amp, 0.0), std::max(sig, 0.0), std::max(sgd, 0.0), 0, logpdf_out);
-    return replace_with_rebuilt(g, g2, rc);
 }
 
 // finite_nongp + logpdf / posterior (nonstationary_gp.jl:153-196, :237-245): the caller evaluates its latent

@@ -283,7 +283,7 @@ static int predict_enqueue(boss_gp* g, const boss_cand* cd, const double* mean_s
         if (!use_winv) (void)hipMemsetAsync(ssmz, 0, sizeof(double) * 64 * ftiles, s);
         if (g->aug)
             hipLaunchKernelGGL(aug_kstar_kernel, dim3(g->Np / 256, ftiles), dim3(256), aug_lds, s, (const double*)g->Xraw, g->ldx,
-                               g->d, g->npts, g->N, g->Np, (const double*)cd->Craw, Mp, g->kernel, g->amp2,
+                               g->d, g->nhead, g->N, g->Np, (const double*)cd->Craw, Mp, g->kernel, g->amp2,
                                (const double*)g->invlam, R, 32);
         else if (g->gibbs)
             gibbs_kstar32_launch(g, cd, clam_dev, camp_dev, ftiles, R, s);
@@ -372,7 +372,7 @@ static int predict_enqueue(boss_gp* g, const boss_cand* cd, const double* mean_s
         double* V = (double*)c->vscratch.p;
         if (g->aug)
             hipLaunchKernelGGL(aug_kstar_kernel, dim3(g->Np / 256, tiles), dim3(256), aug_lds, s, (const double*)g->Xraw, g->ldx, g->d,
-                               g->npts, g->N, g->Np, (const double*)cd->Craw, Mp, g->kernel, g->amp2, (const double*)g->invlam, V, BN);
+                               g->nhead, g->N, g->Np, (const double*)cd->Craw, Mp, g->kernel, g->amp2, (const double*)g->invlam, V, BN);
         else if (BN == 32)
             gibbs_kstar32_launch(g, cd, clam_dev, camp_dev, tiles, V, s);
         else
@@ -444,7 +444,7 @@ static bool predict_set_ok(int n, boss_gp_t* const* gps, const boss_cand* cd, bo
         if (!g || g->aug != g0->aug || g->gibbs != g0->gibbs || !g->fitted || g->pending || g->ctx != cd->ctx || g->N != g0->N || g->Np != g0->Np ||
             g->ld != g0->ld || g->d != g0->d || g->d != cd->d || g->kernel != g0->kernel || g->discrete != g0->discrete)
             return false;
-        if (model && (g->npts != g0->npts || g->ldx != g0->ldx)) return false;
+        if (model && (g->npts != g0->npts || g->ldx != g0->ldx || g->nhead != g0->nhead)) return false;
     }
     return true;
 }
@@ -561,7 +561,7 @@ static int predict_set_enqueue(int n, boss_gp_t* const* gps, const boss_cand* cd
         ++c->set_pre_launches;
         if (g0->aug)
             hipLaunchKernelGGL(aug_kstar_set_kernel, dim3(Np / 256, tiles, cnt), dim3(256), sizeof(double) * ((size_t)d * (G::BN + 256) + d), s,
-                               g0->ldx, d, g0->npts, g0->N, Np, (const double*)cd->Craw, Mp, g0->kernel, dsets + i0,
+                               g0->ldx, d, g0->nhead, g0->N, Np, (const double*)cd->Craw, Mp, g0->kernel, dsets + i0,
                                (double*)c->vscratch.p, (int)G::BN);
         else
             hipLaunchKernelGGL(gibbs_kstar_set_kernel, dim3(Np / 256, tiles, cnt), dim3(256), sizeof(double) * (2 * d * 32 + 32 + 2 * 8 * 256), s,
@@ -1002,7 +1002,7 @@ static int grad_enqueue(boss_gp* g, const boss_cand* cd, const double* mean_s_de
             if (rc) return rc;
             apart = (double*)c->few.p;                       // the forward pass's residuals are dead by now
         }
-        hipLaunchKernelGGL(aug_grad_accum_kernel, dim3(tiles, rsp), dim3(256), 0, s, (const double*)slabs, (const double*)g->avec, Np, g->npts,
+        hipLaunchKernelGGL(aug_grad_accum_kernel, dim3(tiles, rsp), dim3(256), 0, s, (const double*)slabs, (const double*)g->avec, Np, g->npts, g->nhead,
                            (const double*)g->Xraw, g->ldx, (const double*)cd->Craw, d, cd->Mp, M, g->kernel, g->amp2, (const double*)g->invlam,
                            dmu, dvar, apart);
         if (rsp > 1)
@@ -1360,7 +1360,7 @@ static int grad_set_enqueue(int n, boss_gp_t* const* gps, const boss_cand* cd, c
             hipLaunchKernelGGL(gibbs_grad_fold_set_kernel, dim3(tiles, cnt), dim3(256), 0, s, gsets + i0, (const double*)part, rsplit, d, M);
         } else if (g0->aug) {
             rsplit = std::max(1, std::min(rsplit, (g0->npts + 63) / 64));
-            hipLaunchKernelGGL(aug_grad_accum_set_kernel, dim3(tiles, rsplit, cnt), dim3(256), 0, s, gsets + i0, (const double*)slabs, Np, g0->npts,
+            hipLaunchKernelGGL(aug_grad_accum_set_kernel, dim3(tiles, rsplit, cnt), dim3(256), 0, s, gsets + i0, (const double*)slabs, Np, g0->npts, g0->nhead,
                                g0->ldx, (const double*)cd->Craw, d, Mp, M, g0->kernel, rsplit > 1 ? part : nullptr);
             if (rsplit > 1)
                 hipLaunchKernelGGL(aug_grad_finalize_set_kernel, dim3(tiles, cnt), dim3(32), 0, s, gsets + i0, (const double*)part, rsplit, d, M);

@@ -43,7 +43,13 @@ static int track_rebuild(boss_track* t, const boss_cand* cd) {
     if (rc) return rc;
     HIPCHK(hipMemcpy2DAsync(t->V, sizeof(double) * (size_t)t->Ncap * 32, c->vscratch.p, sizeof(double) * (size_t)g->Np * 32,
                             sizeof(double) * (size_t)g->Np * 32, t->tiles, hipMemcpyDeviceToDevice, s));
-    if (!t->gibbs) HIPCHK(hipMemcpyAsync(t->Csc, c->csc.p, sizeof(double) * (size_t)t->d * t->Mp, hipMemcpyDeviceToDevice, s));
+    if (t->aug) {
+        HIPCHK(hipMemcpyAsync(t->Csc, cd->Craw, sizeof(double) * (size_t)t->d * t->Mp, hipMemcpyDeviceToDevice, s));
+        hipLaunchKernelGGL(aug_track_var_kernel, dim3(t->tiles), dim3(256), 0, s, (const double*)t->V, t->Ncap, g->N, t->M, g->amp2, t->var);
+        HIPCHK(hipGetLastError());
+    } else if (!t->gibbs) {
+        HIPCHK(hipMemcpyAsync(t->Csc, c->csc.p, sizeof(double) * (size_t)t->d * t->Mp, hipMemcpyDeviceToDevice, s));
+    }
     t->N = g->N;
     t->epoch = g->epoch;
     return BOSS_OK;
@@ -190,6 +196,47 @@ extern "C" int boss_ngp_track_create_lat(boss_gp_t* g, const boss_cand_t* cand, 
     return ngp_track_create(g, cand, nullptr, nullptr, lat, mean_Xs, out);
 }
 
+// Tracked candidates of a gradient-observation posterior: the V slabs come from the model's own prediction path, the raw
+// candidates stay resident so aug_track_append_kernel can form the cross-covariance of every appended row.
+extern "C" int boss_ggp_track_create(boss_gp_t* g, const boss_cand_t* cand, boss_track_t** out) {
+    if (!out) return fail(BOSS_E_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!g || !cand) return fail(BOSS_E_INVALID, "NULL argument");
+    if (!g->aug) return fail(BOSS_E_INVALID, "handle was not created by boss_ggp_create");
+    if (cand->ctx != g->ctx || cand->d != g->d) return fail(BOSS_E_INVALID, "candidates and posterior must share device and x_dim");
+    Ctx* c = g->ctx;
+    HIPCHK(hipSetDevice(c->device));
+    std::lock_guard<std::mutex> lk(c->mtx);
+    int rc = gp_settle(g);
+    if (rc) return rc;
+    boss_track* t = new boss_track();
+    t->ctx = c;
+    t->gp = g;
+    t->aug = true;
+    t->d = g->d;
+    t->M = cand->M;
+    t->Mp = cand->Mp;
+    t->tiles = (cand->M + 31) / 32;
+    if (dev_malloc((void**)&t->Csc, sizeof(double) * (size_t)t->d * t->Mp) != hipSuccess ||
+        dev_malloc((void**)&t->mu, sizeof(double) * t->M) != hipSuccess ||
+        dev_malloc((void**)&t->var, sizeof(double) * t->M) != hipSuccess ||
+        dev_malloc((void**)&t->mean, sizeof(double) * t->M) != hipSuccess) {
+        (void)hipGetLastError();
+        track_release(t);
+        return fail(BOSS_E_ALLOC, "device allocation failed");
+    }
+    rc = track_rebuild(t, cand);
+    hipError_t e = hipStreamSynchronize(c->stream);
+    if (rc == BOSS_OK && e != hipSuccess) rc = fail(BOSS_E_NO_DEVICE, hipGetErrorString(e));
+    if (rc) {
+        (void)hipGetLastError();
+        track_release(t);
+        return rc;
+    }
+    *out = t;
+    return BOSS_OK;
+}
+
 extern "C" void boss_track_free(boss_track_t* t) {
     if (!t) return;
     if (t->ctx) {
@@ -210,7 +257,11 @@ static int track_sync_locked(boss_track* t) {
     hipStream_t s = t->ctx->stream;
     for (int N0 = t->N; N0 < g->N; N0 += TRACK_ROWS) {
         const int n = std::min(TRACK_ROWS, g->N - N0);
-        if (t->gibbs)
+        if (t->aug)
+            hipLaunchKernelGGL(aug_track_append_kernel, dim3(t->tiles), dim3(256), sizeof(double) * (t->d * 32 + t->d), s, (const double*)g->A,
+                               g->ld, g->Np, N0, n, t->V, t->Ncap, (const double*)g->Xraw, g->ldx, g->nhead, (const double*)t->Csc, t->d,
+                               t->Mp, t->M, g->kernel, g->amp2, (const double*)g->invlam, t->mu, t->var);
+        else if (t->gibbs)
             hipLaunchKernelGGL(gibbs_track_append_kernel, dim3(t->tiles), dim3(256), sizeof(double) * (2 * t->d + 1) * 32, s,
                                (const double*)g->A, g->ld, g->Np, N0, n, t->V, t->Ncap, (const double*)g->Xraw, (const double*)g->lamX,
                                (const double*)g->ampX, g->Np, (const double*)t->Csc, (const double*)t->Clam, (const double*)t->Camp,
@@ -246,6 +297,8 @@ extern "C" int boss_track_moments(boss_track_t* t, int first, int count, double*
     HIPCHK(hipMemcpyAsync(mu, t->mu + first, sizeof(double) * count, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(var, t->var + first, sizeof(double) * count, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
+    if (t->aug)                                              // the reference's max(0, ·); the resident value stays unclipped
+        for (int i = 0; i < count; ++i) var[i] = std::max(0.0, var[i]);
     return BOSS_OK;
 }
 
@@ -289,6 +342,7 @@ extern "C" int boss_acq_ei_tracks(int P, int S, boss_track_t* const* tracks, con
             }
             (void)hipMemcpyAsync(dmu + (size_t)p * M, t->mu, sizeof(double) * M, hipMemcpyDeviceToDevice, s);
             (void)hipMemcpyAsync(dvar + (size_t)p * M, t->var, sizeof(double) * M, hipMemcpyDeviceToDevice, s);
+            if (t->aug) hipLaunchKernelGGL(clip_nonneg_kernel, dim3((M + 255) / 256), dim3(256), 0, s, dvar + (size_t)p * M, M);
         }
         if (sm + 1 < S)
             hipLaunchKernelGGL(ei_accumulate_kernel, dim3((M + 255) / 256), dim3(256), 0, s, dmu, dvar, M, M, par, dcoef, dymax,

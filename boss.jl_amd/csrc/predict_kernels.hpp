@@ -263,11 +263,11 @@ __global__ __launch_bounds__(G::NTHREADS) __attribute__((amdgpu_waves_per_eu(1, 
 // reads: grid = (256-row blocks, candidate tiles, posteriors).  The candidates are shared; the points (the members of one fit share
 // them, the outputs of a model each bring their own copy), 1/λ and α² (gradient model), λ(X), α(X) and the latent values at the
 // candidates (nonstationary model) come from the member's descriptor.
-__global__ __launch_bounds__(256) void aug_kstar_set_kernel(int ldx, int d, int n, int N, int Np,
+__global__ __launch_bounds__(256) void aug_kstar_set_kernel(int ldx, int d, int nhead, int N, int Np,
                                                             const double* __restrict__ Craw, int Mp, int kern,
                                                             const PredSet* __restrict__ sets, double* __restrict__ Vscratch, int BN) {
     const PredSet ps = sets[blockIdx.z];
-    aug_kstar_body(ps.Xraw, ldx, d, n, N, Np, Craw, Mp, kern, ps.amp2, ps.invlam,
+    aug_kstar_body(ps.Xraw, ldx, d, nhead, N, Np, Craw, Mp, kern, ps.amp2, ps.invlam,
                    Vscratch + ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * Np * BN, BN, (int)blockIdx.y);
 }
 __global__ __launch_bounds__(256) void gibbs_kstar_set_kernel(int d, int N, int Np, const double* __restrict__ C, int Mp,

@@ -7,8 +7,9 @@ Every evaluated point contributes its value and its gradient, so n points give a
   mean_and_cov / cov                     -> boss_ggp_predict_cov
   data_loglike_batch (`loglike.(samples)`) -> boss_ggp_loglike_batch (all samples of an output in one call)
   data_loglike_grad_batch (a round of OptimizationMAP) -> boss_ggp_loglike_grad_batch (values and gradients, one call per output)
-The acquisition maximizers (HipBatchAM, …) take these posteriors unchanged; append has its own entry point
-(boss_ggp_append).
+  augment_dataset! at fixed parameters   -> boss_ggp_append (block rows of the factor, on the device), boss_ggp_reserve
+  SequentialBatchAM on fixed candidates  -> gradient_sequential_batch (boss_ggp_track_create + boss_acq_ei_tracks)
+The acquisition maximizers (HipBatchAM, …) take these posteriors unchanged.
 """
 from __future__ import annotations
 
@@ -90,8 +91,96 @@ class HipGradientGPPosteriorSlice(HipGaussianProcessPosteriorSlice):
 
     def append(self, x, y, dy) -> float:
         """augment_dataset! (src/types/problem.jl:191-198) on the fitted slice: new points with values and gradients, hyper-parameters
-        unchanged (boss_ggp_append: the augmented system is rebuilt and factorised, as in the reference)."""
+        unchanged (boss_ggp_append: the new points' rows go to the end of the handle's ordering, the block rows of the factor that
+        hold them are updated on the device)."""
         return self.gp.append(x, y, dy)
+
+    def reserve(self, extra_points: int) -> float:
+        """Storage for `extra_points` further points, so their appends re-allocate nothing (boss_ggp_reserve), then the update under
+        the slice's own parameters that a reserve asks for.  Returns the logpdf."""
+        g, p, i = self.gp, self.params, self.idx
+        g.reserve(points=g.n + int(extra_points))
+        return g.update(p.lengthscales[:, i], p.amplitudes[i], p.noise_std[i], p.grad_noise_std[i])
+
+    def track(self, cand: api.Candidates, Xs=None) -> api.GradTrack:
+        """The slice's resident state at the candidates `cand` (api.GradTrack); Xs, the same candidates as an array, is taken for
+        symmetry with the other models' slices and not read."""
+        return api.GradTrack(self.gp, cand)
+
+
+# Which way an append goes is decided in the library (boss_ggp_append): block rows where at most four 128-row block rows hold new rows,
+# a re-factorisation of the resident data on the device otherwise.  Measured on an MI355X (tools/ggp_append_times.py, one process per
+# shape, p50 of 20 single-point appends after a reserve, ms; the rebuild timed on the previous commit's library; DESIGN.md §4.2,
+# profiles/ggp_append.jsonl):
+#   rows   block rows | re-factorisation on the device | the previous commit's rebuild     track extension | prediction
+#   1017   0.247      | 0.340                          | 1.341                             0.085           | 0.215
+#   4095   0.648      | 1.307                          | 3.151                             0.224           | 0.923
+#   9216   1.405      | 7.671                          | 9.628                             0.483           | 3.856
+#   1024 (d = 3)  0.230 | 0.332                        | 1.528                             0.050           | 0.206
+# The block-row path is the fastest at every measured shape, so no shape is routed to the re-factorisation by a measured boundary.
+def gradient_sequential_batch(posts: Sequence[Sequence[HipGradientGPPosteriorSlice]], Xs, batch_size: int, fit_coefs, y_max=None, Y=None,
+                              valid_mask=None) -> np.ndarray:
+    """SequentialBatchAM (src/acquisition_maximizers/batch.jl:26-38) over the fixed candidates Xs d×M for the S sampled
+    gradient-observation posteriors posts[s][i]: `batch_size` times the arg-max of EI × feasibility is selected by one
+    boss_acq_ei_tracks call, a speculative observation is appended to every slice, and the acquisition is re-evaluated on the
+    extended tracks.
+
+    The reference's own SequentialBatchAM cannot run on GradientData: speculative_evaluation! calls augment_dataset!(problem, x, y)
+    without a Jacobian (batch.jl:32-37), while augment_dataset(::GradientData, x, results::Tuple) unpacks two elements
+    (gradient_data.jl:47-53).  The extension chosen here: the speculative observation is (x, ŷ, ∇ŷ) with ŷ the sample-averaged
+    posterior mean μ(x) and ∇ŷ the sample-averaged ∇μ(x) (mean_and_var_grad) — the posterior mean of a derivative observation is
+    the derivative of the posterior mean.
+
+    Storage for `batch_size` further points is reserved up front (slice.reserve: one re-update per slice under its own parameters;
+    a member of a fitted set leaves the set there), so every append is a block-row update that re-allocates nothing and a track's
+    capacity is never exceeded.  Y (P×N, the observations so far; None: no best-so-far yet) gives EI's incumbent through
+    best_so_far and grows with the speculative values.  Returns the d×batch_size selections."""
+    from .problem import LinFitness, best_so_far
+    if batch_size < 1:
+        raise ValueError("batch_size must be >= 1")
+    posts = [list(row) for row in posts]
+    if not posts or not posts[0]:
+        raise ValueError("posts must hold at least one sample with at least one output")
+    Xs = np.asarray(Xs, float)
+    if Xs.ndim == 1:
+        Xs = Xs[:, None]
+    S, P = len(posts), len(posts[0])
+    coefs = np.asarray(fit_coefs, float).reshape(-1)
+    ymax = np.full(P, np.inf) if y_max is None else np.asarray(y_max, float).reshape(-1)
+    Yrun = None if Y is None else np.asarray(Y, float).reshape(P, -1)
+    dev = posts[0][0].gp.device
+    cand = api.Candidates(Xs, dev)
+    tracks = []
+    try:
+        for row in posts:
+            for p in row:
+                p.reserve(batch_size)
+        for row in posts:                                       # (one by one: whatever was created is closed on an exception)
+            tracks.append([])
+            for p in row:
+                tracks[-1].append(p.track(cand, Xs))
+        xs = []
+        for _ in range(batch_size):
+            b = None if Yrun is None else best_so_far(LinFitness(coefs), Yrun, ymax)
+            _, am, _ = api.acq_ei_tracks(tracks, coefs, y_max, b, valid_mask, want_acq=False)
+            x = Xs[:, am].copy()
+            y, dy = np.zeros(P), np.zeros((P, Xs.shape[0]))
+            for row in posts:
+                for i, p in enumerate(row):
+                    mu, _, dmu, _ = p.mean_and_var_grad(x[:, None])
+                    y[i] += float(np.asarray(mu).reshape(-1)[0]) / S
+                    dy[i] += np.asarray(dmu, float).reshape(-1) / S
+            for row in posts:
+                for i, p in enumerate(row):
+                    p.append(x, y[i], dy[i])
+            Yrun = y[:, None] if Yrun is None else np.concatenate([Yrun, y[:, None]], axis=1)
+            xs.append(x)
+        return np.stack(xs, axis=1)
+    finally:
+        for ts in tracks:
+            for t in ts:
+                t.close()
+        cand.close()
 
 
 # Where data_loglike_batch switches from the loop of boss_ggp_update calls on one resident handle to one boss_ggp_loglike_batch

@@ -816,12 +816,29 @@ function model_posteriors_batched(m::HipGradientGaussianProcess, ps::AbstractVec
     end
     return [[rows[i][s] for i in 1:P] for s in 1:S]
 end
-"augment_dataset! (src/types/problem.jl:191-198) for a fitted gradient-observation slice: new points with values and gradients, same hyper-parameters."
+"""
+augment_dataset! (src/types/problem.jl:191-198) for a fitted gradient-observation slice: new points with values and gradients, same
+hyper-parameters.  The rows of the new points go to the end of the handle's own ordering and the block rows of the factor that hold
+them are updated on the device (`boss_ggp_append`); tracks of the slice (`track_gradient`) are extended by it.
+"""
 function augment!(post::HipPosteriorSlice, X_new::AbstractMatrix{<:Real}, y_new::AbstractVector{<:Real}, dY_new::AbstractMatrix{<:Real})
     lp = Ref{Cdouble}()
     GC.@preserve post check(ccall((:boss_ggp_append, lib), Cint, (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Cdouble}),
         post.h.h, size(X_new, 2), Matrix{Float64}(X_new), Vector{Float64}(y_new), Matrix{Float64}(dY_new), lp))
     return lp[]
+end
+"Room for `extra` later points of a gradient-observation slice that holds `n_points` (`boss_ggp_reserve` counts POINTS); leaves the handle unfitted: follow with the update."
+reserve_gradient!(post::HipPosteriorSlice, n_points::Int, extra::Int) =
+    check(ccall((:boss_ggp_reserve, lib), Cint, (Ptr{Cvoid}, Cint), post.h.h, n_points + extra))
+"""
+Tracked candidates of a gradient-observation slice (`boss_ggp_track_create`): `cand` is the `boss_cand_t` of the candidates;
+`augment!` then extends the state by 1 + x_dim rows per point.  The returned handle goes to `boss_track_moments` /
+`boss_acq_ei_tracks` / `boss_track_free` like a plain slice's; the variances come out as the reference's max(0, σ²).
+"""
+function track_gradient(post::HipPosteriorSlice, cand::Ptr{Cvoid})
+    t = Ref{Ptr{Cvoid}}()
+    GC.@preserve post check(ccall((:boss_ggp_track_create, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ref{Ptr{Cvoid}}), post.h.h, cand, t))
+    return t[]
 end
 # ---------------------------------------------------------------- NonstationaryGP (Gibbs kernel)
 # The latent models stay BOSS's own (ParametrizedGP posteriors or constants); only their values cross the ABI.

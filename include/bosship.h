@@ -146,8 +146,9 @@ int boss_gp_get_factor(const boss_gp_t* gp, double* L_out, double* z_out);
  * k* from _build_cross_cov :221-243; mean_Xs must be NULL), boss_gp_get_factor, boss_acq_ei, boss_acq_ei_moments
  * boss_gp_predict_grad and boss_acq_ei_grad (the gradients ForwardDiff pushes through :334-361 inside OptimizationAM,
  * src/acquisition_maximizers/optimization.jl:36,89-118; mean_Xs / mean_grad must be NULL; var is max(0, .), its gradient that of
- * the unclipped expression) and boss_gp_free work on it; boss_ggp_loglike_grad and boss_ggp_append are its own forms of the
- * likelihood gradient and of augment_dataset!; the entry points that assume value-only observations (boss_gp_update,
+ * the unclipped expression) and boss_gp_free work on it; boss_ggp_loglike_grad, boss_ggp_append, boss_ggp_reserve and
+ * boss_ggp_track_create are its own forms of the likelihood gradient, of augment_dataset!, of reserve and of tracked candidates;
+ * the entry points that assume value-only observations (boss_gp_update,
  * boss_gp_set_y, boss_gp_append, boss_gp_reserve, boss_gp_predict_cov, boss_gp_loglike_grad, boss_track_create) return
  * BOSS_E_INVALID; the posterior covariance of these handles is boss_ggp_predict_cov.
  * Limits: d <= 16, n(1+d) <= 46080. */
@@ -162,10 +163,22 @@ int boss_ggp_update(boss_gp_t* gp, const double* lengthscale, double amplitude, 
  * of the second-derivative block need the third radial profile of the kernel).  logpdf_out may be NULL. */
 int boss_ggp_loglike_grad(boss_gp_t* gp, double* logpdf_out, double* grad_out);
 /* augment_dataset! (src/types/problem.jl:191-198) + the posterior at unchanged hyper-parameters: n_new further points with values
- * and gradients (X_new d×n_new, y_new n_new, dY_new d×n_new column-major).  New observations land inside every block of the
- * ordering [y; dy/dx_1; ...; dy/dx_d], so — as in the reference — the augmented system is rebuilt and factorised again; the handle
- * stays the same object.  logpdf_out: logpdf of all n + n_new points.  Needs a fitted handle (BOSS_E_NOT_FITTED otherwise). */
+ * and gradients (X_new d×n_new, y_new n_new, dY_new d×n_new column-major).  The reference orders the observations
+ * [y; dy/dx_1; ...; dy/dx_d], which would put new rows inside every block.  The handle keeps an ordering of its own instead: the
+ * points present at boss_ggp_create in the reference's order, every later point's 1 + d rows (value first) behind them.  The
+ * posterior, its logpdf, mean, variance and covariance are invariant under this symmetric permutation, and every entry is
+ * evaluated with the row / column roles the reference gives it (the 1e-8 shift of coincident points depends on them).  So, as for
+ * boss_gp_append, only the 128-row blocks that contain new rows are rebuilt on the device (O(N^2) work per block; more than four
+ * such block rows, or all of them: the grown arrays are factorised again, on the device as well), at the hyper-parameters the
+ * last boss_ggp_update staged on the device, verbatim.  Nothing of the handle's data travels to the host; device storage grows as
+ * needed.  logpdf_out: logpdf of all n + n_new points.  Needs a fitted handle (BOSS_E_NOT_FITTED otherwise).  BOSS_E_NOT_PD
+ * leaves the handle unfitted with the new points in it (logpdf -Inf).  Tracks of the handle (boss_ggp_track_create) survive an
+ * append.  boss_gp_get_factor returns the factor in the handle's ordering. */
 int boss_ggp_append(boss_gp_t* gp, int n_new, const double* X_new, const double* y_new, const double* dY_new, double* logpdf_out);
+/* boss_gp_reserve for a gradient-observation handle, counted in POINTS: device storage for n_points_total points, i.e.
+ * n_points_total (1 + d) rows, so appends up to that size need no re-allocation.  Leaves the handle unfitted: follow with
+ * boss_ggp_update. */
+int boss_ggp_reserve(boss_gp_t* gp, int n_points_total);
 
 /* ---- nonstationary posteriors -----------------------------------------------------
  * Replaces: NonstationaryGP — NonstationaryKernel / gibbs_kernel (src/models/nonstationary_gp/nonstationary_gp.jl:61-107),
@@ -589,6 +602,12 @@ int boss_ngp_track_create(boss_gp_t* gp, const boss_cand_t* cand, const double* 
                           boss_track_t** out);
 int boss_ngp_track_create_lat(boss_gp_t* gp, const boss_cand_t* cand, const boss_nlat_t* lat, const double* mean_Xs,
                               boss_track_t** out);
+/* The same for a gradient-observation posterior (boss_ggp_append extends the state, 1 + d rows per appended point).  The
+ * prediction runs once through the model's own path; the track keeps V, mu, the raw candidates and the UNCLIPPED variance
+ * k(x,x) - |v|^2 (a later row is subtracted from it); boss_track_moments and boss_acq_ei_tracks hand out the reference's
+ * max(0, .) (gradient_gp.jl:343-361).  Bound to the hyper-parameters of the preceding boss_ggp_update like any track.  Handles
+ * that are not gradient-observation posteriors: BOSS_E_INVALID; unfitted: BOSS_E_NOT_FITTED. */
+int boss_ggp_track_create(boss_gp_t* gp, const boss_cand_t* cand, boss_track_t** out);
 void boss_track_free(boss_track_t* track);
 int boss_track_sync(boss_track_t* track);
 int boss_track_moments(boss_track_t* track, int first, int count, double* mu, double* var);
