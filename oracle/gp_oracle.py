@@ -769,6 +769,35 @@ def augmented_cross_cov(kernel: int, X, lengthscale, amplitude: float, Xs):
     return out
 
 
+def augmented_cross_cov_allpairs(kernel: int, X, lengthscale, amplitude: float, Xs):
+    """`augmented_cross_cov` for all (candidate, point) pairs at once, with the per-pair arithmetic of `_kernel_and_derivs` on
+    M × n arrays (as `augmented_kernel_matrix` restates its pair loop; pinned against the loop in tests/test_appended_sets_host.py):
+    for callers that predict at hundreds of candidates over a thousand rows (tools/fuzz_models.py)."""
+    kernel = KERNEL_NAMES.get(kernel, kernel) if isinstance(kernel, str) else kernel
+    X = np.asarray(X, dtype=np.float64)
+    Xs = np.asarray(Xs, dtype=np.float64)
+    if Xs.ndim == 1:
+        Xs = Xs[:, None]
+    d, n = X.shape
+    M = Xs.shape[1]
+    lam = np.asarray(lengthscale, dtype=np.float64) + MIN_PARAM_VALUE
+    amp2 = (float(amplitude) + MIN_PARAM_VALUE) ** 2
+    P, Cn = np.ascontiguousarray(X.T), np.ascontiguousarray(Xs.T)
+    U = Cn[:, None, :] - P[None, :, :]                                  # U[c, j] = x*_c − x_j
+    Kv = amp2 * kappa(kernel, np.sqrt(np.sum((U / lam) ** 2, axis=-1)))
+    nc, npnt = np.sqrt(np.einsum("ik,ik->i", Cn, Cn)), np.sqrt(np.einsum("ik,ik->i", P, P))
+    near = np.sqrt(np.sum(U * U, axis=-1)) <= _ISAPPROX_RTOL * np.maximum(nc[:, None], npnt[None, :])
+    if near.any():
+        U = np.where(near[:, :, None], Cn[:, None, :] - (P[None, :, :] + MIN_PARAM_VALUE), U)
+    h = kappa_prime_over_r(kernel, np.sqrt(np.sum((U / lam) ** 2, axis=-1)))
+    dxj = -((amp2 * h)[:, :, None] * (U / lam ** 2))                    # M × n × d
+    out = np.zeros((n * (1 + d), M))
+    out[:n] = Kv.T
+    for l in range(d):
+        out[n + l * n:n + (l + 1) * n] = dxj[:, :, l].T
+    return out
+
+
 def augmented_obs_vector(y, dY):
     """gradient_gp.jl:288-302 `_build_obs_vector`: [y_1..n, ∂y/∂x_1 (1..n), …, ∂y/∂x_d (1..n)];  dY is d×n."""
     return np.concatenate([np.asarray(y, dtype=np.float64)] + [np.asarray(dY, dtype=np.float64)[l, :] for l in range(np.shape(dY)[0])])
@@ -938,6 +967,67 @@ def gradient_gp_loglike_grad(X, y, dY, kernel, lengthscale, amplitude, noise_std
     for t in range(d + 1):
         Ks = np.triu(dK[t]) + np.triu(dK[t], 1).T            # `Symmetric(K)` reads the upper triangle
         grad[t] = 0.5 * float(np.sum(G * Ks))
+    dg = np.diag(G)
+    grad[d + 1] = (float(noise_std) + MIN_PARAM_VALUE) * float(np.sum(dg[:n]))
+    grad[d + 2] = (float(grad_noise_std) + MIN_PARAM_VALUE) * float(np.sum(dg[n:]))
+    return post.logpdf, grad
+
+
+def gradient_gp_loglike_grad_allpairs(X, y, dY, kernel, lengthscale, amplitude, noise_std, grad_noise_std):
+    """`gradient_gp_loglike_grad` with all pairs at once: the per-pair formulas of `_kernel_and_derivs` and `_kernel_derivs_dlam`
+    on n × n arrays (as `augmented_kernel_matrix` restates `_augmented_kernel_matrix_pairs`), one ∂K/∂λ_m at a time.  Pinned
+    against the pair loop in tests/test_appended_sets_host.py; fast enough for a thousand and more rows, where the pair loop takes
+    tens of seconds.  Returns (logpdf, grad[d + 3])."""
+    kernel = KERNEL_NAMES.get(kernel, kernel) if isinstance(kernel, str) else kernel
+    X = np.asarray(X, dtype=np.float64)
+    d, n = X.shape
+    lam = np.asarray(lengthscale, dtype=np.float64) + MIN_PARAM_VALUE
+    amp = float(amplitude) + MIN_PARAM_VALUE
+    amp2 = amp * amp
+    N = n * (1 + d)
+    post = gradient_gp_fit(X, y, dY, kernel, lengthscale, amplitude, noise_std, grad_noise_std)
+    Kinv = sla.cho_solve((post.L, True), np.eye(N), check_finite=False)
+    G = np.outer(post.alpha, post.alpha) - Kinv
+    P = np.ascontiguousarray(X.T)
+    U0 = P[:, None, :] - P[None, :, :]
+    r0 = np.sqrt(np.sum((U0 / lam) ** 2, axis=-1))
+    nrm = np.sqrt(np.einsum("ik,ik->i", P, P))
+    near = np.sqrt(np.sum(U0 * U0, axis=-1)) <= _ISAPPROX_RTOL * np.maximum(nrm[:, None], nrm[None, :])
+    U = np.where(near[:, :, None], P[:, None, :] - (P[None, :, :] + MIN_PARAM_VALUE), U0)
+    r = np.sqrt(np.sum((U / lam) ** 2, axis=-1))
+    h0 = kappa_prime_over_r(kernel, r0)
+    h = kappa_prime_over_r(kernel, r)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        g = kappa_second(kernel, r)
+        q = kappa_third(kernel, r)
+    S = U / lam ** 2                                                    # n × n × d
+    W = -(U ** 2) / lam ** 3
+    blocks = [slice(0, n)] + [slice(n + l * n, n + (l + 1) * n) for l in range(d)]
+    sym = lambda A: np.triu(A) + np.triu(A, 1).T                       # noqa: E731  (`Symmetric(K)` reads the upper triangle)
+    grad = np.zeros(d + 3)
+    for m in range(d):
+        dK = np.zeros((N, N))
+        dK[blocks[0], blocks[0]] = amp2 * h0 * (-(U0[:, :, m] ** 2) / lam[m] ** 3)
+        for l in range(d):
+            ddxi = amp2 * g * W[:, :, m] * S[:, :, l]
+            if l == m:
+                ddxi = ddxi - 2.0 * amp2 * h * S[:, :, m] / lam[m]
+            dK[blocks[1 + l], blocks[0]] = ddxi
+            dK[blocks[0], blocks[1 + l]] = -ddxi
+            for k in range(d):
+                blk = q * W[:, :, m] * S[:, :, l] * S[:, :, k]
+                if l == k:
+                    blk = blk + g * W[:, :, m] / lam[l] ** 2
+                if l == m:
+                    blk = blk - 2.0 * g * S[:, :, m] * S[:, :, k] / lam[m]
+                if k == m:
+                    blk = blk - 2.0 * g * S[:, :, l] * S[:, :, m] / lam[m]
+                if l == m and k == m:
+                    blk = blk - 2.0 * h / lam[m] ** 3
+                dK[blocks[1 + l], blocks[1 + k]] = -amp2 * blk
+        grad[m] = 0.5 * float(np.sum(G * sym(dK)))
+    Kfree = augmented_kernel_matrix(kernel, X, lengthscale, amplitude, -MIN_PARAM_VALUE, -MIN_PARAM_VALUE)   # no noise on the diagonal
+    grad[d] = 0.5 * float(np.sum(G * Kfree)) * 2.0 / amp
     dg = np.diag(G)
     grad[d + 1] = (float(noise_std) + MIN_PARAM_VALUE) * float(np.sum(dg[:n]))
     grad[d + 2] = (float(grad_noise_std) + MIN_PARAM_VALUE) * float(np.sum(dg[n:]))
