@@ -9,7 +9,7 @@ from . import api  # noqa: F401
 from .api import (BossError, Candidates, DomainError, GP, PosDefException, acq_ei, fit,  # noqa: F401
                   ggp_fit_batch, ggp_loglike_batch, load_library, loglike_batch, ngp_fit_batch, ngp_loglike_batch,
                   ngp_acq_ei_grad_set, ngp_predict_grad_set, ngp_predict_set, NgpLatents, ngp_acq_ei_grad_set_lat,
-                  ngp_predict_grad_set_lat, ngp_predict_set_lat)
+                  ngp_predict_grad_set_lat, ngp_predict_set_lat, NgpWhitened)
 from .problem import (BossOptions, BossProblem, Dirac, Domain, ExperimentData, ExpectedImprovement,  # noqa: F401,E402
                       LinFitness, LogNormal, MvDirac, MvLogNormal, NonlinFitness)
 from .model import HipGaussianProcess, HipGPParams, average_mean  # noqa: F401,E402
@@ -22,5 +22,6 @@ from .nonstationary import data_loglike_batch as nonstationary_data_loglike_batc
 from .nonstationary import data_loglike_grad_batch as nonstationary_data_loglike_grad_batch  # noqa: F401,E402
 from .nonstationary import (nonstationary_acq_ei_batch, nonstationary_acq_ei_grad_batch,  # noqa: F401,E402
                             nonstationary_model_posterior_batch, nonstationary_sequential_batch)
-from .fitter import HipBatchedMAP, HipGradientMAP, HipSampleOptMAP, MAPParams  # noqa: F401,E402
+from .fitter import HipBatchedMAP, HipGradientMAP, HipNonstationaryMAP, HipSampleOptMAP, MAPParams  # noqa: F401,E402
+from .nonstationary import HipNonstationaryModel, HipNonstationaryParams  # noqa: F401,E402
 from .maximizer import HipBatchAM, HipGradientAM, HipSequentialBatchAM  # noqa: F401,E402

@@ -105,6 +105,12 @@ SIGNATURES = {
                                    C.POINTER(C.c_int), _c_dp, C.POINTER(C.c_int), _c_dp, _c_ucp, C.POINTER(C.c_void_p)]),
     "boss_nlat_free": (None, [C.c_void_p]),
     "boss_nlat_eval": (C.c_int, [C.c_void_p, C.c_int, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, C.POINTER(C.c_long)]),
+    "boss_nfit_create": (C.c_int, [C.c_int, C.c_int, C.c_int, _c_dp, _c_dp, _c_ucp, _c_dp, C.c_int, _c_dp, C.POINTER(C.c_int), _c_dp,
+                                   C.POINTER(C.c_int), _c_dp, C.POINTER(C.c_int), _c_dp, C.POINTER(C.c_void_p)]),
+    "boss_nfit_free": (None, [C.c_void_p]),
+    "boss_nfit_param_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "boss_nfit_values": (C.c_int, [C.c_void_p, C.c_int, _c_dp, _c_dp, _c_dp, _c_dp, C.POINTER(C.c_int)]),
+    "boss_nfit_loglike_grad": (C.c_int, [C.c_void_p, C.c_int, _c_dp, _c_dp, _c_dp, C.POINTER(C.c_int)]),
     "boss_ngp_predict_lat": (C.c_int, [C.c_void_p, C.c_int, _c_dp, C.c_void_p, _c_dp, _c_dp, _c_dp, C.POINTER(C.c_long)]),
     "boss_ngp_predict_grad_lat": (C.c_int, [C.c_void_p, C.c_int, _c_dp, C.c_void_p, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp,
                                             C.POINTER(C.c_long)]),
@@ -774,6 +780,106 @@ class NgpLatents:
     def close(self):
         if self._h is not None:
             load_library().boss_nlat_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class NgpWhitened:
+    """One output slice of a NonstationaryGP with the whitening of its latent ParametrizedGPs resident on the device (boss_nfit_t):
+    the data log-likelihood and its gradient w.r.t. the whitened parameters yϵ of S parameter sets in one call.
+    factors: a sequence of N×N lower-triangular matrices (L of parametrized_gp.jl:200-202) or an N×N×F array; factor_of: d+2
+    entries in latent order λ_0..λ_{d-1}, α, σ — an index into factors, or -1 for a scalar latent; specs: d+2 entries, for a GP
+    latent (target, (p0, p1), activation, par) with the names of LATENT_TARGETS / LATENT_ACTS (or their codes), ignored (None) for
+    scalar latents; mu: N×(d+2) or None.  Parameter layout: column s of theta (T×S) holds the latents in order, N values of yϵ per
+    GP latent, one value (taken as it is) per scalar latent."""
+
+    def __init__(self, X, y, factors, factor_of, specs, mu=None, mean_X=None, discrete=None, device: int = 0):
+        X = _f64(X, 2)
+        y = _f64(np.asarray(y).reshape(-1), 1)
+        d, N = X.shape
+        if y.shape[0] != N:
+            raise ValueError("y must have one entry per column of X")
+        nq = d + 2
+        fo = np.ascontiguousarray(np.asarray(factor_of).reshape(-1), dtype=np.int32)
+        specs = list(specs)
+        if fo.shape[0] != nq or len(specs) != nq:
+            raise BossError(BOSS_E_INVALID, "factor_of and specs must have d + 2 entries")
+        if isinstance(factors, np.ndarray) and factors.ndim == 3:
+            F = _f64(factors)
+        else:
+            fl = [_f64(f, 2) for f in factors]
+            F = _f64(np.stack(fl, axis=2)) if fl else np.zeros((N, N, 0), order="F")
+        if F.shape[:2] != (N, N):
+            raise ValueError("every factor must be N×N")
+        tgt = (C.c_int * nq)()
+        act = (C.c_int * nq)()
+        tpar = np.zeros(2 * nq)
+        apar = np.zeros(nq)
+        for q, sp in enumerate(specs):
+            if sp is None or fo[q] < 0:
+                continue
+            t, tp, a, ap = sp
+            tgt[q] = LATENT_TARGETS[t] if isinstance(t, str) else int(t)
+            act[q] = LATENT_ACTS[a] if isinstance(a, str) else int(a)
+            tpar[2 * q:2 * q + 2] = tp
+            apar[q] = ap
+        m = None if mu is None else _f64(mu, 2)
+        if m is not None and m.shape != (N, nq):
+            raise ValueError("mu must be N×(d+2)")
+        mx = None if mean_X is None else _f64(np.asarray(mean_X).reshape(-1), 1)
+        if mx is not None and mx.shape[0] != N:
+            raise ValueError("mean_X must have N entries")
+        disc = None if discrete is None else np.ascontiguousarray(np.asarray(discrete, dtype=bool).astype(np.uint8))
+        if disc is not None and disc.shape != (d,):
+            raise BossError(BOSS_E_INVALID, "discrete must have one flag per dimension")
+        self.d, self.N, self.device = d, N, device
+        self._h = None
+        h = C.c_void_p()
+        _check(load_library().boss_nfit_create(device, d, N, _dp(X), _dp(y), _ucp(disc), _dp(mx), F.shape[2], _dp(F),
+                                               fo.ctypes.data_as(C.POINTER(C.c_int)), _dp(m), tgt, _dp(tpar), act, _dp(apar), C.byref(h)))
+        self._h = h
+        T = C.c_int(0)
+        _check(load_library().boss_nfit_param_count(self._h, C.byref(T)))
+        self.T = T.value
+
+    def _theta(self, theta):
+        th = _f64(theta)
+        if th.ndim == 1:
+            th = _f64(th.reshape(-1, 1))
+        if th.ndim != 2 or th.shape[0] != self.T:
+            raise ValueError(f"theta must be T×S with T = {self.T}")
+        return th
+
+    def values(self, theta):
+        """(lam[d, N, S], amp[N, S], noise[N, S], status[S]): the latents' values at the data for every column of theta
+        (boss_nfit_values), in the layouts ngp_loglike_batch takes."""
+        th = self._theta(theta)
+        S = th.shape[1]
+        lam = np.zeros((self.d, self.N, S), order="F")
+        amp, noi = np.zeros((self.N, S), order="F"), np.zeros((self.N, S), order="F")
+        st = np.zeros(S, dtype=np.int32)
+        _check(load_library().boss_nfit_values(self._h, S, _dp(th), _dp(lam), _dp(amp), _dp(noi), st.ctypes.data_as(C.POINTER(C.c_int))))
+        return lam, amp, noi, st
+
+    def loglike_grad(self, theta, want_grad: bool = True):
+        """(ll[S], status[S], grad[T, S] or None): the data log-likelihood of every column of theta and its gradient w.r.t. theta
+        (boss_nfit_loglike_grad); -Inf and a zero column where a set is invalid or not PD."""
+        th = self._theta(theta)
+        S = th.shape[1]
+        ll = np.zeros(S)
+        st = np.zeros(S, dtype=np.int32)
+        grad = np.zeros((self.T, S), order="F") if want_grad else None
+        _check(load_library().boss_nfit_loglike_grad(self._h, S, _dp(th), _dp(ll), _dp(grad), st.ctypes.data_as(C.POINTER(C.c_int))))
+        return ll, st, grad
+
+    def close(self):
+        if self._h is not None:
+            load_library().boss_nfit_free(self._h)
             self._h = None
 
     def __del__(self):

@@ -25,6 +25,7 @@
 #include "small_calls.hpp"
 #include "rider.hpp"
 #include "latent_kernels.hpp"
+#include "nfit_kernels.hpp"
 
 using namespace boss;
 
@@ -646,6 +647,7 @@ static bool few_fused() {
 #include "host_append.inc"
 #include "host_batch.inc"
 #include "host_latent.inc"
+#include "host_nfit.inc"
 #include "host_predict.inc"
 #include "host_acq.inc"
 #include "host_rider.inc"

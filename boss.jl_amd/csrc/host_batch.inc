@@ -379,11 +379,21 @@ struct ModelBatchGrad {
     std::function<void(int s, const double* par, const double* h)> finish;       // set s's outputs from its staged parameters and results; h null: zeros
 };
 
+// Two optional hooks make a whole-chain call of it (boss_nfit_loglike_grad, host_nfit.inc): the parameter blocks of a chunk are
+// written ON THE DEVICE (`fill` enqueues that on c->stream and raises flags[b] != 0 for an invalid set; the flags come back with the
+// failed-pivot flags in one copy), and the gradient pass's results are consumed on the device (`consume` enqueues kernels and its
+// own copy back behind them; `finish` runs after the chunk's synchronisation).  The host `fill` and G->finish are not called then.
+struct ModelBatchDevice {
+    std::function<int(int s0, int nb, double* par_dev, int* flags_dev)> fill;
+    std::function<int(int s0, int nb, const double* sums_dev)> consume;      // null: nothing to consume (likelihoods only)
+    std::function<void(int s, int b, int status)> finish;                    // set s = member b of the chunk just synchronised
+};
+
 static int model_loglike_batch_run(Ctx* c, int N, int Np, int S, const std::vector<double>& pts, const std::vector<double>& yb,
                                    const double* mean_X, int mean_stride, size_t par_doubles,
                                    const std::function<bool(int, double*)>& fill,
                                    const std::function<void(const ModelBatchGramArgs&)>& gram, double* ll_out, int* status_out,
-                                   const ModelBatchGrad* G = nullptr) {
+                                   const ModelBatchGrad* G = nullptr, const ModelBatchDevice* Dv = nullptr) {
     hipStream_t s = c->stream;
     const int nblk = Np / BLK, ld = Np + RHS_ROWS;
     const size_t bstride = (size_t)ld * Np, per = bstride * sizeof(double);
@@ -397,7 +407,7 @@ static int model_loglike_batch_run(Ctx* c, int N, int Np, int S, const std::vect
     if (rc) return rc;
     const int group = llgrad_group_size(G != nullptr, Np, ld, chunk);
     const size_t dinv_doubles = llgrad_dinv_doubles(group, Np), out_doubles = G ? G->out_doubles : 0;
-    rc = ws_reserve(c->batchMisc, sizeof(double) * ((size_t)chunk * (inv16_b + 2 + out_doubles) + dinv_doubles) + sizeof(int) * chunk + 64);
+    rc = ws_reserve(c->batchMisc, sizeof(double) * ((size_t)chunk * (inv16_b + 2 + out_doubles) + dinv_doubles) + sizeof(int) * chunk * (Dv ? 2 : 1) + 64);
     if (rc) return rc;
     double* A = (double*)c->batchA.p;
     double* pts_dev = (double*)c->batchX.p;                  // points | observations | prior means | parameter blocks
@@ -409,12 +419,12 @@ static int model_loglike_batch_run(Ctx* c, int N, int Np, int S, const std::vect
     double* sums = scal + 2 * (size_t)chunk;                 // chunk × out_doubles
     double* dinv_scratch = sums + out_doubles * chunk;
     int* info = (int*)(dinv_scratch + dinv_doubles);
-    std::vector<double> h_sums(out_doubles * chunk);
+    std::vector<double> h_sums(Dv ? 0 : out_doubles * chunk);
     // (the host vectors outlive the copies: every chunk ends with a synchronisation)
     HIPCHK(hipMemcpyAsync(pts_dev, pts.data(), sizeof(double) * pts.size(), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(ydev, yb.data(), sizeof(double) * Np, hipMemcpyHostToDevice, s));
-    std::vector<double> h_par(par_doubles * chunk), h_scal(2 * (size_t)chunk), h_mean;
-    std::vector<int> h_info(chunk), valid(chunk);
+    std::vector<double> h_par(Dv ? 0 : par_doubles * chunk), h_scal(2 * (size_t)chunk), h_mean;
+    std::vector<int> h_info(chunk * (Dv ? 2 : 1)), valid(chunk);   // (device fill: failed-pivot flags | validity flags)
     const int Nm = mean_X ? mean_stride : 0;                 // (mean_stride is 0 or the number of observations)
     if (mean_X && mean_stride == 0) {
         h_mean.assign(Np, 0.0);
@@ -423,8 +433,16 @@ static int model_loglike_batch_run(Ctx* c, int N, int Np, int S, const std::vect
     }
     for (int s0 = 0; s0 < S; s0 += chunk) {
         const int nb = std::min(chunk, S - s0);
-        for (int b = 0; b < nb; ++b) valid[b] = fill(s0 + b, h_par.data() + (size_t)b * par_doubles);
-        HIPCHK(hipMemcpyAsync(par_dev, h_par.data(), sizeof(double) * par_doubles * nb, hipMemcpyHostToDevice, s));
+        if (Dv) {
+            HIPCHK(hipMemsetAsync(info + nb, 0, sizeof(int) * nb, s));
+            if ((rc = Dv->fill(s0, nb, par_dev, info + nb)) != BOSS_OK) {
+                (void)hipStreamSynchronize(s);
+                return rc;
+            }
+        } else {
+            for (int b = 0; b < nb; ++b) valid[b] = fill(s0 + b, h_par.data() + (size_t)b * par_doubles);
+            HIPCHK(hipMemcpyAsync(par_dev, h_par.data(), sizeof(double) * par_doubles * nb, hipMemcpyHostToDevice, s));
+        }
         if (Nm) {
             h_mean.assign((size_t)Np * nb, 0.0);
             for (int b = 0; b < nb; ++b)
@@ -447,15 +465,24 @@ static int model_loglike_batch_run(Ctx* c, int N, int Np, int S, const std::vect
                                          G->view(v, pts_dev, par_dev + (size_t)b * par_doubles);
                                      });
             if (rc) return rc;
-            HIPCHK(hipMemcpyAsync(h_sums.data(), sums, sizeof(double) * out_doubles * nb, hipMemcpyDeviceToHost, s));
+            if (!Dv) HIPCHK(hipMemcpyAsync(h_sums.data(), sums, sizeof(double) * out_doubles * nb, hipMemcpyDeviceToHost, s));
+            else if (Dv->consume && (rc = Dv->consume(s0, nb, sums)) != BOSS_OK) {
+                (void)hipStreamSynchronize(s);
+                return rc;
+            }
         }
         HIPCHK(hipMemcpyAsync(h_scal.data(), scal, sizeof(double) * 2 * nb, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(h_info.data(), info, sizeof(int) * nb, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(h_info.data(), info, sizeof(int) * nb * (Dv ? 2 : 1), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         HIPCHK(hipGetLastError());
         for (int b = 0; b < nb; ++b) {
+            if (Dv) valid[b] = h_info[nb + b] == 0;
             const int st = batch_set_result(N, valid[b], h_info[b], h_scal[2 * b], h_scal[2 * b + 1], &ll_out[s0 + b]);
             if (status_out) status_out[s0 + b] = st;
+            if (Dv) {
+                if (Dv->finish) Dv->finish(s0 + b, b, st);
+                continue;
+            }
             if (G) G->finish(s0 + b, h_par.data() + (size_t)b * par_doubles, st == BOSS_OK ? h_sums.data() + (size_t)b * out_doubles : nullptr);
         }
     }
@@ -560,6 +587,24 @@ extern "C" int boss_ggp_loglike_grad_batch(int device, int kernel, int d, int n,
                                   grad_out);
 }
 
+// What the two nonstationary callers of model_loglike_batch_run (ngp_loglike_batch_impl; boss_nfit_loglike_grad, host_nfit.inc) share:
+// the Gram launch over parameter blocks λ [d][Np] | α [Np] | σ [Np] and the view of one set the gradient pass reads.  One copy, so
+// that the whole-chain call stays bit for bit the array call.
+static void ngp_batch_gram(Ctx* c, int d, int N, int Np, const ModelBatchGramArgs& a) {
+    const size_t par_doubles = ((size_t)d + 2) * Np;
+    const int t64 = Np / 64;
+    hipLaunchKernelGGL(gibbs_gram_kernel, dim3(t64 * (t64 + 1) / 2, 1, a.cnt), dim3(256), 0, c->stream, a.pts, a.par,
+                       a.par + (size_t)d * Np, a.par + (size_t)(d + 1) * Np, par_doubles, par_doubles, d, N, Np, a.A, a.ld, a.bstride, 0);
+}
+static void ngp_batch_view(boss_gp* v, int d, int Np, const double* pts_dev, double* par) {
+    v->d = d;
+    v->gibbs = true;
+    v->Xraw = const_cast<double*>(pts_dev);
+    v->lamX = par;
+    v->ampX = par + (size_t)d * Np;
+    v->noiseX = par + (size_t)(d + 1) * Np;
+}
+
 // S sets of latent values (λ(x_j) d×N, α(x_j) N, σ(x_j) N; set after set) of a NonstationaryGP on one output slice.  The values
 // are taken as given (nothing is added), and checked as boss_ngp_update checks them: a set with a lengthscale that is not finite
 // and positive, or an amplitude or noise that is not finite and non-negative, is reported and the others are computed.
@@ -586,21 +631,10 @@ static int ngp_loglike_batch_impl(int device, int d, int N, const double* X, con
     auto fill = [&](int b, double* p) {
         return ngp_stage_set(d, N, Np, lam_X + (size_t)b * d * N, amp_X + (size_t)b * N, noise_X + (size_t)b * N, p);
     };
-    auto gram = [&](const ModelBatchGramArgs& a) {
-        const int t64 = Np / 64;
-        hipLaunchKernelGGL(gibbs_gram_kernel, dim3(t64 * (t64 + 1) / 2, 1, a.cnt), dim3(256), 0, c->stream, a.pts, a.par,
-                           a.par + (size_t)d * Np, a.par + (size_t)(d + 1) * Np, par_doubles, par_doubles, d, N, Np, a.A, a.ld, a.bstride, 0);
-    };
+    auto gram = [&](const ModelBatchGramArgs& a) { ngp_batch_gram(c, d, N, Np, a); };
     ModelBatchGrad G;
     G.out_doubles = ((size_t)d + 3) * Np;                    // dlam [d][Np] | damp [Np] | dnoise [Np] | dmean [Np]
-    G.view = [&](boss_gp* v, const double* pts_dev, double* par) {
-        v->d = d;
-        v->gibbs = true;
-        v->Xraw = const_cast<double*>(pts_dev);
-        v->lamX = par;
-        v->ampX = par + (size_t)d * Np;
-        v->noiseX = par + (size_t)(d + 1) * Np;
-    };
+    G.view = [&](boss_gp* v, const double* pts_dev, double* par) { ngp_batch_view(v, d, Np, pts_dev, par); };
     G.finish = [&](int b, const double*, const double* h) {
         double* dl = dlam_out ? dlam_out + (size_t)b * d * N : nullptr;
         for (int j = 0; j < N; ++j) {

@@ -229,3 +229,103 @@ class HipSampleOptMAP:
         starts = [scored[i].params for i in order[:self.multistart]]
         opt = HipGradientMAP(self.multistart, self.iters, self.seed, self.group, starts=starts)
         return opt.estimate_parameters(problem, options, return_all)
+
+
+@dataclass
+class HipNonstationaryMAP:
+    """OptimizationMAP semantics (src/model_fitters/optimization.jl:13-164) over a HipNonstationaryModel: multistart local
+    maximisation of  data_loglike + params_loglike  over the whitened outputs yϵ of the latent ParametrizedGPs and the scalar
+    parameters of distribution latents.  HipGradientMAP's lockstep backtracking ascent: every round is ONE device call per output
+    for the trial points of all starts (boss_nfit_loglike_grad: de-whitening, transform, likelihood, gradient and pull-back on the
+    device).  Coordinates: yϵ as it is (its prior is N(0, I): gradient −yϵ), positive scalar latents in log-space, scalars with a
+    Dirac prior do not move."""
+    multistart: int = 8
+    iters: int = 40
+    seed: Optional[int] = None
+    step0: float = 0.3
+    starts: Optional[list] = None
+
+    def estimate_parameters(self, problem: BossProblem, options: BossOptions = BossOptions(), return_all: bool = False):
+        from .nonstationary import HipParametrizedGP
+        model, data = problem.model, problem.data
+        rng = np.random.default_rng(self.seed)
+        starts = list(self.starts) if self.starts is not None else None
+        if starts is None:
+            sampler = model.params_sampler(data)
+            starts = [sampler(rng) for _ in range(self.multistart)]
+        template = starts[0]
+        # the device keeps ONE whitening (L, μ per latent) for all starts: starts must share it (the draws of one sampler do)
+        for k, p in enumerate(starts[1:], 1):
+            for i in range(model.y_dim):
+                for a, b in zip(template.latents(i), p.latents(i)):
+                    if hasattr(a, "L") != hasattr(b, "L") or (hasattr(a, "L") and not (
+                            (a.L is b.L or np.array_equal(a.L, b.L)) and (a.mu is b.mu or np.array_equal(a.mu, b.mu)))):
+                        raise ValueError(f"HipNonstationaryMAP: start {k} does not share the factors L and means μ of start 0 (output {i})")
+        vec, devec = model.vectorizer(data)
+        layout, T = model._layout(data)
+        # per coordinate: is it a log-space scalar, is it free; and the scalar priors
+        logc, free, scalars = np.zeros(T, bool), np.ones(T, bool), []
+        for i, q, at, n in layout:
+            m = model._models(i)[q]
+            if isinstance(m, HipParametrizedGP):
+                continue
+            logc[at] = True
+            free[at] = not isinstance(m, Dirac)
+            scalars.append((at, m))
+        gp = ~logc
+
+        def objective(Th):
+            """log-posterior of every column and its gradient w.r.t. the ascent's coordinates (yϵ, log of the scalars)"""
+            f, G = model.data_loglike_grad_vec(data, template, Th)
+            f = f - 0.5 * (Th[gp] ** 2).sum(axis=0) - 0.5 * gp.sum() * math.log(2.0 * math.pi)
+            G[gp] -= Th[gp]
+            for at, m in scalars:
+                for k in range(Th.shape[1]):
+                    f[k] += m.logpdf(Th[at, k])
+                    G[at, k] += m.grad_logpdf(Th[at, k])
+            G[logc] *= Th[logc]                                       # ∂f/∂log θ = θ ∂f/∂θ
+            G[~free] = 0.0
+            ok = np.isfinite(f)
+            G[:, ~ok] = 0.0
+            return np.where(ok, f, -np.inf), G
+
+        def move(th, dz):
+            out = th + dz
+            out[logc] = th[logc] * np.exp(dz[logc])
+            return out
+
+        Th = np.stack([vec(p) for p in starts], axis=1)
+        f, G = objective(Th)
+        n = Th.shape[1]
+        self.history = [[float(v)] for v in f]                       # accepted log-posteriors per start
+        step = np.full(n, self.step0)
+        its = np.zeros(n, dtype=int)
+        alive = np.isfinite(f) & (self.iters > 0)
+        while alive.any():
+            idx, trial = [], []
+            for k in np.flatnonzero(alive):
+                nrm = math.sqrt(float((G[:, k] ** 2).sum()))
+                if nrm < 1e-10:
+                    alive[k] = False
+                    continue
+                idx.append(k)
+                trial.append(move(Th[:, k], step[k] * G[:, k] / nrm))
+            if not idx:
+                break
+            fq, Gq = objective(np.stack(trial, axis=1))
+            for j, k in enumerate(idx):
+                if fq[j] > f[k]:
+                    Th[:, k], f[k], G[:, k] = trial[j], fq[j], Gq[:, j]
+                    self.history[k].append(float(fq[j]))
+                    step[k] = min(step[k] * 1.6, 2.0)
+                    its[k] += 1
+                    if its[k] >= self.iters:
+                        alive[k] = False
+                else:
+                    step[k] *= 0.4
+                    if step[k] <= 1e-6:
+                        alive[k] = False
+        results = [MAPParams(devec(starts[k], Th[:, k]), float(f[k])) for k in range(n)]
+        if return_all:
+            return results
+        return max(enumerate(results), key=lambda r: (r[1].loglike, -r[0]))[1]

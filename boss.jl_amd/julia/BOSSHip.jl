@@ -1239,6 +1239,68 @@ function acq_grad_samples(problem::BOSS.BossProblem, xs::AbstractMatrix{Float64}
     return acq, dacq
 end
 
+# ---------------------------------------------------------------- the likelihood in whitened latent parameters (boss_nfit_*)
+"""
+One output slice of a NonstationaryGP with the whitening of its latent ParametrizedGPs resident on the device (`boss_nfit_t`): what
+a gradient fitter evaluates per step (src/model_fitters/optimization.jl:146-164) — `data_loglike_slice` through
+`model_posterior_lookup` (parametrized_gp.jl:108-120) and its gradient w.r.t. yϵ — for S parameter sets in one call.  Each latent is
+a `Real` (a distribution latent: one free number) or a pair `(model::BOSS.ParametrizedGP, params::BOSS.ParametrizedGPParams)` whose
+L and μ are uploaded; latents whose `params.L` is the same array share one factor.  Column s of θ (T×S) holds the latents in order
+λ_1..λ_d, α, σ: N values of yϵ per ParametrizedGP latent, one value per scalar latent.  (Not run here: no Julia toolchain.)
+"""
+mutable struct HipWhitened
+    h::Ptr{Cvoid}
+    d::Int
+    N::Int
+    T::Int
+    function HipWhitened(h::Ptr{Cvoid}, d::Int, N::Int, T::Int)
+        obj = new(h, d, N, T)
+        finalizer(close, obj)
+    end
+end
+Base.close(o::HipWhitened) = (o.h == C_NULL || ccall((:boss_nfit_free, lib), Cvoid, (Ptr{Cvoid},), o.h); o.h = C_NULL; nothing)
+function HipWhitened(X::AbstractMatrix{<:Real}, y::AbstractVector{<:Real}, λs::AbstractVector, α, σ; mean = nothing,
+                     discrete::Union{Nothing, AbstractVector{Bool}} = nothing, device::Int = 0)
+    Xm = Matrix{Float64}(X); d, N = size(Xm); lats = Any[λs..., α, σ]; nq = d + 2
+    Ls = Any[]; fof = fill(Cint(-1), nq); μ = zeros(N, nq)
+    tgt = zeros(Cint, nq); act = zeros(Cint, nq); tpar = zeros(2nq); apar = zeros(nq)
+    for (q, l) in enumerate(lats)
+        l isa Real && continue
+        l isa Tuple || error("HipWhitened: latent $q is neither a number nor (ParametrizedGP, ParametrizedGPParams)")
+        t, p0, p1, a, ap = latent_spec(l[1])
+        f = findfirst(L -> L === l[2].L, Ls)
+        isnothing(f) && (push!(Ls, l[2].L); f = length(Ls))
+        fof[q] = f - 1; μ[:, q] .= l[2].μ
+        tgt[q] = t; tpar[2q - 1] = p0; tpar[2q] = p1; act[q] = a; apar[q] = ap
+    end
+    F = Array{Float64}(undef, N, N, length(Ls))
+    for (f, L) in enumerate(Ls); F[:, :, f] .= Matrix(L); end
+    out = Ref{Ptr{Cvoid}}(C_NULL); Tn = Ref{Cint}(0)
+    check(ccall((:boss_nfit_create, lib), Cint,
+        (Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{UInt8}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cint}, Ptr{Cdouble}, Ptr{Cint},
+         Ptr{Cdouble}, Ptr{Cint}, Ptr{Cdouble}, Ref{Ptr{Cvoid}}),
+        device, d, N, Xm, Vector{Float64}(y), isnothing(discrete) ? C_NULL : Vector{UInt8}(discrete), mean_vals(mean, Xm),
+        length(Ls), F, fof, μ, tgt, tpar, act, apar, out))
+    check(ccall((:boss_nfit_param_count, lib), Cint, (Ptr{Cvoid}, Ref{Cint}), out[], Tn))
+    return HipWhitened(out[], d, N, Int(Tn[]))
+end
+"(λ d×N×S, α N×S, σ N×S, status S): the latents' values at the data for every column of θ (`boss_nfit_values`)"
+function latent_values(W::HipWhitened, θ::AbstractMatrix{<:Real})
+    Θ = Matrix{Float64}(θ); S = size(Θ, 2)
+    λ = Array{Float64}(undef, W.d, W.N, S); α = Matrix{Float64}(undef, W.N, S); σ = similar(α); st = zeros(Cint, S)
+    GC.@preserve W check(ccall((:boss_nfit_values, lib), Cint, (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}),
+        W.h, S, Θ, λ, α, σ, st))
+    return λ, α, σ, st
+end
+"(ℓ S, ∂ℓ/∂θ T×S, status S): the data log-likelihood of every column of θ and its gradient (`boss_nfit_loglike_grad`); -Inf and zeros where a set fails"
+function loglike_grad(W::HipWhitened, θ::AbstractMatrix{<:Real})
+    Θ = Matrix{Float64}(θ); S = size(Θ, 2)
+    ll = Vector{Float64}(undef, S); g = Matrix{Float64}(undef, W.T, S); st = zeros(Cint, S)
+    GC.@preserve W check(ccall((:boss_nfit_loglike_grad, lib), Cint, (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}),
+        W.h, S, Θ, ll, g, st))
+    return ll, g, st
+end
+
 # ---------------------------------------------------------------- entry points of include/bosship.h this glue does not call
 # (tests/test_abi_and_host.py checks that every exported symbol is either bound above or listed here with its reason)
 # not bound: boss_set_stream — runs the library on a caller's HIP stream (torch / AMDGPU.jl interop); BOSS.jl itself owns no stream

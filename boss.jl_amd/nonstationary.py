@@ -712,3 +712,219 @@ def nonstationary_acq_ei_grad_batch(posts: Sequence[Sequence[HipNonstationaryPos
     ms = None if all(m is None for m in means) else np.stack([np.zeros(M) if m is None else m for m in means])
     mg = None if mean_grad is None else np.asarray(mean_grad, float).reshape(n, d, M)
     return api.ngp_acq_ei_grad_set([[p.gp for p in row] for row in posts], Xs, lam, amp, Dl, Da, fit_coefs, y_max, best, valid_mask, ms, mg)
+
+
+# ---------------------------------------------------------------------------------------------
+# HipNonstationaryModel — the reference's NonstationaryGP STRUCT (nonstationary_gp.jl:60-110) with latent MODELS in place of the
+# closures of HipNonstationaryGP: what a model fitter moves are the whitened outputs yϵ of the latent ParametrizedGPs (and the scalar
+# parameters of distribution latents); the data log-likelihood and its gradient w.r.t. those run on the device (api.NgpWhitened).
+# ---------------------------------------------------------------------------------------------
+@dataclass
+class HipNonstationaryParams:
+    """NonstationaryGPParams(λ, α, σ) (nonstationary_gp.jl:112-130): per output i the d lengthscale latents lam[i][l], the amplitude
+    latent amp[i] and the noise latent noise[i]; each a HipParametrizedGPParams or a float (a distribution latent's value)."""
+    lam: List[List[object]]
+    amp: List[object]
+    noise: List[object]
+
+    def latents(self, i):
+        return list(self.lam[i]) + [self.amp[i], self.noise[i]]
+
+
+@dataclass
+class HipNonstationaryModel:
+    """Per output i: lengthscale_models[i][l] (l < d), amplitude_models[i], noise_std_models[i] — each a HipParametrizedGP whose
+    transform device_spec() describes, or a univariate prior of problem.py (Dirac, LogNormal: the latent is that one number at every
+    point, `_param_posterior_slice` of a UnivariateDistribution, nonstationary_gp.jl:200-203)."""
+    lengthscale_models: Sequence[Sequence[object]]
+    amplitude_models: Sequence[object]
+    noise_std_models: Sequence[object]
+    mean: Optional[Sequence[Optional[Callable]]] = None
+    discrete: Optional[Sequence[bool]] = None
+    device: int = 0
+    resident_latents: bool = False                              # of the HipNonstationaryGP model_posterior builds
+
+    def __post_init__(self):
+        self._handles = {}
+        for i in range(self.y_dim):
+            for q, m in enumerate(self._models(i)):
+                if isinstance(m, HipParametrizedGP) and m.device_spec() is None:
+                    raise ValueError(f"resident_latents: the transform of latent {self._name(i, q)} (target_dist {m.target_dist!r}, "
+                                     f"act_func {m.act_func!r}) is not one the device evaluates")
+
+    @property
+    def y_dim(self):
+        return len(self.amplitude_models)
+
+    def _models(self, i):
+        return list(self.lengthscale_models[i]) + [self.amplitude_models[i], self.noise_std_models[i]]
+
+    def _name(self, i, q):
+        d = len(self.lengthscale_models[i])
+        return f"lengthscale_models[{i}][{q}]" if q < d else ("amplitude_models", "noise_std_models")[q - d] + f"[{i}]"
+
+    # ---- priors
+    def params_sampler(self, data: ExperimentData):
+        """_params_sampler (nonstationary_gp.jl:281-300): every ParametrizedGP latent through HipParametrizedGP.params_sampler (L, μ;
+        latents with the same kernel, lengthscales and noise share one factor), every distribution latent through rand."""
+        shared = {}
+
+        def one(m):
+            if not isinstance(m, HipParametrizedGP):
+                return lambda rng: float(m.rand(rng))
+            key = (m.kernel, tuple(np.asarray(m.lengthscale, float)), float(m.noise_std), m.device)
+            if key not in shared:
+                shared[key] = m.params_sampler(data)
+            return shared[key]
+        samplers = [[one(m) for m in self._models(i)] for i in range(self.y_dim)]
+
+        def sample(rng):
+            vals = [[s(rng) for s in row] for row in samplers]
+            return HipNonstationaryParams([v[:-2] for v in vals], [v[-2] for v in vals], [v[-1] for v in vals])
+        return sample
+
+    def params_loglike(self, data: ExperimentData = None):
+        """params_loglike (nonstationary_gp.jl:250-279): Σ over the latents — logpdf(MvNormal(0, I), yϵ) or the prior's logpdf."""
+        def ll(p: HipNonstationaryParams):
+            tot = 0.0
+            for i in range(self.y_dim):
+                for m, v in zip(self._models(i), p.latents(i)):
+                    tot += m.params_loglike(data)(v) if isinstance(m, HipParametrizedGP) else float(m.logpdf(v))
+            return tot
+        return ll
+
+    # ---- the flat parameter vector
+    def _layout(self, data: ExperimentData):
+        """[(i, q, start, length)] in the order of vectorizer (nonstationary_gp.jl:302-330): all λ latents (output after output),
+        then all α, then all σ."""
+        N = data.X.shape[1]
+        d = data.X.shape[0]
+        order = [(i, q) for i in range(self.y_dim) for q in range(d)] + [(i, d) for i in range(self.y_dim)] + \
+                [(i, d + 1) for i in range(self.y_dim)]
+        out, at = [], 0
+        for i, q in order:
+            n = N if isinstance(self._models(i)[q], HipParametrizedGP) else 1
+            out.append((i, q, at, n))
+            at += n
+        return out, at
+
+    def vectorizer(self, data: ExperimentData):
+        """(vectorize(params) -> vector, devectorize(params, vector) -> params): yϵ of the ParametrizedGP latents and the values of
+        the distribution latents (Dirac-fixed ones included: a fitter leaves them where they are)."""
+        layout, T = self._layout(data)
+
+        def vectorize(p: HipNonstationaryParams):
+            v = np.zeros(T)
+            for i, q, at, n in layout:
+                x = p.latents(i)[q]
+                v[at:at + n] = x.yeps if isinstance(x, HipParametrizedGPParams) else float(x)
+            return v
+
+        def devectorize(p: HipNonstationaryParams, v):
+            v = np.asarray(v, float)
+            rows = [p.latents(i) for i in range(self.y_dim)]
+            for i, q, at, n in layout:
+                x = rows[i][q]
+                rows[i][q] = HipParametrizedGPParams(x.X, x.mu, x.L, v[at:at + n].copy(), x.lengthscale) \
+                    if isinstance(x, HipParametrizedGPParams) else float(v[at])
+            return HipNonstationaryParams([r[:-2] for r in rows], [r[-2] for r in rows], [r[-1] for r in rows])
+        return vectorize, devectorize
+
+    # ---- the data term on the device
+    def _handle(self, data: ExperimentData, template: HipNonstationaryParams, i: int) -> api.NgpWhitened:
+        """The resident whitening of output i (api.NgpWhitened), built from the template's L and μ and kept while the same data
+        and factors come back (a fit asks for it once per round)."""
+        lat = template.latents(i)
+        gps = [x for x in lat if isinstance(x, HipParametrizedGPParams)]
+        ent = self._handles.get(i)
+        if ent is not None and ent[0] is data.X and ent[1] is data.Y and len(ent[2]) == len(gps) and \
+                all(a.L is b.L and a.mu is b.mu for a, b in zip(ent[2], gps)):
+            return ent[3]
+        if ent is not None:
+            ent[3].close()
+        N = data.X.shape[1]
+        factors, factor_of, specs = [], [], []
+        mu = np.zeros((N, len(lat)), order="F")
+        for q, (m, x) in enumerate(zip(self._models(i), lat)):
+            if not isinstance(x, HipParametrizedGPParams):
+                factor_of.append(-1)
+                specs.append(None)
+                continue
+            f = next((k for k, L in enumerate(factors) if L is x.L), None)
+            if f is None:
+                factors.append(x.L)
+                f = len(factors) - 1
+            factor_of.append(f)
+            specs.append(m.device_spec())
+            mu[:, q] = x.mu
+        mean = None if self.mean is None or self.mean[i] is None else np.array([float(self.mean[i](data.X[:, j])) for j in range(N)])
+        h = api.NgpWhitened(data.X, data.Y[i], factors, factor_of, specs, mu, mean, self.discrete, self.device)
+        self._handles[i] = (data.X, data.Y, gps, h)
+        return h
+
+    def _theta_rows(self, data, i):
+        layout, _ = self._layout(data)
+        d = data.X.shape[0]
+        by_q = {q: (at, n) for ii, q, at, n in layout if ii == i}
+        return np.concatenate([np.arange(by_q[q][0], by_q[q][0] + by_q[q][1]) for q in range(d + 2)])
+
+    def data_loglike_grad_vec(self, data: ExperimentData, template: HipNonstationaryParams, Theta, want_grad: bool = True):
+        """The data log-likelihood (summed over the outputs) of every column of Theta (vectorizer layout, T×S) and its gradient
+        w.r.t. Theta: ONE boss_nfit_loglike_grad call per output for all columns.  L, μ come from `template`.  Returns (ℓ[S],
+        grad[T, S] or None); -Inf and a zero column where a set is invalid or not PD in any output."""
+        Theta = np.asarray(Theta, float)
+        if Theta.ndim == 1:
+            Theta = Theta[:, None]
+        S = Theta.shape[1]
+        tot = np.zeros(S)
+        G = np.zeros(Theta.shape) if want_grad else None
+        for i in range(self.y_dim):
+            rows = self._theta_rows(data, i)
+            ll, st, gr = self._handle(data, template, i).loglike_grad(Theta[rows, :], want_grad)
+            tot += np.where(st == api.BOSS_OK, ll, -np.inf)
+            if want_grad:
+                G[rows, :] = gr
+        bad = ~np.isfinite(tot)
+        tot[bad] = -np.inf
+        if want_grad:
+            G[:, bad] = 0.0
+        return tot, G
+
+    def data_loglike_grad_batch(self, data: ExperimentData, params_list: Sequence[HipNonstationaryParams]):
+        """data_loglike (nonstationary_gp.jl:234-248) of S parameter sets that share L and μ (the draws of one params_sampler, the
+        iterates of a fit) and its gradient in the vectorizer's layout: (ℓ[S], grad[T, S])."""
+        params_list = list(params_list)
+        if not params_list:
+            return np.zeros(0), np.zeros((self._layout(data)[1], 0))
+        vec, _ = self.vectorizer(data)
+        return self.data_loglike_grad_vec(data, params_list[0], np.stack([vec(p) for p in params_list], axis=1))
+
+    def data_loglike_batch(self, data: ExperimentData, params_list: Sequence[HipNonstationaryParams]) -> np.ndarray:
+        params_list = list(params_list)
+        if not params_list:
+            return np.zeros(0)
+        vec, _ = self.vectorizer(data)
+        return self.data_loglike_grad_vec(data, params_list[0], np.stack([vec(p) for p in params_list], axis=1), want_grad=False)[0]
+
+    # ---- the fitted model
+    def posterior_model(self, params: HipNonstationaryParams, data: ExperimentData) -> HipNonstationaryGP:
+        """The HipNonstationaryGP whose closures are the latents' posteriors (`_param_posterior_slice`, nonstationary_gp.jl:200-214)."""
+        def post(m, x):
+            return m.model_posterior(x, data) if isinstance(m, HipParametrizedGP) else constant_latent(float(x))
+        f_lam, f_amp, f_noise = [], [], []
+        for i in range(self.y_dim):
+            posts = [post(m, x) for m, x in zip(self._models(i), params.latents(i))]
+            f_lam.append(stack_latents(posts[:-2]))
+            f_amp.append(posts[-2])
+            f_noise.append(posts[-1])
+        return HipNonstationaryGP(f_lam, f_amp, f_noise, self.mean, self.discrete, self.device, self.resident_latents)
+
+    def model_posterior(self, params: HipNonstationaryParams, data: ExperimentData) -> List[HipNonstationaryPosteriorSlice]:
+        """model_posterior (nonstationary_gp.jl:140-157): the slices of the fitted model — prediction, resident latents, append and
+        tracks work on them as on any HipNonstationaryGP's."""
+        return self.posterior_model(params, data).model_posterior(data)
+
+    def close(self):
+        for ent in self._handles.values():
+            ent[3].close()
+        self._handles = {}

@@ -574,6 +574,49 @@ int boss_ngp_acq_ei_grad_set_lat(int P, int S, boss_gp_t* const* gps, int M, con
                                  const double* mean_Xs, const double* mean_grad, const double* fit_coefs, const double* y_max,
                                  int has_best, double best, const unsigned char* valid_mask, double* acq_out, double* dacq_out);
 
+/* ---- the nonstationary likelihood in whitened latent parameters -------------------------------------
+ * A fitter of the reference does not move lam(x_j), alpha(x_j), sigma(x_j) but the whitened outputs y_eps of the latent
+ * ParametrizedGPs (ParametrizedGPParams(X, mu, L, y_eps, lam), parametrized_gp.jl:49-77): the values at the data are
+ * (L*y_eps + mu) pushed through Normal-cdf -> target quantile -> activation (parametrized_gp.jl:108-120; the closed forms of
+ * boss_nlat_create).  A boss_nfit_t holds one output slice (X d×N, y, discrete, mean_X N values or NULL as boss_ngp_loglike_batch
+ * takes them) and the latents' whitening resident, and evaluates data_loglike_slice (nonstationary_gp.jl:237-248) and its gradient
+ * w.r.t. the whitened parameters of S parameter sets in one call: de-whitening, transform, Gibbs likelihood, its gradient and the
+ * pull-back L'(c .* v') all on the device (nfit_kernels.hpp).
+ *   factors    N×N×n_factors, column-major; the LOWER triangle of each is L of parametrized_gp.jl:200-202 (the rest is not read);
+ *   factor_of  d+2 entries in latent order lam_0..lam_{d-1}, alpha, sigma: index into factors, or -1 = a scalar latent; latents
+ *              with the same kernel and lengthscales share one uploaded factor;
+ *   mu         N×(d+2), column q = mu of latent q (ignored for scalar latents), or NULL = zeros;
+ *   target, target_par, act, act_par: d+2 (2(d+2)) entries as boss_nlat_create takes them, read for GP latents only.
+ * theta T×S: column s holds the latents in order; a GP latent contributes its N values of y_eps, a scalar latent one number that is
+ * its value at every point as given, without transform (_param_posterior_slice of a distribution latent,
+ * nonstationary_gp.jl:200-207).  T = sum_q (N or 1) (boss_nfit_param_count).
+ * Point j gets value j of its latent.  (The reference looks values up in a Dict keyed by the point, so of two identical columns
+ * of X the last one's value would serve both; that is not emulated.)
+ * boss_nfit_values: the lookup values in the layouts boss_ngp_update / boss_ngp_loglike_batch take (lam_out d×N×S, amp_out N×S,
+ *   noise_out N×S), as computed (also for invalid sets); status_out S entries (BOSS_OK / BOSS_E_INVALID) or NULL.
+ * boss_nfit_loglike_grad: ll_out[s] = the DATA term (params_loglike, logpdf(MvNormal(0, I), y_eps), stays with the caller);
+ *   grad_out NULL or T×S: for a GP latent L_f'(c_q .* v'_q) with c_q the cotangent row of boss_ngp_loglike_grad (dlam rows, damp,
+ *   dnoise), for a scalar latent sum_j c_q[j].  ll_out and status_out equal bit for bit what boss_ngp_loglike_batch returns for the
+ *   arrays of boss_nfit_values: the device kernels write the very parameter blocks the array form uploads.  A set with a
+ *   lengthscale that is not finite and > 0, an amplitude or noise that is not finite and >= 0, or a NaN in theta gets
+ *   BOSS_E_INVALID, -Inf and a zero gradient column (a flag the kernel raises); not-PD sets as in boss_ngp_loglike_grad_batch; the
+ *   other sets are unaffected.  A set's results do not depend on S, its position or its neighbours; no floating-point atomics.
+ *   BOSS_MODEL_BATCH_CHUNK_MB chunks the call as it chunks the batched likelihoods; one upload of theta and one copy back of the
+ *   gradients per chunk.  S = 0 is a no-op.  d <= 16.
+ * Memory: the handle keeps every factor AND its transpose (the pull-back runs the same tile core on the transposed copy):
+ * 2·8·Nk² bytes per factor, Nk = N rounded up to 64; per call 3·8·Nk·(columns rounded up to 32 per factor) bytes of chunk buffers,
+ * columns = GP latents × sets of the chunk.  Arguments out of range, NULL arrays, unknown codes: BOSS_E_INVALID before any device
+ * work; factors that do not fit: BOSS_E_ALLOC, nothing is left behind. */
+typedef struct boss_nfit boss_nfit_t;
+int boss_nfit_create(int device, int d, int N, const double* X, const double* y, const unsigned char* discrete, const double* mean_X,
+                     int n_factors, const double* factors, const int* factor_of, const double* mu, const int* target,
+                     const double* target_par, const int* act, const double* act_par, boss_nfit_t** out);
+void boss_nfit_free(boss_nfit_t* fit);
+int boss_nfit_param_count(const boss_nfit_t* fit, int* T_out);
+int boss_nfit_values(boss_nfit_t* fit, int S, const double* theta, double* lam_out, double* amp_out, double* noise_out,
+                     int* status_out);
+int boss_nfit_loglike_grad(boss_nfit_t* fit, int S, const double* theta, double* ll_out, double* grad_out, int* status_out);
+
 /* ---- tracked candidates -----------------------------------------------------------------------
  * SequentialBatchAM (src/acquisition_maximizers/batch.jl:26-38) re-evaluates the acquisition on
  * the whole candidate set after every speculative observation; with a FIXED candidate set (GridAM
