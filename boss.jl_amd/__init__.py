@@ -7,11 +7,11 @@ the repo-root shim:  `import boss_jl_amd`.
 """
 from . import api  # noqa: F401
 from .api import (BossError, Candidates, DomainError, GP, PosDefException, acq_ei, fit,  # noqa: F401
-                  ggp_fit_batch, ggp_loglike_batch, load_library, loglike_batch, ngp_fit_batch, ngp_loglike_batch,
+                  ggp_fit_batch, ggp_loglike_batch, load_library, loglike_batch, loglike_grad_batch_mean, ngp_fit_batch, ngp_loglike_batch,
                   ngp_acq_ei_grad_set, ngp_predict_grad_set, ngp_predict_set, NgpLatents, ngp_acq_ei_grad_set_lat,
                   ngp_predict_grad_set_lat, ngp_predict_set_lat, NgpWhitened)
 from .problem import (BossOptions, BossProblem, Dirac, Domain, ExperimentData, ExpectedImprovement,  # noqa: F401,E402
-                      LinFitness, LogNormal, MvDirac, MvLogNormal, NonlinFitness)
+                      LinFitness, LogNormal, MvDirac, MvLogNormal, NonlinFitness, Normal)
 from .model import HipGaussianProcess, HipGPParams, average_mean  # noqa: F401,E402
 from .gradient_gp import (GradientData, HipGradientGaussianProcess, HipGradientGPParams,  # noqa: F401,E402
                           gradient_sequential_batch, join_gradient_slices)

@@ -49,6 +49,7 @@ SIGNATURES = {
                               _c_ucp, C.POINTER(C.c_void_p), _c_dp]),
     "boss_gp_set_y": (C.c_int, [C.c_void_p, _c_dp]),
     "boss_gp_loglike_grad": (C.c_int, [C.c_void_p, _c_dp, _c_dp]),
+    "boss_gp_loglike_grad_mean": (C.c_int, [C.c_void_p, _c_dp, _c_dp, _c_dp]),
     "boss_gp_reserve": (C.c_int, [C.c_void_p, C.c_int]),
     "boss_gp_n": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "boss_gp_append": (C.c_int, [C.c_void_p, C.c_int, _c_dp, _c_dp, _c_dp, _c_dp]),
@@ -58,6 +59,9 @@ SIGNATURES = {
                                         C.c_int, _c_dp, _c_dp, _c_dp, _c_dp, C.POINTER(C.c_int)]),
     "boss_gp_loglike_grad_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _c_dp, _c_dp, _c_dp, C.c_int, _c_ucp,
                                              C.c_int, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, C.POINTER(C.c_int)]),
+    "boss_gp_loglike_grad_batch_mean": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _c_dp, _c_dp, _c_dp, C.c_int, _c_ucp,
+                                                  C.c_int, _c_dp, _c_dp, _c_dp, C.c_int, _c_dp, C.c_int, _c_dp, _c_dp, _c_dp, _c_dp,
+                                                  C.POINTER(C.c_int)]),
     "boss_ggp_loglike_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _c_dp, _c_dp, _c_dp, C.c_int, _c_dp, _c_dp, _c_dp,
                                          _c_dp, _c_dp, C.POINTER(C.c_int)]),
     "boss_ngp_loglike_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, _c_dp, _c_dp, _c_ucp, C.c_int, _c_dp, _c_dp, _c_dp, _c_dp,
@@ -320,6 +324,18 @@ class GP:
         grad = np.zeros(self.d + 2)
         _check(load_library().boss_gp_loglike_grad(self._h, C.byref(out), _dp(grad)))
         return out.value, grad
+
+    def loglike_grad_mean(self):
+        """(logpdf, grad[d+2], dmean[N]): loglike_grad plus ∂logpdf/∂(prior mean value at x_j) = (K⁻¹(y − m))_j at the handle's current N
+        observations.  With the Jacobian J (N×T) of the mean values w.r.t. the parameters θ of a parametric mean, ∂logpdf/∂θ = Jᵀ dmean."""
+        lib = load_library()
+        n = C.c_int(0)
+        _check(lib.boss_gp_n(self._h, C.byref(n)))
+        out = C.c_double(0.0)
+        grad = np.zeros(self.d + 2)
+        dmean = np.zeros(n.value)
+        _check(lib.boss_gp_loglike_grad_mean(self._h, C.byref(out), _dp(grad), _dp(dmean)))
+        return out.value, grad, dmean
 
     def reserve(self, N_total: int):
         """Reserve storage for N_total observations (later appends need no re-allocation); the handle
@@ -1022,6 +1038,62 @@ def loglike_batch(X, y, kernel, lengthscales, amplitudes, noise_stds, mean_X=Non
                                                 _ucp(disc), S, _dp(lam), _dp(amp), _dp(sig), _dp(ll),
                                                 st.ctypes.data_as(C.POINTER(C.c_int))))
     return ll, st
+
+
+def loglike_grad_batch_mean(X, y, kernel, lengthscales, amplitudes, noise_stds, mean_X=None, mean_jac=None, discrete=None,
+                            device: int = 0, want_dmean: bool = False):
+    """loglike_batch(..., want_grad=True) plus the gradient through the prior mean (boss_gp_loglike_grad_batch_mean).
+    mean_X: None, N values shared by all sets, or S×N (row s = set s).  mean_jac: None, the Jacobian of the mean values w.r.t. T
+    parameters of the mean as N×T (one matrix shared by all sets: a mean that is linear in them) or S×N×T (one per set).
+    Returns (ll[S], status[S], grad[(d+2), S], dmean, dtheta): dmean N×S (column s = K⁻¹(y − m) of set s) if want_dmean else None,
+    dtheta T×S (column s = mean_jac(s)ᵀ dmean(s), folded on the device) if mean_jac is given else None; zero columns where the
+    status is not BOSS_OK."""
+    X = _f64(X, 2)
+    y = _f64(np.asarray(y).reshape(-1), 1)
+    lam = _f64(lengthscales, 2)
+    d, N = X.shape
+    S = lam.shape[1]
+    if lam.shape[0] != d:
+        raise BossError(BOSS_E_INVALID, "lengthscales must be d×S")
+    amp = _f64(np.asarray(amplitudes).reshape(-1), 1)
+    sig = _f64(np.asarray(noise_stds).reshape(-1), 1)
+    if y.shape[0] != N or amp.shape[0] != S or sig.shape[0] != S:
+        raise ValueError("y must have N entries, amplitudes and noise_stds S each")
+    stride = 0
+    m = None
+    if mean_X is not None:
+        m = np.asarray(mean_X, dtype=np.float64)
+        if m.ndim == 2:
+            if m.shape != (S, N):
+                raise ValueError("mean_X must be S×N (one prior-mean row per set) or a vector of N entries")
+            m = np.ascontiguousarray(m)
+            stride = N
+        else:
+            m = np.ascontiguousarray(m.reshape(-1))
+            if m.shape[0] != N:
+                raise ValueError("mean_X must be S×N (one prior-mean row per set) or a vector of N entries")
+    T, jac, jac_stride = 0, None, 0
+    if mean_jac is not None:
+        jac = np.asarray(mean_jac, dtype=np.float64)
+        if jac.ndim == 2 and jac.shape[0] == N and jac.shape[1] >= 1:
+            T = jac.shape[1]
+            jac = np.ascontiguousarray(jac.T)                  # N×T column-major
+        elif jac.ndim == 3 and jac.shape[:2] == (S, N) and jac.shape[2] >= 1:
+            T = jac.shape[2]
+            jac = np.ascontiguousarray(jac.transpose(0, 2, 1))  # set after set, each N×T column-major
+            jac_stride = N * T
+        else:
+            raise ValueError("mean_jac must be N×T (shared by all sets) or S×N×T, T >= 1")
+    disc = None if discrete is None else np.ascontiguousarray(np.asarray(discrete, dtype=bool).astype(np.uint8))
+    ll = np.zeros(S)
+    st = np.zeros(S, dtype=np.int32)
+    grad = np.zeros((d + 2, S), order="F")
+    dmean = np.zeros((N, S), order="F") if want_dmean else None
+    dtheta = np.zeros((T, S), order="F") if T else None
+    _check(load_library().boss_gp_loglike_grad_batch_mean(device, _kernel_id(kernel), d, N, _dp(X), _dp(y), _dp(m), stride, _ucp(disc), S,
+                                                          _dp(lam), _dp(amp), _dp(sig), T, _dp(jac), jac_stride, _dp(ll), _dp(grad),
+                                                          _dp(dmean), _dp(dtheta), st.ctypes.data_as(C.POINTER(C.c_int))))
+    return ll, st, grad, dmean, dtheta
 
 
 def _ggp_batch_args(X, y, dY, lengthscales, amplitudes, noise_stds, grad_noise_stds):

@@ -585,6 +585,15 @@ struct SetBatch {
     size_t sA = 0, sInv16 = 0, sDinv = 0, sDinv2 = 0, sW = 0, sX = 0;
     size_t sPar = 0;                           // the gradient / nonstationary model's parameter block (likelihood-gradient batches)
 };
+// what a gradient pass leaves of a = K⁻¹(y − m) besides ‖a‖² (boss_gp_loglike_grad_mean, boss_gp_loglike_grad_batch_mean): the
+// pointers are those of the pass's first set, the sets of a group lie sJ / N / T doubles apart (mean_fold_kernel)
+struct MeanFold {
+    const double* J = nullptr;                 // N×T column-major Jacobian of the prior mean values (null or T = 0: no fold)
+    size_t sJ = 0;                             // N·T, or 0 for one matrix shared by all sets
+    int T = 0;
+    double* dmean = nullptr;                   // N per set, or null
+    double* dtheta = nullptr;                  // T per set, or null
+};
 static void linv_enqueue(boss_gp* g, hipStream_t s, double* U, double* Lw, const SetBatch& B = SetBatch());
 // largest system the entry points accept: element offsets into the factor stay below 2^31 (exercised up to
 // 36 864 rows = 10.9 GB by the tests)

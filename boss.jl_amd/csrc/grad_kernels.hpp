@@ -1227,6 +1227,48 @@ __global__ __launch_bounds__(256) void avec_partial_kernel(const double* __restr
     partial[(size_t)ch * Np + i] = s;
 }
 
+// The gradient through the prior mean, ∂ℓ/∂m = a = K⁻¹(y − m) (boss_gp_loglike_grad_mean, boss_gp_loglike_grad_batch_mean): a_j is the
+// sum of avec_partial_kernel's nch partials in chunk order (as every consumer above sums them), for j < N only — the padded rows are
+// never read.  dmean[j] = a_j (workgroups of the first column block), dtheta[t] = Σ_{j<N} J[j + N·t] a_j for the N×T column-major
+// Jacobian J of the mean values w.r.t. T parameters of the mean: j is the contiguous index, a wave reads 64 consecutive doubles.
+// One workgroup per (MFOLD_COLS columns, set); blockIdx.z: set of a batch (strides zP, zJ, N, T).  Fixed order throughout — each
+// thread's rows j = tid, tid + 256, …, the wave's butterfly, the four wave partials as (w0 + w1) + (w2 + w3) — and no atomics: a
+// set's result depends on its partials and its Jacobian alone, not on where in a batch it stands.
+// Memory-bound on J (N·T·8 bytes per set, read once; the partials are re-read per column block from L2).
+constexpr int MFOLD_THREADS = 256, MFOLD_COLS = 4;
+__global__ __launch_bounds__(MFOLD_THREADS) void mean_fold_kernel(const double* __restrict__ apart, int nch, int Np, int N,
+                                                                  const double* __restrict__ J, int T, double* __restrict__ dmean,
+                                                                  double* __restrict__ dtheta, size_t zP, size_t zJ) {
+    apart += (size_t)blockIdx.z * zP;
+    __shared__ double red[MFOLD_THREADS / 64][MFOLD_COLS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int t0 = blockIdx.x * MFOLD_COLS;
+    const int nt = (T - t0 < MFOLD_COLS) ? T - t0 : MFOLD_COLS;      // (<= 0: the block that only writes dmean when T = 0)
+    const double* Jc = J ? J + (size_t)blockIdx.z * zJ + (size_t)t0 * N : nullptr;
+    double* dm = (dmean && blockIdx.x == 0) ? dmean + (size_t)blockIdx.z * N : nullptr;
+    double acc[MFOLD_COLS];
+#pragma unroll
+    for (int q = 0; q < MFOLD_COLS; ++q) acc[q] = 0.0;
+    for (int j = tid; j < N; j += MFOLD_THREADS) {
+        double a = 0.0;
+        for (int c = 0; c < nch; ++c) a += apart[(size_t)c * Np + j];
+        if (dm) dm[j] = a;
+#pragma unroll
+        for (int q = 0; q < MFOLD_COLS; ++q)
+            if (q < nt) acc[q] = __builtin_fma(Jc[(size_t)q * N + j], a, acc[q]);
+    }
+    if (!dtheta || nt <= 0) return;                          // (uniform over the workgroup)
+#pragma unroll
+    for (int q = 0; q < MFOLD_COLS; ++q) {
+        double v = acc[q];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+        if (lane == 0) red[wave][q] = v;
+    }
+    __syncthreads();
+    if (tid < nt) dtheta[(size_t)blockIdx.z * T + t0 + tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
+}
+
 constexpr int LLG_MAX_D = 32;
 // out[tile][0..d-1] = Σ_{i>j in tile} G_ij α² h(r_ij) Δu²_ij,m ;  out[tile][d] = Σ_i K⁻¹_ii , out[tile][d+1] = Σ_i a_i²  (diagonal tiles)
 __global__ __launch_bounds__(256) void llgrad_tile_kernel(const double* __restrict__ Xsc, int d, int N, int Np, int kern,

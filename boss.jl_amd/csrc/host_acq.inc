@@ -189,7 +189,9 @@ extern "C" int boss_acq_ei_moments(int device, int P, int S, int M, const double
 // Device part for one factorised posterior (a handle, or a view into a batch): Σ-vector {S_1..S_d, tr K⁻¹, ‖a‖²} into
 // sums_out (device, d+2 doubles).  The per-device workspaces are reused call after call: everything runs in order on s.
 static int llgrad_enqueue(boss_gp* g, hipStream_t s, double* sums_out, int bank, const SetBatch& B, const double* amp2_dev,
-                          int amp2_stride) {
+                          int amp2_stride, const MeanFold* mf) {
+    // mf: null, or where a = K⁻¹(y − m) and its fold with the mean's Jacobian go (mean_fold_kernel, right behind the partials of a on
+    //    the same stream: the bank's workspace is not reused before it has run);
     // bank: which set of workspaces (the batched entry point rotates large sets over several streams);
     // B: nb equally shaped posteriors behind g's pointers (small sets: every launch covers the whole group in grid.z),
     //    α² of set b at amp2_dev[b · amp2_stride], its Σ-vector at sums_out + b (d+2); the gradient-observation model's sets have
@@ -234,6 +236,12 @@ static int llgrad_enqueue(boss_gp* g, hipStream_t s, double* sums_out, int bank,
                        Kinv, ld, Bw.sW);
     hipLaunchKernelGGL(avec_partial_kernel, dim3(Np / 256, nch, nb), dim3(256), 0, s, (const double*)LinvT, ld, Np, N,
                        (const double*)g->A, ld, apart, Bw.sW, B.sA, nb > 1 ? sC : (size_t)0);
+    if (mf && (mf->dmean || (mf->dtheta && mf->T > 0))) {
+        const int T = mf->dtheta ? mf->T : 0;
+        hipLaunchKernelGGL(mean_fold_kernel, dim3(std::max(1, (T + MFOLD_COLS - 1) / MFOLD_COLS), 1, nb), dim3(MFOLD_THREADS), 0, s,
+                           (const double*)apart, nch, Np, N, T ? mf->J : (const double*)nullptr, T, mf->dmean, T ? mf->dtheta : (double*)nullptr,
+                           nb > 1 ? sC : (size_t)0, mf->sJ);
+    }
     const size_t zC = nb > 1 ? sC : (size_t)0, zPar = nb > 1 ? B.sPar : (size_t)0;
     if (g->gibbs) {
         // per-point partial derivatives (boss_ngp_loglike_grad): sums_out holds (d + 3) rows of Np per set
@@ -268,14 +276,16 @@ static void llgrad_finalize(int d, int N, const double* invlam, double amp2, dou
 }
 
 // The sums of one fitted handle on the host (h.size() doubles, see llgrad_enqueue): through the context's prediction workspace, one
-// copy back, one synchronisation.  Caller holds the context's lock.
-static int llgrad_download(boss_gp* g, std::vector<double>& h) {
+// copy back, one synchronisation.  n_mean > 0: the last n_mean doubles of h receive a = K⁻¹(y − m).  Caller holds the context's lock.
+static int llgrad_download(boss_gp* g, std::vector<double>& h, size_t n_mean = 0) {
     Ctx* c = g->ctx;
     hipStream_t s = c->stream;
     int rc = ws_reserve(c->pred, sizeof(double) * h.size());
     if (rc) return rc;
     double* sums = (double*)c->pred.p;
-    rc = llgrad_enqueue(g, s, sums, 0, SetBatch(), g->gibbs ? (const double*)nullptr : (const double*)g->hyp, 0);
+    MeanFold mf;
+    if (n_mean) mf.dmean = sums + (h.size() - n_mean);
+    rc = llgrad_enqueue(g, s, sums, 0, SetBatch(), g->gibbs ? (const double*)nullptr : (const double*)g->hyp, 0, n_mean ? &mf : nullptr);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(h.data(), sums, sizeof(double) * h.size(), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
@@ -299,7 +309,8 @@ extern "C" int boss_gp_loglike_grad(boss_gp_t* g, double* logpdf_out, double* gr
         dinv_join(g);
         hipLaunchKernelGGL(small_llgrad_kernel, dim3(1), dim3(DIAG_THREADS), SMALL_LLG_LDS_BYTES, s, (const double*)g->A, g->ld, g->Np,
                            g->N, d, g->kernel, g->amp2, (const double*)g->inv16, (const double*)g->Xsc, g->ldx, g->host_res_dev + 8, (size_t)0, (size_t)0,
-                           (size_t)0, (const double*)nullptr, 0, 0, ++g->res_seq);
+                           (size_t)0, (const double*)nullptr, 0, 0, ++g->res_seq, (const double*)nullptr, 0, (size_t)0, (double*)nullptr,
+                           (double*)nullptr);
         HIPCHK(hipGetLastError());
         {
             // (as in gp_finish: the kernel writes the Σ-vector, then this call's sequence number, into mapped host memory)
@@ -325,6 +336,43 @@ extern "C" int boss_gp_loglike_grad(boss_gp_t* g, double* logpdf_out, double* gr
     // host_par still holds the staged parameters of the last update: 1/(λ+1e-8), (α+1e-8)², (σ+1e-8)²
     llgrad_finalize(d, g->N, g->host_par, g->host_par[d], g->host_par[d + 1], g->host_res[1], h.data(), grad_out);
     if (logpdf_out) *logpdf_out = loglik(g->N, g->host_res[0], g->host_res[1]);
+    return BOSS_OK;
+}
+
+// boss_gp_loglike_grad plus ∂logpdf/∂mean_X[j] = (K⁻¹(y − m))_j — what carries the likelihood's gradient into the parameters of a
+// Semiparametric model's mean (src/models/semiparametric.jl:79-92 under OptimizationMAP's AD, src/model_fitters/optimization.jl:146-164).
+// Both paths keep a on the device anyway; here it comes back with the Σ-vector in one copy and one synchronisation.
+extern "C" int boss_gp_loglike_grad_mean(boss_gp_t* g, double* logpdf_out, double* grad_out, double* dmean_out) {
+    if (!g || !grad_out || !dmean_out) return fail(BOSS_E_INVALID, "NULL argument");
+    NOT_FOR_AUG(g);                                          // (the nonstationary model has boss_ngp_loglike_grad's dmean_out)
+    Ctx* c = g->ctx;
+    HIPCHK(hipSetDevice(c->device));
+    std::lock_guard<std::mutex> lk(c->mtx);
+    int rc = gp_settle(g);
+    if (rc) return rc;
+    const int d = g->d, nv = d + 2, N = g->N;
+    if (d > LLG_MAX_D) return fail(BOSS_E_INVALID, "x_dim too large for the likelihood-gradient kernel");
+    hipStream_t s = c->stream;
+    std::vector<double> h((size_t)nv + N);
+    if (small_fit_ok(c, N, d)) {
+        // N <= 128: the one-launch kernel, its results in device memory this time (N + d + 2 doubles, one copy back)
+        rc = ws_reserve(c->pred, sizeof(double) * h.size());
+        if (rc) return rc;
+        double* sums = (double*)c->pred.p;
+        dinv_join(g);
+        hipLaunchKernelGGL(small_llgrad_kernel, dim3(1), dim3(DIAG_THREADS), SMALL_LLG_LDS_BYTES, s, (const double*)g->A, g->ld, g->Np, N, d,
+                           g->kernel, g->amp2, (const double*)g->inv16, (const double*)g->Xsc, g->ldx, sums, (size_t)0, (size_t)0, (size_t)0,
+                           (const double*)nullptr, 0, 0, 0ull, (const double*)nullptr, 0, (size_t)0, sums + nv, (double*)nullptr);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(h.data(), sums, sizeof(double) * h.size(), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+    } else {
+        rc = llgrad_download(g, h, (size_t)N);
+        if (rc) return rc;
+    }
+    llgrad_finalize(d, N, g->host_par, g->host_par[d], g->host_par[d + 1], g->host_res[1], h.data(), grad_out);
+    std::copy(h.begin() + nv, h.end(), dmean_out);
+    if (logpdf_out) *logpdf_out = loglik(N, g->host_res[0], g->host_res[1]);
     return BOSS_OK;
 }
 

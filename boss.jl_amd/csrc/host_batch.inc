@@ -5,7 +5,7 @@
 // batched log-likelihood
 // ------------------------------------------------------------------------------------------
 static int llgrad_enqueue(boss_gp* g, hipStream_t s, double* sums_out, int bank, const SetBatch& B, const double* amp2_dev,
-                          int amp2_stride);
+                          int amp2_stride, const MeanFold* mf = nullptr);
 static void llgrad_finalize(int d, int N, const double* invlam, double amp2, double sig2, double zz, const double* h, double* grad_out);
 static void ggp_llgrad_finalize(int d, const double* hp, const double* h, double* grad_out);
 
@@ -125,14 +125,25 @@ static int llgrad_group_size(bool grads, int Np, int ld, int chunk) {
 static size_t llgrad_dinv_one(int Np) { return (size_t)(Np / BLK) * BLK * BLK + (size_t)Np * PRED_RB; }
 static size_t llgrad_dinv_doubles(int group, int Np) { return group ? (size_t)std::max(group, (int)Ctx::LLG_BANKS) * llgrad_dinv_one(Np) : 0; }
 
+// set b's Jacobian and outputs from those of the chunk's first set
+static MeanFold mean_fold_of_set(const MeanFold& m, int N, int b) {
+    MeanFold r = m;
+    if (r.J) r.J += (size_t)b * m.sJ;
+    if (r.dmean) r.dmean += (size_t)b * N;
+    if (r.dtheta) r.dtheta += (size_t)b * m.T;
+    return r;
+}
+
 // The gradient passes of the nb factorised sets of a chunk (shared by the three models' batched likelihood gradients): in groups of
 // `group` sets, or — group = 1 — set after set over up to four streams, each on its own bank of workspaces, so that their small
 // kernels (low levels of the triangular inverse, reductions) overlap the other sets' large ones.  view(v, b, Dinv, Dinv2) makes v a
 // view of set b as a fitted handle; St holds the constant strides between sets; set b's results go to sums + b·sum_stride and its
-// α² (plain model) is read at amp2_dev[2 b].  Everything is complete on s's timeline when the function returns.
+// α² (plain model) is read at amp2_dev[2 b].  mf (plain model, may be null): the chunk's Jacobians and the outputs of the gradient
+// through the prior mean, set 0's; every set's fold runs behind its own partials of a, on that set's stream and bank.
+// Everything is complete on s's timeline when the function returns.
 static int llgrad_sets_enqueue(Ctx* c, hipStream_t s, int nb, int group, int Np, double* dinv_scratch, double* sums, size_t sum_stride,
                                const SetBatch& St, const double* amp2_dev,
-                               const std::function<void(boss_gp*, int, double*, double*)>& view) {
+                               const std::function<void(boss_gp*, int, double*, double*)>& view, const MeanFold* mf = nullptr) {
     const int nblk = Np / BLK;
     const size_t dinv_one = llgrad_dinv_one(Np);
     int rc = BOSS_OK;
@@ -144,7 +155,8 @@ static int llgrad_sets_enqueue(Ctx* c, hipStream_t s, int nb, int group, int Np,
             B.nb = std::min(group, nb - b0);
             B.sDinv = (size_t)nblk * BLK * BLK;
             B.sDinv2 = (size_t)Np * PRED_RB;
-            rc = llgrad_enqueue(&v, s, sums + (size_t)b0 * sum_stride, 0, B, amp2_dev ? amp2_dev + 2 * (size_t)b0 : nullptr, 2);
+            const MeanFold mb = mf ? mean_fold_of_set(*mf, v.N, b0) : MeanFold();
+            rc = llgrad_enqueue(&v, s, sums + (size_t)b0 * sum_stride, 0, B, amp2_dev ? amp2_dev + 2 * (size_t)b0 : nullptr, 2, mf ? &mb : nullptr);
             if (rc) {
                 (void)hipDeviceSynchronize();
                 return rc;
@@ -164,7 +176,9 @@ static int llgrad_sets_enqueue(Ctx* c, hipStream_t s, int nb, int group, int Np,
         boss_gp v;
         double* const dinv = dinv_scratch + (size_t)bank * dinv_one;
         view(&v, b, dinv, dinv + (size_t)nblk * BLK * BLK);
-        rc = llgrad_enqueue(&v, sb, sums + (size_t)b * sum_stride, bank, SetBatch(), amp2_dev ? amp2_dev + 2 * (size_t)b : nullptr, 0);
+        const MeanFold mb = mf ? mean_fold_of_set(*mf, v.N, b) : MeanFold();
+        rc = llgrad_enqueue(&v, sb, sums + (size_t)b * sum_stride, bank, SetBatch(), amp2_dev ? amp2_dev + 2 * (size_t)b : nullptr, 0,
+                            mf ? &mb : nullptr);
         if (rc) {
             (void)hipDeviceSynchronize();
             return rc;
@@ -178,11 +192,21 @@ static int llgrad_sets_enqueue(Ctx* c, hipStream_t s, int nb, int group, int Np,
 }
 
 // grad_out: null, or (d+2)×S — ∂logpdf/∂(λ_1..λ_d, α, σ) of every set (the factorisations run batched, the gradient passes set
-// after set on the shared workspaces)
+// after set on the shared workspaces).  mean (boss_gp_loglike_grad_batch_mean, with grad_out): the Jacobians of the prior means and
+// where ∂logpdf/∂mean_X (N×S) and its fold with them (T×S) go, host pointers; the Jacobians are staged per chunk as the means are,
+// and the two results come back in the chunk's copy-back behind the Σ-vectors.
+// BOSS_MODEL_BATCH_CHUNK_MB=<MB> (tests) lowers the 12 GiB limit as in model_loglike_batch_run below.
+struct BatchMeanGrad {
+    int T = 0;
+    const double* jac = nullptr;
+    int jac_stride = 0;
+    double* dmean_out = nullptr;
+    double* dtheta_out = nullptr;
+};
 static int loglike_batch_impl(int device, int kernel, int d, int N, const double* X, const double* y,
                               const double* mean_X, int mean_stride, const unsigned char* discrete, int S,
                               const double* lengthscales, const double* amplitudes, const double* noise_stds,
-                              double* ll_out, int* status_out, double* grad_out) {
+                              double* ll_out, int* status_out, double* grad_out, const BatchMeanGrad* mean = nullptr) {
     if (kernel < 0 || kernel > 2) return fail(BOSS_E_INVALID, "unknown kernel id");
     if (grad_out && d > LLG_MAX_D) return fail(BOSS_E_INVALID, "x_dim too large for the likelihood-gradient kernel");
     if (d < 1 || N < 1 || S < 0 || !X || !y || !ll_out) return fail(BOSS_E_INVALID, "bad arguments");
@@ -199,30 +223,38 @@ static int loglike_batch_impl(int device, int kernel, int d, int N, const double
     const size_t bstride = (size_t)ld * Np;
     // chunk the batch so the matrices stay below ~12 GiB
     size_t per = bstride * sizeof(double);
-    int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)S, ((size_t)12 << 30) / per));
+    static const double chunk_mb = getenv("BOSS_MODEL_BATCH_CHUNK_MB") ? atof(getenv("BOSS_MODEL_BATCH_CHUNK_MB")) : 12288.0;
+    int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)S, (size_t)(std::max(chunk_mb, 0.0) * 1048576.0) / per));
     const size_t xs_bstride = (size_t)d * Np;
+    // the gradient through the prior mean: T columns folded on the device (0: none), per set N values of a and T of the fold
+    const int T = (mean && mean->dtheta_out) ? mean->T : 0;
+    const size_t jac_one = (size_t)N * T, jac_doubles = T ? (mean->jac_stride ? jac_one * chunk : jac_one) : 0;
+    const size_t mg_n = (mean && mean->dmean_out) ? (size_t)N : 0, mg_doubles = mg_n + T;
     rc = ws_reserve(c->batchA, per * chunk);
     if (rc) return rc;
-    rc = ws_reserve(c->batchX, sizeof(double) * (xs_bstride * (chunk + 1) + (size_t)Np * (chunk + 1)));
+    rc = ws_reserve(c->batchX, sizeof(double) * (xs_bstride * (chunk + 1) + (size_t)Np * (chunk + 1) + jac_doubles));
     if (rc) return rc;
     const size_t inv16_b = (size_t)nblk * 8 * 256;
     const int nv = d + 2;
     // small sets run their gradient passes in groups (every launch covers the group in grid.z), large ones set after set
     const int group = llgrad_group_size(grad_out != nullptr, Np, ld, chunk);
     const size_t dinv_doubles = llgrad_dinv_doubles(group, Np);
-    rc = ws_reserve(c->batchMisc, sizeof(double) * ((size_t)chunk * (inv16_b + 2 + 2 + d + nv) + dinv_doubles) + sizeof(int) * chunk + 64);
+    rc = ws_reserve(c->batchMisc, sizeof(double) * ((size_t)chunk * (inv16_b + 2 + 2 + d + nv + mg_doubles) + dinv_doubles) + sizeof(int) * chunk + 64);
     if (rc) return rc;
     double* A = (double*)c->batchA.p;
     double* Xraw = (double*)c->batchX.p;               // raw points | y | prior means lie together: one upload for small problems
     double* ydev = Xraw + xs_bstride;
     double* meandev = ydev + Np;                       // chunk × Np (or Np when shared)
     double* Xsc = meandev + (size_t)Np * chunk;
+    double* jacdev = Xsc + xs_bstride * chunk;              // chunk × N×T (or one N×T when shared)
     double* inv16 = (double*)c->batchMisc.p;
     double* hyp = inv16 + inv16_b * chunk;
     double* scal = hyp + 2 * (size_t)chunk;
     double* invlam = scal + 2 * (size_t)chunk;
-    double* sums = invlam + (size_t)d * chunk;              // chunk × (d+2)
-    double* dinv_scratch = sums + (size_t)nv * chunk;
+    double* sums = invlam + (size_t)d * chunk;              // chunk × (d+2) | chunk × N (a) | chunk × T (fold): one copy back
+    double* dmeandev = sums + (size_t)nv * chunk;
+    double* dthetadev = dmeandev + mg_n * chunk;
+    double* dinv_scratch = dthetadev + (size_t)T * chunk;
     int* info = (int*)(dinv_scratch + dinv_doubles);
 
     std::vector<double> buf;
@@ -248,8 +280,25 @@ static int loglike_batch_impl(int device, int kernel, int d, int N, const double
     std::vector<double> h_invlam((size_t)d * chunk), h_hyp(2 * (size_t)chunk), h_scal(2 * (size_t)chunk), h_mean;
     std::vector<int> h_info(chunk), valid(chunk);
     std::vector<double> h_sums;
+    MeanFold mf;                                             // (the device side of `mean`, set 0 of a chunk)
+    if (mg_doubles) {
+        mf.J = T ? jacdev : nullptr;
+        mf.sJ = (T && mean->jac_stride) ? jac_one : 0;
+        mf.T = T;
+        mf.dmean = mg_n ? dmeandev : nullptr;
+        mf.dtheta = T ? dthetadev : nullptr;
+        if (T && !mean->jac_stride) HIPCHK(hipMemcpyAsync(jacdev, mean->jac, sizeof(double) * jac_one, hipMemcpyHostToDevice, s));
+    }
+    // what comes back per chunk: the Σ-vectors, then a and the fold where they are asked for, contiguous on the device
+    const auto sums_back = [&](int nb) {
+        h_sums.resize(((size_t)nv + mg_doubles) * chunk);
+        if (!mg_doubles) return hipMemcpyAsync(h_sums.data(), sums, sizeof(double) * nv * nb, hipMemcpyDeviceToHost, s);
+        return hipMemcpyAsync(h_sums.data(), sums, sizeof(double) * (((size_t)nv + mg_n) * chunk + (size_t)T * nb), hipMemcpyDeviceToHost, s);
+    };
     for (int s0 = 0; s0 < S; s0 += chunk) {
         const int nb = std::min(chunk, S - s0);
+        if (T && mean->jac_stride)
+            HIPCHK(hipMemcpyAsync(jacdev, mean->jac + (size_t)s0 * jac_one, sizeof(double) * jac_one * nb, hipMemcpyHostToDevice, s));
         for (int b = 0; b < nb; ++b)
             valid[b] = stage_hyper(d, lengthscales + (size_t)(s0 + b) * d, amplitudes[s0 + b], noise_stds[s0 + b], &h_invlam[(size_t)b * d],
                                    &h_hyp[2 * b]);
@@ -292,9 +341,8 @@ static int loglike_batch_impl(int device, int kernel, int d, int N, const double
             if (grad_out) {
                 hipLaunchKernelGGL(small_llgrad_kernel, dim3(nb), dim3(DIAG_THREADS), SMALL_LLG_LDS_BYTES, s, (const double*)A, ld, Np, N, d,
                                    kernel, 0.0, (const double*)inv16, (const double*)Xsc, Np, sums, bstride, inv16_b, xs_bstride,
-                                   (const double*)hyp, 2, nv, 0ull);
-                h_sums.resize((size_t)nv * nb);
-                HIPCHK(hipMemcpyAsync(h_sums.data(), sums, sizeof(double) * nv * nb, hipMemcpyDeviceToHost, s));
+                                   (const double*)hyp, 2, nv, 0ull, mf.J, T, mf.sJ, mf.dmean, mf.dtheta);
+                HIPCHK(sums_back(nb));
             }
         } else {
         batch_factor_enqueue(c, kernel, d, N, Np, nb, Xraw, ydev, mean_arg, mean_b, invlam, hyp, Xsc, xs_bstride, A, ld, bstride, inv16, inv16_b,
@@ -306,10 +354,9 @@ static int loglike_batch_impl(int device, int kernel, int d, int N, const double
             St.sX = xs_bstride;
             rc = llgrad_sets_enqueue(c, s, nb, group, Np, dinv_scratch, sums, nv, St, hyp, [&](boss_gp* v, int b, double* Dinv, double* Dinv2) {
                 set_view(v, c, kernel, d, N, Np, A + (size_t)b * bstride, inv16 + (size_t)b * inv16_b, Xsc + (size_t)b * xs_bstride, Dinv, Dinv2);
-            });
+            }, mg_doubles ? &mf : nullptr);
             if (rc) return rc;
-            h_sums.resize((size_t)nv * nb);
-            HIPCHK(hipMemcpyAsync(h_sums.data(), sums, sizeof(double) * nv * nb, hipMemcpyDeviceToHost, s));
+            HIPCHK(sums_back(nb));
         }
         }   // !small
         HIPCHK(hipMemcpyAsync(h_scal.data(), scal, sizeof(double) * 2 * nb, hipMemcpyDeviceToHost, s));
@@ -328,6 +375,15 @@ static int loglike_batch_impl(int device, int kernel, int d, int N, const double
                     llgrad_finalize(d, N, &h_invlam[(size_t)b * d], h_hyp[2 * b], h_hyp[2 * b + 1], zz, &h_sums[(size_t)b * nv], gr);
                 else
                     for (int m = 0; m < nv; ++m) gr[m] = 0.0;
+            }
+            // (a set without a factor gets zeros, like its gradient)
+            if (mg_n) {
+                const double* a = &h_sums[(size_t)nv * chunk + (size_t)b * N];
+                for (int j = 0; j < N; ++j) mean->dmean_out[(size_t)(s0 + b) * N + j] = st == BOSS_OK ? a[j] : 0.0;
+            }
+            if (T) {
+                const double* t = &h_sums[((size_t)nv + mg_n) * chunk + (size_t)b * T];
+                for (int k = 0; k < T; ++k) mean->dtheta_out[(size_t)(s0 + b) * T + k] = st == BOSS_OK ? t[k] : 0.0;
             }
         }
     }
@@ -351,6 +407,31 @@ extern "C" int boss_gp_loglike_grad_batch(int device, int kernel, int d, int N, 
     if (!grad_out) return fail(BOSS_E_INVALID, "grad_out is NULL");
     return loglike_batch_impl(device, kernel, d, N, X, y, mean_X, mean_stride, discrete, S, lengthscales, amplitudes, noise_stds,
                               ll_out, status_out, grad_out);
+}
+
+// boss_gp_loglike_grad_batch plus the gradient through the prior mean: ∂logpdf/∂mean_X[j] = (K⁻¹(y − m))_j of every set (dmean_out,
+// N×S) and its fold with the Jacobian of the mean values w.r.t. T parameters of a parametric mean (dtheta_out, T×S) — what
+// OptimizationMAP's AD carries into θ of a Semiparametric model (src/models/semiparametric.jl:79-92).  ll_out, grad_out and
+// status_out are boss_gp_loglike_grad_batch's in every bit: the same launches produce them, the fold only reads their workspace.
+extern "C" int boss_gp_loglike_grad_batch_mean(int device, int kernel, int d, int N, const double* X, const double* y,
+                                               const double* mean_X, int mean_stride, const unsigned char* discrete, int S,
+                                               const double* lengthscales, const double* amplitudes, const double* noise_stds,
+                                               int T, const double* mean_jac, int jac_stride, double* ll_out, double* grad_out,
+                                               double* dmean_out, double* dtheta_out, int* status_out) {
+    if (!grad_out) return fail(BOSS_E_INVALID, "grad_out is NULL");
+    if (T < 0) return fail(BOSS_E_INVALID, "T must be >= 0");
+    if (T > 0 && !mean_jac) return fail(BOSS_E_INVALID, "mean_jac is NULL");
+    if (T == 0 && dtheta_out) return fail(BOSS_E_INVALID, "dtheta_out needs T > 0");
+    if (jac_stride != 0 && (long long)jac_stride != (long long)N * T)
+        return fail(BOSS_E_INVALID, "jac_stride must be 0 or N*T");
+    BatchMeanGrad mg;
+    mg.T = mean_jac ? T : 0;
+    mg.jac = mean_jac;
+    mg.jac_stride = jac_stride;
+    mg.dmean_out = dmean_out;
+    mg.dtheta_out = dtheta_out;
+    return loglike_batch_impl(device, kernel, d, N, X, y, mean_X, mean_stride, discrete, S, lengthscales, amplitudes, noise_stds,
+                              ll_out, status_out, grad_out, &mg);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -957,12 +957,18 @@ constexpr int SMALL_LLG_LDS_DOUBLES = DIAG_TILES * 256 + SMALL_MAX_D * SMALL_MAX
 constexpr int SMALL_LLG_LDS_BYTES = SMALL_LLG_LDS_DOUBLES * 8;
 // blockIdx.x: set of a batch — factor, inverses and scaled points at strides sA / sInv / sX, α² at amp2p[b·amp2_stride] (null: the
 // scalar argument), the Σ-vector to out + b·out_stride (one handle: mapped host memory, a batch: device memory).
+// dmean / dtheta (device memory, may be null; boss_gp_loglike_grad_mean, boss_gp_loglike_grad_batch_mean): a itself, N per set, and
+// its fold with the mean's N×Tm column-major Jacobian J (sets sJ apart), dtheta[t] = Σ_j J[j + N·t] a_j, Tm per set — formed from
+// `av` after its last use above, one wave per column in a fixed order (lane's rows j = lane, lane + 64, then the butterfly); they
+// are ordinary stores the caller reads after a synchronisation, not part of what the polled sequence word announces.
 __global__ __launch_bounds__(DIAG_THREADS) void small_llgrad_kernel(const double* __restrict__ A, int ld, int Np, int N, int d,
                                                                     int kern, double amp2, const double* __restrict__ inv16,
                                                                     const double* __restrict__ Xsc, int ldx,
                                                                     double* __restrict__ host_out, size_t sA, size_t sInv, size_t sX,
                                                                     const double* __restrict__ amp2p, int amp2_stride, int out_stride,
-                                                                    unsigned long long res_seq) {
+                                                                    unsigned long long res_seq, const double* __restrict__ J,
+                                                                    int Tm, size_t sJ, double* __restrict__ dmean,
+                                                                    double* __restrict__ dtheta) {
     extern __shared__ double smem[];
     A += (size_t)blockIdx.x * sA;
     inv16 += (size_t)blockIdx.x * sInv;
@@ -1083,6 +1089,18 @@ __global__ __launch_bounds__(DIAG_THREADS) void small_llgrad_kernel(const double
     if (res_seq) {
         __syncthreads();
         if (tid == 0) __hip_atomic_store(reinterpret_cast<unsigned long long*>(host_out) - 1, res_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    if (dmean && tid < N) dmean[(size_t)blockIdx.x * N + tid] = av[tid];
+    if (dtheta) {
+        const double* Js = J + (size_t)blockIdx.x * sJ;
+        const double a0 = (lane < N) ? av[lane] : 0.0, a1 = (lane + 64 < N) ? av[lane + 64] : 0.0;
+        for (int t = wave; t < Tm; t += DIAG_THREADS / 64) {
+            double v = (lane < N) ? Js[(size_t)t * N + lane] * a0 : 0.0;
+            if (lane + 64 < N) v = __builtin_fma(Js[(size_t)t * N + lane + 64], a1, v);
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+            if (lane == 0) dtheta[(size_t)blockIdx.x * Tm + t] = v;
+        }
     }
 }
 

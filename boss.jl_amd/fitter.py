@@ -18,7 +18,7 @@ import numpy as np
 from . import api
 from . import distributed as dist_util
 from .model import HipGaussianProcess, HipGPParams
-from .problem import BossOptions, BossProblem, Dirac, MvDirac
+from .problem import BossOptions, BossProblem, Dirac, MvDirac, Normal
 
 
 @dataclass
@@ -69,6 +69,9 @@ class HipGradientMAP:
     boss_gp_loglike_grad_batch: values and analytic gradients of all trial points — and the ascent runs in log-parameter space
     (the reference softplus/log-transforms positive parameters the same way, :120-144) with a
     Barzilai–Borwein-free backtracking step.  Parameters with a Dirac prior stay fixed (dirac.jl:36-77).
+    A Semiparametric model (`parametric`) brings θ of its mean as a further parameter group (boss_gp_loglike_grad_batch_mean:
+    the device folds K⁻¹(y − m) with the mean's Jacobian at every trial point's own θ); an entry of θ moves as it is under a
+    Normal prior, in log-space under a positive-support prior, not at all under a Dirac prior.
     Multi-GPU: the starts are sharded across ranks, 16-byte arg-max exchange (as HipBatchedMAP)."""
     multistart: int = 8
     iters: int = 40
@@ -99,6 +102,31 @@ class HipGradientMAP:
         tot = np.where(np.isfinite(tot), tot, -np.inf)
         return tot, gl, ga, gs
 
+    def _objective_semiparametric(self, model, prior_ll, data, plist: List[HipGPParams]):
+        """The same for a model with a parametric mean: values and gradients w.r.t. (λ, α, σ) and θ, one device call per
+        output (data_loglike_grad_batch -> boss_gp_loglike_grad_batch_mean), every trial point's mean row and mean Jacobian
+        taken at its own θ."""
+        S = len(plist)
+        d, P = plist[0].lengthscales.shape
+        T = len(model.theta_priors)
+        tot = np.array([prior_ll(p) for p in plist], dtype=float)
+        gl, ga, gs, gt = np.zeros((S, d, P)), np.zeros((S, P)), np.zeros((S, P)), np.zeros((S, T))
+        lls, gparams = model.data_loglike_grad_batch(data, plist)
+        for k, p in enumerate(plist):
+            tot[k] += lls[k]
+            if not np.isfinite(lls[k]):
+                continue
+            g = gparams[k]
+            gl[k], ga[k], gs[k], gt[k] = g.lengthscales, g.amplitudes, g.noise_std, g.theta
+            for i in range(P):
+                gl[k, :, i] += np.atleast_1d(model.lengthscale_priors[i].grad_logpdf(p.lengthscales[:, i]))
+                ga[k, i] += model.amplitude_priors[i].grad_logpdf(p.amplitudes[i])
+                gs[k, i] += model.noise_std_priors[i].grad_logpdf(p.noise_std[i])
+            for t, pr in enumerate(model.theta_priors):
+                gt[k, t] += pr.grad_logpdf(p.theta[t])
+        tot = np.where(np.isfinite(tot), tot, -np.inf)
+        return tot, gl, ga, gs, gt
+
     def _objective_gradient_model(self, model, prior_ll, data, plist):
         """The same for a HipGradientGaussianProcess (values + gradients): one batched device call per output
         (data_loglike_grad_batch -> boss_ggp_loglike_grad_batch; where that call does not pay, per start and output one
@@ -126,8 +154,10 @@ class HipGradientMAP:
     def estimate_parameters(self, problem: BossProblem, options: BossOptions = BossOptions(), return_all: bool = False):
         model = problem.model
         grad_model = hasattr(model, "grad_noise_std_priors")        # HipGradientGaussianProcess (gradient_gp.py)
-        if not grad_model and model.parametric is not None:
-            raise NotImplementedError("HipGradientMAP treats the prior mean as fixed; use HipBatchedMAP for Semiparametric models")
+        semipar = not grad_model and model.parametric is not None
+        if semipar:
+            if model.theta_priors is None or any(pr is None for pr in model.theta_priors):
+                raise ValueError("HipGradientMAP needs a prior for every entry of theta (Normal, a positive-support prior, or Dirac)")
         data = problem.data
         rng = np.random.default_rng(dist_util.shared_seed(self.seed, self.group))     # the same starts on every rank
         sampler, prior_ll = model.params_sampler(), model.params_loglike()
@@ -143,7 +173,14 @@ class HipGradientMAP:
         free = [np.array([not isinstance(pr, (Dirac, MvDirac)) for pr in model.lengthscale_priors])[None, :],
                 np.array([not isinstance(pr, Dirac) for pr in model.amplitude_priors]),
                 np.array([not isinstance(pr, Dirac) for pr in model.noise_std_priors])]
-        if grad_model:
+        logc = None                                       # per group: which entries move in log-space (None: all of them)
+        if semipar:
+            free.append(np.array([not isinstance(pr, Dirac) for pr in model.theta_priors]))
+            logc = [True, True, True, np.array([not isinstance(pr, Normal) for pr in model.theta_priors])]
+            parts_of = lambda p: [p.lengthscales, p.amplitudes, p.noise_std, np.asarray(p.theta, float).reshape(-1)]
+            remake = lambda p, q: HipGPParams(q[0], q[1], q[2], q[3])
+            objective = lambda pl: (lambda r: (r[0], list(r[1:])))(self._objective_semiparametric(model, prior_ll, data, pl))
+        elif grad_model:
             free.append(np.array([not isinstance(pr, Dirac) for pr in model.grad_noise_std_priors]))
             parts_of = lambda p: [p.lengthscales, p.amplitudes, p.noise_std, p.grad_noise_std]
             remake = lambda p, q: type(p)(q[0], q[1], q[2], q[3])
@@ -168,13 +205,20 @@ class HipGradientMAP:
                 for k in np.flatnonzero(alive):
                     parts = parts_of(ps[k])
                     # ascent direction in log-space: ∂f/∂log θ = θ ∂f/∂θ ; fixed (Dirac) parameters do not move
-                    dirs = [np.where(fr, q * g[k], 0.0) for q, g, fr in zip(parts, grads, free)]
+                    if logc is None:
+                        dirs = [np.where(fr, q * g[k], 0.0) for q, g, fr in zip(parts, grads, free)]
+                    else:                                  # (raw coordinates keep ∂f/∂θ itself)
+                        dirs = [np.where(fr, np.where(lc, q * g[k], g[k]), 0.0) for q, g, fr, lc in zip(parts, grads, free, logc)]
                     nrm = math.sqrt(float(sum((dq * dq).sum() for dq in dirs)))
                     if nrm < 1e-10:
                         alive[k] = False
                         continue
                     idx.append(k)
-                    trial.append(remake(ps[k], [q * np.exp(step[k] * dq / nrm) for q, dq in zip(parts, dirs)]))
+                    if logc is None:
+                        trial.append(remake(ps[k], [q * np.exp(step[k] * dq / nrm) for q, dq in zip(parts, dirs)]))
+                    else:
+                        trial.append(remake(ps[k], [np.where(lc, q * np.exp(step[k] * dq / nrm), q + step[k] * dq / nrm)
+                                                    for q, dq, lc in zip(parts, dirs, logc)]))
                 if not idx:
                     break
                 fq, gq = objective(trial)

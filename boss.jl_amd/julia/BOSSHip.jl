@@ -648,13 +648,16 @@ the objective to an Optimization.jl algorithm with automatic differentiation (:1
 every round is ONE device call per output — `boss_gp_loglike_grad_batch`: values and analytic gradients of all trial points —
 and the ascent runs in log-parameter space (positive parameters; the reference's bijector maps them the same way).  Parameters
 with a Dirac prior stay fixed (src/models/utils/dirac.jl:36-77); the priors' gradient comes from ForwardDiff (a few scalars).
+Over a `HipSemiparametric` θ of the parametric mean moves too: `boss_gp_loglike_grad_batch_mean` folds K⁻¹(y − m) with the
+ForwardDiff Jacobian of the mean values at every trial point's own θ; an entry of θ whose prior is real-valued moves as it is.
 """
 Base.@kwdef struct HipGradientMAP <: BOSS.ModelFitter{BOSS.MAPParams}
-    multistart::Union{Int, Vector{<:HipGPParams}} = 8
+    multistart::Union{Int, Vector{<:HipGPParams}, Vector{<:HipSemiparametricParams}} = 8
     iters::Int = 40
     step0::Float64 = 0.3
 end
-BOSS.set_starts(f::HipGradientMAP, starts::AbstractVector{<:HipGPParams}) = HipGradientMAP(collect(starts), f.iters, f.step0)
+BOSS.set_starts(f::HipGradientMAP, starts::AbstractVector{<:Union{HipGPParams, HipSemiparametricParams}}) =
+    HipGradientMAP(collect(starts), f.iters, f.step0)
 flat(p::HipGPParams) = vcat(vec(p.λ), p.α, p.σ)
 unflat(p::HipGPParams, v::AbstractVector) = (n = length(p.λ); P = length(p.α);
     HipGPParams(reshape(v[1:n], size(p.λ)), v[n+1:n+P], v[n+P+1:n+2P]))
@@ -673,20 +676,60 @@ function objective_batch(m::HipGaussianProcess, data::BOSS.ExperimentData, ps::A
     end
     return f, G
 end
+# The same over a HipSemiparametric: θ of the parametric mean is a further parameter group in front (flat(p) = [θ; vec(λ); α; σ]).
+# Every parameter set's own θ gives its mean row and the Jacobian of the mean values, J[j, t] = ∂ f(x_j; θ)[i] / ∂θ_t (ForwardDiff);
+# the device folds it with K⁻¹(y − m) (boss_gp_loglike_grad_batch_mean), and θ is shared by the outputs: ∂/∂θ = Σ_i J_iᵀ a_i.
+flat(p::HipSemiparametricParams) = vcat(p.θ, vec(p.λ), p.α, p.σ)
+unflat(p::HipSemiparametricParams, v::AbstractVector) = (t = length(p.θ); n = length(p.λ); P = length(p.α);
+    HipSemiparametricParams(v[1:t], reshape(v[t+1:t+n], size(p.λ)), v[t+n+1:t+n+P], v[t+n+P+1:t+n+2P]))
+function loglike_and_grad_batch(m::HipSemiparametric, data::BOSS.ExperimentData, i::Int, ps::AbstractVector{<:HipSemiparametricParams})
+    X = Matrix{Float64}(data.X); d, N = size(X); S = length(ps); T = length(ps[1].θ); k = gp_kernel(m)
+    means, _ = batch_means(m, ps, X, i)                                     # S×N, row s = f(x_j; θ_s)[i]
+    J = Array{Float64}(undef, N, T, S)                                      # set after set, each N×T column-major
+    for (s, p) in enumerate(ps)
+        J[:, :, s] .= BOSS.ForwardDiff.jacobian(θ -> [m.sp.parametric(θ)(x)[i] for x in eachcol(X)], Vector{Float64}(p.θ))
+    end
+    λ = Matrix{Float64}(reduce(hcat, (p.λ[:, i] for p in ps)))
+    ll = Vector{Float64}(undef, S); g = Matrix{Float64}(undef, d + 2, S); dθ = Matrix{Float64}(undef, T, S); st = Vector{Cint}(undef, S)
+    check(ccall((:boss_gp_loglike_grad_batch_mean, lib), Cint,
+        (Cint, Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{UInt8}, Cint, Ptr{Cdouble}, Ptr{Cdouble},
+         Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cint}),
+        m.device, kernel_id(base_kernel(k)), d, N, X, Vector{Float64}(data.Y[i, :]), means, N, discrete_flags(k), S, λ,
+        Float64[p.α[i] for p in ps], Float64[p.σ[i] for p in ps], T, J, N * T, ll, g, C_NULL, dθ, st))
+    return ll, g, dθ, st      # zero columns of g and dθ where st[s] != 0
+end
+function objective_batch(m::HipSemiparametric, data::BOSS.ExperimentData, ps::AbstractVector{<:HipSemiparametricParams})
+    prior = params_loglike(m); S = length(ps); d, P = size(ps[1].λ); T = length(ps[1].θ)
+    f = Float64[prior(p) for p in ps]
+    G = [BOSS.ForwardDiff.gradient(v -> prior(unflat(p, v)), flat(p)) for p in ps]
+    for i in 1:P
+        ll, g, dθ, st = loglike_and_grad_batch(m, data, i, ps)
+        for s in 1:S
+            f[s] += st[s] == 0 ? ll[s] : -Inf
+            G[s][1:T] .+= dθ[:, s]
+            G[s][T+(i-1)*d+1:T+i*d] .+= g[1:d, s]; G[s][T+d*P+i] += g[d+1, s]; G[s][T+d*P+P+i] += g[d+2, s]
+        end
+    end
+    return f, G
+end
+"Which entries of flat(p) the ascent moves in log-space: all but the entries of θ whose prior has negative numbers in its support."
+log_coords(m::HipGaussianProcess, p) = trues(length(flat(p)))
+log_coords(m::HipSemiparametric, p) = vcat(Bool[minimum(pr) >= 0 for pr in m.sp.parametric.theta_priors], trues(length(flat(p)) - length(p.θ)))
 function estimate_parameters(fit::HipGradientMAP, problem::BOSS.BossProblem, options::BOSS.BossOptions; return_all::Bool = false)
-    m = problem.model::HipGaussianProcess; data = problem.data
+    m = problem.model::Union{HipGaussianProcess, HipSemiparametric}; data = problem.data
     sampler = BOSS.params_sampler(m, data)
     ps = fit.multistart isa Int ? [sampler() for _ in 1:fit.multistart] : copy(fit.multistart)
     free = .!first(BOSS.create_dirac_mask(BOSS.param_priors(m)))            # over flat(p): Dirac-prior parameters do not move
+    logc = log_coords(m, ps[1])                                             # θ under a real-valued prior moves as it is
     f, G = objective_batch(m, data, ps)
     step = fill(fit.step0, length(ps)); its = zeros(Int, length(ps)); alive = isfinite.(f) .& (fit.iters > 0)
     while any(alive)
         idx = Int[]; trial = eltype(ps)[]
         for k in findall(alive)
-            v = flat(ps[k]); dir = ifelse.(free, v .* G[k], 0.0)            # ∂f/∂log θ = θ ∂f/∂θ
+            v = flat(ps[k]); dir = ifelse.(free, ifelse.(logc, v .* G[k], G[k]), 0.0)   # ∂f/∂log θ = θ ∂f/∂θ
             nrm = sqrt(sum(abs2, dir))
             nrm < 1e-10 && (alive[k] = false; continue)
-            push!(idx, k); push!(trial, unflat(ps[k], v .* exp.(step[k] .* dir ./ nrm)))
+            push!(idx, k); push!(trial, unflat(ps[k], ifelse.(logc, v .* exp.(step[k] .* dir ./ nrm), v .+ step[k] .* dir ./ nrm)))
         end
         isempty(idx) && break
         fq, Gq = objective_batch(m, data, trial)                            # ALL trial points of the round in one call per output
@@ -1306,6 +1349,7 @@ end
 # not bound: boss_set_stream — runs the library on a caller's HIP stream (torch / AMDGPU.jl interop); BOSS.jl itself owns no stream
 # not bound: boss_device_sync — drains that stream; every entry point used above returns synchronised results
 # not bound: boss_gp_get_factor — test introspection (L and z of a fitted handle); no BOSS.jl API asks for the factor
+# not bound: boss_gp_loglike_grad_mean — one resident handle's K⁻¹(y − m); the fitters here evaluate all trial points of a round with boss_gp_loglike_grad_batch_mean
 # not bound: boss_bench_mfma_f64 — measurement helper of bench.py (fp64 MFMA issue-rate probe)
 # not bound: boss_prof_enable — measurement helper of bench.py (per-kernel-class HIP-event timers)
 # not bound: boss_prof_reset — measurement helper of bench.py

@@ -5,6 +5,8 @@ src/models/semiparametric.jl) over the C ABI:
   model_posterior / model_posterior_slice   -> boss_gp_create + boss_gp_update (resident factor)
   mean / var / mean_and_var / std / ...     -> boss_gp_predict
   data_loglike                              -> boss_gp_update's logpdf (or boss_gp_loglike_batch)
+  data_loglike_grad_batch                   -> boss_gp_loglike_grad_batch_mean (values, ∂/∂(λ, α, σ) and, through the
+                                               Jacobian of the parametric mean, ∂/∂θ)
   params_loglike / params_sampler           -> host (prior bookkeeping, out of the GPU's scope)
 The GP's prior mean (a user closure, or the Semiparametric parametric model m(x;θ)) is evaluated
 on the host and crosses the ABI as dense vectors.
@@ -50,7 +52,10 @@ class HipGaussianProcess:
     """GaussianProcess(mean, kernel, lengthscale_priors, amplitude_priors, noise_std_priors)
     (gaussian_process.jl:34-42).  `mean`: None, a length-P vector, or a function x -> length-P
     vector.  `parametric`: optional (x, θ) -> length-P vector with `theta_priors` — the
-    Semiparametric model (semiparametric.jl:79-92)."""
+    Semiparametric model (semiparametric.jl:79-92).  `parametric_jac`: optional (x, θ) -> P×T matrix ∂parametric(x, θ)/∂θ for
+    the likelihood gradient w.r.t. θ (data_loglike_grad_batch; the reference differentiates the closure by AD).  Without it the
+    Jacobian is taken by central differences of `parametric` in θ with step 1e-6·max(1, |θ_t|): 2T further evaluations of
+    `parametric` per point; the error is about 2⁻⁵³·|m|/h from rounding plus h²·|∂³m/∂θ³|/6 from truncation."""
     lengthscale_priors: Sequence
     amplitude_priors: Sequence
     noise_std_priors: Sequence
@@ -60,13 +65,15 @@ class HipGaussianProcess:
     parametric: Optional[Callable] = None
     theta_priors: Optional[Sequence] = None
     device: int = 0
+    parametric_jac: Optional[Callable] = None
 
     sliceable = True                             # gaussian_process.jl:85
 
     def make_discrete(self, discrete):
         """make_discrete(m, discrete) (gaussian_process.jl:78-79): wrap the kernel in DiscreteKernel."""
         return HipGaussianProcess(self.lengthscale_priors, self.amplitude_priors, self.noise_std_priors, self.mean,
-                                  self.kernel, np.asarray(discrete, bool), self.parametric, self.theta_priors, self.device)
+                                  self.kernel, np.asarray(discrete, bool), self.parametric, self.theta_priors, self.device,
+                                  self.parametric_jac)
 
     @property
     def y_dim(self):
@@ -87,6 +94,33 @@ class HipGaussianProcess:
         if callable(self.mean):
             return np.array([float(np.asarray(self.mean(X[:, j]))[i]) for j in range(n)])
         return np.full(n, float(np.asarray(self.mean, float)[i]))
+
+    def mean_jacobians(self, X, params: HipGPParams, i: int) -> np.ndarray:
+        """∂m_i(x_j; θ)/∂θ_t as an N×T matrix (row j = point j) at params.theta: `parametric_jac` where the model has one, otherwise
+        central differences of `parametric` with step 1e-6·max(1, |θ_t|) (2T evaluations per point)."""
+        X = np.asarray(X, float)
+        if X.ndim == 1:
+            X = X[:, None]
+        n = X.shape[1]
+        th = np.asarray(params.theta, float).reshape(-1)
+        T = th.shape[0]
+        if self.parametric_jac is not None:
+            J = np.empty((n, T))
+            for j in range(n):
+                Jj = np.asarray(self.parametric_jac(X[:, j], th), float)
+                if Jj.shape != (self.y_dim, T):
+                    raise ValueError(f"parametric_jac must return a {self.y_dim}×{T} matrix, got shape {Jj.shape}")
+                J[j] = Jj[i]
+            return J
+        J = np.empty((n, T))
+        for t in range(T):
+            h = 1e-6 * max(1.0, abs(th[t]))
+            up, dn = th.copy(), th.copy()
+            up[t] += h
+            dn[t] -= h
+            for j in range(n):
+                J[j, t] = (float(np.asarray(self.parametric(X[:, j], up))[i]) - float(np.asarray(self.parametric(X[:, j], dn))[i])) / (up[t] - dn[t])
+        return J
 
     # ------------------------------------------------------------------ priors (host bookkeeping)
     def params_sampler(self):
@@ -144,6 +178,40 @@ class HipGaussianProcess:
             ll, _ = api.loglike_batch(data.X, data.Y[i], self.kernel, lam, amp, sig, means, self.discrete, self.device)
             tot += ll
         return tot
+
+    def data_loglike_grad_batch(self, data: ExperimentData, plist: Sequence[HipGPParams]):
+        """data_loglike of every parameter set of `plist` and its gradient w.r.t. (λ, α, σ) AND θ — what ForwardDiff yields
+        through data_loglike inside OptimizationMAP (src/model_fitters/optimization.jl:146-164) for a Semiparametric model.
+        One device call per output (boss_gp_loglike_grad_batch_mean): every set's own θ gives its mean row and its Jacobian
+        J_i (N×T), the device returns J_iᵀ a_i with a_i = K_i⁻¹(y_i − m_i); θ is shared by the outputs, so ∂/∂θ = Σ_i J_iᵀ a_i.
+        Returns (ll[S], grads): grads[k] a HipGPParams of gradients (theta None without a parametric mean); a set that fails
+        in any output has ll = -inf and zero gradients."""
+        S = len(plist)
+        tot = np.zeros(S)
+        if S == 0:
+            return tot, []
+        d, P = plist[0].lengthscales.shape
+        T = 0 if self.parametric is None else np.asarray(plist[0].theta, float).reshape(-1).shape[0]
+        gl, ga, gs, gt = np.zeros((S, d, P)), np.zeros((S, P)), np.zeros((S, P)), np.zeros((S, T))
+        for i in range(P):
+            lam = np.stack([p.lengthscales[:, i] for p in plist], axis=1)
+            amp = np.array([p.amplitudes[i] for p in plist])
+            sig = np.array([p.noise_std[i] for p in plist])
+            if self.parametric is not None:
+                means = np.stack([self.mean_values(data.X, p, i) for p in plist], axis=0)
+                jac = np.stack([self.mean_jacobians(data.X, p, i) for p in plist], axis=0) if T else None
+            else:
+                means, jac = self.mean_values(data.X, None, i), None
+            ll, st, gr, _, dth = api.loglike_grad_batch_mean(data.X, data.Y[i], self.kernel, lam, amp, sig, means, jac, self.discrete,
+                                                             self.device)
+            tot += np.where(st == 0, ll, -np.inf)
+            gl[:, :, i], ga[:, i], gs[:, i] = gr[:d].T, gr[d], gr[d + 1]
+            if dth is not None:
+                gt += dth.T
+        bad = ~np.isfinite(tot)
+        tot[bad] = -np.inf
+        gl[bad], ga[bad], gs[bad], gt[bad] = 0.0, 0.0, 0.0, 0.0
+        return tot, [HipGPParams(gl[k], ga[k], gs[k], gt[k] if self.parametric is not None else None) for k in range(S)]
 
     # ------------------------------------------------------------------ posterior
     def model_posterior_slice(self, params: HipGPParams, data: ExperimentData, i: int,

@@ -49,6 +49,25 @@ class LogNormal:
 
 
 @dataclass
+class Normal:
+    """Normal(μ, σ): a prior on a real-valued parameter — θ of a Semiparametric model's parametric mean; the other priors here
+    have positive support."""
+    mu: float = 0.0
+    sigma: float = 1.0
+
+    def rand(self, rng):
+        return self.mu + self.sigma * rng.standard_normal()
+
+    def logpdf(self, x):
+        z = (x - self.mu) / self.sigma
+        return -math.log(self.sigma) - 0.5 * math.log(2 * math.pi) - 0.5 * z * z
+
+    def grad_logpdf(self, x):
+        """d logpdf / dx."""
+        return -(x - self.mu) / self.sigma ** 2
+
+
+@dataclass
 class MvLogNormal:
     """BOSS.mvlognormal(μ, σ) = MvLogNormal(μ, Diagonal(σ²)) (src/utils/distributions.jl:21-22)."""
     mu: Sequence[float]

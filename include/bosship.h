@@ -120,9 +120,16 @@ void boss_gp_free(boss_gp_t* gp);
  * Evaluated at the hyper-parameters of the last boss_gp_update on this handle:
  *   grad_out[0..d-1] = d logpdf / d lengthscale_m,  grad_out[d] = d/d amplitude,  grad_out[d+1] = d/d noise_std
  *   (d logpdf/d theta = 1/2 tr((a a' - K^-1) dK/dtheta), K^-1 = L^-T L^-1 formed on the device);
- *   logpdf_out (may be NULL) returns the value again.  The prior mean is treated as constant in theta.
+ *   logpdf_out (may be NULL) returns the value again.  grad_out holds the prior mean values fixed; the gradient
+ *   through the mean (a Semiparametric model's theta) comes from boss_gp_loglike_grad_mean below.
  * Costs about one acquisition pass (triangular inverse) + a K = N syrk. */
 int boss_gp_loglike_grad(boss_gp_t* gp, double* logpdf_out, double* grad_out);
+/* boss_gp_loglike_grad plus d logpdf / d mean_X[j] = (K^-1 (y - m))_j, N values (N: the handle's current count, appended
+ * points included).  With the Jacobian J of the mean values w.r.t. the parameters theta of a parametric mean
+ * (src/models/semiparametric.jl:79-92), d logpdf / d theta = J' dmean_out.  logpdf_out and grad_out are
+ * boss_gp_loglike_grad's; logpdf_out may be NULL.  Plain handles only (BOSS_E_INVALID for gradient-observation and
+ * nonstationary handles: the latter have boss_ngp_loglike_grad's dmean_out); needs a fitted handle. */
+int boss_gp_loglike_grad_mean(boss_gp_t* gp, double* logpdf_out, double* grad_out, double* dmean_out);
 
 /* introspection for parity tests: lower Cholesky factor L (N×N column-major, upper part zeroed)
  * and z = L \ (y - m) (N). Either pointer may be NULL. */
@@ -264,6 +271,20 @@ int boss_gp_loglike_grad_batch(int device, int kernel, int d, int N, const doubl
                                const double* mean_X, int mean_stride, const unsigned char* discrete,
                                int S, const double* lengthscales, const double* amplitudes,
                                const double* noise_stds, double* ll_out, double* grad_out, int* status_out);
+/* boss_gp_loglike_grad_batch plus the gradient through the prior mean.
+ *   T, mean_jac: Jacobian of the mean values w.r.t. T mean parameters, N×T column-major per set,
+ *                set after set (jac_stride = N*T), or ONE N×T matrix shared by all sets (jac_stride = 0,
+ *                a mean that is linear in theta); T = 0 / mean_jac NULL: no fold.
+ *   dmean_out  N×S or NULL: column s = d logpdf / d mean_X of set s = K^-1 (y - m);
+ *   dtheta_out T×S or NULL: column s = mean_jac(s)' dmean(s), formed on the device.
+ * ll_out, grad_out and status_out are boss_gp_loglike_grad_batch's for the same arguments in every bit.  A set whose
+ * status is not BOSS_OK gets zeros in both columns.  mean_X may be NULL while mean_jac is given.  BOSS_E_INVALID for
+ * T < 0, T > 0 with mean_jac NULL, a jac_stride other than 0 or N*T, dtheta_out with T = 0. */
+int boss_gp_loglike_grad_batch_mean(int device, int kernel, int d, int N, const double* X, const double* y,
+                                    const double* mean_X, int mean_stride, const unsigned char* discrete, int S,
+                                    const double* lengthscales, const double* amplitudes, const double* noise_stds,
+                                    int T, const double* mean_jac, int jac_stride,
+                                    double* ll_out, double* grad_out, double* dmean_out, double* dtheta_out, int* status_out);
 /* The batched likelihood of the gradient-observation model: S parameter sets on one (X, y, dY) slice, arguments as in
  * boss_ggp_create (X d×n, y n, dY d×n column-major) and boss_ggp_update (every parameter gets +1e-8):
  *   lengthscales d×S (column s = set s), amplitudes S, noise_stds S, grad_noise_stds S;
