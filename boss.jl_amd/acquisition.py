@@ -3,7 +3,8 @@
 (expected_improvement(::NonlinFitness), src/acquisitions/expected_improvement.jl:104-111).
 The GPU still produces the posterior mean/variance for every candidate, output and hyper-parameter
 sample (boss_gp_predict); only the closure evaluation, the ε-average and the feasibility product
-run here.  LinFitness never takes this path (boss_acq_ei evaluates it analytically on the device).
+run here.  LinFitness never takes this path (boss_acq_ei evaluates it analytically on the device), and neither does a DeviceFitness
+(fitness.py: the closure traced into a program, boss_acq_ei_mc) wherever the device route is wired.
 """
 from __future__ import annotations
 

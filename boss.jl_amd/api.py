@@ -131,6 +131,17 @@ SIGNATURES = {
     "boss_track_free": (None, [C.c_void_p]),
     "boss_track_sync": (C.c_int, [C.c_void_p]),
     "boss_track_moments": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _c_dp, _c_dp]),
+    "boss_fit_create": (C.c_int, [C.c_int, C.c_int, _c_dp, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p)]),
+    "boss_fit_free": (None, [C.c_void_p]),
+    "boss_fit_eval_host": (C.c_int, [C.c_void_p, C.c_int, _c_dp, _c_dp, _c_dp]),
+    "boss_acq_ei_mc": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, _c_dp, C.c_void_p, C.c_int, _c_dp, _c_dp, C.c_int,
+                                 C.c_double, _c_ucp, _c_dp, C.POINTER(C.c_long), _c_dp]),
+    "boss_acq_ei_mc_moments": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _c_dp, _c_dp, C.c_void_p, C.c_int, _c_dp, _c_dp, C.c_int,
+                                         C.c_double, _c_ucp, _c_dp, C.POINTER(C.c_long), _c_dp]),
+    "boss_acq_ei_mc_grad": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_int, _c_dp, _c_dp, _c_dp, C.c_void_p, C.c_int, _c_dp,
+                                      _c_dp, C.c_int, C.c_double, _c_ucp, _c_dp, _c_dp]),
+    "boss_acq_ei_mc_grad_moments": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _c_dp, _c_dp, _c_dp, _c_dp, C.c_void_p, C.c_int,
+                                              _c_dp, _c_dp, C.c_int, C.c_double, _c_ucp, _c_dp, _c_dp]),
     "boss_acq_ei_tracks": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_void_p), _c_dp, _c_dp, C.c_int, C.c_double, _c_ucp,
                                      _c_dp, C.POINTER(C.c_long), _c_dp]),
     "boss_init": (C.c_int, [C.POINTER(C.c_int)]),
@@ -1702,6 +1713,235 @@ def acq_ei_moments(mu, var, fit_coefs, y_max=None, best=None, valid_mask=None, d
                                               0 if best is None else 1, 0.0 if best is None else float(best),
                                               _ucp(mask), _dp(acq), C.byref(am), C.byref(mx)))
     return acq, am.value, mx.value
+
+
+# ---------------------------------------------------------------- fitness programs: Monte-Carlo EI of a nonlinear fitness
+FIT_OPS = ("ADD", "SUB", "MUL", "DIV", "NEG", "ABS", "SQUARE", "SQRT", "EXP", "LOG", "SIN", "COS", "TANH", "POW", "MIN", "MAX")
+FIT_OP = {name: i for i, name in enumerate(FIT_OPS)}                 # the BOSS_FIT_* opcodes of bosship.h
+FIT_UNARY = frozenset(range(FIT_OP["NEG"], FIT_OP["TANH"] + 1))
+FIT_MAX_INPUTS, FIT_MAX_CONSTS, FIT_MAX_INSTR = 16, 32, 64
+
+
+class FitnessProgram:
+    """A fitness y -> f(y) as a straight-line program (boss_fit_t): value ids 0..P-1 are the inputs, P..P+C-1 the constants,
+    P+C+i the result of instruction i = (op, a, b) on earlier ids (b = -1 on unary ops); the value is `out_id`.
+    Creating one needs no device.  eval / grad are vectorised numpy interpreters of the program, eval_host runs the
+    library's own interpreter (the function the kernels call) on the host."""
+
+    def __init__(self, P: int, consts, code, out_id: int):
+        self.P = int(P)
+        self.consts = np.ascontiguousarray(np.asarray(consts, dtype=np.float64).reshape(-1))
+        self.code = np.ascontiguousarray(np.asarray(code, dtype=np.intc).reshape(-1, 3))
+        self.out_id = int(out_id)
+        self._h = C.c_void_p()
+        _check(load_library().boss_fit_create(self.P, self.consts.shape[0], _dp(self.consts), self.code.shape[0],
+                                              self.code.ctypes.data_as(C.POINTER(C.c_int)), self.out_id, C.byref(self._h)))
+
+    def _inputs(self, Y):
+        Y = np.asarray(Y, dtype=np.float64)
+        one = Y.ndim == 1
+        Y = Y.reshape(self.P, -1)
+        return Y, one
+
+    def _forward(self, Y):
+        n = Y.shape[1]
+        vals = [Y[p] for p in range(self.P)] + [np.full(n, c) for c in self.consts]
+        with np.errstate(all="ignore"):
+            for op, a, b in self.code:
+                x = vals[a]
+                z = vals[b] if b >= 0 else None
+                name = FIT_OPS[op]
+                if name == "ADD": r = x + z
+                elif name == "SUB": r = x - z
+                elif name == "MUL": r = x * z
+                elif name == "DIV": r = x / z
+                elif name == "NEG": r = -x
+                elif name == "ABS": r = np.abs(x)
+                elif name == "SQUARE": r = x * x
+                elif name == "SQRT": r = np.sqrt(x)
+                elif name == "EXP": r = np.exp(x)
+                elif name == "LOG": r = np.log(x)
+                elif name == "SIN": r = np.sin(x)
+                elif name == "COS": r = np.cos(x)
+                elif name == "TANH": r = np.tanh(x)
+                elif name == "POW": r = np.power(x, z)
+                elif name == "MIN": r = np.where(np.isnan(x) | np.isnan(z), x + z, np.where(x <= z, x, z))
+                else: r = np.where(np.isnan(x) | np.isnan(z), x + z, np.where(x >= z, x, z))
+                vals.append(r)
+        return vals
+
+    def eval(self, Y):
+        """f at the columns of Y (P×n, or one point of length P)."""
+        Y, one = self._inputs(Y)
+        f = self._forward(Y)[self.out_id]
+        return float(f[0]) if one else np.array(f)
+
+    def grad(self, Y):
+        """df/dy at the columns of Y: P×n (the conventions of bosship.h: ABS'(0) = 0, MIN / MAX ties to the first operand, the
+        d/db term of POW dropped for a constant exponent, an instruction with adjoint 0 passes nothing on)."""
+        Y, one = self._inputs(Y)
+        n, P, nc = Y.shape[1], self.P, self.consts.shape[0]
+        vals = self._forward(Y)
+        adj = [np.zeros(n) for _ in vals]
+        adj[self.out_id] = np.ones(n)
+        with np.errstate(all="ignore"):
+            for i in range(self.code.shape[0] - 1, -1, -1):
+                op, a, b = self.code[i]
+                w = adj[P + nc + i]
+                x, r = vals[a], vals[P + nc + i]
+                z = vals[b] if b >= 0 else None
+                name = FIT_OPS[op]
+                da, db = None, None
+                if name == "ADD": da, db = np.ones(n), np.ones(n)
+                elif name == "SUB": da, db = np.ones(n), -np.ones(n)
+                elif name == "MUL": da, db = z, x
+                elif name == "DIV": da, db = 1.0 / z, -r / z
+                elif name == "NEG": da = -np.ones(n)
+                elif name == "ABS": da = np.sign(x)
+                elif name == "SQUARE": da = 2.0 * x
+                elif name == "SQRT": da = 0.5 / r
+                elif name == "EXP": da = r
+                elif name == "LOG": da = 1.0 / x
+                elif name == "SIN": da = np.cos(x)
+                elif name == "COS": da = -np.sin(x)
+                elif name == "TANH": da = 1.0 - r * r
+                elif name == "POW":
+                    da = z * np.power(x, z - 1.0)
+                    db = np.zeros(n) if P <= b < P + nc else r * np.log(x)
+                elif name == "MIN": da, db = (x <= z).astype(float), (~(x <= z)).astype(float)
+                else: da, db = (x >= z).astype(float), (~(x >= z)).astype(float)
+                adj[a] = adj[a] + np.where(w == 0.0, 0.0, w * da)
+                if db is not None:
+                    adj[b] = adj[b] + np.where(w == 0.0, 0.0, w * db)
+        g = np.stack(adj[:P])
+        return g[:, 0] if one else g
+
+    def eval_host(self, Y, want_grad: bool = False):
+        """The same through boss_fit_eval_host.  Returns f[n], or (f[n], df[P, n]) with want_grad."""
+        Y, one = self._inputs(Y)
+        Yf = np.asfortranarray(Y)
+        n = Yf.shape[1]
+        f = np.zeros(n)
+        df = np.zeros((self.P, n), order="F") if want_grad else None
+        _check(load_library().boss_fit_eval_host(self._h, n, _dp(Yf), _dp(f), _dp(df)))
+        if one:
+            return (float(f[0]), df[:, 0]) if want_grad else float(f[0])
+        return (f, df) if want_grad else f
+
+    def close(self):
+        if self._h:
+            load_library().boss_fit_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _mc_common(fit: FitnessProgram, eps, y_max, valid_mask):
+    eps = _f64(eps, 2)                                           # P×n_eps, one ε-sample per column
+    ym = None if y_max is None else _f64(np.asarray(y_max).reshape(-1), 1)
+    mask = None if valid_mask is None else np.ascontiguousarray(np.asarray(valid_mask, dtype=bool).astype(np.uint8))
+    return eps, ym, mask
+
+
+def acq_ei_mc(gps: Sequence[Sequence[GP]], cand: Candidates, fit: FitnessProgram, eps, y_max=None, best=None, valid_mask=None,
+              mean_Xs=None, want_acq: bool = True):
+    """acq_ei with the Monte-Carlo EI of a fitness program (boss_acq_ei_mc): eps P×K for one posterior sample, P×S for S > 1
+    (sample s takes column s).  Returns (acq[M] or None, argmax, max)."""
+    S = len(gps)
+    P = len(gps[0])
+    arr = (C.c_void_p * (P * S))()
+    for s in range(S):
+        for p in range(P):
+            arr[p + P * s] = gps[s][p]._h
+    eps, ym, mask = _mc_common(fit, eps, y_max, valid_mask)
+    M = cand.M
+    ms = None
+    if mean_Xs is not None:
+        a = np.asarray(mean_Xs, dtype=np.float64).reshape(S, P, M)
+        ms = np.ascontiguousarray(a.transpose(0, 2, 1))       # index p + P*(j + M*s)
+    acq = np.zeros(M) if want_acq else None
+    am = C.c_long(-1)
+    mx = C.c_double(0.0)
+    _check(load_library().boss_acq_ei_mc(P, S, arr, cand._h, _dp(ms), fit._h, eps.shape[1], _dp(eps), _dp(ym), 0 if best is None else 1,
+                                         0.0 if best is None else float(best), _ucp(mask), _dp(acq), C.byref(am), C.byref(mx)))
+    return acq, am.value, mx.value
+
+
+def acq_ei_mc_moments(mu, var, fit: FitnessProgram, eps, y_max=None, best=None, valid_mask=None, device: int = 0):
+    """acq_ei_moments with the Monte-Carlo EI of a fitness program (boss_acq_ei_mc_moments).  mu, var: [S][P][M] (or [P][M])."""
+    mu = np.asarray(mu, dtype=np.float64)
+    var = np.asarray(var, dtype=np.float64)
+    if mu.ndim == 2:
+        mu, var = mu[None], var[None]
+    S, P, M = mu.shape
+    if var.shape != mu.shape:
+        raise ValueError("mu and var must have one shape")
+    mu, var = np.ascontiguousarray(mu), np.ascontiguousarray(var)
+    eps, ym, mask = _mc_common(fit, eps, y_max, valid_mask)
+    acq = np.zeros(M)
+    am = C.c_long(-1)
+    mx = C.c_double(0.0)
+    _check(load_library().boss_acq_ei_mc_moments(device, P, S, M, _dp(mu), _dp(var), fit._h, eps.shape[1], _dp(eps), _dp(ym),
+                                                 0 if best is None else 1, 0.0 if best is None else float(best), _ucp(mask), _dp(acq),
+                                                 C.byref(am), C.byref(mx)))
+    return acq, am.value, mx.value
+
+
+def acq_ei_mc_grad(gps: Sequence[Sequence[GP]], Xs, fit: FitnessProgram, eps, y_max=None, best=None, valid_mask=None, mean_Xs=None,
+                   mean_grad=None):
+    """acq_ei_grad_set with the Monte-Carlo EI of a fitness program (boss_acq_ei_mc_grad); S = 1 included.  gps[s][p];
+    mean_Xs None or [S][P][M]; mean_grad None or [S][P][d][M].  Returns (acq[M], dacq[d, M])."""
+    S = len(gps)
+    P = len(gps[0]) if S else 0
+    if S < 1 or P < 1 or any(len(row) != P for row in gps):
+        raise BossError(BOSS_E_INVALID, "gps must be S rows of P posteriors")
+    Xs = _f64(Xs, 2)
+    d, M = Xs.shape
+    arr = (C.c_void_p * (P * S))()
+    for s in range(S):
+        for p in range(P):
+            arr[p + P * s] = gps[s][p]._h
+    eps, ym, mask = _mc_common(fit, eps, y_max, valid_mask)
+    ms = None if mean_Xs is None else np.ascontiguousarray(np.asarray(mean_Xs, dtype=np.float64).reshape(S, P, M))
+    mg = None
+    if mean_grad is not None:
+        a = np.asarray(mean_grad, dtype=np.float64).reshape(S, P, d, M)
+        mg = np.ascontiguousarray(a.transpose(0, 1, 3, 2))        # [s][p][j*d + m]
+    acq = np.zeros(M)
+    dacq = np.zeros((d, M), order="F")
+    _check(load_library().boss_acq_ei_mc_grad(P, S, arr, M, _dp(Xs), _dp(ms), _dp(mg), fit._h, eps.shape[1], _dp(eps), _dp(ym),
+                                              0 if best is None else 1, 0.0 if best is None else float(best), _ucp(mask), _dp(acq),
+                                              _dp(dacq)))
+    return acq, dacq
+
+
+def acq_ei_mc_grad_moments(mu, var, dmu, dvar, fit: FitnessProgram, eps, y_max=None, best=None, valid_mask=None, device: int = 0):
+    """acq_ei_grad_moments over S posterior samples with the Monte-Carlo EI of a fitness program (boss_acq_ei_mc_grad_moments):
+    mu / var [S][P][M] (or [P][M]), dmu / dvar [S][P][d][M].  Returns (acq[M], dacq[d, M])."""
+    mu = np.asarray(mu, dtype=np.float64)
+    var = np.asarray(var, dtype=np.float64)
+    if mu.ndim == 2:
+        mu, var = mu[None], var[None]
+    S, P, M = mu.shape
+    if var.shape != mu.shape:
+        raise ValueError("mu and var must have one shape")
+    mu, var = np.ascontiguousarray(mu), np.ascontiguousarray(var)
+    gm = np.asarray(dmu, dtype=np.float64).reshape(S, P, -1, M)
+    gv = np.asarray(dvar, dtype=np.float64).reshape(S, P, -1, M)
+    d = gm.shape[2]
+    gm = np.ascontiguousarray(gm.transpose(0, 1, 3, 2))           # [s][p][j*d + m]
+    gv = np.ascontiguousarray(gv.transpose(0, 1, 3, 2))
+    eps, ym, mask = _mc_common(fit, eps, y_max, valid_mask)
+    acq = np.zeros(M)
+    dacq = np.zeros((d, M), order="F")
+    _check(load_library().boss_acq_ei_mc_grad_moments(device, P, S, M, d, _dp(mu), _dp(var), _dp(gm), _dp(gv), fit._h, eps.shape[1],
+                                                      _dp(eps), _dp(ym), 0 if best is None else 1, 0.0 if best is None else float(best),
+                                                      _ucp(mask), _dp(acq), _dp(dacq)))
+    return acq, dacq
 
 
 # ---------------------------------------------------------------- several GPUs from one process (boss_multi_*)

@@ -26,6 +26,7 @@
 #include "rider.hpp"
 #include "latent_kernels.hpp"
 #include "nfit_kernels.hpp"
+#include "fitness.hpp"
 
 using namespace boss;
 
@@ -129,7 +130,7 @@ struct Ctx {
     bool prof_on = false;
     std::map<std::string, std::vector<std::pair<hipEvent_t, hipEvent_t>>> prof;
     std::vector<hipEvent_t> ev_pool;
-    Workspace vscratch, csc, pred, acq, batchA, batchX, batchMisc, craw, lgA, lgB, lgC, few, setdesc, setmom, gsetdesc, nlatjobs;
+    Workspace vscratch, csc, pred, acq, batchA, batchX, batchMisc, craw, lgA, lgB, lgC, few, setdesc, setmom, gsetdesc, nlatjobs, mceps;
     // batched likelihood gradients: the gradient passes of consecutive sets rotate over LLG_BANKS streams, each with its
     // own bank of workspaces (bank 0 = the main stream and lgA/lgB/lgC)
     static constexpr int LLG_BANKS = 4;
@@ -384,6 +385,7 @@ static int ctx_init(Ctx* c) {
                                PredictLds<PredG32>::BYTES));
     HIPCHK(hipFuncSetAttribute((const void*)predict_kernel<PredG64, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                PredictLds<PredG64>::BYTES));
+    HIPCHK(hipFuncSetAttribute((const void*)ei_mc_grad_set_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, MC_GRAD_MAX_LDS));
     return BOSS_OK;
 }
 
@@ -657,8 +659,20 @@ static bool few_fused() {
 #include "host_batch.inc"
 #include "host_latent.inc"
 #include "host_nfit.inc"
+// Monte-Carlo EI of a fitness program (host_fitness.inc) behind the prediction stages of host_predict.inc / host_acq.inc
+struct McEpi {
+    const FitProg* g;
+    int n_eps;
+    const double* eps;                                       // host, P × n_eps column-major
+};
+static int mc_stage(Ctx* c, hipStream_t s, int P, const McEpi& mc, const double** deps_out);
+static void mc_accumulate_launch(hipStream_t s, const double* mu, const double* var, size_t sstride, int ldm, int M, int s0, int s1, int S_total,
+                                 const EiPar& par, const McEpi& mc, const double* deps, double* acq_sum, int add);
+static void mc_grad_launch(hipStream_t s, const double* mu, const double* var, const double* dmu, const double* dvar, int M, int d, int S,
+                           const EiPar& par, const McEpi& mc, const double* deps, const unsigned char* mask, double* acq, double* dacq);
 #include "host_predict.inc"
 #include "host_acq.inc"
+#include "host_fitness.inc"
 #include "host_rider.inc"
 #include "host_track.inc"
 #include "host_multi.inc"

@@ -9,8 +9,9 @@
 static int acq_ei_impl(int P, int S, boss_gp_t* const* gps, const boss_cand_t* cand, const double* mean_Xs,
                        const double* fit_coefs, const double* y_max, int has_best, double best,
                        const unsigned char* valid_mask, double* acq_out, long* argmax_out, double* max_out,
-                       double* dpair, long idx_off, bool defer) {
-    if (P < 1 || S < 1 || !gps || !cand || !fit_coefs) return fail(BOSS_E_INVALID, "bad arguments");
+                       double* dpair, long idx_off, bool defer, const McEpi* mc = nullptr) {
+    // mc: the EI term is the Monte-Carlo mean of a fitness program (boss_acq_ei_mc, host_fitness.inc) — fit_coefs is not read, P <= EI_MAXP
+    if (P < 1 || S < 1 || !gps || !cand || (!fit_coefs && !mc)) return fail(BOSS_E_INVALID, "bad arguments");
     Ctx* c = cand->ctx;
     HIPCHK(hipSetDevice(c->device));
     for (int i = 0; i < P * S; ++i) {
@@ -40,8 +41,16 @@ static int acq_ei_impl(int P, int S, boss_gp_t* const* gps, const boss_cand_t* c
     // lock) write — a boss_acq_ei on the same context from another thread in that window cannot overwrite it
     double* hres = (double*)c->pinned + (defer ? MULTI_RES_OFF : 0);
     EiPar par;
-    int rc = ei_params(c, s, P, fit_coefs, y_max, has_best, best, &par, dcoef, dymax);
+    const double no_coefs[EI_MAXP] = {};
+    int rc = ei_params(c, s, P, mc ? no_coefs : fit_coefs, y_max, has_best, best, &par, dcoef, dymax);
     if (rc) return rc;
+    const double* deps = nullptr;
+    if (mc) {
+        rc = mc_stage(c, s, P, *mc, &deps);
+        if (rc) return rc;
+    }
+    EiPar par0 = par;                                        // (mode 0: acq_epilogue_kernel adds 0.0 to the sums the Monte-Carlo kernel left)
+    par0.mode = 0;
     if (valid_mask) (void)hipMemcpyAsync(dmask, valid_mask, M, hipMemcpyHostToDevice, s);
     if (S > 1) (void)hipMemsetAsync(dacq, 0, sizeof(double) * M, s);
     std::vector<double> hmean;
@@ -69,10 +78,12 @@ static int acq_ei_impl(int P, int S, boss_gp_t* const* gps, const boss_cand_t* c
             (void)hipStreamSynchronize(s);
             return rc;
         }
+        if (mc) mc_accumulate_launch(s, mu_all, var_all, pm, M, M, 0, S, S, par, *mc, deps, dacq, 0);
+        else
         hipLaunchKernelGGL(ei_accumulate_set_kernel, dim3((M + 255) / 256), dim3(256), 0, s, (const double*)mu_all, (const double*)var_all, pm, M, M,
                            0, S - 1, par, dcoef, dymax, dacq);
         hipLaunchKernelGGL(acq_epilogue_kernel, dim3(1), dim3(ACQ_EPI_THREADS), 0, s, (const double*)(mu_all + pm * (S - 1)),
-                           (const double*)(var_all + pm * (S - 1)), M, M, par, dcoef, dymax, dacq, 1, 1.0 / S, valid_mask ? dmask : nullptr, hres,
+                           (const double*)(var_all + pm * (S - 1)), M, M, mc ? par0 : par, dcoef, dymax, dacq, 1, 1.0 / S, valid_mask ? dmask : nullptr, hres,
                            (acq_out || defer) ? 0ull : ++c->acq_seq, dpair, idx_off);
     } else
     for (int sm = 0; sm < S; ++sm) {
@@ -95,7 +106,13 @@ static int acq_ei_impl(int P, int S, boss_gp_t* const* gps, const boss_cand_t* c
             }
         }
         ProfScope ps(c, sm + 1 < S ? "ei" : "argmax");
-        if (sm + 1 < S)
+        if (mc) {
+            // this sample's Monte-Carlo term (BI: its own ε column) into the sums; behind the last one the mean, the mask and the arg-max
+            mc_accumulate_launch(s, dmu, dvar, 0, M, M, 0, 1, S, par, *mc, S > 1 ? deps + (size_t)sm * P : deps, dacq, sm > 0 ? 1 : 0);
+            if (sm + 1 == S)
+                hipLaunchKernelGGL(acq_epilogue_kernel, dim3(1), dim3(ACQ_EPI_THREADS), 0, s, dmu, dvar, M, M, par0, dcoef, dymax, dacq, 1, 1.0 / S,
+                                   valid_mask ? dmask : nullptr, hres, (acq_out || defer) ? 0ull : ++c->acq_seq, dpair, idx_off);
+        } else if (sm + 1 < S)
             hipLaunchKernelGGL(ei_accumulate_kernel, dim3((M + 255) / 256), dim3(256), 0, s, dmu, dvar, M, M, par, dcoef, dymax,
                                dacq);
         else                                                 // last sample: EI + BI average + mask + arg-max in one launch

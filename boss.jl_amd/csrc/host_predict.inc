@@ -1384,10 +1384,12 @@ static int grad_set_enqueue(int n, boss_gp_t* const* gps, const boss_cand* cd, c
 // gradients stay on the device ([s][p] slices), and ONE epilogue applies the chain rule per sample and sums in ascending s.
 // Equally shaped members take the set launches (grad_set_enqueue); any other list, BOSS_NO_SET_PREDICT=1 and a set-path
 // allocation failure go member by member through grad_enqueue into the same slices.
-extern "C" int boss_acq_ei_grad_set(int P, int S, boss_gp_t* const* gps, int M, const double* Xs, const double* mean_Xs,
-                                    const double* mean_grad, const double* fit_coefs, const double* y_max, int has_best,
-                                    double best, const unsigned char* valid_mask, double* acq_out, double* dacq_out) {
-    if (P < 1 || S < 1 || !gps || M < 1 || !Xs || !fit_coefs || !acq_out || !dacq_out) return fail(BOSS_E_INVALID, "bad arguments");
+// mc: the EI term and its gradient are those of a fitness program's Monte-Carlo mean (boss_acq_ei_mc_grad, host_fitness.inc); fit_coefs
+// is not read, P <= EI_MAXP, and S = 1 takes this path too.
+static int acq_ei_grad_set_impl(int P, int S, boss_gp_t* const* gps, int M, const double* Xs, const double* mean_Xs,
+                                const double* mean_grad, const double* fit_coefs, const double* y_max, int has_best,
+                                double best, const unsigned char* valid_mask, double* acq_out, double* dacq_out, const McEpi* mc) {
+    if (P < 1 || S < 1 || !gps || M < 1 || !Xs || (!fit_coefs && !mc) || !acq_out || !dacq_out) return fail(BOSS_E_INVALID, "bad arguments");
     if ((long long)P * S * M > (1LL << 30)) return fail(BOSS_E_INVALID, "P·S·M above 2^30 is not supported");
     const int n = P * S;
     for (int i = 0; i < n; ++i) {
@@ -1398,7 +1400,7 @@ extern "C" int boss_acq_ei_grad_set(int P, int S, boss_gp_t* const* gps, int M, 
     }
     for (int i = 0; i < n; ++i)
         if (!gps[i]->fitted) return fail(BOSS_E_NOT_FITTED, "handle has no valid factorisation");
-    if (S == 1)
+    if (S == 1 && !mc)
         return boss_acq_ei_grad(P, gps, M, Xs, mean_Xs, mean_grad, fit_coefs, y_max, has_best, best, valid_mask, acq_out, dacq_out);
     Ctx* c = gps[0]->ctx;
     HIPCHK(hipSetDevice(c->device));
@@ -1425,8 +1427,14 @@ extern "C" int boss_acq_ei_grad_set(int P, int S, boss_gp_t* const* gps, int M, 
     double* dymax = dcoef + P;
     unsigned char* dmask = (unsigned char*)(dacq + nd);
     EiPar par;
-    rc = ei_params(c, s, P, fit_coefs, y_max, has_best, best, &par, dcoef, dymax);
+    const double no_coefs[EI_MAXP] = {};
+    rc = ei_params(c, s, P, mc ? no_coefs : fit_coefs, y_max, has_best, best, &par, dcoef, dymax);
     if (rc) return drain(c, rc);
+    const double* deps = nullptr;
+    if (mc) {
+        rc = mc_stage(c, s, P, *mc, &deps);
+        if (rc) return drain(c, rc);
+    }
     if (mean_Xs) (void)hipMemcpyAsync(dmean, mean_Xs, sizeof(double) * nm, hipMemcpyHostToDevice, s);
     if (mean_grad) (void)hipMemcpyAsync(dmg, mean_grad, sizeof(double) * ndm, hipMemcpyHostToDevice, s);
     if (valid_mask) (void)hipMemcpyAsync(dmask, valid_mask, M, hipMemcpyHostToDevice, s);
@@ -1444,10 +1452,18 @@ extern "C" int boss_acq_ei_grad_set(int P, int S, boss_gp_t* const* gps, int M, 
             if (rc) return drain(c, rc);
         }
     }
+    if (mc) mc_grad_launch(s, dmu, dvar, dgm, dgv, M, d, S, par, *mc, deps, valid_mask ? (const unsigned char*)dmask : nullptr, dacq, ddacq);
+    else
     hipLaunchKernelGGL(ei_grad_set_kernel, dim3((M + 127) / 128), dim3(128), 0, s, (const double*)dmu, (const double*)dvar, (const double*)dgm,
                        (const double*)dgv, M, d, S, par, (const double*)dcoef, (const double*)dymax,
                        valid_mask ? (const unsigned char*)dmask : nullptr, dacq, ddacq);
     return finish(c, {{acq_out, dacq, sizeof(double) * M}, {dacq_out, ddacq, sizeof(double) * dm}});
+}
+
+extern "C" int boss_acq_ei_grad_set(int P, int S, boss_gp_t* const* gps, int M, const double* Xs, const double* mean_Xs,
+                                    const double* mean_grad, const double* fit_coefs, const double* y_max, int has_best,
+                                    double best, const unsigned char* valid_mask, double* acq_out, double* dacq_out) {
+    return acq_ei_grad_set_impl(P, S, gps, M, Xs, mean_Xs, mean_grad, fit_coefs, y_max, has_best, best, valid_mask, acq_out, dacq_out, nullptr);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -1355,4 +1355,11 @@ end
 # not bound: boss_prof_reset — measurement helper of bench.py
 # not bound: boss_prof_get — measurement helper of bench.py
 # not bound: boss_multi_acq_ei — superseded here by boss_multi_cand_create + boss_multi_acq_ei_cand (same exchange, candidate shards uploaded once)
+# not bound: boss_fit_create — fitness programs: a Julia closure is traced by the Python DeviceFitness only; BOSS.NonlinFitness keeps the reference's host path here
+# not bound: boss_fit_free — see boss_fit_create
+# not bound: boss_fit_eval_host — see boss_fit_create (the host run of the kernels' interpreter, used by tests)
+# not bound: boss_acq_ei_mc — Monte-Carlo EI of a fitness program; needs boss_fit_create
+# not bound: boss_acq_ei_mc_moments — Monte-Carlo EI of a fitness program; needs boss_fit_create
+# not bound: boss_acq_ei_mc_grad — Monte-Carlo EI of a fitness program; needs boss_fit_create
+# not bound: boss_acq_ei_mc_grad_moments — Monte-Carlo EI of a fitness program; needs boss_fit_create
 end # module

@@ -25,6 +25,7 @@ import numpy as np
 from . import acquisition as acq_host
 from . import api
 from . import distributed as dist_util
+from .fitness import DeviceFitness
 from .model import HipGaussianProcessPosterior
 from .problem import BossOptions, BossProblem, NonlinFitness, best_so_far, in_bounds, in_cons, in_domain
 
@@ -78,6 +79,13 @@ def moments_acquisition(problem: BossProblem, mu: np.ndarray, var: np.ndarray, X
     return api.acq_ei_moments(mu, var, ei.fitness.coefs, problem.y_max, b, mask, problem.model.device)
 
 
+def _mc_eps(problem: BossProblem, n_posts: int, eps_seed) -> np.ndarray:
+    """The ε-samples of expected_improvement(::NonlinFitness): ϵ_sample_count columns for one posterior, one column per posterior
+    sample otherwise (expected_improvement.jl:116-119)."""
+    count = problem.acquisition.eps_samples if n_posts == 1 else n_posts
+    return acq_host.sample_eps(problem.data.Y.shape[0], count, np.random.default_rng(eps_seed))
+
+
 def acquisition_values(problem: BossProblem, posts: Sequence[HipGaussianProcessPosterior], Xs: np.ndarray,
                        cand: Optional[api.Candidates] = None, eps_seed: Optional[int] = 0):
     """vals = acq.(eachcol(xs)) for acq = construct_safe_acquisition(problem) — device-evaluated.
@@ -92,6 +100,27 @@ def acquisition_values(problem: BossProblem, posts: Sequence[HipGaussianProcessP
     mask = None
     if ei.cons_safe:                                                   # make_safe (expected_improvement.jl:58-65)
         mask = in_bounds(Xs, problem.domain.bounds) & in_cons(Xs, problem.domain.cons)
+    if isinstance(ei.fitness, DeviceFitness):
+        # the closure was traced into a fitness program: the ε-average runs on the device behind the prediction (boss_acq_ei_mc),
+        # with the ε draw of the host path below — DeviceFitness(f) and NonlinFitness(f) see identical ε
+        eps = _mc_eps(problem, len(posts), eps_seed)
+        ym = problem.y_max if constrained else None
+        if any(isinstance(s.gp, api.GibbsGP) for p in posts for s in p.slices):
+            # posteriors whose handles boss_acq_ei does not take: their moments, then the Monte-Carlo epilogue on those
+            if own:
+                cand.close()
+            mv = [p.mean_and_var(Xs) for p in posts]
+            return api.acq_ei_mc_moments(np.stack([m for m, _ in mv]), np.stack([v for _, v in mv]), ei.fitness.program, eps, ym, b, mask,
+                                         problem.model.device)
+        gps = [[s.gp for s in p.slices] for p in posts]
+        means = None
+        if posts[0].slices[0]._mean_s(Xs) is not None:
+            means = np.stack([np.stack([s._mean_s(Xs) for s in p.slices], axis=0) for p in posts], axis=0)   # S×P×M
+        try:
+            return api.acq_ei_mc(gps, cand, ei.fitness.program, eps, ym, b, mask, means)
+        finally:
+            if own:
+                cand.close()
     if isinstance(ei.fitness, NonlinFitness):
         # expected_improvement(::NonlinFitness) needs a user closure per Monte-Carlo sample: the device
         # provides (μ, σ²) for every candidate / output / posterior sample, the ε-average runs on the host
@@ -383,14 +412,26 @@ class HipGradientAM:
     seed: Optional[int] = None
     group: object = None
     mean_grad: Optional[Callable] = None
+    eps_seed: Optional[int] = 0         # DeviceFitness: the ε-samples are drawn once per maximize_acquisition call (common random
+    #                                     numbers across the iterations: the ascent climbs ONE deterministic surface)
+
+    def _eps(self, problem: BossProblem, n_posts: int) -> np.ndarray:
+        """The ε-samples of this maximize_acquisition call (drawn at its first use, kept until the next call begins)."""
+        key = (problem.data.Y.shape[0], problem.acquisition.eps_samples if n_posts == 1 else n_posts)
+        cache = self.__dict__.setdefault("_eps_cache", {})
+        if key not in cache:
+            cache[key] = _mc_eps(problem, n_posts, self.eps_seed)
+        return cache[key]
 
     def _value_and_grad(self, problem: BossProblem, posts, X):
         ei = problem.acquisition
-        if isinstance(ei.fitness, NonlinFitness):
-            raise NotImplementedError("HipGradientAM needs the analytic EI of LinFitness")
+        mc = isinstance(ei.fitness, DeviceFitness)
+        if isinstance(ei.fitness, NonlinFitness) and not mc:
+            raise NotImplementedError("HipGradientAM needs the analytic EI of LinFitness, or a DeviceFitness")
         b = best_so_far(ei.fitness, problem.data.Y, problem.y_max)
         mask = (in_bounds(X, problem.domain.bounds) & in_cons(X, problem.domain.cons)) if ei.cons_safe else None
         M = X.shape[1]
+        eps = self._eps(problem, len(posts)) if mc else None
         mg = None                                            # P×d×M Jacobian of the prior mean: the same for every sample
         if self.mean_grad is not None:
             mg = np.stack([np.asarray(self.mean_grad(X[:, j]), float) for j in range(M)], axis=2)
@@ -402,6 +443,22 @@ class HipGradientAM:
             return np.stack([np.zeros(M) if r is None else np.asarray(r, float) for r in rows])
 
         nonstat = any(isinstance(s.gp, api.GibbsGP) for post in posts for s in post.slices)
+        if mc and nonstat:
+            # nonstationary posteriors: every slice's moments and moment gradients, then the Monte-Carlo chain rule on those
+            # (boss_acq_ei_mc_grad_moments sums the samples in ascending order)
+            mvg = [[s.mean_and_var_grad(X) if mg is None else s.mean_and_var_grad(X, mean_grad=mg[i]) for i, s in enumerate(post.slices)]
+                   for post in posts]
+            mu, var, dmu, dvar = (np.stack([np.stack([r[q] for r in row]) for row in mvg]) for q in range(4))
+            return api.acq_ei_mc_grad_moments(mu, var, dmu, dvar, ei.fitness.program, eps, problem.y_max, b, mask, problem.model.device)
+        if mc:
+            # the Monte-Carlo EI of the traced program and its gradient in ONE device call, one sample or many (boss_acq_ei_mc_grad)
+            mm = [means(post) for post in posts]
+            ms = None
+            if any(m is not None for m in mm):
+                ms = np.stack([np.zeros((len(post.slices), M)) if m is None else m for m, post in zip(mm, posts)])
+            mgs = None if mg is None else np.stack([mg] * len(posts))
+            return api.acq_ei_mc_grad([[s.gp for s in post.slices] for post in posts], X, ei.fitness.program, eps, problem.y_max, b, mask,
+                                      ms, mgs)
         if len(posts) > 1 and not nonstat:
             # BI: the sample mean of the acquisition and of its gradient in ONE device call (boss_acq_ei_grad_set)
             mm = [means(post) for post in posts]
@@ -435,6 +492,7 @@ class HipGradientAM:
             lb, ub = dom.bounds
             span = np.where(np.isfinite(ub - lb), ub - lb, 1.0)[:, None]
             cont = ~dom.discrete
+            self.__dict__.pop("_eps_cache", None)           # a DeviceFitness draws its ε-samples once per call, at the first evaluation
             f, g = self._value_and_grad(problem, posts, X)
             step = np.full(X.shape[1], 0.05)                 # relative to the box, per start
             for _ in range(self.iters):

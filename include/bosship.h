@@ -499,6 +499,83 @@ int boss_acq_ei_grad_set(int P, int S, boss_gp_t* const* gps, int M, const doubl
                          const double* mean_grad, const double* fit_coefs, const double* y_max, int has_best,
                          double best, const unsigned char* valid_mask, double* acq_out, double* dacq_out);
 
+/* ---- fitness programs: Monte-Carlo EI of a nonlinear fitness on the device ------------------------------------------------
+ * Replaces: expected_improvement(::NonlinFitness, ...) (src/acquisitions/expected_improvement.jl:104-111) inside
+ * construct_acquisition (:49-90), and its ForwardDiff derivative inside OptimizationAM (src/acquisition_maximizers/
+ * optimization.jl:36,100).  A closure cannot cross the C ABI; a straight-line arithmetic program can.
+ *
+ * boss_fit_t holds a validated program in SSA form over P inputs y_0..y_{P-1}:
+ *   value ids 0..P-1 are the inputs, P..P+n_const-1 the constants, P+n_const+i the result of instruction i;
+ *   code      3*n_instr ints, instruction i = (op, a, b) at code[3i..3i+2]; a and b are EARLIER value ids, b = -1 on unary ops;
+ *   out_id    the value id that is the program's value (an input or a constant is allowed);
+ *   limits    P <= 16, n_const <= 32, n_instr <= 64.
+ * Opcodes (BOSS_FIT_*): ADD SUB MUL DIV (binary), NEG ABS SQUARE SQRT EXP LOG SIN COS TANH (unary), POW MIN MAX (binary).
+ * Values are what IEEE fp64 arithmetic and libm give (LOG of a negative number is NaN); MIN / MAX return NaN when an operand is NaN.
+ * Derivative conventions (reverse sweep, boss_fit_eval_host and the gradient kernels):
+ *   ABS'(0) = 0;  MIN and MAX pass the derivative of the FIRST operand on a tie;  SQRT'(0) = +Inf, as IEEE gives;
+ *   POW(a, b) differentiates in both operands; the d/db term is dropped when b is a constant id, so that a < 0 with an integer
+ *   constant exponent gives no NaN;  an instruction whose adjoint is exactly 0 passes nothing on.
+ * boss_fit_create returns BOSS_E_INVALID (with a message) for a forward or self reference, an unknown opcode, an exceeded limit, a
+ * non-finite constant, b != -1 on a unary op, a bad out_id.  boss_fit_create / boss_fit_free / boss_fit_eval_host need no device.
+ * boss_fit_eval_host: Y P×n column-major, f_out n values, df_out P×n (df/dy per column) or NULL — the interpreter function the
+ * kernels call, run on the host. */
+#define BOSS_FIT_ADD     0
+#define BOSS_FIT_SUB     1
+#define BOSS_FIT_MUL     2
+#define BOSS_FIT_DIV     3
+#define BOSS_FIT_NEG     4
+#define BOSS_FIT_ABS     5
+#define BOSS_FIT_SQUARE  6
+#define BOSS_FIT_SQRT    7
+#define BOSS_FIT_EXP     8
+#define BOSS_FIT_LOG     9
+#define BOSS_FIT_SIN    10
+#define BOSS_FIT_COS    11
+#define BOSS_FIT_TANH   12
+#define BOSS_FIT_POW    13
+#define BOSS_FIT_MIN    14
+#define BOSS_FIT_MAX    15
+typedef struct boss_fit boss_fit_t;
+int boss_fit_create(int P, int n_const, const double* consts, int n_instr, const int* code, int out_id, boss_fit_t** out);
+void boss_fit_free(boss_fit_t* fit);
+int boss_fit_eval_host(const boss_fit_t* fit, int n, const double* Y, double* f_out, double* df_out);
+
+/* The four acquisition calls with the analytic EI term of LinFitness replaced by the Monte-Carlo mean over eps-samples of a
+ * fitness program.  Every argument is that of the call named beside it, except that `fit_coefs` is replaced by
+ *   fit     the program (its P must equal the call's P);
+ *   n_eps, eps   P×n_eps standard-normal draws, column-major (sample_eps, expected_improvement.jl:119), uploaded once per call.
+ * EI term of one posterior sample, sigma = sqrt(clipped variance):
+ *   S = 1 (MAP):  EI_j = (1/n_eps) sum_k max(0, f(mu_j + sigma_j .* eps_k) - best)                         (:104-107)
+ *   S > 1 (BI):   sample s uses column s of eps alone (n_eps must equal S), the acquisition is the mean over s   (:87-90,108-111)
+ * NaN from the program propagates (max(0, NaN) is NaN, as in Julia; the arg-max ranks NaN largest).  Everything else is as in the
+ * analytic calls: has_best = 0 gives the feasibility product alone (the program is not evaluated), y_max = NULL and has_best = 0
+ * give 0, a variance in [-1e-8, 0) is clipped to 0, below that the candidate is -Inf (gradient 0), +Inf in y_max is factor 1,
+ * valid_mask zeroes, first-index arg-max.
+ * Gradient, with grad sigma_p = grad var_p / (2 sigma_p), and 0 where the variance was clipped or is 0:
+ *   grad EI_j = (1/n_eps) sum_p (A_p grad mu_p + B_p grad sigma_p),
+ *   A_p = sum_k 1[f_k > best] df/dy_p,   B_p = sum_k 1[f_k > best] df/dy_p eps_pk,
+ * and acq = EI*FP, grad acq = grad EI*FP + EI*grad FP as in boss_acq_ei_grad.
+ * The sums over k follow a fixed tree (csrc/fitness.hpp), no atomics: repeated calls agree bit for bit.
+ * BOSS_E_INVALID: fit's P differs from P, n_eps < 1, S > 1 with n_eps != S, P*n_eps > 2^20, a non-finite eps.
+ *   boss_acq_ei_mc               [boss_acq_ei]               prediction on the device, then the Monte-Carlo epilogue, arg-max;
+ *   boss_acq_ei_mc_moments       [boss_acq_ei_moments]       from host moments mu / var S×P×M;
+ *   boss_acq_ei_mc_grad          [boss_acq_ei_grad_set]      value and gradient, S >= 1, the same handle kinds;
+ *   boss_acq_ei_mc_grad_moments  [boss_acq_ei_grad_moments, with a leading S]  mu / var [s][p][M], dmu / dvar [s][p][d×M]; samples
+ *                                summed in ascending s and divided once (nonstationary posteriors: boss_ngp_predict_grad_set output).
+ * Not offered with a fitness program: the boss_multi_* calls, boss_acq_ei_tracks, boss_gp_update_acq. */
+int boss_acq_ei_mc(int P, int S, boss_gp_t* const* gps, const boss_cand_t* cand, const double* mean_Xs, const boss_fit_t* fit,
+                   int n_eps, const double* eps, const double* y_max, int has_best, double best,
+                   const unsigned char* valid_mask, double* acq_out, long* argmax_out, double* max_out);
+int boss_acq_ei_mc_moments(int device, int P, int S, int M, const double* mu, const double* var, const boss_fit_t* fit, int n_eps,
+                           const double* eps, const double* y_max, int has_best, double best,
+                           const unsigned char* valid_mask, double* acq_out, long* argmax_out, double* max_out);
+int boss_acq_ei_mc_grad(int P, int S, boss_gp_t* const* gps, int M, const double* Xs, const double* mean_Xs,
+                        const double* mean_grad, const boss_fit_t* fit, int n_eps, const double* eps, const double* y_max,
+                        int has_best, double best, const unsigned char* valid_mask, double* acq_out, double* dacq_out);
+int boss_acq_ei_mc_grad_moments(int device, int P, int S, int M, int d, const double* mu, const double* var, const double* dmu,
+                                const double* dvar, const boss_fit_t* fit, int n_eps, const double* eps, const double* y_max,
+                                int has_best, double best, const unsigned char* valid_mask, double* acq_out, double* dacq_out);
+
 /* boss_ngp_predict_grad for n nonstationary posteriors at the same M candidates in ONE call, and the sample-averaged acquisition
  * gradient on top of it: boss_acq_ei_grad_set for NonstationaryGP posteriors (BI samples of a finite_nongp model under
  * OptimizationAM, src/acquisitions/expected_improvement.jl:87-90 inside src/acquisition_maximizers/optimization.jl:89-118).
