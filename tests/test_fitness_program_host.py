@@ -46,6 +46,51 @@ def test_traced_program_matches_closure_and_its_derivative(B, name):
     assert np.abs(fd - dfh).max() <= 1e-6 * scale
 
 
+PINNED = ["F1", "F2", "F3", "F4", "F5", "G1", "W3g", "W3v", "W2v", "BIG"]
+
+
+@pytest.mark.parametrize("name", PINNED)
+def test_derivative_against_50_digit_central_differences(B, name):
+    """An independent pin of the reverse sweep: FitnessProgram.grad was written rule for rule from the C sweep, so a rule wrong the same
+    way in both passes every comparison between them.  Here df/dy comes from central differences of a forward-only mpmath interpreter
+    (50 digits, h = 1e-20: error ~1e-30), at 20 standard-normal points, none within 1e-6 of a kink of ABS / MIN / MAX (asserted).
+    Bound: 1e-13 · max(1, max|∇f|), the one numpy grad and eval_host are held to against each other.
+    Observed max|grad - mp| = max|eval_host - mp| (bound): F1 0 (1e-13), F2 2.2e-16 (4.2e-13), F3 0 (1e-13, nearest kink 7.9e-2),
+    F4 8.9e-16 (9.6e-13, nearest kink 9.3e-2), F5 5.6e-17 (1e-13), G1 2.2e-16 (1.0e-13), W3g 2.2e-16 (1.6e-13), W3v 5.6e-17 (1e-13),
+    W2v 2.8e-17 (1e-13), BIG 2.2e-16 (1e-13)."""
+    if name == "BIG":
+        prog = cases.big_program(B.api)
+        assert prog.code.shape[0] == B.api.FIT_MAX_INSTR and prog.consts.shape[0] == B.api.FIT_MAX_CONSTS and prog.P == B.api.FIT_MAX_INPUTS
+        read = set(prog.code[:, 1]) | set(prog.code[:, 2])
+        assert set(range(prog.P + prog.consts.shape[0])) <= read                      # every input and every constant is read
+        ids, uses = np.unique(prog.code[:, 1:], return_counts=True)
+        assert uses[ids >= prog.P + prog.consts.shape[0]].max() >= 3                  # an adjoint that accumulates
+    else:
+        f, P = cases.F[name]
+        prog = B.DeviceFitness(f, P).program
+    Y = np.random.default_rng(21).standard_normal((prog.P, 20))
+    ref, kink = cases.mp_grad(prog, Y)
+    assert kink >= 1e-6, kink
+    g = prog.grad(Y)
+    _, dfh = prog.eval_host(Y, want_grad=True)
+    tol = 1e-13 * max(1.0, np.abs(ref).max())
+    print(f"{name}: max|grad - mp| = {np.abs(g - ref).max():.3e}, max|eval_host - mp| = {np.abs(dfh - ref).max():.3e} (tol {tol:.3e}), "
+          f"nearest kink {kink:.3e}")
+    assert np.abs(g - ref).max() <= tol
+    assert np.abs(dfh - ref).max() <= tol
+
+
+def test_the_closures_reach_every_workgroup_shape(B):
+    """The launch rule of the Monte-Carlo kernels on the traced programs: each kernel runs with 1, 2, 3 and 4 waves somewhere (the
+    device tests pick their programs by this; a closure that changes size cannot lose a shape silently)."""
+    for grad in (False, True):
+        seen = set()
+        for f, P in cases.F.values():
+            prog = B.DeviceFitness(f, P).program
+            seen.add(cases.mc_waves(prog.P, prog.code.shape[0], grad))
+        assert seen == {1, 2, 3, 4}, (grad, seen)
+
+
 def _one(api, op, x, z=None, const_b=False):
     """(value, d/da, d/db) of one instruction through boss_fit_eval_host."""
     name = api.FIT_OP[op]

@@ -197,6 +197,257 @@ def test_moments_gradient_against_the_formula(api, fits, M, d, name, S):
         assert np.abs(g - rg).max() <= 1e-11 * max(1.0, np.abs(rg).max()), mode
 
 
+# ------------------------------------------------------------------------------------------ gradient: the branches of workload sizes
+ALL_MODES = ("both", "best_only", "cons_only", "none")
+SPECIAL_65 = ((2, 64), 4, 6)                                      # (masked, clipped, poisoned) of the test above at M = 65
+SPECIAL_5 = ((1,), 2, 3)
+
+
+def grad_case(dfit, name, S, M, d, K, seed, special=None, best=0.15):
+    """Seeded inputs of a gradient test; `special` = (masked candidates, the one with a variance of -1e-9, the one with -1e-6).
+    The guard is asserted here, on the inputs: choosing a seed needs no device."""
+    P = dfit.y_dim
+    mu, var, dmu, dvar = cases.moments(seed, S, P, M, d)
+    eps = cases.eps_for(seed + 1, S, P, K)
+    mask = np.ones(M, bool)
+    jc = jp = None
+    if special is not None:
+        masked, jc, jp = special
+        mask[list(masked)] = False
+        var[0, 0, jc] = -1e-9
+        var[S - 1, P - 1, jp] = -1e-6
+    guard(dfit, name, mu, var, eps, best)
+    return mu, var, dmu, dvar, eps, mask, jc, jp
+
+
+def check_grad(api, dfit, label, case, best=0.15, modes=ALL_MODES):
+    """Value and gradient of the gradient kernel against the formula in every mode of `modes`, bit-identical on repeat; only the poisoned
+    candidate is exempt from the value comparison (it must be -Inf with gradient 0).  Returns the largest errors seen."""
+    mu, var, dmu, dvar, eps, mask, jc, jp = case
+    ym_all = y_max_for(dfit.y_dim)
+    tol_v = vtol(dfit.program, mu, var, eps, best)
+    worst_v = worst_g = 0.0
+    for mode in modes:
+        hb, cons = MODES[mode]
+        ym, b = ym_all if cons else None, best if hb else None
+        acq, dacq = api.acq_ei_mc_grad_moments(mu, var, dmu, dvar, dfit.program, eps, ym, b, mask)
+        acq2, dacq2 = api.acq_ei_mc_grad_moments(mu, var, dmu, dvar, dfit.program, eps, ym, b, mask)
+        assert np.array_equal(acq, acq2) and np.array_equal(dacq, dacq2), mode
+        ra, rg = cases.ref_value_and_grad(dfit.program, mu, var, dmu, dvar, eps, ym, b, mask)
+        ok = np.isfinite(ra)
+        tol_g = 1e-11 * max(1.0, np.abs(rg).max())
+        with np.errstate(invalid="ignore"):                     # (-Inf minus -Inf at the poisoned candidate, left out by `ok`)
+            ev, eg = np.abs(acq - ra)[ok].max(), np.abs(dacq - rg).max()
+        print(f"{label} {mode}: max|Δacq| = {ev:.3e} (tol {tol_v:.3e}), max|Δ∇acq| = {eg:.3e} (tol {tol_g:.3e})")
+        assert np.array_equal(np.isfinite(acq), ok) and ev <= tol_v, mode
+        assert eg <= tol_g, mode
+        assert np.all(dacq[:, ~mask] == 0.0) and np.all(acq[~mask] == 0.0), mode
+        if jp is not None and mode != "none":
+            assert int((~ok).sum()) == 1 and acq[jp] == -np.inf and np.all(dacq[:, jp] == 0.0), mode
+        else:
+            assert ok.all(), mode
+        worst_v, worst_g = max(worst_v, ev / tol_v), max(worst_g, eg / tol_g)
+    return worst_v, worst_g
+
+
+@pytest.mark.parametrize("K", [64, 65, 128, 200])
+@pytest.mark.parametrize("name", ["F2", "F3", "F5"])
+@pytest.mark.parametrize("d", [1, 8])
+@pytest.mark.parametrize("M", [1, 65])
+def test_moments_gradient_at_the_workload_eps_counts(api, fits, M, d, name, K):
+    """One posterior sample, 64 to 200 ε: one to four passes of the lanes over k, the A / B sums carried across passes, lanes busy in
+    one pass and idle in the next (K = 65, 200), in a four-wave (F2, F3) and a one-wave (F5) workgroup.
+    Observed over the 48 cases and four modes: max|Δacq| = 4.4e-16 (tol >= 1.4e-12), max|Δ∇acq| = 1.1e-14 (tol 1e-11 to 3.5e-10)."""
+    case = grad_case(fits[name], name, 1, M, d, K, 4000 + 10 * K + M + d, SPECIAL_65 if M > 8 else None)
+    check_grad(api, fits[name], f"{name} S=1 M={M} d={d} K={K}", case)
+
+
+@pytest.mark.parametrize("name", ["F2", "F3", "F5"])
+def test_moments_gradient_sums_start_afresh_for_every_sample(api, fits, name):
+    """S = 3, M = 65: one ε column per sample (K = 1 inside the wave); sums left over from the sample before would show in the next.
+    Observed: max|Δacq| = 3.3e-16 (tol >= 2.2e-12), max|Δ∇acq| = 4.4e-16 (tol >= 1e-11)."""
+    case = grad_case(fits[name], name, 3, 65, 8, 3, 4700, SPECIAL_65)
+    check_grad(api, fits[name], f"{name} S=3 M=65 d=8", case)
+
+
+@pytest.mark.parametrize("S", [1, 3])
+@pytest.mark.parametrize("d", [64, 65, 130])
+def test_moments_gradient_wide_x(api, fits, d, S):
+    """One, two and three passes of the lanes over the coordinates (the zeroing, the assembly and the final division), one masked
+    and one poisoned candidate among five.  Observed: max|Δacq| = 2.8e-17 (tol >= 1.7e-12), max|Δ∇acq| = 1.1e-16 (tol 1e-11)."""
+    case = grad_case(fits["F3"], "F3", S, 5, d, 65, 4800 + d + S, SPECIAL_5)
+    check_grad(api, fits["F3"], f"F3 S={S} M=5 d={d} K=65", case, modes=("both",))
+
+
+# ------------------------------------------------------------------------------------------ workgroup shapes
+SHAPE_PROGRAM = {False: {1: "F5", 2: "W2v", 3: "W3v", 4: "F1"}, True: {1: "F5", 2: "F4", 3: "W3g", 4: "F1"}}     # [gradient kernel?][waves]
+
+
+def test_the_closures_reach_every_workgroup_shape(fits):
+    """The launch rule (mc_block) on the traced programs' P and instruction counts: both kernels run with 1, 2, 3 and 4 waves."""
+    for grad in (False, True):
+        seen = {}
+        for name, dfit in fits.items():
+            p = dfit.program
+            seen.setdefault(cases.mc_waves(p.P, p.code.shape[0], grad), []).append(name)
+        print("gradient kernel" if grad else "value kernel", {w: seen[w] for w in sorted(seen)})
+        assert sorted(seen) == [1, 2, 3, 4]
+        for w, name in SHAPE_PROGRAM[grad].items():
+            assert name in seen[w]
+    # the rule itself at its edges: 32 | 33, 42 | 43, 64 | 65 slots
+    assert [cases.mc_waves(1, s - 3, False) for s in (32, 33, 42, 43, 64, 65)] == [4, 3, 3, 2, 2, 1]
+    assert [cases.mc_waves(1, (s - 6) // 2, True) for s in (32, 34, 42, 44, 64, 66)] == [4, 3, 3, 2, 2, 1]
+
+
+@pytest.mark.parametrize("waves", [1, 2, 3, 4])
+@pytest.mark.parametrize("grad", [False, True], ids=["value", "gradient"])
+def test_every_workgroup_shape(api, fits, grad, waves):
+    """A lone candidate, a second block of one wave, a third block of one wave: j = blockIdx.x · waves + wave and the exit of the
+    waves behind the last candidate, for workgroups of 64, 128, 192 and 256 threads.
+    Observed: value max|acq - ref| = 1.1e-16 (tol >= 1e-12); gradient max|Δacq| = 4.4e-16 (tol >= 1.4e-12), max|Δ∇acq| = 8.9e-16 (tol >= 1e-11)."""
+    name = SHAPE_PROGRAM[grad][waves]
+    p = fits[name].program
+    assert cases.mc_waves(p.P, p.code.shape[0], grad) == waves
+    for M in (1, waves + 1, 2 * waves + 1):
+        if grad:
+            case = grad_case(fits[name], name, 1, M, 2, 65, 5000 + 10 * waves + M, SPECIAL_5 if M >= 5 else None)
+            check_grad(api, fits[name], f"{name} waves={waves} M={M}", case, modes=("both",))
+        else:
+            check_value(api, fits, name, 1, M, 65, "both", 5100 + 10 * waves + M)
+
+
+# ------------------------------------------------------------------------------------------ program size limits
+BIG_BEST = 0.05
+
+
+@pytest.mark.parametrize("S", [1, 3])
+def test_largest_program(api, S):
+    """16 inputs, 32 constants, 64 instructions (cases.big_program): 56 KiB of LDS in the value kernel, the 112 KiB the gradient
+    kernel is allowed at most.  Observed: value 5.6e-17 (tol >= 1.3e-12); gradient max|Δacq| = 1.1e-16 (tol >= 1e-12), max|Δ∇acq| = 3.3e-16 (tol 1e-11)."""
+    big = cases.HandFitness(cases.big_program(api))
+    p = big.program
+    assert cases.mc_slots(p.P, p.code.shape[0], True) * 512 == 112 * 1024
+    check_value(api, {"BIG": big}, "BIG", S, 3, 65, "both", 5200 + S)
+    case = grad_case(big, "BIG", S, 3, 2, 65, 5210 + S, best=BIG_BEST)
+    f = np.concatenate([x.ravel() for x in cases.f_values(p, case[0], case[1], case[4])])
+    assert 0.2 <= (f > BIG_BEST).mean() <= 0.8                    # the indicator is on for some ε and off for others
+    check_grad(api, big, f"BIG S={S} M=3 d=2", case, best=BIG_BEST)
+
+
+@pytest.mark.parametrize("out_id", [1, 2], ids=["input", "constant"])
+def test_empty_programs(api, out_id):
+    """No instruction: the value is an input (f = y_1) or a constant (f = 0.7, ∇f = 0: ∇acq = EI ∇FP, and exactly 0 without constraints).
+    Observed: value 3.9e-16 (tol >= 1e-12); gradient max|Δacq| = 2.2e-16 (tol >= 1e-12), max|Δ∇acq| = 1.1e-16 (tol 1e-11)."""
+    fit = cases.HandFitness(api.FitnessProgram(2, [0.7], [], out_id))
+    for S in (1, 3):
+        check_value(api, {"E": fit}, "E", S, 3, 65, "both", 5300 + S)
+        case = grad_case(fit, "E", S, 3, 2, 65, 5310 + S)
+        check_grad(api, fit, f"empty out_id={out_id} S={S}", case)
+    if out_id == 2:
+        mu, var, dmu, dvar, eps, mask, _, _ = grad_case(fit, "E", 1, 3, 2, 65, 5311)
+        ym, best = y_max_for(2), 0.15
+        a_both, g_both = api.acq_ei_mc_grad_moments(mu, var, dmu, dvar, fit.program, eps, ym, best, mask)
+        fp, dfp = api.acq_ei_mc_grad_moments(mu, var, dmu, dvar, fit.program, eps, ym, None, mask)
+        a_best, g_best = api.acq_ei_mc_grad_moments(mu, var, dmu, dvar, fit.program, eps, None, best, mask)
+        assert np.all(g_best == 0.0) and np.all(np.abs(a_best - (0.7 - best)) <= vtol(fit.program, mu, var, eps, best))
+        assert np.abs(g_both - (0.7 - best) * dfp).max() <= 1e-11 * max(1.0, np.abs(g_both).max())
+        assert np.abs(a_both - (0.7 - best) * fp).max() <= vtol(fit.program, mu, var, eps, best)
+
+
+# ------------------------------------------------------------------------------------------ the reverse sweep on the device
+def device_gradient(api, prog, Y):
+    """(f, ∇f) at the columns of Y (P×n) read off the gradient kernel: one posterior sample, σ² = 0 and ε = 0 so y = μ exactly and no σ
+    term arises, ∇μ_p = e_p (d = P), no constraint, best = -1e3 below every value: acq = f - best, ∇acq = ∇f."""
+    P, n = Y.shape
+    dmu = np.zeros((1, P, P, n))
+    for p in range(P):
+        dmu[0, p, p, :] = 1.0
+    acq, dacq = api.acq_ei_mc_grad_moments(Y[None], np.zeros((1, P, n)), dmu, np.ones((1, P, P, n)), prog, np.zeros((P, 1)), None, -1e3, None)
+    return acq, dacq
+
+
+def test_reverse_sweep_conventions_on_the_device(api):
+    """Every opcode through fit_grad as the device runs it (slots strided in LDS, the device's libm), against boss_fit_eval_host at the
+    same points; test_fitness_program_host.py pins that function's conventions to their literal values.  Equality for the arithmetic
+    opcodes and the conventions; DIV and the libm opcodes at 1e-12 · max(1, |f| + |best|) and 1e-11 · max(1, max|∇f|).
+    A partial derivative of ±Inf is read with P = d = 1 (with more inputs the identity ∇μ makes Inf · 0 = NaN elsewhere, as IEEE says).
+    Observed for the opcodes under a tolerance: max|Δf| = 0 (tol 1e-9), max|Δ∇f| = 8.9e-16 (EXP at 1.7; tol 5.5e-11), 0 for the others."""
+    op = api.FIT_OP
+    un = lambda name: (1, [], [[op[name], 0, -1]], 1)             # noqa: E731
+    bi = lambda name: (2, [], [[op[name], 0, 1]], 2)              # noqa: E731
+    exact = [
+        ("ABS", un("ABS"), [[0.0, 1.5, -1.5]]),                                      # ABS'(0) = 0
+        ("NEG", un("NEG"), [[1.5, -3.0]]),
+        ("SQUARE", un("SQUARE"), [[1.5, -3.0]]),
+        ("SQRT", un("SQRT"), [[0.0, 4.0]]),                                          # SQRT'(0) = +Inf
+        ("ADD", bi("ADD"), [[1.5], [2.0]]),
+        ("SUB", bi("SUB"), [[1.5], [2.0]]),
+        ("MUL", bi("MUL"), [[1.5], [2.0]]),
+        ("MIN", bi("MIN"), [[1.0, 2.0, 1.0], [2.0, 1.0, 1.0]]),                      # ordered both ways, tied: the first operand
+        ("MAX", bi("MAX"), [[1.0, 2.0, 1.0], [2.0, 1.0, 1.0]]),
+        ("POW const", (1, [3.0], [[op["POW"], 0, 1]], 2), [[-2.0]]),                 # no ∂/∂b term, no NaN
+        ("POW var", bi("POW"), [[2.0], [3.0]]),                                      # ∂/∂b = r log(a)
+        ("dead branch", (2, [0.0], [[op["SQRT"], 0, -1], [op["MUL"], 3, 2], [op["ADD"], 4, 1]], 5), [[0.0], [0.7]]),
+    ]
+    for label, spec, pts in exact:
+        prog = api.FitnessProgram(*spec)
+        Y = np.array(pts, float)
+        f, df = prog.eval_host(Y, want_grad=True)
+        acq, dacq = device_gradient(api, prog, Y)
+        print(f"{label}: f = {acq - 1e3}, ∇f = {dacq.tolist()} (host {df.tolist()})")
+        assert np.array_equal(acq, f + 1e3), label
+        assert np.array_equal(dacq, df), label
+    # spelled out where a convention decides (the host test holds boss_fit_eval_host to the same literals)
+    _, g = device_gradient(api, api.FitnessProgram(*exact[0][1]), np.array([[0.0, 1.5, -1.5]]))
+    assert g.tolist() == [[0.0, 1.0, -1.0]]
+    _, g = device_gradient(api, api.FitnessProgram(*exact[3][1]), np.array([[0.0]]))
+    assert g[0, 0] == np.inf
+    _, g = device_gradient(api, api.FitnessProgram(*exact[7][1]), np.array(exact[7][2]))
+    assert g.tolist() == [[1.0, 0.0, 1.0], [0.0, 1.0, 0.0]]
+    _, g = device_gradient(api, api.FitnessProgram(*exact[8][1]), np.array(exact[8][2]))
+    assert g.tolist() == [[0.0, 1.0, 1.0], [1.0, 0.0, 0.0]]
+    a, g = device_gradient(api, api.FitnessProgram(*exact[9][1]), np.array([[-2.0]]))
+    assert a[0] == 992.0 and g[0, 0] == 12.0
+    a, g = device_gradient(api, api.FitnessProgram(*exact[11][1]), np.array([[0.0], [0.7]]))
+    assert a[0] == 0.7 + 1e3 and g[:, 0].tolist() == [0.0, 1.0]      # the adjoint 0 of SQRT passes nothing on: no 0 · Inf
+    worst_f = worst_g = 0.0
+    for label, spec, pts in [("DIV", bi("DIV"), [[3.0, -0.7], [2.0, 1.3]])] + \
+                            [(n, un(n), [[0.3, 1.7]]) for n in ("EXP", "LOG", "SIN", "COS", "TANH", "SQRT")]:
+        prog = api.FitnessProgram(*spec)
+        Y = np.array(pts, float)
+        f, df = prog.eval_host(Y, want_grad=True)
+        acq, dacq = device_gradient(api, prog, Y)
+        ef, eg = np.abs(acq - (f + 1e3)).max(), np.abs(dacq - df).max()
+        tol_f, tol_g = 1e-12 * max(1.0, np.abs(f).max() + 1e3), 1e-11 * max(1.0, np.abs(df).max())
+        print(f"{label}: max|Δf| = {ef:.3e} (tol {tol_f:.3e}), max|Δ∇f| = {eg:.3e} (tol {tol_g:.3e})")
+        assert ef <= tol_f and eg <= tol_g, label
+        worst_f, worst_g = max(worst_f, ef), max(worst_g, eg)
+    print(f"libm opcodes: max|Δf| = {worst_f:.3e}, max|Δ∇f| = {worst_g:.3e}")
+
+
+def test_nan_through_the_gradient_kernel(api, B):
+    """LOG of a negative number at one candidate (μ = -1, σ = 0): its acquisition is NaN and its gradient 0 (a NaN value is no
+    improvement and enters no sum); its neighbours match the formula.  Observed: max|Δacq| = 0 (tol 1e-12), max|Δ∇acq| = 1.1e-16 (tol 1e-11)."""
+    lg = B.DeviceFitness(lambda y: np.log(y[0]), 1)
+    M, d, K, best = 40, 2, 5, 0.1
+    rng = np.random.default_rng(5400)
+    mu, var = np.full((1, 1, M), 2.0), np.full((1, 1, M), 0.04)   # σ = 0.2: y > 0 for |ε| < 10
+    mu[0, 0, 17], var[0, 0, 17] = -1.0, 0.0
+    dmu, dvar = rng.uniform(-1, 1, (1, 1, d, M)), rng.uniform(-1, 1, (1, 1, d, M))
+    eps = cases.eps_for(5401, 1, 1, K)
+    others = np.arange(M) != 17
+    f = cases.f_values(lg.program, mu[:, :, others], var[:, :, others], eps)[0]
+    assert np.abs(f - best).min() > 1e-9 and (f > best).any()
+    acq, dacq = api.acq_ei_mc_grad_moments(mu, var, dmu, dvar, lg.program, eps, None, best, None)
+    assert np.isnan(acq[17]) and np.all(dacq[:, 17] == 0.0)
+    with np.errstate(all="ignore"):
+        ra, rg = cases.ref_value_and_grad(lg.program, mu, var, dmu, dvar, eps, None, best, None)
+    tol_v, tol_g = vtol(lg.program, mu[:, :, others], var[:, :, others], eps, best), 1e-11 * max(1.0, np.abs(rg[:, others]).max())
+    ev, eg = np.abs(acq - ra)[others].max(), np.abs(dacq - rg)[:, others].max()
+    print(f"LOG with one NaN candidate: max|Δacq| = {ev:.3e} (tol {tol_v:.3e}), max|Δ∇acq| = {eg:.3e} (tol {tol_g:.3e})")
+    assert ev <= tol_v and eg <= tol_g
+
+
 # ------------------------------------------------------------------------------------------ handles
 def _data(seed, d, N):
     rng = np.random.default_rng(seed)

@@ -53,6 +53,22 @@ def tol_for(O, post, N):
 @pytest.mark.parametrize("kernel", ["matern32", "matern52", "sqexp"])
 @pytest.mark.parametrize("d,N,M", [(3, 300, 70), (8, 512, 64), (2, 513, 1), (8, 1000, 257), (5, 1408, 1024), (8, 1500, 33)])
 def test_update_acq_matches_oracle_and_two_call_path(api, O, kernel, d, N, M):
+    check_update_acq(api, O, kernel, d, N, M)
+
+
+# 49 to 128 candidate strips: the chunk counts of rider_chunks() beyond 48 strips (6 up to 64 strips, 4 above), up to the 4096
+# candidates at which the call still rides.  N = 1408 is eleven block columns: the per-step chunk count takes every value from 1 to 6
+# (1 to 4); N = 1024 is the smallest block count at which a step runs four chunks.  One kernel each.
+@pytest.mark.parametrize("kernel,d,N,M", [("matern32", 5, 1408, 1537), ("matern52", 5, 1408, 2049), ("sqexp", 5, 1408, 4096),
+                                          ("matern52", 8, 1024, 3000)])
+def test_update_acq_many_candidate_strips(api, O, kernel, d, N, M):
+    """Observed, fused (tol = tol_for): M = 1537 |Δlogpdf| 5.0e-13, max|Δμ| 4.1e-14, max|Δσ²| 6.9e-15, max|Δacq| 1.3e-14 (tol 1.6e-7);
+    M = 2049 1.0e-12, 1.4e-13, 8.2e-15, 7.5e-15 (1.6e-7); M = 4096 1.7e-10, 9.1e-13, 1.1e-14, 2.6e-13 (2.3e-7); N = 1024, M = 3000
+    1.1e-13, 1.3e-14, 3.6e-15, 2.5e-15 (1.8e-9)."""
+    check_update_acq(api, O, kernel, d, N, M)
+
+
+def check_update_acq(api, O, kernel, d, N, M):
     X, y, Xs = make(d, N, M, seed=N + M)
     lam = np.linspace(0.3, 0.7, d)
     amp, sig = 1.2, 0.05
@@ -64,7 +80,10 @@ def test_update_acq_matches_oracle_and_two_call_path(api, O, kernel, d, N, M):
     g = api.GP(X, y, kernel)
     cand = api.Candidates(Xs)
     r = g.update_acq(lam, amp, sig, cand, best=best, want_acq=True, want_moments=True)
-    assert r["fused"], "three or more block columns on the library's own stream: the substitution rides along"
+    print(f"{kernel} d={d} N={N} M={M}: fused {r['fused']}, |Δlogpdf| = {abs(r['logpdf'] - post.logpdf):.3e}, max|Δμ| = {np.abs(r['mu'] - mu_o).max():.3e}, "
+          f"max|Δσ²| = {np.abs(r['var'] - var_o).max():.3e}, max|Δacq| = {np.abs(r['acq'] - acq_o).max():.3e} (tol {tol:.3e})")
+    assert r["fused"], ("three or more block columns on the library's own stream: the substitution rides along "
+                        f"(updates repeated on a simpler schedule in this process, chain switched off: {api._fallbacks(0)})")
     assert abs(r["logpdf"] - post.logpdf) <= tol * (1 + abs(post.logpdf))
     assert np.all(np.abs(r["mu"] - mu_o) <= tol * (1 + np.abs(mu_o))), np.abs(r["mu"] - mu_o).max()
     assert np.all(np.abs(r["var"] - var_o) <= tol * amp ** 2), np.abs(r["var"] - var_o).max()
@@ -175,6 +194,35 @@ def test_update_acq_small_and_unfused_shapes(api, O):
         assert np.all(np.abs(r["acq"] - acq_o) <= 1e-9) and r["argmax"] == int(np.argmax(r["acq"]))
         cand.close()
         g.close()
+
+
+@pytest.mark.parametrize("d,M", [(5, 4097), (33, 257)])
+def test_update_acq_unfused_at_rider_sized_n(api, O, d, M):
+    """Eleven block columns, but one candidate more than the rider takes, or one dimension more: the two phases one after the other,
+    the same numbers, and an ordinary fitted posterior afterwards.
+    Observed: d = 5, M = 4097 |Δlogpdf| 3.9e-12, max|Δacq| 5.2e-14 (tol 1.6e-7); d = 33, M = 257 0, 1.4e-16 (tol 1e-9)."""
+    N = 1408
+    X, y, Xs = make(d, N, M, seed=N + M)
+    lam = np.linspace(0.3, 0.7, d)
+    amp, sig = 1.2, 0.05
+    best = float(y.max())
+    post = O.gp_fit(X, y, "matern52", lam, amp, sig)
+    mu_o, _ = O.gp_mean_and_var(post, Xs, clip=False)
+    acq_o = O.ei_acquisition([post], Xs, [1.0], None, best)
+    tol = tol_for(O, post, N)
+    g = api.GP(X, y, "matern52")
+    cand = api.Candidates(Xs)
+    r = g.update_acq(lam, amp, sig, cand, best=best, want_acq=True)
+    assert not r["fused"]
+    print(f"d={d} M={M}: |Δlogpdf| = {abs(r['logpdf'] - post.logpdf):.3e}, max|Δacq| = {np.abs(r['acq'] - acq_o).max():.3e} (tol {tol:.3e})")
+    assert abs(r["logpdf"] - post.logpdf) <= tol * (1 + abs(post.logpdf))
+    assert np.all(np.abs(r["acq"] - acq_o) <= tol), np.abs(r["acq"] - acq_o).max()
+    assert r["acq"][r["argmax"]] == r["acq"].max() == r["max"] and r["argmax"] == int(np.argmax(r["acq"]))
+    assert abs(acq_o[r["argmax"]] - acq_o.max()) <= 2 * tol
+    mu3, _ = g.predict(Xs)
+    assert np.all(np.abs(mu3 - mu_o) <= tol * (1 + np.abs(mu_o)))
+    cand.close()
+    g.close()
 
 
 def test_update_acq_falls_back_with_the_chain():
