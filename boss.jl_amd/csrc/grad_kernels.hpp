@@ -248,10 +248,13 @@ __global__ __launch_bounds__(GU::NTHREADS) void few_back_update_kernel(const dou
 }
 
 // ∇μ, ∇σ² from the W slabs:  with q_i = α² h(r_i),
-//     ∇μ_m  = ∇m_m + (u*_m Σ_i a_i q_i − Σ_i a_i q_i u_i,m) / λ_m ,   ∇σ²_m = −2 (u*_m Σ_i w_i q_i − Σ_i w_i q_i u_i,m) / λ_m
-// (u = x ⊘ λ).  One workgroup per 32-candidate slab: lanes run along the candidates, 8 row subsets;
-// the rows' coordinates and a_i are staged through LDS 64 rows at a time (broadcast reads), the W
-// loads of a chunk are issued together.  Dimensions are handled 16 at a time (registers).
+//     ∇μ_m  = ∇m_m + Σ_i a_i q_i (u*_m − u_i,m) / λ_m ,   ∇σ²_m = −2 Σ_i w_i q_i (u*_m − u_i,m) / λ_m
+// (u = x ⊘ λ).  The differences are summed, not u*_m Σ_i a_i q_i − Σ_i a_i q_i u_i,m: the two halves of that form are
+// |u*| / |u* − u_i| times the result each, and at λ = 0.01·√d (|u| ≈ 50) the ∇σ² of a candidate on a training point, 0 in exact
+// arithmetic, came out 1.5 bars wide (tests/test_gpu_regimes.py, case b-matern32-l0.01-a1.2-s0.001).
+// One workgroup per 32-candidate slab: lanes run along the candidates, 8 row subsets; the rows' coordinates and a_i are staged
+// through LDS 64 rows at a time (broadcast reads), the W loads of a chunk are issued together.  Dimensions are handled 16 at a
+// time (registers).
 constexpr int GRAD_MAX_D = 16;
 constexpr int GRAD_CHUNK = 64;
 __device__ __forceinline__ void grad_accum_body(const double* __restrict__ W, const double* __restrict__ avec,
@@ -273,9 +276,12 @@ __device__ __forceinline__ void grad_accum_body(const double* __restrict__ W, co
     const int j = bx * BN + c;
     for (int m0 = 0; m0 < d; m0 += GRAD_MAX_D) {            // d > 16: passes of 16 dimensions
         const int dm = (d - m0 < GRAD_MAX_D) ? (d - m0) : GRAD_MAX_D;
-        double S1 = 0.0, S2 = 0.0, T1[GRAD_MAX_D], T2[GRAD_MAX_D];
+        double T1[GRAD_MAX_D], T2[GRAD_MAX_D], uc[GRAD_MAX_D];     // Σ a_i q_i (u* − u_i), Σ w_i q_i (u* − u_i), u* of this pass
 #pragma unroll
-        for (int m = 0; m < GRAD_MAX_D; ++m) T1[m] = T2[m] = 0.0;
+        for (int m = 0; m < GRAD_MAX_D; ++m) {
+            T1[m] = T2[m] = 0.0;
+            uc[m] = (m < dm) ? Csc[(size_t)(m0 + m) * Mp + j] : 0.0;
+        }
         const int nchunk = (N + GRAD_CHUNK - 1) / GRAD_CHUNK;
         const int cpb = (nchunk + ny - 1) / ny;
         const int rbeg = by * cpb * GRAD_CHUNK;
@@ -302,12 +308,10 @@ __device__ __forceinline__ void grad_accum_body(const double* __restrict__ W, co
                 }
                 const double q = amp2 * kappa_prime_over_r_r2(kern, r2);
                 const double qa = q * as[rr], qw = q * w[k];
-                S1 += qa;
-                S2 += qw;
 #pragma unroll
                 for (int m = 0; m < GRAD_MAX_D; ++m)
                     if (m < dm) {
-                        const double x = xs[(m0 + m) * GRAD_CHUNK + rr];
+                        const double x = uc[m] - xs[(m0 + m) * GRAD_CHUNK + rr];
                         T1[m] = __builtin_fma(qa, x, T1[m]);
                         T2[m] = __builtin_fma(qw, x, T2[m]);
                     }
@@ -315,8 +319,8 @@ __device__ __forceinline__ void grad_accum_body(const double* __restrict__ W, co
         }
         __syncthreads();
         double* rd = red + (size_t)rs * (2 * (GRAD_MAX_D + 1)) * BN;
-        rd[0 * BN + c] = S1;
-        rd[1 * BN + c] = S2;
+        rd[0 * BN + c] = 0.0;                                 // (slots 0, 1 of the layout are not used)
+        rd[1 * BN + c] = 0.0;
 #pragma unroll
         for (int m = 0; m < GRAD_MAX_D; ++m) {
             rd[(2 + 2 * m) * BN + c] = T1[m];
@@ -334,12 +338,6 @@ __device__ __forceinline__ void grad_accum_body(const double* __restrict__ W, co
             return;
         }
         if (rs == 0 && j < M) {
-            double s1 = 0.0, s2 = 0.0;
-            for (int k = 0; k < 8; ++k) {
-                const double* rk = red + (size_t)k * (2 * (GRAD_MAX_D + 1)) * BN;
-                s1 += rk[c];
-                s2 += rk[BN + c];
-            }
             for (int m = 0; m < dm; ++m) {
                 double t1 = 0.0, t2 = 0.0;
                 for (int k = 0; k < 8; ++k) {
@@ -348,10 +346,10 @@ __device__ __forceinline__ void grad_accum_body(const double* __restrict__ W, co
                     t2 += rk[(3 + 2 * m) * BN + c];
                 }
                 const int mm = m0 + m;
-                const double u = Csc[(size_t)mm * Mp + j], il = invlam[mm];
+                const double il = invlam[mm];
                 const bool disc = discrete && discrete[mm];
-                const double g1 = disc ? 0.0 : (u * s1 - t1) * il;
-                const double g2 = disc ? 0.0 : -2.0 * (u * s2 - t2) * il;
+                const double g1 = disc ? 0.0 : t1 * il;
+                const double g2 = disc ? 0.0 : -2.0 * t2 * il;
                 dmu[(size_t)j * d + mm] = g1 + (mean_grad ? mean_grad[(size_t)j * d + mm] : 0.0);
                 dvar[(size_t)j * d + mm] = g2;
             }
@@ -1493,21 +1491,16 @@ __device__ __forceinline__ void grad_finalize_body(const double* __restrict__ pt
     constexpr int BN = 32, NS = 2 * (GRAD_MAX_D + 1);
     const int c = threadIdx.x, j = blockIdx.x * BN + c;
     if (j >= M) return;
-    double s1 = 0.0, s2 = 0.0;
-    for (int y = 0; y < rsplit; ++y) {
-        s1 += pt[((size_t)y * NS + 0) * BN + c];
-        s2 += pt[((size_t)y * NS + 1) * BN + c];
-    }
     for (int m = 0; m < d; ++m) {
         double t1 = 0.0, t2 = 0.0;
         for (int y = 0; y < rsplit; ++y) {
             t1 += pt[((size_t)y * NS + 2 + 2 * m) * BN + c];
             t2 += pt[((size_t)y * NS + 3 + 2 * m) * BN + c];
         }
-        const double u = Csc[(size_t)m * Mp + j], il = invlam[m];
+        const double il = invlam[m];
         const bool disc = discrete && discrete[m];
-        const double g1 = disc ? 0.0 : (u * s1 - t1) * il;
-        const double g2 = disc ? 0.0 : -2.0 * (u * s2 - t2) * il;
+        const double g1 = disc ? 0.0 : t1 * il;
+        const double g2 = disc ? 0.0 : -2.0 * t2 * il;
         dmu[(size_t)j * d + m] = g1 + (mean_grad ? mean_grad[(size_t)j * d + m] : 0.0);
         dvar[(size_t)j * d + m] = g2;
     }

@@ -1228,18 +1228,13 @@ __global__ __launch_bounds__(SPG_THREADS) void small_predict_grad_kernel(const d
         // gradient sums over the rows
         const double ah0 = as[lane] * hv[lane], ah1 = as[lane + 64] * hv[lane + 64];
         const double wh0 = w0 * hv[lane], wh1 = w1 * hv[lane + 64];
-        double s1 = ah0 + ah1, s2 = wh0 + wh1;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            s1 += __shfl_xor(s1, off);
-            s2 += __shfl_xor(s2, off);
-        }
         if (lane == 0) {
             mu[j] = (mean_s ? mean_s[j] : 0.0) + sm;
             var[j] = amp2 - sv;
         }
         for (int m = 0; m < d; ++m) {
-            const double x0 = xs[m * SMALL_MAX_N + lane], x1 = xs[m * SMALL_MAX_N + lane + 64];
+            // the differences u*_m − u_i,m are summed (not u*_m Σ − Σ u_i,m, which cancels |u*| / |u* − u_i| of its digits: grad_accum_body)
+            const double x0 = us[m] - xs[m * SMALL_MAX_N + lane], x1 = us[m] - xs[m * SMALL_MAX_N + lane + 64];
             double t1 = ah0 * x0 + ah1 * x1, t2 = wh0 * x0 + wh1 * x1;
 #pragma unroll
             for (int off = 32; off > 0; off >>= 1) {
@@ -1247,10 +1242,10 @@ __global__ __launch_bounds__(SPG_THREADS) void small_predict_grad_kernel(const d
                 t2 += __shfl_xor(t2, off);
             }
             if (lane == 0) {
-                const double u = us[m], il = invlam[m];
+                const double il = invlam[m];
                 const bool disc = discrete && discrete[m];
-                dmu[(size_t)j * d + m] = (disc ? 0.0 : (u * s1 - t1) * il) + (mean_grad ? mean_grad[(size_t)j * d + m] : 0.0);
-                dvar[(size_t)j * d + m] = disc ? 0.0 : -2.0 * (u * s2 - t2) * il;
+                dmu[(size_t)j * d + m] = (disc ? 0.0 : t1 * il) + (mean_grad ? mean_grad[(size_t)j * d + m] : 0.0);
+                dvar[(size_t)j * d + m] = disc ? 0.0 : -2.0 * t2 * il;
             }
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // us / kv are rewritten for the next candidate

@@ -3,6 +3,10 @@
 Independent of numpy/LAPACK rounding: used to pin the fp64 oracle (and, through it, the HIP path)
 for small N.  Formulas: src/models/gradient_gp.jl:323-361,403 (explicit Cholesky algebra) and
 src/models/gaussian_process.jl:216-248 (the +1e-8 parameter offsets, α²·κ(r/λ), σ²I noise).
+
+`posterior` is the plain posterior of tests/golden/make_golden.py.  `plain_truth`, `grad_obs_truth` and `gibbs_truth` (second half
+of the file) are the truths of tests/golden/make_regimes.py: candidate gradients, likelihood gradients, the gradient-observation
+model and the Gibbs model, differentiated numerically at high precision.
 """
 from __future__ import annotations
 
@@ -68,3 +72,277 @@ def posterior(X, y, kernel, lengthscale, amplitude, noise_std, Xs, mean_X=None, 
         mus.append(float(mu))
         vars_.append(float(var))
     return float(logpdf), mus, vars_
+
+
+# ------------------------------------------------------------------------------------------------
+# Truths for tests/golden/make_regimes.py.  Everything below is written from the models' defining
+# formulas (Rasmussen & Williams 2006, eqs. 2.25-2.30 and 5.9 for the posterior and the marginal
+# likelihood; Solak et al. 2003 for derivative observations; Gibbs 1997 / Paciorek & Schervish 2004
+# for the nonstationary kernel) and differentiates NUMERICALLY at high precision (mp.diff, or a
+# central difference of the whole likelihood) instead of restating the analytic κ', h, g, q profiles
+# of gp_oracle.py: the two files share the kernels' definitions and nothing else.
+# ------------------------------------------------------------------------------------------------
+_OFF = "1e-8"
+
+
+def _mpv(v):
+    return [mp.mpf(float(t)) for t in v]
+
+
+def _cols(X):
+    d, N = len(X), len(X[0])
+    return [[mp.mpf(float(X[k][j])) for k in range(d)] for j in range(N)]
+
+
+def _fsub(L, b):
+    """L z = b, L lower triangular (N² operations; mp.lu_solve would factor L again)."""
+    n = len(b)
+    z = [mp.mpf(0)] * n
+    for i in range(n):
+        s = b[i]
+        for k in range(i):
+            s -= L[i, k] * z[k]
+        z[i] = s / L[i, i]
+    return z
+
+
+def _bsub(L, z):
+    """Lᵀ a = z."""
+    n = len(z)
+    a = [mp.mpf(0)] * n
+    for i in range(n - 1, -1, -1):
+        s = z[i]
+        for k in range(i + 1, n):
+            s -= L[k, i] * a[k]
+        a[i] = s / L[i, i]
+    return a
+
+
+def _dot(a, b):
+    return mp.fsum(x * y for x, y in zip(a, b))
+
+
+def _logpdf_of(K, delta):
+    """log N(delta; 0, K) and the pieces predictions reuse: (logpdf, L, a = K⁻¹delta).  Raises ZeroDivisionError/ValueError
+    where K is not positive definite (mp.cholesky)."""
+    n = len(delta)
+    L = mp.cholesky(K)
+    z = _fsub(L, delta)
+    a = _bsub(L, z)
+    logdet = 2 * mp.fsum(mp.log(L[i, i]) for i in range(n))
+    return -(n * mp.log(2 * mp.pi) + logdet + _dot(z, z)) / 2, L, a
+
+
+def _cdiff(f, theta, i, h):
+    """Central difference of the scalar f along parameter i.  With dps digits, step h and conditioning c the result keeps about
+    min(2·|log10 h|, dps − |log10 h| − log10 c) digits: callers choose dps and h so that both exceed 30."""
+    tp, tm = list(theta), list(theta)
+    tp[i] = theta[i] + h
+    tm[i] = theta[i] - h
+    return (f(tp) - f(tm)) / (2 * h)
+
+
+def _plain_gram(kernel, cols, lam, amp, sig):
+    n = len(cols)
+    K = mp.matrix(n, n)
+    for i in range(n):
+        for j in range(i):
+            K[i, j] = K[j, i] = _k(kernel, cols[i], cols[j], lam, amp)
+        K[i, i] = amp * amp + sig * sig
+    return K
+
+
+def plain_truth(X, y, kernel, lengthscale, amplitude, noise_std, Xs, mean_X=None, mean_s=None, dps: int = 50,
+                want_llgrad: bool = True, lift: str = _OFF):
+    """Everything the plain model's tests compare: dict of python floats / nested lists rounded from `dps`-digit arithmetic.
+        logpdf, mu[M], var[M] (with the 1e-18 jitter, unclipped), dmu[d][M], dvar[d][M]  (∂/∂x*, mp.diff of μ(x*) and σ²(x*) as wholes),
+        llgrad[d+2] = ∂logpdf/∂(λ_1..λ_d, α, σ) AS GIVEN, i.e. through the +1e-8 lift (central difference of the whole likelihood at
+        dps + 30 digits, h = 1e-25: ≥ 40 digits kept up to cond 1e15)."""
+    mp.mp.dps = dps
+    d, N, M = len(X), len(X[0]), len(Xs[0])
+    off = mp.mpf(lift)
+    cols, scol = _cols(X), _cols(Xs)
+    delta = [mp.mpf(float(y[j])) - (mp.mpf(float(mean_X[j])) if mean_X is not None else 0) for j in range(N)]
+
+    def ll(theta):
+        lam = [t + off for t in theta[:d]]
+        return _logpdf_of(_plain_gram(kernel, cols, lam, theta[d] + off, theta[d + 1] + off), delta)[0]
+
+    theta = _mpv(lengthscale) + [mp.mpf(float(amplitude)), mp.mpf(float(noise_std))]
+    lam, amp, sig = [t + off for t in theta[:d]], theta[d] + off, theta[d + 1] + off
+    logpdf, L, a = _logpdf_of(_plain_gram(kernel, cols, lam, amp, sig), delta)
+    out = {"logpdf": float(logpdf), "mu": [], "var": [], "dmu": [[0.0] * M for _ in range(d)], "dvar": [[0.0] * M for _ in range(d)]}
+
+    def mu_at(xs):
+        return _dot([_k(kernel, cols[i], xs, lam, amp) for i in range(N)], a)
+
+    def var_at(xs):
+        v = _fsub(L, [_k(kernel, cols[i], xs, lam, amp) for i in range(N)])
+        return amp * amp - _dot(v, v) + mp.mpf("1e-18")
+
+    for j in range(M):
+        xs = scol[j]
+        out["mu"].append(float(mu_at(xs) + (mp.mpf(float(mean_s[j])) if mean_s is not None else 0)))
+        out["var"].append(float(var_at(xs)))
+        for m in range(d):
+            along = lambda f: (lambda t: f(xs[:m] + [t] + xs[m + 1:]))          # noqa: E731
+            out["dmu"][m][j] = float(mp.diff(along(mu_at), xs[m]))
+            out["dvar"][m][j] = float(mp.diff(along(var_at), xs[m]))
+    if want_llgrad:
+        mp.mp.dps = dps + 30
+        h = mp.mpf("1e-25")
+        out["llgrad"] = [float(_cdiff(ll, theta, i, h)) for i in range(d + 2)]
+        mp.mp.dps = dps
+    return out
+
+
+# ---- gradient-observation model (Solak et al. 2003): cov(f(x), ∂f(x')/∂x'_l) = ∂k/∂x'_l, cov(∂f/∂x_l, ∂f/∂x'_m) = ∂²k/∂x_l∂x'_m ----
+def _aug_gram(kernel, cols, lam, amp, sig, sgd):
+    """The n(1+d) square matrix over [f(x_1..n), ∂f/∂x_1(x_1..n), …, ∂f/∂x_d(x_1..n)] with σ² on the value rows' diagonal and σ_∂² on the
+    derivative rows'.  Every derivative block is a mixed partial of the scalar kernel by mp.diff with a multi-index over
+    (x_1..x_d, x'_1..x'_d).  The training points must be pairwise distinct (Matérn-3/2 has no second derivative at r = 0, and the
+    model's x_j + 1e-8 rule for near-coincident pairs is pinned elsewhere); a point against itself follows that rule, below."""
+    n, d = len(cols), len(cols[0])
+    Na = n * (1 + d)
+    K = mp.matrix(Na, Na)
+
+    def kk(*z):
+        return _k(kernel, list(z[:d]), list(z[d:]), lam, amp)
+
+    def idx(l, m):                  # multi-index: first derivative along x_l (l >= 0) and along x'_m (m >= 0)
+        o = [0] * (2 * d)
+        if l >= 0:
+            o[l] += 1
+        if m >= 0:
+            o[d + m] += 1
+        return tuple(o)
+
+    # A point against itself: the model (gradient_gp.jl:143-159) takes the value at the point and every derivative block at
+    # (x_i, x_i + 1e-8), the shifted point as fp64 forms it, and factorises the upper triangle mirrored.  The pair is then a pair of
+    # distinct points like any other; only the value block and the mirroring differ.
+    for i in range(n):
+        K[i, i] = amp * amp + sig * sig
+        z = tuple(cols[i]) + tuple(mp.mpf(float(t) + 1e-8) for t in cols[i])
+        for l in range(d):
+            K[i, n + l * n + i] = K[n + l * n + i, i] = mp.diff(kk, z, idx(-1, l))
+            for m in range(l + 1):
+                K[n + l * n + i, n + m * n + i] = K[n + m * n + i, n + l * n + i] = mp.diff(kk, z, idx(l, m))
+            K[n + l * n + i, n + l * n + i] += sgd * sgd
+    for i in range(n):
+        for j in range(i):
+            z = tuple(cols[i]) + tuple(cols[j])
+            K[i, j] = K[j, i] = kk(*z)
+            for l in range(d):
+                v = mp.diff(kk, z, idx(-1, l))                  # cov(f(x_i), ∂f(x_j)/∂x_l)
+                K[i, n + l * n + j] = K[n + l * n + j, i] = v
+                K[j, n + l * n + i] = K[n + l * n + i, j] = -v  # k depends on x − x' only
+                for m in range(l + 1):
+                    w = mp.diff(kk, z, idx(l, m))               # cov(∂f(x_i)/∂x_l, ∂f(x_j)/∂x_m), symmetric in (l, m) and in (i, j)
+                    for (p, q) in ((l, m), (m, l)):
+                        K[n + p * n + i, n + q * n + j] = K[n + q * n + j, n + p * n + i] = w
+                        K[n + p * n + j, n + q * n + i] = K[n + q * n + i, n + p * n + j] = w
+    return K
+
+
+def grad_obs_truth(X, y, dY, kernel, lengthscale, amplitude, noise_std, grad_noise_std, Xs, dps: int = 50,
+                   want_llgrad: bool = True, lift: str = _OFF):
+    """The gradient-observation model: logpdf of [y; dY rows], value μ[M] and var[M] (= α² − k*ᵀK⁻¹k*, no jitter, unclipped) at the
+    candidates, llgrad[d+3] w.r.t. (λ, α, σ, σ_∂) as given (central difference of the whole likelihood, dps + 30 digits)."""
+    mp.mp.dps = dps
+    d, n, M = len(X), len(X[0]), len(Xs[0])
+    off = mp.mpf(lift)
+    cols, scol = _cols(X), _cols(Xs)
+    yt = _mpv(y) + [mp.mpf(float(dY[l][j])) for l in range(d) for j in range(n)]
+
+    def unpack(theta):
+        return [t + off for t in theta[:d]], theta[d] + off, theta[d + 1] + off, theta[d + 2] + off
+
+    def ll(theta):
+        return _logpdf_of(_aug_gram(kernel, cols, *unpack(theta)), yt)[0]
+
+    theta = _mpv(lengthscale) + [mp.mpf(float(amplitude)), mp.mpf(float(noise_std)), mp.mpf(float(grad_noise_std))]
+    lam, amp, sig, sgd = unpack(theta)
+    logpdf, L, a = _logpdf_of(_aug_gram(kernel, cols, lam, amp, sig, sgd), yt)
+    out = {"logpdf": float(logpdf), "mu": [], "var": []}
+    for c in range(M):
+        xs = scol[c]
+        ks = [_k(kernel, xs, cols[j], lam, amp) for j in range(n)]
+        for l in range(d):
+            for j in range(n):
+                xj = cols[j]
+                ks.append(mp.diff(lambda t: _k(kernel, xs, xj[:l] + [t] + xj[l + 1:], lam, amp), xj[l]))
+        v = _fsub(L, ks)
+        out["mu"].append(float(_dot(ks, a)))
+        out["var"].append(float(amp * amp - _dot(v, v)))
+    if want_llgrad:
+        mp.mp.dps = dps + 30
+        h = mp.mpf("1e-25")
+        out["llgrad"] = [float(_cdiff(ll, theta, i, h)) for i in range(d + 3)]
+        mp.mp.dps = dps
+    return out
+
+
+# ---- Gibbs / Paciorek-Schervish nonstationary kernel with per-point λ, α, σ ----
+def _gibbs_factor(la, lb, dx):
+    s = la * la + lb * lb
+    return mp.sqrt(2 * la * lb / s) * mp.e ** (-dx * dx / s)
+
+
+def _gibbs_k(xa, la, aa, xb, lb, ab):
+    """((α(x)+α(y))/2)² Π_i sqrt(2 λ_i(x) λ_i(y) / (λ_i(x)² + λ_i(y)²)) exp(−(x_i − y_i)² / (λ_i(x)² + λ_i(y)²))."""
+    k = ((aa + ab) / 2) ** 2
+    for i in range(len(xa)):
+        k *= _gibbs_factor(la[i], lb[i], xa[i] - xb[i])
+    return k
+
+
+def gibbs_truth(X, y, lam_X, amp_X, noise_X, Xs, lam_Xs, amp_Xs, mean_X=None, mean_s=None, dps: int = 50, want_llgrad: bool = True):
+    """The nonstationary model with the latent values given at every point: logpdf, μ[M], var[M] (= α(x*)² − k*ᵀK⁻¹k* + 1e-18,
+    unclipped) and, from ∂ℓ/∂θ = ½ tr((a aᵀ − K⁻¹) ∂K/∂θ) (R&W eq. 5.9) with ∂K_ij/∂λ_l(x_i) by mp.diff of the one factor that holds
+    it, dlam[d][N], damp[N], dnoise[N], dmean[N].  Raises where K is not positive definite."""
+    mp.mp.dps = dps
+    d, N, M = len(X), len(X[0]), len(Xs[0])
+    cols, scol = _cols(X), _cols(Xs)
+    lam, lams = _cols(lam_X), _cols(lam_Xs)
+    amp, amps, noi = _mpv(amp_X), _mpv(amp_Xs), _mpv(noise_X)
+    delta = [mp.mpf(float(y[j])) - (mp.mpf(float(mean_X[j])) if mean_X is not None else 0) for j in range(N)]
+    K = mp.matrix(N, N)
+    for i in range(N):
+        for j in range(i):
+            K[i, j] = K[j, i] = _gibbs_k(cols[i], lam[i], amp[i], cols[j], lam[j], amp[j])
+        K[i, i] = amp[i] * amp[i] + noi[i] * noi[i]
+    logpdf, L, a = _logpdf_of(K, delta)
+    out = {"logpdf": float(logpdf), "mu": [], "var": []}
+    for c in range(M):
+        ks = [_gibbs_k(cols[i], lam[i], amp[i], scol[c], lams[c], amps[c]) for i in range(N)]
+        v = _fsub(L, ks)
+        out["mu"].append(float(_dot(ks, a) + (mp.mpf(float(mean_s[c])) if mean_s is not None else 0)))
+        out["var"].append(float(amps[c] * amps[c] - _dot(v, v) + mp.mpf("1e-18")))
+    if want_llgrad:
+        Kinv = []                                                # rows of K⁻¹ (symmetric)
+        for i in range(N):
+            e = [mp.mpf(0)] * N
+            e[i] = mp.mpf(1)
+            z = _fsub(L, e)                                      # zero up to i: the generic solve, kept simple
+            Kinv.append(_bsub(L, z))
+        dlam = [[0.0] * N for _ in range(d)]
+        damp, dnoise = [0.0] * N, [0.0] * N
+        for i in range(N):
+            G = [a[i] * a[j] - Kinv[i][j] for j in range(N)]
+            sa = G[i] * amp[i]                                   # ½ G_ii ∂(α_i²)/∂α_i
+            sl = [mp.mpf(0)] * d
+            for j in range(N):
+                if j == i:
+                    continue
+                sa += G[j] * K[i, j] * 2 / (amp[i] + amp[j])     # G_ij ∂K_ij/∂α_i = G_ij K_ij · 2/(α_i+α_j)  (each pair counted twice in the trace)
+                for l in range(d):
+                    dx, lb = cols[i][l] - cols[j][l], lam[j][l]
+                    f = _gibbs_factor(lam[i][l], lb, dx)
+                    df = mp.diff(lambda t: _gibbs_factor(t, lb, dx), lam[i][l])
+                    sl[l] += G[j] * K[i, j] * df / f
+            for l in range(d):
+                dlam[l][i] = float(sl[l])
+            damp[i] = float(sa)
+            dnoise[i] = float(noi[i] * G[i])
+        out.update(dlam=dlam, damp=damp, dnoise=dnoise, dmean=[float(t) for t in a])
+    return out

@@ -3,6 +3,7 @@ HipNonstationaryModel, HipNonstationaryMAP) against the host reference chain and
 
 Shapes (N, d, S) = (37, 1, 3), (129, 2, 3), (200, 3, 3), (260, 2, 2): one past a 128 block / two 64-row tiles of the products; a
 gradient step padded to 256; three lengthscale latents sharing a factor; two 256-row steps and a product whose K loop crosses tiles.
+(129, 2, 3) once more with a prior mean at the data and one discrete dimension.
 
 Bars, with u = 2⁻⁵³ and tol = max(1e-9, cond(K)·N·u·8) (the project's bar for the nonstationary likelihood and its cotangents):
  1. values:     |Δv_j| <= |v′_j|·8·N·u·(|L||θ| + |μ|)_j + 8u|v_j|      (the dot-product bound through the transform's derivative)
@@ -55,7 +56,7 @@ def B(api):
 
 
 def handle(api, c):
-    return api.NgpWhitened(c.X, c.y, c.factors, c.factor_of, c.specs, c.mu)
+    return api.NgpWhitened(c.X, c.y, c.factors, c.factor_of, c.specs, c.mu, mean_X=c.mean_X, discrete=c.discrete)
 
 
 _cache = {}
@@ -66,14 +67,15 @@ def reference(B, key):
     cotangents, cond(K)."""
     if key in _cache:
         return _cache[key]
-    N, d, S, scalar = key
-    c = H.family(N, d, S, scalar=scalar)
+    N, d, S, scalar = key[:4]
+    c = H.family(N, d, S, scalar=scalar, **dict(key[4:]))          # (further entries: (name, value) pairs of the family's options)
     r = H.Case()
     r.v, r.dv, r.bnd, r.ll, r.g, r.cot, r.cond = [], [], [], [], [], [], []
     for s in range(S):
         v, dv, _, bnd = H.ref_values(B, c, c.theta[:, s])
         ll, g, cot, _ = H.ref_chain(B, c, c.theta[:, s])
-        K = H.O.gibbs_kernel_matrix(c.X, v[:d], v[d], c.X, v[:d], v[d]) + np.diag(v[d + 1] ** 2)
+        Xr = H.O.discrete_round(c.X, c.discrete)
+        K = H.O.gibbs_kernel_matrix(Xr, v[:d], v[d], Xr, v[:d], v[d]) + np.diag(v[d + 1] ** 2)
         r.v.append(v), r.dv.append(dv), r.bnd.append(bnd), r.ll.append(ll), r.g.append(g), r.cot.append(cot), r.cond.append(np.linalg.cond(K))
     _cache[key] = (c, r)
     return c, r
@@ -91,9 +93,9 @@ def check_all_bars(api, B, key):
         h.close()
     assert not stv.any() and not st.any() and g0 is None
     # 2. the array twin
-    ll_t, st_t = api.ngp_loglike_batch(c.X, c.y, lam, amp, noi)
+    ll_t, st_t = api.ngp_loglike_batch(c.X, c.y, lam, amp, noi, mean_X=c.mean_X, discrete=c.discrete)
     assert np.array_equal(ll, ll_t) and np.array_equal(st, st_t) and np.array_equal(ll0, ll_t) and np.array_equal(st0, st_t)
-    res = api.ngp_loglike_grad_batch(c.X, c.y, lam, amp, noi)
+    res = api.ngp_loglike_grad_batch(c.X, c.y, lam, amp, noi, mean_X=c.mean_X, discrete=c.discrete)
     assert np.array_equal(res[0], ll)
     for s in range(S):
         v_dev = np.vstack([lam[:, :, s], amp[None, :, s], noi[None, :, s]])
@@ -143,6 +145,25 @@ def test_scalar_latents(api, B):
     lam, amp, noi, _ = h.values(c.theta)
     h.close()
     assert (lam[1] == 0.4).all() and (noi == 0.1).all()            # taken as given, at every point
+
+
+def test_prior_mean_and_discrete_dimension(api, B):
+    """NgpWhitened(mean_X=…, discrete=…) at (129, 2, 3): a prior mean at the data and the second dimension rounded inside the kernel
+    (five levels), through every bar of the module docstring; the reference chain carries both (tests/test_nfit_host.py), and the
+    likelihood is neither that of the handle without the mean nor that of the handle without the rounding."""
+    key = (129, 2, 3, (), ("mean", True), ("discrete", (False, True)))
+    c, g = check_all_bars(api, B, key)
+    assert c.mean_X is not None and c.discrete.tolist() == [False, True] and np.isfinite(g).all()
+    _, r = reference(B, key)
+    for drop in ("mean_X", "discrete"):
+        kw = dict(mean_X=c.mean_X, discrete=c.discrete)
+        kw[drop] = None
+        h = api.NgpWhitened(c.X, c.y, c.factors, c.factor_of, c.specs, c.mu, **kw)
+        try:
+            ll, st, _ = h.loglike_grad(c.theta, want_grad=False)
+        finally:
+            h.close()
+        assert not st.any() and (np.abs(ll - np.array(r.ll)) > 1e-3).all(), (drop, ll, r.ll)
 
 
 # ------------------------------------------------------------------------------------------ 6. position independence, determinism

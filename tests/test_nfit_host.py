@@ -38,9 +38,11 @@ class Case:
     pass
 
 
-def family(N, d, S, seed=0, scalar=(), scalar_values=None):
+def family(N, d, S, seed=0, scalar=(), scalar_values=None, mean=False, discrete=None):
     """The family of the module docstring.  scalar: latent indices q that are scalar latents (their value: scalar_values[q],
-    default 0.4 for a lengthscale, 1.0 amplitude, 0.1 noise)."""
+    default 0.4 for a lengthscale, 1.0 amplitude, 0.1 noise).  mean: the prior mean m(x) = 0.3 + 0.2 Σx at the data (c.mean_X, else
+    None).  discrete: per-dimension flags (c.discrete, else None); the flagged coordinates are stretched to [0, 4] so that the
+    kernel's rounding yields five levels (y, the factors and theta are those of the unstretched family: the same random stream)."""
     rng = np.random.default_rng(1000 + 17 * N + d + seed)
     c = Case()
     c.N, c.d, c.S = N, d, S
@@ -51,6 +53,12 @@ def family(N, d, S, seed=0, scalar=(), scalar_values=None):
     c.factors = [np.asfortranarray(np.tril(L)) for L in c.factors]
     c.specs = [("lognormal", (math.log(0.3), 0.3), "identity", 0.0) if l % 2 == 0 else ("uniform", (0.15, 0.6), "identity", 0.0)
                for l in range(d)] + [("normal", (0.5, 0.4), "softplus", 0.2), ("none", (0.0, 0.0), "exp", 0.0)]
+    c.mean_X, c.discrete = None, None
+    if discrete is not None:
+        c.discrete = np.asarray(discrete, dtype=bool)
+        c.X = np.asfortranarray(np.where(c.discrete[:, None], 4.0 * c.X, c.X))
+    if mean:
+        c.mean_X = 0.3 + 0.2 * c.X.sum(0)
     c.factor_of = [0] * d + [1, 1]
     c.mu = np.zeros((N, d + 2), order="F")
     c.mu[:, d + 1] = -1.5
@@ -103,14 +111,14 @@ def pull_back(c, cot, dv):
 def ref_chain(B, c, th):
     """(ℓ, g [T], cotangents [d+2, N], v′) of one column of theta through the oracle."""
     v, dv, _, _ = ref_values(B, c, th)
-    ll, dlam, damp, dnoise, _ = O.nonstationary_loglike_grad(c.X, c.y, v[:c.d], v[c.d], v[c.d + 1])
+    ll, dlam, damp, dnoise, _ = O.nonstationary_loglike_grad(c.X, c.y, v[:c.d], v[c.d], v[c.d + 1], mean=c.mean_X, discrete=c.discrete)
     cot = np.vstack([dlam, damp[None], dnoise[None]])
     return ll, pull_back(c, cot, dv), cot, dv
 
 
 def ref_loglike(B, c, th):
     v = ref_values(B, c, th)[0]
-    return O.nonstationary_fit(c.X, c.y, v[:c.d], v[c.d], v[c.d + 1]).logpdf
+    return O.nonstationary_fit(c.X, c.y, v[:c.d], v[c.d], v[c.d + 1], mean=c.mean_X, discrete=c.discrete).logpdf
 
 
 # ------------------------------------------------------------------------------------------ tests
@@ -130,6 +138,24 @@ def test_reference_chain_agrees_with_central_differences(B, N, d):
     for u in dirs:
         fd = (ref_loglike(B, c, th + h * u) - ref_loglike(B, c, th - h * u)) / (2 * h)
         assert abs(fd - g @ u) <= 1e-6 * max(1.0, np.abs(g).max()), (fd, g @ u)
+
+
+def test_reference_chain_with_prior_mean_and_discrete_dimension(B):
+    """The family member tests/test_gpu_nfit.py passes to NgpWhitened(mean_X=…, discrete=…): the chain through the oracle's prior mean
+    and rounding against central differences, by the bar of the test above; and both arguments change the likelihood."""
+    c = family(37, 2, 1, mean=True, discrete=(False, True))
+    assert c.mean_X.shape == (37,) and c.X[1].max() > 1.0 and len(np.unique(np.rint(c.X[1]))) == 5
+    th = c.theta[:, 0]
+    ll, g, _, _ = ref_chain(B, c, th)
+    rng = np.random.default_rng(6)
+    h = 1e-5
+    for u in [np.eye(c.T)[k] for k in rng.choice(c.T, 12, replace=False)] + [g / np.linalg.norm(g)]:
+        fd = (ref_loglike(B, c, th + h * u) - ref_loglike(B, c, th - h * u)) / (2 * h)
+        assert abs(fd - g @ u) <= 1e-6 * max(1.0, np.abs(g).max()), (fd, g @ u)
+    for change in (dict(mean_X=None), dict(discrete=None)):
+        c2 = family(37, 2, 1, mean=True, discrete=(False, True))
+        vars(c2).update(change)
+        assert abs(ref_loglike(B, c2, th) - ll) > 1e-3
 
 
 def test_reference_chain_scalar_latents(B):
