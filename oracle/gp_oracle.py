@@ -426,7 +426,9 @@ def expected_improvement_lin_grad(fit_coefs, mu, var, dmu, dvar, best_yet: float
     dvf = np.einsum("p,pdm->dm", c * c, dvar)
     with np.errstate(divide="ignore", invalid="ignore"):
         dsf = np.where(sf > 0, dvf / (2.0 * sf), 0.0)
-    dei = normcdf(z) * dmuf + normpdf(z) * dsf
+        dei = normcdf(z) * dmuf + normpdf(z) * dsf
+    # diff == 0 and σf == 0: the reference returns the constant 0 (:96), whose derivative is 0 (z = 0/0 above)
+    dei = np.where((muf - best_yet == 0.0) & (sf == 0.0), 0.0, dei)
     return ei, dei
 
 

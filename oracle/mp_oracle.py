@@ -6,7 +6,8 @@ src/models/gaussian_process.jl:216-248 (the +1e-8 parameter offsets, α²·κ(r/
 
 `posterior` is the plain posterior of tests/golden/make_golden.py.  `plain_truth`, `grad_obs_truth` and `gibbs_truth` (second half
 of the file) are the truths of tests/golden/make_regimes.py: candidate gradients, likelihood gradients, the gradient-observation
-model and the Gibbs model, differentiated numerically at high precision.
+model and the Gibbs model, differentiated numerically at high precision.  `acq_truth` (end of the file) is the truth of
+tests/golden/make_acq_tails.py: the EI × feasibility acquisition of one candidate and its gradient, with the condition sums of the bars.
 """
 from __future__ import annotations
 
@@ -345,4 +346,128 @@ def gibbs_truth(X, y, lam_X, amp_X, noise_X, Xs, lam_Xs, amp_Xs, mean_X=None, me
             damp[i] = float(sa)
             dnoise[i] = float(noi[i] * G[i])
         out.update(dlam=dlam, damp=damp, dnoise=dnoise, dmean=[float(t) for t in a])
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
+# Truth of the acquisition epilogue for tests/golden/make_acq_tails.py: construct_ei's four variants
+# (expected_improvement.jl:68-101,113-114) of ONE candidate and ONE hyper-parameter sample, from fp64 moments taken as exact.
+# ------------------------------------------------------------------------------------------------
+def _ncdf(z):
+    """Φ(z) = erfc(−z/√2)/2: relative accuracy in both tails (mp.erfc), ±Inf included."""
+    if mp.isinf(z):
+        return mp.mpf(1) if z > 0 else mp.mpf(0)
+    return mp.erfc(-z / mp.sqrt(2)) / 2
+
+
+def _npdf(z):
+    if mp.isinf(z):
+        return mp.mpf(0)
+    return mp.e ** (-z * z / 2) / mp.sqrt(2 * mp.pi)
+
+
+def acq_truth(mu, var, coefs, y_max, best, dmu=None, dvar=None, dps: int = 50):
+    """mu[P], var[P]: one candidate's moments; coefs[P] and best (None: no incumbent, expected_improvement.jl:68-73); y_max[P] or None
+    (`constraints === nothing`; +Inf: the Infinity singleton, factor 1).  dmu / dvar: [P][d] moment gradients, or None.
+    The variance is clipped as the device clips it: [−1e-8, 0) → 0; below −1e-8 the value is −Inf and the gradient 0.
+    Returns python floats rounded from `dps`-digit arithmetic:
+        value, cond                      the acquisition and its first-order condition sum (the bar of a result is C·u·cond):
+                                         EI  (1+z²)(|T1|+|T2|) + P·Φ(z)(Σ|c_p μ_p| + |b|),  T1 = (μf − b)Φ(z), T2 = σf φ(z)
+                                         FP  FP·Σ_p (1+t_p²)   (finite t_p only: a factor that is exactly 0 or 1 has no rounding)
+                                         EI·FP  cond_EI·FP + |EI|·cond_FP
+        grad[d], gcond[d]                the chain rule of ei_grad_point's comment and, term by term, the same construction: the sum
+                                         of the absolute addends of Φ∇μf + φ∇σf times (1+z²)·P, of ∇FP times Σ_p(1+t_p²)·P, and the
+                                         product rule over (EI, cond_EI, ∇EI, gcond_EI) × (FP, …)
+        z, T1, T2, ei, fp, t[P]          the pieces (t_p: NaN for an output without a finite constraint)."""
+    mp.mp.dps = dps
+    P = len(mu)
+    has_best, constrained = best is not None, y_max is not None
+    d = 0 if dmu is None else len(dmu[0])
+    out = {"value": 0.0, "cond": 0.0, "grad": [0.0] * d, "gcond": [0.0] * d, "z": float("nan"), "T1": 0.0, "T2": 0.0, "ei": float("nan"),
+           "fp": float("nan"), "t": [float("nan")] * P}
+    if not has_best and not constrained:
+        return out
+    m = _mpv(mu)
+    v, live = [], []
+    for p in range(P):
+        x = float(var[p])
+        if x < -1e-8:
+            out["value"] = float("-inf")
+            return out
+        live.append(x > 0.0)
+        v.append(mp.mpf(max(x, 0.0)))
+    gm = [[mp.mpf(float(t)) for t in dmu[p]] for p in range(P)] if d else None
+    gv = [[mp.mpf(float(t)) if live[p] else mp.mpf(0) for t in dvar[p]] for p in range(P)] if d else None
+    zero = mp.mpf(0)
+    ei, c_ei, dei, gc_ei = mp.mpf(1), zero, [zero] * d, [zero] * d
+    if has_best:
+        c = _mpv(coefs)
+        b = mp.mpf(float(best))
+        muf = mp.fsum(c[p] * m[p] for p in range(P))
+        sf = mp.sqrt(mp.fsum(c[p] * c[p] * v[p] for p in range(P)))
+        diff = muf - b
+        if sf == 0:
+            z = zero if diff == 0 else (mp.inf if diff > 0 else -mp.inf)
+            Phi, phi = (zero if diff == 0 else _ncdf(z)), zero
+            T1, T2, zz = (diff if diff > 0 else zero), zero, zero
+        else:
+            z = diff / sf
+            Phi, phi = _ncdf(z), _npdf(z)
+            T1, T2, zz = diff * Phi, sf * phi, z * z
+        ei = T1 + T2
+        c_ei = (1 + zz) * (abs(T1) + abs(T2)) + P * Phi * (mp.fsum(abs(c[p] * m[p]) for p in range(P)) + abs(b))
+        for k in range(d):
+            a1 = mp.fsum(c[p] * gm[p][k] for p in range(P))
+            a2 = mp.fsum(c[p] * c[p] * gv[p][k] for p in range(P)) / (2 * sf) if sf != 0 else zero
+            s1 = mp.fsum(abs(c[p] * gm[p][k]) for p in range(P))
+            s2 = mp.fsum(abs(c[p] * c[p] * gv[p][k]) for p in range(P)) / (2 * sf) if sf != 0 else zero
+            dei[k] = Phi * a1 + phi * a2
+            gc_ei[k] = (1 + zz) * P * (Phi * s1 + phi * s2)
+        out.update(z=float(z), T1=float(T1), T2=float(T2), ei=float(ei))
+    fp, c_fp, dfp, gc_fp = mp.mpf(1), zero, [zero] * d, [zero] * d
+    if constrained:
+        ym = [mp.mpf(float(t)) for t in y_max]
+        Phis, ts, tsum = [], [], zero
+        for p in range(P):
+            if mp.isinf(ym[p]) and ym[p] > 0:
+                Phis.append(None)
+                ts.append(None)
+                continue
+            s = mp.sqrt(v[p])
+            if s == 0:
+                t = mp.inf if ym[p] >= m[p] else -mp.inf
+            else:
+                t = (ym[p] - m[p]) / s
+            Phis.append(_ncdf(t))
+            ts.append(t)
+            if not mp.isinf(t):
+                tsum += 1 + t * t
+                out["t"][p] = float(t)
+        for q in Phis:
+            if q is not None:
+                fp *= q
+        c_fp = fp * tsum
+        for k in range(d):
+            for p in range(P):
+                if Phis[p] is None or not live[p] or mp.isinf(ts[p]):
+                    continue
+                others = mp.mpf(1)
+                for q in range(P):
+                    if q != p and Phis[q] is not None:
+                        others *= Phis[q]
+                s = mp.sqrt(v[p])
+                b1, b2 = -gm[p][k] / s, -(ym[p] - m[p]) * gv[p][k] / (2 * s * v[p])
+                w = others * _npdf(ts[p])
+                dfp[k] += w * (b1 + b2)
+                gc_fp[k] += tsum * P * w * (abs(b1) + abs(b2))
+        out["fp"] = float(fp)
+    if has_best and constrained:
+        val, cond = ei * fp, c_ei * fp + abs(ei) * c_fp
+        grad = [dei[k] * fp + ei * dfp[k] for k in range(d)]
+        gcond = [gc_ei[k] * fp + abs(dei[k]) * c_fp + c_ei * abs(dfp[k]) + abs(ei) * gc_fp[k] for k in range(d)]
+    elif has_best:
+        val, cond, grad, gcond = ei, c_ei, dei, gc_ei
+    else:
+        val, cond, grad, gcond = fp, c_fp, dfp, gc_fp
+    out.update(value=float(val), cond=float(cond), grad=[float(t) for t in grad], gcond=[float(t) for t in gcond])
     return out
