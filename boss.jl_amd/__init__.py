@@ -14,6 +14,8 @@ from .problem import (BossOptions, BossProblem, Dirac, Domain, ExperimentData, E
                       LinFitness, LogNormal, MvDirac, MvLogNormal, NonlinFitness, Normal)
 from .fitness import DeviceFitness  # noqa: F401,E402
 from .api import FitnessProgram, acq_ei_mc, acq_ei_mc_grad, acq_ei_mc_grad_moments, acq_ei_mc_moments  # noqa: F401,E402
+from .mean import DeviceMean, trace_mean  # noqa: F401,E402
+from .api import MeanProgram  # noqa: F401,E402
 from .model import HipGaussianProcess, HipGPParams, average_mean  # noqa: F401,E402
 from .gradient_gp import (GradientData, HipGradientGaussianProcess, HipGradientGPParams,  # noqa: F401,E402
                           gradient_sequential_batch, join_gradient_slices)

@@ -142,6 +142,11 @@ SIGNATURES = {
                                       _c_dp, C.c_int, C.c_double, _c_ucp, _c_dp, _c_dp]),
     "boss_acq_ei_mc_grad_moments": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _c_dp, _c_dp, _c_dp, _c_dp, C.c_void_p, C.c_int,
                                               _c_dp, _c_dp, C.c_int, C.c_double, _c_ucp, _c_dp, _c_dp]),
+    "boss_mean_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), _c_dp, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                   C.POINTER(C.c_int), C.POINTER(C.c_void_p)]),
+    "boss_mean_free": (None, [C.c_void_p]),
+    "boss_mean_eval_host": (C.c_int, [C.c_void_p, C.c_int, _c_dp, C.c_int, _c_dp, C.c_int, _c_dp, _c_dp, _c_dp]),
+    "boss_mean_eval": (C.c_int, [C.c_int, C.c_void_p, C.c_int, _c_dp, C.c_int, _c_dp, C.c_int, _c_dp, _c_dp, _c_dp]),
     "boss_acq_ei_tracks": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_void_p), _c_dp, _c_dp, C.c_int, C.c_double, _c_ucp,
                                      _c_dp, C.POINTER(C.c_long), _c_dp]),
     "boss_init": (C.c_int, [C.POINTER(C.c_int)]),
@@ -1737,6 +1742,18 @@ class FitnessProgram:
         _check(load_library().boss_fit_create(self.P, self.consts.shape[0], _dp(self.consts), self.code.shape[0],
                                               self.code.ctypes.data_as(C.POINTER(C.c_int)), self.out_id, C.byref(self._h)))
 
+    @classmethod
+    def _interpreter(cls, P: int, consts, code, out_id: int) -> "FitnessProgram":
+        """The numpy interpreter (eval / grad) of a program without a library handle: one output of a MeanProgram, whose d + T
+        inputs may exceed what boss_fit_create takes (the MeanProgram's own handle validates it)."""
+        self = cls.__new__(cls)
+        self.P = int(P)
+        self.consts = np.ascontiguousarray(np.asarray(consts, dtype=np.float64).reshape(-1))
+        self.code = np.ascontiguousarray(np.asarray(code, dtype=np.intc).reshape(-1, 3))
+        self.out_id = int(out_id)
+        self._h = C.c_void_p()
+        return self
+
     def _inputs(self, Y):
         Y = np.asarray(Y, dtype=np.float64)
         one = Y.ndim == 1
@@ -1942,6 +1959,107 @@ def acq_ei_mc_grad_moments(mu, var, dmu, dvar, fit: FitnessProgram, eps, y_max=N
                                                       _dp(eps), _dp(ym), 0 if best is None else 1, 0.0 if best is None else float(best),
                                                       _ucp(mask), _dp(acq), _dp(dacq)))
     return acq, dacq
+
+
+# ---------------------------------------------------------------- mean programs: the parametric mean and its Jacobians on the device
+MEAN_MAX_INPUTS, MEAN_MAX_CONSTS, MEAN_MAX_INSTR, MEAN_MAX_OUTPUTS = 32, 32, 64, 16
+MEAN_SAMPLE_MAJOR, MEAN_OUTPUT_MAJOR = 0, 1                          # the `layout` of boss_mean_eval
+
+
+class MeanProgram:
+    """The mean (x, θ) -> length-P vector as P straight-line programs over the shared inputs x (d) and θ (T) (boss_mean_t).
+    outputs: per output (consts, code, out_id) as FitnessProgram takes them, with value ids 0..d-1 = x, d..d+T-1 = θ.
+    Creating one needs no device.  eval / jac are numpy interpreters (FitnessProgram.eval / grad per output), eval_host runs the
+    library's interpreter on the host, eval_device the kernel (boss_mean_eval): all points, outputs and θ sets in one call.
+
+    Shapes returned by eval_host / eval_device, with B = (S, P) for layout 0 (sample-major) and (P, S) for layout 1:
+    m B×n, jac_theta B×n×T, jac_x B×d×n — views of the blocks the C ABI fills (jac_theta[b] is n×T column-major, jac_x[b] d×n
+    column-major)."""
+
+    def __init__(self, d: int, T: int, outputs):
+        self.d, self.T, self.P = int(d), int(T), len(outputs)
+        self.outputs = [FitnessProgram._interpreter(self.d + self.T, c, k, o) for c, k, o in outputs]
+        nc = np.array([q.consts.shape[0] for q in self.outputs], dtype=np.intc)
+        ni = np.array([q.code.shape[0] for q in self.outputs], dtype=np.intc)
+        consts = np.ascontiguousarray(np.concatenate([q.consts for q in self.outputs] + [np.zeros(0)]))
+        code = np.ascontiguousarray(np.concatenate([q.code.reshape(-1) for q in self.outputs] + [np.zeros(0, dtype=np.intc)]).astype(np.intc))
+        outs = np.array([q.out_id for q in self.outputs], dtype=np.intc)
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+        self._h = C.c_void_p()
+        _check(load_library().boss_mean_create(self.d, self.T, self.P, ip(nc), _dp(consts), ip(ni), ip(code), ip(outs), C.byref(self._h)))
+
+    def _args(self, X, thetas):
+        X = np.asfortranarray(X, dtype=np.float64)
+        if X.ndim == 1:
+            X = np.asfortranarray(X[:, None])
+        if X.ndim != 2 or X.shape[0] != self.d:
+            raise ValueError(f"X must be {self.d}×n")
+        if self.T == 0:
+            if thetas is not None and np.size(thetas):
+                raise ValueError("this mean program takes no parameters (T = 0)")
+            return X, None, 1
+        th = np.asarray(thetas, dtype=np.float64)
+        if th.ndim == 1:
+            th = th[:, None]
+        if th.ndim != 2 or th.shape[0] != self.T:
+            raise ValueError(f"thetas must be {self.T}×S (one parameter set per column)")
+        return X, np.asfortranarray(th), th.shape[1]
+
+    def _Y(self, X, th, s):
+        n = X.shape[1]
+        return X if th is None else np.vstack([X, np.repeat(th[:, s:s + 1], n, axis=1)])
+
+    def eval(self, X, thetas=None):
+        """m[S, P, n] by the numpy interpreter."""
+        X, th, S = self._args(X, thetas)
+        return np.stack([np.stack([np.asarray(q.eval(self._Y(X, th, s)), float).reshape(-1) for q in self.outputs]) for s in range(S)])
+
+    def jac(self, X, thetas=None):
+        """(∂m/∂θ [S, P, n, T], ∂m/∂x [S, P, d, n]) by the numpy reverse sweep."""
+        X, th, S = self._args(X, thetas)
+        G = np.stack([np.stack([q.grad(self._Y(X, th, s)).reshape(self.d + self.T, -1) for q in self.outputs]) for s in range(S)])
+        return np.ascontiguousarray(G[:, :, self.d:, :].transpose(0, 1, 3, 2)), np.ascontiguousarray(G[:, :, :self.d, :])
+
+    def _run(self, fn, head, X, thetas, layout, jac_theta, jac_x):
+        X, th, S = self._args(X, thetas)
+        if layout not in (MEAN_SAMPLE_MAJOR, MEAN_OUTPUT_MAJOR):
+            raise BossError(BOSS_E_INVALID, "layout must be 0 (sample-major) or 1 (output-major)")
+        if jac_theta and self.T == 0:
+            raise BossError(BOSS_E_INVALID, "jac_theta asked of a mean program without parameters (T = 0)")
+        n, P, d, T = X.shape[1], self.P, self.d, self.T
+        B = (S, P) if layout == MEAN_SAMPLE_MAJOR else (P, S)
+        m = np.zeros(B + (n,))
+        jt = np.zeros(B + (T, n)) if jac_theta else None
+        jx = np.zeros(B + (n, d)) if jac_x else None
+        _check(fn(*head, self._h, n, _dp(X), S, _dp(th), layout, _dp(m), _dp(jt), _dp(jx)))
+        return m, (None if jt is None else jt.transpose(0, 1, 3, 2)), (None if jx is None else jx.transpose(0, 1, 3, 2))
+
+    def eval_host(self, X, thetas=None, layout: int = 0, jac_theta: bool = False, jac_x: bool = False):
+        """(m, jac_theta or None, jac_x or None) through boss_mean_eval_host."""
+        return self._run(load_library().boss_mean_eval_host, (), X, thetas, layout, jac_theta, jac_x)
+
+    def eval_device(self, X, thetas=None, layout: int = 0, jac_theta: bool = False, jac_x: bool = False, device: int = 0):
+        """(m, jac_theta or None, jac_x or None) in one device call (boss_mean_eval)."""
+        return self._run(load_library().boss_mean_eval, (device,), X, thetas, layout, jac_theta, jac_x)
+
+    def workgroup(self, n: int, grad: bool):
+        """(waves per workgroup, dynamic LDS bytes) boss_mean_eval launches for n points (introspection for the tests)."""
+        lib = load_library()
+        lib.boss_debug_mean_block.restype = C.c_int
+        lib.boss_debug_mean_block.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int)]
+        lds = C.c_int(0)
+        return lib.boss_debug_mean_block(self._h, 1 if grad else 0, int(n), C.byref(lds)), lds.value
+
+    def close(self):
+        if self._h:
+            load_library().boss_mean_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 # ---------------------------------------------------------------- several GPUs from one process (boss_multi_*)

@@ -27,6 +27,7 @@
 #include "latent_kernels.hpp"
 #include "nfit_kernels.hpp"
 #include "fitness.hpp"
+#include "mean_program.hpp"
 
 using namespace boss;
 
@@ -130,7 +131,7 @@ struct Ctx {
     bool prof_on = false;
     std::map<std::string, std::vector<std::pair<hipEvent_t, hipEvent_t>>> prof;
     std::vector<hipEvent_t> ev_pool;
-    Workspace vscratch, csc, pred, acq, batchA, batchX, batchMisc, craw, lgA, lgB, lgC, few, setdesc, setmom, gsetdesc, nlatjobs, mceps;
+    Workspace vscratch, csc, pred, acq, batchA, batchX, batchMisc, craw, lgA, lgB, lgC, few, setdesc, setmom, gsetdesc, nlatjobs, mceps, meanws;
     // batched likelihood gradients: the gradient passes of consecutive sets rotate over LLG_BANKS streams, each with its
     // own bank of workspaces (bank 0 = the main stream and lgA/lgB/lgC)
     static constexpr int LLG_BANKS = 4;
@@ -386,6 +387,7 @@ static int ctx_init(Ctx* c) {
     HIPCHK(hipFuncSetAttribute((const void*)predict_kernel<PredG64, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                PredictLds<PredG64>::BYTES));
     HIPCHK(hipFuncSetAttribute((const void*)ei_mc_grad_set_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, MC_GRAD_MAX_LDS));
+    HIPCHK(hipFuncSetAttribute((const void*)mean_eval_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, MEAN_MAX_LDS));
     return BOSS_OK;
 }
 
@@ -673,6 +675,7 @@ static void mc_grad_launch(hipStream_t s, const double* mu, const double* var, c
 #include "host_predict.inc"
 #include "host_acq.inc"
 #include "host_fitness.inc"
+#include "host_mean.inc"
 #include "host_rider.inc"
 #include "host_track.inc"
 #include "host_multi.inc"

@@ -7,26 +7,26 @@ struct boss_fit {
 // ------------------------------------------------------------------------------------------
 // the handle: validation only, no device
 // ------------------------------------------------------------------------------------------
-extern "C" int boss_fit_create(int P, int n_const, const double* consts, int n_instr, const int* code, int out_id, boss_fit_t** out) {
-    if (!out) return fail(BOSS_E_INVALID, "out is NULL");
-    *out = nullptr;
-    if (P < 1 || P > EI_MAXP) return fail(BOSS_E_INVALID, "a fitness program takes 1 to 16 inputs");
-    if (n_const < 0 || n_const > FIT_MAXC) return fail(BOSS_E_INVALID, "a fitness program holds at most 32 constants");
-    if (n_instr < 0 || n_instr > FIT_MAXI) return fail(BOSS_E_INVALID, "a fitness program holds at most 64 instructions");
-    if ((n_const > 0 && !consts) || (n_instr > 0 && !code)) return fail(BOSS_E_INVALID, "NULL constants or code");
+// The checks of a program over n_in inputs, shared with boss_mean_create (host_mean.inc): `pre` is put in front of every message
+// (a mean program names its output there), `what` names the kind of program.
+static int fit_build(int n_in, int n_const, const double* consts, int n_instr, const int* code, int out_id, const std::string& pre,
+                     const char* what, FitProg* out) {
+    if (n_const < 0 || n_const > FIT_MAXC) return fail(BOSS_E_INVALID, pre + "a " + what + " program holds at most 32 constants");
+    if (n_instr < 0 || n_instr > FIT_MAXI) return fail(BOSS_E_INVALID, pre + "a " + what + " program holds at most 64 instructions");
+    if ((n_const > 0 && !consts) || (n_instr > 0 && !code)) return fail(BOSS_E_INVALID, pre + "NULL constants or code");
     FitProg g;
     std::memset(&g, 0, sizeof g);
-    g.P = P;
+    g.P = n_in;
     g.nC = n_const;
     g.nI = n_instr;
     for (int k = 0; k < n_const; ++k) {
-        if (!std::isfinite(consts[k])) return fail(BOSS_E_INVALID, "constant " + std::to_string(k) + " of the fitness program is not finite");
+        if (!std::isfinite(consts[k])) return fail(BOSS_E_INVALID, pre + "constant " + std::to_string(k) + " of the " + what + " program is not finite");
         g.c[k] = consts[k];
     }
-    const int base = P + n_const;
+    const int base = n_in + n_const;
     for (int i = 0; i < n_instr; ++i) {
         const int op = code[3 * i], a = code[3 * i + 1], b = code[3 * i + 2];
-        const std::string at = "instruction " + std::to_string(i) + ": ";
+        const std::string at = pre + "instruction " + std::to_string(i) + ": ";
         if (op < 0 || op >= FIT_NOPS) return fail(BOSS_E_INVALID, at + "unknown opcode " + std::to_string(op));
         if (a < 0 || a >= base + i) return fail(BOSS_E_INVALID, at + "operand a must be an earlier value id");
         if (fit_is_unary(op)) {
@@ -38,8 +38,19 @@ extern "C" int boss_fit_create(int P, int n_const, const double* consts, int n_i
         g.a[i] = (unsigned char)a;
         g.b[i] = (unsigned char)(b < 0 ? FIT_NOARG : b);
     }
-    if (out_id < 0 || out_id >= base + n_instr) return fail(BOSS_E_INVALID, "out_id is not a value id of the program");
+    if (out_id < 0 || out_id >= base + n_instr) return fail(BOSS_E_INVALID, pre + "out_id is not a value id of the program");
     g.out = out_id;
+    *out = g;
+    return BOSS_OK;
+}
+
+extern "C" int boss_fit_create(int P, int n_const, const double* consts, int n_instr, const int* code, int out_id, boss_fit_t** out) {
+    if (!out) return fail(BOSS_E_INVALID, "out is NULL");
+    *out = nullptr;
+    if (P < 1 || P > EI_MAXP) return fail(BOSS_E_INVALID, "a fitness program takes 1 to 16 inputs");
+    FitProg g;
+    int rc = fit_build(P, n_const, consts, n_instr, code, out_id, "", "fitness", &g);
+    if (rc) return rc;
     boss_fit* f = new boss_fit();
     f->g = g;
     *out = f;

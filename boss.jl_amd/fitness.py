@@ -24,8 +24,9 @@ _UFUNC_OPS = {np.add: "ADD", np.subtract: "SUB", np.multiply: "MUL", np.true_div
 
 
 class _Tracer:
-    def __init__(self, P: int):
+    def __init__(self, P: int, label: str = "DeviceFitness", noun: str = "fitness"):
         self.P = P
+        self.label, self.noun = label, noun   # who speaks in the error messages (DeviceMean traces with the same classes, mean.py)
         self.consts = []                 # values, in id order
         self.const_id = {}               # bit pattern -> value id
         self.code = []                   # (op, a, b)
@@ -34,7 +35,7 @@ class _Tracer:
     def const(self, c) -> "_Sym":
         c = float(c)
         if not np.isfinite(c):
-            raise ValueError("DeviceFitness: the closure uses a constant that is not finite")
+            raise ValueError(f"{self.label}: the closure uses a constant that is not finite")
         key = np.float64(c).tobytes()
         if key not in self.const_id:
             self.const_id[key] = len(self.consts)
@@ -46,7 +47,7 @@ class _Tracer:
             return x
         if isinstance(x, (numbers.Real, np.floating, np.integer)) or (isinstance(x, np.ndarray) and x.ndim == 0):
             return self.const(x)
-        raise ValueError(f"DeviceFitness: cannot trace an operand of type {type(x).__name__}")
+        raise ValueError(f"{self.label}: cannot trace an operand of type {type(x).__name__}")
 
     def emit(self, op: str, a, b=None) -> "_Sym":
         a = self.sym(a)
@@ -59,9 +60,9 @@ class _Tracer:
     def program(self, out: "_Sym") -> api.FitnessProgram:
         nc = len(self.consts)
         if nc > api.FIT_MAX_CONSTS:
-            raise ValueError(f"DeviceFitness: the closure needs {nc} constants, a fitness program holds at most {api.FIT_MAX_CONSTS}")
+            raise ValueError(f"{self.label}: the closure needs {nc} constants, a {self.noun} program holds at most {api.FIT_MAX_CONSTS}")
         if len(self.code) > api.FIT_MAX_INSTR:
-            raise ValueError(f"DeviceFitness: the closure traces into {len(self.code)} instructions, a fitness program holds at most "
+            raise ValueError(f"{self.label}: the closure traces into {len(self.code)} instructions, a {self.noun} program holds at most "
                              f"{api.FIT_MAX_INSTR}")
 
         def vid(ref):
@@ -71,9 +72,28 @@ class _Tracer:
         return api.FitnessProgram(self.P, self.consts, np.asarray(code, dtype=np.intc).reshape(-1, 3), vid(out.ref))
 
 
+def _label_of(*xs) -> str:
+    """The label of the tracer behind the first traced operand ("DeviceFitness" where there is none to ask)."""
+    for x in xs:
+        if isinstance(x, _Sym):
+            return x.tr.label
+        if isinstance(x, _SymVec) and x.items:
+            return x.items[0].tr.label
+    return "DeviceFitness"
+
+
+def _noun_of(*xs) -> str:
+    for x in xs:
+        if isinstance(x, _Sym):
+            return x.tr.noun
+        if isinstance(x, _SymVec) and x.items:
+            return x.items[0].tr.noun
+    return "fitness"
+
+
 def _no_value(what):
     def raiser(self, *a, **k):
-        raise ValueError(f"DeviceFitness: the closure {what}: its result would depend on the value of an input, which a traced "
+        raise ValueError(f"{_label_of(self)}: the closure {what}: its result would depend on the value of an input, which a traced "
                          "program cannot express (data-dependent control flow, math.* functions and float() are not traceable; "
                          "use the numpy functions and np.minimum / np.maximum)")
     return raiser
@@ -139,14 +159,16 @@ class _SymVec:
         return acc
 
     def dot(self, w):
+        if isinstance(w, _SymVec):                           # two traced vectors (θ[1:] @ x of a mean closure)
+            return (self * w).sum()
         w = np.asarray(w, dtype=np.float64)
         if w.shape[0] != len(self.items):
-            raise ValueError("DeviceFitness: y @ w with a weight array of another length")
+            raise ValueError(f"{_label_of(self)}: y @ w with a weight array of another length")
         if w.ndim == 1:
             return _SymVec([x * float(c) for x, c in zip(self.items, w)]).sum()
         if w.ndim == 2:
             return _SymVec([_SymVec([x * float(c) for x, c in zip(self.items, w[:, k])]).sum() for k in range(w.shape[1])])
-        raise ValueError("DeviceFitness: y @ w takes a vector or a matrix of weights")
+        raise ValueError(f"{_label_of(self)}: y @ w takes a vector or a matrix of weights")
 
     def __matmul__(self, w): return self.dot(w)
     def __rmatmul__(self, w): return _SymVec(self.items).dot(np.asarray(w, dtype=np.float64).T)
@@ -179,7 +201,7 @@ class _SymVec:
         if func is np.dot and len(args) == 2 and not kwargs:
             a, b = args
             return a.dot(b) if isinstance(a, _SymVec) else b.__rmatmul__(a)
-        raise ValueError(f"DeviceFitness: np.{getattr(func, '__name__', func)} is not supported in a device fitness")
+        raise ValueError(f"{_label_of(self, *args)}: np.{getattr(func, '__name__', func)} is not supported in a device {_noun_of(self, *args)}")
 
 
 def _tracer_of(*xs):
@@ -207,7 +229,7 @@ def _binary(op, a, b):
     def item(x, k):
         if isinstance(x, _SymVec) or (isinstance(x, (np.ndarray, list, tuple)) and np.ndim(x) == 1):
             if len(x) != n:
-                raise ValueError("DeviceFitness: element-wise operation on vectors of different lengths")
+                raise ValueError(f"{tr.label}: element-wise operation on vectors of different lengths")
             return x[k]
         return x
     return _SymVec([_scalar_binary(tr, op, item(a, k), item(b, k)) for k in range(n)])
@@ -215,8 +237,8 @@ def _binary(op, a, b):
 
 def _apply_ufunc(ufunc, method, inputs, kwargs):
     if method != "__call__" or kwargs or ufunc not in _UFUNC_OPS:
-        raise ValueError(f"DeviceFitness: np.{ufunc.__name__}{'' if method == '__call__' else '.' + method} is not supported in a "
-                         f"device fitness (supported: {', '.join(sorted(u.__name__ for u in _UFUNC_OPS))})")
+        raise ValueError(f"{_label_of(*inputs)}: np.{ufunc.__name__}{'' if method == '__call__' else '.' + method} is not supported in a "
+                         f"device {_noun_of(*inputs)} (supported: {', '.join(sorted(u.__name__ for u in _UFUNC_OPS))})")
     op = _UFUNC_OPS[ufunc]
     if len(inputs) == 2:
         return _binary(op, inputs[0], inputs[1])

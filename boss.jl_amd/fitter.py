@@ -17,6 +17,7 @@ import numpy as np
 
 from . import api
 from . import distributed as dist_util
+from .mean import device_mean_of
 from .model import HipGaussianProcess, HipGPParams
 from .problem import BossOptions, BossProblem, Dirac, MvDirac, Normal
 
@@ -87,11 +88,13 @@ class HipGradientMAP:
         d, P = plist[0].lengthscales.shape
         tot = np.array([prior_ll(p) for p in plist], dtype=float)
         gl, ga, gs = np.zeros((S, d, P)), np.zeros((S, P)), np.zeros((S, P))
+        dev = model.mean_values_all(data.X, None) if device_mean_of(model) is not None else None   # a DeviceMean: all outputs in one call
         for i in range(P):
             lam = np.stack([p.lengthscales[:, i] for p in plist], axis=1)
             amp = np.array([p.amplitudes[i] for p in plist])
             sig = np.array([p.noise_std[i] for p in plist])
-            ll, st, gr = api.loglike_batch(data.X, data.Y[i], model.kernel, lam, amp, sig, model.mean_values(data.X, None, i),
+            ll, st, gr = api.loglike_batch(data.X, data.Y[i], model.kernel, lam, amp, sig,
+                                           model.mean_values(data.X, None, i) if dev is None else np.ascontiguousarray(dev[i]),
                                            model.discrete, model.device, want_grad=True)
             tot += np.where(st == 0, ll, -np.inf)
             gl[:, :, i], ga[:, i], gs[:, i] = gr[:d].T, gr[d], gr[d + 1]

@@ -1362,4 +1362,8 @@ end
 # not bound: boss_acq_ei_mc_moments — Monte-Carlo EI of a fitness program; needs boss_fit_create
 # not bound: boss_acq_ei_mc_grad — Monte-Carlo EI of a fitness program; needs boss_fit_create
 # not bound: boss_acq_ei_mc_grad_moments — Monte-Carlo EI of a fitness program; needs boss_fit_create
+# not bound: boss_mean_create — mean programs: the mean closure is traced by the Python DeviceMean only; a Julia mean or parametric closure keeps the host path of this glue
+# not bound: boss_mean_free — see boss_mean_create
+# not bound: boss_mean_eval_host — see boss_mean_create (the host run of the kernel's interpreter, used by tests)
+# not bound: boss_mean_eval — the traced mean and its Jacobians on the device; needs boss_mean_create
 end # module

@@ -26,6 +26,7 @@ from . import acquisition as acq_host
 from . import api
 from . import distributed as dist_util
 from .fitness import DeviceFitness
+from .mean import device_mean_of
 from .model import HipGaussianProcessPosterior
 from .problem import BossOptions, BossProblem, NonlinFitness, best_so_far, in_bounds, in_cons, in_domain
 
@@ -79,6 +80,19 @@ def moments_acquisition(problem: BossProblem, mu: np.ndarray, var: np.ndarray, X
     return api.acq_ei_moments(mu, var, ei.fitness.coefs, problem.y_max, b, mask, problem.model.device)
 
 
+def _device_mean_model(posts):
+    """The model of the posteriors when its prior mean is a DeviceMean (one boss_mean_eval serves all samples and outputs), else None."""
+    model = getattr(posts[0].slices[0], "model", None)
+    return model if device_mean_of(model) is not None else None
+
+
+def _device_prior_means(posts, Xs, jac_x: bool = False):
+    """(S×P×M prior means, S×P×d×M ∂m/∂x or None) of the posteriors at the columns of Xs from ONE device call, every sample at its
+    own θ."""
+    m, _, jx = _device_mean_model(posts).device_means(Xs, [p.slices[0].params for p in posts], api.MEAN_SAMPLE_MAJOR, jac_x=jac_x)
+    return m, jx
+
+
 def _mc_eps(problem: BossProblem, n_posts: int, eps_seed) -> np.ndarray:
     """The ε-samples of expected_improvement(::NonlinFitness): ϵ_sample_count columns for one posterior, one column per posterior
     sample otherwise (expected_improvement.jl:116-119)."""
@@ -114,7 +128,9 @@ def acquisition_values(problem: BossProblem, posts: Sequence[HipGaussianProcessP
                                          problem.model.device)
         gps = [[s.gp for s in p.slices] for p in posts]
         means = None
-        if posts[0].slices[0]._mean_s(Xs) is not None:
+        if _device_mean_model(posts) is not None:
+            means = _device_prior_means(posts, Xs)[0]
+        elif posts[0].slices[0]._mean_s(Xs) is not None:
             means = np.stack([np.stack([s._mean_s(Xs) for s in p.slices], axis=0) for p in posts], axis=0)   # S×P×M
         try:
             return api.acq_ei_mc(gps, cand, ei.fitness.program, eps, ym, b, mask, means)
@@ -135,8 +151,9 @@ def acquisition_values(problem: BossProblem, posts: Sequence[HipGaussianProcessP
         return acq, am, float(acq[am])
     gps = [[s.gp for s in p.slices] for p in posts]
     means = None
-    m0 = posts[0].slices[0]._mean_s(Xs)
-    if m0 is not None:
+    if _device_mean_model(posts) is not None:
+        means = _device_prior_means(posts, Xs)[0]
+    elif posts[0].slices[0]._mean_s(Xs) is not None:
         means = np.stack([np.stack([s._mean_s(Xs) for s in p.slices], axis=0) for p in posts], axis=0)   # S×P×M
     acq, am, mx = api.acq_ei(gps, cand, ei.fitness.coefs, problem.y_max if constrained else None, b, mask, means)
     if own:
@@ -225,9 +242,14 @@ class HipBatchAM:
         g = api.GP(data.X, data.Y[0], model.kernel, model.discrete, model.device)
         cand = api.Candidates(Xs, model.device)
         try:
+            if device_mean_of(model) is not None:            # the data's and the candidates' means from one device call
+                both = model.mean_values(np.hstack([data.X, Xs]), prm, 0)
+                mX, mXs = np.ascontiguousarray(both[:data.X.shape[1]]), np.ascontiguousarray(both[data.X.shape[1]:])
+            else:
+                mX, mXs = model.mean_values(data.X, prm, 0), model.mean_values(Xs, prm, 0)
             r = g.update_acq(prm.lengthscales[:, 0], prm.amplitudes[0], prm.noise_std[0], cand, fit_coef=float(np.asarray(ei.fitness.coefs)[0]),
-                             y_max=float(np.asarray(problem.y_max, float)[0]), best=b, mean_X=model.mean_values(data.X, prm, 0),
-                             mean_Xs=model.mean_values(Xs, prm, 0), valid_mask=mask, want_acq=want_acq)
+                             y_max=float(np.asarray(problem.y_max, float)[0]), best=b, mean_X=mX,
+                             mean_Xs=mXs, valid_mask=mask, want_acq=want_acq)
         finally:
             cand.close()
             g.close()
@@ -250,7 +272,9 @@ class HipBatchAM:
         b = best_so_far(ei.fitness, problem.data.Y, problem.y_max)
         mask = (in_bounds(Xs, problem.domain.bounds) & in_cons(Xs, problem.domain.cons)) if ei.cons_safe else None
         means = None
-        if problem.model.mean_values(Xs[:, :1], plist[0], 0) is not None:
+        if device_mean_of(problem.model) is not None:
+            means = problem.model.device_means(Xs, plist)[0]                                                            # S×P×M, one device call
+        elif problem.model.mean_values(Xs[:, :1], plist[0], 0) is not None:
             means = np.stack([np.stack([problem.model.mean_values(Xs, prm, i) for i in range(P)]) for prm in plist])   # S×P×M
         slices = []                                                      # everything to close afterwards
         try:
@@ -359,7 +383,10 @@ class HipSequentialBatchAM:
         dev = prob.model.device
         cand = api.Candidates(Xs[:, lo:hi], dev) if hi > lo else None
         tracks = []
-        if cand is not None:
+        if cand is not None and _device_mean_model(posts) is not None:
+            mm = _device_prior_means(posts, Xs[:, lo:hi])[0]
+            tracks = [[api.Track(s.gp, cand, np.ascontiguousarray(mm[k, i])) for i, s in enumerate(p.slices)] for k, p in enumerate(posts)]
+        elif cand is not None:
             tracks = [[api.Track(s.gp, cand, s._mean_s(Xs[:, lo:hi])) for s in p.slices] for p in posts]
         mask = None
         if ei.cons_safe and hi > lo:
@@ -404,7 +431,9 @@ class HipGradientAM:
     ascent with a per-start Barzilai–Borwein step and backtracking.  Discrete dimensions are rounded
     (their gradient is zero), `cons` is honoured through make_safe (acq = 0 outside) and a final
     in-domain filter.  Multi-GPU: the starts are sharded across ranks, 16-byte arg-max exchange.
-    `mean_grad`: optional x -> P×d Jacobian of the GP's prior mean (zero / constant means need none)."""
+    `mean_grad`: optional x -> P×d Jacobian of the GP's prior mean (zero / constant means need none).  A model whose mean is a
+    DeviceMean needs none either: ∂m/∂x comes from the traced program at every iteration, every parameter sample at its own θ, in the
+    device call that gives the mean values; giving `mean_grad` as well raises ValueError."""
     x_prior: Callable = None
     multistart: int = 200
     iters: int = 30
@@ -433,8 +462,20 @@ class HipGradientAM:
         M = X.shape[1]
         eps = self._eps(problem, len(posts)) if mc else None
         mg = None                                            # P×d×M Jacobian of the prior mean: the same for every sample
+        dev = _device_mean_model(posts) is not None
+        if dev and self.mean_grad is not None:
+            raise ValueError("HipGradientAM: the model's mean is a DeviceMean, which gives its own ∂m/∂x; drop mean_grad")
         if self.mean_grad is not None:
             mg = np.stack([np.asarray(self.mean_grad(X[:, j]), float) for j in range(M)], axis=2)
+        if dev:
+            # DeviceMean: S×P×M means and S×P×d×M ∂m/∂x of all samples and outputs at their own θ from one device call
+            dms, dmg = _device_prior_means(posts, X, jac_x=True)
+            gps = [[s.gp for s in post.slices] for post in posts]
+            if mc:
+                return api.acq_ei_mc_grad(gps, X, ei.fitness.program, eps, problem.y_max, b, mask, dms, dmg)
+            if len(posts) > 1:
+                return api.acq_ei_grad_set(gps, X, ei.fitness.coefs, problem.y_max, b, mask, dms, dmg)
+            return api.acq_ei_grad(gps[0], X, ei.fitness.coefs, problem.y_max, b, mask, dms[0], dmg[0])
 
         def means(post):                                     # P×M prior means of one sample, or None when no slice has one
             rows = [s._mean_s(X) for s in post.slices]
@@ -475,6 +516,8 @@ class HipGradientAM:
         return acc / len(posts), gacc / len(posts)
 
     def maximize_acquisition(self, problem: BossProblem, options: BossOptions = BossOptions(), posts=None):
+        if self.mean_grad is not None and device_mean_of(problem.model) is not None:
+            raise ValueError("HipGradientAM: the model's mean is a DeviceMean, which gives its own ∂m/∂x; drop mean_grad")
         rng = np.random.default_rng(dist_util.shared_seed(self.seed, self.group))     # the same starts on every rank
         dom = problem.domain
         starts = [_rand_in_domain(self.x_prior, dom, rng, self.max_attempts) for _ in range(self.multistart)]

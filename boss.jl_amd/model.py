@@ -9,7 +9,9 @@ src/models/semiparametric.jl) over the C ABI:
                                                Jacobian of the parametric mean, ∂/∂θ)
   params_loglike / params_sampler           -> host (prior bookkeeping, out of the GPU's scope)
 The GP's prior mean (a user closure, or the Semiparametric parametric model m(x;θ)) is evaluated
-on the host and crosses the ABI as dense vectors.
+on the host and crosses the ABI as dense vectors — unless it is a DeviceMean (mean.py): then the traced program
+gives the mean, ∂m/∂θ and ∂m/∂x of all points, outputs and parameter sets in one device call (boss_mean_eval) and the closure is
+never called.
 """
 from __future__ import annotations
 
@@ -20,6 +22,7 @@ from typing import Callable, List, Optional, Sequence
 import numpy as np
 
 from . import api
+from .mean import DeviceMean, device_mean_of
 from .problem import ExperimentData
 
 
@@ -55,7 +58,9 @@ class HipGaussianProcess:
     Semiparametric model (semiparametric.jl:79-92).  `parametric_jac`: optional (x, θ) -> P×T matrix ∂parametric(x, θ)/∂θ for
     the likelihood gradient w.r.t. θ (data_loglike_grad_batch; the reference differentiates the closure by AD).  Without it the
     Jacobian is taken by central differences of `parametric` in θ with step 1e-6·max(1, |θ_t|): 2T further evaluations of
-    `parametric` per point; the error is about 2⁻⁵³·|m|/h from rounding plus h²·|∂³m/∂θ³|/6 from truncation."""
+    `parametric` per point; the error is about 2⁻⁵³·|m|/h from rounding plus h²·|∂³m/∂θ³|/6 from truncation.
+    `parametric` (or `mean`, with theta_dim = 0) may be a DeviceMean: values and exact Jacobians then come from its traced program on
+    the device, and `parametric_jac` is ignored."""
     lengthscale_priors: Sequence
     amplitude_priors: Sequence
     noise_std_priors: Sequence
@@ -79,6 +84,32 @@ class HipGaussianProcess:
     def y_dim(self):
         return len(self.amplitude_priors)
 
+    # ------------------------------------------------------------------ prior mean on the device (DeviceMean)
+    def device_means(self, X, plist: Sequence[Optional[HipGPParams]], layout: int = api.MEAN_SAMPLE_MAJOR, jac_theta: bool = False,
+                     jac_x: bool = False):
+        """ONE boss_mean_eval for all outputs at the columns of X and the θ of every parameter set of `plist`:
+        (m, ∂m/∂θ or None, ∂m/∂x or None) with leading axes (S, P) for layout 0 and (P, S) for layout 1 (api.MeanProgram).  A mean
+        without parameters (theta_dim = 0) is evaluated once and repeated along the set axis."""
+        dm = device_mean_of(self)
+        X = np.asarray(X, float)
+        if X.ndim == 1:
+            X = X[:, None]
+        S = len(plist)
+        if dm.theta_dim == 0:
+            out = dm.evaluate(X, None, layout, False, jac_x, self.device)
+            return tuple(None if a is None else np.repeat(a, S, axis=0 if layout == api.MEAN_SAMPLE_MAJOR else 1) for a in out)
+        th = np.stack([np.asarray(p.theta, float).reshape(-1) for p in plist], axis=1)
+        if th.shape[0] != dm.theta_dim:
+            raise ValueError(f"theta has {th.shape[0]} entries, the DeviceMean was traced with theta_dim = {dm.theta_dim}")
+        return dm.evaluate(X, th, layout, jac_theta, jac_x, self.device)
+
+    def mean_values_all(self, X, params: Optional[HipGPParams]):
+        """m_i(x_j) of every output as a P×n array (None without a prior mean): one device call with a DeviceMean."""
+        if device_mean_of(self) is not None:
+            return self.device_means(X, [params])[0][0]
+        rows = [self.mean_values(X, params, i) for i in range(self.y_dim)]
+        return None if rows[0] is None else np.stack(rows)
+
     # ------------------------------------------------------------------ prior mean on the host
     def mean_values(self, X, params: Optional[HipGPParams], i: int):
         """m_i(x_j) for all columns j — mean_getindex (gaussian_process.jl:101-103) / parametric(θ)."""
@@ -86,6 +117,8 @@ class HipGaussianProcess:
         if X.ndim == 1:
             X = X[:, None]
         n = X.shape[1]
+        if device_mean_of(self) is not None:
+            return np.ascontiguousarray(self.device_means(X, [params])[0][0, i])
         if self.parametric is not None:
             th = params.theta
             return np.array([float(np.asarray(self.parametric(X[:, j], th))[i]) for j in range(n)])
@@ -104,6 +137,8 @@ class HipGaussianProcess:
         n = X.shape[1]
         th = np.asarray(params.theta, float).reshape(-1)
         T = th.shape[0]
+        if isinstance(self.parametric, DeviceMean):          # the exact reverse sweep of the traced program (parametric_jac is ignored)
+            return np.ascontiguousarray(self.device_means(X, [params], jac_theta=True)[1][0, i])
         if self.parametric_jac is not None:
             J = np.empty((n, T))
             for j in range(n):
@@ -152,9 +187,10 @@ class HipGaussianProcess:
 
         def ll(p: HipGPParams):
             tot = 0.0
+            means = self.mean_values_all(data.X, p)
             for i, g in enumerate(gps):
                 try:
-                    tot += g.update(p.lengthscales[:, i], p.amplitudes[i], p.noise_std[i], self.mean_values(data.X, p, i))
+                    tot += g.update(p.lengthscales[:, i], p.amplitudes[i], p.noise_std[i], None if means is None else means[i])
                 except api.PosDefException:
                     return -math.inf                    # safe_data_loglike (src/surrogate_model.jl:2-12)
             return tot
@@ -165,12 +201,17 @@ class HipGaussianProcess:
         """`loglike.(samples)` (src/model_fitters/sampling.jl:64,77) in one batched call per output."""
         S = len(samples)
         tot = np.zeros(S)
+        dev = None                                           # DeviceMean: every output's S×N mean rows from one device call
+        if device_mean_of(self) is not None and S:
+            dev = self.device_means(data.X, samples, api.MEAN_OUTPUT_MAJOR)[0]
         for i in range(data.Y.shape[0]):
             lam = np.stack([s.lengthscales[:, i] for s in samples], axis=1)
             amp = np.array([s.amplitudes[i] for s in samples])
             sig = np.array([s.noise_std[i] for s in samples])
             means = None
-            if self.parametric is not None:
+            if dev is not None:
+                means = dev[i]
+            elif self.parametric is not None:
                 means = np.stack([self.mean_values(data.X, s, i) for s in samples], axis=0)
             else:
                 mv = self.mean_values(data.X, None, i)
@@ -193,11 +234,16 @@ class HipGaussianProcess:
         d, P = plist[0].lengthscales.shape
         T = 0 if self.parametric is None else np.asarray(plist[0].theta, float).reshape(-1).shape[0]
         gl, ga, gs, gt = np.zeros((S, d, P)), np.zeros((S, P)), np.zeros((S, P)), np.zeros((S, T))
+        dev = None                                           # DeviceMean: means and θ-Jacobians of all sets and outputs from one device call
+        if device_mean_of(self) is not None:
+            dev = self.device_means(data.X, plist, api.MEAN_OUTPUT_MAJOR, jac_theta=T > 0)
         for i in range(P):
             lam = np.stack([p.lengthscales[:, i] for p in plist], axis=1)
             amp = np.array([p.amplitudes[i] for p in plist])
             sig = np.array([p.noise_std[i] for p in plist])
-            if self.parametric is not None:
+            if dev is not None:
+                means, jac = dev[0][i], (dev[1][i] if T else None)
+            elif self.parametric is not None:
                 means = np.stack([self.mean_values(data.X, p, i) for p in plist], axis=0)
                 jac = np.stack([self.mean_jacobians(data.X, p, i) for p in plist], axis=0) if T else None
             else:
@@ -215,10 +261,11 @@ class HipGaussianProcess:
 
     # ------------------------------------------------------------------ posterior
     def model_posterior_slice(self, params: HipGPParams, data: ExperimentData, i: int,
-                              reserve: int = 0) -> "HipGaussianProcessPosteriorSlice":
-        """model_posterior_slice (gaussian_process.jl:133-141).  reserve: room for later appends."""
+                              reserve: int = 0, mean_X=None) -> "HipGaussianProcessPosteriorSlice":
+        """model_posterior_slice (gaussian_process.jl:133-141).  reserve: room for later appends.  mean_X: the prior mean of output i
+        at data.X where the caller has it already (model_posterior evaluates a DeviceMean once for all outputs)."""
         g = api.fit(data.X, data.Y[i], self.kernel, params.lengthscales[:, i], params.amplitudes[i], params.noise_std[i],
-                    self.mean_values(data.X, params, i), self.discrete, self.device, reserve)
+                    self.mean_values(data.X, params, i) if mean_X is None else mean_X, self.discrete, self.device, reserve)
         return HipGaussianProcessPosteriorSlice(self, params, i, g)
 
     def model_posterior(self, params, data: ExperimentData, reserve: int = 0):
@@ -230,8 +277,11 @@ class HipGaussianProcess:
                 # the reference's cholesky would inside the broadcast (src/posterior.jl:15-19)
                 P, S = data.Y.shape[0], len(params)
                 per_out = []
+                dev = None                                   # DeviceMean: the S×N mean rows of every output from one device call
+                if device_mean_of(self) is not None:
+                    dev = self.device_means(data.X, params, api.MEAN_OUTPUT_MAJOR)[0]
                 for i in range(P):
-                    means = [self.mean_values(data.X, p, i) for p in params]
+                    means = [self.mean_values(data.X, p, i) for p in params] if dev is None else list(dev[i])
                     mX = None if all(m is None for m in means) else np.stack([np.zeros(data.X.shape[1]) if m is None else np.asarray(m, float)
                                                                               for m in means])
                     gps, _, st = api.fit_batch(data.X, data.Y[i], self.kernel, np.stack([p.lengthscales[:, i] for p in params], axis=1),
@@ -251,6 +301,10 @@ class HipGaussianProcess:
                 return [HipGaussianProcessPosterior([HipGaussianProcessPosteriorSlice(self, params[s], i, per_out[i][s]) for i in range(P)])
                         for s in range(S)]
             return [self.model_posterior(p, data, reserve) for p in params]
+        if device_mean_of(self) is not None:                 # one evaluation for all outputs
+            mX = self.mean_values_all(data.X, params)
+            return HipGaussianProcessPosterior([self.model_posterior_slice(params, data, i, reserve, np.ascontiguousarray(mX[i]))
+                                                for i in range(data.Y.shape[0])])
         return HipGaussianProcessPosterior([self.model_posterior_slice(params, data, i, reserve)
                                             for i in range(data.Y.shape[0])])
 

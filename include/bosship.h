@@ -576,6 +576,44 @@ int boss_acq_ei_mc_grad_moments(int device, int P, int S, int M, int d, const do
                                 const double* dvar, const boss_fit_t* fit, int n_eps, const double* eps, const double* y_max,
                                 int has_best, double best, const unsigned char* valid_mask, double* acq_out, double* dacq_out);
 
+/* ---- mean programs: the Semiparametric model's parametric mean on the device, with its Jacobians ------------------------------
+ * Replaces: the per-point calls of the parametric model m(x; θ) (src/models/parametric.jl:31-34,186-207) behind the Semiparametric
+ * mean (src/models/semiparametric.jl:79-92) and of a GaussianProcess mean function (src/models/gaussian_process.jl:101-103), and the
+ * ForwardDiff derivatives of both w.r.t. θ (OptimizationMAP, src/model_fitters/optimization.jl:146-164) and w.r.t. x (OptimizationAM,
+ * src/acquisition_maximizers/optimization.jl:36,100).  A closure cannot cross the C ABI; straight-line programs can.
+ *
+ * boss_mean_t holds P validated programs, one per output, over ONE shared input vector: inputs 0..d-1 are x, inputs d..d+T-1 are θ
+ * (T = 0: a plain mean function of x).  Each program is a fitness program (above) over d + T inputs — the same value ids, opcodes,
+ * values and derivative conventions, the same interpreter — given as
+ *   n_const[P], consts     the constants of output 0, then of output 1, ... (n_const[p] each);
+ *   n_instr[P], code       3 ints per instruction, output after output;
+ *   out_ids[P]             each output's value id;
+ *   limits                 d >= 1, T >= 0, d + T <= 32, 1 <= P <= 16, per output 32 constants and 64 instructions.
+ * boss_mean_create returns BOSS_E_INVALID for everything boss_fit_create refuses, the message naming the output and the instruction.
+ * boss_mean_create / boss_mean_free / boss_mean_eval_host need no device.
+ *
+ * boss_mean_eval evaluates every output at the n columns of X (d×n column-major) for S parameter sets (thetas T×S column-major,
+ * NULL iff T == 0) in ONE kernel launch — one thread per (point, output, set) — and returns on the host
+ *   m          P·S blocks of n values;
+ *   jac_theta  P·S blocks n×T column-major (j + n*t): ∂m/∂θ_t at point j, or NULL;
+ *   jac_x      P·S blocks d×n column-major (k + d*j): ∂m/∂x_k at point j, or NULL
+ * (both NULL: the reverse sweep is skipped).  Block (s, p) sits at
+ *   layout = 0 (sample-major)   p + P*s: m is the mean_Xs S×P×M, jac_x the mean_grad [s][p][d×M] of boss_acq_ei_grad_set;
+ *   layout = 1 (output-major)   s + S*p: one output's blocks are the mean_X S×N (mean_stride = N) and the mean_jac
+ *                               (jac_stride = N*T) of boss_gp_loglike_grad_batch_mean.
+ * NaN and Inf computed by a program are returned as computed.  No atomics: repeated calls agree bit for bit.
+ * boss_mean_eval_host: the same arguments and layouts through the same interpreter functions on the host (tests).
+ * BOSS_E_INVALID: n < 1, S < 1, NULL X or m, NULL thetas with T > 0, jac_theta with T == 0, layout not 0 or 1,
+ * P·S·n·max(1, T, d) above 2^30.  BOSS_E_NO_DEVICE: boss_mean_eval without a GPU. */
+typedef struct boss_mean boss_mean_t;
+int boss_mean_create(int d, int T, int P, const int* n_const, const double* consts, const int* n_instr, const int* code,
+                     const int* out_ids, boss_mean_t** out);
+void boss_mean_free(boss_mean_t* mean);
+int boss_mean_eval_host(const boss_mean_t* mean, int n, const double* X, int S, const double* thetas, int layout, double* m,
+                        double* jac_theta, double* jac_x);
+int boss_mean_eval(int device, const boss_mean_t* mean, int n, const double* X, int S, const double* thetas, int layout, double* m,
+                   double* jac_theta, double* jac_x);
+
 /* boss_ngp_predict_grad for n nonstationary posteriors at the same M candidates in ONE call, and the sample-averaged acquisition
  * gradient on top of it: boss_acq_ei_grad_set for NonstationaryGP posteriors (BI samples of a finite_nongp model under
  * OptimizationAM, src/acquisitions/expected_improvement.jl:87-90 inside src/acquisition_maximizers/optimization.jl:89-118).
