@@ -17,6 +17,10 @@ from .api import FitnessProgram, acq_ei_mc, acq_ei_mc_grad, acq_ei_mc_grad_momen
 from .mean import DeviceMean, trace_mean  # noqa: F401,E402
 from .api import MeanProgram  # noqa: F401,E402
 from .model import HipGaussianProcess, HipGPParams, average_mean  # noqa: F401,E402
+from .api import WarpProgram  # noqa: F401,E402
+from .transformed import (DeviceInputTransform, DeviceOutputTransform, DeviceSlicedOutputTransform,  # noqa: F401,E402
+                          HipTransformedModel, HipTransformedPosterior, InputTransform, JointOutputTransform,
+                          SlicedOutputTransform)
 from .gradient_gp import (GradientData, HipGradientGaussianProcess, HipGradientGPParams,  # noqa: F401,E402
                           gradient_sequential_batch, join_gradient_slices)
 from .nonstationary import HipNonstationaryGP, HipParametrizedGP, stack_latents  # noqa: F401,E402

@@ -147,6 +147,22 @@ SIGNATURES = {
     "boss_mean_free": (None, [C.c_void_p]),
     "boss_mean_eval_host": (C.c_int, [C.c_void_p, C.c_int, _c_dp, C.c_int, _c_dp, C.c_int, _c_dp, _c_dp, _c_dp]),
     "boss_mean_eval": (C.c_int, [C.c_int, C.c_void_p, C.c_int, _c_dp, C.c_int, _c_dp, C.c_int, _c_dp, _c_dp, _c_dp]),
+    "boss_warp_create": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "boss_warp_free": (None, [C.c_void_p]),
+    "boss_warp_apply_host": (C.c_int, [C.c_void_p, C.c_int, _c_dp, _c_dp, _c_dp]),
+    "boss_warp_apply": (C.c_int, [C.c_int, C.c_void_p, C.c_int, _c_dp, _c_dp, _c_dp]),
+    "boss_warp_moments_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp,
+                                         _c_dp, C.POINTER(C.c_long)]),
+    "boss_warp_moments": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp,
+                                    _c_dp, _c_dp, C.POINTER(C.c_long)]),
+    "boss_warp_predict": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_int, _c_dp, _c_dp, _c_dp, _c_dp,
+                                    C.POINTER(C.c_long)]),
+    "boss_warp_predict_grad": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_int, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp,
+                                         _c_dp, _c_dp, C.POINTER(C.c_long)]),
+    "boss_acq_ei_warp": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_int, _c_dp, _c_dp, _c_dp, _c_dp, C.c_int,
+                                   C.c_double, _c_ucp, _c_dp, C.POINTER(C.c_long), _c_dp]),
+    "boss_acq_ei_grad_warp": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_int, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp,
+                                        C.c_int, C.c_double, _c_ucp, _c_dp, _c_dp]),
     "boss_acq_ei_tracks": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_void_p), _c_dp, _c_dp, C.c_int, C.c_double, _c_ucp,
                                      _c_dp, C.POINTER(C.c_long), _c_dp]),
     "boss_init": (C.c_int, [C.POINTER(C.c_int)]),
@@ -2053,6 +2069,186 @@ class MeanProgram:
     def close(self):
         if self._h:
             load_library().boss_mean_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ---------------------------------------------------------------- warps: input warp and output transform as device programs
+WARP_MAX_DIM, WARP_MAX_OUTPUTS = 16, 8
+
+
+class WarpProgram:
+    """The input warp x -> x_ and the output transform (mu_, sd_) -> (mu, sd) of a transformed model (boss_warp_t).
+    in_prog: None or a MeanProgram with T = 0, d = d_user inputs and d_model outputs; out_prog: None or a MeanProgram with T = 0 over
+    the 2P inputs (mu_0.., sd_0..) with 2P outputs; P the number of model outputs.  The warp keeps copies: the MeanPrograms may be
+    closed afterwards.  Creating one needs no device.
+
+    apply / apply_host: Xs d_user×M -> (X_ d_model×M, J [M, d_model, d_user] or None).
+    moments / moments_host: mu_, var_ [S, P, M] (or [P, M]), gradients dmu_, dvar_ [S, P, d_model, M], jac = J of apply ->
+    (mu, var[, dmu, dvar [S, P, d_user, M]]).  check=True raises DomainError (.bad_index) at a variance below -1e-8; check=False
+    passes such a candidate's moments through with zero gradients (the acquisition convention)."""
+
+    def __init__(self, in_prog: Optional["MeanProgram"], P: int, out_prog: Optional["MeanProgram"]):
+        self.P = int(P)
+        self.d_user = None if in_prog is None else in_prog.d
+        self.d_model = None if in_prog is None else in_prog.P
+        self.has_out = out_prog is not None
+        self._h = C.c_void_p()
+        _check(load_library().boss_warp_create(None if in_prog is None else in_prog._h, self.P, None if out_prog is None else out_prog._h,
+                                               C.byref(self._h)))
+
+    def _apply(self, fn, head, Xs, jac):
+        Xs = _f64(Xs, 2)
+        if self.d_user is not None and Xs.shape[0] != self.d_user:
+            raise ValueError(f"Xs must be {self.d_user}×M")
+        M = Xs.shape[1]
+        dm = self.d_model or 0
+        Xo = np.zeros((dm, M), order="F")
+        J = np.zeros((M, self.d_user or 0, dm)) if jac else None     # per candidate d_model×d_user column-major
+        _check(fn(*head, self._h, M, _dp(Xs), _dp(Xo), _dp(J)))
+        return Xo, (None if J is None else J.transpose(0, 2, 1))
+
+    def apply_host(self, Xs, jac: bool = False):
+        return self._apply(load_library().boss_warp_apply_host, (), Xs, jac)
+
+    def apply(self, Xs, jac: bool = False, device: int = 0):
+        return self._apply(load_library().boss_warp_apply, (device,), Xs, jac)
+
+    def _moments(self, fn, head, mu_, var_, dmu_, dvar_, jac, d_user, check):
+        mu_ = np.asarray(mu_, dtype=np.float64)
+        var_ = np.asarray(var_, dtype=np.float64)
+        squeeze = mu_.ndim == 2
+        if squeeze:
+            mu_, var_ = mu_[None], var_[None]
+        if mu_.ndim != 3 or var_.shape != mu_.shape or mu_.shape[1] != self.P:
+            raise ValueError(f"mu_ and var_ must be [S, {self.P}, M] (or [{self.P}, M])")
+        S, P, M = mu_.shape
+        mu_, var_ = np.ascontiguousarray(mu_), np.ascontiguousarray(var_)
+        grad = dmu_ is not None
+        if grad != (dvar_ is not None):
+            raise ValueError("dmu_ and dvar_ come together")
+        gm = gv = Jc = dmu = dvar = None
+        du = self.d_user if d_user is None else int(d_user)
+        if grad:
+            gm = np.asarray(dmu_, dtype=np.float64).reshape(S, P, -1, M)
+            gv = np.asarray(dvar_, dtype=np.float64).reshape(S, P, -1, M)
+            if du is None:
+                du = gm.shape[2]
+            gm = np.ascontiguousarray(gm.transpose(0, 1, 3, 2))       # [s][p][j*d_model + k']
+            gv = np.ascontiguousarray(gv.transpose(0, 1, 3, 2))
+            if jac is not None:
+                Jc = np.ascontiguousarray(np.asarray(jac, dtype=np.float64).transpose(0, 2, 1))   # [j][k][k']: d_model×d_user column-major
+            dmu, dvar = np.zeros((S, P, M, du)), np.zeros((S, P, M, du))
+        if du is None:
+            du = 1                                                   # (no gradients, no input program: the value is not used)
+        mu, var = np.zeros((S, P, M)), np.zeros((S, P, M))
+        bad = C.c_long(-1)
+        try:
+            _check(fn(*head, self._h, S, M, du, _dp(mu_), _dp(var_), _dp(gm), _dp(gv), _dp(Jc), _dp(mu), _dp(var), _dp(dmu), _dp(dvar),
+                      C.byref(bad) if check else None))
+        except DomainError as e:
+            e.bad_index = bad.value
+            raise
+        out = (mu, var) if not grad else (mu, var, dmu.transpose(0, 1, 3, 2), dvar.transpose(0, 1, 3, 2))
+        return tuple(a[0] for a in out) if squeeze else out
+
+    def moments_host(self, mu_, var_, dmu_=None, dvar_=None, jac=None, d_user=None, check: bool = True):
+        return self._moments(load_library().boss_warp_moments_host, (), mu_, var_, dmu_, dvar_, jac, d_user, check)
+
+    def moments(self, mu_, var_, dmu_=None, dvar_=None, jac=None, d_user=None, check: bool = True, device: int = 0):
+        return self._moments(load_library().boss_warp_moments, (device,), mu_, var_, dmu_, dvar_, jac, d_user, check)
+
+    # -- one-call paths: gps[s][p] fitted on model-space data, Xs d_user×M in user space; mean_Xs None or [S][P][M] (the base model's
+    #    prior mean at the warped points), mean_grad None or [S][P][d_model][M] (its gradient w.r.t. x_)
+    def _set_args(self, gps, Xs, mean_Xs, mean_grad):
+        S = len(gps)
+        P = len(gps[0]) if S else 0
+        if S < 1 or P < 1 or any(len(row) != P for row in gps):
+            raise BossError(BOSS_E_INVALID, "gps must be S rows of P posteriors")
+        Xs = _f64(Xs, 2)
+        du, M = Xs.shape
+        dm = self.d_model if self.d_model is not None else du
+        arr = (C.c_void_p * (P * S))()
+        for s in range(S):
+            for p in range(P):
+                arr[p + P * s] = gps[s][p]._h
+        ms = None if mean_Xs is None else np.ascontiguousarray(np.asarray(mean_Xs, dtype=np.float64).reshape(S, P, M))
+        mg = None
+        if mean_grad is not None:
+            mg = np.ascontiguousarray(np.asarray(mean_grad, dtype=np.float64).reshape(S, P, dm, M).transpose(0, 1, 3, 2))
+        return S, P, M, du, arr, Xs, ms, mg
+
+    def predict(self, gps, Xs, mean_Xs=None):
+        """(mu, var) [S, P, M] in user space (boss_warp_predict).  DomainError (.bad_index) at a model variance below -1e-8."""
+        S, P, M, du, arr, Xs, ms, _ = self._set_args(gps, Xs, mean_Xs, None)
+        mu, var = np.zeros((S, P, M)), np.zeros((S, P, M))
+        bad = C.c_long(-1)
+        try:
+            _check(load_library().boss_warp_predict(self._h, P, S, arr, M, _dp(Xs), _dp(ms), _dp(mu), _dp(var), C.byref(bad)))
+        except DomainError as e:
+            e.bad_index = bad.value
+            raise
+        return mu, var
+
+    def predict_grad(self, gps, Xs, mean_Xs=None, mean_grad=None):
+        """(mu, var [S, P, M], dmu, dvar [S, P, d_user, M]) in user space (boss_warp_predict_grad)."""
+        S, P, M, du, arr, Xs, ms, mg = self._set_args(gps, Xs, mean_Xs, mean_grad)
+        mu, var = np.zeros((S, P, M)), np.zeros((S, P, M))
+        dmu, dvar = np.zeros((S, P, M, du)), np.zeros((S, P, M, du))
+        bad = C.c_long(-1)
+        try:
+            _check(load_library().boss_warp_predict_grad(self._h, P, S, arr, M, _dp(Xs), _dp(ms), _dp(mg), _dp(mu), _dp(var), _dp(dmu),
+                                                         _dp(dvar), C.byref(bad)))
+        except DomainError as e:
+            e.bad_index = bad.value
+            raise
+        return mu, var, dmu.transpose(0, 1, 3, 2), dvar.transpose(0, 1, 3, 2)
+
+    @staticmethod
+    def _acq_args(fit_coefs, y_max, valid_mask):
+        coefs = _f64(np.asarray(fit_coefs).reshape(-1), 1)
+        ym = None if y_max is None else _f64(np.asarray(y_max).reshape(-1), 1)
+        mask = None if valid_mask is None else np.ascontiguousarray(np.asarray(valid_mask, dtype=bool).astype(np.uint8))
+        return coefs, ym, mask
+
+    def acq_ei(self, gps, Xs, fit_coefs, y_max=None, best=None, valid_mask=None, mean_Xs=None, want_acq: bool = True):
+        """EI × feasibility of the warped model over user-space candidates (boss_acq_ei_warp): (acq[M] or None, argmax, max)."""
+        S, P, M, du, arr, Xs, ms, _ = self._set_args(gps, Xs, mean_Xs, None)
+        coefs, ym, mask = self._acq_args(fit_coefs, y_max, valid_mask)
+        acq = np.zeros(M) if want_acq else None
+        am = C.c_long(-1)
+        mx = C.c_double(0.0)
+        _check(load_library().boss_acq_ei_warp(self._h, P, S, arr, M, _dp(Xs), _dp(ms), _dp(coefs), _dp(ym), 0 if best is None else 1,
+                                               0.0 if best is None else float(best), _ucp(mask), _dp(acq), C.byref(am), C.byref(mx)))
+        return acq, am.value, mx.value
+
+    def acq_ei_grad(self, gps, Xs, fit_coefs, y_max=None, best=None, valid_mask=None, mean_Xs=None, mean_grad=None):
+        """The same with its gradient w.r.t. the user-space candidates (boss_acq_ei_grad_warp): (acq[M], dacq[d_user, M])."""
+        S, P, M, du, arr, Xs, ms, mg = self._set_args(gps, Xs, mean_Xs, mean_grad)
+        coefs, ym, mask = self._acq_args(fit_coefs, y_max, valid_mask)
+        acq = np.zeros(M)
+        dacq = np.zeros((du, M), order="F")
+        _check(load_library().boss_acq_ei_grad_warp(self._h, P, S, arr, M, _dp(Xs), _dp(ms), _dp(mg), _dp(coefs), _dp(ym),
+                                                    0 if best is None else 1, 0.0 if best is None else float(best), _ucp(mask), _dp(acq),
+                                                    _dp(dacq)))
+        return acq, dacq
+
+    def workgroup(self, stage: int, n: int, grad: bool, d_model: int = 0):
+        """(waves per workgroup, dynamic LDS bytes) of stage 0 (the input warp) or 1 (the moments) for n candidates (tests)."""
+        lib = load_library()
+        lib.boss_debug_warp_block.restype = C.c_int
+        lib.boss_debug_warp_block.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
+        lds = C.c_int(0)
+        return lib.boss_debug_warp_block(self._h, int(stage), 1 if grad else 0, int(n), int(d_model), C.byref(lds)), lds.value
+
+    def close(self):
+        if self._h:
+            load_library().boss_warp_free(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

@@ -28,6 +28,7 @@
 #include "nfit_kernels.hpp"
 #include "fitness.hpp"
 #include "mean_program.hpp"
+#include "warp_kernels.hpp"
 
 using namespace boss;
 
@@ -131,7 +132,7 @@ struct Ctx {
     bool prof_on = false;
     std::map<std::string, std::vector<std::pair<hipEvent_t, hipEvent_t>>> prof;
     std::vector<hipEvent_t> ev_pool;
-    Workspace vscratch, csc, pred, acq, batchA, batchX, batchMisc, craw, lgA, lgB, lgC, few, setdesc, setmom, gsetdesc, nlatjobs, mceps, meanws;
+    Workspace vscratch, csc, pred, acq, batchA, batchX, batchMisc, craw, lgA, lgB, lgC, few, setdesc, setmom, gsetdesc, nlatjobs, mceps, meanws, warpws;
     // batched likelihood gradients: the gradient passes of consecutive sets rotate over LLG_BANKS streams, each with its
     // own bank of workspaces (bank 0 = the main stream and lgA/lgB/lgC)
     static constexpr int LLG_BANKS = 4;
@@ -676,6 +677,7 @@ static void mc_grad_launch(hipStream_t s, const double* mu, const double* var, c
 #include "host_acq.inc"
 #include "host_fitness.inc"
 #include "host_mean.inc"
+#include "host_warp.inc"
 #include "host_rider.inc"
 #include "host_track.inc"
 #include "host_multi.inc"

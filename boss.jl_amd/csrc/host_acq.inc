@@ -6,6 +6,7 @@
 // dpair / idx_off / defer: one shard of a multi-device call (host_multi.inc) — the epilogue also leaves (max, global index) in the
 // device buffer dpair, and with defer the call returns right behind the enqueue (the caller runs the exchange on the same stream and
 // waits once); the shard's own (max, index) are then read from the context's pinned block by acq_shard_result.
+// (warp_call, host_warp.inc, restates this function's path selection and epilogue launches for warped models: keep the two in step)
 static int acq_ei_impl(int P, int S, boss_gp_t* const* gps, const boss_cand_t* cand, const double* mean_Xs,
                        const double* fit_coefs, const double* y_max, int has_best, double best,
                        const unsigned char* valid_mask, double* acq_out, long* argmax_out, double* max_out,

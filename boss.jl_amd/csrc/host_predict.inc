@@ -1386,6 +1386,7 @@ static int grad_set_enqueue(int n, boss_gp_t* const* gps, const boss_cand* cd, c
 // allocation failure go member by member through grad_enqueue into the same slices.
 // mc: the EI term and its gradient are those of a fitness program's Monte-Carlo mean (boss_acq_ei_mc_grad, host_fitness.inc); fit_coefs
 // is not read, P <= EI_MAXP, and S = 1 takes this path too.
+// (warp_call, host_warp.inc, restates this function's path selection and epilogue launches for warped models: keep the two in step)
 static int acq_ei_grad_set_impl(int P, int S, boss_gp_t* const* gps, int M, const double* Xs, const double* mean_Xs,
                                 const double* mean_grad, const double* fit_coefs, const double* y_max, int has_best,
                                 double best, const unsigned char* valid_mask, double* acq_out, double* dacq_out, const McEpi* mc) {

@@ -20,6 +20,7 @@ from . import distributed as dist_util
 from .mean import device_mean_of
 from .model import HipGaussianProcess, HipGPParams
 from .problem import BossOptions, BossProblem, Dirac, MvDirac, Normal
+from .transformed import base_problem
 
 
 @dataclass
@@ -37,6 +38,7 @@ class HipBatchedMAP:
 
     def estimate_parameters(self, problem: BossProblem, options: BossOptions = BossOptions(), return_all: bool = False):
         """estimate_parameters(::SamplingMAP, problem, options; return_all) (sampling.jl:17-28)."""
+        problem = base_problem(problem)                      # a HipTransformedModel: its base model on the transformed data
         model: HipGaussianProcess = problem.model
         rng = np.random.default_rng(dist_util.shared_seed(self.seed, self.group))     # the same draws on every rank
         sampler = model.params_sampler()
@@ -155,6 +157,7 @@ class HipGradientMAP:
         return tot, gl, ga, gs, gd
 
     def estimate_parameters(self, problem: BossProblem, options: BossOptions = BossOptions(), return_all: bool = False):
+        problem = base_problem(problem)                      # a HipTransformedModel: its base model on the transformed data
         model = problem.model
         grad_model = hasattr(model, "grad_noise_std_priors")        # HipGradientGaussianProcess (gradient_gp.py)
         semipar = not grad_model and model.parametric is not None

@@ -1366,4 +1366,14 @@ end
 # not bound: boss_mean_free — see boss_mean_create
 # not bound: boss_mean_eval_host — see boss_mean_create (the host run of the kernel's interpreter, used by tests)
 # not bound: boss_mean_eval — the traced mean and its Jacobians on the device; needs boss_mean_create
+# not bound: boss_warp_create — warps: the transforms of a TransformedModel are traced by the Python DeviceInputTransform / DeviceOutputTransform only; a Julia TransformedModel keeps the reference's host path
+# not bound: boss_warp_free — see boss_warp_create
+# not bound: boss_warp_apply_host — see boss_warp_create (the host run of the input-warp kernel's functions, used by tests)
+# not bound: boss_warp_apply — the traced input warp and its Jacobians on the device; needs boss_warp_create
+# not bound: boss_warp_moments_host — see boss_warp_create (the host run of the moments kernel's functions, used by tests)
+# not bound: boss_warp_moments — model-space moments to user space on the device; needs boss_warp_create
+# not bound: boss_warp_predict — prediction of a warped model in one call; needs boss_warp_create
+# not bound: boss_warp_predict_grad — prediction of a warped model with gradients in one call; needs boss_warp_create
+# not bound: boss_acq_ei_warp — acquisition of a warped model in one call; needs boss_warp_create
+# not bound: boss_acq_ei_grad_warp — acquisition gradient of a warped model in one call; needs boss_warp_create
 end # module

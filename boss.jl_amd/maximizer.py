@@ -29,6 +29,21 @@ from .fitness import DeviceFitness
 from .mean import device_mean_of
 from .model import HipGaussianProcessPosterior
 from .problem import BossOptions, BossProblem, NonlinFitness, best_so_far, in_bounds, in_cons, in_domain
+from .transformed import HipTransformedModel, HipTransformedPosterior, warped_acquisition_values, warped_value_and_grad
+
+
+def _unwarped(posts):
+    """Posteriors of a HipTransformedModel without transforms are the base model's: (posts to go on with, whether they are warped)."""
+    if not posts or not isinstance(posts[0], HipTransformedPosterior):
+        return posts, False
+    if posts[0]._identity():
+        return [p.base for p in posts], False
+    return posts, True
+
+
+def _no_warp(problem: BossProblem, what: str):
+    if isinstance(problem.model, HipTransformedModel):
+        raise NotImplementedError(f"{what} is not supported for a HipTransformedModel (use shard='candidates' on a single device)")
 
 
 def _rand_in_domain(x_prior: Callable, domain, rng, max_attempts: int):
@@ -106,6 +121,11 @@ def acquisition_values(problem: BossProblem, posts: Sequence[HipGaussianProcessP
     Returns (acq[M], local argmax, local max)."""
     ei = problem.acquisition
     Xs = np.asfortranarray(Xs, dtype=np.float64)
+    posts, warped = _unwarped(posts)
+    if warped:                                               # user-space candidates: the warp runs inside the call
+        if cand is not None:
+            raise NotImplementedError("resident candidates are not supported for a HipTransformedModel")
+        return warped_acquisition_values(problem, posts, Xs)
     own = cand is None
     if own:
         cand = api.Candidates(Xs, problem.model.device)
@@ -173,7 +193,9 @@ class HipBatchAM:
     group: object = None
     shard: str = "candidates"           # "candidates" | "outputs" | "samples"
     fused: bool = True                  # one output, one parameter sample, LinFitness: the posterior update and the acquisition in ONE device
-    #                                     call (boss_gp_update_acq: the candidates' substitution rides along the factorisation)
+    #                                     call (boss_gp_update_acq: the candidates' substitution rides along the factorisation).  The flag is a
+    #                                     permission, on by default: models the fused call does not take — the gradient-observation and
+    #                                     nonstationary models, a HipTransformedModel — run the two-call path without an error
     devices: Optional[Sequence[int]] = None   # ONE process driving GPUs 0..G-1: the shard modes run inside the library
     #                                           (boss_multi_*: one host thread per device, exchanges over RCCL) — what a Julia
     #                                           caller uses; None = one process per GPU over torch.distributed (or a single GPU)
@@ -196,6 +218,8 @@ class HipBatchAM:
         Xs = self.candidates(problem)                                   # identical on every rank (seeded)
         M = Xs.shape[1]
         rank, world = dist_util.rank_world(self.group)
+        if self.devices is not None or self.shard != "candidates":
+            _no_warp(problem, "devices=[...]" if self.devices is not None else f"shard={self.shard!r}")
         if self.devices is not None:
             assert world == 1 and posts is None, "devices=[...] is the single-process mode"
             return self._maximize_in_library(problem, Xs, return_all)
@@ -351,6 +375,7 @@ class HipSequentialBatchAM:
 
     def maximize_acquisition(self, problem: BossProblem, options: BossOptions = BossOptions()):
         import copy
+        _no_warp(problem, "HipSequentialBatchAM (appending observations, tracked candidates)")
         prob = copy.copy(problem)                                        # problem_ = deepcopy(problem) (batch.jl:27)
         prob.data = type(problem.data)(problem.data.X.copy(), problem.data.Y.copy())
         posts = posteriors_of(prob, reserve=self.batch_size)             # no re-allocation when the appends arrive
@@ -453,6 +478,11 @@ class HipGradientAM:
         return cache[key]
 
     def _value_and_grad(self, problem: BossProblem, posts, X):
+        posts, warped = _unwarped(posts)
+        if warped:
+            if self.mean_grad is not None:
+                raise ValueError("HipGradientAM: mean_grad is not taken for a HipTransformedModel (a DeviceMean gives its own ∂m/∂x_)")
+            return warped_value_and_grad(problem, posts, X)
         ei = problem.acquisition
         mc = isinstance(ei.fitness, DeviceFitness)
         if isinstance(ei.fitness, NonlinFitness) and not mc:

@@ -614,6 +614,89 @@ int boss_mean_eval_host(const boss_mean_t* mean, int n, const double* X, int S, 
 int boss_mean_eval(int device, const boss_mean_t* mean, int n, const double* X, int S, const double* thetas, int layout, double* m,
                    double* jac_theta, double* jac_x);
 
+/* ---- warps: the input warp and the output transform of a TransformedModel as device programs ------------------------------------
+ * Replaces: the per-column InputTransform.forward calls and the OutputTransform.forward calls per point of a TransformedModel's
+ * posterior (src/models/transformed.jl:222-257,330-378), and the ForwardDiff derivatives OptimizationAM pushes through both closures
+ * (src/acquisition_maximizers/optimization.jl:36).
+ *
+ * boss_warp_t holds validated COPIES of up to two programs, each given as a boss_mean_t with T == 0 (validation, limits, opcodes and
+ * derivative conventions are those of mean programs; the handles may be freed afterwards):
+ *   in_prog    NULL (identity) or x -> x_: d = d_user <= 16 inputs, d_model outputs (1..16; d_model may differ from d_user);
+ *   out_prog   NULL (identity) or (mu_0..mu_{P-1}, sd_0..sd_{P-1}) -> (mu_0.., sd_0..): 2P inputs, 2P outputs, so P <= 8.  A joint
+ *              transform is traced as it is; a per-output (sliced) one is packed into this form, its cross-derivatives exact zeros;
+ *   P          the number of model outputs: 1..8 with an output program, 1..16 without.
+ * BOSS_E_INVALID: both programs NULL, a program with T != 0, in_prog with more than 16 inputs, out_prog whose input or output count
+ * is not 2P, P out of range.  boss_warp_create / boss_warp_free and the _host calls need no device.
+ *
+ * boss_warp_apply: Xs d_user×M column-major -> X_out d_model×M column-major (the layout boss_cand_create takes) and, unless NULL,
+ * jac_out: per candidate j the block d_model×d_user column-major, jac_out[r + d_model*(k + d_user*j)] = d x__r / d x_k.  One thread
+ * per candidate.  BOSS_E_INVALID: no input program, M < 1, NULL Xs or X_out, M·d_model·d_user above 2^30.
+ *
+ * boss_warp_moments: the model-space moments of S posterior samples to user space.
+ *   mu_, var_      [s][p][M];
+ *   dmu_, dvar_    [s][p][d_model×M] column-major per block (k' + d_model*j): gradients w.r.t. x_;
+ *   jac            boss_warp_apply's jac_out, or NULL = the identity (then d_model = d_user);
+ *   mu, var        [s][p][M];  dmu, dvar [s][p][d_user×M] (k + d_user*j): gradients w.r.t. x;
+ *   the four gradient arrays are all NULL or all given; jac needs them, and they need jac when the warp has an input program.
+ * Per sample and candidate, with sd_ = sqrt(var_) after a variance in [-1e-8, 0) is clipped to 0, and grad sd_ = grad var_/(2 sd_),
+ * 0 where the variance was clipped or is 0 (the conventions of the Monte-Carlo section above):
+ *   (mu, sd) = out_prog(mu_, sd_),  var = sd·sd whatever the sign of sd (transformed.jl:343,350);
+ *   grad_{x_} out_r = sum_q d out_r/d mu_q grad mu_q + d out_r/d sd_q grad sd_q   (ascending q, the mu term first),
+ *   grad_x = J' grad_{x_} (ascending k'),  grad var = 2 sd grad sd.
+ * out_prog == NULL passes mu_ and var_ through bit for bit (no clip) and applies J' to dmu_ and dvar_.  NaN and Inf from a program
+ * are returned as computed.  One thread per (candidate, sample, output row of 2P); no atomics: repeated calls agree bit for bit.
+ * A variance below -1e-8 keeps the meaning it has for the caller: with bad_index given, the first one in memory order fails the call
+ * with BOSS_E_NEG_VAR, *bad_index = its candidate, before any work (boss_gp_predict's convention); with bad_index NULL, the
+ * sample's moments at that candidate pass through untouched with zero gradients, so that an acquisition epilogue behind this stage
+ * makes the candidate -Inf (boss_acq_ei_grad_set's convention).
+ * BOSS_E_INVALID: S < 1, M < 1, d_user outside 1..16 or different from the input program's, NULL moments, gradient arrays partly
+ * given, jac without them or without an input program, S·P·M·max(d_model, d_user) above 2^30.
+ * The _host calls run the same __host__ __device__ functions as the kernels on the host (tests). */
+typedef struct boss_warp boss_warp_t;
+int boss_warp_create(const boss_mean_t* in_prog, int P, const boss_mean_t* out_prog, boss_warp_t** out);
+void boss_warp_free(boss_warp_t* warp);
+int boss_warp_apply_host(const boss_warp_t* warp, int M, const double* Xs, double* X_out, double* jac_out);
+int boss_warp_apply(int device, const boss_warp_t* warp, int M, const double* Xs, double* X_out, double* jac_out);
+int boss_warp_moments_host(const boss_warp_t* warp, int S, int M, int d_user, const double* mu_, const double* var_,
+                           const double* dmu_, const double* dvar_, const double* jac, double* mu, double* var, double* dmu,
+                           double* dvar, long* bad_index);
+int boss_warp_moments(int device, const boss_warp_t* warp, int S, int M, int d_user, const double* mu_, const double* var_,
+                      const double* dmu_, const double* dvar_, const double* jac, double* mu, double* var, double* dmu,
+                      double* dvar, long* bad_index);
+
+/* The prediction and acquisition calls of a warped model in ONE call each: Xs (d_user×M, user space) goes up once, the input warp
+ * writes a temporary candidate set on the device, the handles predict in model space exactly as the plain calls make them, the
+ * moments of every sample go through boss_warp_moments' kernel where they lie, and the EI × feasibility epilogues of the plain
+ * calls run on the user-space result — y_max, best and the arg-max are in user space, as in the reference, and for S > 1 the mean
+ * over samples is taken on user-space EI (expected_improvement.jl:87-90 over TransformedPosteriors).  One copy back; no
+ * intermediate result visits the host.
+ *   gps        gps[p + P*s], fitted on model-space data: plain, semiparametric and gradient-observation handles as
+ *              boss_acq_ei_grad_set takes them (nonstationary handles: BOSS_E_INVALID); their x_dim must be the warp's d_model;
+ *   mean_Xs    the base model's prior mean at the WARPED points, [s][p][M], or NULL;
+ *   mean_grad  its gradient w.r.t. x_ there, [s][p][d_model×M], or NULL (the layouts of boss_acq_ei_grad_set);
+ *   mu, var    [s][p][M];  dmu, dvar [s][p][d_user×M];  acq_out M (may be NULL in boss_acq_ei_warp);  dacq_out d_user×M.
+ * boss_warp_predict / boss_warp_predict_grad: a model variance below -1e-8 fails the call with BOSS_E_NEG_VAR, *bad_index = the
+ * first such candidate; the acquisition calls make such a candidate -Inf with a zero gradient.
+ * What the calls return, bit for bit: with an input program alone, boss_acq_ei_warp what boss_acq_ei returns on a candidate set
+ * created from boss_warp_apply's X_out, boss_warp_predict what boss_gp_predict returns there; at S = 1, boss_warp_predict_grad
+ * what boss_warp_apply -> boss_gp_predict_grad per output -> boss_warp_moments return, and boss_acq_ei_grad_warp what
+ * boss_acq_ei_grad_moments makes of that.  In the acquisition calls equally shaped handles of S > 1 samples take the set launches
+ * of the plain acquisition calls; the prediction calls go handle by handle, as boss_gp_predict[_grad] do.
+ * Everything else (fit_coefs, y_max, has_best / best, valid_mask, arg-max rules) as in boss_acq_ei and boss_acq_ei_grad_set.
+ * BOSS_E_INVALID: P differs from the warp's, handles of different devices or x_dim, x_dim different from d_model or above 16,
+ * P·S·M·max(d_model, d_user) above 2^30.  After an error nothing stays enqueued and every handle stays usable. */
+int boss_warp_predict(const boss_warp_t* warp, int P, int S, boss_gp_t* const* gps, int M, const double* Xs, const double* mean_Xs,
+                      double* mu, double* var, long* bad_index);
+int boss_warp_predict_grad(const boss_warp_t* warp, int P, int S, boss_gp_t* const* gps, int M, const double* Xs,
+                           const double* mean_Xs, const double* mean_grad, double* mu, double* var, double* dmu, double* dvar,
+                           long* bad_index);
+int boss_acq_ei_warp(const boss_warp_t* warp, int P, int S, boss_gp_t* const* gps, int M, const double* Xs, const double* mean_Xs,
+                     const double* fit_coefs, const double* y_max, int has_best, double best, const unsigned char* valid_mask,
+                     double* acq_out, long* argmax_out, double* max_out);
+int boss_acq_ei_grad_warp(const boss_warp_t* warp, int P, int S, boss_gp_t* const* gps, int M, const double* Xs,
+                          const double* mean_Xs, const double* mean_grad, const double* fit_coefs, const double* y_max, int has_best,
+                          double best, const unsigned char* valid_mask, double* acq_out, double* dacq_out);
+
 /* boss_ngp_predict_grad for n nonstationary posteriors at the same M candidates in ONE call, and the sample-averaged acquisition
  * gradient on top of it: boss_acq_ei_grad_set for NonstationaryGP posteriors (BI samples of a finite_nongp model under
  * OptimizationAM, src/acquisitions/expected_improvement.jl:87-90 inside src/acquisition_maximizers/optimization.jl:89-118).
