@@ -2494,3 +2494,52 @@ def _set_grad_launches(device: int = 0):
     a = C.c_long(0)
     fn(device, C.byref(a))
     return a.value
+
+
+def _acq_path(device: int = 0):
+    """What the last arg-max-only boss_acq_ei on `device` did (boss_debug_acq_path; tests): (path, round-1 count, round-2 count,
+    head blocks s, whether a = L⁻ᵀz was rebuilt); path 0: full kernel, 1: pruned, 2: fallback after an attempt, 3: skipped by the
+    back-off."""
+    fn = load_library().boss_debug_acq_path
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_int, C.POINTER(C.c_int)]
+    out = (C.c_int * 5)()
+    _check(fn(device, out))
+    return tuple(out)
+
+
+def _acq_prune_set(device: int = 0, min_tiles: int = -1, K: int = -1, s: int = -1, cap: int = -1, slack: Optional[float] = None):
+    """Settings of the arg-max-only acquisition path (boss_debug_acq_prune_set / boss_debug_acq_prune_slack; tests): candidate tiles
+    above which it is tried, round-1 size, head blocks, round-2 cap, scale of the bound's slacks.  -1 / None keeps a value, anything
+    below -1 restores its default."""
+    lib = load_library()
+    fn = lib.boss_debug_acq_prune_set
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_int] * 5
+    _check(fn(device, int(min_tiles), int(K), int(s), int(cap)))
+    if slack is not None:
+        fs = lib.boss_debug_acq_prune_slack
+        fs.restype = C.c_int
+        fs.argtypes = [C.c_int, C.c_double]
+        _check(fs(device, float(slack)))
+
+
+def _acq_prune_bounds(M: int, device: int = 0):
+    """(μ_a, σ²_s, ub) of the last pruned attempt over M candidates on `device` (boss_debug_acq_prune_bounds; measurements)."""
+    fn = load_library().boss_debug_acq_prune_bounds
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    mua, vs, ub = np.zeros(M), np.zeros(M), np.zeros(M)
+    _check(fn(device, int(M), mua.ctypes.data, vs.ctypes.data, ub.ctypes.data))
+    return mua, vs, ub
+
+
+def _acq_counters(g: GP):
+    """(resident inverse factors exist, few-candidates call count of the handle, device allocations of the process, kernels the
+    arg-max-only path enqueued on the handle's device) (boss_debug_acq_counters; tests)."""
+    fn = load_library().boss_debug_acq_counters
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.POINTER(C.c_long)]
+    out = (C.c_long * 4)()
+    _check(fn(g._h, out))
+    return tuple(out)

@@ -29,6 +29,7 @@
 #include "fitness.hpp"
 #include "mean_program.hpp"
 #include "warp_kernels.hpp"
+#include "prune_kernels.hpp"
 
 using namespace boss;
 
@@ -65,10 +66,12 @@ constexpr size_t PINNED_UP_OFF = 4096, PINNED_UP_BYTES = 1024 * 1024, PINNED_DOW
 // every device allocation goes through here; BOSS_POISON_ALLOC=1 (tests) fills new memory with NaN bit patterns so that
 // reads of never-written memory show up instead of passing on the zeros a fresh process happens to get
 static bool release_cached_slabs();                        // (defined with the contexts below)
+static std::atomic<long> g_dev_allocs{0};                  // device allocations so far (boss_debug_acq_counters: a repeated call must not allocate)
 static std::atomic<int> g_fail_allocs{0};                  // tests (boss_debug_fail_next_alloc): that many first attempts report "out of memory"
 static hipError_t dev_malloc(void** p, size_t bytes) {
     static const bool poison = getenv("BOSS_POISON_ALLOC") && atoi(getenv("BOSS_POISON_ALLOC"));
     hipError_t e = hipErrorOutOfMemory;
+    g_dev_allocs.fetch_add(1, std::memory_order_relaxed);
     if (g_fail_allocs.load(std::memory_order_relaxed) > 0 && g_fail_allocs.fetch_sub(1) > 0) *p = nullptr;
     else e = hipMalloc(p, bytes);
     if (e != hipSuccess) (void)hipGetLastError();            // a failed allocation must not surface later as a stale launch error
@@ -132,7 +135,7 @@ struct Ctx {
     bool prof_on = false;
     std::map<std::string, std::vector<std::pair<hipEvent_t, hipEvent_t>>> prof;
     std::vector<hipEvent_t> ev_pool;
-    Workspace vscratch, csc, pred, acq, batchA, batchX, batchMisc, craw, lgA, lgB, lgC, few, setdesc, setmom, gsetdesc, nlatjobs, mceps, meanws, warpws;
+    Workspace vscratch, csc, pred, acq, batchA, batchX, batchMisc, craw, lgA, lgB, lgC, few, setdesc, setmom, gsetdesc, nlatjobs, mceps, meanws, warpws, prunews;
     // batched likelihood gradients: the gradient passes of consecutive sets rotate over LLG_BANKS streams, each with its
     // own bank of workspaces (bank 0 = the main stream and lgA/lgB/lgC)
     static constexpr int LLG_BANKS = 4;
@@ -141,6 +144,9 @@ struct Ctx {
     hipEvent_t llg_join[LLG_BANKS - 1] = {nullptr, nullptr, nullptr};
     //   // lg*: log-likelihood gradient (LinvT, K⁻¹, partials)   // craw: raw candidates of one-shot calls
     void* pinned = nullptr;   // small host-pinned result area
+    int prune_last[5] = {0, 0, 0, 0, 0};       // the last arg-max-only acquisition (boss_debug_acq_path): path, round-1 / round-2 counts, head blocks, a rebuilt
+    long prune_launches = 0;                   // kernels the arg-max-only path itself enqueued so far (boss_debug_acq_counters)
+    int prune_M = 0;                           // candidates of the last pruned attempt (prunews holds its bounds)
     // work tables of the deferred trailing update under the chain (BOSS_CHAIN_TRAIL=4), one per block-column count: planned and
     // uploaded by the first factorisation of that size (trail_table, host_factor.inc)
     struct TrailTab {
@@ -359,6 +365,8 @@ static int ctx_init(Ctx* c) {
     HIPCHK(hipFuncSetAttribute((const void*)rider_step_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
     HIPCHK(hipFuncSetAttribute((const void*)predict_kernel<PredG32>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                PredictLds<PredG32>::BYTES));
+    HIPCHK(hipFuncSetAttribute((const void*)prune_head_kernel<PredG32>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               PredictLds<PredG32>::BYTES));
     HIPCHK(hipFuncSetAttribute((const void*)predict_kernel_set<PredG32>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                PredictLds<PredG32>::BYTES));
     HIPCHK(hipFuncSetAttribute((const void*)grad_accum_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
@@ -558,6 +566,12 @@ struct boss_gp {
     bool have_winv = false;
     int few_calls = 0;
     int append_calls = 0;                      // single-observation appends since the last update (the second one builds the inverses)
+    // arg-max-only acquisition (host_prune.inc): a = L⁻ᵀz [Np] | residual [Np] with the factor generation it was built for, and the
+    // back-off after a fallback (calls still to skip, length of the next pause)
+    double* prune_a = nullptr;
+    int prune_a_np = 0;
+    unsigned long long prune_a_gen = ~0ull;
+    int prune_skip = 0, prune_backoff = 0;
     int append_path = 0;                       // how the last append ran (boss_debug_append_path): 0 none yet, 1 block rows, 2 re-factorised, 3 rank-one
 };
 
@@ -674,6 +688,7 @@ static void mc_accumulate_launch(hipStream_t s, const double* mu, const double* 
 static void mc_grad_launch(hipStream_t s, const double* mu, const double* var, const double* dmu, const double* dvar, int M, int d, int S,
                            const EiPar& par, const McEpi& mc, const double* deps, const unsigned char* mask, double* acq, double* dacq);
 #include "host_predict.inc"
+#include "host_prune.inc"
 #include "host_acq.inc"
 #include "host_fitness.inc"
 #include "host_mean.inc"

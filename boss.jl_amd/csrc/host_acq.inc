@@ -54,6 +54,23 @@ static int acq_ei_impl(int P, int S, boss_gp_t* const* gps, const boss_cand_t* c
     par0.mode = 0;
     if (valid_mask) (void)hipMemcpyAsync(dmask, valid_mask, M, hipMemcpyHostToDevice, s);
     if (S > 1) (void)hipMemsetAsync(dacq, 0, sizeof(double) * M, s);
+    if (!acq_out && !defer) {
+        // arg-max only: bound every candidate, finish the contenders (host_prune.inc); anything it declines runs the full kernel below
+        for (int i = 0; i < 5; ++i) c->prune_last[i] = 0;
+        if (prune_eligible(gps[0], cand, P, S, par, acq_out != nullptr, defer, mc != nullptr, dpair)) {
+            if (mean_Xs) (void)hipMemcpyAsync(dmean, mean_Xs, sizeof(double) * M, hipMemcpyHostToDevice, s);   // (P = S = 1: the caller's layout is [j])
+            bool done = false;
+            double pmax = 0.0;
+            long pidx = 0;
+            rc = acq_prune_try(gps[0], cand, mean_Xs ? dmean : nullptr, valid_mask ? dmask : nullptr, par, &done, &pmax, &pidx);
+            if (rc) return rc;
+            if (done) {
+                if (argmax_out) *argmax_out = pidx;
+                if (max_out) *max_out = pmax;
+                return BOSS_OK;
+            }
+        }
+    }
     std::vector<double> hmean;
     static const bool set_off = getenv("BOSS_NO_SET_PREDICT") && atoi(getenv("BOSS_NO_SET_PREDICT"));
     if (S > 1 && par.mode != 0 && !set_off && predict_set_ok(P * S, gps, cand)) {

@@ -634,6 +634,7 @@ static void gp_release(boss_gp* g) {
     if (g->Winv) (void)hipFree(g->Winv);
     if (g->Linv) (void)hipFree(g->Linv);
     if (g->W2) (void)hipFree(g->W2);
+    if (g->prune_a) (void)hipFree(g->prune_a);
     if (g->lamX) (void)hipFree(g->lamX);
     if (g->ampX) (void)hipFree(g->ampX);
     if (g->noiseX) (void)hipFree(g->noiseX);

@@ -191,8 +191,9 @@ static bool small_predict_ok(const boss_gp* g, int M) {
 
 static int predict_enqueue(boss_gp* g, const boss_cand* cd, const double* mean_s_dev, double* mu, double* var,
                            bool for_grad = false, const double* clam_dev = nullptr, const double* camp_dev = nullptr,
-                           bool need_v = false) {
+                           bool need_v = false, bool internal = false) {
     // need_v: the caller reads V = L⁻¹K* from the slab scratch afterwards (covariances); for_grad implies it
+    // internal: a round of the arg-max-only acquisition (host_prune.inc) — it does not count as a few-candidates call of the user's
     Ctx* c = g->ctx;
     hipStream_t s = c->stream;
     if (!g->fitted) return fail(BOSS_E_NOT_FITTED, "handle has no valid factorisation");
@@ -265,7 +266,7 @@ static int predict_enqueue(boss_gp* g, const boss_cand* cd, const double* mean_s
         // without sequential steps (inv_fwd_kernel / inv_bwd_kernel)
         static const int winv_after = getenv("BOSS_WINV_AFTER") ? atoi(getenv("BOSS_WINV_AFTER")) : 2;
         const size_t winv_lds = sizeof(double) * (size_t)g->Np * (cd->M == 1 ? 1 : cd->M == 2 ? 2 : WINV_MAX_M);   // K* staged in LDS
-        if (winv_after > 0 && !g->have_winv && ++g->few_calls >= winv_after) {
+        if (winv_after > 0 && !g->have_winv && !internal && ++g->few_calls >= winv_after) {
             const size_t bytes = sizeof(double) * (size_t)g->ld * g->Np;
             bool ok = (g->Winv != nullptr || dev_malloc((void**)&g->Winv, bytes) == hipSuccess) &&
                       (g->Linv != nullptr || dev_malloc((void**)&g->Linv, bytes) == hipSuccess);
