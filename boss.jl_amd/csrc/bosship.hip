@@ -68,8 +68,11 @@ constexpr size_t PINNED_UP_OFF = 4096, PINNED_UP_BYTES = 1024 * 1024, PINNED_DOW
 static bool release_cached_slabs();                        // (defined with the contexts below)
 static std::atomic<long> g_dev_allocs{0};                  // device allocations so far (boss_debug_acq_counters: a repeated call must not allocate)
 static std::atomic<int> g_fail_allocs{0};                  // tests (boss_debug_fail_next_alloc): that many first attempts report "out of memory"
+static bool poison_alloc() {
+    static const bool v = getenv("BOSS_POISON_ALLOC") && atoi(getenv("BOSS_POISON_ALLOC"));
+    return v;
+}
 static hipError_t dev_malloc(void** p, size_t bytes) {
-    static const bool poison = getenv("BOSS_POISON_ALLOC") && atoi(getenv("BOSS_POISON_ALLOC"));
     hipError_t e = hipErrorOutOfMemory;
     g_dev_allocs.fetch_add(1, std::memory_order_relaxed);
     if (g_fail_allocs.load(std::memory_order_relaxed) > 0 && g_fail_allocs.fetch_sub(1) > 0) *p = nullptr;
@@ -79,7 +82,7 @@ static hipError_t dev_malloc(void** p, size_t bytes) {
         e = hipMalloc(p, bytes);
         if (e != hipSuccess) (void)hipGetLastError();
     }
-    if (e == hipSuccess && poison) {
+    if (e == hipSuccess && poison_alloc()) {
         (void)hipMemset(*p, 0xff, bytes);                    // null stream: the library's streams do not wait for it ...
         (void)hipDeviceSynchronize();                        // ... so finish it before anything else touches the block
     }
@@ -492,7 +495,7 @@ struct boss_gpset {
 };
 static bool slab_cache_on() {
     static const bool v = !(getenv("BOSS_SLAB_CACHE") && atoi(getenv("BOSS_SLAB_CACHE")) == 0) &&
-                          !(getenv("BOSS_POISON_ALLOC") && atoi(getenv("BOSS_POISON_ALLOC")));   // (poisoned allocations are for finding reads of never-written memory: always fresh)
+                          !poison_alloc();                   // (poisoned allocations are for finding reads of never-written memory: always fresh)
     return v;
 }
 // the last member of a set is gone: its storage goes to the context's one-entry cache (the larger block wins) or back to the device

@@ -72,8 +72,7 @@ static int acq_ei_impl(int P, int S, boss_gp_t* const* gps, const boss_cand_t* c
         }
     }
     std::vector<double> hmean;
-    static const bool set_off = getenv("BOSS_NO_SET_PREDICT") && atoi(getenv("BOSS_NO_SET_PREDICT"));
-    if (S > 1 && par.mode != 0 && !set_off && predict_set_ok(P * S, gps, cand)) {
+    if (S > 1 && par.mode != 0 && !set_predict_off() && predict_set_ok(P * S, gps, cand)) {
         // Bayesian-inference average over S posteriors of one shape: ALL P·S predictions in one launch (grid = candidate tiles ×
         // posteriors), moments [s][p][j] resident, then the EI sum over the samples in sample order and the usual epilogue
         const size_t pm = (size_t)P * M;

@@ -240,6 +240,102 @@ static int reserve_locked_entry(boss_gp* g, int N_total) {
     return BOSS_OK;
 }
 
+// Knobs the rank-one append shares with the few-candidate prediction (host_predict.inc).  BOSS_WINV_AFTER: the call with few
+// candidates on one factorisation from which on the inverse factors are built and kept resident (0: never).  BOSS_NO_FEW_ARGS=1:
+// points and candidates go through device buffers, never through kernel arguments.
+static int winv_after() {
+    static const int v = getenv("BOSS_WINV_AFTER") ? atoi(getenv("BOSS_WINV_AFTER")) : 2;
+    return v;
+}
+static bool few_args_off() {
+    static const bool v = getenv("BOSS_NO_FEW_ARGS") && atoi(getenv("BOSS_NO_FEW_ARGS"));
+    return v;
+}
+
+// A pending update is finished and the handle must be fitted (gp_settle); a posterior with a prior mean needs its values at the
+// new points.  Caller holds the context lock.
+static int append_settle(boss_gp* g, const char* unfitted, const double* mean_new) {
+    int rc = gp_settle(g, unfitted);
+    if (rc) return rc;
+    if (g->has_mean && !mean_new)
+        return fail(BOSS_E_INVALID, "the posterior has a prior mean: mean_new (its values at the new points) is required");
+    return BOSS_OK;
+}
+
+// The n new points (rounded where discrete) behind the resident ones, the ny new rows of y and, where given, of the prior mean
+// behind row N; waits for the copies, so the caller's and the staging buffers may go.  Caller holds the context lock; the handle
+// has room (gp_grow) and still counts the old observations.
+static int append_upload(boss_gp* g, int n, const double* X_new, int ny, const double* y_rows, const double* mean_new) {
+    hipStream_t s = g->ctx->stream;
+    const int d = g->d, N0 = g->N;
+    const int col0 = g->aug ? g->npts : N0, pitch = g->aug ? g->ldx : g->Np;   // (a gradient-observation handle: one column per POINT)
+    std::vector<double> xb;
+    pack_points(xb, X_new, d, n, n, g->discrete.empty() ? nullptr : g->discrete.data());
+    HIPCHK(hipMemcpy2DAsync(g->Xraw + col0, sizeof(double) * pitch, xb.data(), sizeof(double) * n, sizeof(double) * n, d,
+                            hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(g->y + N0, y_rows, sizeof(double) * ny, hipMemcpyHostToDevice, s));
+    if (mean_new) {
+        HIPCHK(hipMemcpyAsync(g->mean + N0, mean_new, sizeof(double) * ny, hipMemcpyHostToDevice, s));
+        g->has_mean = true;
+    }
+    HIPCHK(hipStreamSynchronize(s));           // staging buffers go out of scope
+    return BOSS_OK;
+}
+
+// The block rows N0 … N1 − 1 of the factor, for every model: those holding new observations and, when the storage has just grown
+// (Np_before != Np), the pure padding block rows behind them as well (identity blocks of the factor and their inverses: the new
+// arrays are uninitialised).  Each block row's Gram tiles — from the model's own Gram kernel — are swept through the finished
+// panels, then its diagonal block is factorised; where most of the matrix is new, a plain re-factorisation is cheaper than
+// block-row sweeps.  Ends with the results on their way to host_res: follow with update_finish.  Caller holds the context lock;
+// the data of the new rows is resident and g->N counts them.
+static int append_rows_enqueue(boss_gp* g, int N0, int N1, int Np_before) {
+    hipStream_t s = g->ctx->stream;
+    const int kb0 = N0 / BLK, kb1 = (g->Np != Np_before) ? g->nblk - 1 : (N1 - 1) / BLK;
+    if (kb1 - kb0 + 1 > 4 || kb1 - kb0 + 1 >= g->nblk) {
+        g->append_path = 2;
+        return factor_enqueue(g);
+    }
+    g->append_path = 1;
+    const int d = g->d, Np = g->Np, ld = g->ld;
+    dinv_join(g);
+    HIPCHK(hipMemsetAsync(g->info, 0, sizeof(int), s));
+    if (!g->aug && !g->gibbs)
+        hipLaunchKernelGGL(scale_points_kernel, dim3((Np + 255) / 256, 1, 1), dim3(256), 0, s, g->Xraw, g->Xsc, (size_t)0,
+                           g->invlam, d, Np);
+    for (int kb = kb0; kb <= kb1; ++kb) {
+        hipLaunchKernelGGL(rhs_rows_kernel, dim3(1, 1, 1), dim3(BLK), 0, s, g->A, ld, (size_t)0, N1, Np, g->y, g->mean,
+                           (size_t)0, kb * BLK, (int*)nullptr);
+        // 128 rows × columns 0 … (kb+1)·128 − 1: the 4·kb + 3 tiles from triangular tile index kb (2 kb + 1), a full build's arithmetic
+        const dim3 tiles(4 * kb + 3, 1, 1);
+        const int tile0 = kb * (2 * kb + 1);
+        if (g->aug)
+            hipLaunchKernelGGL(aug_gram_kernel, tiles, dim3(256), 0, s, (const double*)g->Xraw, g->ldx, d, g->nhead, N1,
+                               Np, g->kernel, (const double*)g->hyp, (const double*)g->invlam, (size_t)0, g->A, ld, (size_t)0, tile0);
+        else if (g->gibbs)
+            hipLaunchKernelGGL(gibbs_gram_kernel, tiles, dim3(256), 0, s, (const double*)g->Xraw,
+                               (const double*)g->lamX, (const double*)g->ampX, (const double*)g->noiseX, (size_t)0, (size_t)0, d, N1,
+                               Np, g->A, ld, (size_t)0, tile0);
+        else
+            hipLaunchKernelGGL(gram_kernel, tiles, dim3(256), 0, s, g->Xsc, (size_t)0, d, N1, Np, g->kernel,
+                               g->hyp, g->A, ld, (size_t)0, tile0);
+        for (int k = 0; k < kb; ++k) {
+            hipLaunchKernelGGL(potrf_trsm_kernel, dim3(8, 1, 1), dim3(TRSM_THREADS), 0, s, g->A, ld, (size_t)0, k, g->inv16, (size_t)0,
+                               kb * BLK);
+            hipLaunchKernelGGL(potrf_rowupd_kernel, dim3(4 * (kb - k) + 1), dim3(256), 0, s, g->A, ld, k, kb, Np);
+        }
+        hipLaunchKernelGGL(potrf_diag_kernel, dim3(1, 1, 1), dim3(DIAG_THREADS), DIAG_LDS_BYTES, s, g->A, ld, (size_t)0, kb,
+                           g->inv16, (size_t)0, g->info, (unsigned long long*)nullptr, 0ull);
+        hipLaunchKernelGGL(potrf_trsm_kernel, dim3(1, 1, 1), dim3(TRSM_THREADS), 0, s, g->A, ld, (size_t)0, kb, g->inv16, (size_t)0,
+                           Np);
+    }
+    dinv_eager(g);
+    hipLaunchKernelGGL(potrf_logdet_kernel, dim3(1, 1, 1), dim3(LOGDET_THREADS), 0, s, g->A, ld, (size_t)0, N1, Np, g->scal,
+                       (double*)nullptr, (const int*)nullptr, (unsigned long long*)nullptr, 0ull, 0ull);
+    HIPCHK(hipMemcpyAsync(g->host_res, g->scal, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&g->host_res[2], g->info, sizeof(int), hipMemcpyDeviceToHost, s));
+    return BOSS_OK;
+}
+
 static int append_locked(boss_gp* g, int n, const double* X_new, const double* y_new, const double* mean_new, double* logpdf_out);
 
 extern "C" int boss_gp_append(boss_gp_t* g, int n, const double* X_new, const double* y_new, const double* mean_new,
@@ -263,19 +359,15 @@ extern "C" int boss_gp_append(boss_gp_t* g, int n, const double* X_new, const do
 // caller holds the context lock
 static int append_locked(boss_gp* g, int n, const double* X_new, const double* y_new, const double* mean_new, double* logpdf_out) {
     Ctx* c = g->ctx;
-    int rc = gp_settle(g, "append needs a fitted handle (its hyper-parameters are reused)");
+    int rc = append_settle(g, "append needs a fitted handle (its hyper-parameters are reused)", mean_new);
     if (rc) return rc;
-    if (g->has_mean && !mean_new)
-        return fail(BOSS_E_INVALID, "the posterior has a prior mean: mean_new (its values at the new points) is required");
     hipStream_t s = c->stream;
     const int d = g->d, N0 = g->N, N1 = N0 + n;
     const int Np_before = g->Np;
     // one observation into existing storage, not the first such append on these hyper-parameters: rank-one append on the
     // resident inverse factors (built here if they are not resident yet)
-    static const int winv_after = getenv("BOSS_WINV_AFTER") ? atoi(getenv("BOSS_WINV_AFTER")) : 2;
     bool fast = false;
-    g->append_path = 0;
-    if (n == 1 && N1 <= g->Np && winv_after > 0 && sizeof(double) * (size_t)g->Np <= 144 * 1024) {
+    if (n == 1 && N1 <= g->Np && winv_after() > 0 && sizeof(double) * (size_t)g->Np <= 144 * 1024) {
         if (!g->have_winv && ++g->append_calls >= 2 && g->few_calls >= 0) {
             const size_t bytes = sizeof(double) * (size_t)g->ld * g->Np;
             bool ok = (g->Winv != nullptr || dev_malloc((void**)&g->Winv, bytes) == hipSuccess) &&
@@ -297,28 +389,12 @@ static int append_locked(boss_gp* g, int n, const double* X_new, const double* y
     }
     rc = gp_grow(g, N1);
     if (rc) return rc;
-    g->fitted = false;
-    g->have_lt = false;
-    ++g->factor_gen;                                         // every append changes the factor: a block 0 of Dinv built on its own before it is stale
-    if (!fast) {
-        g->have_dinv = false;
-        g->have_winv = false;
-        g->few_calls = 0;
-    }
+    gp_invalidate_append(g, fast);
     // one observation on resident inverse factors, x_dim small enough for kernel arguments: no upload, no synchronisation in front
-    static const bool args_off = getenv("BOSS_NO_FEW_ARGS") && atoi(getenv("BOSS_NO_FEW_ARGS"));
-    const bool by_args = fast && n == 1 && d <= FEW_ARGS_MAX_D && !args_off;
+    const bool by_args = fast && n == 1 && d <= FEW_ARGS_MAX_D && !few_args_off();
     if (!by_args) {
-        std::vector<double> xb;
-        pack_points(xb, X_new, d, n, n, g->discrete.empty() ? nullptr : g->discrete.data());
-        HIPCHK(hipMemcpy2DAsync(g->Xraw + N0, sizeof(double) * g->Np, xb.data(), sizeof(double) * n, sizeof(double) * n, d,
-                                hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(g->y + N0, y_new, sizeof(double) * n, hipMemcpyHostToDevice, s));
-        if (mean_new) {
-            HIPCHK(hipMemcpyAsync(g->mean + N0, mean_new, sizeof(double) * n, hipMemcpyHostToDevice, s));
-            g->has_mean = true;
-        }
-        HIPCHK(hipStreamSynchronize(s));       // staging buffers go out of scope
+        rc = append_upload(g, n, X_new, n, y_new, mean_new);
+        if (rc) return rc;
     }
     g->N = N1;
     if (fast) {
@@ -421,42 +497,8 @@ static int append_locked(boss_gp* g, int n, const double* X_new, const double* y
         }
         return rc;
     }
-    // block rows to (re)build: those holding new observations and, when the storage has just grown, the pure padding
-    // block rows behind them as well (identity blocks of the factor and their inverses: the new arrays are uninitialised)
-    const int kb0 = N0 / BLK, kb1 = (g->Np != Np_before) ? g->nblk - 1 : (N1 - 1) / BLK;
-    if (kb1 - kb0 + 1 > 4 || kb1 - kb0 + 1 >= g->nblk) {
-        // most of the matrix is new: a plain re-factorisation is cheaper than block-row sweeps
-        g->append_path = 2;
-        rc = factor_enqueue(g);
-        if (rc) return rc;
-    } else {
-        g->append_path = 1;
-        const int Np = g->Np, ld = g->ld;
-        dinv_join(g);
-        HIPCHK(hipMemsetAsync(g->info, 0, sizeof(int), s));
-        hipLaunchKernelGGL(scale_points_kernel, dim3((Np + 255) / 256, 1, 1), dim3(256), 0, s, g->Xraw, g->Xsc, (size_t)0,
-                           g->invlam, d, Np);
-        for (int kb = kb0; kb <= kb1; ++kb) {
-            hipLaunchKernelGGL(rhs_rows_kernel, dim3(1, 1, 1), dim3(BLK), 0, s, g->A, ld, (size_t)0, N1, Np, g->y, g->mean,
-                               (size_t)0, kb * BLK, (int*)nullptr);
-            hipLaunchKernelGGL(gram_kernel, dim3(4 * kb + 3, 1, 1), dim3(256), 0, s, g->Xsc, (size_t)0, d, N1, Np, g->kernel,
-                               g->hyp, g->A, ld, (size_t)0, kb * (2 * kb + 1));
-            for (int k = 0; k < kb; ++k) {
-                hipLaunchKernelGGL(potrf_trsm_kernel, dim3(8, 1, 1), dim3(TRSM_THREADS), 0, s, g->A, ld, (size_t)0, k, g->inv16, (size_t)0,
-                                   kb * BLK);
-                hipLaunchKernelGGL(potrf_rowupd_kernel, dim3(4 * (kb - k) + 1), dim3(256), 0, s, g->A, ld, k, kb, Np);
-            }
-            hipLaunchKernelGGL(potrf_diag_kernel, dim3(1, 1, 1), dim3(DIAG_THREADS), DIAG_LDS_BYTES, s, g->A, ld, (size_t)0, kb,
-                               g->inv16, (size_t)0, g->info, (unsigned long long*)nullptr, 0ull);
-            hipLaunchKernelGGL(potrf_trsm_kernel, dim3(1, 1, 1), dim3(TRSM_THREADS), 0, s, g->A, ld, (size_t)0, kb, g->inv16, (size_t)0,
-                               Np);
-        }
-        dinv_eager(g);
-        hipLaunchKernelGGL(potrf_logdet_kernel, dim3(1, 1, 1), dim3(LOGDET_THREADS), 0, s, g->A, ld, (size_t)0, N1, Np, g->scal,
-                           (double*)nullptr, (const int*)nullptr, (unsigned long long*)nullptr, 0ull, 0ull);
-        HIPCHK(hipMemcpyAsync(g->host_res, g->scal, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(&g->host_res[2], g->info, sizeof(int), hipMemcpyDeviceToHost, s));
-    }
+    rc = append_rows_enqueue(g, N0, N1, Np_before);
+    if (rc) return rc;
     return update_finish(g, 0, logpdf_out);
 }
 
@@ -464,8 +506,8 @@ static int append_locked(boss_gp* g, int n, const double* X_new, const double* y
 // the caller AT THE NEW POINTS only.  k(x_i, x_j) depends on λ, α at x_i and x_j alone, and those of the old points stay resident
 // (lamX, ampX, noiseX): no entry between two old points changes, the new observations go to the end of the ordering, so the
 // leading block of the factor stays valid exactly as for a stationary kernel — the block rows that hold new observations are
-// rebuilt (append_locked's condition and sweep, the Gram tiles from gibbs_gram_kernel), or the grown arrays are factorised
-// again on the device where most of the matrix is new.  Nothing of the handle's data travels to the host.
+// rebuilt (append_rows_enqueue, the Gram tiles from gibbs_gram_kernel), or the grown arrays are factorised again on the device
+// where most of the matrix is new.  Nothing of the handle's data travels to the host.
 extern "C" int boss_ngp_append(boss_gp_t* g, int n_new, const double* X_new, const double* y_new, const double* lam_new,
                                const double* amp_new, const double* noise_new, const double* mean_new, double* logpdf_out) {
     if (!g || n_new < 1 || !X_new || !y_new || !lam_new || !amp_new || !noise_new) return fail(BOSS_E_INVALID, "NULL argument or n_new < 1");
@@ -484,73 +526,24 @@ extern "C" int boss_ngp_append(boss_gp_t* g, int n_new, const double* X_new, con
     }
     HIPCHK(hipSetDevice(c->device));
     std::lock_guard<std::mutex> lk(c->mtx);
-    int rc = gp_settle(g, "handle has no valid factorisation (its per-point hyper-parameters are the ones re-used)");
+    int rc = append_settle(g, "handle has no valid factorisation (its per-point hyper-parameters are the ones re-used)", mean_new);
     if (rc) return rc;
-    if (g->has_mean && !mean_new)
-        return fail(BOSS_E_INVALID, "the posterior has a prior mean: mean_new (its values at the new points) is required");
     if ((long long)g->N + n > MAX_ROWS) return fail(BOSS_E_INVALID, "more than 46080 observations are not supported");
     hipStream_t s = c->stream;
     const int N0 = g->N, N1 = N0 + n;
     const int Np_before = g->Np;
     rc = gp_grow(g, N1);
     if (rc) return rc;
-    g->fitted = false;
-    g->have_lt = false;
-    ++g->factor_gen;
-    g->have_dinv = false;
-    g->have_winv = false;
-    g->few_calls = 0;
-    g->append_path = 0;
-    {
-        std::vector<double> xb;
-        pack_points(xb, X_new, d, n, n, g->discrete.empty() ? nullptr : g->discrete.data());
-        const size_t pitch = sizeof(double) * g->Np, row = sizeof(double) * n;
-        HIPCHK(hipMemcpy2DAsync(g->Xraw + N0, pitch, xb.data(), row, row, d, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpy2DAsync(g->lamX + N0, pitch, lb.data(), row, row, d, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(g->ampX + N0, amp_new, row, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(g->noiseX + N0, noise_new, row, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(g->y + N0, y_new, row, hipMemcpyHostToDevice, s));
-        if (mean_new) {
-            HIPCHK(hipMemcpyAsync(g->mean + N0, mean_new, row, hipMemcpyHostToDevice, s));
-            g->has_mean = true;
-        }
-        HIPCHK(hipStreamSynchronize(s));       // staging buffers go out of scope
-    }
+    gp_invalidate_append(g, false);
+    const size_t pitch = sizeof(double) * g->Np, row = sizeof(double) * n;
+    HIPCHK(hipMemcpy2DAsync(g->lamX + N0, pitch, lb.data(), row, row, d, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(g->ampX + N0, amp_new, row, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(g->noiseX + N0, noise_new, row, hipMemcpyHostToDevice, s));
+    rc = append_upload(g, n, X_new, n, y_new, mean_new);     // (waits for the three copies above as well)
+    if (rc) return rc;
     g->N = N1;
-    // the block rows to (re)build and the switch to a plain re-factorisation: append_locked's
-    const int kb0 = N0 / BLK, kb1 = (g->Np != Np_before) ? g->nblk - 1 : (N1 - 1) / BLK;
-    if (kb1 - kb0 + 1 > 4 || kb1 - kb0 + 1 >= g->nblk) {
-        g->append_path = 2;
-        rc = factor_enqueue(g);
-        if (rc) return rc;
-    } else {
-        g->append_path = 1;
-        const int Np = g->Np, ld = g->ld;
-        dinv_join(g);
-        HIPCHK(hipMemsetAsync(g->info, 0, sizeof(int), s));
-        for (int kb = kb0; kb <= kb1; ++kb) {
-            hipLaunchKernelGGL(rhs_rows_kernel, dim3(1, 1, 1), dim3(BLK), 0, s, g->A, ld, (size_t)0, N1, Np, g->y, g->mean,
-                               (size_t)0, kb * BLK, (int*)nullptr);
-            // 128 rows × columns 0 … (kb+1)·128 − 1: the 4·kb + 3 tiles from triangular tile index kb (2 kb + 1), a full build's arithmetic
-            hipLaunchKernelGGL(gibbs_gram_kernel, dim3(4 * kb + 3, 1, 1), dim3(256), 0, s, (const double*)g->Xraw,
-                               (const double*)g->lamX, (const double*)g->ampX, (const double*)g->noiseX, (size_t)0, (size_t)0, d, N1,
-                               Np, g->A, ld, (size_t)0, kb * (2 * kb + 1));
-            for (int k = 0; k < kb; ++k) {
-                hipLaunchKernelGGL(potrf_trsm_kernel, dim3(8, 1, 1), dim3(TRSM_THREADS), 0, s, g->A, ld, (size_t)0, k, g->inv16, (size_t)0,
-                                   kb * BLK);
-                hipLaunchKernelGGL(potrf_rowupd_kernel, dim3(4 * (kb - k) + 1), dim3(256), 0, s, g->A, ld, k, kb, Np);
-            }
-            hipLaunchKernelGGL(potrf_diag_kernel, dim3(1, 1, 1), dim3(DIAG_THREADS), DIAG_LDS_BYTES, s, g->A, ld, (size_t)0, kb,
-                               g->inv16, (size_t)0, g->info, (unsigned long long*)nullptr, 0ull);
-            hipLaunchKernelGGL(potrf_trsm_kernel, dim3(1, 1, 1), dim3(TRSM_THREADS), 0, s, g->A, ld, (size_t)0, kb, g->inv16, (size_t)0,
-                               Np);
-        }
-        dinv_eager(g);
-        hipLaunchKernelGGL(potrf_logdet_kernel, dim3(1, 1, 1), dim3(LOGDET_THREADS), 0, s, g->A, ld, (size_t)0, N1, Np, g->scal,
-                           (double*)nullptr, (const int*)nullptr, (unsigned long long*)nullptr, 0ull, 0ull);
-        HIPCHK(hipMemcpyAsync(g->host_res, g->scal, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(&g->host_res[2], g->info, sizeof(int), hipMemcpyDeviceToHost, s));
-    }
+    rc = append_rows_enqueue(g, N0, N1, Np_before);
+    if (rc) return rc;
     return update_finish(g, 0, logpdf_out);
 }
 
@@ -558,8 +551,8 @@ extern "C" int boss_ngp_append(boss_gp_t* g, int n_new, const double* X_new, con
 // model.  X_new d×n_new, y_new n_new, dY_new d×n_new column-major.  The reference's ordering [y; ∂_1 y; …; ∂_d y] would put new rows
 // inside every block; the handle's own ordering (aug_row_decode, gram_kernels.hpp) puts the 1 + d rows of every appended point at
 // the end instead, a symmetric permutation the posterior does not see.  The leading block of the factor then survives, and the
-// append runs as the other models' does: the block rows that hold new rows are rebuilt (append_locked's condition and sweep, the
-// Gram tiles from aug_gram_kernel), or the grown arrays are factorised again on the device where most of the matrix is new.
+// append runs as the other models' does: the block rows that hold new rows are rebuilt (append_rows_enqueue, the Gram tiles
+// from aug_gram_kernel), or the grown arrays are factorised again on the device where most of the matrix is new.
 // Nothing of the handle's data travels to the host and the hyper-parameters staged on the device by the last update are the ones
 // used, verbatim.
 extern "C" int boss_ggp_append(boss_gp_t* g, int n_new, const double* X_new, const double* y_new, const double* dY_new, double* logpdf_out) {
@@ -572,68 +565,24 @@ extern "C" int boss_ggp_append(boss_gp_t* g, int n_new, const double* X_new, con
     std::lock_guard<std::mutex> lk(c->mtx);
     int rc = gp_settle(g, "handle has no valid factorisation (its hyper-parameters are the ones re-used)");
     if (rc) return rc;
-    hipStream_t s = c->stream;
     const int N0 = g->N, N1 = N0 + n * (1 + d), n0 = g->npts;
     const int Np_before = g->Np;
     rc = gp_grow(g, N1);                                     // (a member of a batch-fitted set leaves it here: gp_own)
     if (rc) return rc;
     rc = ggp_grow_points(g, n0 + n);
     if (rc) return rc;
-    g->fitted = false;
-    g->have_lt = false;
-    ++g->factor_gen;
-    g->have_dinv = false;
-    g->have_winv = false;
-    g->few_calls = 0;
-    g->append_path = 0;
-    {
-        std::vector<double> xb, yb((size_t)n * (1 + d));
-        pack_points(xb, X_new, d, n, n, nullptr);
-        for (int j = 0; j < n; ++j) {                        // the rows of an appended point: [y_j, ∂y_j/∂x_1 … ∂y_j/∂x_d]
-            yb[(size_t)j * (1 + d)] = y_new[j];
-            for (int l = 0; l < d; ++l) yb[(size_t)j * (1 + d) + 1 + l] = dY_new[(size_t)j * d + l];
-        }
-        HIPCHK(hipMemcpy2DAsync(g->Xraw + n0, sizeof(double) * g->ldx, xb.data(), sizeof(double) * n, sizeof(double) * n, d,
-                                hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(g->y + N0, yb.data(), sizeof(double) * yb.size(), hipMemcpyHostToDevice, s));
-        HIPCHK(hipStreamSynchronize(s));       // staging buffers go out of scope
+    gp_invalidate_append(g, false);
+    std::vector<double> yb((size_t)n * (1 + d));
+    for (int j = 0; j < n; ++j) {                            // the rows of an appended point: [y_j, ∂y_j/∂x_1 … ∂y_j/∂x_d]
+        yb[(size_t)j * (1 + d)] = y_new[j];
+        for (int l = 0; l < d; ++l) yb[(size_t)j * (1 + d) + 1 + l] = dY_new[(size_t)j * d + l];
     }
+    rc = append_upload(g, n, X_new, (int)yb.size(), yb.data(), nullptr);
+    if (rc) return rc;
     g->N = N1;
     g->npts = n0 + n;
-    // the block rows to (re)build and the switch to a plain re-factorisation: append_locked's
-    const int kb0 = N0 / BLK, kb1 = (g->Np != Np_before) ? g->nblk - 1 : (N1 - 1) / BLK;
-    if (kb1 - kb0 + 1 > 4 || kb1 - kb0 + 1 >= g->nblk) {
-        g->append_path = 2;
-        rc = factor_enqueue(g);
-        if (rc) return rc;
-    } else {
-        g->append_path = 1;
-        const int Np = g->Np, ld = g->ld;
-        dinv_join(g);
-        HIPCHK(hipMemsetAsync(g->info, 0, sizeof(int), s));
-        for (int kb = kb0; kb <= kb1; ++kb) {
-            hipLaunchKernelGGL(rhs_rows_kernel, dim3(1, 1, 1), dim3(BLK), 0, s, g->A, ld, (size_t)0, N1, Np, g->y, g->mean,
-                               (size_t)0, kb * BLK, (int*)nullptr);
-            // 128 rows × columns 0 … (kb+1)·128 − 1: the 4·kb + 3 tiles from triangular tile index kb (2 kb + 1), a full build's arithmetic
-            hipLaunchKernelGGL(aug_gram_kernel, dim3(4 * kb + 3, 1, 1), dim3(256), 0, s, (const double*)g->Xraw, g->ldx, d, g->nhead, N1,
-                               Np, g->kernel, (const double*)g->hyp, (const double*)g->invlam, (size_t)0, g->A, ld, (size_t)0,
-                               kb * (2 * kb + 1));
-            for (int k = 0; k < kb; ++k) {
-                hipLaunchKernelGGL(potrf_trsm_kernel, dim3(8, 1, 1), dim3(TRSM_THREADS), 0, s, g->A, ld, (size_t)0, k, g->inv16, (size_t)0,
-                                   kb * BLK);
-                hipLaunchKernelGGL(potrf_rowupd_kernel, dim3(4 * (kb - k) + 1), dim3(256), 0, s, g->A, ld, k, kb, Np);
-            }
-            hipLaunchKernelGGL(potrf_diag_kernel, dim3(1, 1, 1), dim3(DIAG_THREADS), DIAG_LDS_BYTES, s, g->A, ld, (size_t)0, kb,
-                               g->inv16, (size_t)0, g->info, (unsigned long long*)nullptr, 0ull);
-            hipLaunchKernelGGL(potrf_trsm_kernel, dim3(1, 1, 1), dim3(TRSM_THREADS), 0, s, g->A, ld, (size_t)0, kb, g->inv16, (size_t)0,
-                               Np);
-        }
-        dinv_eager(g);
-        hipLaunchKernelGGL(potrf_logdet_kernel, dim3(1, 1, 1), dim3(LOGDET_THREADS), 0, s, g->A, ld, (size_t)0, N1, Np, g->scal,
-                           (double*)nullptr, (const int*)nullptr, (unsigned long long*)nullptr, 0ull, 0ull);
-        HIPCHK(hipMemcpyAsync(g->host_res, g->scal, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(&g->host_res[2], g->info, sizeof(int), hipMemcpyDeviceToHost, s));
-    }
+    rc = append_rows_enqueue(g, N0, N1, Np_before);
+    if (rc) return rc;
     return update_finish(g, 0, logpdf_out);
 }
 

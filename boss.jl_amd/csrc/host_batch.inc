@@ -191,6 +191,12 @@ static int llgrad_sets_enqueue(Ctx* c, hipStream_t s, int nb, int group, int Np,
     return BOSS_OK;
 }
 
+// the matrices of one chunk of a batched likelihood stay below this many bytes: 12 GiB, or BOSS_MODEL_BATCH_CHUNK_MB=<MB> (tests)
+static size_t batch_chunk_bytes() {
+    static const double mb = getenv("BOSS_MODEL_BATCH_CHUNK_MB") ? atof(getenv("BOSS_MODEL_BATCH_CHUNK_MB")) : 12288.0;
+    return (size_t)(std::max(mb, 0.0) * 1048576.0);
+}
+
 // grad_out: null, or (d+2)×S — ∂logpdf/∂(λ_1..λ_d, α, σ) of every set (the factorisations run batched, the gradient passes set
 // after set on the shared workspaces).  mean (boss_gp_loglike_grad_batch_mean, with grad_out): the Jacobians of the prior means and
 // where ∂logpdf/∂mean_X (N×S) and its fold with them (T×S) go, host pointers; the Jacobians are staged per chunk as the means are,
@@ -223,8 +229,7 @@ static int loglike_batch_impl(int device, int kernel, int d, int N, const double
     const size_t bstride = (size_t)ld * Np;
     // chunk the batch so the matrices stay below ~12 GiB
     size_t per = bstride * sizeof(double);
-    static const double chunk_mb = getenv("BOSS_MODEL_BATCH_CHUNK_MB") ? atof(getenv("BOSS_MODEL_BATCH_CHUNK_MB")) : 12288.0;
-    int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)S, (size_t)(std::max(chunk_mb, 0.0) * 1048576.0) / per));
+    int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)S, batch_chunk_bytes() / per));
     const size_t xs_bstride = (size_t)d * Np;
     // the gradient through the prior mean: T columns folded on the device (0: none), per set N values of a and T of the fold
     const int T = (mean && mean->dtheta_out) ? mean->T : 0;
@@ -478,9 +483,7 @@ static int model_loglike_batch_run(Ctx* c, int N, int Np, int S, const std::vect
     hipStream_t s = c->stream;
     const int nblk = Np / BLK, ld = Np + RHS_ROWS;
     const size_t bstride = (size_t)ld * Np, per = bstride * sizeof(double);
-    static const double chunk_mb = getenv("BOSS_MODEL_BATCH_CHUNK_MB") ? atof(getenv("BOSS_MODEL_BATCH_CHUNK_MB")) : 12288.0;
-    const size_t limit = (size_t)(std::max(chunk_mb, 0.0) * 1048576.0);
-    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)S, limit / per));
+    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)S, batch_chunk_bytes() / per));
     const size_t inv16_b = (size_t)nblk * 8 * 256, mean_doubles = mean_X ? (mean_stride == 0 ? (size_t)Np : (size_t)Np * chunk) : 0;
     int rc = ws_reserve(c->batchA, per * chunk);
     if (rc) return rc;

@@ -820,7 +820,7 @@ static bool small_fit_ok(const Ctx* c, int N, int d) {
 }
 
 // What a new factorisation of the handle's data under new hyper-parameters makes stale (every model's update).  The appends
-// (gp_grow, append_locked) keep part of it on purpose — have_winv survives a rank-one append — and clear their own lists.
+// keep part of it on purpose — the epoch, and have_winv over a rank-one append — and clear their own list (gp_invalidate_append).
 static void gp_invalidate(boss_gp* g) {
     g->fitted = false;
     g->have_dinv = false;
@@ -830,6 +830,19 @@ static void gp_invalidate(boss_gp* g) {
     g->fell_back = false;
     ++g->epoch;
     g->append_calls = 0;
+}
+// What new observations under unchanged hyper-parameters make stale (every model's append).  keep_inverses: a rank-one append
+// patches the resident inverse factors itself.
+static void gp_invalidate_append(boss_gp* g, bool keep_inverses) {
+    g->fitted = false;
+    g->have_lt = false;
+    ++g->factor_gen;                                         // every append changes the factor: a block 0 of Dinv built on its own before it is stale
+    if (!keep_inverses) {
+        g->have_dinv = false;
+        g->have_winv = false;
+        g->few_calls = 0;
+    }
+    g->append_path = 0;
 }
 
 // A pending update is finished (its error is the caller's), then the handle must hold a valid factorisation.  Caller holds the

@@ -137,6 +137,21 @@ static int invgemm_max_tiles() {
     static const int v = getenv("BOSS_INVGEMM_MAX_TILES") ? atoi(getenv("BOSS_INVGEMM_MAX_TILES")) : 128;
     return v;
 }
+// the few-candidates paths (prediction, its gradient, the arg-max rounds of host_prune.inc): BOSS_NO_FEW=1 switches them off,
+// BOSS_FEW_MAX_TILES is the number of candidate tiles (of 32) up to which they are taken
+static bool few_off() {
+    static const bool v = getenv("BOSS_NO_FEW") && atoi(getenv("BOSS_NO_FEW"));
+    return v;
+}
+static int few_max_tiles() {
+    static const int v = getenv("BOSS_FEW_MAX_TILES") ? atoi(getenv("BOSS_FEW_MAX_TILES")) : 128;
+    return v;
+}
+// BOSS_NO_SET_PREDICT=1: calls over several posteriors go member by member, never through the set launches
+static bool set_predict_off() {
+    static const bool v = getenv("BOSS_NO_SET_PREDICT") && atoi(getenv("BOSS_NO_SET_PREDICT"));
+    return v;
+}
 
 // width of the V slabs predict_enqueue leaves (and the covariances read): 64 candidates per workgroup once that still fills the
 // machine (BOSS_FORCE_BN64=1: tests); the gradient pass (adjoint substitution) runs on 32-candidate slabs
@@ -242,11 +257,9 @@ static int predict_enqueue(boss_gp* g, const boss_cand* cd, const double* mean_s
 #else
     constexpr int dbg = 0;
 #endif
-    static const bool no_few = getenv("BOSS_NO_FEW") && atoi(getenv("BOSS_NO_FEW"));
-    static const int few_max_tiles = getenv("BOSS_FEW_MAX_TILES") ? atoi(getenv("BOSS_FEW_MAX_TILES")) : 128;
     const int ftiles = (cd->M + 31) / 32;
     const size_t aug_lds = sizeof(double) * ((size_t)g->d * (64 + 256) + g->d);
-    if (ftiles <= few_max_tiles && g->Np >= 4 * PRED_RB && g->d <= 64 && !no_few && (BN == 32 || for_grad)) {
+    if (ftiles <= few_max_tiles() && g->Np >= 4 * PRED_RB && g->d <= 64 && !few_off() && (BN == 32 || for_grad)) {
         // few candidates (the fused kernel would occupy `ftiles` of 256 CUs for its whole latency):
         // right-looking substitution, every 256-row step spread over the chip
         typedef PredG32 G;
@@ -264,9 +277,8 @@ static int predict_enqueue(boss_gp* g, const boss_cand* cd, const double* mean_s
         // repeated calls with few candidates on one factorisation: from the second call on both inverse factors are
         // resident — one to four candidates take a single pass over L⁻ᵀ (winv_gemv_kernel), more take two GEMMs
         // without sequential steps (inv_fwd_kernel / inv_bwd_kernel)
-        static const int winv_after = getenv("BOSS_WINV_AFTER") ? atoi(getenv("BOSS_WINV_AFTER")) : 2;
         const size_t winv_lds = sizeof(double) * (size_t)g->Np * (cd->M == 1 ? 1 : cd->M == 2 ? 2 : WINV_MAX_M);   // K* staged in LDS
-        if (winv_after > 0 && !g->have_winv && !internal && ++g->few_calls >= winv_after) {
+        if (winv_after() > 0 && !g->have_winv && !internal && ++g->few_calls >= winv_after()) {
             const size_t bytes = sizeof(double) * (size_t)g->ld * g->Np;
             bool ok = (g->Winv != nullptr || dev_malloc((void**)&g->Winv, bytes) == hipSuccess) &&
                       (g->Linv != nullptr || dev_malloc((void**)&g->Linv, bytes) == hipSuccess);
@@ -588,9 +600,8 @@ extern "C" int boss_gp_predict(boss_gp_t* g, int M, const double* Xs, const doub
     std::lock_guard<std::mutex> lk(c->mtx);                 // the per-device scratch areas are shared
     {
         // one to four candidates on resident inverse factors: candidates in the kernel arguments, results polled in mapped memory
-        static const bool args_off = getenv("BOSS_NO_FEW_ARGS") && atoi(getenv("BOSS_NO_FEW_ARGS"));
         const size_t winv_lds = sizeof(double) * (size_t)g->Np * (M == 1 ? 1 : M == 2 ? 2 : WINV_MAX_M);
-        if (!args_off && M <= WINV_MAX_M && g->have_winv && !g->pending && !g->aug && !g->gibbs && g->d <= FEW_ARGS_MAX_D && !c->prof_on &&
+        if (!few_args_off() && M <= WINV_MAX_M && g->have_winv && !g->pending && !g->aug && !g->gibbs && g->d <= FEW_ARGS_MAX_D && !c->prof_on &&
             winv_lds <= 144 * 1024 && g->N > SMALL_MAX_N) {
             hipStream_t s = c->stream;
             const int nwg = g->Np / WINV_ROWS;
@@ -879,8 +890,7 @@ static int ngp_predict_set_call(int n, boss_gp_t* const* gps, int M, const doubl
     }
     if (mean_Xs) (void)hipMemcpyAsync(dmean, mean_Xs, sizeof(double) * nm, hipMemcpyHostToDevice, s);
     (void)hipMemsetAsync(dbad, 0xff, sizeof(unsigned long long), s);
-    static const bool set_off = getenv("BOSS_NO_SET_PREDICT") && atoi(getenv("BOSS_NO_SET_PREDICT"));
-    if (!set_off && predict_set_ok(n, gps, &cd, true)) {
+    if (!set_predict_off() && predict_set_ok(n, gps, &cd, true)) {
         rc = predict_set_enqueue(n, gps, &cd, mean_Xs ? dmean : nullptr, dmu, dvar, (size_t)M, clam, camp);
         if (rc) return drain(c, rc);
     } else {
@@ -964,16 +974,14 @@ static int grad_enqueue(boss_gp* g, const boss_cand* cd, const double* mean_s_de
     typedef PredG32 G;
     const int tiles = (M + 31) / 32;
     double* slabs = (double*)c->vscratch.p;
-    static const bool no_few = getenv("BOSS_NO_FEW") && atoi(getenv("BOSS_NO_FEW"));
-    static const int few_max_tiles = getenv("BOSS_FEW_MAX_TILES") ? atoi(getenv("BOSS_FEW_MAX_TILES")) : 128;
-    if (tiles <= few_max_tiles && tiles <= invgemm_max_tiles() && Np >= 4 * PRED_RB && !no_few && g->have_winv) {
+    if (tiles <= few_max_tiles() && tiles <= invgemm_max_tiles() && Np >= 4 * PRED_RB && !few_off() && g->have_winv) {
         // both inverse factors are resident (repeated calls on this factorisation): W = L⁻ᵀV as one GEMM
         typedef GemmDirect<4, 1, 2, 2, 8> GU;
         double* Wsl = slabs + (size_t)tiles * 32 * Np;
         hipLaunchKernelGGL(inv_bwd_kernel<GU>, dim3(tiles, Np / BLK), dim3(GU::NTHREADS), 0, s, (const double*)g->Winv, g->ld, Np,
                            (const double*)slabs, Wsl);
         slabs = Wsl;
-    } else if (tiles <= few_max_tiles && Np >= 4 * PRED_RB && !no_few) {
+    } else if (tiles <= few_max_tiles() && Np >= 4 * PRED_RB && !few_off()) {
         // few candidates: the adjoint substitution step by step across the chip (see few_back_* kernels)
         typedef GemmDirect<4, 1, 2, 2, 8> GU;
         for (int ib = Np / PRED_RB - 1; ib >= 0; --ib) {
@@ -1441,9 +1449,8 @@ static int acq_ei_grad_set_impl(int P, int S, boss_gp_t* const* gps, int M, cons
     if (mean_grad) (void)hipMemcpyAsync(dmg, mean_grad, sizeof(double) * ndm, hipMemcpyHostToDevice, s);
     if (valid_mask) (void)hipMemcpyAsync(dmask, valid_mask, M, hipMemcpyHostToDevice, s);
     if (par.mode != 0) {
-        static const bool set_off = getenv("BOSS_NO_SET_PREDICT") && atoi(getenv("BOSS_NO_SET_PREDICT"));
         bool done = false;
-        if (!set_off && grad_set_ok(n, gps, &cd)) {
+        if (!set_predict_off() && grad_set_ok(n, gps, &cd)) {
             rc = grad_set_enqueue(n, gps, &cd, mean_Xs ? dmean : nullptr, mean_grad ? dmg : nullptr, dmu, dvar, dgm, dgv);
             if (rc != BOSS_OK && rc != BOSS_E_ALLOC) return drain(c, rc);
             done = rc == BOSS_OK;                            // (no memory for the set launches: the call goes on member by member)
@@ -1583,9 +1590,8 @@ static int ngp_grad_set_call(int n, boss_gp_t* const* gps, int M, const double* 
     if (ei && ei->valid_mask) (void)hipMemcpyAsync(dmask, ei->valid_mask, M, hipMemcpyHostToDevice, s);
     if (!ei) (void)hipMemsetAsync(dbad, 0xff, sizeof(unsigned long long), s);
     if (!ei || par.mode != 0) {
-        static const bool set_off = getenv("BOSS_NO_SET_PREDICT") && atoi(getenv("BOSS_NO_SET_PREDICT"));
         bool done = false;
-        if (!set_off && ngp_grad_set_ok(n, gps, &cd)) {
+        if (!set_predict_off() && ngp_grad_set_ok(n, gps, &cd)) {
             rc = grad_set_enqueue(n, gps, &cd, mean_Xs ? dmean : nullptr, mean_grad ? dmg : nullptr, dmu_, dvar_, dgm, dgv, clam, camp,
                                   has_jl ? djl : nullptr, has_ja ? dja : nullptr);
             if (rc != BOSS_OK && rc != BOSS_E_ALLOC) return drain(c, rc);

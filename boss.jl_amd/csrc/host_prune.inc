@@ -82,22 +82,16 @@ extern "C" int boss_debug_acq_prune_bounds(int device, int M, double* mua_out, d
     return BOSS_OK;
 }
 
-// predict_enqueue's limit of its few-candidates branch, in tiles of 32: the rounds must stay below it
-static int prune_few_max_tiles() {
-    static const int few_max_tiles = getenv("BOSS_FEW_MAX_TILES") ? atoi(getenv("BOSS_FEW_MAX_TILES")) : 128;
-    return few_max_tiles;
-}
 // may this call take the pruned path?  (everything else keeps the full kernel: see the conditions in DESIGN.md §4.5)
 static bool prune_eligible(const boss_gp* g, const boss_cand* cd, int P, int S, const EiPar& par, bool has_out, bool defer, bool has_mc,
                            const double* dpair) {
     if (!prune_enabled() || has_out || defer || dpair || has_mc || P != 1 || S != 1 || par.mode != 1) return false;
     if (g->aug || g->gibbs || g->ctx->prof_on) return false;
-    static const bool no_few = getenv("BOSS_NO_FEW") && atoi(getenv("BOSS_NO_FEW"));
-    const int ftiles = (cd->M + 31) / 32, few_max_tiles = prune_few_max_tiles();
-    const int min_tiles = g_prune.min_tiles >= 0 ? g_prune.min_tiles : few_max_tiles;
-    if (no_few || ftiles <= min_tiles || g->Np < 4 * PRED_RB || g->d > 64 || cd->d != g->d || slab_bn(cd->M, false) != 32) return false;
+    const int ftiles = (cd->M + 31) / 32;                    // (few_max_tiles: predict_enqueue's limit of its few-candidates branch — the rounds must stay below it)
+    const int min_tiles = g_prune.min_tiles >= 0 ? g_prune.min_tiles : few_max_tiles();
+    if (few_off() || ftiles <= min_tiles || g->Np < 4 * PRED_RB || g->d > 64 || cd->d != g->d || slab_bn(cd->M, false) != 32) return false;
     if (small_predict_ok(g, cd->M) || cd->M <= g_prune.K || cd->M > PRUNE_THREADS * PRUNE_CPT_MAX) return false;
-    if (g_prune.K > 32 * few_max_tiles) return false;         // (round 1 would not reach the few-candidates branch)
+    if (g_prune.K > 32 * few_max_tiles()) return false;       // (round 1 would not reach the few-candidates branch)
     return g_prune.s < g->Np / PRED_RB;
 }
 
@@ -170,7 +164,7 @@ static int acq_prune_try(boss_gp* g, const boss_cand* cd, const double* mean_dev
     }
     const int M = cd->M, Mp = cd->Mp, d = g->d, Np = g->Np, nch = Np / PRUNE_MU_ROWS, sblk = g_prune.s, K = g_prune.K;
     // (a round 2 beyond the few-candidates limit would run the fused kernel on the internal block: the full kernel answers instead)
-    const int cap = std::min(g_prune.cap, 32 * prune_few_max_tiles()), tiles = (M + 31) / 32;
+    const int cap = std::min(g_prune.cap, 32 * few_max_tiles()), tiles = (M + 31) / 32;
     const size_t nint = (size_t)round_up(std::max(K, cap), 64);            // columns of the internal candidate block
     // doubles: μ_a | σ²_s | ub | keys | part [nch][M] | μ, σ², m of the internal block | its coordinates [d][nint] | (T, index)
     const size_t nd = (size_t)4 * M + (size_t)nch * M + 3 * nint + (size_t)d * nint + 2;

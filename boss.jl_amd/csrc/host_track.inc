@@ -55,50 +55,82 @@ static int track_rebuild(boss_track* t, const boss_cand* cd) {
     return BOSS_OK;
 }
 
+// A track of any model's posterior at `cand` (the entry points below have checked their arguments).  A pending update is finished
+// under the lock; every failure after the track exists goes through one clean-up.  A nonstationary posterior takes λ(x*), α(x*)
+// from lam [d][Mp] / amp [Mp], or has its latent models write them into the same buffers (lat): the track keeps them and the
+// rounded raw candidates, so gibbs_track_append_kernel can form k_Gibbs(x_r, x*) for every appended row.
+static int track_create(boss_gp* g, const boss_cand* cand, const double* lam, const double* amp, const boss_nlat_t* lat,
+                        const double* mean_Xs, boss_track_t** out) {
+    Ctx* c = g->ctx;
+    HIPCHK(hipSetDevice(c->device));
+    std::lock_guard<std::mutex> lk(c->mtx);
+    int rc = gp_settle(g);
+    if (rc) return rc;
+    hipStream_t s = c->stream;
+    const int d = g->d, M = cand->M, Mp = cand->Mp;
+    boss_track* t = new boss_track();
+    t->ctx = c;
+    t->gp = g;
+    t->aug = g->aug;
+    t->gibbs = g->gibbs;
+    t->d = d;
+    t->M = M;
+    t->Mp = Mp;
+    t->tiles = (M + 31) / 32;
+    auto bail = [&](int code) {
+        (void)hipStreamSynchronize(s);
+        (void)hipGetLastError();
+        track_release(t);
+        return code;
+    };
+    auto bail_hip = [&](hipError_t e) { return bail(fail(BOSS_E_NO_DEVICE, hipGetErrorString(e))); };
+    if (dev_malloc((void**)&t->Csc, sizeof(double) * (size_t)d * Mp) != hipSuccess ||
+        (t->gibbs && (dev_malloc((void**)&t->Clam, sizeof(double) * (size_t)d * Mp) != hipSuccess ||
+                      dev_malloc((void**)&t->Camp, sizeof(double) * ((size_t)Mp + 1)) != hipSuccess)) ||
+        dev_malloc((void**)&t->mu, sizeof(double) * M) != hipSuccess ||
+        dev_malloc((void**)&t->var, sizeof(double) * M) != hipSuccess ||
+        dev_malloc((void**)&t->mean, sizeof(double) * M) != hipSuccess)
+        return bail(fail(BOSS_E_ALLOC, "device allocation failed"));
+    hipError_t e = hipSuccess;
+    if (t->gibbs) {
+        hipLaunchKernelGGL(round_cand_kernel, dim3((Mp + 255) / 256), dim3(256), 0, s, (const double*)cand->Craw, t->Csc,
+                           (const unsigned char*)g->discrete_dev, d, Mp);
+        if (lat) {
+            boss_nlat_t* one = const_cast<boss_nlat_t*>(lat);
+            unsigned long long* dbad = (unsigned long long*)(t->Camp + Mp);
+            rc = nlat_enqueue(c, 1, &one, t->Csc, Mp, M, t->Clam, 0, t->Camp, 0, nullptr, 0, nullptr, 0, nullptr, dbad);
+            if (rc == BOSS_OK) rc = nlat_check(c, dbad, nullptr);
+            if (rc) return bail(rc);
+        } else {
+            e = hipMemcpyAsync(t->Clam, lam, sizeof(double) * (size_t)d * Mp, hipMemcpyHostToDevice, s);
+            if (e == hipSuccess) e = hipMemcpyAsync(t->Camp, amp, sizeof(double) * Mp, hipMemcpyHostToDevice, s);
+        }
+    }
+    if (mean_Xs && e == hipSuccess) {
+        e = hipMemcpyAsync(t->mean, mean_Xs, sizeof(double) * M, hipMemcpyHostToDevice, s);
+        t->has_mean = true;
+    }
+    if ((t->gibbs || mean_Xs) && e == hipSuccess) e = hipStreamSynchronize(s);   // the caller's arrays may go
+    if (e != hipSuccess) return bail_hip(e);
+    rc = track_rebuild(t, cand);
+    if (rc) return bail(rc);
+    e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return bail_hip(e);
+    *out = t;
+    return BOSS_OK;
+}
+
 extern "C" int boss_track_create(boss_gp_t* g, const boss_cand_t* cand, const double* mean_Xs, boss_track_t** out) {
     if (!out) return fail(BOSS_E_INVALID, "out is NULL");
     *out = nullptr;
     if (!g || !cand) return fail(BOSS_E_INVALID, "NULL argument");
     NOT_FOR_AUG(g);
-    if (!g->fitted) return fail(BOSS_E_NOT_FITTED, "handle has no valid factorisation");
     if (cand->ctx != g->ctx || cand->d != g->d) return fail(BOSS_E_INVALID, "candidates and posterior must share device and x_dim");
-    Ctx* c = g->ctx;
-    HIPCHK(hipSetDevice(c->device));
-    std::lock_guard<std::mutex> lk(c->mtx);
-    boss_track* t = new boss_track();
-    t->ctx = c;
-    t->gp = g;
-    t->d = g->d;
-    t->M = cand->M;
-    t->Mp = cand->Mp;
-    t->tiles = (cand->M + 31) / 32;
-    if (dev_malloc((void**)&t->Csc, sizeof(double) * (size_t)t->d * t->Mp) != hipSuccess ||
-        dev_malloc((void**)&t->mu, sizeof(double) * t->M) != hipSuccess ||
-        dev_malloc((void**)&t->var, sizeof(double) * t->M) != hipSuccess ||
-        dev_malloc((void**)&t->mean, sizeof(double) * t->M) != hipSuccess) {
-        (void)hipGetLastError();
-        track_release(t);
-        return fail(BOSS_E_ALLOC, "device allocation failed");
-    }
-    if (mean_Xs) {
-        HIPCHK(hipMemcpyAsync(t->mean, mean_Xs, sizeof(double) * t->M, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        t->has_mean = true;
-    }
-    int rc = track_rebuild(t, cand);
-    if (rc) {
-        (void)hipStreamSynchronize(c->stream);
-        track_release(t);
-        return rc;
-    }
-    HIPCHK(hipStreamSynchronize(c->stream));
-    *out = t;
-    return BOSS_OK;
+    return track_create(g, cand, nullptr, nullptr, nullptr, mean_Xs, out);
 }
 
 // Tracked candidates of a nonstationary posterior: the prediction runs once through the nonstationary path (unclipped moments);
-// the track keeps the V slabs, μ, σ², the rounded raw candidates and λ(x*), α(x*) — from the caller's arrays, or written by the
-// latent kernel into the same buffers (lat) — so gibbs_track_append_kernel can form k_Gibbs(x_r, x*) for every appended row.
+// λ(x*), α(x*) come from the caller's arrays, checked and padded here, or from the latent models on the device (lat).
 constexpr int NGP_TRACK_MAX_D = 16;
 static int ngp_track_create(boss_gp_t* g, const boss_cand_t* cand, const double* lam_Xs, const double* amp_Xs, const boss_nlat_t* lat,
                             const double* mean_Xs, boss_track_t** out) {
@@ -124,62 +156,7 @@ static int ngp_track_create(boss_gp_t* g, const boss_cand_t* cand, const double*
             amp[j] = amp_Xs[j];
         }
     }
-    Ctx* c = g->ctx;
-    HIPCHK(hipSetDevice(c->device));
-    std::lock_guard<std::mutex> lk(c->mtx);
-    int rc = gp_settle(g);
-    if (rc) return rc;
-    hipStream_t s = c->stream;
-    boss_track* t = new boss_track();
-    t->ctx = c;
-    t->gp = g;
-    t->gibbs = true;
-    t->d = d;
-    t->M = M;
-    t->Mp = Mp;
-    t->tiles = (M + 31) / 32;
-    if (dev_malloc((void**)&t->Csc, sizeof(double) * (size_t)d * Mp) != hipSuccess ||
-        dev_malloc((void**)&t->Clam, sizeof(double) * (size_t)d * Mp) != hipSuccess ||
-        dev_malloc((void**)&t->Camp, sizeof(double) * ((size_t)Mp + 1)) != hipSuccess ||
-        dev_malloc((void**)&t->mu, sizeof(double) * M) != hipSuccess ||
-        dev_malloc((void**)&t->var, sizeof(double) * M) != hipSuccess ||
-        dev_malloc((void**)&t->mean, sizeof(double) * M) != hipSuccess) {
-        (void)hipGetLastError();
-        track_release(t);
-        return fail(BOSS_E_ALLOC, "device allocation failed");
-    }
-    auto bail = [&](int code) {
-        (void)hipStreamSynchronize(s);
-        (void)hipGetLastError();
-        track_release(t);
-        return code;
-    };
-    hipLaunchKernelGGL(round_cand_kernel, dim3((Mp + 255) / 256), dim3(256), 0, s, (const double*)cand->Craw, t->Csc,
-                       (const unsigned char*)g->discrete_dev, d, Mp);
-    if (lat) {
-        boss_nlat_t* one = const_cast<boss_nlat_t*>(lat);
-        unsigned long long* dbad = (unsigned long long*)(t->Camp + Mp);
-        rc = nlat_enqueue(c, 1, &one, t->Csc, Mp, M, t->Clam, 0, t->Camp, 0, nullptr, 0, nullptr, 0, nullptr, dbad);
-        if (rc == BOSS_OK) rc = nlat_check(c, dbad, nullptr);
-        if (rc) return bail(rc);
-    } else {
-        hipError_t e = hipMemcpyAsync(t->Clam, lam.data(), sizeof(double) * (size_t)d * Mp, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(t->Camp, amp.data(), sizeof(double) * Mp, hipMemcpyHostToDevice, s);
-        if (e != hipSuccess) return bail(fail(BOSS_E_NO_DEVICE, hipGetErrorString(e)));
-    }
-    if (mean_Xs) {
-        hipError_t e = hipMemcpyAsync(t->mean, mean_Xs, sizeof(double) * M, hipMemcpyHostToDevice, s);
-        if (e != hipSuccess) return bail(fail(BOSS_E_NO_DEVICE, hipGetErrorString(e)));
-        t->has_mean = true;
-    }
-    hipError_t e = hipStreamSynchronize(s);                  // the staging vectors and the caller's mean may go
-    if (e != hipSuccess) return bail(fail(BOSS_E_NO_DEVICE, hipGetErrorString(e)));
-    rc = track_rebuild(t, cand);
-    if (rc) return bail(rc);
-    e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return bail(fail(BOSS_E_NO_DEVICE, hipGetErrorString(e)));
-    *out = t;
-    return BOSS_OK;
+    return track_create(g, cand, lam.data(), amp.data(), lat, mean_Xs, out);
 }
 extern "C" int boss_ngp_track_create(boss_gp_t* g, const boss_cand_t* cand, const double* lam_Xs, const double* amp_Xs,
                                      const double* mean_Xs, boss_track_t** out) {
@@ -204,37 +181,7 @@ extern "C" int boss_ggp_track_create(boss_gp_t* g, const boss_cand_t* cand, boss
     if (!g || !cand) return fail(BOSS_E_INVALID, "NULL argument");
     if (!g->aug) return fail(BOSS_E_INVALID, "handle was not created by boss_ggp_create");
     if (cand->ctx != g->ctx || cand->d != g->d) return fail(BOSS_E_INVALID, "candidates and posterior must share device and x_dim");
-    Ctx* c = g->ctx;
-    HIPCHK(hipSetDevice(c->device));
-    std::lock_guard<std::mutex> lk(c->mtx);
-    int rc = gp_settle(g);
-    if (rc) return rc;
-    boss_track* t = new boss_track();
-    t->ctx = c;
-    t->gp = g;
-    t->aug = true;
-    t->d = g->d;
-    t->M = cand->M;
-    t->Mp = cand->Mp;
-    t->tiles = (cand->M + 31) / 32;
-    if (dev_malloc((void**)&t->Csc, sizeof(double) * (size_t)t->d * t->Mp) != hipSuccess ||
-        dev_malloc((void**)&t->mu, sizeof(double) * t->M) != hipSuccess ||
-        dev_malloc((void**)&t->var, sizeof(double) * t->M) != hipSuccess ||
-        dev_malloc((void**)&t->mean, sizeof(double) * t->M) != hipSuccess) {
-        (void)hipGetLastError();
-        track_release(t);
-        return fail(BOSS_E_ALLOC, "device allocation failed");
-    }
-    rc = track_rebuild(t, cand);
-    hipError_t e = hipStreamSynchronize(c->stream);
-    if (rc == BOSS_OK && e != hipSuccess) rc = fail(BOSS_E_NO_DEVICE, hipGetErrorString(e));
-    if (rc) {
-        (void)hipGetLastError();
-        track_release(t);
-        return rc;
-    }
-    *out = t;
-    return BOSS_OK;
+    return track_create(g, cand, nullptr, nullptr, nullptr, nullptr, out);
 }
 
 extern "C" void boss_track_free(boss_track_t* t) {

@@ -397,7 +397,7 @@ static int warp_call(const boss_warp_t* w, int P, int S, boss_gp_t* const* gps, 
     if (mean_Xs) (void)hipMemcpyAsync(dmean, mean_Xs, sizeof(double) * nm, hipMemcpyHostToDevice, s);
     if (mean_grad && grad) (void)hipMemcpyAsync(dmg, mean_grad, sizeof(double) * gi, hipMemcpyHostToDevice, s);
     if (par.mode != 0) {
-        static const bool set_off = getenv("BOSS_NO_SET_PREDICT") && atoi(getenv("BOSS_NO_SET_PREDICT"));
+        const bool set_off = set_predict_off();
         const double* mean_all = mean_Xs ? dmean : nullptr;
         const double* mg_all = mean_grad && grad ? dmg : nullptr;
         bool done = false;
