@@ -16,6 +16,8 @@ from .fitness import DeviceFitness  # noqa: F401,E402
 from .api import FitnessProgram, acq_ei_mc, acq_ei_mc_grad, acq_ei_mc_grad_moments, acq_ei_mc_moments  # noqa: F401,E402
 from .mean import DeviceMean, trace_mean  # noqa: F401,E402
 from .api import MeanProgram  # noqa: F401,E402
+from .kernel import DeviceKernel, trace_kernel  # noqa: F401,E402
+from .api import KernelGP, KernelProgram  # noqa: F401,E402
 from .model import HipGaussianProcess, HipGPParams, average_mean  # noqa: F401,E402
 from .api import WarpProgram  # noqa: F401,E402
 from .transformed import (DeviceInputTransform, DeviceOutputTransform, DeviceSlicedOutputTransform,  # noqa: F401,E402

@@ -147,6 +147,10 @@ SIGNATURES = {
     "boss_mean_free": (None, [C.c_void_p]),
     "boss_mean_eval_host": (C.c_int, [C.c_void_p, C.c_int, _c_dp, C.c_int, _c_dp, C.c_int, _c_dp, _c_dp, _c_dp]),
     "boss_mean_eval": (C.c_int, [C.c_int, C.c_void_p, C.c_int, _c_dp, C.c_int, _c_dp, C.c_int, _c_dp, _c_dp, _c_dp]),
+    "boss_kern_create": (C.c_int, [C.c_int, C.c_int, _c_dp, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p)]),
+    "boss_kern_free": (None, [C.c_void_p]),
+    "boss_kern_eval_host": (C.c_int, [C.c_void_p, C.c_int, _c_dp, _c_dp, _c_dp]),
+    "boss_kgp_create": (C.c_int, [C.c_int, C.c_int, C.c_int, _c_dp, _c_dp, _c_ucp, C.c_void_p, C.POINTER(C.c_void_p)]),
     "boss_warp_create": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
     "boss_warp_free": (None, [C.c_void_p]),
     "boss_warp_apply_host": (C.c_int, [C.c_void_p, C.c_int, _c_dp, _c_dp, _c_dp]),
@@ -1871,6 +1875,81 @@ class FitnessProgram:
             self.close()
         except Exception:
             pass
+
+
+# ---------------------------------------------------------------- kernel programs: a user-defined covariance function
+KERN_MAX_DIM = 16                                                    # two points of up to 16 dimensions: 32 inputs
+
+
+class KernelProgram:
+    """A covariance function (u, v) -> k as a straight-line program (boss_kern_t): the layout of a FitnessProgram over 2·d inputs,
+    u[0..d) first, then v[0..d).  Creating one needs no device.  eval is the vectorised numpy interpreter, eval_host runs the
+    library's own interpreter (the function the kernels call) on the host."""
+
+    def __init__(self, d: int, consts, code, out_id: int):
+        self.d = int(d)
+        self.consts = np.ascontiguousarray(np.asarray(consts, dtype=np.float64).reshape(-1))
+        self.code = np.ascontiguousarray(np.asarray(code, dtype=np.intc).reshape(-1, 3))
+        self.out_id = int(out_id)
+        self._h = C.c_void_p()
+        _check(load_library().boss_kern_create(self.d, self.consts.shape[0], _dp(self.consts), self.code.shape[0],
+                                               self.code.ctypes.data_as(C.POINTER(C.c_int)), self.out_id, C.byref(self._h)))
+        self._interp = FitnessProgram._interpreter(2 * self.d, self.consts, self.code, self.out_id)
+
+    def _pairs(self, U, V):
+        U, V = np.asarray(U, dtype=np.float64), np.asarray(V, dtype=np.float64)
+        one = U.ndim == 1
+        U, V = U.reshape(self.d, -1), V.reshape(self.d, -1)
+        if U.shape != V.shape:
+            raise ValueError("U and V must hold the same number of points")
+        return U, V, one
+
+    def eval(self, U, V):
+        """k(U[:, j], V[:, j]) for every column j (d×n each, or two points of length d)."""
+        U, V, one = self._pairs(U, V)
+        k = self._interp.eval(np.vstack([U, V]))
+        return float(k[0]) if one else k
+
+    def eval_host(self, U, V):
+        """The same through boss_kern_eval_host."""
+        U, V, one = self._pairs(U, V)
+        Uf, Vf = np.asfortranarray(U), np.asfortranarray(V)
+        k = np.zeros(Uf.shape[1])
+        _check(load_library().boss_kern_eval_host(self._h, Uf.shape[1], _dp(Uf), _dp(Vf), _dp(k)))
+        return float(k[0]) if one else k
+
+    def close(self):
+        if self._h:
+            load_library().boss_kern_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class KernelGP(GP):
+    """One output slice's posterior under a KernelProgram (boss_kgp_create): update, sync, predict, set_y, factor and acq_ei work as
+    for a GP; every other call of the base class is refused by the library (BOSS_E_INVALID, "program-kernel posteriors")."""
+
+    def __init__(self, X, y, kern: KernelProgram, discrete=None, device: int = 0):
+        lib = load_library()
+        X = _f64(X, 2)
+        y = _f64(np.asarray(y).reshape(-1), 1)
+        self.d, self.N = X.shape
+        if y.shape[0] != self.N:
+            raise ValueError("y must have one entry per column of X")
+        if not isinstance(kern, KernelProgram):
+            raise TypeError("kern must be a KernelProgram")
+        self.device = device
+        self.kernel = kern
+        disc = None if discrete is None else np.ascontiguousarray(np.asarray(discrete, dtype=bool).astype(np.uint8))
+        h = C.c_void_p()
+        _check(lib.boss_kgp_create(device, self.d, self.N, _dp(X), _dp(y), _ucp(disc), kern._h, C.byref(h)))
+        self._h = h
+        self.logpdf = None
 
 
 def _mc_common(fit: FitnessProgram, eps, y_max, valid_mask):

@@ -30,6 +30,7 @@
 #include "mean_program.hpp"
 #include "warp_kernels.hpp"
 #include "prune_kernels.hpp"
+#include "kprog_kernels.hpp"
 
 using namespace boss;
 
@@ -138,7 +139,7 @@ struct Ctx {
     bool prof_on = false;
     std::map<std::string, std::vector<std::pair<hipEvent_t, hipEvent_t>>> prof;
     std::vector<hipEvent_t> ev_pool;
-    Workspace vscratch, csc, pred, acq, batchA, batchX, batchMisc, craw, lgA, lgB, lgC, few, setdesc, setmom, gsetdesc, nlatjobs, mceps, meanws, warpws, prunews;
+    Workspace vscratch, csc, pred, acq, batchA, batchX, batchMisc, craw, lgA, lgB, lgC, few, setdesc, setmom, gsetdesc, nlatjobs, mceps, meanws, warpws, prunews, kpv;   // kpv: per-candidate prior variances of a program-kernel posterior (host_kprog.inc)
     // batched likelihood gradients: the gradient passes of consecutive sets rotate over LLG_BANKS streams, each with its
     // own bank of workspaces (bank 0 = the main stream and lgA/lgB/lgC)
     static constexpr int LLG_BANKS = 4;
@@ -559,6 +560,10 @@ struct boss_gp {
     // (rounded where discrete) training points
     bool gibbs = false;
     double *lamX = nullptr, *ampX = nullptr, *noiseX = nullptr;
+    // program-kernel posterior (boss_kgp_create, host_kprog.inc): the covariance function is the traced program *kp (the handle's own
+    // copy), kernel == KERN_PROGRAM; Xsc holds the scaled points as for the plain model
+    bool kprog = false;
+    FitProg* kp = nullptr;
     // explicit L⁻ᵀ for calls with one to four candidates (built on the second such call on a factorisation)
     double *Winv = nullptr, *Linv = nullptr;   // L⁻ᵀ (upper) and L⁻¹ (lower)
     // W_i = Dinv2_i · L[i, i-1] (few_w_kernel): built by the first few-candidates call on a factorisation
@@ -674,6 +679,10 @@ static bool few_fused() {
     return v;
 }
 
+// program-kernel posteriors (host_kprog.inc): the launches factor_enqueue / predict_enqueue make for them
+static void kprog_gram_launch(boss_gp* g, hipStream_t s);
+static void kprog_kstar_launch(boss_gp* g, const boss_cand* cd, const double* Csc, int BN, int tiles, double* out, double* pvar, hipStream_t s);
+static void kprog_var_launch(hipStream_t s, double* var, const double* pvar, int M);
 #include "host_factor.inc"
 #include "host_append.inc"
 #include "host_batch.inc"
@@ -694,6 +703,7 @@ static void mc_grad_launch(hipStream_t s, const double* mu, const double* var, c
 #include "host_prune.inc"
 #include "host_acq.inc"
 #include "host_fitness.inc"
+#include "host_kprog.inc"
 #include "host_mean.inc"
 #include "host_warp.inc"
 #include "host_rider.inc"

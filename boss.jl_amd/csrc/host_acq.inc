@@ -18,6 +18,7 @@ static int acq_ei_impl(int P, int S, boss_gp_t* const* gps, const boss_cand_t* c
     for (int i = 0; i < P * S; ++i) {
         if (!gps[i]) return fail(BOSS_E_INVALID, "NULL posterior handle");
         if (gps[i]->ctx != c) return fail(BOSS_E_INVALID, "all handles and candidates must live on one device");
+        if (mc) NOT_FOR_KPROG(gps[i]);                       // (Monte-Carlo EI: built-in kernels only; the multi-device callers refuse such handles themselves)
         if (!gps[i]->fitted) return fail(BOSS_E_NOT_FITTED, "handle has no valid factorisation");
     }
     std::lock_guard<std::mutex> lk(c->mtx);                 // the per-device scratch areas are shared

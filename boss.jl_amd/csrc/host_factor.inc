@@ -639,6 +639,7 @@ static void gp_release(boss_gp* g) {
     if (g->ampX) (void)hipFree(g->ampX);
     if (g->noiseX) (void)hipFree(g->noiseX);
     if (g->host_par) (void)hipHostFree(g->host_par);
+    delete g->kp;
     if (g->par_ev) (void)hipEventDestroy(g->par_ev);
     if (g->dinv_ev) (void)hipEventDestroy(g->dinv_ev);
     delete g;
@@ -764,15 +765,28 @@ extern "C" int boss_ggp_create(int device, int kernel, int d, int n, const doubl
     return gp_create_common(device, kernel, d, n, n * (1 + d), X, yt.data(), nullptr, true, out);
 }
 
-#define NOT_FOR_AUG(g)                                                                                            \
+#define NOT_FOR_KPROG(g)                                                                                               \
+    do {                                                                                                               \
+        if ((g)->kprog) return fail(BOSS_E_INVALID, "not available for program-kernel posteriors (boss_kgp_create)");     \
+    } while (0)
+
+// entry points of the plain model that program-kernel posteriors share (boss_gp_update)
+#define NOT_FOR_MODELS(g)                                                                                         \
     do {                                                                                                          \
         if ((g)->aug) return fail(BOSS_E_INVALID, "not available for gradient-observation posteriors (boss_ggp_*)"); \
         if ((g)->gibbs) return fail(BOSS_E_INVALID, "not available for nonstationary posteriors (boss_ngp_*)");      \
     } while (0)
 
+#define NOT_FOR_AUG(g)      \
+    do {                    \
+        NOT_FOR_MODELS(g);  \
+        NOT_FOR_KPROG(g);   \
+    } while (0)
+
 // entry points that take gradient-observation posteriors but not (yet) nonstationary ones; the former have no prior mean
 #define NOT_FOR_GIBBS(g, mean_a, mean_b)                                                                            \
     do {                                                                                                            \
+        NOT_FOR_KPROG(g);                                                                                           \
         if ((g)->gibbs) return fail(BOSS_E_INVALID, "not available for nonstationary posteriors (boss_ngp_*)");        \
         if ((g)->aug && ((mean_a) || (mean_b)))                                                                      \
             return fail(BOSS_E_INVALID, "gradient-observation posteriors take no prior mean (gradient_gp.jl:307-361)"); \
@@ -1077,7 +1091,7 @@ static int factor_enqueue(boss_gp* g, RiderReq* rider) {
     const ChainPlan plan = chain_begin(c, g->A, g->ld, g->Np, g->inv16, g->info);
     BOSS_STAMP(2);
     // (the resident strips recognise an inverse tile the chain has not written yet by this pattern: follow_strip, chain.hpp)
-    const bool fill_in_prep = plan.on && !g->aug && !g->gibbs && g->par_in_args;   // (scale_points_args_kernel writes the pattern itself)
+    const bool fill_in_prep = plan.on && !g->aug && !g->gibbs && !g->kprog && g->par_in_args;   // (scale_points_args_kernel writes the pattern itself)
     if (plan.on && !fill_in_prep) (void)hipMemsetAsync(g->inv16, 0xff, sizeof(double) * (size_t)g->nblk * 8 * 256, s);
     {
         ProfScope ps(c, "prep");
@@ -1114,12 +1128,15 @@ static int factor_enqueue(boss_gp* g, RiderReq* rider) {
         hipLaunchKernelGGL(gibbs_gram_kernel, dim3(t64 * (t64 + 1) / 2), dim3(256), 0, s, (const double*)g->Xraw,
                            (const double*)g->lamX, (const double*)g->ampX, (const double*)g->noiseX, (size_t)0, (size_t)0, g->d, g->N,
                            g->Np, g->A, g->ld, (size_t)0, 0);
+    } else if (g->kprog) {
+        ProfScope ps(c, "gram");
+        kprog_gram_launch(g, s);
     } else {
         gram_enqueue(c, g->Xsc, 0, g->d, g->N, g->Np, g->kernel, g->hyp, g->A, g->ld, 0, 1);
     }
     BOSS_STAMP(3);
     chain_ready(c, plan, g->Np, g->info);
-    const bool riding = rider && plan.on && rider->step && chain_trail_mode(g->nblk) != 2 && g->par_in_args;
+    const bool riding = rider && plan.on && rider->step && chain_trail_mode(g->nblk) != 2 && g->par_in_args && !g->kprog;
     if (rider) rider->plan = riding ? plan : ChainPlan();
     potrf_enqueue(c, g->A, g->ld, g->Np, 1, 0, g->inv16, 0, g->info, true, &plan, riding ? &rider->step : nullptr);
     // the block inverses go on the side stream right away only when the previous factorisation's were used (update → predict
@@ -1156,7 +1173,7 @@ static int gp_update_enqueue(boss_gp* g, const double* lengthscale, double ampli
     Ctx* c = g->ctx;
     hipStream_t s = c->stream;
     gp_invalidate(g);
-    const bool small = small_fit_ok(c, g->N, g->d);          // one launch does it all
+    const bool small = small_fit_ok(c, g->N, g->d) && !g->kprog;   // one launch does it all (built-in kernels only)
     if (!g->par_ev) {                         // a member of a batch-fitted set: created here, on its first update (boss_gp_fit_batch)
         HIPCHK(hipEventCreateWithFlags(&g->par_ev, hipEventDisableTiming));
         if (!g->dinv_ev) HIPCHK(hipEventCreateWithFlags(&g->dinv_ev, hipEventDisableTiming));
@@ -1166,7 +1183,7 @@ static int gp_update_enqueue(boss_gp* g, const double* lengthscale, double ampli
     double* hyp = g->host_par + g->d;
     (void)stage_hyper(g->d, lengthscale, amplitude, noise_std, invlam, hyp);   // (validated by the caller)
     g->amp2 = hyp[0];
-    g->par_in_args = !small && g->d <= HYP_ARGS_MAX_D;          // the first kernel of the update deposits them on the device
+    g->par_in_args = !small && g->d <= HYP_ARGS_MAX_D && !g->kprog;          // the first kernel of the update deposits them on the device
     if (!small && !g->par_in_args) {
         HIPCHK(hipMemcpyAsync(g->invlam, invlam, sizeof(double) * (g->d + 2), hipMemcpyHostToDevice, s));   // hyp follows invlam on both sides
         HIPCHK(hipEventRecord(g->par_ev, s));
@@ -1213,7 +1230,7 @@ static int gp_update_enqueue(boss_gp* g, const double* lengthscale, double ampli
 extern "C" int boss_gp_update(boss_gp_t* g, const double* lengthscale, double amplitude, double noise_std,
                               const double* mean_X, int flags, double* logpdf_out) {
     if (!g) return fail(BOSS_E_INVALID, "gp is NULL");
-    NOT_FOR_AUG(g);
+    NOT_FOR_MODELS(g);                                       // (program-kernel posteriors update here too)
     int rc = validate_hyper(g->d, lengthscale, amplitude, noise_std);
     if (rc) return rc;
     Ctx* c = g->ctx;

@@ -84,6 +84,7 @@ extern "C" int boss_nlat_create(int device, int d, boss_gp_t* const* lam_gps, co
             continue;
         }
         if (g->aug || g->gibbs) return fail(BOSS_E_INVALID, "a latent model must be a plain posterior (boss_gp_create)");
+        NOT_FOR_KPROG(g);
         if (g->d != d) return fail(BOSS_E_INVALID, "a latent model's x_dim differs from d");
         if (g->ctx->logical != device) return fail(BOSS_E_INVALID, "a latent model lives on another device");
         if (g->has_mean) return fail(BOSS_E_INVALID, "a latent model with a prior mean cannot be evaluated on the device");

@@ -251,8 +251,10 @@ static int on_devices(int G, F fn) {
 extern "C" int boss_multi_gp_update(int G, boss_gp_t* const* gps, const double* lengthscale, double amplitude, double noise_std,
                                     const double* mean_X, double* logpdf_out) {
     if (!gps || G < 1) return fail(BOSS_E_INVALID, "bad arguments");
-    for (int g = 0; g < G; ++g)
+    for (int g = 0; g < G; ++g) {
         if (!gps[g]) return fail(BOSS_E_INVALID, "NULL posterior handle");
+        NOT_FOR_KPROG(gps[g]);
+    }
     int first = BOSS_OK;
     std::string msg;
     for (int g = 0; g < G; ++g) {                            // enqueue everywhere, then wait: the devices factorise concurrently
@@ -340,6 +342,7 @@ static int multi_acq_ei_on(Multi& m, int G, int P, int S, boss_gp_t* const* gps,
         for (size_t i = 0; i < PS; ++i) {
             const boss_gp* h = gps[PS * g + i];
             if (!h) return fail(BOSS_E_INVALID, "NULL posterior handle");
+            NOT_FOR_KPROG(h);
             if (h->ctx != m.ctx[g]) return fail(BOSS_E_INVALID, "replica g of every posterior must live on device g");
             if (h->d != mc->d) return fail(BOSS_E_INVALID, "candidates and posteriors differ in x_dim");
         }
@@ -520,6 +523,7 @@ extern "C" int boss_multi_acq_ei_outputs(int P, int S, boss_gp_t* const* gps, in
     int d = 0;
     for (size_t i = 0; i < PS; ++i) {
         if (!gps[i]) return fail(BOSS_E_INVALID, "NULL posterior handle");
+        NOT_FOR_KPROG(gps[i]);
         if (!gps[i]->fitted) return fail(BOSS_E_NOT_FITTED, "handle has no valid factorisation");
         owner[i] = device_index_of(m, gps[i]->ctx);
         if (owner[i] < 0) return fail(BOSS_E_INVALID, "handle lives on a device boss_init did not open");
@@ -610,6 +614,7 @@ extern "C" int boss_multi_acq_ei_samples(int P, int S, boss_gp_t* const* gps, in
         for (int p = 0; p < P; ++p) {
             const boss_gp* h = gps[p + (size_t)P * sm];
             if (!h) return fail(BOSS_E_INVALID, "NULL posterior handle");
+            NOT_FOR_KPROG(h);
             if (!h->fitted) return fail(BOSS_E_NOT_FITTED, "handle has no valid factorisation");
             const int o = device_index_of(m, h->ctx);
             if (o < 0) return fail(BOSS_E_INVALID, "handle lives on a device boss_init did not open");

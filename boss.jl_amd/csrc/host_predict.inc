@@ -201,7 +201,7 @@ static bool small_predict_ok(const boss_gp* g, int M) {
     // one wave per candidate costs ∝ N² per candidate: up to 1024 candidates at N = 128, proportionally more below (the tiled
     // kernels take over where they are faster: 251 against 367 µs at N = 100, M = 8192)
     const long long cap = std::min<long long>(16384, 1024LL * SMALL_MAX_N * SMALL_MAX_N / ((long long)g->N * g->N));
-    return small_fit_ok(g->ctx, g->N, g->d) && M <= cap && !g->aug && !g->gibbs;
+    return small_fit_ok(g->ctx, g->N, g->d) && M <= cap && !g->aug && !g->gibbs && !g->kprog;
 }
 
 static int predict_enqueue(boss_gp* g, const boss_cand* cd, const double* mean_s_dev, double* mu, double* var,
@@ -214,6 +214,8 @@ static int predict_enqueue(boss_gp* g, const boss_cand* cd, const double* mean_s
     if (!g->fitted) return fail(BOSS_E_NOT_FITTED, "handle has no valid factorisation");
     if (g->gibbs && !clam_dev)
         return fail(BOSS_E_INVALID, "nonstationary posteriors predict through boss_ngp_predict (λ(x*), α(x*) are needed)");
+    if (g->kprog && (for_grad || need_v))
+        return fail(BOSS_E_INVALID, "not available for program-kernel posteriors (boss_kgp_create): gradients and covariances");
     if (cd->ctx != c) return fail(BOSS_E_INVALID, "candidates and posterior live on different devices");
     if (cd->d != g->d) return fail(BOSS_E_INVALID, "candidate dimension differs from the model's x_dim");
     if (!for_grad && !need_v && small_predict_ok(g, cd->M)) {
@@ -249,6 +251,13 @@ static int predict_enqueue(boss_gp* g, const boss_cand* cd, const double* mean_s
     rc = ws_reserve(c->vscratch, sizeof(double) * (size_t)tiles * BN * g->Np * (for_grad ? 2 : 1));   // gradients: V and W slabs
     if (rc) return rc;
     double* Csc = (double*)c->csc.p;
+    double* kpv = nullptr;                                   // program kernel: k(x*, x*) per candidate, written beside K*
+    if (g->kprog) {
+        rc = ws_reserve(c->kpv, sizeof(double) * (size_t)Mp);
+        if (rc) return rc;
+        kpv = (double*)c->kpv.p;
+    }
+    const int vmode = g->aug ? 1 : (g->gibbs || g->kprog) ? 2 : 0;   // how the finish kernels leave σ² (predict_kernels.hpp)
     if (!g->gibbs)
         hipLaunchKernelGGL(scale_cand_kernel, dim3((Mp + 255) / 256), dim3(256), 0, s, cd->Craw, Csc, g->invlam,
                            g->discrete_dev, g->d, Mp);
@@ -300,6 +309,8 @@ static int predict_enqueue(boss_gp* g, const boss_cand* cd, const double* mean_s
                                (const double*)g->invlam, R, 32);
         else if (g->gibbs)
             gibbs_kstar32_launch(g, cd, clam_dev, camp_dev, ftiles, R, s);
+        else if (g->kprog)
+            kprog_kstar_launch(g, cd, Csc, 32, ftiles, R, kpv, s);
         else
             hipLaunchKernelGGL(kstar_rows_kernel, dim3(g->Np / 256, ftiles), dim3(256), sizeof(double) * (g->d * 32 + KSTAR_LDS_EXTRA), s,
                                (const double*)g->Xsc, g->Np, g->N, (const double*)Csc, g->d, Mp, g->kernel, g->amp2, R,
@@ -313,8 +324,9 @@ static int predict_enqueue(boss_gp* g, const boss_cand* cd, const double* mean_s
             hipLaunchKernelGGL(inv_fwd_kernel<GU>, dim3(ftiles, nrb), dim3(GU::NTHREADS), 0, s, (const double*)g->Linv, g->ld, g->Np,
                                (const double*)g->A, g->ld, (const double*)R, V, ssp);
             hipLaunchKernelGGL(inv_fwd_finish_kernel, dim3(ftiles), dim3(256), 0, s, (const double*)ssp, nrb, mean_s_dev, cd->M,
-                               g->amp2, g->aug ? 1 : g->gibbs ? 2 : 0, mu, var);
+                               g->amp2, vmode, mu, var);
             if (g->gibbs) hipLaunchKernelGGL(gibbs_var_kernel, dim3((cd->M + 255) / 256), dim3(256), 0, s, var, camp_dev, cd->M);
+            if (g->kprog) kprog_var_launch(s, var, kpv, cd->M);
             HIPCHK(hipGetLastError());
             return BOSS_OK;
         }
@@ -326,8 +338,9 @@ static int predict_enqueue(boss_gp* g, const boss_cand* cd, const double* mean_s
             hipLaunchKernelGGL(kfn, dim3(nwg), dim3(256), lds, s, (const double*)g->Winv, g->ld, g->Np,
                                (const double*)g->A, g->ld, (const double*)R, cd->M, part, (double*)nullptr);
             hipLaunchKernelGGL(winv_finish_kernel, dim3(1), dim3(256), 0, s, (const double*)part, nwg, cd->M, mean_s_dev, g->amp2,
-                               g->aug ? 1 : g->gibbs ? 2 : 0, mu, var);
+                               vmode, mu, var);
             if (g->gibbs) hipLaunchKernelGGL(gibbs_var_kernel, dim3(1), dim3(256), 0, s, var, camp_dev, cd->M);
+            if (g->kprog) kprog_var_launch(s, var, kpv, cd->M);
             HIPCHK(hipGetLastError());
             return BOSS_OK;
         }
@@ -361,31 +374,38 @@ static int predict_enqueue(boss_gp* g, const boss_cand* cd, const double* mean_s
                                    g->Np, nb, ib, ftiles, R, (const double*)g->Dinv2, (const double*)g->W2, V, part);
             }
             hipLaunchKernelGGL(few_sum_kernel, dim3(ftiles), dim3(256), 0, s, (const double*)part, nb, mean_s_dev, cd->M, g->amp2, mu, var,
-                               g->aug ? 1 : g->gibbs ? 2 : 0);
+                               vmode);
             if (g->gibbs) hipLaunchKernelGGL(gibbs_var_kernel, dim3((cd->M + 255) / 256), dim3(256), 0, s, var, camp_dev, cd->M);
+            if (g->kprog) kprog_var_launch(s, var, kpv, cd->M);
             HIPCHK(hipGetLastError());
             return BOSS_OK;
         }
         for (int ib = 0; ib < nb; ++ib) {
             hipLaunchKernelGGL(few_finish_kernel<G>, dim3(ftiles), dim3(G::NTHREADS), PredictLds<G>::BYTES, s, (const double*)g->A,
                                g->ld, g->Np, ib, (const double*)R, (const double*)g->Dinv2, V, ssmz, ib == nb - 1 ? 1 : 0,
-                               mean_s_dev, cd->M, g->amp2, mu, var, g->aug ? 1 : g->gibbs ? 2 : 0);
+                               mean_s_dev, cd->M, g->amp2, mu, var, vmode);
             const int nupd = (nb - 1 - ib) * (PRED_RB / BLK);
             if (nupd > 0)
                 hipLaunchKernelGGL(few_update_kernel<GU>, dim3(ftiles, nupd), dim3(GU::NTHREADS), 0, s, (const double*)g->A, g->ld,
                                    g->Np, ib, (const double*)V, R);
         }
         if (g->gibbs) hipLaunchKernelGGL(gibbs_var_kernel, dim3((cd->M + 255) / 256), dim3(256), 0, s, var, camp_dev, cd->M);
+        if (g->kprog) kprog_var_launch(s, var, kpv, cd->M);
         HIPCHK(hipGetLastError());
         return BOSS_OK;
     }
     join_dinv();
-    if (g->aug || g->gibbs) {
+    if (g->aug || g->gibbs || g->kprog) {
         ProfScope ps(c, "predict");
         double* V = (double*)c->vscratch.p;
+        // a program kernel's epilogue is the nonstationary one: −Σv² from the kernel, k(x*, x*) added behind it (KERN_PROGRAM itself
+        // never reaches a kernel that evaluates kappa_*)
+        const int pre_kern = g->kprog ? KERN_GIBBS : g->kernel;
         if (g->aug)
             hipLaunchKernelGGL(aug_kstar_kernel, dim3(g->Np / 256, tiles), dim3(256), aug_lds, s, (const double*)g->Xraw, g->ldx, g->d,
                                g->nhead, g->N, g->Np, (const double*)cd->Craw, Mp, g->kernel, g->amp2, (const double*)g->invlam, V, BN);
+        else if (g->kprog)
+            kprog_kstar_launch(g, cd, Csc, BN, tiles, V, kpv, s);
         else if (BN == 32)
             gibbs_kstar32_launch(g, cd, clam_dev, camp_dev, tiles, V, s);
         else
@@ -395,13 +415,14 @@ static int predict_enqueue(boss_gp* g, const boss_cand* cd, const double* mean_s
         if (BN == 32) {
             typedef PredG32 G;
             hipLaunchKernelGGL((predict_kernel<G, true>), dim3(tiles), dim3(G::NTHREADS), PredictLds<G>::BYTES, s, g->A, g->ld, g->Np,
-                               g->N, g->Dinv2, g->Xsc, Csc, g->d, Mp, g->kernel, g->amp2, V, mean_s_dev, cd->M, mu, var, dbg);
+                               g->N, g->Dinv2, g->Xsc, Csc, g->d, Mp, pre_kern, g->amp2, V, mean_s_dev, cd->M, mu, var, dbg);
         } else {
             typedef PredG64 G;
             hipLaunchKernelGGL((predict_kernel<G, true>), dim3(tiles), dim3(G::NTHREADS), PredictLds<G>::BYTES, s, g->A, g->ld, g->Np,
-                               g->N, g->Dinv, g->Xsc, Csc, g->d, Mp, g->kernel, g->amp2, V, mean_s_dev, cd->M, mu, var, dbg);
+                               g->N, g->Dinv, g->Xsc, Csc, g->d, Mp, pre_kern, g->amp2, V, mean_s_dev, cd->M, mu, var, dbg);
         }
         if (g->gibbs) hipLaunchKernelGGL(gibbs_var_kernel, dim3((cd->M + 255) / 256), dim3(256), 0, s, var, camp_dev, cd->M);
+        if (g->kprog) kprog_var_launch(s, var, kpv, cd->M);
         HIPCHK(hipGetLastError());
         return BOSS_OK;
     }
@@ -448,6 +469,8 @@ static int set_np_max() {
 // nonstationary models)
 static bool predict_set_ok(int n, boss_gp_t* const* gps, const boss_cand* cd, bool with_latents = false) {
     if (n < 2) return false;
+    for (int i = 0; i < n; ++i)
+        if (gps[i] && gps[i]->kprog) return false;           // program kernels go member by member
     const boss_gp* g0 = gps[0];
     if (!g0 || g0->Np > set_np_max() || g0->ctx->prof_on || g0->d > 64) return false;
     if (g0->gibbs && (!with_latents || g0->d > GIBBS_KSTAR_MAX_D)) return false;
@@ -601,7 +624,7 @@ extern "C" int boss_gp_predict(boss_gp_t* g, int M, const double* Xs, const doub
     {
         // one to four candidates on resident inverse factors: candidates in the kernel arguments, results polled in mapped memory
         const size_t winv_lds = sizeof(double) * (size_t)g->Np * (M == 1 ? 1 : M == 2 ? 2 : WINV_MAX_M);
-        if (!few_args_off() && M <= WINV_MAX_M && g->have_winv && !g->pending && !g->aug && !g->gibbs && g->d <= FEW_ARGS_MAX_D && !c->prof_on &&
+        if (!few_args_off() && M <= WINV_MAX_M && g->have_winv && !g->pending && !g->aug && !g->gibbs && !g->kprog && g->d <= FEW_ARGS_MAX_D && !c->prof_on &&
             winv_lds <= 144 * 1024 && g->N > SMALL_MAX_N) {
             hipStream_t s = c->stream;
             const int nwg = g->Np / WINV_ROWS;
@@ -1242,7 +1265,7 @@ static bool grad_set_ok(int n, boss_gp_t* const* gps, const boss_cand* cd) {
     if (!predict_set_ok(n, gps, cd)) return false;
     const boss_gp* g0 = gps[0];
     // (N <= 128 with few candidates: the one-launch small_predict_grad_kernel of grad_enqueue is the better path)
-    return !g0->gibbs && !small_predict_ok(g0, cd->M) && (!g0->aug || g0->d <= AUG_MAX_D);
+    return !g0->gibbs && !g0->kprog && !small_predict_ok(g0, cd->M) && (!g0->aug || g0->d <= AUG_MAX_D);
 }
 
 // mu / var of member i at mu_all + i·M (unclipped), ∇μ / ∇σ² at gm_all + i·d·M; mean_all / mg_all (or null): the prior means and

@@ -86,7 +86,7 @@ extern "C" int boss_debug_acq_prune_bounds(int device, int M, double* mua_out, d
 static bool prune_eligible(const boss_gp* g, const boss_cand* cd, int P, int S, const EiPar& par, bool has_out, bool defer, bool has_mc,
                            const double* dpair) {
     if (!prune_enabled() || has_out || defer || dpair || has_mc || P != 1 || S != 1 || par.mode != 1) return false;
-    if (g->aug || g->gibbs || g->ctx->prof_on) return false;
+    if (g->aug || g->gibbs || g->kprog || g->ctx->prof_on) return false;
     const int ftiles = (cd->M + 31) / 32;                    // (few_max_tiles: predict_enqueue's limit of its few-candidates branch — the rounds must stay below it)
     const int min_tiles = g_prune.min_tiles >= 0 ? g_prune.min_tiles : few_max_tiles();
     if (few_off() || ftiles <= min_tiles || g->Np < 4 * PRED_RB || g->d > 64 || cd->d != g->d || slab_bn(cd->M, false) != 32) return false;

@@ -302,6 +302,7 @@ extern "C" int boss_gp_update_acq(boss_gp_t* g, const double* lengthscale, doubl
 // ms_out: average duration of one launch by HIP events.
 extern "C" int boss_debug_rider_replay(boss_gp_t* g, const boss_cand_t* cand, int k, int reps, int s_only, double* ms_out) {
     if (!g || !cand || !ms_out || k < 2 || k >= g->nblk || reps < 1) return fail(BOSS_E_INVALID, "bad argument");
+    NOT_FOR_KPROG(g);
     Ctx* c = g->ctx;
     HIPCHK(hipSetDevice(c->device));
     std::lock_guard<std::mutex> lk(c->mtx);

@@ -17,6 +17,7 @@ import numpy as np
 
 from . import api
 from . import distributed as dist_util
+from .kernel import refuse_device_kernel
 from .mean import device_mean_of
 from .model import HipGaussianProcess, HipGPParams
 from .problem import BossOptions, BossProblem, Dirac, MvDirac, Normal
@@ -159,6 +160,7 @@ class HipGradientMAP:
     def estimate_parameters(self, problem: BossProblem, options: BossOptions = BossOptions(), return_all: bool = False):
         problem = base_problem(problem)                      # a HipTransformedModel: its base model on the transformed data
         model = problem.model
+        refuse_device_kernel(model, "HipGradientMAP (likelihood gradients)")
         grad_model = hasattr(model, "grad_noise_std_priors")        # HipGradientGaussianProcess (gradient_gp.py)
         semipar = not grad_model and model.parametric is not None
         if semipar:
@@ -274,6 +276,7 @@ class HipSampleOptMAP:
         assert self.samples >= self.multistart                       # sample_opt.jl:30
 
     def estimate_parameters(self, problem: BossProblem, options: BossOptions = BossOptions(), return_all: bool = False):
+        refuse_device_kernel(base_problem(problem).model, "HipSampleOptMAP (its HipGradientMAP stage needs likelihood gradients)")
         scored = HipBatchedMAP(self.samples, self.seed, self.group).estimate_parameters(problem, options, return_all=True)
         order = sorted(range(len(scored)), key=lambda i: -scored[i].loglike)             # sortperm(...; rev=true), stable
         starts = [scored[i].params for i in order[:self.multistart]]

@@ -20,6 +20,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import api
+from .kernel import refuse_device_kernel
 from .model import HipGaussianProcessPosterior, HipGaussianProcessPosteriorSlice
 from .problem import ExperimentData
 
@@ -239,6 +240,9 @@ class HipGradientGaussianProcess:
     device: int = 0
 
     sliceable = True                                            # gradient_gp.jl:69
+
+    def __post_init__(self):
+        refuse_device_kernel(self, "HipGradientGaussianProcess (the augmented Gram matrix needs the kernel's derivatives)")
 
     @property
     def y_dim(self):

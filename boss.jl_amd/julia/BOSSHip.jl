@@ -1374,6 +1374,10 @@ end
 # not bound: boss_warp_moments — model-space moments to user space on the device; needs boss_warp_create
 # not bound: boss_warp_predict — prediction of a warped model in one call; needs boss_warp_create
 # not bound: boss_warp_predict_grad — prediction of a warped model with gradients in one call; needs boss_warp_create
+# not bound: boss_kern_create — kernel programs: the covariance closure is traced by the Python DeviceKernel only; a Julia KernelFunctions.Kernel beyond the three built-in ones keeps the reference's host path
+# not bound: boss_kern_free — see boss_kern_create
+# not bound: boss_kern_eval_host — see boss_kern_create (the host run of the kernels' interpreter, used by tests)
+# not bound: boss_kgp_create — a posterior handle over a kernel program; needs boss_kern_create
 # not bound: boss_acq_ei_warp — acquisition of a warped model in one call; needs boss_warp_create
 # not bound: boss_acq_ei_grad_warp — acquisition gradient of a warped model in one call; needs boss_warp_create
 end # module

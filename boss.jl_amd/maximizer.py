@@ -26,6 +26,7 @@ from . import acquisition as acq_host
 from . import api
 from . import distributed as dist_util
 from .fitness import DeviceFitness
+from .kernel import device_kernel_of, refuse_device_kernel
 from .mean import device_mean_of
 from .model import HipGaussianProcessPosterior
 from .problem import BossOptions, BossProblem, NonlinFitness, best_so_far, in_bounds, in_cons, in_domain
@@ -139,8 +140,8 @@ def acquisition_values(problem: BossProblem, posts: Sequence[HipGaussianProcessP
         # with the ε draw of the host path below — DeviceFitness(f) and NonlinFitness(f) see identical ε
         eps = _mc_eps(problem, len(posts), eps_seed)
         ym = problem.y_max if constrained else None
-        if any(isinstance(s.gp, api.GibbsGP) for p in posts for s in p.slices):
-            # posteriors whose handles boss_acq_ei does not take: their moments, then the Monte-Carlo epilogue on those
+        if any(isinstance(s.gp, (api.GibbsGP, api.KernelGP)) for p in posts for s in p.slices):
+            # posteriors whose handles boss_acq_ei_mc does not take: their moments, then the Monte-Carlo epilogue on those
             if own:
                 cand.close()
             mv = [p.mean_and_var(Xs) for p in posts]
@@ -221,6 +222,7 @@ class HipBatchAM:
         if self.devices is not None or self.shard != "candidates":
             _no_warp(problem, "devices=[...]" if self.devices is not None else f"shard={self.shard!r}")
         if self.devices is not None:
+            refuse_device_kernel(problem.model, "HipBatchAM(devices=[...])")
             assert world == 1 and posts is None, "devices=[...] is the single-process mode"
             return self._maximize_in_library(problem, Xs, return_all)
         if self.shard == "outputs":
@@ -253,7 +255,8 @@ class HipBatchAM:
         """`model_posterior(problem)` is ONE factorisation (one output, one parameter sample) of the plain GP / semiparametric
         model and the acquisition is the analytic EI: the two halves of the BO iteration (src/bo.jl:30-48) fit one device call."""
         from .model import HipGaussianProcess
-        return (problem is not None and type(problem.model) is HipGaussianProcess and problem.data.Y.shape[0] == 1 and
+        return (problem is not None and type(problem.model) is HipGaussianProcess and device_kernel_of(problem.model) is None and
+                problem.data.Y.shape[0] == 1 and
                 not isinstance(problem.params, (list, tuple)) and not isinstance(problem.acquisition.fitness, NonlinFitness))
 
     def _update_and_acquire(self, problem: BossProblem, Xs, want_acq: bool):
@@ -376,6 +379,7 @@ class HipSequentialBatchAM:
     def maximize_acquisition(self, problem: BossProblem, options: BossOptions = BossOptions()):
         import copy
         _no_warp(problem, "HipSequentialBatchAM (appending observations, tracked candidates)")
+        refuse_device_kernel(problem.model, "HipSequentialBatchAM (appending observations, tracked candidates)")
         prob = copy.copy(problem)                                        # problem_ = deepcopy(problem) (batch.jl:27)
         prob.data = type(problem.data)(problem.data.X.copy(), problem.data.Y.copy())
         posts = posteriors_of(prob, reserve=self.batch_size)             # no re-allocation when the appends arrive
@@ -546,6 +550,7 @@ class HipGradientAM:
         return acc / len(posts), gacc / len(posts)
 
     def maximize_acquisition(self, problem: BossProblem, options: BossOptions = BossOptions(), posts=None):
+        refuse_device_kernel(problem.model, "HipGradientAM (candidate gradients)")
         if self.mean_grad is not None and device_mean_of(problem.model) is not None:
             raise ValueError("HipGradientAM: the model's mean is a DeviceMean, which gives its own ∂m/∂x; drop mean_grad")
         rng = np.random.default_rng(dist_util.shared_seed(self.seed, self.group))     # the same starts on every rank

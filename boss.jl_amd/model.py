@@ -22,6 +22,7 @@ from typing import Callable, List, Optional, Sequence
 import numpy as np
 
 from . import api
+from .kernel import device_kernel_of, refuse_device_kernel
 from .mean import DeviceMean, device_mean_of
 from .problem import ExperimentData
 
@@ -60,12 +61,15 @@ class HipGaussianProcess:
     Jacobian is taken by central differences of `parametric` in θ with step 1e-6·max(1, |θ_t|): 2T further evaluations of
     `parametric` per point; the error is about 2⁻⁵³·|m|/h from rounding plus h²·|∂³m/∂θ³|/6 from truncation.
     `parametric` (or `mean`, with theta_dim = 0) may be a DeviceMean: values and exact Jacobians then come from its traced program on
-    the device, and `parametric_jac` is ignored."""
+    the device, and `parametric_jac` is ignored.
+    `kernel`: "matern32" | "matern52" | "sqexp", or a DeviceKernel (kernel.py) — a user-defined covariance function traced into a
+    device program (boss_kgp_create).  Such a model fits, predicts and drives HipBatchedMAP / HipBatchAM / bo; what needs gradients,
+    covariances, appends or tracks raises NotImplementedError."""
     lengthscale_priors: Sequence
     amplitude_priors: Sequence
     noise_std_priors: Sequence
     mean: object = None
-    kernel: str = "matern52"                     # default per src/deprecated.jl:34
+    kernel: object = "matern52"                  # default per src/deprecated.jl:34; or a DeviceKernel
     discrete: Optional[Sequence[bool]] = None
     parametric: Optional[Callable] = None
     theta_priors: Optional[Sequence] = None
@@ -83,6 +87,13 @@ class HipGaussianProcess:
     @property
     def y_dim(self):
         return len(self.amplitude_priors)
+
+    def _new_gp(self, X, y):
+        """An unfitted resident handle for one output: boss_gp_create, or boss_kgp_create under a DeviceKernel."""
+        dk = device_kernel_of(self)
+        if dk is not None:
+            return api.KernelGP(X, y, dk.program, self.discrete, self.device)
+        return api.GP(X, y, self.kernel, self.discrete, self.device)
 
     # ------------------------------------------------------------------ prior mean on the device (DeviceMean)
     def device_means(self, X, plist: Sequence[Optional[HipGPParams]], layout: int = api.MEAN_SAMPLE_MAJOR, jac_theta: bool = False,
@@ -183,7 +194,7 @@ class HipGaussianProcess:
     def data_loglike(self, data: ExperimentData):
         """data_loglike (gaussian_process.jl:250-267): Σ over outputs of logpdf(FiniteGP_i, Y[i,:]).
         Keeps one resident handle per output; each call is one boss_gp_update."""
-        gps = [api.GP(data.X, data.Y[i], self.kernel, self.discrete, self.device) for i in range(data.Y.shape[0])]
+        gps = [self._new_gp(data.X, data.Y[i]) for i in range(data.Y.shape[0])]
 
         def ll(p: HipGPParams):
             tot = 0.0
@@ -204,6 +215,27 @@ class HipGaussianProcess:
         dev = None                                           # DeviceMean: every output's S×N mean rows from one device call
         if device_mean_of(self) is not None and S:
             dev = self.device_means(data.X, samples, api.MEAN_OUTPUT_MAJOR)[0]
+        if device_kernel_of(self) is not None:
+            # a program kernel: the batched factorisation is built-in-kernel only — S updates on one resident handle per output
+            for i in range(data.Y.shape[0]):
+                g = self._new_gp(data.X, data.Y[i])
+                try:
+                    for k, s in enumerate(samples):
+                        if dev is not None:
+                            m = np.ascontiguousarray(dev[i][k])
+                        else:
+                            m = self.mean_values(data.X, s if self.parametric is not None else None, i)
+                        try:
+                            tot[k] += g.update(s.lengthscales[:, i], s.amplitudes[i], s.noise_std[i], m)
+                        except api.PosDefException:
+                            tot[k] = -math.inf               # safe_data_loglike (src/surrogate_model.jl:2-12)
+                        except api.BossError as e:           # an invalid parameter set is a sample of likelihood -inf, as its status is
+                            if e.code != api.BOSS_E_INVALID:  # in the batched call of the built-in kernels; anything else is an error
+                                raise
+                            tot[k] = -math.inf
+                finally:
+                    g.close()
+            return tot
         for i in range(data.Y.shape[0]):
             lam = np.stack([s.lengthscales[:, i] for s in samples], axis=1)
             amp = np.array([s.amplitudes[i] for s in samples])
@@ -227,6 +259,7 @@ class HipGaussianProcess:
         J_i (N×T), the device returns J_iᵀ a_i with a_i = K_i⁻¹(y_i − m_i); θ is shared by the outputs, so ∂/∂θ = Σ_i J_iᵀ a_i.
         Returns (ll[S], grads): grads[k] a HipGPParams of gradients (theta None without a parametric mean); a set that fails
         in any output has ll = -inf and zero gradients."""
+        refuse_device_kernel(self, "data_loglike_grad_batch (the likelihood gradient of HipGradientMAP)")
         S = len(plist)
         tot = np.zeros(S)
         if S == 0:
@@ -264,14 +297,25 @@ class HipGaussianProcess:
                               reserve: int = 0, mean_X=None) -> "HipGaussianProcessPosteriorSlice":
         """model_posterior_slice (gaussian_process.jl:133-141).  reserve: room for later appends.  mean_X: the prior mean of output i
         at data.X where the caller has it already (model_posterior evaluates a DeviceMean once for all outputs)."""
+        mX = self.mean_values(data.X, params, i) if mean_X is None else mean_X
+        if device_kernel_of(self) is not None:
+            if reserve:
+                refuse_device_kernel(self, "model_posterior with room for appends (HipSequentialBatchAM)")
+            g = self._new_gp(data.X, data.Y[i])
+            try:
+                g.update(params.lengthscales[:, i], params.amplitudes[i], params.noise_std[i], mX)
+            except Exception:
+                g.close()
+                raise
+            return HipGaussianProcessPosteriorSlice(self, params, i, g)
         g = api.fit(data.X, data.Y[i], self.kernel, params.lengthscales[:, i], params.amplitudes[i], params.noise_std[i],
-                    self.mean_values(data.X, params, i) if mean_X is None else mean_X, self.discrete, self.device, reserve)
+                    mX, self.discrete, self.device, reserve)
         return HipGaussianProcessPosteriorSlice(self, params, i, g)
 
     def model_posterior(self, params, data: ExperimentData, reserve: int = 0):
         """model_posterior (src/posterior.jl:8-19,38-41): a vector of params broadcasts (BI samples)."""
         if isinstance(params, (list, tuple)):
-            if len(params) > 1 and reserve == 0:
+            if len(params) > 1 and reserve == 0 and device_kernel_of(self) is None:   # (a program kernel: create + update per sample)
                 # the S samples of a BI fit: per output ONE batched factorisation (boss_gp_fit_batch) — X and y uploaded once,
                 # the S posteriors resident as members of one set.  A sample whose matrix is not positive definite raises, as
                 # the reference's cholesky would inside the broadcast (src/posterior.jl:15-19)
@@ -348,6 +392,7 @@ class HipGaussianProcessPosteriorSlice:
     def mean_and_var_grad(self, X, mean_grad=None):
         """mean_and_var(post, X) with its gradient w.r.t. the columns of X (analytic, on the device):
         (mu[M], var[M], dmu[d,M], dvar[d,M]).  mean_grad: d×M gradient of the prior mean, if it has one."""
+        refuse_device_kernel(self.model, "mean_and_var_grad")
         X = np.asarray(X, float)
         if X.ndim == 1:
             X = X[:, None]
@@ -355,6 +400,7 @@ class HipGaussianProcessPosteriorSlice:
 
     def mean_and_cov(self, X):
         """mean_and_cov(post, X::Matrix) (gaussian_process.jl:180-184) -> (mu[M], Σ[M,M])."""
+        refuse_device_kernel(self.model, "cov / mean_and_cov")
         X = np.asarray(X, float)
         return self.gp.predict_cov(X, self._mean_s(X))
 
@@ -365,6 +411,7 @@ class HipGaussianProcessPosteriorSlice:
         """Posterior of the data augmented by (x, y_i) under the same hyper-parameters — what
         model_posterior returns after augment_dataset! (problem.jl:191-198) — as a block Cholesky
         append on the resident factor (boss_gp_append).  x: length-d vector or d×n matrix."""
+        refuse_device_kernel(self.model, "append")
         x = np.asarray(x, float)
         return self.gp.append(x, y_i, self._mean_s(x))
 

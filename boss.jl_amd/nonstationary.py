@@ -15,6 +15,7 @@ from typing import Callable, List, Optional, Sequence
 import numpy as np
 
 from . import api
+from .kernel import refuse_device_kernel
 from .problem import ExperimentData
 
 
@@ -125,6 +126,9 @@ class HipParametrizedGP:
     act_func: Callable = identity_act
     noise_std: float = 0.0
     device: int = 0
+
+    def __post_init__(self):
+        refuse_device_kernel(self, "HipNonstationaryGP (a latent HipParametrizedGP; the nonstationary kernel itself is the Gibbs kernel)")
 
     def transform(self, y):
         """construct_variable_transform (:122-134) then act_func: z = quantile(target, cdf(Normal(0,1), y))."""

@@ -204,6 +204,8 @@ class HipTransformedModel:
         if type(self.base_model) not in (HipGaussianProcess, HipGradientGaussianProcess):
             raise NotImplementedError(f"HipTransformedModel wraps a HipGaussianProcess or a HipGradientGaussianProcess; "
                                       f"{type(self.base_model).__name__} as the base model is not supported")
+        from .kernel import refuse_device_kernel
+        refuse_device_kernel(self.base_model, "HipTransformedModel over such a base model (the warped calls are built-in-kernel only)")
         it, ot = self.input_transform, self.output_transform
         self.gradient_base = type(self.base_model) is HipGradientGaussianProcess
         if it is not None and not isinstance(it, InputTransform):

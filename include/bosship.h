@@ -697,6 +697,31 @@ int boss_acq_ei_grad_warp(const boss_warp_t* warp, int P, int S, boss_gp_t* cons
                           const double* mean_Xs, const double* mean_grad, const double* fit_coefs, const double* y_max, int has_best,
                           double best, const unsigned char* valid_mask, double* acq_out, double* dacq_out);
 
+/* Kernel programs: a user-defined covariance function k(u, v) as a traced straight-line program (KernelFunctions.Kernel /
+ * CustomKernel(f), src/models/utils/kernels.jl:3-13, wrapped by finite_gp, gaussian_process.jl:239-243, as
+ * (α+1e-8)² · with_lengthscale(kernel, λ+1e-8)).  The program has 2·d inputs — u[0..d) then v[0..d) — and otherwise the layout,
+ * opcodes and limits (32 constants, 64 instructions) of a fitness program; d is 1..16.  boss_kern_create validates as
+ * boss_fit_create does; boss_kern_create / boss_kern_free / boss_kern_eval_host need no device.
+ * boss_kern_eval_host: U, V d×n column-major, k_out[j] = f(U[:, j], V[:, j]) — the interpreter function the kernels run.
+ *
+ * boss_kgp_create returns an ordinary posterior handle over such a program (the handle keeps a copy: the boss_kern_t may be freed
+ * first).  With u_i = r(x_i) ⊘ (λ + 1e-8), r rounding the discrete dims half-to-even (DiscreteKernel, kernels.jl:56-59):
+ *   K_ij = (α+1e-8)² f(u_i, u_j) + δ_ij (σ+1e-8)²,   K*_ij = (α+1e-8)² f(u_i, u*_j),   k(x*, x*) = (α+1e-8)² f(u*, u*),
+ * the prior variance being EVALUATED per candidate, not taken as α².  The entry (i, j), i > j, of the matrix that is factorised is
+ * f(u_j, u_i): cholesky(Symmetric(K)) reads the upper triangle.  logpdf, μ, σ² (+1e-18, _clip_var), BOSS_E_NOT_PD, BOSS_E_NEG_VAR
+ * and prior means are those of boss_gp_create handles.  The kernels hold no atomics: repeated calls agree bit for bit.
+ * Calls that take the handle: boss_gp_update (flags, logpdf_out as usual), boss_gp_sync, boss_gp_predict, boss_acq_ei (one-shot or
+ * resident candidates, P outputs × S samples, member by member), boss_gp_set_y, boss_gp_n, boss_gp_get_factor, boss_gp_free.
+ * Every other entry point that takes a boss_gp_t* returns BOSS_E_INVALID ("not available for program-kernel posteriors"), or, for
+ * the boss_ggp_* / boss_ngp_* calls, their own "handle was not created by ..." refusal.
+ * BOSS_E_INVALID: d outside 1..16, N < 1 or above 46080, NULL X, y or kern. */
+typedef struct boss_kern boss_kern_t;
+int boss_kern_create(int d, int n_const, const double* consts, int n_instr, const int* code, int out_id, boss_kern_t** out);
+void boss_kern_free(boss_kern_t* kern);
+int boss_kern_eval_host(const boss_kern_t* kern, int n, const double* U, const double* V, double* k_out);
+int boss_kgp_create(int device, int d, int N, const double* X, const double* y, const unsigned char* discrete,
+                    const boss_kern_t* kern, boss_gp_t** out);
+
 /* boss_ngp_predict_grad for n nonstationary posteriors at the same M candidates in ONE call, and the sample-averaged acquisition
  * gradient on top of it: boss_acq_ei_grad_set for NonstationaryGP posteriors (BI samples of a finite_nongp model under
  * OptimizationAM, src/acquisitions/expected_improvement.jl:87-90 inside src/acquisition_maximizers/optimization.jl:89-118).
