@@ -2,12 +2,7 @@
 paths against the staged composition of existing calls (bit for bit), against the 50-digit truths of tests/golden/warp.json, and a
 device-warped HipTransformedModel under both maximizers against the plain-closure host path of the same model.
 
-Device against host twin: the project's interpreter bars, values 1e-12·max(1, max|·|), gradients 1e-11·max(1, max|·|).
-
-Not tested here: the negative-variance conventions of the ONE-CALL paths (BOSS_E_NEG_VAR with bad_index in boss_warp_predict[_grad], the
--Inf candidate with a zero gradient in the acquisition calls).  A fitted GP does not produce a variance below -1e-8 on demand; the same
-branches of the moments stage are tested on given arrays (test_stage_conventions_on_the_device and tests/test_warp_host.py), and the
-one-call paths add to them clip_var_kernel and the EI epilogues, which the plain calls' tests cover."""
+Device against host twin: the project's interpreter bars, values 1e-12·max(1, max|·|), gradients 1e-11·max(1, max|·|)."""
 import os
 import sys
 
