@@ -151,6 +151,8 @@ SIGNATURES = {
     "boss_kern_free": (None, [C.c_void_p]),
     "boss_kern_eval_host": (C.c_int, [C.c_void_p, C.c_int, _c_dp, _c_dp, _c_dp]),
     "boss_kgp_create": (C.c_int, [C.c_int, C.c_int, C.c_int, _c_dp, _c_dp, _c_ucp, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "boss_kern_grad_host": (C.c_int, [C.c_void_p, C.c_int, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
+    "boss_kgp_set_grad": (C.c_int, [C.c_void_p, C.c_int]),
     "boss_warp_create": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
     "boss_warp_free": (None, [C.c_void_p]),
     "boss_warp_apply_host": (C.c_int, [C.c_void_p, C.c_int, _c_dp, _c_dp, _c_dp]),
@@ -1918,6 +1920,17 @@ class KernelProgram:
         _check(load_library().boss_kern_eval_host(self._h, Uf.shape[1], _dp(Uf), _dp(Vf), _dp(k)))
         return float(k[0]) if one else k
 
+    def grad(self, U, V):
+        """(k, dU, dV) through boss_kern_grad_host: the program's value and its partials ∂f/∂u, ∂f/∂v (d×n each, or length d for two
+        points) by the reverse sweep the gradient kernels run; a local partial of exactly 0 passes 0 on (finite at coincident
+        points)."""
+        U, V, one = self._pairs(U, V)
+        Uf, Vf = np.asfortranarray(U), np.asfortranarray(V)
+        n = Uf.shape[1]
+        k, dU, dV = np.zeros(n), np.zeros((self.d, n), order="F"), np.zeros((self.d, n), order="F")
+        _check(load_library().boss_kern_grad_host(self._h, n, _dp(Uf), _dp(Vf), _dp(k), _dp(dU), _dp(dV)))
+        return (float(k[0]), dU[:, 0].copy(), dV[:, 0].copy()) if one else (k, dU, dV)
+
     def close(self):
         if self._h:
             load_library().boss_kern_free(self._h)
@@ -1932,9 +1945,10 @@ class KernelProgram:
 
 class KernelGP(GP):
     """One output slice's posterior under a KernelProgram (boss_kgp_create): update, sync, predict, set_y, factor and acq_ei work as
-    for a GP; every other call of the base class is refused by the library (BOSS_E_INVALID, "program-kernel posteriors")."""
+    for a GP; every other call of the base class is refused by the library (BOSS_E_INVALID, "program-kernel posteriors").
+    grad=True (boss_kgp_set_grad) adds loglike_grad, loglike_grad_mean, predict_grad, acq_ei_grad and acq_ei_grad_set."""
 
-    def __init__(self, X, y, kern: KernelProgram, discrete=None, device: int = 0):
+    def __init__(self, X, y, kern: KernelProgram, discrete=None, device: int = 0, grad: bool = False):
         lib = load_library()
         X = _f64(X, 2)
         y = _f64(np.asarray(y).reshape(-1), 1)
@@ -1950,6 +1964,13 @@ class KernelGP(GP):
         _check(lib.boss_kgp_create(device, self.d, self.N, _dp(X), _dp(y), _ucp(disc), kern._h, C.byref(h)))
         self._h = h
         self.logpdf = None
+        self.grad = bool(grad)
+        if self.grad:
+            try:
+                _check(lib.boss_kgp_set_grad(self._h, 1))
+            except Exception:
+                self.close()
+                raise
 
 
 def _mc_common(fit: FitnessProgram, eps, y_max, valid_mask):

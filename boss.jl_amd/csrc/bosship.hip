@@ -401,6 +401,8 @@ static int ctx_init(Ctx* c) {
                                PredictLds<PredG64>::BYTES));
     HIPCHK(hipFuncSetAttribute((const void*)ei_mc_grad_set_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, MC_GRAD_MAX_LDS));
     HIPCHK(hipFuncSetAttribute((const void*)mean_eval_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, MEAN_MAX_LDS));
+    HIPCHK(hipFuncSetAttribute((const void*)kprog_llgrad_tile_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, KPROG_GRAD_MAX_LDS));
+    HIPCHK(hipFuncSetAttribute((const void*)kprog_grad_accum_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, KPROG_GRAD_MAX_LDS));
     return BOSS_OK;
 }
 
@@ -563,6 +565,7 @@ struct boss_gp {
     // program-kernel posterior (boss_kgp_create, host_kprog.inc): the covariance function is the traced program *kp (the handle's own
     // copy), kernel == KERN_PROGRAM; Xsc holds the scaled points as for the plain model
     bool kprog = false;
+    bool kgrad = false;                                      // boss_kgp_set_grad: the gradient entry points take this handle
     FitProg* kp = nullptr;
     // explicit L⁻ᵀ for calls with one to four candidates (built on the second such call on a factorisation)
     double *Winv = nullptr, *Linv = nullptr;   // L⁻ᵀ (upper) and L⁻¹ (lower)
@@ -683,6 +686,9 @@ static bool few_fused() {
 static void kprog_gram_launch(boss_gp* g, hipStream_t s);
 static void kprog_kstar_launch(boss_gp* g, const boss_cand* cd, const double* Csc, int BN, int tiles, double* out, double* pvar, hipStream_t s);
 static void kprog_var_launch(hipStream_t s, double* var, const double* pvar, int M);
+static void kprog_llgrad_launch(boss_gp* g, hipStream_t s, int ntiles, const double* Kinv, const double* apart, int nch, double* parts);
+static void kprog_grad_accum_launch(boss_gp* g, const boss_cand* cd, hipStream_t s, int tiles, int rsplit, const double* slabs, const double* Csc,
+                                    const double* mean_grad_dev, double* dmu, double* dvar, double* part);
 #include "host_factor.inc"
 #include "host_append.inc"
 #include "host_batch.inc"

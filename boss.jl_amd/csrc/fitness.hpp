@@ -67,11 +67,16 @@ __host__ __device__ inline double fit_eval(const FitProg& g, const double* y, do
 // here).  Conventions: ABS'(0) = 0; MIN / MAX pass the derivative to the FIRST operand on a tie; SQRT'(0) = +Inf; POW(a, b)
 // differentiates in both operands, the ∂/∂b term dropped when b is a constant id (a < 0 with an integer constant exponent gives no
 // NaN).  An instruction whose adjoint is exactly 0 is skipped (it passes nothing on, whatever its partial derivatives are).
+// KZERO (kernel programs, kern_grad): a local partial that is exactly 0 passes 0 on as well, whatever the adjoint is (0·±Inf = 0).
+// A kernel spelled through a distance — exp(-sqrt(r2)), sqrt(5 r2) — meets SQRT'(0) = +Inf times SQUARE' = 2·0 at coincident points
+// (the Gram diagonal, a candidate on a training point); the 0 is the Matérn family's true derivative at r = 0 and what
+// KernelFunctions / Distances return for the exponential kernel.
 __host__ __device__ inline void fit_adj_add(const FitProg& g, double* ay, double* av, int st, int id, double w) {
     if (id < g.P) ay[(size_t)id * st] += w;
     else if (id >= g.P + g.nC) av[(size_t)(id - g.P - g.nC) * st] += w;
 }
-__host__ __device__ inline void fit_grad(const FitProg& g, const double* y, const double* v, double* ay, double* av, int st) {
+template <bool KZERO>
+__host__ __device__ inline void fit_grad_sweep(const FitProg& g, const double* y, const double* v, double* ay, double* av, int st) {
     for (int p = 0; p < g.P; ++p) ay[(size_t)p * st] = 0.0;
     for (int i = 0; i < g.nI; ++i) av[(size_t)i * st] = 0.0;
     fit_adj_add(g, ay, av, st, g.out, 1.0);
@@ -104,9 +109,16 @@ __host__ __device__ inline void fit_grad(const FitProg& g, const double* y, cons
             case FIT_MIN: if (x <= z) da = 1.0; else db = 1.0; break;
             default: if (x >= z) da = 1.0; else db = 1.0; break;   // FIT_MAX
         }
-        fit_adj_add(g, ay, av, st, ia, w * da);
-        if (ib != FIT_NOARG) fit_adj_add(g, ay, av, st, ib, w * db);
+        fit_adj_add(g, ay, av, st, ia, (KZERO && da == 0.0) ? 0.0 : w * da);
+        if (ib != FIT_NOARG) fit_adj_add(g, ay, av, st, ib, (KZERO && db == 0.0) ? 0.0 : w * db);
     }
+}
+__host__ __device__ inline void fit_grad(const FitProg& g, const double* y, const double* v, double* ay, double* av, int st) {
+    fit_grad_sweep<false>(g, y, v, ay, av, st);
+}
+// ... of a kernel program over u | v: ay[0..d) = ∂f/∂u, ay[d..2d) = ∂f/∂v
+__host__ __device__ inline void kern_grad(const FitProg& g, const double* y, const double* v, double* ay, double* av, int st) {
+    fit_grad_sweep<true>(g, y, v, ay, av, st);
 }
 
 #ifdef __HIPCC__

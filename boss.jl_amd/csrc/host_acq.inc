@@ -293,6 +293,8 @@ static int llgrad_enqueue(boss_gp* g, hipStream_t s, double* sums_out, int bank,
         hipLaunchKernelGGL(aug_llgrad_tile_kernel, dim3(ntiles, 1, nb), dim3(256), 0, s, (const double*)g->Xraw, g->ldx, d, g->nhead, N, Np,
                            g->kernel, (const double*)g->hyp, (const double*)g->invlam, zPar, (const double*)Kinv, ld, (const double*)apart, nch,
                            parts, Bw.sW, zC);
+    else if (g->kprog)
+        kprog_llgrad_launch(g, s, ntiles, Kinv, apart, nch, parts);   // (one posterior: the batched calls are built-in only)
     else
     hipLaunchKernelGGL(llgrad_tile_kernel, dim3(ntiles, 1, nb), dim3(256), 0, s, (const double*)g->Xsc, d, N, Np, g->kernel, amp2_dev,
                        amp2_stride, (const double*)Kinv, ld, (const double*)apart, nch, parts, B.sX, Bw.sW, nb > 1 ? sC : (size_t)0,
@@ -330,7 +332,8 @@ static int llgrad_download(boss_gp* g, std::vector<double>& h, size_t n_mean = 0
 
 extern "C" int boss_gp_loglike_grad(boss_gp_t* g, double* logpdf_out, double* grad_out) {
     if (!g || !grad_out) return fail(BOSS_E_INVALID, "NULL argument");
-    NOT_FOR_AUG(g);
+    NOT_FOR_MODELS(g);
+    KPROG_NEEDS_GRAD(g);
     Ctx* c = g->ctx;
     HIPCHK(hipSetDevice(c->device));
     std::lock_guard<std::mutex> lk(c->mtx);
@@ -339,7 +342,7 @@ extern "C" int boss_gp_loglike_grad(boss_gp_t* g, double* logpdf_out, double* gr
     const int d = g->d, nv = d + 2;
     if (d > LLG_MAX_D) return fail(BOSS_E_INVALID, "x_dim too large for the likelihood-gradient kernel");
     hipStream_t s = c->stream;
-    if (small_fit_ok(c, g->N, d) && !g->gibbs) {
+    if (small_fit_ok(c, g->N, d) && !g->gibbs && !g->kprog) {
         // N <= 128: one workgroup, one launch, the Σ-vector lands in mapped host memory (small_llgrad_kernel)
         dinv_join(g);
         hipLaunchKernelGGL(small_llgrad_kernel, dim3(1), dim3(DIAG_THREADS), SMALL_LLG_LDS_BYTES, s, (const double*)g->A, g->ld, g->Np,
@@ -379,7 +382,8 @@ extern "C" int boss_gp_loglike_grad(boss_gp_t* g, double* logpdf_out, double* gr
 // Both paths keep a on the device anyway; here it comes back with the Σ-vector in one copy and one synchronisation.
 extern "C" int boss_gp_loglike_grad_mean(boss_gp_t* g, double* logpdf_out, double* grad_out, double* dmean_out) {
     if (!g || !grad_out || !dmean_out) return fail(BOSS_E_INVALID, "NULL argument");
-    NOT_FOR_AUG(g);                                          // (the nonstationary model has boss_ngp_loglike_grad's dmean_out)
+    NOT_FOR_MODELS(g);                                       // (the nonstationary model has boss_ngp_loglike_grad's dmean_out)
+    KPROG_NEEDS_GRAD(g);
     Ctx* c = g->ctx;
     HIPCHK(hipSetDevice(c->device));
     std::lock_guard<std::mutex> lk(c->mtx);
@@ -389,7 +393,7 @@ extern "C" int boss_gp_loglike_grad_mean(boss_gp_t* g, double* logpdf_out, doubl
     if (d > LLG_MAX_D) return fail(BOSS_E_INVALID, "x_dim too large for the likelihood-gradient kernel");
     hipStream_t s = c->stream;
     std::vector<double> h((size_t)nv + N);
-    if (small_fit_ok(c, N, d)) {
+    if (small_fit_ok(c, N, d) && !g->kprog) {
         // N <= 128: the one-launch kernel, its results in device memory this time (N + d + 2 doubles, one copy back)
         rc = ws_reserve(c->pred, sizeof(double) * h.size());
         if (rc) return rc;

@@ -777,6 +777,13 @@ extern "C" int boss_ggp_create(int device, int kernel, int d, int n, const doubl
         if ((g)->gibbs) return fail(BOSS_E_INVALID, "not available for nonstationary posteriors (boss_ngp_*)");      \
     } while (0)
 
+// the gradient entry points: a program-kernel posterior is refused unless boss_kgp_set_grad switched its gradients on
+#define KPROG_NEEDS_GRAD(g)                                                                                                      \
+    do {                                                                                                                         \
+        if ((g)->kprog && !(g)->kgrad)                                                                                           \
+            return fail(BOSS_E_INVALID, "not available for program-kernel posteriors (boss_kgp_create) without boss_kgp_set_grad"); \
+    } while (0)
+
 #define NOT_FOR_AUG(g)      \
     do {                    \
         NOT_FOR_MODELS(g);  \
@@ -784,12 +791,16 @@ extern "C" int boss_ggp_create(int device, int kernel, int d, int n, const doubl
     } while (0)
 
 // entry points that take gradient-observation posteriors but not (yet) nonstationary ones; the former have no prior mean
-#define NOT_FOR_GIBBS(g, mean_a, mean_b)                                                                            \
+#define NOT_FOR_GIBBS_MODEL(g, mean_a, mean_b)                                                                      \
     do {                                                                                                            \
-        NOT_FOR_KPROG(g);                                                                                           \
         if ((g)->gibbs) return fail(BOSS_E_INVALID, "not available for nonstationary posteriors (boss_ngp_*)");        \
         if ((g)->aug && ((mean_a) || (mean_b)))                                                                      \
             return fail(BOSS_E_INVALID, "gradient-observation posteriors take no prior mean (gradient_gp.jl:307-361)"); \
+    } while (0)
+#define NOT_FOR_GIBBS(g, mean_a, mean_b)           \
+    do {                                           \
+        NOT_FOR_KPROG(g);                          \
+        NOT_FOR_GIBBS_MODEL(g, mean_a, mean_b);    \
     } while (0)
 
 // NonstationaryGP (src/models/nonstationary_gp/nonstationary_gp.jl): the data of one output slice; the

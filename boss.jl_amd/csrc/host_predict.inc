@@ -214,8 +214,8 @@ static int predict_enqueue(boss_gp* g, const boss_cand* cd, const double* mean_s
     if (!g->fitted) return fail(BOSS_E_NOT_FITTED, "handle has no valid factorisation");
     if (g->gibbs && !clam_dev)
         return fail(BOSS_E_INVALID, "nonstationary posteriors predict through boss_ngp_predict (λ(x*), α(x*) are needed)");
-    if (g->kprog && (for_grad || need_v))
-        return fail(BOSS_E_INVALID, "not available for program-kernel posteriors (boss_kgp_create): gradients and covariances");
+    if (g->kprog && ((for_grad && !g->kgrad) || need_v))
+        return fail(BOSS_E_INVALID, "not available for program-kernel posteriors (boss_kgp_create): covariances, and gradients without boss_kgp_set_grad");
     if (cd->ctx != c) return fail(BOSS_E_INVALID, "candidates and posterior live on different devices");
     if (cd->d != g->d) return fail(BOSS_E_INVALID, "candidate dimension differs from the model's x_dim");
     if (!for_grad && !need_v && small_predict_ok(g, cd->M)) {
@@ -1042,6 +1042,7 @@ static int grad_enqueue(boss_gp* g, const boss_cand* cd, const double* mean_s_de
         HIPCHK(hipGetLastError());
         return BOSS_OK;
     }
+    if (g->kprog && d > GRAD_MAX_D) return fail(BOSS_E_INVALID, "x_dim too large for the program-kernel gradient kernel");
     // few tiles: split the rows of every tile over several workgroups (one workgroup per tile would walk all N rows alone)
     int rsplit = 1;
     if (d <= GRAD_MAX_D && tiles < 128) {
@@ -1054,6 +1055,9 @@ static int grad_enqueue(boss_gp* g, const boss_cand* cd, const double* mean_s_de
         if (rc) return rc;
         part = (double*)c->few.p;                          // the forward pass's residuals are dead by now
     }
+    if (g->kprog)
+        kprog_grad_accum_launch(g, cd, s, tiles, rsplit, slabs, (const double*)c->csc.p, mean_grad_dev, dmu, dvar, part);
+    else
     hipLaunchKernelGGL(grad_accum_kernel, dim3(tiles, rsplit), dim3(256), glds, s, (const double*)slabs, (const double*)g->avec, Np,
                        g->N, (const double*)g->Xsc, (const double*)c->csc.p, d, cd->Mp, M, g->kernel, g->amp2,
                        (const double*)g->invlam, (const unsigned char*)g->discrete_dev, mean_grad_dev, dmu, dvar, part);
@@ -1067,7 +1071,8 @@ static int grad_enqueue(boss_gp* g, const boss_cand* cd, const double* mean_s_de
 extern "C" int boss_gp_predict_grad(boss_gp_t* g, int M, const double* Xs, const double* mean_Xs, const double* mean_grad,
                                     double* mu, double* var, double* dmu, double* dvar, long* bad_index) {
     if (!g || !Xs || !mu || !var || !dmu || !dvar) return fail(BOSS_E_INVALID, "NULL argument");
-    NOT_FOR_GIBBS(g, mean_Xs, mean_grad);
+    KPROG_NEEDS_GRAD(g);
+    NOT_FOR_GIBBS_MODEL(g, mean_Xs, mean_grad);
     if (M < 1) return fail(BOSS_E_INVALID, "M must be >= 1");
     if (bad_index) *bad_index = -1;
     if (!g->fitted) return fail(BOSS_E_NOT_FITTED, "handle has no valid factorisation");
@@ -1207,7 +1212,8 @@ extern "C" int boss_acq_ei_grad(int P, boss_gp_t* const* gps, int M, const doubl
     if (P < 1 || !gps || M < 1 || !Xs || !fit_coefs || !acq_out || !dacq_out) return fail(BOSS_E_INVALID, "bad arguments");
     for (int p = 0; p < P; ++p) {
         if (!gps[p]) return fail(BOSS_E_INVALID, "NULL posterior handle");
-        NOT_FOR_GIBBS(gps[p], mean_Xs, mean_grad);
+        KPROG_NEEDS_GRAD(gps[p]);                            // (so a call mixing flagged and unflagged program handles is refused)
+        NOT_FOR_GIBBS_MODEL(gps[p], mean_Xs, mean_grad);
         if (gps[p]->ctx != gps[0]->ctx || gps[p]->d != gps[0]->d)
             return fail(BOSS_E_INVALID, "all handles must live on one device and share x_dim");
         if (!gps[p]->fitted) return fail(BOSS_E_NOT_FITTED, "handle has no valid factorisation");
@@ -1427,7 +1433,9 @@ static int acq_ei_grad_set_impl(int P, int S, boss_gp_t* const* gps, int M, cons
     const int n = P * S;
     for (int i = 0; i < n; ++i) {
         if (!gps[i]) return fail(BOSS_E_INVALID, "NULL posterior handle");
-        NOT_FOR_GIBBS(gps[i], mean_Xs, mean_grad);
+        if (mc) NOT_FOR_KPROG(gps[i]);                       // (Monte-Carlo EI: built-in kernels only)
+        KPROG_NEEDS_GRAD(gps[i]);                            // (flagged program handles go member by member: grad_set_ok)
+        NOT_FOR_GIBBS_MODEL(gps[i], mean_Xs, mean_grad);
         if (gps[i]->ctx != gps[0]->ctx || gps[i]->d != gps[0]->d)
             return fail(BOSS_E_INVALID, "all handles must live on one device and share x_dim");
     }

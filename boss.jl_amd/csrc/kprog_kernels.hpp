@@ -24,6 +24,8 @@ constexpr int KERN_PROGRAM = 4;                               // internal id of 
 constexpr int KPROG_MAX_D = 16;                               // 2·d inputs <= MEAN_MAXIN = 32
 constexpr int KPROG_MAX_WAVES = 4;
 __host__ __device__ constexpr int kprog_slots(int d, int nI) { return 2 * d + nI; }
+__host__ __device__ constexpr int kprog_grad_slots(int d, int nI) { return 2 * kprog_slots(d, nI); }   // values, then adjoints
+constexpr int KPROG_GRAD_MAX_LDS = 64 * (int)sizeof(double) * kprog_grad_slots(KPROG_MAX_D, FIT_MAXI);   // one wave of the longest program: 96 KiB
 
 #ifdef __HIPCC__
 // f(a, b) for the points a = A[·][ia], b = B[·][ib] (dimension-major, leading dimensions lda / ldb) in this thread's LDS column
@@ -90,6 +92,180 @@ __global__ __launch_bounds__(64 * KPROG_MAX_WAVES) void kprog_kstar_kernel(FitPr
 __global__ void kprog_var_kernel(double* __restrict__ var, const double* __restrict__ pvar, int M) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j < M) var[j] = pvar[j] + var[j] + PREDICT_JITTER;
+}
+// ------------------------------------------------------------------------------------------
+// Gradients of a program-kernel posterior (boss_kgp_set_grad): the reverse sweep kern_grad behind fit_eval gives all 2d partials
+// f_u = ∂f/∂u, f_v = ∂f/∂v of a pair.  A column then holds 2·(2d + nI) doubles, values | adjoints (kprog_grad_slots): the longest
+// program takes 96 KiB for one wave, so both kernels opt in to the larger dynamic LDS (KPROG_GRAD_MAX_LDS, within a CU's 160 KiB).
+// ------------------------------------------------------------------------------------------
+// f(a, b) as kprog_pair, then the sweep: ay[0..d) = f_u, ay[d..2d) = f_v in the column's adjoint slots
+__device__ __forceinline__ double kprog_pair_grad(const FitProg& g, int d, const double* __restrict__ A, int lda, int ia,
+                                                  const double* __restrict__ B, int ldb, int ib, double* __restrict__ col, int st) {
+    const double f = kprog_pair(g, d, A, lda, ia, B, ldb, ib, col, st);
+    double* v = col + (size_t)2 * d * st;
+    double* ay = v + (size_t)g.nI * st;
+    kern_grad(g, col, v, ay, ay + (size_t)2 * d * st, st);
+    return f;
+}
+
+// Likelihood gradient: the Σ-vector of llgrad_tile_kernel per 64×64 tile of the lower triangle, out[tile][0..d-1] = S_m,
+// out[tile][d] = Σ_i K⁻¹_ii, out[tile][d+1] = Σ_i a_i² (diagonal tiles), with G = a aᵀ − K⁻¹ and the stored entry (i, j), i > j, being
+// f(u_j, u_i):
+//     S_m = Σ_{i>j} G_ij α² D_m(j, i) + ½ Σ_i G_ii α² D_m(i, i) ,   D_m(a, b) = f_u,m u_a,m + f_v,m u_b,m
+// (K = α² F + σ² I for any F: llgrad_reduce_kernel and llgrad_finalize follow unchanged, ∂ℓ/∂λ_m = −S_m/(λ_m+1e-8)).  The diagonal term
+// is real: a dot-product kernel's k(x, x) depends on λ.  D_m is evaluated as (f_u,m + f_v,m) u_b,m + f_u,m (u_a,m − u_b,m): for a
+// stationary kernel the first term is rounding noise and the second the difference form grad_accum_body's comment argues for.
+// A thread keeps its row i (its lane) and walks the tile's columns; sums: per thread in ascending column, butterfly over the wave,
+// waves in ascending order — no atomics, repeated calls agree bit for bit.
+__global__ __launch_bounds__(64 * KPROG_MAX_WAVES) void kprog_llgrad_tile_kernel(FitProg g, const double* __restrict__ Xsc, int d, int N, int Np,
+                                                                                 const double* __restrict__ hyp,
+                                                                                 const double* __restrict__ Kinv, int ldk,
+                                                                                 const double* __restrict__ apart, int nch,
+                                                                                 double* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) char kprog_lds_raw[];
+    double* col = reinterpret_cast<double*>(kprog_lds_raw) + threadIdx.x;
+    __shared__ double aj[64];
+    __shared__ double red[KPROG_MAX_WAVES];
+    const int st = blockDim.x, tid = threadIdx.x, t = blockIdx.x, lane = tid & 63, wave = tid >> 6, nw = st >> 6;
+    int bi = (int)((sqrt(8.0 * t + 1.0) - 1.0) * 0.5);
+    while ((bi + 1) * (bi + 2) / 2 <= t) ++bi;
+    while (bi * (bi + 1) / 2 > t) --bi;
+    const int bj = t - bi * (bi + 1) / 2;
+    const double amp2 = hyp[0];
+    if (tid < 64) {
+        double s = 0.0;
+        for (int c = 0; c < nch; ++c) s += apart[(size_t)c * Np + bj * 64 + tid];
+        aj[tid] = s;
+    }
+    const int i = bi * 64 + lane;
+    double ai = 0.0;
+    for (int c = 0; c < nch; ++c) ai += apart[(size_t)c * Np + i];
+    __syncthreads();
+    const double* fu = col + (size_t)(2 * d + g.nI) * st;     // the adjoint slots of this column: f_u[d] | f_v[d]
+    const double* fv = fu + (size_t)d * st;
+    double S[KPROG_MAX_D];
+#pragma unroll
+    for (int m = 0; m < KPROG_MAX_D; ++m) S[m] = 0.0;
+    double tr = 0.0, aa = 0.0;
+    for (int jl = wave; jl < 64; jl += nw) {
+        const int j = bj * 64 + jl;
+        if (i >= N || j >= N || i < j) continue;
+        const double kinv = Kinv[(size_t)j * ldk + i];
+        (void)kprog_pair_grad(g, d, Xsc, Np, j, Xsc, Np, i, col, st);   // a = j, b = i
+        double q = amp2 * (ai * aj[jl] - kinv);
+        if (i == j) {
+            tr += kinv;
+            aa += ai * ai;
+            q *= 0.5;
+        }
+#pragma unroll
+        for (int m = 0; m < KPROG_MAX_D; ++m)
+            if (m < d) {
+                const double ua = col[(size_t)m * st], ub = col[(size_t)(d + m) * st], pu = fu[(size_t)m * st], pv = fv[(size_t)m * st];
+                S[m] = __builtin_fma(q, __builtin_fma(pu + pv, ub, pu * (ua - ub)), S[m]);
+            }
+    }
+    for (int m = 0; m < d + 2; ++m) {
+        double v = 0.0;
+#pragma unroll
+        for (int mm = 0; mm < KPROG_MAX_D; ++mm)
+            if (mm == m) v = S[mm];
+        if (m >= d) v = (m == d) ? tr : aa;
+        v = wave_sum(v);
+        __syncthreads();
+        if (lane == 0) red[wave] = v;
+        __syncthreads();
+        if (tid == 0) {
+            double s = 0.0;
+            for (int w = 0; w < nw; ++w) s += red[w];
+            out[(size_t)t * (d + 2) + m] = s;
+        }
+    }
+}
+
+// ∇μ, ∇σ² from the W slabs (the place grad_accum_kernel takes for the built-in kernels; same grid, same part layout, so
+// grad_finalize_kernel finishes a split tile).  Per candidate j and dimension m, 1/λ_m short for 1/(λ_m+1e-8):
+//     ∇μ_m  = ∇m_m + (1/λ_m) Σ_i a_i α² f_v,m(u_i, u*_j)
+//     ∇σ²_m = (1/λ_m) α² (f_u,m + f_v,m)(u*_j, u*_j) − (2/λ_m) Σ_i w_ij α² f_v,m(u_i, u*_j)
+// The sums T1 = Σ a_i α² f_v,m and T2 = Σ w_ij α² f_v,m go to the slots grad_accum_body uses; the prior variance's own gradient rides
+// in T2 as −½ α² (f_u,m + f_v,m)(u*_j, u*_j), added once per candidate (row split 0, row subset 0) — exactly 0 for a stationary kernel.
+// Lanes run along the tile's 32 candidates, blockDim.x / 32 row subsets; the sums of the subsets are added in ascending order.
+__global__ __launch_bounds__(64 * KPROG_MAX_WAVES) void kprog_grad_accum_kernel(FitProg g, const double* __restrict__ Wslabs,
+                                                                                const double* __restrict__ avec, int Np, int N,
+                                                                                const double* __restrict__ Xsc, const double* __restrict__ Csc,
+                                                                                int d, int Mp, int M, double amp2,
+                                                                                const double* __restrict__ invlam,
+                                                                                const unsigned char* __restrict__ discrete,
+                                                                                const double* __restrict__ mean_grad, double* __restrict__ dmu,
+                                                                                double* __restrict__ dvar, double* __restrict__ part) {
+    constexpr int BN = 32, NS = 2 * (GRAD_MAX_D + 1);
+    extern __shared__ __attribute__((aligned(16))) char kprog_lds_raw[];
+    double* lds = reinterpret_cast<double*>(kprog_lds_raw);
+    double* col = lds + threadIdx.x;
+    const int st = blockDim.x, tid = threadIdx.x, c = tid & 31, rs = tid >> 5, nrs = st >> 5;
+    const int bx = blockIdx.x, by = blockIdx.y, ny = gridDim.y;
+    const double* W = Wslabs + (size_t)bx * Np * BN;
+    const int j = bx * BN + c;                               // (candidates >= M are padding inside Mp: evaluated, never written)
+    const double* fu = col + (size_t)(2 * d + g.nI) * st;
+    const double* fv = fu + (size_t)d * st;
+    double T1[GRAD_MAX_D], T2[GRAD_MAX_D];
+#pragma unroll
+    for (int m = 0; m < GRAD_MAX_D; ++m) T1[m] = T2[m] = 0.0;
+    if (by == 0 && rs == 0) {
+        (void)kprog_pair_grad(g, d, Csc, Mp, j, Csc, Mp, j, col, st);
+#pragma unroll
+        for (int m = 0; m < GRAD_MAX_D; ++m)
+            if (m < d) T2[m] = -0.5 * amp2 * (fu[(size_t)m * st] + fv[(size_t)m * st]);
+    }
+    const int nchunk = (N + GRAD_CHUNK - 1) / GRAD_CHUNK;
+    const int cpb = (nchunk + ny - 1) / ny;
+    const int rbeg = by * cpb * GRAD_CHUNK;
+    const int rend = (rbeg + cpb * GRAD_CHUNK < N) ? rbeg + cpb * GRAD_CHUNK : N;
+    for (int r = rbeg + rs; r < rend; r += nrs) {
+        const double qa = amp2 * avec[r], qw = amp2 * W[(size_t)r * BN + c];
+        (void)kprog_pair_grad(g, d, Xsc, Np, r, Csc, Mp, j, col, st);
+#pragma unroll
+        for (int m = 0; m < GRAD_MAX_D; ++m)
+            if (m < d) {
+                const double p = fv[(size_t)m * st];
+                T1[m] = __builtin_fma(qa, p, T1[m]);
+                T2[m] = __builtin_fma(qw, p, T2[m]);
+            }
+    }
+    __syncthreads();                                         // the columns are done: their LDS becomes red[nrs][NS][BN]
+    double* rd = lds + (size_t)rs * NS * BN;
+    rd[0 * BN + c] = 0.0;                                    // (slots 0, 1 of the layout are not used)
+    rd[1 * BN + c] = 0.0;
+#pragma unroll
+    for (int m = 0; m < GRAD_MAX_D; ++m) {
+        rd[(2 + 2 * m) * BN + c] = T1[m];
+        rd[(3 + 2 * m) * BN + c] = T2[m];
+    }
+    __syncthreads();
+    if (ny > 1) {
+        // this workgroup's sums (over its row subsets) go to global; grad_finalize_kernel finishes
+        double* pw = part + ((size_t)bx * ny + by) * NS * BN;
+        for (int slot = rs; slot < NS; slot += nrs) {
+            double v = 0.0;
+            for (int k = 0; k < nrs; ++k) v += lds[((size_t)k * NS + slot) * BN + c];
+            pw[slot * BN + c] = v;
+        }
+        return;
+    }
+    if (rs == 0 && j < M) {
+        for (int m = 0; m < d; ++m) {
+            double t1 = 0.0, t2 = 0.0;
+            for (int k = 0; k < nrs; ++k) {
+                const double* rk = lds + (size_t)k * NS * BN;
+                t1 += rk[(2 + 2 * m) * BN + c];
+                t2 += rk[(3 + 2 * m) * BN + c];
+            }
+            const double il = invlam[m];
+            const bool disc = discrete && discrete[m];
+            dmu[(size_t)j * d + m] = (disc ? 0.0 : t1 * il) + (mean_grad ? mean_grad[(size_t)j * d + m] : 0.0);
+            dvar[(size_t)j * d + m] = disc ? 0.0 : -2.0 * t2 * il;
+        }
+    }
 }
 #endif  // __HIPCC__
 

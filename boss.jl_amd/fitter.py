@@ -17,7 +17,7 @@ import numpy as np
 
 from . import api
 from . import distributed as dist_util
-from .kernel import refuse_device_kernel
+from .kernel import device_kernel_of, refuse_device_kernel
 from .mean import device_mean_of
 from .model import HipGaussianProcess, HipGPParams
 from .problem import BossOptions, BossProblem, Dirac, MvDirac, Normal
@@ -91,6 +91,18 @@ class HipGradientMAP:
         d, P = plist[0].lengthscales.shape
         tot = np.array([prior_ll(p) for p in plist], dtype=float)
         gl, ga, gs = np.zeros((S, d, P)), np.zeros((S, P)), np.zeros((S, P))
+        if device_kernel_of(model) is not None:
+            # a DeviceKernel(grad=True): the batched call is built-in-kernel only, the model runs update + gradient per set on
+            # one resident handle per output (data_loglike_grad_batch)
+            lls, gparams = model.data_loglike_grad_batch(data, plist)
+            for k, p in enumerate(plist):
+                tot[k] += lls[k]
+                gl[k], ga[k], gs[k] = gparams[k].lengthscales, gparams[k].amplitudes, gparams[k].noise_std
+                for i in range(P):
+                    gl[k, :, i] += np.atleast_1d(model.lengthscale_priors[i].grad_logpdf(p.lengthscales[:, i]))
+                    ga[k, i] += model.amplitude_priors[i].grad_logpdf(p.amplitudes[i])
+                    gs[k, i] += model.noise_std_priors[i].grad_logpdf(p.noise_std[i])
+            return np.where(np.isfinite(tot), tot, -np.inf), gl, ga, gs
         dev = model.mean_values_all(data.X, None) if device_mean_of(model) is not None else None   # a DeviceMean: all outputs in one call
         for i in range(P):
             lam = np.stack([p.lengthscales[:, i] for p in plist], axis=1)
@@ -160,7 +172,7 @@ class HipGradientMAP:
     def estimate_parameters(self, problem: BossProblem, options: BossOptions = BossOptions(), return_all: bool = False):
         problem = base_problem(problem)                      # a HipTransformedModel: its base model on the transformed data
         model = problem.model
-        refuse_device_kernel(model, "HipGradientMAP (likelihood gradients)")
+        refuse_device_kernel(model, "HipGradientMAP (likelihood gradients)", grad_ok=True)
         grad_model = hasattr(model, "grad_noise_std_priors")        # HipGradientGaussianProcess (gradient_gp.py)
         semipar = not grad_model and model.parametric is not None
         if semipar:
@@ -276,7 +288,8 @@ class HipSampleOptMAP:
         assert self.samples >= self.multistart                       # sample_opt.jl:30
 
     def estimate_parameters(self, problem: BossProblem, options: BossOptions = BossOptions(), return_all: bool = False):
-        refuse_device_kernel(base_problem(problem).model, "HipSampleOptMAP (its HipGradientMAP stage needs likelihood gradients)")
+        refuse_device_kernel(base_problem(problem).model, "HipSampleOptMAP (its HipGradientMAP stage needs likelihood gradients)",
+                             grad_ok=True)
         scored = HipBatchedMAP(self.samples, self.seed, self.group).estimate_parameters(problem, options, return_all=True)
         order = sorted(range(len(scored)), key=lambda i: -scored[i].loglike)             # sortperm(...; rev=true), stable
         starts = [scored[i].params for i in order[:self.multistart]]

@@ -11,6 +11,13 @@ Limits: x_dim <= 16 (32 inputs), 32 constants, 64 instructions.  The traced prog
 closure, and for symmetry — f(u, v) and f(v, u) may differ by 16 ulp of |f|, or of the largest |f| over the test pairs where f is
 smaller than that (the order of a sum), an asymmetric function is not a kernel.  Hyper-parameters beyond λ, α, σ (the shape of a
 rational-quadratic kernel, a period) are traced constants.
+
+DeviceKernel(f, x_dim, grad=True) switches the model's gradients on (boss_kgp_set_grad): mean_and_var_grad, data_loglike_grad_batch,
+HipGradientMAP, HipSampleOptMAP and HipGradientAM then work as for a built-in kernel.  Tracing then also checks the DERIVATIVE
+program (api.KernelProgram.grad, the reverse sweep the gradient kernels run): at the 8 seeded pairs every partial ∂f/∂u, ∂f/∂v must be
+finite and agree with central differences of the closure (h = 1e-5) within 1e-6·max(1, |∂f|) — truncation is of order h², rounding of
+order ε/h, both far below that —, and at 8 coincident pairs (u, u) every partial must be finite (a one-sided cusp has no central
+difference to agree with; the sweep passes a local partial of exactly 0 on as 0, which is what makes exp(-sqrt(r2)) finite there).
 """
 from __future__ import annotations
 
@@ -25,8 +32,38 @@ _LABEL = "DeviceKernel"
 _SYM_ULPS = 16.0                                             # |f(u, v) − f(v, u)| <= 16 · 2⁻⁵² · |f|: re-ordered sums and products
 
 
-def trace_kernel(closure: Callable, x_dim: int) -> api.KernelProgram:
-    """Trace `closure` on two symbolic points of x_dim entries and check the program.  ValueError names what failed."""
+_FD_H, _FD_TOL = 1e-5, 1e-6
+
+
+def _check_derivative(closure: Callable, prog: api.KernelProgram, U, V):
+    """The grad=True validation of the derivative program (module docstring).  ValueError names what failed."""
+    d = prog.d
+    _, dU, dV = prog.grad(U, V)
+    _, cU, cV = prog.grad(U, U)
+    for what, arrs in (("a test pair", (dU, dV)), ("a coincident pair (u, u)", (cU, cV))):
+        for side, a in zip("uv", arrs):
+            if not np.all(np.isfinite(a)):
+                m, k = (int(i[0]) for i in np.nonzero(~np.isfinite(a)))
+                raise ValueError(f"{_LABEL}: grad=True, but the derivative program gives ∂f/∂{side}[{m}] = {a[m, k]!r} at {what}: "
+                                 "every partial must be finite")
+    with np.errstate(all="ignore"):
+        for k in range(U.shape[1]):
+            for side, got in (("u", dU), ("v", dV)):
+                for m in range(d):
+                    pts = []
+                    for sgn in (1.0, -1.0):
+                        u, v = U[:, k].copy(), V[:, k].copy()
+                        (u if side == "u" else v)[m] += sgn * _FD_H
+                        pts.append(float(closure(u, v)))
+                    fd = (pts[0] - pts[1]) / (2.0 * _FD_H)
+                    if not abs(got[m, k] - fd) <= _FD_TOL * max(1.0, abs(got[m, k])):
+                        raise ValueError(f"{_LABEL}: grad=True, but the derivative program disagrees with the closure's central "
+                                         f"differences at a test pair (∂f/∂{side}[{m}]: program {got[m, k]!r}, differences {fd!r})")
+
+
+def trace_kernel(closure: Callable, x_dim: int, grad: bool = False) -> api.KernelProgram:
+    """Trace `closure` on two symbolic points of x_dim entries and check the program — with grad=True its derivative program too.
+    ValueError names what failed."""
     d = int(x_dim)
     if d < 1 or d > api.KERN_MAX_DIM:
         raise ValueError(f"{_LABEL}: x_dim = {d}, a kernel program takes two points of 1 to {api.KERN_MAX_DIM} dimensions")
@@ -74,17 +111,20 @@ def trace_kernel(closure: Callable, x_dim: int) -> api.KernelProgram:
         k = int(np.flatnonzero(~sym)[0])
         raise ValueError(f"{_LABEL}: the closure is not symmetric (f(u, v) = {got[k]!r}, f(v, u) = {swapped[k]!r} at a test point): "
                          "an asymmetric function is not a kernel")
+    if grad:
+        _check_derivative(closure, prog, U, V)
     return prog
 
 
 class DeviceKernel:
     """The covariance closure with its traced program: HipGaussianProcess(kernel=DeviceKernel(f, x_dim)).  Calling it calls the
-    original closure.  `program` is the api.KernelProgram."""
+    original closure.  `program` is the api.KernelProgram.  grad=True: the model's handles carry gradients (module docstring)."""
 
-    def __init__(self, closure: Callable, x_dim: int):
+    def __init__(self, closure: Callable, x_dim: int, grad: bool = False):
         self.closure = closure
         self.x_dim = int(x_dim)
-        self.program = trace_kernel(closure, x_dim)
+        self.grad = bool(grad)
+        self.program = trace_kernel(closure, x_dim, self.grad)
 
     def __call__(self, u, v):
         return self.closure(u, v)
@@ -96,8 +136,14 @@ def device_kernel_of(model) -> Optional[DeviceKernel]:
     return k if isinstance(k, DeviceKernel) else None
 
 
-def refuse_device_kernel(model, what: str):
-    """NotImplementedError for the parts of the plugin surface a DeviceKernel model does not reach yet."""
-    if device_kernel_of(model) is not None:
-        raise NotImplementedError(f"{what} is not available for a model whose kernel is a DeviceKernel (a traced program kernel has no "
-                                  "candidate / likelihood gradients, covariances, appends, tracks or in-library multi-device path yet)")
+def refuse_device_kernel(model, what: str, grad_ok: bool = False):
+    """NotImplementedError for the parts of the plugin surface a DeviceKernel model does not reach.  grad_ok: the part needs only
+    gradients, which DeviceKernel(..., grad=True) provides."""
+    dk = device_kernel_of(model)
+    if dk is None or (grad_ok and dk.grad):
+        return
+    if grad_ok:
+        raise NotImplementedError(f"{what} is not available for a model whose kernel is a DeviceKernel traced without gradients: "
+                                  "DeviceKernel(f, x_dim, grad=True) switches candidate / likelihood gradients on")
+    raise NotImplementedError(f"{what} is not available for a model whose kernel is a DeviceKernel (a traced program kernel has no "
+                              "covariances, appends, tracks, warps or in-library multi-device path yet)")

@@ -550,7 +550,9 @@ class HipGradientAM:
         return acc / len(posts), gacc / len(posts)
 
     def maximize_acquisition(self, problem: BossProblem, options: BossOptions = BossOptions(), posts=None):
-        refuse_device_kernel(problem.model, "HipGradientAM (candidate gradients)")
+        refuse_device_kernel(problem.model, "HipGradientAM (candidate gradients)", grad_ok=True)
+        if isinstance(getattr(problem.acquisition, "fitness", None), DeviceFitness):
+            refuse_device_kernel(problem.model, "HipGradientAM with a DeviceFitness (Monte-Carlo EI gradients are built-in-kernel only)")
         if self.mean_grad is not None and device_mean_of(problem.model) is not None:
             raise ValueError("HipGradientAM: the model's mean is a DeviceMean, which gives its own ∂m/∂x; drop mean_grad")
         rng = np.random.default_rng(dist_util.shared_seed(self.seed, self.group))     # the same starts on every rank

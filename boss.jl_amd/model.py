@@ -63,8 +63,9 @@ class HipGaussianProcess:
     `parametric` (or `mean`, with theta_dim = 0) may be a DeviceMean: values and exact Jacobians then come from its traced program on
     the device, and `parametric_jac` is ignored.
     `kernel`: "matern32" | "matern52" | "sqexp", or a DeviceKernel (kernel.py) — a user-defined covariance function traced into a
-    device program (boss_kgp_create).  Such a model fits, predicts and drives HipBatchedMAP / HipBatchAM / bo; what needs gradients,
-    covariances, appends or tracks raises NotImplementedError."""
+    device program (boss_kgp_create).  Such a model fits, predicts and drives HipBatchedMAP / HipBatchAM / bo; what needs covariances,
+    appends or tracks raises NotImplementedError, and so does what needs gradients (mean_and_var_grad, data_loglike_grad_batch,
+    HipGradientMAP, HipSampleOptMAP, HipGradientAM) unless the kernel was traced with DeviceKernel(f, x_dim, grad=True)."""
     lengthscale_priors: Sequence
     amplitude_priors: Sequence
     noise_std_priors: Sequence
@@ -92,7 +93,7 @@ class HipGaussianProcess:
         """An unfitted resident handle for one output: boss_gp_create, or boss_kgp_create under a DeviceKernel."""
         dk = device_kernel_of(self)
         if dk is not None:
-            return api.KernelGP(X, y, dk.program, self.discrete, self.device)
+            return api.KernelGP(X, y, dk.program, self.discrete, self.device, grad=dk.grad)
         return api.GP(X, y, self.kernel, self.discrete, self.device)
 
     # ------------------------------------------------------------------ prior mean on the device (DeviceMean)
@@ -252,6 +253,39 @@ class HipGaussianProcess:
             tot += ll
         return tot
 
+    def _program_loglike_grad(self, data, plist, i, dev, T, tot, gl, ga, gs, gt):
+        """Output i of data_loglike_grad_batch under a DeviceKernel(grad=True), added into the caller's arrays."""
+        d = plist[0].lengthscales.shape[0]
+        # a program kernel (grad=True): the batched calls are built-in-kernel only — per set one update and one
+        # loglike_grad[_mean] on ONE resident handle per output, the pattern of data_loglike_batch
+        g = self._new_gp(data.X, data.Y[i])
+        try:
+            for k, p in enumerate(plist):
+                if dev is not None:
+                    m, J = np.ascontiguousarray(dev[0][i][k]), (dev[1][i][k] if T else None)
+                else:
+                    m = self.mean_values(data.X, p if self.parametric is not None else None, i)
+                    J = self.mean_jacobians(data.X, p, i) if T else None
+                try:
+                    g.update(p.lengthscales[:, i], p.amplitudes[i], p.noise_std[i], m)
+                    if T:
+                        ll, gr, dmean = g.loglike_grad_mean()
+                        gt[k] += np.asarray(J, float).T @ dmean
+                    else:
+                        ll, gr = g.loglike_grad()
+                except api.PosDefException:
+                    tot[k] = -math.inf                   # safe_data_loglike (src/surrogate_model.jl:2-12)
+                    continue
+                except api.BossError as e:               # an invalid parameter set: -inf, as its status is in the batched calls
+                    if e.code != api.BOSS_E_INVALID:
+                        raise
+                    tot[k] = -math.inf
+                    continue
+                tot[k] += ll
+                gl[k, :, i], ga[k, i], gs[k, i] = gr[:d], gr[d], gr[d + 1]
+        finally:
+            g.close()
+
     def data_loglike_grad_batch(self, data: ExperimentData, plist: Sequence[HipGPParams]):
         """data_loglike of every parameter set of `plist` and its gradient w.r.t. (λ, α, σ) AND θ — what ForwardDiff yields
         through data_loglike inside OptimizationMAP (src/model_fitters/optimization.jl:146-164) for a Semiparametric model.
@@ -259,7 +293,7 @@ class HipGaussianProcess:
         J_i (N×T), the device returns J_iᵀ a_i with a_i = K_i⁻¹(y_i − m_i); θ is shared by the outputs, so ∂/∂θ = Σ_i J_iᵀ a_i.
         Returns (ll[S], grads): grads[k] a HipGPParams of gradients (theta None without a parametric mean); a set that fails
         in any output has ll = -inf and zero gradients."""
-        refuse_device_kernel(self, "data_loglike_grad_batch (the likelihood gradient of HipGradientMAP)")
+        refuse_device_kernel(self, "data_loglike_grad_batch (the likelihood gradient of HipGradientMAP)", grad_ok=True)
         S = len(plist)
         tot = np.zeros(S)
         if S == 0:
@@ -271,6 +305,9 @@ class HipGaussianProcess:
         if device_mean_of(self) is not None:
             dev = self.device_means(data.X, plist, api.MEAN_OUTPUT_MAJOR, jac_theta=T > 0)
         for i in range(P):
+            if device_kernel_of(self) is not None:
+                self._program_loglike_grad(data, plist, i, dev, T, tot, gl, ga, gs, gt)
+                continue
             lam = np.stack([p.lengthscales[:, i] for p in plist], axis=1)
             amp = np.array([p.amplitudes[i] for p in plist])
             sig = np.array([p.noise_std[i] for p in plist])
@@ -392,7 +429,7 @@ class HipGaussianProcessPosteriorSlice:
     def mean_and_var_grad(self, X, mean_grad=None):
         """mean_and_var(post, X) with its gradient w.r.t. the columns of X (analytic, on the device):
         (mu[M], var[M], dmu[d,M], dvar[d,M]).  mean_grad: d×M gradient of the prior mean, if it has one."""
-        refuse_device_kernel(self.model, "mean_and_var_grad")
+        refuse_device_kernel(self.model, "mean_and_var_grad", grad_ok=True)
         X = np.asarray(X, float)
         if X.ndim == 1:
             X = X[:, None]
@@ -443,6 +480,11 @@ class HipGaussianProcessPosterior:
     def mean_and_std(self, x):
         mu, var = self.mean_and_var(x)
         return mu, np.sqrt(var)
+
+    def mean_and_var_grad(self, X, mean_grad=None):
+        """Every slice's mean_and_var_grad stacked: (mu, var [P, M], dmu, dvar [P, d, M]).  mean_grad: None or P×d×M."""
+        res = [s.mean_and_var_grad(X, None if mean_grad is None else mean_grad[i]) for i, s in enumerate(self.slices)]
+        return tuple(np.stack([r[q] for r in res]) for q in range(4))
 
     def mean_and_cov(self, X):
         """src/posterior.jl:74-79: means stacked as rows, covariances along dims=3 (M×M×P)."""

@@ -714,13 +714,28 @@ int boss_acq_ei_grad_warp(const boss_warp_t* warp, int P, int S, boss_gp_t* cons
  * resident candidates, P outputs × S samples, member by member), boss_gp_set_y, boss_gp_n, boss_gp_get_factor, boss_gp_free.
  * Every other entry point that takes a boss_gp_t* returns BOSS_E_INVALID ("not available for program-kernel posteriors"), or, for
  * the boss_ggp_* / boss_ngp_* calls, their own "handle was not created by ..." refusal.
- * BOSS_E_INVALID: d outside 1..16, N < 1 or above 46080, NULL X, y or kern. */
+ * BOSS_E_INVALID: d outside 1..16, N < 1 or above 46080, NULL X, y or kern.
+ *
+ * Gradients are opt-in.  boss_kern_grad_host (no device): the program's value and all 2d partials of n pairs by one reverse sweep,
+ * dU[m + d·j] = ∂f/∂u_m, dV[m + d·j] = ∂f/∂v_m at (U[:, j], V[:, j]); k_out may be NULL.  One convention beyond boss_fit_eval_host's
+ * sweep: a local partial that is exactly 0 passes 0 on whatever the adjoint is (0·±Inf = 0), so a kernel spelled through a distance
+ * (exp(-sqrt(r2)), sqrt(5 r2)) has finite partials at coincident points — the Matérn family's true 0, the exponential kernel's 0 of
+ * KernelFunctions / Distances.
+ * boss_kgp_set_grad(g, on) sets or clears a flag on a boss_kgp_create handle (BOSS_E_INVALID for any other handle), before or after
+ * boss_gp_update.  While it is set, boss_gp_loglike_grad, boss_gp_loglike_grad_mean, boss_gp_predict_grad, boss_acq_ei_grad and
+ * boss_acq_ei_grad_set (member by member) take the handle: ∂logpdf/∂(λ, α, σ) = ½ Σ G_ij ∂K_ij/∂·, G = a aᵀ − K⁻¹, with
+ * ∂K_ij/∂λ_m = −α² (f_u,m u_i,m + f_v,m u_j,m)/(λ_m+1e-8), and at a candidate
+ *   ∇μ_m = ∇m_m + Σ_i a_i α² f_v,m(u_i, u*)/(λ_m+1e-8),
+ *   ∇σ²_m = [α² (f_u,m + f_v,m)(u*, u*) − 2 Σ_i w_i α² f_v,m(u_i, u*)]/(λ_m+1e-8),   w = K⁻¹ k*,
+ * 0 in discrete dims.  A call that holds an unflagged program handle is refused as before.  Every other refusal stands. */
 typedef struct boss_kern boss_kern_t;
 int boss_kern_create(int d, int n_const, const double* consts, int n_instr, const int* code, int out_id, boss_kern_t** out);
 void boss_kern_free(boss_kern_t* kern);
 int boss_kern_eval_host(const boss_kern_t* kern, int n, const double* U, const double* V, double* k_out);
 int boss_kgp_create(int device, int d, int N, const double* X, const double* y, const unsigned char* discrete,
                     const boss_kern_t* kern, boss_gp_t** out);
+int boss_kern_grad_host(const boss_kern_t* kern, int n, const double* U, const double* V, double* k_out, double* dU, double* dV);
+int boss_kgp_set_grad(boss_gp_t* g, int on);
 
 /* boss_ngp_predict_grad for n nonstationary posteriors at the same M candidates in ONE call, and the sample-averaged acquisition
  * gradient on top of it: boss_acq_ei_grad_set for NonstationaryGP posteriors (BI samples of a finite_nongp model under
