@@ -6,7 +6,8 @@
 // dpair / idx_off / defer: one shard of a multi-device call (host_multi.inc) — the epilogue also leaves (max, global index) in the
 // device buffer dpair, and with defer the call returns right behind the enqueue (the caller runs the exchange on the same stream and
 // waits once); the shard's own (max, index) are then read from the context's pinned block by acq_shard_result.
-// (warp_call, host_warp.inc, restates this function's path selection and epilogue launches for warped models: keep the two in step)
+// The prediction stays this function's own (the arg-max-only attempt, the deferred shard, the caller's mean layout and the per-sample
+// loop on P×M scratch); whether the set launches are taken is members_set_path's answer, the set branch ends in the shared epilogue.
 static int acq_ei_impl(int P, int S, boss_gp_t* const* gps, const boss_cand_t* cand, const double* mean_Xs,
                        const double* fit_coefs, const double* y_max, int has_best, double best,
                        const unsigned char* valid_mask, double* acq_out, long* argmax_out, double* max_out,
@@ -54,7 +55,6 @@ static int acq_ei_impl(int P, int S, boss_gp_t* const* gps, const boss_cand_t* c
     EiPar par0 = par;                                        // (mode 0: acq_epilogue_kernel adds 0.0 to the sums the Monte-Carlo kernel left)
     par0.mode = 0;
     if (valid_mask) (void)hipMemcpyAsync(dmask, valid_mask, M, hipMemcpyHostToDevice, s);
-    if (S > 1) (void)hipMemsetAsync(dacq, 0, sizeof(double) * M, s);
     if (!acq_out && !defer) {
         // arg-max only: bound every candidate, finish the contenders (host_prune.inc); anything it declines runs the full kernel below
         for (int i = 0; i < 5; ++i) c->prune_last[i] = 0;
@@ -73,7 +73,9 @@ static int acq_ei_impl(int P, int S, boss_gp_t* const* gps, const boss_cand_t* c
         }
     }
     std::vector<double> hmean;
-    if (S > 1 && par.mode != 0 && !set_predict_off() && predict_set_ok(P * S, gps, cand)) {
+    const bool set_path = members_set_path(P * S, gps, cand, S > 1 && par.mode != 0, false, false);
+    if (S > 1 && !set_path) (void)hipMemsetAsync(dacq, 0, sizeof(double) * M, s);
+    if (set_path) {
         // Bayesian-inference average over S posteriors of one shape: ALL P·S predictions in one launch (grid = candidate tiles ×
         // posteriors), moments [s][p][j] resident, then the EI sum over the samples in sample order and the usual epilogue
         const size_t pm = (size_t)P * M;
@@ -96,13 +98,8 @@ static int acq_ei_impl(int P, int S, boss_gp_t* const* gps, const boss_cand_t* c
             (void)hipStreamSynchronize(s);
             return rc;
         }
-        if (mc) mc_accumulate_launch(s, mu_all, var_all, pm, M, M, 0, S, S, par, *mc, deps, dacq, 0);
-        else
-        hipLaunchKernelGGL(ei_accumulate_set_kernel, dim3((M + 255) / 256), dim3(256), 0, s, (const double*)mu_all, (const double*)var_all, pm, M, M,
-                           0, S - 1, par, dcoef, dymax, dacq);
-        hipLaunchKernelGGL(acq_epilogue_kernel, dim3(1), dim3(ACQ_EPI_THREADS), 0, s, (const double*)(mu_all + pm * (S - 1)),
-                           (const double*)(var_all + pm * (S - 1)), M, M, mc ? par0 : par, dcoef, dymax, dacq, 1, 1.0 / S, valid_mask ? dmask : nullptr, hres,
-                           (acq_out || defer) ? 0ull : ++c->acq_seq, dpair, idx_off);
+        ei_value_epilogue_launch(s, mu_all, var_all, M, S, par, dcoef, dymax, valid_mask ? dmask : nullptr, mc, deps, dacq, hres,
+                                 (acq_out || defer) ? 0ull : ++c->acq_seq, dpair, idx_off);
     } else
     for (int sm = 0; sm < S; ++sm) {
         if (par.mode != 0) {
@@ -203,12 +200,7 @@ extern "C" int boss_acq_ei_moments(int device, int P, int S, int M, const double
     (void)hipMemcpyAsync(dmu, mu, sizeof(double) * pm * S, hipMemcpyHostToDevice, s);
     (void)hipMemcpyAsync(dvar, var, sizeof(double) * pm * S, hipMemcpyHostToDevice, s);
     if (valid_mask) (void)hipMemcpyAsync(dmask, valid_mask, M, hipMemcpyHostToDevice, s);
-    if (S > 1) (void)hipMemsetAsync(dacq, 0, sizeof(double) * M, s);
-    for (int sm = 0; sm + 1 < S; ++sm)
-        hipLaunchKernelGGL(ei_accumulate_kernel, dim3((M + 255) / 256), dim3(256), 0, s, dmu + pm * sm, dvar + pm * sm, M, M, par,
-                           dcoef, dymax, dacq);
-    hipLaunchKernelGGL(acq_epilogue_kernel, dim3(1), dim3(ACQ_EPI_THREADS), 0, s, dmu + pm * (S - 1), dvar + pm * (S - 1), M, M,
-                       par, dcoef, dymax, dacq, S > 1 ? 1 : 0, 1.0 / S, valid_mask ? dmask : nullptr, hres, 0ull);
+    ei_value_epilogue_launch(s, dmu, dvar, M, S, par, dcoef, dymax, valid_mask ? dmask : nullptr, nullptr, nullptr, dacq, hres, 0ull);
     if (acq_out) (void)hipMemcpyAsync(acq_out, dacq, sizeof(double) * M, hipMemcpyDeviceToHost, s);
     hipError_t e = hipStreamSynchronize(s);
     if (e != hipSuccess) return fail(BOSS_E_NO_DEVICE, hipGetErrorString(e));

@@ -177,11 +177,7 @@ extern "C" int boss_acq_ei_mc_moments(int device, int P, int S, int M, const dou
     (void)hipMemcpyAsync(dmu, mu, sizeof(double) * pm * S, hipMemcpyHostToDevice, s);
     (void)hipMemcpyAsync(dvar, var, sizeof(double) * pm * S, hipMemcpyHostToDevice, s);
     if (valid_mask) (void)hipMemcpyAsync(dmask, valid_mask, M, hipMemcpyHostToDevice, s);
-    mc_accumulate_launch(s, dmu, dvar, pm, M, M, 0, S, S, par, mc, deps, dacq, 0);
-    EiPar par0 = par;
-    par0.mode = 0;                                           // the mean over s, the mask and the arg-max of the sums
-    hipLaunchKernelGGL(acq_epilogue_kernel, dim3(1), dim3(ACQ_EPI_THREADS), 0, s, (const double*)dmu, (const double*)dvar, M, M, par0,
-                       (const double*)nullptr, (const double*)nullptr, dacq, 1, 1.0 / S, valid_mask ? dmask : nullptr, hres, 0ull);
+    ei_value_epilogue_launch(s, dmu, dvar, M, S, par, nullptr, nullptr, valid_mask ? dmask : nullptr, &mc, deps, dacq, hres, 0ull);
     if (acq_out) (void)hipMemcpyAsync(acq_out, dacq, sizeof(double) * M, hipMemcpyDeviceToHost, s);
     hipError_t e = hipStreamSynchronize(s);
     hipError_t e2 = hipGetLastError();
@@ -230,6 +226,6 @@ extern "C" int boss_acq_ei_mc_grad_moments(int device, int P, int S, int M, int 
     (void)hipMemcpyAsync(d_gm, dmu, sizeof(double) * ndm, hipMemcpyHostToDevice, s);
     (void)hipMemcpyAsync(d_gv, dvar, sizeof(double) * ndm, hipMemcpyHostToDevice, s);
     if (valid_mask) (void)hipMemcpyAsync(dmask, valid_mask, M, hipMemcpyHostToDevice, s);
-    mc_grad_launch(s, d_mu, d_var, d_gm, d_gv, M, d, S, par, mc, deps, valid_mask ? (const unsigned char*)dmask : nullptr, dacq, ddacq);
+    ei_grad_epilogue_launch(s, d_mu, d_var, d_gm, d_gv, M, d, S, false, par, nullptr, nullptr, valid_mask ? dmask : nullptr, &mc, deps, dacq, ddacq);
     return finish(c, {{acq_out, dacq, sizeof(double) * M}, {dacq_out, ddacq, sizeof(double) * dm}});
 }

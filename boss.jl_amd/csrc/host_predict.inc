@@ -845,102 +845,6 @@ extern "C" int boss_ngp_predict_lat(boss_gp_t* g, int M, const double* Xs, const
     return ngp_predict_call(g, M, Xs, nullptr, nullptr, lat, mean_Xs, mu, var, bad_index);
 }
 
-// mean_and_var of n NonstationaryGP posteriors at the same M candidates in one call — the posteriors of the S samples of a
-// Bayesian-inference fit (src/posterior.jl:15-19), each with its own latent models: lam_Xs d×M×n, amp_Xs M×n, mean_Xs null or M×n
-// (member after member); mu, var [n][M].  Equally shaped handles (the members of a boss_ngp_fit_batch) take the one-launch set
-// prediction; any other list of nonstationary handles is predicted member by member inside the same call.  The variances are clipped as boss_ngp_predict clips
-// them; the first member with a variance below the threshold fails the call with BOSS_E_NEG_VAR, bad_index_out = the candidate.
-// (lats: n resident latent objects — boss_ngp_predict_set_lat — instead of lam_Xs / amp_Xs)
-static int ngp_predict_set_call(int n, boss_gp_t* const* gps, int M, const double* Xs, const double* lam_Xs, const double* amp_Xs,
-                                boss_nlat_t* const* lats, const double* mean_Xs, double* mu, double* var, long* bad_index_out) {
-    if (M < 1) return fail(BOSS_E_INVALID, "M must be >= 1");
-    if ((long long)n * M > (1LL << 30)) return fail(BOSS_E_INVALID, "n·M above 2^30 is not supported");
-    if (bad_index_out) *bad_index_out = -1;
-    for (int i = 0; i < n; ++i) {
-        if (!gps[i]) return fail(BOSS_E_INVALID, "NULL posterior handle");
-        if (!gps[i]->gibbs) return fail(BOSS_E_INVALID, "handle was not created by boss_ngp_create / boss_ngp_fit_batch");
-        if (gps[i]->ctx != gps[0]->ctx || gps[i]->d != gps[0]->d) return fail(BOSS_E_INVALID, "all handles must live on one device and share x_dim");
-        if (gps[i]->discrete != gps[0]->discrete) return fail(BOSS_E_INVALID, "all handles must round the same dimensions");
-        if (!gps[i]->fitted) return fail(BOSS_E_NOT_FITTED, "handle has no valid factorisation");
-    }
-    boss_gp* g0 = gps[0];
-    const int d = g0->d, Mp = round_up(M, 64);
-    std::vector<NgpCand> pk(lats ? 1 : n);
-    if (lats) {
-        int rc = nlat_match(n, gps, lats);
-        if (rc) return rc;
-        ngp_pack_x(g0, M, Xs, pk[0]);
-    }
-    for (int i = 0; i < n && !lats; ++i) {
-        int rc = ngp_pack(g0, M, Xs, lam_Xs + (size_t)i * d * M, amp_Xs + (size_t)i * M, pk[i]);
-        if (rc) return rc;
-    }
-    Ctx* c = g0->ctx;
-    HIPCHK(hipSetDevice(c->device));
-    std::lock_guard<std::mutex> lk(c->mtx);
-    hipStream_t s = c->stream;
-    for (int i = 0; i < n; ++i) {
-        int rc = gp_settle(gps[i]);
-        if (rc) return rc;
-    }
-    // candidates | λ(x*) of every member | α(x*) of every member [| the latent kernel's flag];  outputs mu | var | bad, prior means behind them
-    const size_t nm = (size_t)n * M;
-    int rc = ws_reserve(c->craw, sizeof(double) * ((size_t)d * Mp + (size_t)n * ((size_t)d * Mp + Mp) + (lats ? 1 : 0)));
-    if (rc) return rc;
-    rc = ws_reserve(c->pred, sizeof(double) * (3 * nm + 2));
-    if (rc) return rc;
-    boss_cand cd;
-    cd.ctx = c;
-    cd.d = d;
-    cd.M = M;
-    cd.Mp = Mp;
-    cd.Craw = (double*)c->craw.p;
-    double* clam = cd.Craw + (size_t)d * Mp;
-    double* camp = clam + (size_t)n * d * Mp;
-    double* dev = (double*)c->pred.p;
-    double *dmu = dev, *dvar = dev + nm, *dmean = dev + 2 * nm + 1;
-    unsigned long long* dbad = (unsigned long long*)(dev + 2 * nm);
-    HIPCHK(hipMemcpyAsync(cd.Craw, pk[0].x.data(), sizeof(double) * d * Mp, hipMemcpyHostToDevice, s));
-    for (int i = 0; i < n && !lats; ++i) {
-        HIPCHK(hipMemcpyAsync(clam + (size_t)i * d * Mp, pk[i].lam.data(), sizeof(double) * d * Mp, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(camp + (size_t)i * Mp, pk[i].amp.data(), sizeof(double) * Mp, hipMemcpyHostToDevice, s));
-    }
-    if (lats) {
-        unsigned long long* lbad = (unsigned long long*)(camp + (size_t)n * Mp);
-        rc = nlat_enqueue(c, n, lats, cd.Craw, Mp, M, clam, (size_t)d * Mp, camp, (size_t)Mp, nullptr, 0, nullptr, 0, nullptr, lbad);
-        if (rc == BOSS_OK) rc = nlat_check(c, lbad, nullptr);
-        if (rc) return drain(c, rc);
-    }
-    if (mean_Xs) (void)hipMemcpyAsync(dmean, mean_Xs, sizeof(double) * nm, hipMemcpyHostToDevice, s);
-    (void)hipMemsetAsync(dbad, 0xff, sizeof(unsigned long long), s);
-    if (!set_predict_off() && predict_set_ok(n, gps, &cd, true)) {
-        rc = predict_set_enqueue(n, gps, &cd, mean_Xs ? dmean : nullptr, dmu, dvar, (size_t)M, clam, camp);
-        if (rc) return drain(c, rc);
-    } else {
-        for (int i = 0; i < n; ++i) {
-            rc = predict_enqueue(gps[i], &cd, mean_Xs ? dmean + (size_t)i * M : nullptr, dmu + (size_t)i * M, dvar + (size_t)i * M, false,
-                                 clam + (size_t)i * d * Mp, camp + (size_t)i * Mp);
-            if (rc) return drain(c, rc);
-        }
-    }
-    // (member after member in one array: the smallest flat index is the first member's first offender)
-    hipLaunchKernelGGL(clip_var_kernel, dim3((unsigned)((nm + 255) / 256)), dim3(256), 0, s, dvar, (int)nm, dbad);
-    unsigned long long bad = 0;
-    rc = finish(c, {{mu, dmu, sizeof(double) * nm}, {var, dvar, sizeof(double) * nm}, {&bad, dbad, sizeof bad}});
-    if (rc) return rc;
-    return bad != ~0ULL ? neg_var_error(bad_index_out, bad % (unsigned long long)M, var[bad]) : BOSS_OK;
-}
-extern "C" int boss_ngp_predict_set(int n, boss_gp_t* const* gps, int M, const double* Xs, const double* lam_Xs, const double* amp_Xs,
-                                    const double* mean_Xs, double* mu, double* var, long* bad_index_out) {
-    if (n < 1 || !gps || !Xs || !lam_Xs || !amp_Xs || !mu || !var) return fail(BOSS_E_INVALID, "NULL argument or n < 1");
-    return ngp_predict_set_call(n, gps, M, Xs, lam_Xs, amp_Xs, nullptr, mean_Xs, mu, var, bad_index_out);
-}
-extern "C" int boss_ngp_predict_set_lat(int n, boss_gp_t* const* gps, int M, const double* Xs, boss_nlat_t* const* lats,
-                                        const double* mean_Xs, double* mu, double* var, long* bad_index_out) {
-    if (n < 1 || !gps || !Xs || !lats || !mu || !var) return fail(BOSS_E_INVALID, "NULL argument or n < 1");
-    return ngp_predict_set_call(n, gps, M, Xs, nullptr, nullptr, lats, mean_Xs, mu, var, bad_index_out);
-}
-
 // EI parameters: by value in the kernel arguments for P <= EI_MAXP, else in device arrays.
 static int ei_params(Ctx* c, hipStream_t s, int P, const double* fit_coefs, const double* y_max, int has_best, double best,
                      EiPar* par, double* dcoef, double* dymax) {
@@ -958,6 +862,39 @@ static int ei_params(Ctx* c, hipStream_t s, int P, const double* fit_coefs, cons
         HIPCHK(hipStreamSynchronize(s));
     }
     return BOSS_OK;
+}
+
+// The two epilogues every acquisition call ends in, on device-resident moments (coef / ymax: ei_params' device arrays, read for
+// P > EI_MAXP only; mask or null; mc or null: the EI term is the Monte-Carlo mean of a fitness program, deps its ε on the device).
+// Value and gradient from mu / var [s][p][M], gm / gv [s][p][d×M].  single: one sample through ei_grad_kernel — the caller says
+// so, because ei_grad_set_kernel with S = 1 adds the sample to 0.0 and is not the same bits (0.0 + (−0.0)).
+static void ei_grad_epilogue_launch(hipStream_t s, const double* mu, const double* var, const double* gm, const double* gv, int M, int d, int S,
+                                    bool single, const EiPar& par, const double* coef, const double* ymax, const unsigned char* mask,
+                                    const McEpi* mc, const double* deps, double* acq, double* dacq) {
+    if (mc)
+        mc_grad_launch(s, mu, var, gm, gv, M, d, S, par, *mc, deps, mask, acq, dacq);
+    else if (single)
+        hipLaunchKernelGGL(ei_grad_kernel, dim3((M + 127) / 128), dim3(128), 0, s, mu, var, gm, gv, M, d, par, coef, ymax, mask, acq, dacq);
+    else
+        hipLaunchKernelGGL(ei_grad_set_kernel, dim3((M + 127) / 128), dim3(128), 0, s, mu, var, gm, gv, M, d, S, par, coef, ymax, mask, acq, dacq);
+}
+// Value, mask and arg-max from mu / var [s][p][M]: samples 0 … S−2 summed into acq in sample order, the last one with the mean,
+// the mask and the arg-max (into hres; res_seq, dpair, idx_off: acq_epilogue_kernel's).  mc: the Monte-Carlo sums of all S samples,
+// then the epilogue in mode 0 (it adds 0.0 to them).
+static void ei_value_epilogue_launch(hipStream_t s, const double* mu, const double* var, int M, int S, const EiPar& par, const double* coef,
+                                     const double* ymax, const unsigned char* mask, const McEpi* mc, const double* deps, double* acq,
+                                     double* hres, unsigned long long res_seq, double* dpair = nullptr, long idx_off = 0) {
+    const size_t pm = (size_t)par.P * M;
+    EiPar last = par;
+    if (mc) {
+        mc_accumulate_launch(s, mu, var, pm, M, M, 0, S, S, par, *mc, deps, acq, 0);
+        last.mode = 0;
+    } else if (S > 1) {
+        (void)hipMemsetAsync(acq, 0, sizeof(double) * M, s);
+        hipLaunchKernelGGL(ei_accumulate_set_kernel, dim3((M + 255) / 256), dim3(256), 0, s, mu, var, pm, M, M, 0, S - 1, par, coef, ymax, acq);
+    }
+    hipLaunchKernelGGL(acq_epilogue_kernel, dim3(1), dim3(ACQ_EPI_THREADS), 0, s, mu + pm * (S - 1), var + pm * (S - 1), M, M, last, coef, ymax,
+                       acq, mc || S > 1 ? 1 : 0, 1.0 / S, mask, hres, res_seq, dpair, idx_off);
 }
 
 // SURVEY §8f3.  Enqueue μ, σ² (unclipped) and ∇μ, ∇σ² of one posterior at resident candidates:
@@ -1204,64 +1141,6 @@ extern "C" int boss_ngp_predict_grad_lat(boss_gp_t* g, int M, const double* Xs, 
     return ngp_predict_grad_call(g, M, Xs, nullptr, nullptr, nullptr, nullptr, lat, mean_Xs, mean_grad, mu, var, dmu, dvar, bad_index);
 }
 
-// Acquisition value AND gradient w.r.t. the candidates for one hyper-parameter sample (MAP): the EI x feasibility
-// chain rule runs on the device right behind the moment gradients of the P outputs.
-extern "C" int boss_acq_ei_grad(int P, boss_gp_t* const* gps, int M, const double* Xs, const double* mean_Xs,
-                                const double* mean_grad, const double* fit_coefs, const double* y_max, int has_best,
-                                double best, const unsigned char* valid_mask, double* acq_out, double* dacq_out) {
-    if (P < 1 || !gps || M < 1 || !Xs || !fit_coefs || !acq_out || !dacq_out) return fail(BOSS_E_INVALID, "bad arguments");
-    for (int p = 0; p < P; ++p) {
-        if (!gps[p]) return fail(BOSS_E_INVALID, "NULL posterior handle");
-        KPROG_NEEDS_GRAD(gps[p]);                            // (so a call mixing flagged and unflagged program handles is refused)
-        NOT_FOR_GIBBS_MODEL(gps[p], mean_Xs, mean_grad);
-        if (gps[p]->ctx != gps[0]->ctx || gps[p]->d != gps[0]->d)
-            return fail(BOSS_E_INVALID, "all handles must live on one device and share x_dim");
-        if (!gps[p]->fitted) return fail(BOSS_E_NOT_FITTED, "handle has no valid factorisation");
-    }
-    Ctx* c = gps[0]->ctx;
-    HIPCHK(hipSetDevice(c->device));
-    std::lock_guard<std::mutex> lk(c->mtx);
-    const int d = gps[0]->d;
-    boss_cand cd;
-    int rc = temp_cand(c, d, M, Xs, &cd);
-    if (rc) return drain(c, rc);
-    hipStream_t s = c->stream;
-    const size_t dm = (size_t)d * M;
-    // device scratch: mu[P][M] | var[P][M] | mean[P][M] | mean_grad[P][dM] | dmu[P][dM] | dvar[P][dM] | acq[M] | dacq[dM] | coefs[P] | ymax[P] | mask
-    const size_t nd = (size_t)3 * P * M + (size_t)3 * P * dm + M + dm + 2 * P;
-    rc = ws_reserve(c->pred, sizeof(double) * nd + M);
-    if (rc) return drain(c, rc);
-    double* dev = (double*)c->pred.p;
-    double* dmu = dev;
-    double* dvar = dmu + (size_t)P * M;
-    double* dmean = dvar + (size_t)P * M;
-    double* dmg = dmean + (size_t)P * M;
-    double* dgm = dmg + (size_t)P * dm;
-    double* dgv = dgm + (size_t)P * dm;
-    double* dacq = dgv + (size_t)P * dm;
-    double* ddacq = dacq + M;
-    double* dcoef = ddacq + dm;
-    double* dymax = dcoef + P;
-    unsigned char* dmask = (unsigned char*)(dev + nd);
-    EiPar par;
-    rc = ei_params(c, s, P, fit_coefs, y_max, has_best, best, &par, dcoef, dymax);
-    if (rc) return drain(c, rc);
-    if (mean_Xs) (void)hipMemcpyAsync(dmean, mean_Xs, sizeof(double) * P * M, hipMemcpyHostToDevice, s);
-    if (mean_grad) (void)hipMemcpyAsync(dmg, mean_grad, sizeof(double) * P * dm, hipMemcpyHostToDevice, s);
-    if (valid_mask) (void)hipMemcpyAsync(dmask, valid_mask, M, hipMemcpyHostToDevice, s);
-    if (par.mode != 0) {
-        for (int p = 0; p < P; ++p) {
-            rc = grad_enqueue(gps[p], &cd, mean_Xs ? dmean + (size_t)p * M : nullptr, mean_grad ? dmg + (size_t)p * dm : nullptr,
-                              dmu + (size_t)p * M, dvar + (size_t)p * M, dgm + (size_t)p * dm, dgv + (size_t)p * dm);
-            if (rc) return drain(c, rc);
-        }
-    }
-    hipLaunchKernelGGL(ei_grad_kernel, dim3((M + 127) / 128), dim3(128), 0, s, (const double*)dmu, (const double*)dvar,
-                       (const double*)dgm, (const double*)dgv, M, d, par, (const double*)dcoef, (const double*)dymax,
-                       valid_mask ? (const unsigned char*)dmask : nullptr, dacq, ddacq);
-    return finish(c, {{acq_out, dacq, sizeof(double) * M}, {dacq_out, ddacq, sizeof(double) * dm}});
-}
-
 // ------------------------------------------------------------------------------------------
 // Moments AND moment gradients of a SET of equally shaped posteriors at the same candidates (boss_acq_ei_grad_set): the forward
 // substitution of all members through predict_set_enqueue, and behind every group of members the adjoint substitution
@@ -1416,15 +1295,64 @@ static int grad_set_enqueue(int n, boss_gp_t* const* gps, const boss_cand* cd, c
     };
     return predict_set_enqueue(n, gps, cd, mean_all, mu_all, var_all, (size_t)M, clam_all, camp_all, &after);
 }
+static bool ngp_grad_set_ok(int n, boss_gp_t* const* gps, const boss_cand* cd) {
+    return predict_set_ok(n, gps, cd, true) && gps[0]->d <= GIBBS_GRAD_MAX_D;
+}
+
+// ------------------------------------------------------------------------------------------
+// The moments (and, with q.gm, their gradients) of n posteriors at one candidate set into device slices: THE place that chooses
+// between the set launches and member by member, and the only loop over members, of every acquisition and set-prediction call
+// (acq_ei_impl, host_acq.inc, keeps its own per-sample loop and asks members_set_path).  Enqueue only: the caller holds the
+// context lock and drains on error.
+// ------------------------------------------------------------------------------------------
+struct MemberSlices {                                        // device pointers; member i at + i·M (moments) / + i·d·M (gradients)
+    const double *mean = nullptr, *mean_grad = nullptr;      // prior means and their gradients, or null
+    double *mu = nullptr, *var = nullptr, *gm = nullptr, *gv = nullptr;   // gm null: values only
+    // nonstationary members: λ(x*) [n][d×Mp], α(x*) [n][Mp], their Jacobians [n][M][d×d] / [n][M][d] (or null), and the sums of ONE
+    // member ([2 (2 d + 1)][Mp]) for the member-by-member gradient
+    const double *clam = nullptr, *camp = nullptr, *dlam = nullptr, *damp = nullptr;
+    double* sums = nullptr;
+};
+// allow_set: what the entry point permits; BOSS_NO_SET_PREDICT and the members' shapes decide the rest
+static bool members_set_path(int n, boss_gp_t* const* gps, const boss_cand* cd, bool allow_set, bool grad, bool latents) {
+    if (!allow_set || set_predict_off()) return false;
+    return !grad ? predict_set_ok(n, gps, cd, latents) : latents ? ngp_grad_set_ok(n, gps, cd) : grad_set_ok(n, gps, cd);
+}
+static int members_enqueue(int n, boss_gp_t* const* gps, const boss_cand* cd, const MemberSlices& q, bool allow_set) {
+    const int d = cd->d, M = cd->M, Mp = cd->Mp;
+    const size_t dm = (size_t)d * M;
+    if (members_set_path(n, gps, cd, allow_set, q.gm != nullptr, q.clam != nullptr)) {
+        if (!q.gm) return predict_set_enqueue(n, gps, cd, q.mean, q.mu, q.var, (size_t)M, q.clam, q.camp);
+        int rc = grad_set_enqueue(n, gps, cd, q.mean, q.mean_grad, q.mu, q.var, q.gm, q.gv, q.clam, q.camp, q.dlam, q.damp);
+        if (rc != BOSS_E_ALLOC) return rc;                   // (no memory for the set launches: the call goes on member by member)
+    }
+    for (int i = 0; i < n; ++i) {
+        const double *mean = q.mean ? q.mean + (size_t)i * M : nullptr, *mg = q.mean_grad ? q.mean_grad + (size_t)i * dm : nullptr;
+        const double *cl = q.clam ? q.clam + (size_t)i * d * Mp : nullptr, *ca = q.clam ? q.camp + (size_t)i * Mp : nullptr;
+        double *mu = q.mu + (size_t)i * M, *var = q.var + (size_t)i * M;
+        int rc;
+        if (!q.gm)
+            rc = predict_enqueue(gps[i], cd, mean, mu, var, false, cl, ca);
+        else if (!q.clam)
+            rc = grad_enqueue(gps[i], cd, mean, mg, mu, var, q.gm + (size_t)i * dm, q.gv + (size_t)i * dm);
+        else
+            rc = grad_enqueue(gps[i], cd, mean, nullptr, mu, var, nullptr, nullptr, cl, ca, q.sums);
+        if (rc) return rc;
+        if (q.gm && q.clam)                                  // the latent models' Jacobians and the prior mean's gradient into the member's slices
+            hipLaunchKernelGGL(gibbs_grad_fold_kernel, dim3((M + 31) / 32), dim3(256), 0, cd->ctx->stream, (const double*)q.sums, Mp,
+                               q.dlam ? q.dlam + (size_t)i * d * dm : nullptr, q.damp ? q.damp + (size_t)i * dm : nullptr, ca, mg,
+                               q.gm + (size_t)i * dm, q.gv + (size_t)i * dm, d, M);
+    }
+    return BOSS_OK;
+}
 
 // boss_acq_ei_grad averaged over S hyper-parameter samples in one call (expected_improvement.jl:87-90 inside the multistart
 // refinement of optimization.jl:89-118): gps[p + P·s]; the candidates are uploaded once, every member's moments and moment
 // gradients stay on the device ([s][p] slices), and ONE epilogue applies the chain rule per sample and sums in ascending s.
-// Equally shaped members take the set launches (grad_set_enqueue); any other list, BOSS_NO_SET_PREDICT=1 and a set-path
-// allocation failure go member by member through grad_enqueue into the same slices.
+// Equally shaped members take the set launches, any other list goes member by member into the same slices (members_enqueue).
+// S = 1 (boss_acq_ei_grad, one hyper-parameter sample): always member by member, and ei_grad_kernel.
 // mc: the EI term and its gradient are those of a fitness program's Monte-Carlo mean (boss_acq_ei_mc_grad, host_fitness.inc); fit_coefs
-// is not read, P <= EI_MAXP, and S = 1 takes this path too.
-// (warp_call, host_warp.inc, restates this function's path selection and epilogue launches for warped models: keep the two in step)
+// is not read, P <= EI_MAXP, and S = 1 may take the set launches too.
 static int acq_ei_grad_set_impl(int P, int S, boss_gp_t* const* gps, int M, const double* Xs, const double* mean_Xs,
                                 const double* mean_grad, const double* fit_coefs, const double* y_max, int has_best,
                                 double best, const unsigned char* valid_mask, double* acq_out, double* dacq_out, const McEpi* mc) {
@@ -1441,8 +1369,6 @@ static int acq_ei_grad_set_impl(int P, int S, boss_gp_t* const* gps, int M, cons
     }
     for (int i = 0; i < n; ++i)
         if (!gps[i]->fitted) return fail(BOSS_E_NOT_FITTED, "handle has no valid factorisation");
-    if (S == 1 && !mc)
-        return boss_acq_ei_grad(P, gps, M, Xs, mean_Xs, mean_grad, fit_coefs, y_max, has_best, best, valid_mask, acq_out, dacq_out);
     Ctx* c = gps[0]->ctx;
     HIPCHK(hipSetDevice(c->device));
     std::lock_guard<std::mutex> lk(c->mtx);
@@ -1480,24 +1406,23 @@ static int acq_ei_grad_set_impl(int P, int S, boss_gp_t* const* gps, int M, cons
     if (mean_grad) (void)hipMemcpyAsync(dmg, mean_grad, sizeof(double) * ndm, hipMemcpyHostToDevice, s);
     if (valid_mask) (void)hipMemcpyAsync(dmask, valid_mask, M, hipMemcpyHostToDevice, s);
     if (par.mode != 0) {
-        bool done = false;
-        if (!set_predict_off() && grad_set_ok(n, gps, &cd)) {
-            rc = grad_set_enqueue(n, gps, &cd, mean_Xs ? dmean : nullptr, mean_grad ? dmg : nullptr, dmu, dvar, dgm, dgv);
-            if (rc != BOSS_OK && rc != BOSS_E_ALLOC) return drain(c, rc);
-            done = rc == BOSS_OK;                            // (no memory for the set launches: the call goes on member by member)
-        }
-        for (int i = 0; i < n && !done; ++i) {
-            rc = grad_enqueue(gps[i], &cd, mean_Xs ? dmean + (size_t)i * M : nullptr, mean_grad ? dmg + (size_t)i * dm : nullptr,
-                              dmu + (size_t)i * M, dvar + (size_t)i * M, dgm + (size_t)i * dm, dgv + (size_t)i * dm);
-            if (rc) return drain(c, rc);
-        }
+        MemberSlices q;
+        q.mean = mean_Xs ? dmean : nullptr;
+        q.mean_grad = mean_grad ? dmg : nullptr;
+        q.mu = dmu, q.var = dvar, q.gm = dgm, q.gv = dgv;
+        rc = members_enqueue(n, gps, &cd, q, mc || S > 1);
+        if (rc) return drain(c, rc);
     }
-    if (mc) mc_grad_launch(s, dmu, dvar, dgm, dgv, M, d, S, par, *mc, deps, valid_mask ? (const unsigned char*)dmask : nullptr, dacq, ddacq);
-    else
-    hipLaunchKernelGGL(ei_grad_set_kernel, dim3((M + 127) / 128), dim3(128), 0, s, (const double*)dmu, (const double*)dvar, (const double*)dgm,
-                       (const double*)dgv, M, d, S, par, (const double*)dcoef, (const double*)dymax,
-                       valid_mask ? (const unsigned char*)dmask : nullptr, dacq, ddacq);
+    ei_grad_epilogue_launch(s, dmu, dvar, dgm, dgv, M, d, S, S == 1 && !mc, par, dcoef, dymax, valid_mask ? dmask : nullptr, mc, deps, dacq, ddacq);
     return finish(c, {{acq_out, dacq, sizeof(double) * M}, {dacq_out, ddacq, sizeof(double) * dm}});
+}
+
+// Acquisition value AND gradient w.r.t. the candidates for one hyper-parameter sample (MAP): the EI x feasibility
+// chain rule runs on the device right behind the moment gradients of the P outputs.
+extern "C" int boss_acq_ei_grad(int P, boss_gp_t* const* gps, int M, const double* Xs, const double* mean_Xs,
+                                const double* mean_grad, const double* fit_coefs, const double* y_max, int has_best,
+                                double best, const unsigned char* valid_mask, double* acq_out, double* dacq_out) {
+    return acq_ei_grad_set_impl(P, 1, gps, M, Xs, mean_Xs, mean_grad, fit_coefs, y_max, has_best, best, valid_mask, acq_out, dacq_out, nullptr);
 }
 
 extern "C" int boss_acq_ei_grad_set(int P, int S, boss_gp_t* const* gps, int M, const double* Xs, const double* mean_Xs,
@@ -1507,16 +1432,14 @@ extern "C" int boss_acq_ei_grad_set(int P, int S, boss_gp_t* const* gps, int M, 
 }
 
 // ------------------------------------------------------------------------------------------
-// boss_ngp_predict_grad over a list of nonstationary posteriors (boss_ngp_predict_grad_set), and boss_acq_ei_grad_set's counterpart
-// for them (boss_ngp_acq_ei_grad_set): one enqueue path.  Candidates, every member's λ(x*), α(x*) and Jacobians go up once; equally
-// shaped members take grad_set_enqueue (gibbs_grad_accum_set_kernel + gibbs_grad_fold_set_kernel behind every group), any other
-// list, BOSS_NO_SET_PREDICT=1 and a failed allocation of the set path's scratch go member by member through grad_enqueue's
-// nonstationary branch + gibbs_grad_fold_kernel into the same slices; one copy back.
+// mean_and_var of a list of nonstationary posteriors at the same M candidates (boss_ngp_predict_set: the posteriors of the S samples
+// of a Bayesian-inference fit, src/posterior.jl:15-19, each with its own latent models), boss_ngp_predict_grad over such a list
+// (boss_ngp_predict_grad_set), and boss_acq_ei_grad_set's counterpart for them (boss_ngp_acq_ei_grad_set): one enqueue path.
+// Candidates, every member's λ(x*), α(x*) and Jacobians go up once: lam_Xs d×M×n, amp_Xs M×n, mean_Xs null or M×n (member after
+// member); equally shaped members (those of a boss_ngp_fit_batch) take the set launches, any other list goes member by member
+// into the same slices (members_enqueue); one copy back.  The prediction calls clip the variances as boss_ngp_predict clips them:
+// the first member with a variance below the threshold fails the call with BOSS_E_NEG_VAR, bad_index_out = the candidate.
 // ------------------------------------------------------------------------------------------
-static bool ngp_grad_set_ok(int n, boss_gp_t* const* gps, const boss_cand* cd) {
-    return predict_set_ok(n, gps, cd, true) && gps[0]->d <= GIBBS_GRAD_MAX_D;
-}
-
 struct NgpEiArgs {
     int P, S;
     const double *fit_coefs, *y_max;
@@ -1526,8 +1449,9 @@ struct NgpEiArgs {
     double *acq_out, *dacq_out;
 };
 
-// ei: null (the members' moments and gradients come back: mu / var [n][M], dmu / dvar [n][d×M]) or the acquisition's arguments
-// (acq_out / dacq_out come back)
+// ei: null (the members' moments come back: mu / var [n][M], and with dmu their gradients dmu / dvar [n][d×M]; dmu null: values
+// only — no Jacobian, gradient or sum areas are reserved, and a handle whose update is still pending is refused as unfitted, which
+// the gradient calls accept) or the acquisition's arguments (acq_out / dacq_out come back)
 // lats: n resident latent objects (the _lat calls) instead of the four host arrays — the latent kernel fills the same buffers
 static int ngp_grad_set_call(int n, boss_gp_t* const* gps, int M, const double* Xs, const double* lam_Xs, const double* amp_Xs,
                              const double* dlam_Xs, const double* damp_Xs, boss_nlat_t* const* lats, const double* mean_Xs, const double* mean_grad,
@@ -1543,10 +1467,11 @@ static int ngp_grad_set_call(int n, boss_gp_t* const* gps, int M, const double* 
     }
     boss_gp* g0 = gps[0];
     const int d = g0->d, Mp = round_up(M, 64);
-    if (d > GIBBS_GRAD_MAX_D) return fail(BOSS_E_INVALID, "x_dim above 16 is not supported by the nonstationary gradient kernel");
-    if ((long long)n * M * d * d > NGP_GRAD_SET_MAX_JAC) return fail(BOSS_E_INVALID, "n·M·x_dim² above 2^27 is not supported");
+    const bool grad = ei || dmu, accept_pending = grad;
+    if (grad && d > GIBBS_GRAD_MAX_D) return fail(BOSS_E_INVALID, "x_dim above 16 is not supported by the nonstationary gradient kernel");
+    if (grad && (long long)n * M * d * d > NGP_GRAD_SET_MAX_JAC) return fail(BOSS_E_INVALID, "n·M·x_dim² above 2^27 is not supported");
     for (int i = 0; i < n; ++i)
-        if (!gps[i]->fitted && !gps[i]->pending) return fail(BOSS_E_NOT_FITTED, "handle has no valid factorisation");
+        if (!gps[i]->fitted && !(accept_pending && gps[i]->pending)) return fail(BOSS_E_NOT_FITTED, "handle has no valid factorisation");
     std::vector<NgpCand> pk(lats ? 1 : n);
     if (lats) {
         int rc = nlat_match(n, gps, lats);
@@ -1565,15 +1490,15 @@ static int ngp_grad_set_call(int n, boss_gp_t* const* gps, int M, const double* 
         int rc = gp_settle(gps[i]);
         if (rc) return rc;
     }
-    const size_t dm = (size_t)d * M, nm = (size_t)n * M, ndm = (size_t)n * dm, nsums = (size_t)2 * (2 * d + 1) * Mp;
+    const size_t dm = (size_t)d * M, nm = (size_t)n * M, ndm = grad ? (size_t)n * dm : 0, nsums = grad ? (size_t)2 * (2 * d + 1) * Mp : 0;
     const int P = ei ? ei->P : 0;
-    const bool has_jl = lats || dlam_Xs, has_ja = lats || damp_Xs;
+    const bool has_jl = grad && (lats || dlam_Xs), has_ja = grad && (lats || damp_Xs);
     // candidates | λ(x*) of every member | α(x*) of every member | ∂λ/∂x | ∂α/∂x [| the latent kernel's flag]
     int rc = ws_reserve(c->craw, sizeof(double) * ((size_t)d * Mp + (size_t)n * ((size_t)d * Mp + Mp) + (has_jl ? ndm * d : 0) + (has_ja ? ndm : 0) + (lats ? 1 : 0)));
     if (rc) return rc;
     // acq | dacq | mu | var | dmu | dvar | bad | mean | mean_grad | sums of one member (member-by-member path) | coefs | ymax | mask
     const size_t nacq = ei ? M + dm : 0, nd = nacq + 3 * nm + 3 * ndm + 1 + nsums + 2 * (size_t)P;
-    rc = ws_reserve(c->pred, sizeof(double) * nd + M);
+    rc = ws_reserve(c->pred, sizeof(double) * nd + (ei ? M : 0));
     if (rc) return rc;
     boss_cand cd;
     cd.ctx = c;
@@ -1612,48 +1537,53 @@ static int ngp_grad_set_call(int n, boss_gp_t* const* gps, int M, const double* 
     if (damp_Xs) HIPCHK(hipMemcpyAsync(dja, damp_Xs, sizeof(double) * ndm, hipMemcpyHostToDevice, s));
     if (lats) {
         unsigned long long* lbad = (unsigned long long*)(dja + ndm);
-        rc = nlat_enqueue(c, n, lats, cd.Craw, Mp, M, clam, (size_t)d * Mp, camp, (size_t)Mp, djl, dm * d, dja, dm, nullptr, lbad);
+        rc = nlat_enqueue(c, n, lats, cd.Craw, Mp, M, clam, (size_t)d * Mp, camp, (size_t)Mp, grad ? djl : nullptr, grad ? dm * d : 0,
+                          grad ? dja : nullptr, grad ? dm : 0, nullptr, lbad);
         if (rc == BOSS_OK) rc = nlat_check(c, lbad, nullptr);
         if (rc) return drain(c, rc);
     }
     if (mean_Xs) (void)hipMemcpyAsync(dmean, mean_Xs, sizeof(double) * nm, hipMemcpyHostToDevice, s);
-    if (mean_grad) (void)hipMemcpyAsync(dmg, mean_grad, sizeof(double) * ndm, hipMemcpyHostToDevice, s);
+    if (mean_grad && grad) (void)hipMemcpyAsync(dmg, mean_grad, sizeof(double) * ndm, hipMemcpyHostToDevice, s);
     if (ei && ei->valid_mask) (void)hipMemcpyAsync(dmask, ei->valid_mask, M, hipMemcpyHostToDevice, s);
     if (!ei) (void)hipMemsetAsync(dbad, 0xff, sizeof(unsigned long long), s);
     if (!ei || par.mode != 0) {
-        bool done = false;
-        if (!set_predict_off() && ngp_grad_set_ok(n, gps, &cd)) {
-            rc = grad_set_enqueue(n, gps, &cd, mean_Xs ? dmean : nullptr, mean_grad ? dmg : nullptr, dmu_, dvar_, dgm, dgv, clam, camp,
-                                  has_jl ? djl : nullptr, has_ja ? dja : nullptr);
-            if (rc != BOSS_OK && rc != BOSS_E_ALLOC) return drain(c, rc);
-            done = rc == BOSS_OK;                            // (no memory for the set launches: the call goes on member by member)
-        }
-        const int tiles = (M + 31) / 32;
-        for (int i = 0; i < n && !done; ++i) {
-            const double *cl = clam + (size_t)i * d * Mp, *ca = camp + (size_t)i * Mp;
-            rc = grad_enqueue(gps[i], &cd, mean_Xs ? dmean + (size_t)i * M : nullptr, nullptr, dmu_ + (size_t)i * M, dvar_ + (size_t)i * M,
-                              nullptr, nullptr, cl, ca, dsums);
-            if (rc) return drain(c, rc);
-            hipLaunchKernelGGL(gibbs_grad_fold_kernel, dim3(tiles), dim3(256), 0, s, (const double*)dsums, Mp,
-                               has_jl ? (const double*)djl + (size_t)i * d * dm : nullptr, has_ja ? (const double*)dja + (size_t)i * dm : nullptr,
-                               ca, mean_grad ? (const double*)dmg + (size_t)i * dm : nullptr, dgm + (size_t)i * dm, dgv + (size_t)i * dm, d, M);
-        }
+        MemberSlices q;
+        q.mean = mean_Xs ? dmean : nullptr;
+        q.mean_grad = mean_grad && grad ? dmg : nullptr;
+        q.mu = dmu_, q.var = dvar_, q.gm = grad ? dgm : nullptr, q.gv = grad ? dgv : nullptr;
+        q.clam = clam, q.camp = camp, q.dlam = has_jl ? djl : nullptr, q.damp = has_ja ? dja : nullptr;
+        q.sums = dsums;
+        rc = members_enqueue(n, gps, &cd, q, true);
+        if (rc) return drain(c, rc);
     }
     if (ei) {
-        hipLaunchKernelGGL(ei_grad_set_kernel, dim3((M + 127) / 128), dim3(128), 0, s, (const double*)dmu_, (const double*)dvar_,
-                           (const double*)dgm, (const double*)dgv, M, d, ei->S, par, (const double*)dcoef, (const double*)dymax,
-                           ei->valid_mask ? (const unsigned char*)dmask : nullptr, dacq, ddacq);
+        // (ei_grad_set_kernel for every S, 1 included)
+        ei_grad_epilogue_launch(s, dmu_, dvar_, dgm, dgv, M, d, ei->S, false, par, dcoef, dymax, ei->valid_mask ? dmask : nullptr, nullptr, nullptr,
+                                dacq, ddacq);
         return finish(c, {{ei->acq_out, dacq, sizeof(double) * M}, {ei->dacq_out, ddacq, sizeof(double) * dm}});
     }
     // (member after member in one array: the smallest flat index is the first member's first offender)
     hipLaunchKernelGGL(clip_var_kernel, dim3((unsigned)((nm + 255) / 256)), dim3(256), 0, s, dvar_, (int)nm, dbad);
     unsigned long long bad = 0;
-    rc = finish(c, {{mu, dmu_, sizeof(double) * nm}, {var, dvar_, sizeof(double) * nm}, {dmu, dgm, sizeof(double) * ndm},
-                    {dvar, dgv, sizeof(double) * ndm}, {&bad, dbad, sizeof bad}});
+    if (grad)
+        rc = finish(c, {{mu, dmu_, sizeof(double) * nm}, {var, dvar_, sizeof(double) * nm}, {dmu, dgm, sizeof(double) * ndm},
+                        {dvar, dgv, sizeof(double) * ndm}, {&bad, dbad, sizeof bad}});
+    else
+        rc = finish(c, {{mu, dmu_, sizeof(double) * nm}, {var, dvar_, sizeof(double) * nm}, {&bad, dbad, sizeof bad}});
     if (rc) return rc;
     return bad != ~0ULL ? neg_var_error(bad_index_out, bad % (unsigned long long)M, var[bad]) : BOSS_OK;
 }
 
+extern "C" int boss_ngp_predict_set(int n, boss_gp_t* const* gps, int M, const double* Xs, const double* lam_Xs, const double* amp_Xs,
+                                    const double* mean_Xs, double* mu, double* var, long* bad_index_out) {
+    if (n < 1 || !gps || !Xs || !lam_Xs || !amp_Xs || !mu || !var) return fail(BOSS_E_INVALID, "NULL argument or n < 1");
+    return ngp_grad_set_call(n, gps, M, Xs, lam_Xs, amp_Xs, nullptr, nullptr, nullptr, mean_Xs, nullptr, nullptr, mu, var, nullptr, nullptr, bad_index_out);
+}
+extern "C" int boss_ngp_predict_set_lat(int n, boss_gp_t* const* gps, int M, const double* Xs, boss_nlat_t* const* lats,
+                                        const double* mean_Xs, double* mu, double* var, long* bad_index_out) {
+    if (n < 1 || !gps || !Xs || !lats || !mu || !var) return fail(BOSS_E_INVALID, "NULL argument or n < 1");
+    return ngp_grad_set_call(n, gps, M, Xs, nullptr, nullptr, nullptr, nullptr, lats, mean_Xs, nullptr, nullptr, mu, var, nullptr, nullptr, bad_index_out);
+}
 extern "C" int boss_ngp_predict_grad_set(int n, boss_gp_t* const* gps, int M, const double* Xs, const double* lam_Xs, const double* amp_Xs,
                                          const double* dlam_Xs, const double* damp_Xs, const double* mean_Xs, const double* mean_grad,
                                          double* mu, double* var, double* dmu, double* dvar, long* bad_index_out) {
@@ -1724,9 +1654,7 @@ extern "C" int boss_acq_ei_grad_moments(int device, int P, int M, int d, const d
     (void)hipMemcpyAsync(d_gm, dmu, sizeof(double) * P * dm, hipMemcpyHostToDevice, s);
     (void)hipMemcpyAsync(d_gv, dvar, sizeof(double) * P * dm, hipMemcpyHostToDevice, s);
     if (valid_mask) (void)hipMemcpyAsync(dmask, valid_mask, M, hipMemcpyHostToDevice, s);
-    hipLaunchKernelGGL(ei_grad_kernel, dim3((M + 127) / 128), dim3(128), 0, s, (const double*)d_mu, (const double*)d_var, (const double*)d_gm,
-                       (const double*)d_gv, M, d, par, (const double*)dcoef, (const double*)dymax,
-                       valid_mask ? (const unsigned char*)dmask : nullptr, dacq, ddacq);
+    ei_grad_epilogue_launch(s, d_mu, d_var, d_gm, d_gv, M, d, 1, true, par, dcoef, dymax, valid_mask ? dmask : nullptr, nullptr, nullptr, dacq, ddacq);
     return finish(c, {{acq_out, dacq, sizeof(double) * M}, {dacq_out, ddacq, sizeof(double) * dm}});
 }
 

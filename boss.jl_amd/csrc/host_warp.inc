@@ -288,12 +288,10 @@ extern "C" int boss_warp_moments(int device, const boss_warp_t* w, int S, int M,
 // ------------------------------------------------------------------------------------------
 // one-call paths: boss_warp_predict, boss_warp_predict_grad, boss_acq_ei_warp, boss_acq_ei_grad_warp — one enqueue path, as the
 // nonstationary set calls have (ngp_grad_set_call).  Xs goes up once, warp_x_kernel writes the rows of a temporary candidate set,
-// the prediction enqueues of the plain calls run on it unchanged, warp_moments_kernel takes the device-resident moments of every
-// sample to user space, and the epilogues of the plain calls (ei_accumulate_set_kernel / acq_epilogue_kernel, ei_grad_kernel /
-// ei_grad_set_kernel) run on the result: y_max, best and the arg-max are in user space.  One copy back.
-// KEEP IN STEP with its twins, acq_ei_impl (host_acq.inc) and acq_ei_grad_set_impl / boss_acq_ei_grad (host_predict.inc): the choice
-// between set launches and member by member (S > 1, BOSS_NO_SET_PREDICT, predict_set_ok / grad_set_ok, the BOSS_E_ALLOC fallback),
-// the par.mode gate and the epilogue launches are restated here; tests/test_gpu_warp.py holds the two to the same bits.
+// the members' prediction of the plain calls runs on it unchanged (members_enqueue), warp_moments_kernel takes the device-resident
+// moments of every sample to user space, and the epilogues of the plain calls (ei_value_epilogue_launch, ei_grad_epilogue_launch)
+// run on the result: y_max, best and the arg-max are in user space.  One copy back.  tests/test_gpu_warp.py holds these paths to
+// the plain calls' bits.
 // ------------------------------------------------------------------------------------------
 struct WarpAcq {
     const double* fit_coefs;
@@ -397,32 +395,12 @@ static int warp_call(const boss_warp_t* w, int P, int S, boss_gp_t* const* gps, 
     if (mean_Xs) (void)hipMemcpyAsync(dmean, mean_Xs, sizeof(double) * nm, hipMemcpyHostToDevice, s);
     if (mean_grad && grad) (void)hipMemcpyAsync(dmg, mean_grad, sizeof(double) * gi, hipMemcpyHostToDevice, s);
     if (par.mode != 0) {
-        const bool set_off = set_predict_off();
-        const double* mean_all = mean_Xs ? dmean : nullptr;
-        const double* mg_all = mean_grad && grad ? dmg : nullptr;
-        bool done = false;
-        if (grad) {
-            if (!set_off && acq && S > 1 && grad_set_ok(n, gps, &cd)) {   // (S = 1 and the prediction calls: member by member, as the plain calls)
-                rc = grad_set_enqueue(n, gps, &cd, mean_all, mg_all, i_mu, i_var, i_gm, i_gv);
-                if (rc != BOSS_OK && rc != BOSS_E_ALLOC) return drain(c, rc);
-                done = rc == BOSS_OK;                        // (no memory for the set launches: member by member)
-            }
-            for (int i = 0; i < n && !done; ++i) {
-                rc = grad_enqueue(gps[i], &cd, mean_all ? mean_all + (size_t)i * M : nullptr, mg_all ? mg_all + (size_t)i * dm * M : nullptr,
-                                  i_mu + (size_t)i * M, i_var + (size_t)i * M, i_gm + (size_t)i * dm * M, i_gv + (size_t)i * dm * M);
-                if (rc) return drain(c, rc);
-            }
-        } else {
-            if (!set_off && acq && S > 1 && predict_set_ok(n, gps, &cd)) {
-                rc = predict_set_enqueue(n, gps, &cd, mean_all, i_mu, i_var, (size_t)M);
-                if (rc) return drain(c, rc);
-                done = true;
-            }
-            for (int i = 0; i < n && !done; ++i) {
-                rc = predict_enqueue(gps[i], &cd, mean_all ? mean_all + (size_t)i * M : nullptr, i_mu + (size_t)i * M, i_var + (size_t)i * M);
-                if (rc) return drain(c, rc);
-            }
-        }
+        MemberSlices q;
+        q.mean = mean_Xs ? dmean : nullptr;
+        q.mean_grad = mean_grad && grad ? dmg : nullptr;
+        q.mu = i_mu, q.var = i_var, q.gm = grad ? i_gm : nullptr, q.gv = grad ? i_gv : nullptr;
+        rc = members_enqueue(n, gps, &cd, q, acq && S > 1);  // (S = 1 and the prediction calls: member by member, as the plain calls)
+        if (rc) return drain(c, rc);
         if (!acq) {
             // the prediction calls' convention for a variance below the clip, on the model's own variances (member i = p + P·s at i·M)
             (void)hipMemsetAsync(dbad, 0xff, sizeof(unsigned long long), s);
@@ -445,27 +423,13 @@ static int warp_call(const boss_warp_t* w, int P, int S, boss_gp_t* const* gps, 
         HIPCHK(hipMemcpy(&v, i_var + bad, sizeof v, hipMemcpyDeviceToHost));
         return neg_var_error(bad_index, bad % (unsigned long long)M, v);
     }
-    const size_t pm = (size_t)P * M;
-    const double* cf = dcoef;
-    const double* ym = dymax;
     const unsigned char* mk = acq->valid_mask ? dmask : nullptr;
     if (grad) {
-        if (S == 1)
-            hipLaunchKernelGGL(ei_grad_kernel, dim3((M + 127) / 128), dim3(128), 0, s, (const double*)o_mu, (const double*)o_var,
-                               (const double*)o_gm, (const double*)o_gv, M, du, par, cf, ym, mk, dacq, ddacq);
-        else
-            hipLaunchKernelGGL(ei_grad_set_kernel, dim3((M + 127) / 128), dim3(128), 0, s, (const double*)o_mu, (const double*)o_var,
-                               (const double*)o_gm, (const double*)o_gv, M, du, S, par, cf, ym, mk, dacq, ddacq);
+        ei_grad_epilogue_launch(s, o_mu, o_var, o_gm, o_gv, M, du, S, S == 1, par, dcoef, dymax, mk, nullptr, nullptr, dacq, ddacq);
         return finish(c, {{acq->acq_out, dacq, sizeof(double) * M}, {acq->dacq_out, ddacq, sizeof(double) * duM}});
     }
     double* hres = (double*)c->pinned;
-    if (S > 1) {
-        (void)hipMemsetAsync(dacq, 0, sizeof(double) * M, s);
-        hipLaunchKernelGGL(ei_accumulate_set_kernel, dim3((M + 255) / 256), dim3(256), 0, s, (const double*)o_mu, (const double*)o_var, pm, M, M, 0,
-                           S - 1, par, cf, ym, dacq);
-    }
-    hipLaunchKernelGGL(acq_epilogue_kernel, dim3(1), dim3(ACQ_EPI_THREADS), 0, s, (const double*)(o_mu + pm * (S - 1)),
-                       (const double*)(o_var + pm * (S - 1)), M, M, par, cf, ym, dacq, S > 1 ? 1 : 0, 1.0 / S, mk, hres, 0ull);
+    ei_value_epilogue_launch(s, o_mu, o_var, M, S, par, dcoef, dymax, mk, nullptr, nullptr, dacq, hres, 0ull);
     if (acq->acq_out) (void)hipMemcpyAsync(acq->acq_out, dacq, sizeof(double) * M, hipMemcpyDeviceToHost, s);
     rc = warp_finish(s);
     if (rc) return rc;
