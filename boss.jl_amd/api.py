@@ -153,6 +153,10 @@ SIGNATURES = {
     "boss_kgp_create": (C.c_int, [C.c_int, C.c_int, C.c_int, _c_dp, _c_dp, _c_ucp, C.c_void_p, C.POINTER(C.c_void_p)]),
     "boss_kern_grad_host": (C.c_int, [C.c_void_p, C.c_int, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
     "boss_kgp_set_grad": (C.c_int, [C.c_void_p, C.c_int]),
+    "boss_kgp_loglike_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, _c_dp, _c_dp, _c_ucp, C.c_void_p, C.c_int, _c_dp, _c_dp, _c_dp, _c_dp,
+                                         C.c_int, _c_dp, C.POINTER(C.c_int)]),
+    "boss_kgp_fit_batch": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, _c_dp, _c_dp, _c_dp, C.c_int, _c_ucp, C.c_int, _c_dp, _c_dp,
+                                     _c_dp, C.POINTER(C.c_void_p), _c_dp, C.POINTER(C.c_int)]),
     "boss_warp_create": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
     "boss_warp_free": (None, [C.c_void_p]),
     "boss_warp_apply_host": (C.c_int, [C.c_void_p, C.c_int, _c_dp, _c_dp, _c_dp]),
@@ -1971,6 +1975,84 @@ class KernelGP(GP):
             except Exception:
                 self.close()
                 raise
+
+
+def _kgp_batch_args(X, y, kern, lengthscales, amplitudes, noise_stds, mean_X, discrete):
+    """The arrays boss_kgp_loglike_batch / boss_kgp_fit_batch read, converted and checked (no device is touched): X d×N, y N,
+    lengthscales d×S, amplitudes / noise_stds S, mean_X None, N values or S×N rows."""
+    if not isinstance(kern, KernelProgram):
+        raise TypeError("kern must be a KernelProgram")
+    X = _f64(X, 2)
+    y = _f64(np.asarray(y).reshape(-1), 1)
+    lam = _f64(lengthscales, 2)
+    d, N = X.shape
+    S = lam.shape[1]
+    if lam.shape[0] != d:
+        raise BossError(BOSS_E_INVALID, "lengthscales must be d×S")
+    amp = _f64(np.asarray(amplitudes).reshape(-1), 1)
+    sig = _f64(np.asarray(noise_stds).reshape(-1), 1)
+    if amp.shape[0] != S or sig.shape[0] != S:
+        raise BossError(BOSS_E_INVALID, "amplitudes and noise_stds must have one entry per set")
+    if y.shape[0] != N:
+        raise ValueError("y must have one entry per column of X")
+    stride, m = 0, None
+    if mean_X is not None:
+        m = np.asarray(mean_X, dtype=np.float64)
+        if m.ndim == 2:
+            if m.shape != (S, N):
+                raise ValueError("mean_X must be S×N (one prior-mean row per set) or a vector of N entries")
+            m, stride = np.ascontiguousarray(m), N
+        else:
+            m = np.ascontiguousarray(m.reshape(-1))
+            if m.shape[0] != N:
+                raise ValueError("mean_X must be S×N (one prior-mean row per set) or a vector of N entries")
+    disc = None if discrete is None else np.ascontiguousarray(np.asarray(discrete, dtype=bool).astype(np.uint8))
+    return X, y, lam, amp, sig, m, stride, disc, d, N, S
+
+
+def kgp_loglike_batch(X, y, kern: KernelProgram, lengthscales, amplitudes, noise_stds, mean_X=None, discrete=None, device: int = 0):
+    """S log marginal likelihoods of one output slice under a KernelProgram in one call (boss_kgp_loglike_batch); lengthscales is
+    d×S.  Returns (ll[S], status[S]); ll = -Inf where a set is invalid or its matrix is not PD (safe_data_loglike).  Every value is
+    bit for bit the logpdf of KernelGP.update at the same parameters."""
+    X, y, lam, amp, sig, m, stride, disc, d, N, S = _kgp_batch_args(X, y, kern, lengthscales, amplitudes, noise_stds, mean_X, discrete)
+    ll = np.zeros(S)
+    st = np.zeros(S, dtype=np.int32)
+    _check(load_library().boss_kgp_loglike_batch(device, d, N, _dp(X), _dp(y), _ucp(disc), kern._h, S, _dp(lam), _dp(amp), _dp(sig),
+                                                 _dp(m), stride, _dp(ll), st.ctypes.data_as(C.POINTER(C.c_int))))
+    return ll, st
+
+
+def kgp_fit_batch(X, y, kern: KernelProgram, lengthscales, amplitudes, noise_stds, mean_X=None, discrete=None, device: int = 0,
+                  grad: bool = False):
+    """S resident posteriors of one output slice under a KernelProgram from ONE batched factorisation (boss_kgp_fit_batch): what
+    model_posterior builds per sample of a BI fit (src/posterior.jl:15-19).  Returns (gps[S], logpdf[S], status[S]): KernelGP
+    members of one set (grad=True: boss_kgp_set_grad on each); members with status != 0 are unfitted handles."""
+    X, y, lam, amp, sig, m, stride, disc, d, N, S = _kgp_batch_args(X, y, kern, lengthscales, amplitudes, noise_stds, mean_X, discrete)
+    if not (np.isfinite(amp).all() and np.isfinite(sig).all() and np.isfinite(lam).all()):
+        raise BossError(BOSS_E_INVALID, "hyper-parameters must be finite")
+    lib = load_library()
+    hs = (C.c_void_p * max(S, 1))()
+    ll = np.zeros(S)
+    st = np.zeros(S, dtype=np.int32)
+    _check(lib.boss_kgp_fit_batch(device, kern._h, d, N, _dp(X), _dp(y), _dp(m), stride, _ucp(disc), S, _dp(lam), _dp(amp), _dp(sig),
+                                  hs, _dp(ll), st.ctypes.data_as(C.POINTER(C.c_int))))
+    gps = []
+    for s in range(S):
+        g = KernelGP.__new__(KernelGP)
+        g.d, g.N, g.device, g.kernel, g._h = d, N, device, kern, C.c_void_p(hs[s])
+        g.logpdf = float(ll[s]) if st[s] == 0 else None
+        g.grad = False
+        gps.append(g)
+    if grad:
+        try:
+            for g in gps:
+                _check(lib.boss_kgp_set_grad(g._h, 1))
+                g.grad = True
+        except Exception:
+            for g in gps:
+                g.close()
+            raise
+    return gps, ll, st
 
 
 def _mc_common(fit: FitnessProgram, eps, y_max, valid_mask):

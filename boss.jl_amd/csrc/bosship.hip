@@ -139,7 +139,7 @@ struct Ctx {
     bool prof_on = false;
     std::map<std::string, std::vector<std::pair<hipEvent_t, hipEvent_t>>> prof;
     std::vector<hipEvent_t> ev_pool;
-    Workspace vscratch, csc, pred, acq, batchA, batchX, batchMisc, craw, lgA, lgB, lgC, few, setdesc, setmom, gsetdesc, nlatjobs, mceps, meanws, warpws, prunews, kpv;   // kpv: per-candidate prior variances of a program-kernel posterior (host_kprog.inc)
+    Workspace vscratch, csc, pred, acq, batchA, batchX, batchMisc, craw, lgA, lgB, lgC, few, setdesc, setmom, gsetdesc, nlatjobs, mceps, meanws, warpws, prunews, kpv, kxs;   // kpv: per-candidate prior variances of a program-kernel posterior, kxs: the scaled points of a chunk of its batched likelihood (host_kprog.inc)
     // batched likelihood gradients: the gradient passes of consecutive sets rotate over LLG_BANKS streams, each with its
     // own bank of workspaces (bank 0 = the main stream and lgA/lgB/lgC)
     static constexpr int LLG_BANKS = 4;
@@ -686,6 +686,9 @@ static bool few_fused() {
 static void kprog_gram_launch(boss_gp* g, hipStream_t s);
 static void kprog_kstar_launch(boss_gp* g, const boss_cand* cd, const double* Csc, int BN, int tiles, double* out, double* pvar, hipStream_t s);
 static void kprog_var_launch(hipStream_t s, double* var, const double* pvar, int M);
+static void kprog_kstar_set_launch(boss_gp* g0, const boss_cand* cd, const PredSet* dsets, int tiles, int cnt, double* V, double* pvar, size_t spv,
+                                   hipStream_t s);
+static void kprog_var_set_launch(hipStream_t s, const PredSet* dsets, int cnt, const double* pvar, size_t spv, int M);
 static void kprog_llgrad_launch(boss_gp* g, hipStream_t s, int ntiles, const double* Kinv, const double* apart, int nch, double* parts);
 static void kprog_grad_accum_launch(boss_gp* g, const boss_cand* cd, hipStream_t s, int tiles, int rsplit, const double* slabs, const double* Csc,
                                     const double* mean_grad_dev, double* dmu, double* dvar, double* part);

@@ -1,5 +1,6 @@
 // host_batch.inc — boss_gp_loglike_batch, boss_ggp_loglike_batch, boss_ngp_loglike_batch and their _grad_batch forms, boss_gp_fit_batch, boss_ggp_fit_batch,
-// boss_ngp_fit_batch: S hyper-parameter sets on one data slice (included by bosship.hip).
+// boss_ngp_fit_batch: S hyper-parameter sets on one data slice (included by bosship.hip).  boss_kgp_loglike_batch and boss_kgp_fit_batch
+// (host_kprog.inc) run on the same hooks.
 
 // ------------------------------------------------------------------------------------------
 // batched log-likelihood
@@ -827,6 +828,7 @@ static int fit_batch_run(Ctx* c, const FitBatchSpec& sp, const std::function<hip
             if (g->par_ev) (void)hipEventDestroy(g->par_ev);
             if (g->dinv_ev) (void)hipEventDestroy(g->dinv_ev);
             if (g->discrete_dev) (void)hipFree(g->discrete_dev);
+            delete g->kp;                                    // (program-kernel members: their copy of the program)
             delete g;
         }
         gpset_release_storage(st);

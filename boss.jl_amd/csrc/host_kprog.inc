@@ -1,5 +1,6 @@
 // host_kprog.inc — kernel programs (boss_kern_t) and the posteriors built on them (boss_kgp_create): validation, the host
-// interpreter, and the launches factor_enqueue / predict_enqueue make for such a handle (included by bosship.hip).
+// interpreter, the launches factor_enqueue / predict_enqueue / predict_set_enqueue make for such handles, and the batched entry
+// points boss_kgp_loglike_batch / boss_kgp_fit_batch on the hooks of host_batch.inc (included by bosship.hip, behind host_batch.inc).
 
 struct boss_kern {
     FitProg g;                                               // 2·d inputs: u[0..d) then v[0..d)
@@ -106,8 +107,20 @@ static void kprog_gram_launch(boss_gp* g, hipStream_t s) {
     size_t lds;
     const int threads = kprog_block(*g->kp, g->d, &lds);
     const int t64 = g->Np / 64;
-    hipLaunchKernelGGL(kprog_gram_kernel, dim3(t64 * (t64 + 1) / 2), dim3(threads), lds, s, *g->kp, (const double*)g->Xsc, g->d, g->N, g->Np,
-                       (const double*)g->hyp, g->A, g->ld);
+    hipLaunchKernelGGL(kprog_gram_kernel, dim3(t64 * (t64 + 1) / 2, 1, 1), dim3(threads), lds, s, *g->kp, (const double*)g->Xsc, (size_t)0, g->d,
+                       g->N, g->Np, (const double*)g->hyp, (size_t)0, g->A, g->ld, (size_t)0);
+}
+
+// ... of cnt parameter sets with constant strides (boss_kgp_loglike_batch, boss_kgp_fit_batch): the sets' scaled points from the
+// shared raw points and their 1/λ (par, sPar apart), then all Gram matrices in one launch (grid.z = set; hyp = {α², σ²} per set)
+static void kprog_gram_batch_launch(const FitProg& kp, int d, int N, int Np, int cnt, const double* Xraw, const double* par, size_t sPar,
+                                    const double* hyp, size_t sHyp, double* Xsc, size_t sX, double* A, int ld, size_t bstride, hipStream_t s) {
+    size_t lds;
+    const int threads = kprog_block(kp, d, &lds);
+    const int t64 = Np / 64;
+    hipLaunchKernelGGL(kprog_scale_set_kernel, dim3((Np + 255) / 256, cnt), dim3(256), 0, s, Xraw, Xsc, sX, par, sPar, d, Np);
+    hipLaunchKernelGGL(kprog_gram_kernel, dim3(t64 * (t64 + 1) / 2, 1, cnt), dim3(threads), lds, s, kp, (const double*)Xsc, sX, d, N, Np, hyp,
+                       sHyp, A, ld, bstride);
 }
 
 // K* of `tiles` candidate tiles of BN (32 or 64) into out[tile][Np][BN], and k(x*, x*) of their candidates into pvar
@@ -121,6 +134,19 @@ static void kprog_kstar_launch(boss_gp* g, const boss_cand* cd, const double* Cs
 
 static void kprog_var_launch(hipStream_t s, double* var, const double* pvar, int M) {
     hipLaunchKernelGGL(kprog_var_kernel, dim3((M + 255) / 256), dim3(256), 0, s, var, pvar, M);
+}
+
+// K* of cnt members of a set (descriptors dsets, one program, one shape: predict_set_ok) into their V slabs of 32 candidates, their
+// prior variances into pvar (spv apart); and the σ² of the set behind predict_kernel_set<G, true> (predict_set_enqueue)
+static void kprog_kstar_set_launch(boss_gp* g0, const boss_cand* cd, const PredSet* dsets, int tiles, int cnt, double* V, double* pvar,
+                                   size_t spv, hipStream_t s) {
+    size_t lds;
+    const int threads = kprog_block(*g0->kp, g0->d, &lds);
+    hipLaunchKernelGGL(kprog_kstar_set_kernel, dim3(g0->Np / 256, tiles, cnt), dim3(threads), lds, s, *g0->kp, g0->d, g0->N, g0->Np, cd->Mp,
+                       cd->M, dsets, V, pvar, spv);
+}
+static void kprog_var_set_launch(hipStream_t s, const PredSet* dsets, int cnt, const double* pvar, size_t spv, int M) {
+    hipLaunchKernelGGL(kprog_var_set_kernel, dim3((M + 255) / 256, cnt), dim3(256), 0, s, dsets, pvar, spv, M);
 }
 
 // ... of the gradient kernels: a column holds values and adjoints (kprog_grad_slots), at least min_slots doubles per thread
@@ -147,4 +173,112 @@ static void kprog_grad_accum_launch(boss_gp* g, const boss_cand* cd, hipStream_t
     hipLaunchKernelGGL(kprog_grad_accum_kernel, dim3(tiles, rsplit), dim3(threads), lds, s, *g->kp, slabs, (const double*)g->avec, g->Np, g->N,
                        (const double*)g->Xsc, Csc, g->d, cd->Mp, cd->M, g->amp2, (const double*)g->invlam,
                        (const unsigned char*)g->discrete_dev, mean_grad_dev, dmu, dvar, part);
+}
+
+// ------------------------------------------------------------------------------------------
+// S hyper-parameter sets of one output slice under one program (boss_kgp_loglike_batch, boss_kgp_fit_batch): `loglike.(samples)` of
+// src/model_fitters/sampling.jl:59-78 and the S posteriors of a Bayesian-inference fit (src/posterior.jl:15-19) for a
+// KernelFunctions.Kernel beyond the built-in ones.  The fourth model on the hooks of host_batch.inc: the parameter block of a set is
+// [1/λ (d) | α², σ²] as stage_hyper leaves it (the resident block of a handle), the Gram hook scales the shared points per set and
+// launches kprog_gram_kernel over all sets of the chunk (kprog_gram_batch_launch).
+// ------------------------------------------------------------------------------------------
+static int kgp_batch_args(const boss_kern_t* kern, int d, int N, int S, const double* X, const double* y) {
+    if (!kern) return fail(BOSS_E_INVALID, "kern is NULL");
+    if (d != kern->d)
+        return fail(BOSS_E_INVALID, "the kernel program was created for x_dim = " + std::to_string(kern->d) + ", the call has d = " + std::to_string(d));
+    if (S < 0) return fail(BOSS_E_INVALID, "S must be >= 0");
+    if (N < 1 || !X || !y) return fail(BOSS_E_INVALID, "need N >= 1 and non-NULL X, y");
+    if (N > MAX_ROWS) return fail(BOSS_E_INVALID, "more than 46080 observations are not supported");
+    return BOSS_OK;
+}
+
+extern "C" int boss_kgp_loglike_batch(int device, int d, int N, const double* X, const double* y, const unsigned char* discrete,
+                                      const boss_kern_t* kern, int S, const double* lengthscales, const double* amplitudes,
+                                      const double* noise_stds, const double* mean_X, int mean_stride, double* ll_out, int* status_out) {
+    int rc = kgp_batch_args(kern, d, N, S, X, y);
+    if (rc) return rc;
+    if (S == 0) return BOSS_OK;
+    if (!ll_out) return fail(BOSS_E_INVALID, "ll_out is NULL");
+    if (!lengthscales || !amplitudes || !noise_stds) return fail(BOSS_E_INVALID, "NULL hyper-parameter array");
+    if (mean_X && mean_stride != 0 && mean_stride != N) return fail(BOSS_E_INVALID, "mean_stride must be 0 or N");
+    Ctx* c;
+    rc = get_ctx(device, &c);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(c->mtx);
+    const int Np = round_up(N, BLK);
+    std::vector<double> pts, yb(Np, 0.0);
+    pack_points(pts, X, d, N, Np, discrete);
+    std::copy(y, y + N, yb.begin());
+    const size_t par_doubles = (size_t)d + 2, sX = (size_t)d * Np, bstride = (size_t)(Np + RHS_ROWS) * Np;
+    // the scaled points of a chunk's sets, [set][d][Np] (the chunk is model_loglike_batch_run's: its matrices below batch_chunk_bytes)
+    const size_t chunk = std::max<size_t>(1, std::min<size_t>((size_t)S, batch_chunk_bytes() / (bstride * sizeof(double))));
+    rc = ws_reserve(c->kxs, sizeof(double) * sX * chunk);
+    if (rc) return rc;
+    auto fill = [&](int b, double* p) { return stage_hyper(d, lengthscales + (size_t)b * d, amplitudes[b], noise_stds[b], p, p + d); };
+    auto gram = [&](const ModelBatchGramArgs& a) {
+        const size_t b0 = (size_t)(a.A - (double*)c->batchA.p) / a.bstride;   // (first set of this launch within the chunk)
+        kprog_gram_batch_launch(kern->g, d, N, Np, a.cnt, a.pts, a.par, par_doubles, a.par + d, par_doubles, (double*)c->kxs.p + b0 * sX, sX, a.A,
+                                a.ld, a.bstride, c->stream);
+    };
+    return model_loglike_batch_run(c, N, Np, S, pts, yb, mean_X, mean_stride, par_doubles, fill, gram, ll_out, status_out);
+}
+
+// The S posteriors as resident handles out of one batched factorisation: members of one slab as boss_gp_fit_batch's, each a program
+// handle (kprog, KERN_PROGRAM, its own copy of the program) — whatever takes or refuses a boss_kgp_create handle treats a member alike.
+extern "C" int boss_kgp_fit_batch(int device, const boss_kern_t* kern, int d, int N, const double* X, const double* y, const double* mean_X,
+                                  int mean_stride, const unsigned char* discrete, int S, const double* lengthscales,
+                                  const double* amplitudes, const double* noise_stds, boss_gp_t** out, double* logpdf_out, int* status_out) {
+    if (out)
+        for (int b = 0; b < S; ++b) out[b] = nullptr;
+    int rc = kgp_batch_args(kern, d, N, S, X, y);
+    if (rc) return rc;
+    if (S == 0) return BOSS_OK;
+    if (!out) return fail(BOSS_E_INVALID, "out is NULL");
+    if (!lengthscales || !amplitudes || !noise_stds) return fail(BOSS_E_INVALID, "NULL hyper-parameter array");
+    if (mean_X && mean_stride != 0 && mean_stride != N) return fail(BOSS_E_INVALID, "mean_stride must be 0 or N");
+    Ctx* c;
+    rc = get_ctx(device, &c);
+    if (rc) return rc;
+    const int Np = round_up(N, PRED_RB);
+    std::vector<double> pts, yb(Np, 0.0), h_par;
+    std::vector<int> valid(S);
+    pack_points(pts, X, d, N, Np, discrete);
+    std::copy(y, y + N, yb.begin());
+    FitBatchSpec sp;
+    sp.kernel = KERN_PROGRAM;
+    sp.d = d;
+    sp.N = sp.npts = N;
+    sp.ldx = Np;
+    sp.S = S;
+    sp.pts = &pts;
+    sp.yb = &yb;
+    sp.mean_X = mean_X;
+    sp.mean_stride = mean_stride;
+    sp.discrete = discrete;
+    auto factor = [&](FitBatchSlab& L, hipStream_t s) {
+        h_par.assign(L.sPar * S, 0.0);                       // the members' own blocks [1/λ (d) | α², σ², -, -], uploaded in place
+        for (int b = 0; b < S; ++b) {
+            double* p = &h_par[(size_t)b * L.sPar];
+            valid[b] = stage_hyper(d, lengthscales + (size_t)b * d, amplitudes[b], noise_stds[b], p, p + d);
+        }
+        hipError_t e = hipMemcpyAsync(L.par, h_par.data(), sizeof(double) * L.sPar * S, hipMemcpyHostToDevice, s);
+        if (e != hipSuccess) return e;
+        batch_middle_enqueue(c, N, Np, S, L.y, (const double*)L.mean, L.sMean, L.A, L.ld, L.sA, L.inv16, L.sInv, L.scalB, L.infoB, BatchStage(),
+                             [&](int b0, int cnt) {
+                                 ProfScope ps(c, "gram");
+                                 const double* par = L.par + (size_t)b0 * L.sPar;
+                                 kprog_gram_batch_launch(kern->g, d, N, Np, cnt, L.pts, par, L.sPar, par + d, L.sPar, L.Xsc + (size_t)b0 * L.sX, L.sX,
+                                                         L.A + (size_t)b0 * L.sA, L.ld, L.sA, c->stream);
+                             });
+        return hipSuccess;
+    };
+    auto member = [&](int b, boss_gp* g) {
+        const double* p = &h_par[(size_t)b * round_up(d + 4, 8)];
+        for (int k = 0; k < d + 2; ++k) g->host_par[k] = p[k];
+        g->amp2 = p[d];
+        g->kprog = true;
+        g->kp = new FitProg(kern->g);
+        return valid[b] != 0;
+    };
+    return fit_batch_run(c, sp, factor, member, out, logpdf_out, status_out);
 }

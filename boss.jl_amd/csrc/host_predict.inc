@@ -465,12 +465,10 @@ static int set_np_max() {
 }
 // may the n posteriors be predicted by one launch?  (models of one kind and shape on the candidates' device, fused 32-candidate
 // kernel: plain stationary models; gradient-observation models of one point count — the members of boss_ggp_fit_batch calls on the
-// outputs of a model —; and, where the caller brings the latent values at the candidates (with_latents, boss_ngp_predict_set),
-// nonstationary models)
+// outputs of a model —; where the caller brings the latent values at the candidates (with_latents, boss_ngp_predict_set),
+// nonstationary models; and the members of boss_kgp_fit_batch calls — program-kernel models — whose programs are bytewise equal)
 static bool predict_set_ok(int n, boss_gp_t* const* gps, const boss_cand* cd, bool with_latents = false) {
     if (n < 2) return false;
-    for (int i = 0; i < n; ++i)
-        if (gps[i] && gps[i]->kprog) return false;           // program kernels go member by member
     const boss_gp* g0 = gps[0];
     if (!g0 || g0->Np > set_np_max() || g0->ctx->prof_on || g0->d > 64) return false;
     if (g0->gibbs && (!with_latents || g0->d > GIBBS_KSTAR_MAX_D)) return false;
@@ -480,6 +478,10 @@ static bool predict_set_ok(int n, boss_gp_t* const* gps, const boss_cand* cd, bo
         if (!g || g->aug != g0->aug || g->gibbs != g0->gibbs || !g->fitted || g->pending || g->ctx != cd->ctx || g->N != g0->N || g->Np != g0->Np ||
             g->ld != g0->ld || g->d != g0->d || g->d != cd->d || g->kernel != g0->kernel || g->discrete != g0->discrete)
             return false;
+        // program kernels: members of fitted sets (boss_kgp_fit_batch) under ONE program (the set launch carries it in its arguments);
+        // a list that mixes built-in and program handles, or two programs, goes member by member, and so do handles that stand alone
+        // (boss_kgp_create, or a member that was detached)
+        if (g->kprog != g0->kprog || (g->kprog && (!g->set || std::memcmp(g->kp, g0->kp, sizeof(FitProg)) != 0))) return false;
         if (model && (g->npts != g0->npts || g->ldx != g0->ldx || g->nhead != g0->nhead)) return false;
     }
     return true;
@@ -544,9 +546,16 @@ static int predict_set_enqueue(int n, boss_gp_t* const* gps, const boss_cand* cd
         rc = ws_reserve(c->vscratch, v_one * group);
     }
     if (rc) return rc;
-    const bool pre = g0->aug || g0->gibbs;
-    if (!pre) rc = ws_reserve(c->csc, sizeof(double) * (size_t)d * Mp * n);
+    const bool pre = g0->aug || g0->gibbs || g0->kprog;
+    const bool own_csc = !g0->aug && !g0->gibbs;             // (K* from the member's scaled points: the candidates scaled per member)
+    if (own_csc) rc = ws_reserve(c->csc, sizeof(double) * (size_t)d * Mp * n);
     if (rc) return rc;
+    double* kpv = nullptr;                                   // program kernel: k(x*, x*) per member and candidate, written beside K*
+    if (g0->kprog) {
+        rc = ws_reserve(c->kpv, sizeof(double) * (size_t)Mp * n);
+        if (rc) return rc;
+        kpv = (double*)c->kpv.p;
+    }
     rc = ws_reserve(c->setdesc, sizeof(PredSet) * (size_t)n);
     if (rc) return rc;
     std::vector<PredSet> desc(n);
@@ -555,13 +564,13 @@ static int predict_set_enqueue(int n, boss_gp_t* const* gps, const boss_cand* cd
         desc[i].A = g->A;
         desc[i].Dinv = g->Dinv2;
         desc[i].Xsc = g->Xsc;
-        desc[i].Csc = pre ? nullptr : (const double*)c->csc.p + (size_t)i * d * Mp;
+        desc[i].Csc = own_csc ? (const double*)c->csc.p + (size_t)i * d * Mp : nullptr;
         desc[i].mean_s = mean_all ? mean_all + (size_t)i * mstride : nullptr;
         desc[i].invlam = g->invlam;
         desc[i].mu = mu_all + (size_t)i * mstride;
         desc[i].var = var_all + (size_t)i * mstride;
         desc[i].amp2 = g->amp2;
-        desc[i].Xraw = pre ? g->Xraw : nullptr;
+        desc[i].Xraw = own_csc ? nullptr : g->Xraw;
         if (g->gibbs) {
             desc[i].lamX = g->lamX;
             desc[i].ampX = g->ampX;
@@ -581,7 +590,7 @@ static int predict_set_enqueue(int n, boss_gp_t* const* gps, const boss_cand* cd
         HIPCHK(hipStreamSynchronize(s));
     }
     const PredSet* dsets = (const PredSet*)c->setdesc.p;
-    if (!pre)
+    if (own_csc)
         for (int i0 = 0; i0 < n; i0 += 65535)
             hipLaunchKernelGGL(scale_cand_set_kernel, dim3((Mp + 255) / 256, std::min(65535, n - i0)), dim3(256), 0, s, (const double*)cd->Craw,
                                dsets + i0, (const unsigned char*)g0->discrete_dev, d, Mp);
@@ -595,16 +604,20 @@ static int predict_set_enqueue(int n, boss_gp_t* const* gps, const boss_cand* cd
             continue;
         }
         ++c->set_pre_launches;
-        if (g0->aug)
+        if (g0->kprog)
+            kprog_kstar_set_launch(g0, cd, dsets + i0, tiles, cnt, (double*)c->vscratch.p, kpv + (size_t)i0 * Mp, (size_t)Mp, s);
+        else if (g0->aug)
             hipLaunchKernelGGL(aug_kstar_set_kernel, dim3(Np / 256, tiles, cnt), dim3(256), sizeof(double) * ((size_t)d * (G::BN + 256) + d), s,
                                g0->ldx, d, g0->nhead, g0->N, Np, (const double*)cd->Craw, Mp, g0->kernel, dsets + i0,
                                (double*)c->vscratch.p, (int)G::BN);
         else
             hipLaunchKernelGGL(gibbs_kstar_set_kernel, dim3(Np / 256, tiles, cnt), dim3(256), sizeof(double) * (2 * d * 32 + 32 + 2 * 8 * 256), s,
                                d, g0->N, Np, (const double*)cd->Craw, Mp, dsets + i0, (double*)c->vscratch.p);
+        // (a program kernel's epilogue is the nonstationary one, variance mode 2, as in predict_enqueue: KERN_PROGRAM never reaches kappa_*)
         hipLaunchKernelGGL((predict_kernel_set<G, true>), dim3(tiles, cnt), dim3(G::NTHREADS), PredictLds<G>::BYTES, s, dsets + i0, g0->ld, Np,
-                           g0->N, d, Mp, g0->kernel, (double*)c->vscratch.p, cd->M);
+                           g0->N, d, Mp, g0->kprog ? KERN_GIBBS : g0->kernel, (double*)c->vscratch.p, cd->M);
         if (g0->gibbs) hipLaunchKernelGGL(gibbs_var_set_kernel, dim3((cd->M + 255) / 256, cnt), dim3(256), 0, s, dsets + i0, cd->M);
+        if (g0->kprog) kprog_var_set_launch(s, dsets + i0, cnt, kpv + (size_t)i0 * Mp, (size_t)Mp, cd->M);
         if (after_group && (rc = (*after_group)(i0, cnt)) != BOSS_OK) return rc;
     }
     HIPCHK(hipGetLastError());

@@ -15,6 +15,10 @@
 // workgroup is sized at launch (kprog_block, host_kprog.inc): as many of 4 waves as fit 64 KiB, so the longest program (96 slots,
 // 48 KiB per wave) runs one wave per workgroup and a short one keeps four, several workgroups to a CU either way.  Every thread
 // walks several entries in a stride loop.  The program travels in the kernel arguments.  No atomics: repeated calls agree bit for bit.
+//
+// Many hyper-parameter sets at once (boss_kgp_loglike_batch, boss_kgp_fit_batch, predict_set_enqueue): kprog_gram_kernel takes the
+// set in blockIdx.z over constant strides, kprog_scale_set_kernel writes every set's scaled points, and kprog_kstar_set_kernel /
+// kprog_var_set_kernel are the set forms (grid.z / grid.y = member) of the K* and variance kernels — same bodies, same bits.
 #pragma once
 #include "fitness.hpp"
 
@@ -38,13 +42,30 @@ __device__ __forceinline__ double kprog_pair(const FitProg& g, int d, const doub
     [[clang::always_inline]] return fit_eval(g, col, col + (size_t)2 * d * st, st);
 }
 
+// u = r(x) ⊘ (λ+1e-8) of nb parameter sets from the shared raw points (boss_kgp_loglike_batch, boss_kgp_fit_batch): grid.y = set, set b
+// reads its 1/λ at par + b·sPar and writes Xsc + b·sX.  The product is scale_points_kernel's — the packed point (discrete dims
+// rounded on the host) times the stored 1/λ —, so a set's scaled points are those of a handle updated at the same parameters.
+__global__ void kprog_scale_set_kernel(const double* __restrict__ Xraw, double* __restrict__ Xsc, size_t sX, const double* __restrict__ par,
+                                       size_t sPar, int d, int ldp) {
+    const int b = blockIdx.y;
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= ldp) return;
+    for (int k = 0; k < d; ++k) Xsc[(size_t)b * sX + (size_t)k * ldp + j] = Xraw[(size_t)k * ldp + j] * par[(size_t)b * sPar + k];
+}
+
 // One workgroup per 64×64 tile of the lower triangle (the grid, the padding rows and the unit diagonal of gibbs_gram_kernel):
 // A[i + j·ld] for i >= j; rows / columns >= N are those of the identity.  hyp = {(α+1e-8)², (σ+1e-8)²} on the device.
-__global__ __launch_bounds__(64 * KPROG_MAX_WAVES) void kprog_gram_kernel(FitProg g, const double* __restrict__ Xsc, int d, int N, int Np,
-                                                                          const double* __restrict__ hyp, double* __restrict__ A, int ld) {
+// blockIdx.z = parameter set (as aug_gram_kernel / gibbs_gram_kernel): set z reads its scaled points at Xsc + z·sX and its hyp at
+// hyp + z·sHyp and writes A + z·bstride; a handle's update launches grid.z = 1 with zero strides.
+__global__ __launch_bounds__(64 * KPROG_MAX_WAVES) void kprog_gram_kernel(FitProg g, const double* __restrict__ Xsc, size_t sX, int d, int N, int Np,
+                                                                          const double* __restrict__ hyp, size_t sHyp, double* __restrict__ A, int ld,
+                                                                          size_t bstride) {
     extern __shared__ __attribute__((aligned(16))) char kprog_lds_raw[];
     double* col = reinterpret_cast<double*>(kprog_lds_raw) + threadIdx.x;
     const int st = blockDim.x, t = blockIdx.x;
+    Xsc += (size_t)blockIdx.z * sX;
+    hyp += (size_t)blockIdx.z * sHyp;
+    A += (size_t)blockIdx.z * bstride;
     int bi = (int)((sqrt(8.0 * t + 1.0) - 1.0) * 0.5);
     while ((bi + 1) * (bi + 2) / 2 <= t) ++bi;
     while (bi * (bi + 1) / 2 > t) --bi;
@@ -67,31 +88,58 @@ __global__ __launch_bounds__(64 * KPROG_MAX_WAVES) void kprog_gram_kernel(FitPro
 // K* where the substitution kernels take their right-hand side: out[tile][row][BN] (the layout of gibbs_kstar_kernel<BN>: the V
 // slabs of predict_kernel<G, true>, or the residual array of the few-candidates path).  Grid (Np / 256, tiles); rows >= N and
 // candidates >= M are 0.  The workgroups of row block 0 also write pvar[j] = (α+1e-8)² f(u*_j, u*_j) for their tile's candidates.
+// (one body for the single-handle and the set launch: `out` is the tile's slab, rblock / tile the workgroup's place in the grid)
 template <int BN>
-__global__ __launch_bounds__(64 * KPROG_MAX_WAVES) void kprog_kstar_kernel(FitProg g, const double* __restrict__ Xsc, int d, int N, int Np,
-                                                                           const double* __restrict__ Csc, int Mp, int M, double amp2,
-                                                                           double* __restrict__ out, double* __restrict__ pvar) {
-    extern __shared__ __attribute__((aligned(16))) char kprog_lds_raw[];
-    double* col = reinterpret_cast<double*>(kprog_lds_raw) + threadIdx.x;
-    const int st = blockDim.x, c0 = blockIdx.y * BN, rbase = blockIdx.x * 256;
-    out += (size_t)blockIdx.y * Np * BN;
+__device__ __forceinline__ void kprog_kstar_body(const FitProg& g, const double* __restrict__ Xsc, int d, int N, int Np,
+                                                 const double* __restrict__ Csc, int Mp, int M, double amp2, double* __restrict__ out,
+                                                 double* __restrict__ pvar, int rblock, int tile, double* __restrict__ col, int st) {
+    const int c0 = tile * BN, rbase = rblock * 256;
     for (int e = threadIdx.x; e < 256 * BN; e += st) {       // (consecutive threads: consecutive doubles of the slab)
         const int row = rbase + e / BN, c = e % BN, j = c0 + c;
         double v = 0.0;
         if (row < N && j < M) v = amp2 * kprog_pair(g, d, Xsc, Np, row, Csc, Mp, j, col, st);
         out[(size_t)row * BN + c] = v;
     }
-    if (blockIdx.x == 0)
+    if (rblock == 0)
         for (int c = threadIdx.x; c < BN; c += st) {
             const int j = c0 + c;
             if (j < M) pvar[j] = amp2 * kprog_pair(g, d, Csc, Mp, j, Csc, Mp, j, col, st);
         }
+}
+template <int BN>
+__global__ __launch_bounds__(64 * KPROG_MAX_WAVES) void kprog_kstar_kernel(FitProg g, const double* __restrict__ Xsc, int d, int N, int Np,
+                                                                           const double* __restrict__ Csc, int Mp, int M, double amp2,
+                                                                           double* __restrict__ out, double* __restrict__ pvar) {
+    extern __shared__ __attribute__((aligned(16))) char kprog_lds_raw[];
+    double* col = reinterpret_cast<double*>(kprog_lds_raw) + threadIdx.x;
+    kprog_kstar_body<BN>(g, Xsc, d, N, Np, Csc, Mp, M, amp2, out + (size_t)blockIdx.y * Np * BN, pvar, (int)blockIdx.x, (int)blockIdx.y, col,
+                         (int)blockDim.x);
+}
+
+// K* of a SET of equally shaped program-kernel posteriors under ONE program, into the V slabs predict_kernel_set<G, true> reads
+// (the layout of gibbs_kstar_set_kernel: member z, tile t at slab z·tiles + t, 32 candidates wide): grid = (256-row blocks,
+// candidate tiles, members).  A member's scaled points, its scaled candidates (scale_cand_set_kernel) and α² come from its
+// descriptor; its prior variances go to pvar + z·spv (the workgroups of row block 0).
+__global__ __launch_bounds__(64 * KPROG_MAX_WAVES) void kprog_kstar_set_kernel(FitProg g, int d, int N, int Np, int Mp, int M,
+                                                                               const PredSet* __restrict__ sets, double* __restrict__ Vscratch,
+                                                                               double* __restrict__ pvar, size_t spv) {
+    extern __shared__ __attribute__((aligned(16))) char kprog_lds_raw[];
+    double* col = reinterpret_cast<double*>(kprog_lds_raw) + threadIdx.x;
+    const PredSet ps = sets[blockIdx.z];
+    kprog_kstar_body<32>(g, ps.Xsc, d, N, Np, ps.Csc, Mp, M, ps.amp2, Vscratch + ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * Np * 32,
+                         pvar + (size_t)blockIdx.z * spv, (int)blockIdx.x, (int)blockIdx.y, col, (int)blockDim.x);
 }
 
 // σ²(x*) = k(x*, x*) − Σv² + 1e-18: the finish kernels left −Σv² in var (their mode 2, as for the nonstationary model)
 __global__ void kprog_var_kernel(double* __restrict__ var, const double* __restrict__ pvar, int M) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j < M) var[j] = pvar[j] + var[j] + PREDICT_JITTER;
+}
+// ... of a set: grid.y = member, its σ² in its descriptor, its prior variances at pvar + y·spv
+__global__ void kprog_var_set_kernel(const PredSet* __restrict__ sets, const double* __restrict__ pvar, size_t spv, int M) {
+    const PredSet ps = sets[blockIdx.y];
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < M) ps.var[j] = pvar[(size_t)blockIdx.y * spv + j] + ps.var[j] + PREDICT_JITTER;
 }
 // ------------------------------------------------------------------------------------------
 // Gradients of a program-kernel posterior (boss_kgp_set_grad): the reverse sweep kern_grad behind fit_eval gives all 2d partials

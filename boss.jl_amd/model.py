@@ -216,26 +216,8 @@ class HipGaussianProcess:
         dev = None                                           # DeviceMean: every output's S×N mean rows from one device call
         if device_mean_of(self) is not None and S:
             dev = self.device_means(data.X, samples, api.MEAN_OUTPUT_MAJOR)[0]
-        if device_kernel_of(self) is not None:
-            # a program kernel: the batched factorisation is built-in-kernel only — S updates on one resident handle per output
-            for i in range(data.Y.shape[0]):
-                g = self._new_gp(data.X, data.Y[i])
-                try:
-                    for k, s in enumerate(samples):
-                        if dev is not None:
-                            m = np.ascontiguousarray(dev[i][k])
-                        else:
-                            m = self.mean_values(data.X, s if self.parametric is not None else None, i)
-                        try:
-                            tot[k] += g.update(s.lengthscales[:, i], s.amplitudes[i], s.noise_std[i], m)
-                        except api.PosDefException:
-                            tot[k] = -math.inf               # safe_data_loglike (src/surrogate_model.jl:2-12)
-                        except api.BossError as e:           # an invalid parameter set is a sample of likelihood -inf, as its status is
-                            if e.code != api.BOSS_E_INVALID:  # in the batched call of the built-in kernels; anything else is an error
-                                raise
-                            tot[k] = -math.inf
-                finally:
-                    g.close()
+        dk = device_kernel_of(self)                          # a program kernel: boss_kgp_loglike_batch, same arrays
+        if dk is not None and S == 0:
             return tot
         for i in range(data.Y.shape[0]):
             lam = np.stack([s.lengthscales[:, i] for s in samples], axis=1)
@@ -249,7 +231,10 @@ class HipGaussianProcess:
             else:
                 mv = self.mean_values(data.X, None, i)
                 means = mv
-            ll, _ = api.loglike_batch(data.X, data.Y[i], self.kernel, lam, amp, sig, means, self.discrete, self.device)
+            if dk is not None:
+                ll, _ = api.kgp_loglike_batch(data.X, data.Y[i], dk.program, lam, amp, sig, means, self.discrete, self.device)
+            else:
+                ll, _ = api.loglike_batch(data.X, data.Y[i], self.kernel, lam, amp, sig, means, self.discrete, self.device)
             tot += ll
         return tot
 
@@ -352,11 +337,13 @@ class HipGaussianProcess:
     def model_posterior(self, params, data: ExperimentData, reserve: int = 0):
         """model_posterior (src/posterior.jl:8-19,38-41): a vector of params broadcasts (BI samples)."""
         if isinstance(params, (list, tuple)):
-            if len(params) > 1 and reserve == 0 and device_kernel_of(self) is None:   # (a program kernel: create + update per sample)
-                # the S samples of a BI fit: per output ONE batched factorisation (boss_gp_fit_batch) — X and y uploaded once,
+            if len(params) > 1 and reserve == 0:
+                # the S samples of a BI fit: per output ONE batched factorisation (boss_gp_fit_batch; boss_kgp_fit_batch under a
+                # DeviceKernel) — X and y uploaded once,
                 # the S posteriors resident as members of one set.  A sample whose matrix is not positive definite raises, as
                 # the reference's cholesky would inside the broadcast (src/posterior.jl:15-19)
                 P, S = data.Y.shape[0], len(params)
+                dk = device_kernel_of(self)
                 per_out = []
                 dev = None                                   # DeviceMean: the S×N mean rows of every output from one device call
                 if device_mean_of(self) is not None:
@@ -365,9 +352,12 @@ class HipGaussianProcess:
                     means = [self.mean_values(data.X, p, i) for p in params] if dev is None else list(dev[i])
                     mX = None if all(m is None for m in means) else np.stack([np.zeros(data.X.shape[1]) if m is None else np.asarray(m, float)
                                                                               for m in means])
-                    gps, _, st = api.fit_batch(data.X, data.Y[i], self.kernel, np.stack([p.lengthscales[:, i] for p in params], axis=1),
-                                               [p.amplitudes[i] for p in params], [p.noise_std[i] for p in params], mX, self.discrete,
-                                               self.device)
+                    lam = np.stack([p.lengthscales[:, i] for p in params], axis=1)
+                    amp, sig = [p.amplitudes[i] for p in params], [p.noise_std[i] for p in params]
+                    if dk is not None:
+                        gps, _, st = api.kgp_fit_batch(data.X, data.Y[i], dk.program, lam, amp, sig, mX, self.discrete, self.device, grad=dk.grad)
+                    else:
+                        gps, _, st = api.fit_batch(data.X, data.Y[i], self.kernel, lam, amp, sig, mX, self.discrete, self.device)
                     if np.any(st != 0):
                         for g in gps:
                             g.close()

@@ -711,7 +711,7 @@ int boss_acq_ei_grad_warp(const boss_warp_t* warp, int P, int S, boss_gp_t* cons
  * f(u_j, u_i): cholesky(Symmetric(K)) reads the upper triangle.  logpdf, μ, σ² (+1e-18, _clip_var), BOSS_E_NOT_PD, BOSS_E_NEG_VAR
  * and prior means are those of boss_gp_create handles.  The kernels hold no atomics: repeated calls agree bit for bit.
  * Calls that take the handle: boss_gp_update (flags, logpdf_out as usual), boss_gp_sync, boss_gp_predict, boss_acq_ei (one-shot or
- * resident candidates, P outputs × S samples, member by member), boss_gp_set_y, boss_gp_n, boss_gp_get_factor, boss_gp_free.
+ * resident candidates, P outputs × S samples; the members of boss_kgp_fit_batch calls as a set, see there), boss_gp_set_y, boss_gp_n, boss_gp_get_factor, boss_gp_free.
  * Every other entry point that takes a boss_gp_t* returns BOSS_E_INVALID ("not available for program-kernel posteriors"), or, for
  * the boss_ggp_* / boss_ngp_* calls, their own "handle was not created by ..." refusal.
  * BOSS_E_INVALID: d outside 1..16, N < 1 or above 46080, NULL X, y or kern.
@@ -736,6 +736,30 @@ int boss_kgp_create(int device, int d, int N, const double* X, const double* y, 
                     const boss_kern_t* kern, boss_gp_t** out);
 int boss_kern_grad_host(const boss_kern_t* kern, int n, const double* U, const double* V, double* k_out, double* dU, double* dV);
 int boss_kgp_set_grad(boss_gp_t* g, int on);
+
+/* S hyper-parameter sets of one output slice under ONE kernel program: `loglike.(samples)` of SamplingMAP
+ * (src/model_fitters/sampling.jl:59-78) and the S posteriors of a Bayesian-inference fit (src/posterior.jl:15-19).
+ * boss_kgp_loglike_batch: X d×N, y N, lengthscales d×S, amplitudes / noise_stds S, mean_X NULL, N values (mean_stride 0) or N×S
+ * (mean_stride N); ll_out[s] is bit for bit the logpdf of boss_gp_update on a boss_kgp_create handle at the parameters of set s.
+ * A set with invalid parameters (BOSS_E_INVALID) or a matrix that is not positive definite (BOSS_E_NOT_PD) gets -Inf and its
+ * status in status_out (may be NULL); the other sets are computed.  The Gram matrices of all sets of a chunk (12 GiB of matrices)
+ * are written by one launch.  S = 0 returns BOSS_OK and touches nothing.
+ * boss_kgp_fit_batch: the arguments of boss_gp_fit_batch with the program in the kernel id's place (S = 0: BOSS_OK, nothing is
+ * built).  out[s] are ordinary program-kernel handles — views into one slab, each with its own copy of the program — with the
+ * factor, logpdf and predictions of a boss_kgp_create handle updated at set s; boss_gp_update on a member rewrites only that
+ * member, boss_gp_set_y detaches it from the slab first, boss_kgp_set_grad works on a member, and whatever refuses a program-kernel
+ * handle refuses a member with the same message.  n >= 2 members of such calls that have one shape and bytewise equal programs
+ * (the S samples × P outputs of a model: one call per output over one boss_kern_t) are predicted by ONE set of launches in
+ * boss_acq_ei (P × S) and the other value-only set calls; a list that mixes programs, or program and built-in handles, or holds a
+ * boss_kgp_create handle or a detached member, goes member by member as before, and so do the gradient calls.
+ * BOSS_E_INVALID (decided before a device is needed): NULL kern, d != the program's x_dim, S < 0, N < 1, NULL X or y, and for
+ * S > 0 a NULL hyper-parameter array, ll_out or out. */
+int boss_kgp_loglike_batch(int device, int d, int N, const double* X, const double* y, const unsigned char* discrete,
+                           const boss_kern_t* kern, int S, const double* lengthscales, const double* amplitudes,
+                           const double* noise_stds, const double* mean_X, int mean_stride, double* ll_out, int* status_out);
+int boss_kgp_fit_batch(int device, const boss_kern_t* kern, int d, int N, const double* X, const double* y, const double* mean_X,
+                       int mean_stride, const unsigned char* discrete, int S, const double* lengthscales, const double* amplitudes,
+                       const double* noise_stds, boss_gp_t** out, double* logpdf_out, int* status_out);
 
 /* boss_ngp_predict_grad for n nonstationary posteriors at the same M candidates in ONE call, and the sample-averaged acquisition
  * gradient on top of it: boss_acq_ei_grad_set for NonstationaryGP posteriors (BI samples of a finite_nongp model under

@@ -1,5 +1,6 @@
-// kernel_program_fuzz.cpp — boss_kern_create's validation and the host interpreter (boss_kern_eval_host) over malformed and random
-// programs, as a stand-alone host program for a sanitizer build.  No device is touched: only entry points that need none are called.
+// kernel_program_fuzz.cpp — boss_kern_create's validation, the host interpreter (boss_kern_eval_host) and the argument checks of the
+// batched entry points (boss_kgp_loglike_batch, boss_kgp_fit_batch) over malformed and random programs, as a stand-alone host
+// program for a sanitizer build.  No device is touched: only entry points that need none are called.
 //
 //   hipcc -O1 -g --offload-arch=gfx950 -std=c++17 -w -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-omit-frame-pointer \
 //         -pthread -ldl -o /tmp/kernel_program_fuzz tools/kernel_program_fuzz.cpp boss.jl_amd/csrc/bosship.hip
@@ -26,6 +27,34 @@ static int rnd_int(int lo, int hi) { return lo + (int)(rnd() % (uint64_t)(hi - l
 
 static long n_ok = 0, n_bad = 0;
 
+// The batched entry points over an accepted program, as far as they go without a device: every call here is decided by the argument
+// checks in front of the device context (NULL program, another x_dim, S < 0, NULL arrays with S > 0 -> BOSS_E_INVALID; S = 0 -> BOSS_OK
+// with nothing written).  X doubles as the hyper-parameter arrays: it is never read.
+static void batch_refusals(const boss_kern_t* k, int d, const double* X, double* out) {
+    boss_gp_t* hs[3] = {nullptr, nullptr, nullptr};
+    int st[3] = {0, 0, 0};
+    const int S = rnd_int(1, 3), N = rnd_int(1, 16);
+    struct Case { const boss_kern_t* k; int d, S; const double *X, *y, *lam, *amp, *sig; int want; };
+    const Case cases[] = {
+        {nullptr, d, S, X, X, X, X, X, BOSS_E_INVALID},     {k, d + 1, S, X, X, X, X, X, BOSS_E_INVALID},
+        {k, d, -rnd_int(1, 5), X, X, X, X, X, BOSS_E_INVALID}, {k, d, S, nullptr, X, X, X, X, BOSS_E_INVALID},
+        {k, d, S, X, nullptr, X, X, X, BOSS_E_INVALID},      {k, d, S, X, X, nullptr, X, X, BOSS_E_INVALID},
+        {k, d, S, X, X, X, nullptr, X, BOSS_E_INVALID},      {k, d, S, X, X, X, X, nullptr, BOSS_E_INVALID},
+        {k, d, 0, X, X, nullptr, nullptr, nullptr, BOSS_OK},
+    };
+    for (const Case& c : cases) {
+        const int a = boss_kgp_loglike_batch(0, c.d, N, c.X, c.y, nullptr, c.k, c.S, c.lam, c.amp, c.sig, nullptr, 0, out, st);
+        const int b = boss_kgp_fit_batch(0, c.k, c.d, N, c.X, c.y, nullptr, 0, nullptr, c.S, c.lam, c.amp, c.sig, hs, out, st);
+        if (a != c.want || b != c.want || hs[0] || hs[1] || hs[2]) {
+            std::fprintf(stderr, "batched entry points: status %d / %d, expected %d (%s)\n", a, b, c.want, boss_last_error());
+            std::exit(7);
+        }
+    }
+    if (boss_kgp_loglike_batch(0, d, N, X, X, nullptr, k, S, X, X, X, nullptr, 0, nullptr, st) != BOSS_E_INVALID ||
+        boss_kgp_fit_batch(0, k, d, N, X, X, nullptr, 0, nullptr, S, X, X, X, nullptr, out, st) != BOSS_E_INVALID)
+        std::exit(7);
+}
+
 static int try_program(int d, int nc, const double* consts, int ni, const int* code, int out_id) {
     boss_kern_t* k = nullptr;
     const int rc = boss_kern_create(d, nc, consts, ni, code, out_id, &k);
@@ -44,6 +73,7 @@ static int try_program(int d, int nc, const double* consts, int ni, const int* c
     for (auto& x : V) x = (double)rnd_int(-3000, 3000) / 1000.0;
     if (boss_kern_eval_host(k, n, U.data(), V.data(), out.data()) != BOSS_OK) std::exit(3);
     if (boss_kern_eval_host(k, 0, nullptr, nullptr, nullptr) != BOSS_OK) std::exit(3);
+    batch_refusals(k, d, U.data(), out.data());
     boss_kern_free(k);
     return rc;
 }
