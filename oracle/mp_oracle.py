@@ -6,7 +6,9 @@ src/models/gaussian_process.jl:216-248 (the +1e-8 parameter offsets, α²·κ(r/
 
 `posterior` is the plain posterior of tests/golden/make_golden.py.  `plain_truth`, `grad_obs_truth` and `gibbs_truth` (second half
 of the file) are the truths of tests/golden/make_regimes.py: candidate gradients, likelihood gradients, the gradient-observation
-model and the Gibbs model, differentiated numerically at high precision.  `acq_truth` (end of the file) is the truth of
+model and the Gibbs model, differentiated numerically at high precision.  `plain_cov_truth`, `grad_obs_pred_truth`, `gibbs_pred_truth`
+and `kprog_truth` are the truths of tests/golden/make_regimes_more.py: posterior covariances, the candidate gradients of the
+gradient-observation and Gibbs models, and program-kernel posteriors.  `acq_truth` (end of the file) is the truth of
 tests/golden/make_acq_tails.py: the EI × feasibility acquisition of one candidate and its gradient, with the condition sums of the bars.
 """
 from __future__ import annotations
@@ -346,6 +348,176 @@ def gibbs_truth(X, y, lam_X, amp_X, noise_X, Xs, lam_Xs, amp_Xs, mean_X=None, me
             damp[i] = float(sa)
             dnoise[i] = float(noi[i] * G[i])
         out.update(dlam=dlam, damp=damp, dnoise=dnoise, dmean=[float(t) for t in a])
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
+# Truths for tests/golden/make_regimes_more.py: posterior covariances of the three models, candidate gradients of the
+# gradient-observation and the Gibbs model, and the posterior of a program kernel.  Same conventions as above (the +1e-8 lift, the
+# 1e-18 jitter where the model has one, unclipped variances), and again no differentiation rule of a kernel: mp.diff of the scalar
+# kernel by multi-index, mp.diff of μ and σ² as wholes, a central difference of the whole likelihood.
+# ------------------------------------------------------------------------------------------------
+def _cov_of(L, kstars, kss, jitter):
+    """K** − VᵀV from the columns k*_c (lists) and the prior covariance kss(c, e); jitter on the diagonal.  M×M nested list of floats,
+    mirrored from one triangle (exactly symmetric)."""
+    M = len(kstars)
+    V = [_fsub(L, ks) for ks in kstars]
+    out = [[0.0] * M for _ in range(M)]
+    for c in range(M):
+        for e in range(c + 1):
+            out[c][e] = out[e][c] = float(kss(c, e) - _dot(V[c], V[e]) + (jitter if c == e else 0))
+    return out
+
+
+def plain_cov_truth(X, kernel, lengthscale, amplitude, noise_std, Xs, dps: int = 50, lift: str = _OFF):
+    """cov[M][M] of the plain model at the candidates: K** − K*ᵀ(K + σ²I)⁻¹K* + 1e-18·I, unclipped."""
+    mp.mp.dps = dps
+    off = mp.mpf(lift)
+    cols, scol = _cols(X), _cols(Xs)
+    lam, amp, sig = [t + off for t in _mpv(lengthscale)], mp.mpf(float(amplitude)) + off, mp.mpf(float(noise_std)) + off
+    L = mp.cholesky(_plain_gram(kernel, cols, lam, amp, sig))
+    kstars = [[_k(kernel, x, xs, lam, amp) for x in cols] for xs in scol]
+    return _cov_of(L, kstars, lambda c, e: _k(kernel, scol[c], scol[e], lam, amp), mp.mpf("1e-18"))
+
+
+def grad_obs_pred_truth(X, y, dY, kernel, lengthscale, amplitude, noise_std, grad_noise_std, Xs, dps: int = 50, lift: str = _OFF):
+    """The gradient-observation model at the candidates: dmu[d][M] = (∂k*/∂x*_m)ᵀa, dvar[d][M] = −2(K⁻¹k*)ᵀ∂k*/∂x*_m (the prior
+    variance α² is constant) and the value posterior's cov[M][M] = K** − k*ᵀK⁻¹k* (neither jittered nor clipped).  The rows of k* are
+    those of grad_obs_truth; the rows of ∂k*/∂x*_m are mixed partials of the scalar kernel over (x*, x_j) by multi-index mp.diff, as
+    _aug_gram forms its blocks."""
+    mp.mp.dps = dps
+    d, n, M = len(X), len(X[0]), len(Xs[0])
+    off = mp.mpf(lift)
+    cols, scol = _cols(X), _cols(Xs)
+    yt = _mpv(y) + [mp.mpf(float(dY[l][j])) for l in range(d) for j in range(n)]
+    lam = [t + off for t in _mpv(lengthscale)]
+    amp, sig, sgd = (mp.mpf(float(t)) + off for t in (amplitude, noise_std, grad_noise_std))
+    _, L, a = _logpdf_of(_aug_gram(kernel, cols, lam, amp, sig, sgd), yt)
+
+    def kk(*z):
+        return _k(kernel, list(z[:d]), list(z[d:]), lam, amp)
+
+    def idx(m, l):                  # derivative along x*_m (m >= 0) and along (x_j)_l (l >= 0)
+        o = [0] * (2 * d)
+        if m >= 0:
+            o[m] += 1
+        if l >= 0:
+            o[d + l] += 1
+        return tuple(o)
+
+    out = {"dmu": [[0.0] * M for _ in range(d)], "dvar": [[0.0] * M for _ in range(d)]}
+    kstars = []
+    for c in range(M):
+        zs = [tuple(scol[c]) + tuple(cols[j]) for j in range(n)]
+        ks = [kk(*z) for z in zs] + [mp.diff(kk, zs[j], idx(-1, l)) for l in range(d) for j in range(n)]
+        kstars.append(ks)
+        w = _bsub(L, _fsub(L, ks))                               # K⁻¹k*
+        for m in range(d):
+            dks = [mp.diff(kk, z, idx(m, -1)) for z in zs] + [mp.diff(kk, zs[j], idx(m, l)) for l in range(d) for j in range(n)]
+            out["dmu"][m][c] = float(_dot(dks, a))
+            out["dvar"][m][c] = float(-2 * _dot(dks, w))
+    out["cov"] = _cov_of(L, kstars, lambda c, e: _k(kernel, scol[c], scol[e], lam, amp), 0)
+    return out
+
+
+def gibbs_pred_truth(X, y, lam_X, amp_X, noise_X, Xs, lam_Xs, amp_Xs, dlam_Xs, damp_Xs, mean_X=None, dps: int = 50):
+    """The nonstationary model at the candidates: cov[M][M] (+1e-18 on the diagonal, unclipped) and dmu[d][M], dvar[d][M] with the
+    candidate's latent values and Jacobians taken as given numbers (dlam_Xs[l][m][c] = ∂λ_l/∂x_m, damp_Xs[m][c] = ∂α/∂x_m): the
+    derivative at t = 0 of μ (of σ²) along (x* + t·e_m, λ* + t·dlam[:, m], α* + t·damp[m]), by mp.diff of the whole expression."""
+    mp.mp.dps = dps
+    d, N, M = len(X), len(X[0]), len(Xs[0])
+    cols, scol = _cols(X), _cols(Xs)
+    lam, lams = _cols(lam_X), _cols(lam_Xs)
+    amp, amps, noi = _mpv(amp_X), _mpv(amp_Xs), _mpv(noise_X)
+    delta = [mp.mpf(float(y[j])) - (mp.mpf(float(mean_X[j])) if mean_X is not None else 0) for j in range(N)]
+    K = mp.matrix(N, N)
+    for i in range(N):
+        for j in range(i):
+            K[i, j] = K[j, i] = _gibbs_k(cols[i], lam[i], amp[i], cols[j], lam[j], amp[j])
+        K[i, i] = amp[i] * amp[i] + noi[i] * noi[i]
+    _, L, a = _logpdf_of(K, delta)
+    kstars = [[_gibbs_k(cols[i], lam[i], amp[i], scol[c], lams[c], amps[c]) for i in range(N)] for c in range(M)]
+    out = {"cov": _cov_of(L, kstars, lambda c, e: _gibbs_k(scol[c], lams[c], amps[c], scol[e], lams[e], amps[e]), mp.mpf("1e-18")),
+           "dmu": [[0.0] * M for _ in range(d)], "dvar": [[0.0] * M for _ in range(d)]}
+    for c in range(M):
+        for m in range(d):
+            dl = [mp.mpf(float(dlam_Xs[l][m][c])) for l in range(d)]
+            da = mp.mpf(float(damp_Xs[m][c]))
+
+            def kstar(t):
+                xs = [scol[c][k] + (t if k == m else 0) for k in range(d)]
+                ls = [lams[c][l] + t * dl[l] for l in range(d)]
+                al = amps[c] + t * da
+                return [_gibbs_k(cols[i], lam[i], amp[i], xs, ls, al) for i in range(N)], al
+
+            def mu_t(t):
+                return _dot(kstar(t)[0], a)
+
+            def var_t(t):
+                ks, al = kstar(t)
+                v = _fsub(L, ks)
+                return al * al - _dot(v, v) + mp.mpf("1e-18")
+
+            out["dmu"][m][c] = float(mp.diff(mu_t, 0))
+            out["dvar"][m][c] = float(mp.diff(var_t, 0))
+    return out
+
+
+def kprog_truth(f, X, y, lengthscale, amplitude, noise_std, Xs, mean_X=None, mean_s=None, no_grad_at=(), dps: int = 50,
+                want_llgrad: bool = True, lift: str = _OFF):
+    """The posterior under a program kernel k(x, y) = (α+1e-8)² f(x ⊘ (λ+1e-8), y ⊘ (λ+1e-8)); f(u, v) takes two lists of mpmath
+    numbers (the caller wraps the 50-digit interpreter of the traced program).  Keys and conventions of plain_truth: logpdf, mu[M],
+    var[M] (k(x*, x*) − k*ᵀK⁻¹k* + 1e-18, unclipped), dmu[d][M], dvar[d][M] (mp.diff of μ(x*) and σ²(x*) as wholes, the prior
+    variance included; NaN at the candidates listed in no_grad_at, where f has a cusp), llgrad[d+2] (central difference of the whole
+    likelihood).  Raises where K is not positive definite."""
+    mp.mp.dps = dps
+    d, N, M = len(X), len(X[0]), len(Xs[0])
+    off = mp.mpf(lift)
+    cols, scol = _cols(X), _cols(Xs)
+    delta = [mp.mpf(float(y[j])) - (mp.mpf(float(mean_X[j])) if mean_X is not None else 0) for j in range(N)]
+
+    def kf(xa, xb, lam, amp):
+        return amp * amp * f([xa[k] / lam[k] for k in range(d)], [xb[k] / lam[k] for k in range(d)])
+
+    def gram(lam, amp, sig):
+        K = mp.matrix(N, N)
+        for i in range(N):
+            for j in range(i):
+                K[i, j] = K[j, i] = kf(cols[i], cols[j], lam, amp)
+            K[i, i] = kf(cols[i], cols[i], lam, amp) + sig * sig
+        return K
+
+    def ll(theta):
+        return _logpdf_of(gram([t + off for t in theta[:d]], theta[d] + off, theta[d + 1] + off), delta)[0]
+
+    theta = _mpv(lengthscale) + [mp.mpf(float(amplitude)), mp.mpf(float(noise_std))]
+    lam, amp, sig = [t + off for t in theta[:d]], theta[d] + off, theta[d + 1] + off
+    logpdf, L, a = _logpdf_of(gram(lam, amp, sig), delta)
+    nan = float("nan")
+    out = {"logpdf": float(logpdf), "mu": [], "var": [], "dmu": [[nan] * M for _ in range(d)], "dvar": [[nan] * M for _ in range(d)]}
+
+    def mu_at(xs):
+        return _dot([kf(cols[i], xs, lam, amp) for i in range(N)], a)
+
+    def var_at(xs):
+        v = _fsub(L, [kf(cols[i], xs, lam, amp) for i in range(N)])
+        return kf(xs, xs, lam, amp) - _dot(v, v) + mp.mpf("1e-18")
+
+    for j in range(M):
+        xs = scol[j]
+        out["mu"].append(float(mu_at(xs) + (mp.mpf(float(mean_s[j])) if mean_s is not None else 0)))
+        out["var"].append(float(var_at(xs)))
+        if j in no_grad_at:
+            continue
+        for m in range(d):
+            along = lambda g: (lambda t: g(xs[:m] + [t] + xs[m + 1:]))          # noqa: E731
+            out["dmu"][m][j] = float(mp.diff(along(mu_at), xs[m]))
+            out["dvar"][m][j] = float(mp.diff(along(var_at), xs[m]))
+    if want_llgrad:
+        mp.mp.dps = dps + 30
+        h = mp.mpf("1e-25")
+        out["llgrad"] = [float(_cdiff(ll, theta, i, h)) for i in range(d + 2)]
+        mp.mp.dps = dps
     return out
 
 

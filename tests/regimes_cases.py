@@ -12,7 +12,10 @@ Bars, with u = 2⁻⁵³, rows = N or n(1+d), B = cond(K)·rows·u (the project'
 B >= rows·u >= 36u here; were B < 8u, the multiple of B is replaced by 64u (a sum of `rows` terms).
 
 Variance clip: the device maps var ∈ (−1e-8, 0) to 0 and raises below; a candidate whose TRUE variance is <= 2·(var bar) + 1e-8 is
-left out of the call (keep_mask) so that a rounding error cannot turn into another code path."""
+left out of the call (keep_mask) so that a rounding error cannot turn into another code path.
+
+The second half of the file holds the same for the second fixture, tests/golden/regimes_more.json (make_regimes_more.py,
+test_regimes_more_host.py, test_gpu_regimes_more.py): further truths of the same cases and the program-kernel cases."""
 import json
 import os
 
@@ -205,10 +208,13 @@ def ratios(c, got, model, keep=None):
     B = unit(c)
     for k, v in got.items():
         want = gibbs_llgrad(c) if (model == "gibbs" and k == "llgrad") else np.asarray(c[k])
-        scale = c["amp2"] if k == "var" else (1 + float(np.abs(want).max()))
+        held = np.isfinite(want)                                   # (a truth left out on purpose is stored as NaN: regimes_more)
+        scale = c["amp2"] if k in ("var", "cov") else (1 + float(np.abs(want[held]).max()))
         if keep is not None and k in ("mu", "var", "dmu", "dvar"):
-            want = want[..., keep]
-        err = float(np.abs(np.asarray(v) - want).max()) if want.size else 0.0
+            want, held = want[..., keep], held[..., keep]
+        if keep is not None and k == "cov":
+            want, held = want[np.ix_(keep, keep)], held[np.ix_(keep, keep)]
+        err = float(np.asarray(np.abs(np.asarray(v) - want))[held].max()) if held.any() else 0.0
         out[k] = err / (B * scale)
     return out
 
@@ -216,12 +222,14 @@ def ratios(c, got, model, keep=None):
 LIMIT = {"logpdf": 8, "mu": 8, "var": 8, "dmu": 100, "dvar": 100, "llgrad": 100}
 
 
-def check(c, got, model, what, frac=1.0, keep=None):
-    """Asserts every quantity of `got` within frac × its bar of the case's truths; returns the ratios err/(B·scale)."""
+def check(c, got, model, what, frac=1.0, keep=None, limit=None):
+    """Asserts every quantity of `got` within frac × its bar of the case's truths; returns the ratios err/(B·scale).  limit: the bars'
+    multipliers per key where they are not LIMIT's (limit_more)."""
+    mult = LIMIT if limit is None else limit
     r = ratios(c, got, model, keep)
     B = unit(c)
     for k, v in r.items():
-        lim = LIMIT[k] * (1.0 if B >= 8 * U else 64 * U / (LIMIT[k] * B)) * frac
+        lim = mult[k] * (1.0 if B >= 8 * U else 64 * U / (mult[k] * B)) * frac
         assert v <= lim, f"{what} {c['name']}: {k} err/B = {v:.3g} > {lim:.3g} (cond {c['cond']:.3g}, B {B:.3g})"
     return r
 
@@ -335,3 +343,257 @@ def is_corner(model, c):
     if model == "grad":
         return c["lam_rel"] in (0.05, 30.0)
     return c["gm"] in (0.05, 5.0) and c["clam"] in (1, 100)
+
+
+# ================================================================================================ the second fixture
+# tests/golden/regimes_more.json + regimes_more_arrays.npy (tests/golden/make_regimes_more.py), for tests/test_regimes_more_host.py and
+# tests/test_gpu_regimes_more.py: further truths of the cases above, referred to by name — cov[M][M] (all three models), dmu / dvar
+# (gradient-observation and Gibbs model) — and the cases of a fourth model, "kprog": program-kernel posteriors on the plain datasets.
+# Same encoding.  Bars: cov entries 8·B·amp2, every gradient 100·B·(1 + max|want|), kprog logpdf / mu / var as plain; the multiplier of
+# a quantity whose fp64 oracle does not stay within an eighth of it is 8 × the oracle's worst ratio, rounded up to a power of two — the
+# header holds the worst ratios and the multipliers (limit_more), chosen from the oracle alone.
+PATH_MORE = os.path.join(HERE, "golden", "regimes_more.json")
+ARRAYS_MORE = os.path.join(HERE, "golden", "regimes_more_arrays.npy")
+MODELS_MORE = ("plain", "grad", "gibbs", "kprog")
+KPROG_CLOSURES = ("expo", "ratquad", "persq", "dot1")          # of tests/kernel_program_cases.py
+BASE_MULT = {"logpdf": 8, "mu": 8, "var": 8, "cov": 8, "dmu": 100, "dvar": 100, "llgrad": 100}
+
+
+def more_layout(model, D):
+    """[(key, shape)] of what the second fixture stores per case."""
+    d = D["X"].shape[0]
+    M = D["Xs"].shape[1]
+    if model == "plain":
+        return [("cov", (M, M))]
+    if model in ("grad", "gibbs"):
+        return [("dmu", (d, M)), ("dvar", (d, M)), ("cov", (M, M))]
+    return [("logpdf", ()), ("mu", (M,)), ("var", (M,)), ("dmu", (d, M)), ("dvar", (d, M)), ("llgrad", (d + 2,))]
+
+
+def gibbs_latent_jacobians(X, c):
+    """(dlam d×d×n, damp d×n) of gibbs_latents at the columns of X, in closed form: ∂λ_l/∂x_m = δ_lm λ_l ln C_λ, ∂α/∂x_m = α ln C_α / d."""
+    lam, amp, _ = gibbs_latents(X, c)
+    d, n = lam.shape
+    dlam = np.zeros((d, d, n))
+    for l in range(d):
+        dlam[l, l] = lam[l] * np.log(float(c["clam"]))
+    return dlam, np.tile(amp * np.log(float(c["camp"])) / d, (d, 1))
+
+
+def kprog_closure(c):
+    import kernel_program_cases as cases
+    return cases.CLOSURES[c["closure"]]
+
+
+def kprog_derived(D, c):
+    """name, rows and the variance scale amp2 = (α+1e-8)²·max_j f(u*_j, u*_j) of a kprog case (dot1 has no constant prior variance)."""
+    import kernel_program_cases as cases
+    d, N = D["X"].shape
+    Us = D["Xs"] / (c["lam_rel"] * np.sqrt(d) + 1e-8)
+    return dict(name=f"{c['data']}-{c['closure']}-l{c['lam_rel']:g}-a{c['amp']:g}-s{c['sig']:g}", rows=N,
+                amp2=float((c["amp"] + 1e-8) ** 2 * cases.pairs(kprog_closure(c), Us, Us).max()))
+
+
+def no_grad_at(c):
+    """Candidates left out of a kprog case's dmu / dvar: the exponential kernel has a cusp at candidate 0, which lies on a training
+    point (the device's convention there is pinned by tests/test_gpu_kernel_grad.py)."""
+    return (0,) if c["closure"] == "expo" else ()
+
+
+_fxm = None
+
+
+def load_more():
+    """{"header", model: [cases]}: every case of the first fixture that the second one names, as a copy with the further truths under
+    their keys, and the kprog cases with theirs (read once per process)."""
+    global _fxm
+    if _fxm is None:
+        fx = load()
+        with open(PATH_MORE) as f:
+            raw = json.load(f)
+        flat = np.load(ARRAYS_MORE)
+        out = {"header": raw["header"]}
+        for model in ("plain", "grad", "gibbs"):
+            by_name = {c["name"]: c for c in fx[model]["cases"]}
+            out[model] = []
+            for e in raw[model]:
+                c = dict(by_name[e["case"]])
+                _take(flat, e["at"], more_layout(model, fx[model]["datasets"][c["data"]]), c)
+                out[model].append(c)
+        out["kprog"] = []
+        for c in raw["kprog"]:
+            D = fx["plain"]["datasets"][c["data"]]
+            _take(flat, c["at"], more_layout("kprog", D), c)
+            c.update(kprog_derived(D, c))
+            out["kprog"].append(c)
+        _fxm = out
+    return _fxm
+
+
+def limit_more(fxm, model):
+    """The multipliers of the second fixture's bars per key, from its header."""
+    return dict(BASE_MULT, **fxm["header"]["multiplier"][model])
+
+
+def multiplier_of(key, worst):
+    """The rule by which make_regimes_more.py chooses a multiplier from the fp64 oracle's worst err/(B·scale)."""
+    base = BASE_MULT[key]
+    return base if worst <= base / 8 else int(2 ** np.ceil(np.log2(8 * worst)))
+
+
+def kprog_programs(B):
+    """{(closure name, d): api.KernelProgram traced with gradients} for the kprog cases; B is the imported package (library built)."""
+    import kernel_program_cases as cases
+    return {(n, d): B.DeviceKernel(cases.CLOSURES[n], d, grad=True).program for n in KPROG_CLOSURES for d in (2, 3)}
+
+
+def mp_kernel(prog):
+    """f(u, v) on two lists of mpmath numbers through the 50-digit program interpreter (fitness_mc_cases.mp_eval)."""
+    from fitness_mc_cases import mp_eval
+    return lambda u, v: mp_eval(prog, list(u) + list(v))[0]
+
+
+# ------------------------------------------------------------------------------------------ the fp64 oracle on the further truths
+def _pair_partials(prog, A, Bm):
+    """(∂f/∂u, ∂f/∂v) of the program at every pair (A[:, i], Bm[:, j]): d×p×q each, by KernelProgram.grad."""
+    d, p, q = A.shape[0], A.shape[1], Bm.shape[1]
+    _, dU, dV = prog.grad(np.repeat(A, q, axis=1), np.tile(Bm, (1, p)))
+    return dU.reshape(d, p, q), dV.reshape(d, p, q)
+
+
+def kprog_oracle(prog, c, X, y, Xs, lam, amp, sig, mX, ms):
+    """kernel_program_cases.Restated, and the formulas of kernel_grad_cases.RestatedGrad with the partials of the traced program
+    (KernelProgram.grad) in place of closed forms: logpdf, mu, var (unclipped), dmu, dvar, llgrad; and cond(K)."""
+    import scipy.linalg as sla
+    import kernel_program_cases as cases
+    ref = cases.Restated(kprog_closure(c), X, y, lam, amp, sig, Xs, None, mX, ms)
+    N = X.shape[1]
+    lamp = np.asarray(lam, float) + 1e-8
+    G = np.outer(ref.a, ref.a) - sla.cho_solve((ref.L, True), np.eye(N), check_finite=False)
+    Fu, Fv = _pair_partials(prog, ref.U, ref.U)
+    dK = -ref.a2 * (Fu * ref.U[:, :, None] + Fv * ref.U[:, None, :]) / lamp[:, None, None]
+    F = (ref.K - ref.s2 * np.eye(N)) / ref.a2
+    llgrad = np.concatenate([0.5 * (G[None] * dK).sum((1, 2)), [0.5 * (G * F).sum() * 2.0 * (amp + 1e-8), 0.5 * np.trace(G) * 2.0 * (sig + 1e-8)]])
+    Us = ref.scaled(Xs)
+    W = sla.cho_solve((ref.L, True), ref.a2 * cases.gram(ref.f, ref.U, Us), check_finite=False)
+    _, Fvs = _pair_partials(prog, ref.U, Us)
+    _, su, sv = prog.grad(Us, Us)
+    dmu = ref.a2 * np.einsum("i,dij->dj", ref.a, Fvs) / lamp[:, None]
+    dvar = ref.a2 * ((su + sv) - 2.0 * np.einsum("ij,dij->dj", W, Fvs)) / lamp[:, None]
+    return {"logpdf": ref.logpdf, "mu": ref.mu, "var": ref.var, "dmu": dmu, "dvar": dvar, "llgrad": llgrad}, ref.cond
+
+
+def oracle_more(O, model, fx, c, shift=0.0, progs=None, jacobians=True):
+    """[(got, keep)]: the fp64 oracle's value of every further truth of the case, with the candidates it was evaluated at (None: all;
+    keep_mask where the oracle clips as the device does).  shift: see oracle_outputs.  jacobians=False: the Gibbs gradients with
+    dlam_Xs = damp_Xs = None (the chain through the latent models left out)."""
+    import scipy.linalg as sla
+    if model == "plain":
+        X, y, Xs, lam, amp, sig, mX, ms = plain_inputs(fx, c, shift)
+        keep = keep_mask(c)
+        if not keep.any():
+            return []
+        post = O.gp_fit(X, y, c["kernel"], lam, amp, sig, mean=mX)
+        _, S = O.gp_mean_and_cov(post, Xs[:, keep], None if ms is None else ms[keep])
+        return [({"cov": S}, keep)]
+    if model == "grad":
+        X, y, dY, Xs, lam, amp, sig, gsig = grad_inputs(fx, c, shift)
+        post = O.gradient_gp_fit(X, y, dY, c["kernel"], lam, amp, sig, gsig)
+        _, _, dmu, dvar = O.gradient_gp_mean_and_var_grad(post, Xs)
+        Ks = O.augmented_cross_cov(c["kernel"], X, lam, amp, Xs)
+        V = sla.solve_triangular(post.L, Ks, lower=True, check_finite=False)
+        Kss = (amp + 1e-8) ** 2 * O.kappa(O.KERNEL_NAMES[c["kernel"]], O.scaled_distance(Xs, Xs, lam + 1e-8))
+        return [({"dmu": dmu, "dvar": dvar, "cov": Kss - V.T @ V}, None)]
+    if model == "gibbs":
+        X, y, Xs, lam, amp, noi, lam_s, amp_s = gibbs_inputs(fx, c, shift)
+        dlam_s, damp_s = gibbs_latent_jacobians(Xs, c) if jacobians else (None, None)
+        post = O.nonstationary_fit(X, y, lam, amp, noi)
+        _, _, dmu, dvar = O.nonstationary_mean_and_var_grad(post, Xs, lam_s, amp_s, dlam_s, damp_s)
+        Ks = O.gibbs_kernel_matrix(X, lam, amp, Xs, lam_s, amp_s)
+        V = sla.solve_triangular(post.L, Ks, lower=True, check_finite=False)
+        S = O.gibbs_kernel_matrix(Xs, lam_s, amp_s, Xs, lam_s, amp_s) - V.T @ V + 1e-18 * np.eye(Xs.shape[1])
+        return [({"dmu": dmu, "dvar": dvar, "cov": S}, None)]
+    X, y, Xs, lam, amp, sig, mX, ms = plain_inputs(fx, c, shift)
+    return [(kprog_oracle(progs[(c["closure"], X.shape[0])], c, X, y, Xs, lam, amp, sig, mX, ms)[0], None)]
+
+
+# ------------------------------------------------------------------------------------------ the device on the further truths
+# As DEVICE above: [(what, got, keep)], keep None where a call was given every candidate.  `g`: a handle on the case's dataset
+# (kprog: and closure) to reuse, or None.
+def device_plain_more(api, fx, c, g=None, shift=0.0, progs=None):
+    X, y, Xs, lam, amp, sig, mX, ms = plain_inputs(fx, c, shift)
+    keep = keep_mask(c)
+    h = api.GP(X, y, c["kernel"]) if g is None else g
+    out = []
+    try:
+        h.update(lam, amp, sig, mX)
+        if keep.any():
+            mu, S = h.predict_cov(np.asfortranarray(Xs[:, keep]), None if ms is None else ms[keep])
+            assert np.array_equal(S, S.T), f"{c['name']}: predict_cov is not bitwise symmetric"
+            out.append(("predict_cov", {"mu": mu, "cov": S, "var": np.diag(S).copy()}, keep))
+    finally:
+        if g is None:
+            h.close()
+    return out
+
+
+def device_grad_more(api, fx, c, g=None, shift=0.0, progs=None):
+    X, y, dY, Xs, lam, amp, sig, gsig = grad_inputs(fx, c, shift)
+    keep = keep_mask(c)
+    h = api.GradGP(X, y, dY, c["kernel"]) if g is None else g
+    out = []
+    try:
+        h.update(lam, amp, sig, gsig)
+        if keep.any():
+            mu, var, dmu, dvar = h.predict_grad(np.asfortranarray(Xs[:, keep]))
+            out.append(("predict_grad", {"mu": mu, "var": var, "dmu": dmu, "dvar": dvar}, keep))
+        mu, S = h.predict_value_cov(Xs)
+        out.append(("predict_value_cov", {"mu": mu, "cov": S}, None))
+    finally:
+        if g is None:
+            h.close()
+    return out
+
+
+def device_gibbs_more(api, fx, c, g=None, shift=0.0, progs=None):
+    X, y, Xs, lam, amp, noi, lam_s, amp_s = gibbs_inputs(fx, c, shift)
+    dlam_s, damp_s = gibbs_latent_jacobians(Xs, c)
+    keep = keep_mask(c)
+    h = api.GibbsGP(X, y) if g is None else g
+    out = []
+    try:
+        h.update(lam, amp, noi)
+        if keep.any():
+            Xk, lk, ak = np.asfortranarray(Xs[:, keep]), np.asfortranarray(lam_s[:, keep]), amp_s[keep]
+            mu, var, dmu, dvar = h.predict_grad(Xk, lk, ak, dlam_s[:, :, keep], damp_s[:, keep])
+            out.append(("predict_grad", {"mu": mu, "var": var, "dmu": dmu, "dvar": dvar}, keep))
+            if c["clam"] == 1 and c["camp"] == 1:            # the Jacobians vanish: the call without them is the same derivative
+                mu, var, dmu, dvar = h.predict_grad(Xk, lk, ak)
+                out.append(("predict_grad without Jacobians", {"mu": mu, "var": var, "dmu": dmu, "dvar": dvar}, keep))
+            mu, S = h.predict_cov(Xk, lk, ak)
+            out.append(("predict_cov", {"mu": mu, "cov": S, "var": np.diag(S).copy()}, keep))
+    finally:
+        if g is None:
+            h.close()
+    return out
+
+
+def device_kprog(api, fx, c, g=None, shift=0.0, progs=None):
+    X, y, Xs, lam, amp, sig, mX, ms = plain_inputs(fx, c, shift)
+    keep = keep_mask(c)
+    h = api.KernelGP(X, y, progs[(c["closure"], X.shape[0])], grad=True) if g is None else g
+    try:
+        first = {"logpdf": h.update(lam, amp, sig, mX)}
+        ll, gr = h.loglike_grad()
+        third = {}
+        if keep.any():
+            Xk, mk = np.asfortranarray(Xs[:, keep]), (None if ms is None else ms[keep])
+            first["mu"], first["var"] = h.predict(Xk, mk)
+            third["mu"], third["var"], third["dmu"], third["dvar"] = h.predict_grad(Xk, mk)
+    finally:
+        if g is None:
+            h.close()
+    return [("update/predict", first, keep), ("loglike_grad", {"logpdf": ll, "llgrad": gr}, keep), ("predict_grad", third, keep)]
+
+
+DEVICE_MORE = {"plain": device_plain_more, "grad": device_grad_more, "gibbs": device_gibbs_more, "kprog": device_kprog}
