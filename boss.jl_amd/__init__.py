@@ -14,6 +14,9 @@ from .problem import (BossOptions, BossProblem, Dirac, Domain, ExperimentData, E
                       LinFitness, LogNormal, MvDirac, MvLogNormal, NonlinFitness, Normal)
 from .fitness import DeviceFitness  # noqa: F401,E402
 from .api import FitnessProgram, acq_ei_mc, acq_ei_mc_grad, acq_ei_mc_grad_moments, acq_ei_mc_moments  # noqa: F401,E402
+from .acq_program import (DeviceAcquisition, ProbabilityOfImprovement, UpperConfidenceBound, normcdf, normpdf,  # noqa: F401,E402
+                          trace_acquisition)
+from .api import AcqProgram, acq_prog, acq_prog_grad, acq_prog_grad_moments, acq_prog_moments  # noqa: F401,E402
 from .mean import DeviceMean, trace_mean  # noqa: F401,E402
 from .api import MeanProgram  # noqa: F401,E402
 from .kernel import DeviceKernel, trace_kernel  # noqa: F401,E402

@@ -142,6 +142,17 @@ SIGNATURES = {
                                       _c_dp, C.c_int, C.c_double, _c_ucp, _c_dp, _c_dp]),
     "boss_acq_ei_mc_grad_moments": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _c_dp, _c_dp, _c_dp, _c_dp, C.c_void_p, C.c_int,
                                               _c_dp, _c_dp, C.c_int, C.c_double, _c_ucp, _c_dp, _c_dp]),
+    "boss_acqp_create": (C.c_int, [C.c_int, C.c_int, C.c_int, _c_dp, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p)]),
+    "boss_acqp_free": (None, [C.c_void_p]),
+    "boss_acqp_eval_host": (C.c_int, [C.c_void_p, C.c_int, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
+    "boss_acq_prog": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, _c_dp, C.c_void_p, _c_dp, _c_ucp, C.c_double, _c_dp,
+                                C.POINTER(C.c_long), _c_dp]),
+    "boss_acq_prog_moments": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _c_dp, _c_dp, C.c_void_p, _c_dp, _c_ucp, C.c_double, _c_dp,
+                                        C.POINTER(C.c_long), _c_dp]),
+    "boss_acq_prog_grad": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_int, _c_dp, _c_dp, _c_dp, C.c_void_p, _c_dp, _c_ucp,
+                                     C.c_double, _c_dp, _c_dp]),
+    "boss_acq_prog_grad_moments": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _c_dp, _c_dp, _c_dp, _c_dp, C.c_void_p, _c_dp,
+                                             _c_ucp, C.c_double, _c_dp, _c_dp]),
     "boss_mean_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), _c_dp, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                    C.POINTER(C.c_int), C.POINTER(C.c_void_p)]),
     "boss_mean_free": (None, [C.c_void_p]),
@@ -1751,6 +1762,18 @@ FIT_OPS = ("ADD", "SUB", "MUL", "DIV", "NEG", "ABS", "SQUARE", "SQRT", "EXP", "L
 FIT_OP = {name: i for i, name in enumerate(FIT_OPS)}                 # the BOSS_FIT_* opcodes of bosship.h
 FIT_UNARY = frozenset(range(FIT_OP["NEG"], FIT_OP["TANH"] + 1))
 FIT_MAX_INPUTS, FIT_MAX_CONSTS, FIT_MAX_INSTR = 16, 32, 64
+ACQ_OPS = FIT_OPS + ("NORMCDF", "NORMPDF")                           # acquisition programs alone know the last two (BOSS_ACQ_*)
+ACQ_OP = {name: i for i, name in enumerate(ACQ_OPS)}
+ACQ_MAX_OUTPUTS, ACQ_MAX_SCALARS = 8, 16
+
+
+def _normcdf(z):
+    from scipy.special import erfc
+    return 0.5 * erfc(-z * 0.7071067811865476)
+
+
+def _normpdf(z):
+    return np.exp(-0.5 * z * z) * 0.3989422804014327
 
 
 class FitnessProgram:
@@ -1793,7 +1816,7 @@ class FitnessProgram:
             for op, a, b in self.code:
                 x = vals[a]
                 z = vals[b] if b >= 0 else None
-                name = FIT_OPS[op]
+                name = ACQ_OPS[op]                           # (NORMCDF / NORMPDF: an AcqProgram alone holds them)
                 if name == "ADD": r = x + z
                 elif name == "SUB": r = x - z
                 elif name == "MUL": r = x * z
@@ -1809,6 +1832,8 @@ class FitnessProgram:
                 elif name == "TANH": r = np.tanh(x)
                 elif name == "POW": r = np.power(x, z)
                 elif name == "MIN": r = np.where(np.isnan(x) | np.isnan(z), x + z, np.where(x <= z, x, z))
+                elif name == "NORMCDF": r = _normcdf(x)
+                elif name == "NORMPDF": r = _normpdf(x)
                 else: r = np.where(np.isnan(x) | np.isnan(z), x + z, np.where(x >= z, x, z))
                 vals.append(r)
         return vals
@@ -1833,7 +1858,7 @@ class FitnessProgram:
                 w = adj[P + nc + i]
                 x, r = vals[a], vals[P + nc + i]
                 z = vals[b] if b >= 0 else None
-                name = FIT_OPS[op]
+                name = ACQ_OPS[op]                           # (NORMCDF / NORMPDF: an AcqProgram alone holds them)
                 da, db = None, None
                 if name == "ADD": da, db = np.ones(n), np.ones(n)
                 elif name == "SUB": da, db = np.ones(n), -np.ones(n)
@@ -1852,6 +1877,8 @@ class FitnessProgram:
                     da = z * np.power(x, z - 1.0)
                     db = np.zeros(n) if P <= b < P + nc else r * np.log(x)
                 elif name == "MIN": da, db = (x <= z).astype(float), (~(x <= z)).astype(float)
+                elif name == "NORMCDF": da = _normpdf(x)
+                elif name == "NORMPDF": da = -x * r
                 else: da, db = (x >= z).astype(float), (~(x >= z)).astype(float)
                 adj[a] = adj[a] + np.where(w == 0.0, 0.0, w * da)
                 if db is not None:
@@ -2156,6 +2183,153 @@ def acq_ei_mc_grad_moments(mu, var, dmu, dvar, fit: FitnessProgram, eps, y_max=N
     _check(load_library().boss_acq_ei_mc_grad_moments(device, P, S, M, d, _dp(mu), _dp(var), _dp(gm), _dp(gv), fit._h, eps.shape[1],
                                                       _dp(eps), _dp(ym), 0 if best is None else 1, 0.0 if best is None else float(best),
                                                       _ucp(mask), _dp(acq), _dp(dacq)))
+    return acq, dacq
+
+
+# ---------------------------------------------------------------- acquisition programs: a user-defined acquisition on the device
+class AcqProgram(FitnessProgram):
+    """An acquisition (mu, var, q) -> value as a straight-line program (boss_acqp_t) over 2P + Q inputs: value ids 0..P-1 are the
+    posterior means, P..2P-1 the (clipped) variances, 2P..2P+Q-1 the runtime scalars; then constants and instructions as in a
+    FitnessProgram, with the two extra unary opcodes NORMCDF / NORMPDF (ACQ_OPS).  Creating one needs no device.  eval / grad
+    (inherited) are the numpy interpreters over the stacked inputs [mu; var; q]; eval_host runs the library's interpreter."""
+
+    def __init__(self, y_dim: int, n_params: int, consts, code, out_id: int):
+        self.y_dim, self.n_params = int(y_dim), int(n_params)
+        self.P = 2 * self.y_dim + self.n_params               # (the interpreter's input count)
+        self.consts = np.ascontiguousarray(np.asarray(consts, dtype=np.float64).reshape(-1))
+        self.code = np.ascontiguousarray(np.asarray(code, dtype=np.intc).reshape(-1, 3))
+        self.out_id = int(out_id)
+        self._h = C.c_void_p()
+        _check(load_library().boss_acqp_create(self.y_dim, self.n_params, self.consts.shape[0], _dp(self.consts), self.code.shape[0],
+                                               self.code.ctypes.data_as(C.POINTER(C.c_int)), self.out_id, C.byref(self._h)))
+
+    def scalars(self, q):
+        q = np.zeros(0) if q is None else np.ascontiguousarray(np.asarray(q, dtype=np.float64).reshape(-1))
+        if q.shape[0] != self.n_params:
+            raise ValueError(f"the acquisition program takes {self.n_params} runtime scalars, got {q.shape[0]}")
+        return q
+
+    def stack(self, mu, var, q=None):
+        """[mu; var; q] as the P×n input block of eval / grad (mu, var: y_dim×n or length y_dim)."""
+        mu = np.asarray(mu, dtype=np.float64).reshape(self.y_dim, -1)
+        var = np.asarray(var, dtype=np.float64).reshape(self.y_dim, -1)
+        q = self.scalars(q)
+        return np.vstack([mu, var, np.repeat(q[:, None], mu.shape[1], axis=1)])
+
+    def eval_host(self, mu, var, q=None, want_grad: bool = False):
+        """The raw program (no clip, no mask) through boss_acqp_eval_host at the columns of mu / var (y_dim×n).  Returns a[n], or
+        (a[n], da_dmu[y_dim, n], da_dvar[y_dim, n]) with want_grad."""
+        mu = np.asfortranarray(np.asarray(mu, dtype=np.float64).reshape(self.y_dim, -1))
+        var = np.asfortranarray(np.asarray(var, dtype=np.float64).reshape(self.y_dim, -1))
+        q = self.scalars(q)
+        n = mu.shape[1]
+        a = np.zeros(n)
+        dm = np.zeros((self.y_dim, n), order="F") if want_grad else None
+        dv = np.zeros((self.y_dim, n), order="F") if want_grad else None
+        _check(load_library().boss_acqp_eval_host(self._h, n, _dp(mu), _dp(var), _dp(q) if q.shape[0] else None, _dp(a), _dp(dm), _dp(dv)))
+        return (a, dm, dv) if want_grad else a
+
+    def close(self):
+        if self._h:
+            load_library().boss_acqp_free(self._h)
+            self._h = C.c_void_p()
+
+
+def _handles(gps):
+    S = len(gps)
+    P = len(gps[0]) if S else 0
+    if S < 1 or P < 1 or any(len(row) != P for row in gps):
+        raise BossError(BOSS_E_INVALID, "gps must be S rows of P posteriors")
+    arr = (C.c_void_p * (P * S))()
+    for s in range(S):
+        for p in range(P):
+            arr[p + P * s] = gps[s][p]._h
+    return S, P, arr
+
+
+def _mask_u8(valid_mask):
+    return None if valid_mask is None else np.ascontiguousarray(np.asarray(valid_mask, dtype=bool).astype(np.uint8))
+
+
+def acq_prog(gps: Sequence[Sequence[GP]], cand: Candidates, prog: AcqProgram, q=None, valid_mask=None, outside: float = -np.inf,
+             mean_Xs=None, want_acq: bool = True):
+    """The acquisition program behind the prediction of gps[s][p] at resident candidates (boss_acq_prog): sample mean, mask to
+    `outside`, first-index arg-max.  mean_Xs None or [S][P][M].  Returns (acq[M] or None, argmax, max)."""
+    S, P, arr = _handles(gps)
+    q = prog.scalars(q)
+    M = cand.M
+    ms = None
+    if mean_Xs is not None:
+        ms = np.ascontiguousarray(np.asarray(mean_Xs, dtype=np.float64).reshape(S, P, M).transpose(0, 2, 1))   # index p + P*(j + M*s)
+    mask = _mask_u8(valid_mask)
+    acq = np.zeros(M) if want_acq else None
+    am = C.c_long(-1)
+    mx = C.c_double(0.0)
+    _check(load_library().boss_acq_prog(P, S, arr, cand._h, _dp(ms), prog._h, _dp(q) if q.shape[0] else None, _ucp(mask), float(outside),
+                                        _dp(acq), C.byref(am), C.byref(mx)))
+    return acq, am.value, mx.value
+
+
+def _moments(mu, var):
+    mu = np.asarray(mu, dtype=np.float64)
+    var = np.asarray(var, dtype=np.float64)
+    if mu.ndim == 2:
+        mu, var = mu[None], var[None]
+    if var.shape != mu.shape:
+        raise ValueError("mu and var must have one shape")
+    return np.ascontiguousarray(mu), np.ascontiguousarray(var)
+
+
+def acq_prog_moments(mu, var, prog: AcqProgram, q=None, valid_mask=None, outside: float = -np.inf, device: int = 0):
+    """acq_prog from moments on the host (boss_acq_prog_moments).  mu, var: [S][P][M] (or [P][M])."""
+    mu, var = _moments(mu, var)
+    S, P, M = mu.shape
+    q = prog.scalars(q)
+    mask = _mask_u8(valid_mask)
+    acq = np.zeros(M)
+    am = C.c_long(-1)
+    mx = C.c_double(0.0)
+    _check(load_library().boss_acq_prog_moments(device, P, S, M, _dp(mu), _dp(var), prog._h, _dp(q) if q.shape[0] else None, _ucp(mask),
+                                                float(outside), _dp(acq), C.byref(am), C.byref(mx)))
+    return acq, am.value, mx.value
+
+
+def acq_prog_grad(gps: Sequence[Sequence[GP]], Xs, prog: AcqProgram, q=None, valid_mask=None, outside: float = -np.inf, mean_Xs=None,
+                  mean_grad=None):
+    """Value and gradient w.r.t. the candidates of the acquisition program, averaged over the S samples (boss_acq_prog_grad).
+    gps[s][p]; mean_Xs None or [S][P][M]; mean_grad None or [S][P][d][M].  Returns (acq[M], dacq[d, M])."""
+    S, P, arr = _handles(gps)
+    Xs = _f64(Xs, 2)
+    d, M = Xs.shape
+    q = prog.scalars(q)
+    mask = _mask_u8(valid_mask)
+    ms = None if mean_Xs is None else np.ascontiguousarray(np.asarray(mean_Xs, dtype=np.float64).reshape(S, P, M))
+    mg = None
+    if mean_grad is not None:
+        mg = np.ascontiguousarray(np.asarray(mean_grad, dtype=np.float64).reshape(S, P, d, M).transpose(0, 1, 3, 2))   # [s][p][j*d + m]
+    acq = np.zeros(M)
+    dacq = np.zeros((d, M), order="F")
+    _check(load_library().boss_acq_prog_grad(P, S, arr, M, _dp(Xs), _dp(ms), _dp(mg), prog._h, _dp(q) if q.shape[0] else None, _ucp(mask),
+                                             float(outside), _dp(acq), _dp(dacq)))
+    return acq, dacq
+
+
+def acq_prog_grad_moments(mu, var, dmu, dvar, prog: AcqProgram, q=None, valid_mask=None, outside: float = -np.inf, device: int = 0):
+    """acq_prog_grad from moments and moment gradients on the host (boss_acq_prog_grad_moments): mu / var [S][P][M] (or [P][M]),
+    dmu / dvar [S][P][d][M].  Returns (acq[M], dacq[d, M])."""
+    mu, var = _moments(mu, var)
+    S, P, M = mu.shape
+    gm = np.asarray(dmu, dtype=np.float64).reshape(S, P, -1, M)
+    gv = np.asarray(dvar, dtype=np.float64).reshape(S, P, -1, M)
+    d = gm.shape[2]
+    gm = np.ascontiguousarray(gm.transpose(0, 1, 3, 2))           # [s][p][j*d + m]
+    gv = np.ascontiguousarray(gv.transpose(0, 1, 3, 2))
+    q = prog.scalars(q)
+    mask = _mask_u8(valid_mask)
+    acq = np.zeros(M)
+    dacq = np.zeros((d, M), order="F")
+    _check(load_library().boss_acq_prog_grad_moments(device, P, S, M, d, _dp(mu), _dp(var), _dp(gm), _dp(gv), prog._h,
+                                                     _dp(q) if q.shape[0] else None, _ucp(mask), float(outside), _dp(acq), _dp(dacq)))
     return acq, dacq
 
 

@@ -96,7 +96,8 @@ __device__ __forceinline__ bool better(double a, long ia, double b, long ib) {
 
 // Fused epilogue of one acquisition batch (one 1024-thread workgroup):
 //   acq[j] = (acq_sum[j] (previous samples, if any) + acq_S(x_j)) / S, masked to 0 outside the domain
-//   (make_safe, expected_improvement.jl:58-65), written back to acq_sum, and its first-index
+//   (make_safe, expected_improvement.jl:58-65; `masked`: an acquisition program's value outside the domain instead of 0,
+//   construct_safe_acquisition, src/acquisition.jl:21-25), written back to acq_sum, and its first-index
 //   arg-max, written straight into host-pinned memory (res[0] = value, res[1] = index as int64).
 constexpr int ACQ_EPI_THREADS = 1024;
 __global__ __launch_bounds__(ACQ_EPI_THREADS) void acq_epilogue_kernel(const double* __restrict__ mu,
@@ -106,7 +107,8 @@ __global__ __launch_bounds__(ACQ_EPI_THREADS) void acq_epilogue_kernel(const dou
                                                                        double* __restrict__ acq_sum, int have_prev,
                                                                        double inv_s, const unsigned char* __restrict__ mask,
                                                                        double* __restrict__ res, unsigned long long res_seq,
-                                                                       double* __restrict__ dpair = nullptr, long idx_off = 0) {
+                                                                       double* __restrict__ dpair = nullptr, long idx_off = 0,
+                                                                       double masked = 0.0) {
     __shared__ double sv[ACQ_EPI_THREADS];
     __shared__ long si[ACQ_EPI_THREADS];
     constexpr long NONE = 0x7fffffffffffffffL;
@@ -114,9 +116,9 @@ __global__ __launch_bounds__(ACQ_EPI_THREADS) void acq_epilogue_kernel(const dou
     long bi = NONE;
     for (int j = threadIdx.x; j < M; j += ACQ_EPI_THREADS) {
         double a = ei_value(mu, var, ldm, j, par, coefs_dev, ymax_dev);
-        if (have_prev) a += acq_sum[j];
+        if (have_prev) a = have_prev == 2 ? acq_sum[j] : a + acq_sum[j];   // (2: the sum is the value itself — an acquisition program's, -0.0 kept)
         a *= inv_s;
-        if (mask && !mask[j]) a = 0.0;
+        if (mask && !mask[j]) a = masked;
         acq_sum[j] = a;
         if (bi == NONE || better(a, j, bv, bi)) { bv = a; bi = j; }
     }

@@ -27,6 +27,7 @@
 #include "latent_kernels.hpp"
 #include "nfit_kernels.hpp"
 #include "fitness.hpp"
+#include "acqprog_kernels.hpp"
 #include "mean_program.hpp"
 #include "warp_kernels.hpp"
 #include "prune_kernels.hpp"
@@ -400,6 +401,7 @@ static int ctx_init(Ctx* c) {
     HIPCHK(hipFuncSetAttribute((const void*)predict_kernel<PredG64, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                PredictLds<PredG64>::BYTES));
     HIPCHK(hipFuncSetAttribute((const void*)ei_mc_grad_set_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, MC_GRAD_MAX_LDS));
+    HIPCHK(hipFuncSetAttribute((const void*)acqp_grad_set_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, ACQP_GRAD_MAX_LDS));
     HIPCHK(hipFuncSetAttribute((const void*)mean_eval_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, MEAN_MAX_LDS));
     HIPCHK(hipFuncSetAttribute((const void*)kprog_llgrad_tile_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, KPROG_GRAD_MAX_LDS));
     HIPCHK(hipFuncSetAttribute((const void*)kprog_grad_accum_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, KPROG_GRAD_MAX_LDS));
@@ -708,10 +710,21 @@ static void mc_accumulate_launch(hipStream_t s, const double* mu, const double* 
                                  const EiPar& par, const McEpi& mc, const double* deps, double* acq_sum, int add);
 static void mc_grad_launch(hipStream_t s, const double* mu, const double* var, const double* dmu, const double* dvar, int M, int d, int S,
                            const EiPar& par, const McEpi& mc, const double* deps, const unsigned char* mask, double* acq, double* dacq);
+// An acquisition program (host_acqprog.inc) in the place of the EI epilogues: its runtime scalars and the value of masked candidates
+struct AcqpEpi {
+    const FitProg* g;
+    AcqpPar ap;
+    double outside;
+};
+static void acqp_accumulate_launch(hipStream_t s, const double* mu, const double* var, size_t sstride, int ldm, int M, int s0, int s1,
+                                   const AcqpEpi& pg, double* acq_sum, int add);
+static void acqp_grad_launch(hipStream_t s, const double* mu, const double* var, const double* dmu, const double* dvar, int M, int d, int S,
+                             const AcqpEpi& pg, const unsigned char* mask, double* acq, double* dacq);
 #include "host_predict.inc"
 #include "host_prune.inc"
 #include "host_acq.inc"
 #include "host_fitness.inc"
+#include "host_acqprog.inc"
 #include "host_kprog.inc"
 #include "host_mean.inc"
 #include "host_warp.inc"

@@ -14,9 +14,15 @@ namespace boss {
 constexpr int FIT_MAXC = 32, FIT_MAXI = 64, FIT_NOARG = 255;
 enum FitOp : int {
     FIT_ADD = 0, FIT_SUB, FIT_MUL, FIT_DIV, FIT_NEG, FIT_ABS, FIT_SQUARE, FIT_SQRT, FIT_EXP, FIT_LOG, FIT_SIN, FIT_COS, FIT_TANH,
-    FIT_POW, FIT_MIN, FIT_MAX, FIT_NOPS
+    FIT_POW, FIT_MIN, FIT_MAX, FIT_NOPS,
+    // acquisition programs only (boss_acqp_create; every other program keeps FIT_NOPS opcodes): Φ and φ of the standard normal
+    FIT_NORMCDF = FIT_NOPS, FIT_NORMPDF, ACQ_NOPS
 };
-__host__ __device__ inline bool fit_is_unary(int op) { return op >= FIT_NEG && op <= FIT_TANH; }
+__host__ __device__ inline bool fit_is_unary(int op) { return (op >= FIT_NEG && op <= FIT_TANH) || op == FIT_NORMCDF || op == FIT_NORMPDF; }
+
+// normcdf_dev / normpdf_dev (common.hpp) for host and device: the host interpreter computes the same expressions
+__host__ __device__ inline double fit_normcdf(double z) { return 0.5 * erfc(-z * 0.7071067811865476); }
+__host__ __device__ inline double fit_normpdf(double z) { return exp(-0.5 * z * z) * 0.3989422804014327; }
 
 struct FitProg {
     int P, nC, nI, out;
@@ -35,11 +41,17 @@ __host__ __device__ inline double fit_get(const FitProg& g, const double* y, con
 
 // Forward pass: y[P] inputs (read), v[nI] instruction results (written).  Returns the program's value.
 // MIN / MAX give NaN when either operand is NaN (Julia's min / max); everything else is what IEEE arithmetic and libm give.
+// ACQ: the program may hold NORMCDF / NORMPDF (acquisition programs); the other interpreters are compiled without the two cases.
+template <bool ACQ = false>
 __host__ __device__ inline double fit_eval(const FitProg& g, const double* y, double* v, int st) {
     for (int i = 0; i < g.nI; ++i) {
         const double x = fit_get(g, y, v, st, g.a[i]);
         const double z = g.b[i] == FIT_NOARG ? 0.0 : fit_get(g, y, v, st, g.b[i]);
         double r;
+        if (ACQ && g.op[i] >= FIT_NORMCDF) {
+            v[(size_t)i * st] = g.op[i] == FIT_NORMCDF ? fit_normcdf(x) : fit_normpdf(x);
+            continue;
+        }
         switch (g.op[i]) {
             case FIT_ADD: r = x + z; break;
             case FIT_SUB: r = x - z; break;
@@ -75,7 +87,8 @@ __host__ __device__ inline void fit_adj_add(const FitProg& g, double* ay, double
     if (id < g.P) ay[(size_t)id * st] += w;
     else if (id >= g.P + g.nC) av[(size_t)(id - g.P - g.nC) * st] += w;
 }
-template <bool KZERO>
+// ACQ as in fit_eval: NORMCDF' = φ, NORMPDF'(z) = −z φ(z).
+template <bool KZERO, bool ACQ = false>
 __host__ __device__ inline void fit_grad_sweep(const FitProg& g, const double* y, const double* v, double* ay, double* av, int st) {
     for (int p = 0; p < g.P; ++p) ay[(size_t)p * st] = 0.0;
     for (int i = 0; i < g.nI; ++i) av[(size_t)i * st] = 0.0;
@@ -88,6 +101,11 @@ __host__ __device__ inline void fit_grad_sweep(const FitProg& g, const double* y
         const double z = ib == FIT_NOARG ? 0.0 : fit_get(g, y, v, st, ib);
         const double r = v[(size_t)i * st];
         double da = 0.0, db = 0.0;
+        if (ACQ && g.op[i] >= FIT_NORMCDF) {
+            da = g.op[i] == FIT_NORMCDF ? fit_normpdf(x) : -x * r;
+            fit_adj_add(g, ay, av, st, ia, w * da);
+            continue;
+        }
         switch (g.op[i]) {
             case FIT_ADD: da = 1.0; db = 1.0; break;
             case FIT_SUB: da = 1.0; db = -1.0; break;

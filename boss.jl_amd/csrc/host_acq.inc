@@ -11,9 +11,11 @@
 static int acq_ei_impl(int P, int S, boss_gp_t* const* gps, const boss_cand_t* cand, const double* mean_Xs,
                        const double* fit_coefs, const double* y_max, int has_best, double best,
                        const unsigned char* valid_mask, double* acq_out, long* argmax_out, double* max_out,
-                       double* dpair, long idx_off, bool defer, const McEpi* mc = nullptr) {
+                       double* dpair, long idx_off, bool defer, const McEpi* mc = nullptr, const AcqpEpi* pg = nullptr) {
     // mc: the EI term is the Monte-Carlo mean of a fitness program (boss_acq_ei_mc, host_fitness.inc) — fit_coefs is not read, P <= EI_MAXP
-    if (P < 1 || S < 1 || !gps || !cand || (!fit_coefs && !mc)) return fail(BOSS_E_INVALID, "bad arguments");
+    // pg: an acquisition program over the moments in the place of EI (boss_acq_prog, host_acqprog.inc) — the caller passes has_best = 1
+    //     (mode != 0: the predictions run), fit_coefs / y_max / best are not read, P <= ACQP_MAXP, every handle kind of the EI call
+    if (P < 1 || S < 1 || !gps || !cand || (!fit_coefs && !mc && !pg)) return fail(BOSS_E_INVALID, "bad arguments");
     Ctx* c = cand->ctx;
     HIPCHK(hipSetDevice(c->device));
     for (int i = 0; i < P * S; ++i) {
@@ -45,7 +47,7 @@ static int acq_ei_impl(int P, int S, boss_gp_t* const* gps, const boss_cand_t* c
     double* hres = (double*)c->pinned + (defer ? MULTI_RES_OFF : 0);
     EiPar par;
     const double no_coefs[EI_MAXP] = {};
-    int rc = ei_params(c, s, P, mc ? no_coefs : fit_coefs, y_max, has_best, best, &par, dcoef, dymax);
+    int rc = ei_params(c, s, P, (mc || pg) ? no_coefs : fit_coefs, y_max, has_best, best, &par, dcoef, dymax);
     if (rc) return rc;
     const double* deps = nullptr;
     if (mc) {
@@ -58,7 +60,7 @@ static int acq_ei_impl(int P, int S, boss_gp_t* const* gps, const boss_cand_t* c
     if (!acq_out && !defer) {
         // arg-max only: bound every candidate, finish the contenders (host_prune.inc); anything it declines runs the full kernel below
         for (int i = 0; i < 5; ++i) c->prune_last[i] = 0;
-        if (prune_eligible(gps[0], cand, P, S, par, acq_out != nullptr, defer, mc != nullptr, dpair)) {
+        if (prune_eligible(gps[0], cand, P, S, par, acq_out != nullptr, defer, mc != nullptr || pg != nullptr, dpair)) {
             if (mean_Xs) (void)hipMemcpyAsync(dmean, mean_Xs, sizeof(double) * M, hipMemcpyHostToDevice, s);   // (P = S = 1: the caller's layout is [j])
             bool done = false;
             double pmax = 0.0;
@@ -99,7 +101,7 @@ static int acq_ei_impl(int P, int S, boss_gp_t* const* gps, const boss_cand_t* c
             return rc;
         }
         ei_value_epilogue_launch(s, mu_all, var_all, M, S, par, dcoef, dymax, valid_mask ? dmask : nullptr, mc, deps, dacq, hres,
-                                 (acq_out || defer) ? 0ull : ++c->acq_seq, dpair, idx_off);
+                                 (acq_out || defer) ? 0ull : ++c->acq_seq, dpair, idx_off, pg);
     } else
     for (int sm = 0; sm < S; ++sm) {
         if (par.mode != 0) {
@@ -121,7 +123,13 @@ static int acq_ei_impl(int P, int S, boss_gp_t* const* gps, const boss_cand_t* c
             }
         }
         ProfScope ps(c, sm + 1 < S ? "ei" : "argmax");
-        if (mc) {
+        if (pg) {
+            // this sample's program value into the sums; behind the last one the mean, the mask (to pg->outside) and the arg-max
+            acqp_accumulate_launch(s, dmu, dvar, 0, M, M, 0, 1, *pg, dacq, sm > 0 ? 1 : 0);
+            if (sm + 1 == S)
+                hipLaunchKernelGGL(acq_epilogue_kernel, dim3(1), dim3(ACQ_EPI_THREADS), 0, s, dmu, dvar, M, M, par0, dcoef, dymax, dacq, 2, 1.0 / S,
+                                   valid_mask ? dmask : nullptr, hres, (acq_out || defer) ? 0ull : ++c->acq_seq, dpair, idx_off, pg->outside);
+        } else if (mc) {
             // this sample's Monte-Carlo term (BI: its own ε column) into the sums; behind the last one the mean, the mask and the arg-max
             mc_accumulate_launch(s, dmu, dvar, 0, M, M, 0, 1, S, par, *mc, S > 1 ? deps + (size_t)sm * P : deps, dacq, sm > 0 ? 1 : 0);
             if (sm + 1 == S)

@@ -9,8 +9,9 @@ struct boss_fit {
 // ------------------------------------------------------------------------------------------
 // The checks of a program over n_in inputs, shared with boss_mean_create (host_mean.inc): `pre` is put in front of every message
 // (a mean program names its output there), `what` names the kind of program.
+// n_ops: how many opcodes the caller's kind of program knows (FIT_NOPS; ACQ_NOPS for acquisition programs, host_acqprog.inc).
 static int fit_build(int n_in, int n_const, const double* consts, int n_instr, const int* code, int out_id, const std::string& pre,
-                     const char* what, FitProg* out) {
+                     const char* what, int n_ops, FitProg* out) {
     if (n_const < 0 || n_const > FIT_MAXC) return fail(BOSS_E_INVALID, pre + "a " + what + " program holds at most 32 constants");
     if (n_instr < 0 || n_instr > FIT_MAXI) return fail(BOSS_E_INVALID, pre + "a " + what + " program holds at most 64 instructions");
     if ((n_const > 0 && !consts) || (n_instr > 0 && !code)) return fail(BOSS_E_INVALID, pre + "NULL constants or code");
@@ -27,7 +28,7 @@ static int fit_build(int n_in, int n_const, const double* consts, int n_instr, c
     for (int i = 0; i < n_instr; ++i) {
         const int op = code[3 * i], a = code[3 * i + 1], b = code[3 * i + 2];
         const std::string at = pre + "instruction " + std::to_string(i) + ": ";
-        if (op < 0 || op >= FIT_NOPS) return fail(BOSS_E_INVALID, at + "unknown opcode " + std::to_string(op));
+        if (op < 0 || op >= n_ops) return fail(BOSS_E_INVALID, at + "unknown opcode " + std::to_string(op));
         if (a < 0 || a >= base + i) return fail(BOSS_E_INVALID, at + "operand a must be an earlier value id");
         if (fit_is_unary(op)) {
             if (b != -1) return fail(BOSS_E_INVALID, at + "a unary operation takes b = -1");
@@ -49,7 +50,7 @@ extern "C" int boss_fit_create(int P, int n_const, const double* consts, int n_i
     *out = nullptr;
     if (P < 1 || P > EI_MAXP) return fail(BOSS_E_INVALID, "a fitness program takes 1 to 16 inputs");
     FitProg g;
-    int rc = fit_build(P, n_const, consts, n_instr, code, out_id, "", "fitness", &g);
+    int rc = fit_build(P, n_const, consts, n_instr, code, out_id, "", "fitness", FIT_NOPS, &g);
     if (rc) return rc;
     boss_fit* f = new boss_fit();
     f->g = g;

@@ -15,7 +15,7 @@ extern "C" int boss_kern_create(int d, int n_const, const double* consts, int n_
     *out = nullptr;
     if (d < 1 || d > KPROG_MAX_D) return fail(BOSS_E_INVALID, "a kernel program takes two points of 1 to 16 dimensions");
     FitProg g;
-    int rc = fit_build(2 * d, n_const, consts, n_instr, code, out_id, "", "kernel", &g);
+    int rc = fit_build(2 * d, n_const, consts, n_instr, code, out_id, "", "kernel", FIT_NOPS, &g);
     if (rc) return rc;
     boss_kern* k = new boss_kern();
     k->g = g;

@@ -23,7 +23,7 @@ extern "C" int boss_mean_create(int d, int T, int P, const int* n_const, const d
     const double* c = consts;
     const int* k = code;
     for (int p = 0; p < P; ++p) {
-        int rc = fit_build(d + T, n_const[p], c, n_instr[p], k, out_ids[p], "output " + std::to_string(p) + ": ", "mean", &mp->g[p]);
+        int rc = fit_build(d + T, n_const[p], c, n_instr[p], k, out_ids[p], "output " + std::to_string(p) + ": ", "mean", FIT_NOPS, &mp->g[p]);
         if (rc) {
             delete mp;
             return rc;

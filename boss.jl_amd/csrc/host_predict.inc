@@ -883,8 +883,10 @@ static int ei_params(Ctx* c, hipStream_t s, int P, const double* fit_coefs, cons
 // so, because ei_grad_set_kernel with S = 1 adds the sample to 0.0 and is not the same bits (0.0 + (−0.0)).
 static void ei_grad_epilogue_launch(hipStream_t s, const double* mu, const double* var, const double* gm, const double* gv, int M, int d, int S,
                                     bool single, const EiPar& par, const double* coef, const double* ymax, const unsigned char* mask,
-                                    const McEpi* mc, const double* deps, double* acq, double* dacq) {
-    if (mc)
+                                    const McEpi* mc, const double* deps, double* acq, double* dacq, const AcqpEpi* pg = nullptr) {
+    if (pg)                                                  // an acquisition program: value and chain rule of all S samples in its own kernel
+        acqp_grad_launch(s, mu, var, gm, gv, M, d, S, *pg, mask, acq, dacq);
+    else if (mc)
         mc_grad_launch(s, mu, var, gm, gv, M, d, S, par, *mc, deps, mask, acq, dacq);
     else if (single)
         hipLaunchKernelGGL(ei_grad_kernel, dim3((M + 127) / 128), dim3(128), 0, s, mu, var, gm, gv, M, d, par, coef, ymax, mask, acq, dacq);
@@ -893,13 +895,18 @@ static void ei_grad_epilogue_launch(hipStream_t s, const double* mu, const doubl
 }
 // Value, mask and arg-max from mu / var [s][p][M]: samples 0 … S−2 summed into acq in sample order, the last one with the mean,
 // the mask and the arg-max (into hres; res_seq, dpair, idx_off: acq_epilogue_kernel's).  mc: the Monte-Carlo sums of all S samples,
-// then the epilogue in mode 0 (it adds 0.0 to them).
+// then the epilogue in mode 0 (it adds 0.0 to them).  pg: the sums of an acquisition program, taken as they are (have_prev = 2) and
+// masked to pg->outside.
 static void ei_value_epilogue_launch(hipStream_t s, const double* mu, const double* var, int M, int S, const EiPar& par, const double* coef,
                                      const double* ymax, const unsigned char* mask, const McEpi* mc, const double* deps, double* acq,
-                                     double* hres, unsigned long long res_seq, double* dpair = nullptr, long idx_off = 0) {
+                                     double* hres, unsigned long long res_seq, double* dpair = nullptr, long idx_off = 0,
+                                     const AcqpEpi* pg = nullptr) {
     const size_t pm = (size_t)par.P * M;
     EiPar last = par;
-    if (mc) {
+    if (pg) {
+        acqp_accumulate_launch(s, mu, var, pm, M, M, 0, S, *pg, acq, 0);
+        last.mode = 0;
+    } else if (mc) {
         mc_accumulate_launch(s, mu, var, pm, M, M, 0, S, S, par, *mc, deps, acq, 0);
         last.mode = 0;
     } else if (S > 1) {
@@ -907,7 +914,7 @@ static void ei_value_epilogue_launch(hipStream_t s, const double* mu, const doub
         hipLaunchKernelGGL(ei_accumulate_set_kernel, dim3((M + 255) / 256), dim3(256), 0, s, mu, var, pm, M, M, 0, S - 1, par, coef, ymax, acq);
     }
     hipLaunchKernelGGL(acq_epilogue_kernel, dim3(1), dim3(ACQ_EPI_THREADS), 0, s, mu + pm * (S - 1), var + pm * (S - 1), M, M, last, coef, ymax,
-                       acq, mc || S > 1 ? 1 : 0, 1.0 / S, mask, hres, res_seq, dpair, idx_off);
+                       acq, pg ? 2 : (mc || S > 1 ? 1 : 0), 1.0 / S, mask, hres, res_seq, dpair, idx_off, pg ? pg->outside : 0.0);
 }
 
 // SURVEY §8f3.  Enqueue μ, σ² (unclipped) and ∇μ, ∇σ² of one posterior at resident candidates:
@@ -1365,11 +1372,13 @@ static int members_enqueue(int n, boss_gp_t* const* gps, const boss_cand* cd, co
 // Equally shaped members take the set launches, any other list goes member by member into the same slices (members_enqueue).
 // S = 1 (boss_acq_ei_grad, one hyper-parameter sample): always member by member, and ei_grad_kernel.
 // mc: the EI term and its gradient are those of a fitness program's Monte-Carlo mean (boss_acq_ei_mc_grad, host_fitness.inc); fit_coefs
-// is not read, P <= EI_MAXP, and S = 1 may take the set launches too.
+// is not read, P <= EI_MAXP, and S = 1 may take the set launches too.  pg: an acquisition program's value and gradient instead
+// (boss_acq_prog_grad, host_acqprog.inc); neither fit_coefs nor y_max / best is read, program-kernel handles are taken as for EI.
 static int acq_ei_grad_set_impl(int P, int S, boss_gp_t* const* gps, int M, const double* Xs, const double* mean_Xs,
                                 const double* mean_grad, const double* fit_coefs, const double* y_max, int has_best,
-                                double best, const unsigned char* valid_mask, double* acq_out, double* dacq_out, const McEpi* mc) {
-    if (P < 1 || S < 1 || !gps || M < 1 || !Xs || (!fit_coefs && !mc) || !acq_out || !dacq_out) return fail(BOSS_E_INVALID, "bad arguments");
+                                double best, const unsigned char* valid_mask, double* acq_out, double* dacq_out, const McEpi* mc,
+                                const AcqpEpi* pg = nullptr) {
+    if (P < 1 || S < 1 || !gps || M < 1 || !Xs || (!fit_coefs && !mc && !pg) || !acq_out || !dacq_out) return fail(BOSS_E_INVALID, "bad arguments");
     if ((long long)P * S * M > (1LL << 30)) return fail(BOSS_E_INVALID, "P·S·M above 2^30 is not supported");
     const int n = P * S;
     for (int i = 0; i < n; ++i) {
@@ -1408,7 +1417,7 @@ static int acq_ei_grad_set_impl(int P, int S, boss_gp_t* const* gps, int M, cons
     unsigned char* dmask = (unsigned char*)(dacq + nd);
     EiPar par;
     const double no_coefs[EI_MAXP] = {};
-    rc = ei_params(c, s, P, mc ? no_coefs : fit_coefs, y_max, has_best, best, &par, dcoef, dymax);
+    rc = ei_params(c, s, P, (mc || pg) ? no_coefs : fit_coefs, y_max, has_best, best, &par, dcoef, dymax);
     if (rc) return drain(c, rc);
     const double* deps = nullptr;
     if (mc) {
@@ -1426,7 +1435,7 @@ static int acq_ei_grad_set_impl(int P, int S, boss_gp_t* const* gps, int M, cons
         rc = members_enqueue(n, gps, &cd, q, mc || S > 1);
         if (rc) return drain(c, rc);
     }
-    ei_grad_epilogue_launch(s, dmu, dvar, dgm, dgv, M, d, S, S == 1 && !mc, par, dcoef, dymax, valid_mask ? dmask : nullptr, mc, deps, dacq, ddacq);
+    ei_grad_epilogue_launch(s, dmu, dvar, dgm, dgv, M, d, S, S == 1 && !mc, par, dcoef, dymax, valid_mask ? dmask : nullptr, mc, deps, dacq, ddacq, pg);
     return finish(c, {{acq_out, dacq, sizeof(double) * M}, {dacq_out, ddacq, sizeof(double) * dm}});
 }
 

@@ -236,10 +236,15 @@ def _binary(op, a, b):
 
 
 def _apply_ufunc(ufunc, method, inputs, kwargs):
-    if method != "__call__" or kwargs or ufunc not in _UFUNC_OPS:
+    ops = _UFUNC_OPS
+    extra = next((getattr(x.tr if isinstance(x, _Sym) else x.items[0].tr, "extra_ufuncs", None) for x in inputs
+                  if isinstance(x, _Sym) or (isinstance(x, _SymVec) and x.items)), None)
+    if extra:                                                # (the tracer of a DeviceAcquisition also knows scipy.special.ndtr, acq_program.py)
+        ops = {**_UFUNC_OPS, **extra}
+    if method != "__call__" or kwargs or ufunc not in ops:
         raise ValueError(f"{_label_of(*inputs)}: np.{ufunc.__name__}{'' if method == '__call__' else '.' + method} is not supported in a "
-                         f"device {_noun_of(*inputs)} (supported: {', '.join(sorted(u.__name__ for u in _UFUNC_OPS))})")
-    op = _UFUNC_OPS[ufunc]
+                         f"device {_noun_of(*inputs)} (supported: {', '.join(sorted(u.__name__ for u in ops))})")
+    op = ops[ufunc]
     if len(inputs) == 2:
         return _binary(op, inputs[0], inputs[1])
     x = inputs[0]

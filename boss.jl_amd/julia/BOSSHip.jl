@@ -1384,4 +1384,11 @@ end
 # not bound: boss_kgp_fit_batch — S kernel-program posteriors out of one batched factorisation; needs boss_kern_create
 # not bound: boss_acq_ei_warp — acquisition of a warped model in one call; needs boss_warp_create
 # not bound: boss_acq_ei_grad_warp — acquisition gradient of a warped model in one call; needs boss_warp_create
+# not bound: boss_acqp_create — acquisition programs: the acquisition closure is traced by the Python DeviceAcquisition only; a custom Julia AcquisitionFunction keeps the reference's host path
+# not bound: boss_acqp_free — see boss_acqp_create
+# not bound: boss_acqp_eval_host — see boss_acqp_create (the host run of the kernels' interpreter, used by tests)
+# not bound: boss_acq_prog — acquisition of a traced acquisition program in one call; needs boss_acqp_create
+# not bound: boss_acq_prog_moments — a traced acquisition program on host moments; needs boss_acqp_create
+# not bound: boss_acq_prog_grad — value and gradient of a traced acquisition program; needs boss_acqp_create
+# not bound: boss_acq_prog_grad_moments — value and gradient of a traced acquisition program from host moments; needs boss_acqp_create
 end # module

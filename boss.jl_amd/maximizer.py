@@ -25,6 +25,7 @@ import numpy as np
 from . import acquisition as acq_host
 from . import api
 from . import distributed as dist_util
+from .acq_program import DeviceAcquisition
 from .fitness import DeviceFitness
 from .kernel import device_kernel_of, refuse_device_kernel
 from .mean import device_mean_of
@@ -47,6 +48,26 @@ def _no_warp(problem: BossProblem, what: str):
         raise NotImplementedError(f"{what} is not supported for a HipTransformedModel (use shard='candidates' on a single device)")
 
 
+def _program_acquisition(problem: BossProblem, what: str = "") -> bool:
+    """Whether the problem's acquisition is a DeviceAcquisition (asked before anything reads `.fitness`); `what`: a mode that does
+    not take one."""
+    if not isinstance(getattr(problem, "acquisition", None), DeviceAcquisition):
+        return False
+    if what:
+        raise NotImplementedError(f"{what} is not supported for a DeviceAcquisition (the traced acquisition program runs on a single "
+                                  "device: use shard='candidates', 'outputs' or 'samples' without devices=[...])")
+    if isinstance(problem.model, HipTransformedModel):
+        raise NotImplementedError("a DeviceAcquisition is not supported for a HipTransformedModel (the program's moments would be "
+                                  "model-space moments)")
+    return True
+
+
+def _program_mask(problem: BossProblem, Xs):
+    if not problem.acquisition.cons_safe:
+        return None
+    return in_bounds(Xs, problem.domain.bounds) & in_cons(Xs, problem.domain.cons)
+
+
 def _rand_in_domain(x_prior: Callable, domain, rng, max_attempts: int):
     """_rand_in_domain / _rand_in_discrete (sampling.jl:59-75)."""
     for _ in range(max_attempts):
@@ -62,7 +83,7 @@ def posteriors_of(problem: BossProblem, lo: Optional[int] = None, hi: Optional[i
     [lo, hi) restricts the construction to a shard of the samples; reserve: room for later appends."""
     params = problem.params
     if lo is not None:
-        params = list(params)[lo:hi]
+        params = (list(params) if isinstance(params, (list, tuple)) else [params])[lo:hi]   # (a MAP fit is one sample)
         if not params:
             return []
     post = problem.model.model_posterior(params, problem.data, reserve) if reserve else \
@@ -86,9 +107,13 @@ def output_moments(problem: BossProblem, i: int, Xs: np.ndarray) -> np.ndarray:
     return out
 
 
-def moments_acquisition(problem: BossProblem, mu: np.ndarray, var: np.ndarray, Xs: np.ndarray):
-    """EI x feasibility + arg-max on the device from gathered moments mu/var [S][P][M]."""
+def moments_acquisition(problem: BossProblem, mu: np.ndarray, var: np.ndarray, Xs: np.ndarray, q=None):
+    """EI x feasibility + arg-max on the device from gathered moments mu/var [S][P][M].  q: a DeviceAcquisition's runtime scalars of
+    this maximisation (default: asked for here)."""
     ei = problem.acquisition
+    if _program_acquisition(problem):
+        q = ei.scalars(problem) if q is None else q
+        return api.acq_prog_moments(mu, var, ei.program, q, _program_mask(problem, Xs), ei.outside, problem.model.device)
     b = best_so_far(ei.fitness, problem.data.Y, problem.y_max)
     mask = None
     if ei.cons_safe:
@@ -117,11 +142,13 @@ def _mc_eps(problem: BossProblem, n_posts: int, eps_seed) -> np.ndarray:
 
 
 def acquisition_values(problem: BossProblem, posts: Sequence[HipGaussianProcessPosterior], Xs: np.ndarray,
-                       cand: Optional[api.Candidates] = None, eps_seed: Optional[int] = 0):
+                       cand: Optional[api.Candidates] = None, eps_seed: Optional[int] = 0, q=None):
     """vals = acq.(eachcol(xs)) for acq = construct_safe_acquisition(problem) — device-evaluated.
-    Returns (acq[M], local argmax, local max)."""
+    Returns (acq[M], local argmax, local max).  q: a DeviceAcquisition's runtime scalars of this maximisation (default: asked for here)."""
     ei = problem.acquisition
     Xs = np.asfortranarray(Xs, dtype=np.float64)
+    if _program_acquisition(problem):
+        return _program_values(problem, posts, Xs, cand, ei.scalars(problem) if q is None else q)
     posts, warped = _unwarped(posts)
     if warped:                                               # user-space candidates: the warp runs inside the call
         if cand is not None:
@@ -182,6 +209,31 @@ def acquisition_values(problem: BossProblem, posts: Sequence[HipGaussianProcessP
     return acq, am, mx
 
 
+def _program_values(problem: BossProblem, posts, Xs: np.ndarray, cand, q):
+    """acquisition_values for a DeviceAcquisition: the traced program behind the prediction in one device call (boss_acq_prog) for
+    posteriors of the plain and the gradient-observation model, built-in kernel or DeviceKernel; from the slices' moments
+    (boss_acq_prog_moments) for nonstationary posteriors."""
+    acq = problem.acquisition
+    mask = _program_mask(problem, Xs)
+    if any(isinstance(s.gp, api.GibbsGP) for p in posts for s in p.slices):
+        mv = [p.mean_and_var(Xs) for p in posts]
+        return api.acq_prog_moments(np.stack([m for m, _ in mv]), np.stack([v for _, v in mv]), acq.program, q, mask, acq.outside,
+                                    problem.model.device)
+    own = cand is None
+    if own:
+        cand = api.Candidates(Xs, problem.model.device)
+    try:
+        means = None
+        if _device_mean_model(posts) is not None:
+            means = _device_prior_means(posts, Xs)[0]
+        elif posts[0].slices[0]._mean_s(Xs) is not None:
+            means = np.stack([np.stack([s._mean_s(Xs) for s in p.slices], axis=0) for p in posts], axis=0)   # S×P×M
+        return api.acq_prog([[s.gp for s in p.slices] for p in posts], cand, acq.program, q, mask, acq.outside, means)
+    finally:
+        if own:
+            cand.close()
+
+
 @dataclass
 class HipBatchAM:
     """x_prior: rng -> x (the reference takes a MultivariateDistribution); points: optional fixed
@@ -216,6 +268,8 @@ class HipBatchAM:
         """maximize_acquisition(::SamplingAM, problem, options) (sampling.jl:20-40) -> (x, val).
         posts: already-built posteriors of `problem` (HipSequentialBatchAM keeps them resident and
         extends them by block Cholesky appends); default: build them from problem.params."""
+        prog = _program_acquisition(problem, "HipBatchAM(devices=[...])" if self.devices is not None else "")
+        q = problem.acquisition.scalars(problem) if prog else None      # params(problem): once per maximisation
         Xs = self.candidates(problem)                                   # identical on every rank (seeded)
         M = Xs.shape[1]
         rank, world = dist_util.rank_world(self.group)
@@ -226,12 +280,12 @@ class HipBatchAM:
             assert world == 1 and posts is None, "devices=[...] is the single-process mode"
             return self._maximize_in_library(problem, Xs, return_all)
         if self.shard == "outputs":
-            return self._maximize_by_outputs(problem, Xs, rank, world, return_all)
+            return self._maximize_by_outputs(problem, Xs, rank, world, return_all, q)
         if self.shard == "samples":
-            return self._maximize_by_samples(problem, Xs, rank, world, return_all)
+            return self._maximize_by_samples(problem, Xs, rank, world, return_all, q)
         assert self.shard == "candidates", self.shard
         lo, hi = dist_util.shard_range(M, rank, world)
-        if posts is None and self.fused and hi > lo and self._fusable(problem):
+        if posts is None and self.fused and not prog and hi > lo and self._fusable(problem):
             acq, am, mx = self._update_and_acquire(problem, Xs[:, lo:hi], return_all)
             am += lo
             if return_all:
@@ -241,7 +295,8 @@ class HipBatchAM:
         if posts is None:
             posts = posteriors_of(problem)
         if hi > lo:
-            acq, am, mx = acquisition_values(problem, posts, Xs[:, lo:hi])
+            # (q travels only with a DeviceAcquisition: an acquisition_values put in its place by a caller keeps the older signature)
+            acq, am, mx = acquisition_values(problem, posts, Xs[:, lo:hi], **({} if q is None else {"q": q}))
             am += lo
         else:
             acq, am, mx = np.zeros(0), M, -np.inf
@@ -332,28 +387,28 @@ class HipBatchAM:
         return Xs[:, am].copy(), mx
 
     # (the two modes below factorise only a shard of the outputs / samples on each rank)
-    def _maximize_by_outputs(self, problem: BossProblem, Xs, rank, world, return_all):
-        if isinstance(problem.acquisition.fitness, NonlinFitness):
+    def _maximize_by_outputs(self, problem: BossProblem, Xs, rank, world, return_all, q=None):
+        if q is None and isinstance(problem.acquisition.fitness, NonlinFitness):   # (q: a DeviceAcquisition, which needs no fitness)
             raise NotImplementedError("shard='outputs' needs the analytic EI of LinFitness; use shard='candidates'")
         P, S, M = problem.data.Y.shape[0], n_samples(problem), Xs.shape[1]
         mine = {i: output_moments(problem, i, Xs) for i in range(P) if dist_util.owner_of(i, world) == rank}
         rows = dist_util.allgather_owned(mine, P, (S, 2, M), self.group)        # [P][S][2][M]
         mu = np.ascontiguousarray(rows[:, :, 0, :].transpose(1, 0, 2))          # [S][P][M]
         var = np.ascontiguousarray(rows[:, :, 1, :].transpose(1, 0, 2))
-        acq, am, mx = moments_acquisition(problem, mu, var, Xs)                  # identical on every rank
+        acq, am, mx = moments_acquisition(problem, mu, var, Xs, **({} if q is None else {"q": q}))   # identical on every rank
         if return_all:
             return Xs, acq
         return Xs[:, am].copy(), mx
 
-    def _maximize_by_samples(self, problem: BossProblem, Xs, rank, world, return_all):
-        if isinstance(problem.acquisition.fitness, NonlinFitness):
+    def _maximize_by_samples(self, problem: BossProblem, Xs, rank, world, return_all, q=None):
+        if q is None and isinstance(problem.acquisition.fitness, NonlinFitness):
             raise NotImplementedError("shard='samples' needs the analytic EI of LinFitness; use shard='candidates'")
         S, M = n_samples(problem), Xs.shape[1]
         lo, hi = dist_util.shard_range(S, rank, world)
         part = np.zeros(M)
         if hi > lo:
             posts = posteriors_of(problem, lo, hi)
-            acq, _, _ = acquisition_values(problem, posts, Xs)                   # mean over the local samples
+            acq, _, _ = acquisition_values(problem, posts, Xs, **({} if q is None else {"q": q}))   # mean over the local samples
             part = acq * (hi - lo)
         acq = dist_util.allreduce_sum(part, self.group) / S                      # (:87-90) mean over all samples
         if return_all:
@@ -384,7 +439,8 @@ class HipSequentialBatchAM:
         prob.data = type(problem.data)(problem.data.X.copy(), problem.data.Y.copy())
         posts = posteriors_of(prob, reserve=self.batch_size)             # no re-allocation when the appends arrive
         fixed = self.am.points is not None or self.am.seed is not None   # same candidate set at every selection
-        lin = not isinstance(prob.acquisition.fitness, NonlinFitness)
+        # (a DeviceAcquisition takes the untracked loop a NonlinFitness takes: the tracks know the EI epilogue alone)
+        lin = not _program_acquisition(prob) and not isinstance(prob.acquisition.fitness, NonlinFitness)
         try:
             if fixed and lin and self.am.shard == "candidates":
                 return self._tracked(prob, posts), None
@@ -488,6 +544,8 @@ class HipGradientAM:
                 raise ValueError("HipGradientAM: mean_grad is not taken for a HipTransformedModel (a DeviceMean gives its own ∂m/∂x_)")
             return warped_value_and_grad(problem, posts, X)
         ei = problem.acquisition
+        if _program_acquisition(problem):
+            return self._program_value_and_grad(problem, posts, X)
         mc = isinstance(ei.fitness, DeviceFitness)
         if isinstance(ei.fitness, NonlinFitness) and not mc:
             raise NotImplementedError("HipGradientAM needs the analytic EI of LinFitness, or a DeviceFitness")
@@ -549,8 +607,48 @@ class HipGradientAM:
             acc, gacc = acc + a, gacc + g
         return acc / len(posts), gacc / len(posts)
 
+    def _program_value_and_grad(self, problem: BossProblem, posts, X):
+        """A DeviceAcquisition: the traced program and its reverse sweep behind the moment gradients in ONE device call, one sample
+        or many (boss_acq_prog_grad); from the slices' moments and moment gradients for nonstationary posteriors."""
+        acq = problem.acquisition
+        q = self.__dict__.get("_acq_q")
+        if q is None:                                        # (called outside maximize_acquisition)
+            q = acq.scalars(problem)
+        mask = _program_mask(problem, X)
+        M = X.shape[1]
+        gps = [[s.gp for s in post.slices] for post in posts]
+        dev = _device_mean_model(posts) is not None
+        if dev and self.mean_grad is not None:
+            raise ValueError("HipGradientAM: the model's mean is a DeviceMean, which gives its own ∂m/∂x; drop mean_grad")
+        if dev:
+            dms, dmg = _device_prior_means(posts, X, jac_x=True)
+            return api.acq_prog_grad(gps, X, acq.program, q, mask, acq.outside, dms, dmg)
+        mg = None
+        if self.mean_grad is not None:
+            mg = np.stack([np.asarray(self.mean_grad(X[:, j]), float) for j in range(M)], axis=2)
+        if any(isinstance(s.gp, api.GibbsGP) for post in posts for s in post.slices):
+            mvg = [[s.mean_and_var_grad(X) if mg is None else s.mean_and_var_grad(X, mean_grad=mg[i]) for i, s in enumerate(post.slices)]
+                   for post in posts]
+            mu, var, dmu, dvar = (np.stack([np.stack([r[k] for r in row]) for row in mvg]) for k in range(4))
+            return api.acq_prog_grad_moments(mu, var, dmu, dvar, acq.program, q, mask, acq.outside, problem.model.device)
+        rows = [[s._mean_s(X) for s in post.slices] for post in posts]
+        ms = None
+        if any(r is not None for row in rows for r in row):  # slices without a prior mean travel as zeros
+            ms = np.stack([np.stack([np.zeros(M) if r is None else np.asarray(r, float) for r in row]) for row in rows])   # S×P×M
+        mgs = None if mg is None else np.stack([mg] * len(posts))
+        return api.acq_prog_grad(gps, X, acq.program, q, mask, acq.outside, ms, mgs)
+
     def maximize_acquisition(self, problem: BossProblem, options: BossOptions = BossOptions(), posts=None):
         refuse_device_kernel(problem.model, "HipGradientAM (candidate gradients)", grad_ok=True)
+        self.__dict__.pop("_acq_q", None)
+        if _program_acquisition(problem):
+            self.__dict__["_acq_q"] = problem.acquisition.scalars(problem)   # params(problem): once per maximisation
+        try:
+            return self._maximize(problem, posts)
+        finally:
+            self.__dict__.pop("_acq_q", None)                # (a later _value_and_grad call asks params(problem) itself)
+
+    def _maximize(self, problem: BossProblem, posts):
         if isinstance(getattr(problem.acquisition, "fitness", None), DeviceFitness):
             refuse_device_kernel(problem.model, "HipGradientAM with a DeviceFitness (Monte-Carlo EI gradients are built-in-kernel only)")
         if self.mean_grad is not None and device_mean_of(problem.model) is not None:

@@ -224,7 +224,7 @@ class BossProblem:
     """src/types/problem.jl:38-58 (fields the hot path's callers touch)."""
     f: Optional[Callable]
     domain: Domain
-    acquisition: ExpectedImprovement
+    acquisition: object          # ExpectedImprovement, or a DeviceAcquisition (acq_program.py): any acquisition the maximizers dispatch on
     model: object
     data: ExperimentData
     y_max: Optional[Sequence[float]] = None

@@ -576,6 +576,64 @@ int boss_acq_ei_mc_grad_moments(int device, int P, int S, int M, int d, const do
                                 const double* dvar, const boss_fit_t* fit, int n_eps, const double* eps, const double* y_max,
                                 int has_best, double best, const unsigned char* valid_mask, double* acq_out, double* dacq_out);
 
+/* ---- acquisition programs: a user-defined acquisition function on the device -------------------------------------------------
+ * Replaces: construct_acquisition(acq::AcquisitionFunction, problem, options) -> (x -> Real) for a custom acquisition
+ * (src/types/acquisition.jl:1-57) behind construct_safe_acquisition (src/acquisition.jl:21-25), and its ForwardDiff derivative
+ * inside OptimizationAM.  The function of the posterior moments of one candidate travels as a straight-line program.
+ *
+ * boss_acqp_t holds a validated program in the form of boss_fit_t over 2P + Q inputs:
+ *   value ids 0..P-1       mu_p, the posterior means of the P outputs;
+ *   value ids P..2P-1      var_p, the posterior variances AFTER the clip below;
+ *   value ids 2P..2P+Q-1   Q runtime scalars q, given with every call (best-so-far, beta_t, y_max: what changes per BO iteration);
+ *   then the constants and the instruction results, as in boss_fit_t;
+ *   limits    1 <= P <= 8, 0 <= Q <= 16, n_const <= 32, n_instr <= 64.
+ * Opcodes: the BOSS_FIT_* ones and two unary ones that only boss_acqp_create accepts (every other *_create answers "unknown
+ * opcode" for them):
+ *   BOSS_ACQ_NORMCDF  Phi(z) = 0.5 erfc(-z / sqrt 2),          derivative phi(z);
+ *   BOSS_ACQ_NORMPDF  phi(z) = exp(-z^2 / 2) / sqrt(2 pi),     derivative -z phi(z).
+ * Derivative conventions: those of boss_fit_t.  boss_acqp_create refuses what boss_fit_create refuses.
+ * boss_acqp_create / boss_acqp_free / boss_acqp_eval_host need no device.
+ * boss_acqp_eval_host: the RAW program and its reverse sweep at n moment columns — mu, var P×n column-major, q Q scalars (may be
+ * NULL when Q = 0), a_out n values, da_dmu / da_dvar P×n or NULL.  No clip and no mask are applied.
+ *
+ * The four acquisition calls.  Arguments are those of the EI call named beside each, with fit_coefs / y_max / has_best / best
+ * replaced by the program, its scalars q (Q doubles, non-finite values allowed) and `outside`.  For candidate j and sample s:
+ *   variance clip   a variance in [-1e-8, 0) enters the program as 0; a variance below -1e-8 in any output of any sample makes
+ *                   the candidate's value -Inf and its gradient 0, and the program is not consulted for that sample;
+ *   sample average  a_s = program(mu, var, q); S = 1: the value is a_0; S > 1: the a_s are added in ascending s and the sum is
+ *                   multiplied by 1/S once.  No atomics: repeated calls agree bit for bit;
+ *   mask            a candidate whose valid_mask byte is 0 gets the value `outside` (any double; -Inf is the value of
+ *                   construct_safe_acquisition) and gradient 0;
+ *   arg-max         first index of the maximum, NaN counts as the largest value;
+ *   gradient        d acq / d x_m = (1/S) sum_s sum_p (abar_mu_p d mu_p / d x_m + abar_var_p d var_p / d x_m), abar from the reverse
+ *                   sweep; p ascending, the mu term before the var term, s ascending; an output whose variance is <= 0 after
+ *                   the clip contributes no var term.
+ *   boss_acq_prog               [boss_acq_ei]               every handle kind boss_acq_ei takes, fitted sets included;
+ *   boss_acq_prog_moments       [boss_acq_ei_moments]       from host moments mu / var S×P×M;
+ *   boss_acq_prog_grad          [boss_acq_ei_grad_set]      value and gradient, S >= 1; program-kernel handles need boss_kgp_set_grad;
+ *   boss_acq_prog_grad_moments  [boss_acq_ei_mc_grad_moments]  mu / var [s][p][M], dmu / dvar [s][p][d×M].
+ * BOSS_E_INVALID: the program's P differs from P, q is NULL with Q > 0.
+ * Not offered with an acquisition program: the boss_multi_* calls, boss_acq_ei_tracks, boss_gp_update_acq, the *_warp calls. */
+#define BOSS_ACQ_NORMCDF 16
+#define BOSS_ACQ_NORMPDF 17
+typedef struct boss_acqp boss_acqp_t;
+int boss_acqp_create(int P, int Q, int n_const, const double* consts, int n_instr, const int* code, int out_id, boss_acqp_t** out);
+void boss_acqp_free(boss_acqp_t* acqp);
+int boss_acqp_eval_host(const boss_acqp_t* acqp, int n, const double* mu, const double* var, const double* q, double* a_out,
+                        double* da_dmu, double* da_dvar);
+int boss_acq_prog(int P, int S, boss_gp_t* const* gps, const boss_cand_t* cand, const double* mean_Xs, const boss_acqp_t* acqp,
+                  const double* q, const unsigned char* valid_mask, double outside, double* acq_out, long* argmax_out,
+                  double* max_out);
+int boss_acq_prog_moments(int device, int P, int S, int M, const double* mu, const double* var, const boss_acqp_t* acqp,
+                          const double* q, const unsigned char* valid_mask, double outside, double* acq_out, long* argmax_out,
+                          double* max_out);
+int boss_acq_prog_grad(int P, int S, boss_gp_t* const* gps, int M, const double* Xs, const double* mean_Xs, const double* mean_grad,
+                       const boss_acqp_t* acqp, const double* q, const unsigned char* valid_mask, double outside, double* acq_out,
+                       double* dacq_out);
+int boss_acq_prog_grad_moments(int device, int P, int S, int M, int d, const double* mu, const double* var, const double* dmu,
+                               const double* dvar, const boss_acqp_t* acqp, const double* q, const unsigned char* valid_mask,
+                               double outside, double* acq_out, double* dacq_out);
+
 /* ---- mean programs: the Semiparametric model's parametric mean on the device, with its Jacobians ------------------------------
  * Replaces: the per-point calls of the parametric model m(x; θ) (src/models/parametric.jl:31-34,186-207) behind the Semiparametric
  * mean (src/models/semiparametric.jl:79-92) and of a GaussianProcess mean function (src/models/gaussian_process.jl:101-103), and the
