@@ -164,6 +164,7 @@ SIGNATURES = {
     "boss_kgp_create": (C.c_int, [C.c_int, C.c_int, C.c_int, _c_dp, _c_dp, _c_ucp, C.c_void_p, C.POINTER(C.c_void_p)]),
     "boss_kern_grad_host": (C.c_int, [C.c_void_p, C.c_int, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
     "boss_kgp_set_grad": (C.c_int, [C.c_void_p, C.c_int]),
+    "boss_kgp_set_sequential": (C.c_int, [C.c_void_p, C.c_int]),
     "boss_kgp_loglike_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, _c_dp, _c_dp, _c_ucp, C.c_void_p, C.c_int, _c_dp, _c_dp, _c_dp, _c_dp,
                                          C.c_int, _c_dp, C.POINTER(C.c_int)]),
     "boss_kgp_fit_batch": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, _c_dp, _c_dp, _c_dp, C.c_int, _c_ucp, C.c_int, _c_dp, _c_dp,
@@ -1977,9 +1978,10 @@ class KernelProgram:
 class KernelGP(GP):
     """One output slice's posterior under a KernelProgram (boss_kgp_create): update, sync, predict, set_y, factor and acq_ei work as
     for a GP; every other call of the base class is refused by the library (BOSS_E_INVALID, "program-kernel posteriors").
-    grad=True (boss_kgp_set_grad) adds loglike_grad, loglike_grad_mean, predict_grad, acq_ei_grad and acq_ei_grad_set."""
+    grad=True (boss_kgp_set_grad) adds loglike_grad, loglike_grad_mean, predict_grad, acq_ei_grad and acq_ei_grad_set.
+    sequential=True (boss_kgp_set_sequential) adds append, reserve and Track(gp, cand) with acq_ei_tracks."""
 
-    def __init__(self, X, y, kern: KernelProgram, discrete=None, device: int = 0, grad: bool = False):
+    def __init__(self, X, y, kern: KernelProgram, discrete=None, device: int = 0, grad: bool = False, sequential: bool = False):
         lib = load_library()
         X = _f64(X, 2)
         y = _f64(np.asarray(y).reshape(-1), 1)
@@ -1996,12 +1998,15 @@ class KernelGP(GP):
         self._h = h
         self.logpdf = None
         self.grad = bool(grad)
-        if self.grad:
-            try:
+        self.sequential = bool(sequential)
+        try:
+            if self.grad:
                 _check(lib.boss_kgp_set_grad(self._h, 1))
-            except Exception:
-                self.close()
-                raise
+            if self.sequential:
+                _check(lib.boss_kgp_set_sequential(self._h, 1))
+        except Exception:
+            self.close()
+            raise
 
 
 def _kgp_batch_args(X, y, kern, lengthscales, amplitudes, noise_stds, mean_X, discrete):
@@ -2050,10 +2055,11 @@ def kgp_loglike_batch(X, y, kern: KernelProgram, lengthscales, amplitudes, noise
 
 
 def kgp_fit_batch(X, y, kern: KernelProgram, lengthscales, amplitudes, noise_stds, mean_X=None, discrete=None, device: int = 0,
-                  grad: bool = False):
+                  grad: bool = False, sequential: bool = False):
     """S resident posteriors of one output slice under a KernelProgram from ONE batched factorisation (boss_kgp_fit_batch): what
     model_posterior builds per sample of a BI fit (src/posterior.jl:15-19).  Returns (gps[S], logpdf[S], status[S]): KernelGP
-    members of one set (grad=True: boss_kgp_set_grad on each); members with status != 0 are unfitted handles."""
+    members of one set (grad=True: boss_kgp_set_grad on each, sequential=True: boss_kgp_set_sequential on each); members with
+    status != 0 are unfitted handles."""
     X, y, lam, amp, sig, m, stride, disc, d, N, S = _kgp_batch_args(X, y, kern, lengthscales, amplitudes, noise_stds, mean_X, discrete)
     if not (np.isfinite(amp).all() and np.isfinite(sig).all() and np.isfinite(lam).all()):
         raise BossError(BOSS_E_INVALID, "hyper-parameters must be finite")
@@ -2068,13 +2074,17 @@ def kgp_fit_batch(X, y, kern: KernelProgram, lengthscales, amplitudes, noise_std
         g = KernelGP.__new__(KernelGP)
         g.d, g.N, g.device, g.kernel, g._h = d, N, device, kern, C.c_void_p(hs[s])
         g.logpdf = float(ll[s]) if st[s] == 0 else None
-        g.grad = False
+        g.grad = g.sequential = False
         gps.append(g)
-    if grad:
+    if grad or sequential:
         try:
             for g in gps:
-                _check(lib.boss_kgp_set_grad(g._h, 1))
-                g.grad = True
+                if grad:
+                    _check(lib.boss_kgp_set_grad(g._h, 1))
+                    g.grad = True
+                if sequential:
+                    _check(lib.boss_kgp_set_sequential(g._h, 1))
+                    g.sequential = True
         except Exception:
             for g in gps:
                 g.close()

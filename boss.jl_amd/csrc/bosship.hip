@@ -568,6 +568,7 @@ struct boss_gp {
     // copy), kernel == KERN_PROGRAM; Xsc holds the scaled points as for the plain model
     bool kprog = false;
     bool kgrad = false;                                      // boss_kgp_set_grad: the gradient entry points take this handle
+    bool kseq = false;                                       // boss_kgp_set_sequential: boss_gp_append / _reserve and boss_track_create take it
     FitProg* kp = nullptr;
     // explicit L⁻ᵀ for calls with one to four candidates (built on the second such call on a factorisation)
     double *Winv = nullptr, *Linv = nullptr;   // L⁻ᵀ (upper) and L⁻¹ (lower)
@@ -601,6 +602,7 @@ struct boss_track {                            // resident predictive state of (
     unsigned long long epoch = 0;
     double *V = nullptr, *Csc = nullptr, *mu = nullptr, *var = nullptr, *mean = nullptr;
     bool has_mean = false;
+    double* rhs = nullptr;                     // a program-kernel posterior's track: [tiles][TRACK_ROWS][32] right-hand sides of the rows being appended
     // a nonstationary posterior's track (boss_ngp_track_create): Csc holds the ROUNDED RAW candidates, Clam [d][Mp] and
     // Camp [Mp] the latent models' λ(x*), α(x*) there (one spare word behind Camp: the latent kernel's validity flag)
     bool gibbs = false;
@@ -684,10 +686,13 @@ static bool few_fused() {
     return v;
 }
 
-// program-kernel posteriors (host_kprog.inc): the launches factor_enqueue / predict_enqueue make for them
+// program-kernel posteriors (host_kprog.inc): the launches factor_enqueue / predict_enqueue / the appends / the tracks make for them
 static void kprog_gram_launch(boss_gp* g, hipStream_t s);
 static void kprog_kstar_launch(boss_gp* g, const boss_cand* cd, const double* Csc, int BN, int tiles, double* out, double* pvar, hipStream_t s);
 static void kprog_var_launch(hipStream_t s, double* var, const double* pvar, int M);
+static void kprog_gram_rows_launch(boss_gp* g, int kb, hipStream_t s);
+static void kprog_append_col_launch(boss_gp* g, int N0, const double* Csc, double* R, double* kself, hipStream_t s);
+static void kprog_track_rhs_launch(boss_gp* g, int N0, int n, const double* Csc, int Mp, int M, int tiles, double* rhs, hipStream_t s);
 static void kprog_kstar_set_launch(boss_gp* g0, const boss_cand* cd, const PredSet* dsets, int tiles, int cnt, double* V, double* pvar, size_t spv,
                                    hipStream_t s);
 static void kprog_var_set_launch(hipStream_t s, const PredSet* dsets, int cnt, const double* pvar, size_t spv, int M);

@@ -772,12 +772,16 @@ __global__ __launch_bounds__(256) void gibbs_grad_fold_set_kernel(const GradSet*
 // Up to 8 new rows per launch (one read of V for all of them).  One workgroup per 32-candidate slab:
 // lanes along the candidates, 8 subsets of the old rows; the new rows of L are staged through LDS.
 // ------------------------------------------------------------------------------------------
+// RHS_BUF: the right-hand sides k(x_r, x*) come from rhs[tile][TRACK_ROWS][32] (a program kernel's, written by
+// kprog_track_rhs_kernel in front of this launch) instead of kappa_r2 on the scaled points; everything else is one body.
 constexpr int TRACK_ROWS = 8;
+template <bool RHS_BUF = false>
 __global__ __launch_bounds__(256) void track_append_kernel(const double* __restrict__ A, int ld, int Np, int N0, int n,
                                                            double* __restrict__ Vslabs, int Ncap,
                                                            const double* __restrict__ Xsc, int Npx,
                                                            const double* __restrict__ Csc, int d, int Mp, int M, int kern,
-                                                           double amp2, double* __restrict__ mu, double* __restrict__ var) {
+                                                           double amp2, double* __restrict__ mu, double* __restrict__ var,
+                                                           const double* __restrict__ rhs = nullptr) {
     constexpr int BN = 32, CH = 64;
     __shared__ double Lr[TRACK_ROWS][CH];
     __shared__ double red[8][TRACK_ROWS][BN];
@@ -811,12 +815,18 @@ __global__ __launch_bounds__(256) void track_append_kernel(const double* __restr
         for (int q = 0; q < n; ++q) {
             double dot = 0.0;
             for (int k = 0; k < 8; ++k) dot += red[k][q][c];
-            double r2 = 0.0;
-            for (int m = 0; m < d; ++m) {
-                const double diff = Csc[(size_t)m * Mp + j] - Xsc[(size_t)m * Npx + N0 + q];
-                r2 = __builtin_fma(diff, diff, r2);
+            double kv;
+            if constexpr (RHS_BUF) {
+                kv = rhs[((size_t)blockIdx.x * TRACK_ROWS + q) * BN + c];
+            } else {
+                double r2 = 0.0;
+                for (int m = 0; m < d; ++m) {
+                    const double diff = Csc[(size_t)m * Mp + j] - Xsc[(size_t)m * Npx + N0 + q];
+                    r2 = __builtin_fma(diff, diff, r2);
+                }
+                kv = amp2 * kappa_r2(kern, r2);
             }
-            double t = amp2 * kappa_r2(kern, r2) - dot;
+            double t = kv - dot;
             for (int qq = 0; qq < q; ++qq) t = __builtin_fma(-A[(size_t)(N0 + qq) * ld + N0 + q], vnew[qq], t);
             const double v = t / A[(size_t)(N0 + q) * ld + N0 + q];
             vnew[q] = v;

@@ -170,7 +170,8 @@ static int gp_grow(boss_gp* g, int Nnew) {
 static int reserve_locked_entry(boss_gp* g, int N_total);
 extern "C" int boss_gp_reserve(boss_gp_t* g, int N_total) {
     if (!g || N_total < 1) return fail(BOSS_E_INVALID, "bad arguments");
-    NOT_FOR_AUG(g);
+    NOT_FOR_MODELS(g);
+    KPROG_NEEDS_SEQ(g);
     return reserve_locked_entry(g, N_total);
 }
 // The same for a nonstationary handle: λ(X), α(X), σ(X) grow with the rest (gp_grow); follow with boss_ngp_update, whose latent
@@ -315,6 +316,8 @@ static int append_rows_enqueue(boss_gp* g, int N0, int N1, int Np_before) {
             hipLaunchKernelGGL(gibbs_gram_kernel, tiles, dim3(256), 0, s, (const double*)g->Xraw,
                                (const double*)g->lamX, (const double*)g->ampX, (const double*)g->noiseX, (size_t)0, (size_t)0, d, N1,
                                Np, g->A, ld, (size_t)0, tile0);
+        else if (g->kprog)
+            kprog_gram_rows_launch(g, kb, s);                // (the same tiles under the program: N1 = g->N bounds the valid rows)
         else
             hipLaunchKernelGGL(gram_kernel, tiles, dim3(256), 0, s, g->Xsc, (size_t)0, d, N1, Np, g->kernel,
                                g->hyp, g->A, ld, (size_t)0, tile0);
@@ -341,7 +344,8 @@ static int append_locked(boss_gp* g, int n, const double* X_new, const double* y
 extern "C" int boss_gp_append(boss_gp_t* g, int n, const double* X_new, const double* y_new, const double* mean_new,
                               double* logpdf_out) {
     if (!g || n < 1 || !X_new || !y_new) return fail(BOSS_E_INVALID, "need a handle, n >= 1 and non-NULL X_new, y_new");
-    NOT_FOR_AUG(g);
+    NOT_FOR_MODELS(g);
+    KPROG_NEEDS_SEQ(g);
     Ctx* c = g->ctx;
     HIPCHK(hipSetDevice(c->device));
     std::lock_guard<std::mutex> lk(c->mtx);
@@ -391,7 +395,9 @@ static int append_locked(boss_gp* g, int n, const double* X_new, const double* y
     if (rc) return rc;
     gp_invalidate_append(g, fast);
     // one observation on resident inverse factors, x_dim small enough for kernel arguments: no upload, no synchronisation in front
-    const bool by_args = fast && n == 1 && d <= FEW_ARGS_MAX_D && !few_args_off();
+    // (a program kernel takes the device-buffer variant: its K* needs the interpreter, which the kernel-argument and fused variants
+    // do not carry — a later optimisation)
+    const bool by_args = fast && n == 1 && d <= FEW_ARGS_MAX_D && !few_args_off() && !g->kprog;
     if (!by_args) {
         rc = append_upload(g, n, X_new, n, y_new, mean_new);
         if (rc) return rc;
@@ -414,6 +420,7 @@ static int append_locked(boss_gp* g, int n, const double* X_new, const double* y
         double* lvec = part + (size_t)nwg * 8;
         double* wvec = lvec + Np;
         double* dz = wvec + Np;
+        double* kself = g->kprog ? dz + 2 : nullptr;         // program kernel: k(x_new, x_new), evaluated (no constant prior variance)
         double* Csc = (double*)c->csc.p;
         bool fused_done = false;
         if (by_args) {
@@ -467,8 +474,11 @@ static int append_locked(boss_gp* g, int n, const double* X_new, const double* y
             hipLaunchKernelGGL(scale_points_kernel, dim3((Np + 255) / 256, 1, 1), dim3(256), 0, s, g->Xraw, g->Xsc, (size_t)0, g->invlam, d, Np);
             // the new (scaled) point as candidate 0 of a 64-wide candidate block
             HIPCHK(hipMemcpy2DAsync(Csc, sizeof(double) * 64, g->Xsc + N0, sizeof(double) * Np, sizeof(double), d, hipMemcpyDeviceToDevice, s));
-            hipLaunchKernelGGL(kstar_rows_kernel, dim3(Np / 256, 1), dim3(256), sizeof(double) * (d * 32 + KSTAR_LDS_EXTRA), s, (const double*)g->Xsc, Np, N0,
-                               (const double*)Csc, d, 64, g->kernel, g->amp2, R, 1);
+            if (g->kprog)
+                kprog_append_col_launch(g, N0, Csc, R, kself, s);
+            else
+                hipLaunchKernelGGL(kstar_rows_kernel, dim3(Np / 256, 1), dim3(256), sizeof(double) * (d * 32 + KSTAR_LDS_EXTRA), s, (const double*)g->Xsc, Np, N0,
+                                   (const double*)Csc, d, 64, g->kernel, g->amp2, R, 1);
         }
         if (!fused_done) {
             hipLaunchKernelGGL(winv_gemv_kernel<1>, dim3(nwg), dim3(256), sizeof(double) * (size_t)Np, s, (const double*)g->Winv, ld, Np,
@@ -476,7 +486,7 @@ static int append_locked(boss_gp* g, int n, const double* X_new, const double* y
             // (by_args: the scalars kernel hands {logdet, zᵀz, info} to the host itself — the call returns while the second pass runs)
             hipLaunchKernelGGL(append_scalars_kernel, dim3(1), dim3(256), 0, s, (const double*)part, nwg, (const double*)g->hyp,
                                (const double*)g->y, (const double*)g->mean, N0, g->scal, dz, g->info, by_args ? g->host_res_dev : (double*)nullptr,
-                               by_args ? ++g->res_seq : 0ull);
+                               by_args ? ++g->res_seq : 0ull, (const double*)kself);
         }
         hipLaunchKernelGGL(linv_col_gemv_kernel, dim3((N0 + 7) / 8), dim3(256), 0, s, (const double*)g->Linv, ld, N0,
                            (const double*)lvec, wvec);

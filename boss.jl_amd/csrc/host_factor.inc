@@ -784,6 +784,13 @@ extern "C" int boss_ggp_create(int device, int kernel, int d, int n, const doubl
             return fail(BOSS_E_INVALID, "not available for program-kernel posteriors (boss_kgp_create) without boss_kgp_set_grad"); \
     } while (0)
 
+// appends, reserve and tracked candidates: a program-kernel posterior is refused unless boss_kgp_set_sequential switched them on
+#define KPROG_NEEDS_SEQ(g)                                                                                                             \
+    do {                                                                                                                               \
+        if ((g)->kprog && !(g)->kseq)                                                                                                  \
+            return fail(BOSS_E_INVALID, "not available for program-kernel posteriors (boss_kgp_create) without boss_kgp_set_sequential"); \
+    } while (0)
+
 #define NOT_FOR_AUG(g)      \
     do {                    \
         NOT_FOR_MODELS(g);  \

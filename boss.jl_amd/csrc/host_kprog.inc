@@ -91,8 +91,19 @@ extern "C" int boss_kgp_set_grad(boss_gp_t* g, int on) {
     return BOSS_OK;
 }
 
+// Appends and tracked candidates on (on != 0) or off for a program-kernel posterior: boss_gp_append, boss_gp_reserve and
+// boss_track_create (and with it boss_track_sync / _moments / _free, boss_acq_ei_tracks) take the handle while the flag is set.
+// Before or after boss_gp_update; nothing resident changes; independent of boss_kgp_set_grad.
+extern "C" int boss_kgp_set_sequential(boss_gp_t* g, int on) {
+    if (!g) return fail(BOSS_E_INVALID, "gp is NULL");
+    if (!g->kprog) return fail(BOSS_E_INVALID, "handle was not created by boss_kgp_create");
+    std::lock_guard<std::mutex> lk(g->ctx->mtx);
+    g->kseq = on != 0;
+    return BOSS_OK;
+}
+
 // ------------------------------------------------------------------------------------------
-// launches (declared in bosship.hip for host_factor.inc / host_predict.inc)
+// launches (declared in bosship.hip for host_factor.inc / host_append.inc / host_predict.inc / host_track.inc)
 // ------------------------------------------------------------------------------------------
 // workgroup size (whole waves) and dynamic LDS of a program over d dimensions: as many of the 4 waves as fit 64 KiB
 static int kprog_block(const FitProg& g, int d, size_t* lds) {
@@ -108,7 +119,16 @@ static void kprog_gram_launch(boss_gp* g, hipStream_t s) {
     const int threads = kprog_block(*g->kp, g->d, &lds);
     const int t64 = g->Np / 64;
     hipLaunchKernelGGL(kprog_gram_kernel, dim3(t64 * (t64 + 1) / 2, 1, 1), dim3(threads), lds, s, *g->kp, (const double*)g->Xsc, (size_t)0, g->d,
-                       g->N, g->Np, (const double*)g->hyp, (size_t)0, g->A, g->ld, (size_t)0);
+                       g->N, g->Np, (const double*)g->hyp, (size_t)0, g->A, g->ld, (size_t)0, 0);
+}
+
+// ... of block row kb alone (append_rows_enqueue): its 4·kb + 3 tiles of 64×64 from triangular tile index kb (2 kb + 1), the
+// built-in kernels' numbers; g->N counts the new observations, rows behind them are those of the identity
+static void kprog_gram_rows_launch(boss_gp* g, int kb, hipStream_t s) {
+    size_t lds;
+    const int threads = kprog_block(*g->kp, g->d, &lds);
+    hipLaunchKernelGGL(kprog_gram_kernel, dim3(4 * kb + 3, 1, 1), dim3(threads), lds, s, *g->kp, (const double*)g->Xsc, (size_t)0, g->d, g->N,
+                       g->Np, (const double*)g->hyp, (size_t)0, g->A, g->ld, (size_t)0, kb * (2 * kb + 1));
 }
 
 // ... of cnt parameter sets with constant strides (boss_kgp_loglike_batch, boss_kgp_fit_batch): the sets' scaled points from the
@@ -120,7 +140,7 @@ static void kprog_gram_batch_launch(const FitProg& kp, int d, int N, int Np, int
     const int t64 = Np / 64;
     hipLaunchKernelGGL(kprog_scale_set_kernel, dim3((Np + 255) / 256, cnt), dim3(256), 0, s, Xraw, Xsc, sX, par, sPar, d, Np);
     hipLaunchKernelGGL(kprog_gram_kernel, dim3(t64 * (t64 + 1) / 2, 1, cnt), dim3(threads), lds, s, kp, (const double*)Xsc, sX, d, N, Np, hyp,
-                       sHyp, A, ld, bstride);
+                       sHyp, A, ld, bstride, 0);
 }
 
 // K* of `tiles` candidate tiles of BN (32 or 64) into out[tile][Np][BN], and k(x*, x*) of their candidates into pvar
@@ -130,6 +150,24 @@ static void kprog_kstar_launch(boss_gp* g, const boss_cand* cd, const double* Cs
     auto kfn = BN == 32 ? kprog_kstar_kernel<32> : kprog_kstar_kernel<64>;
     hipLaunchKernelGGL(kfn, dim3(g->Np / 256, tiles), dim3(threads), lds, s, *g->kp, (const double*)g->Xsc, g->d, g->N, g->Np, Csc, cd->Mp,
                        cd->M, g->amp2, out, pvar);
+}
+
+// The new column of a rank-one append (append_locked): R[row][0] = (α+1e-8)² f(u_row, u_new) for the N0 old rows in column 0 of a
+// 32-wide tile (the layout kstar_rows_kernel writes there; 0 for the rows behind them), and kself[0] = (α+1e-8)² f(u_new, u_new), the
+// prior variance the new diagonal entry starts from.  Csc: the new scaled point as candidate 0 of a 64-wide candidate block.
+static void kprog_append_col_launch(boss_gp* g, int N0, const double* Csc, double* R, double* kself, hipStream_t s) {
+    size_t lds;
+    const int threads = kprog_block(*g->kp, g->d, &lds);
+    hipLaunchKernelGGL(kprog_col_kernel, dim3((g->Np + threads - 1) / threads), dim3(threads), lds, s, *g->kp, (const double*)g->Xsc, g->d, N0,
+                       g->Np, Csc, 64, g->amp2, R, kself);
+}
+
+// the right-hand sides of the n <= TRACK_ROWS rows from N0 on for `tiles` candidate tiles of a track (track_sync_locked)
+static void kprog_track_rhs_launch(boss_gp* g, int N0, int n, const double* Csc, int Mp, int M, int tiles, double* rhs, hipStream_t s) {
+    size_t lds;
+    const int threads = kprog_block(*g->kp, g->d, &lds);
+    hipLaunchKernelGGL(kprog_track_rhs_kernel, dim3(tiles), dim3(threads), lds, s, *g->kp, (const double*)g->Xsc, g->d, g->Np, N0, n, Csc, Mp, M,
+                       g->amp2, rhs);
 }
 
 static void kprog_var_launch(hipStream_t s, double* var, const double* pvar, int M) {

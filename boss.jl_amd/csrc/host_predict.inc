@@ -214,7 +214,9 @@ static int predict_enqueue(boss_gp* g, const boss_cand* cd, const double* mean_s
     if (!g->fitted) return fail(BOSS_E_NOT_FITTED, "handle has no valid factorisation");
     if (g->gibbs && !clam_dev)
         return fail(BOSS_E_INVALID, "nonstationary posteriors predict through boss_ngp_predict (λ(x*), α(x*) are needed)");
-    if (g->kprog && ((for_grad && !g->kgrad) || need_v))
+    // (for_grad also keeps the 32-wide V slabs for a new track: the gradient entry points check boss_kgp_set_grad themselves, the
+    // track's asks for boss_kgp_set_sequential)
+    if (g->kprog && ((for_grad && !g->kgrad && !g->kseq) || need_v))
         return fail(BOSS_E_INVALID, "not available for program-kernel posteriors (boss_kgp_create): covariances, and gradients without boss_kgp_set_grad");
     if (cd->ctx != c) return fail(BOSS_E_INVALID, "candidates and posterior live on different devices");
     if (cd->d != g->d) return fail(BOSS_E_INVALID, "candidate dimension differs from the model's x_dim");

@@ -6,7 +6,7 @@
 static void track_release(boss_track* t) {
     if (!t) return;
     if (t->ctx) (void)hipSetDevice(t->ctx->device);
-    void* ptrs[] = {t->V, t->Csc, t->mu, t->var, t->mean, t->Clam, t->Camp};
+    void* ptrs[] = {t->V, t->Csc, t->mu, t->var, t->mean, t->Clam, t->Camp, t->rhs};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     delete t;
@@ -38,7 +38,9 @@ static int track_rebuild(boss_track* t, const boss_cand* cd) {
         own.Craw = t->Csc;
         rc = predict_enqueue(g, &own, t->has_mean ? t->mean : nullptr, t->mu, t->var, true, t->Clam, t->Camp);
     } else {
-        rc = predict_enqueue(g, cd, t->has_mean ? t->mean : nullptr, t->mu, t->var, true);   // 32-wide slabs in the scratch
+        // 32-wide slabs in the scratch; a program kernel's σ² = k(x*, x*) − Σv² + 1e-18 arrives unclipped (kprog_var_launch), its scaled
+        // candidates stay in the context's buffer like the built-in kernels'
+        rc = predict_enqueue(g, cd, t->has_mean ? t->mean : nullptr, t->mu, t->var, true);
     }
     if (rc) return rc;
     HIPCHK(hipMemcpy2DAsync(t->V, sizeof(double) * (size_t)t->Ncap * 32, c->vscratch.p, sizeof(double) * (size_t)g->Np * 32,
@@ -87,6 +89,7 @@ static int track_create(boss_gp* g, const boss_cand* cand, const double* lam, co
     if (dev_malloc((void**)&t->Csc, sizeof(double) * (size_t)d * Mp) != hipSuccess ||
         (t->gibbs && (dev_malloc((void**)&t->Clam, sizeof(double) * (size_t)d * Mp) != hipSuccess ||
                       dev_malloc((void**)&t->Camp, sizeof(double) * ((size_t)Mp + 1)) != hipSuccess)) ||
+        (g->kprog && dev_malloc((void**)&t->rhs, sizeof(double) * (size_t)t->tiles * TRACK_ROWS * 32) != hipSuccess) ||
         dev_malloc((void**)&t->mu, sizeof(double) * M) != hipSuccess ||
         dev_malloc((void**)&t->var, sizeof(double) * M) != hipSuccess ||
         dev_malloc((void**)&t->mean, sizeof(double) * M) != hipSuccess)
@@ -124,7 +127,8 @@ extern "C" int boss_track_create(boss_gp_t* g, const boss_cand_t* cand, const do
     if (!out) return fail(BOSS_E_INVALID, "out is NULL");
     *out = nullptr;
     if (!g || !cand) return fail(BOSS_E_INVALID, "NULL argument");
-    NOT_FOR_AUG(g);
+    NOT_FOR_MODELS(g);
+    KPROG_NEEDS_SEQ(g);
     if (cand->ctx != g->ctx || cand->d != g->d) return fail(BOSS_E_INVALID, "candidates and posterior must share device and x_dim");
     return track_create(g, cand, nullptr, nullptr, nullptr, mean_Xs, out);
 }
@@ -213,10 +217,16 @@ static int track_sync_locked(boss_track* t) {
                                (const double*)g->A, g->ld, g->Np, N0, n, t->V, t->Ncap, (const double*)g->Xraw, (const double*)g->lamX,
                                (const double*)g->ampX, g->Np, (const double*)t->Csc, (const double*)t->Clam, (const double*)t->Camp,
                                t->d, t->Mp, t->M, t->mu, t->var);
-        else
-            hipLaunchKernelGGL(track_append_kernel, dim3(t->tiles), dim3(256), 0, s, (const double*)g->A, g->ld, g->Np, N0, n, t->V,
+        else if (g->kprog) {
+            // the program's right-hand sides first (its interpreter needs a workgroup shape of its own), then the shared pass over V
+            kprog_track_rhs_launch(g, N0, n, t->Csc, t->Mp, t->M, t->tiles, t->rhs, s);
+            hipLaunchKernelGGL(track_append_kernel<true>, dim3(t->tiles), dim3(256), 0, s, (const double*)g->A, g->ld, g->Np, N0, n, t->V,
                                t->Ncap, (const double*)g->Xsc, g->Np, (const double*)t->Csc, t->d, t->Mp, t->M, g->kernel, g->amp2,
-                               t->mu, t->var);
+                               t->mu, t->var, (const double*)t->rhs);
+        } else
+            hipLaunchKernelGGL(track_append_kernel<false>, dim3(t->tiles), dim3(256), 0, s, (const double*)g->A, g->ld, g->Np, N0, n, t->V,
+                               t->Ncap, (const double*)g->Xsc, g->Np, (const double*)t->Csc, t->d, t->Mp, t->M, g->kernel, g->amp2,
+                               t->mu, t->var, (const double*)nullptr);
     }
     t->N = g->N;
     HIPCHK(hipGetLastError());

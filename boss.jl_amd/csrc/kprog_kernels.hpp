@@ -57,12 +57,14 @@ __global__ void kprog_scale_set_kernel(const double* __restrict__ Xraw, double* 
 // A[i + j·ld] for i >= j; rows / columns >= N are those of the identity.  hyp = {(α+1e-8)², (σ+1e-8)²} on the device.
 // blockIdx.z = parameter set (as aug_gram_kernel / gibbs_gram_kernel): set z reads its scaled points at Xsc + z·sX and its hyp at
 // hyp + z·sHyp and writes A + z·bstride; a handle's update launches grid.z = 1 with zero strides.
+// tile0: triangular index of the first tile (gram_kernel's): 0 for a whole matrix; the block rows of an append (append_rows_enqueue)
+// launch the 4·kb + 3 tiles of block row kb from tile kb (2 kb + 1) — per tile a full build's arithmetic.
 __global__ __launch_bounds__(64 * KPROG_MAX_WAVES) void kprog_gram_kernel(FitProg g, const double* __restrict__ Xsc, size_t sX, int d, int N, int Np,
                                                                           const double* __restrict__ hyp, size_t sHyp, double* __restrict__ A, int ld,
-                                                                          size_t bstride) {
+                                                                          size_t bstride, int tile0) {
     extern __shared__ __attribute__((aligned(16))) char kprog_lds_raw[];
     double* col = reinterpret_cast<double*>(kprog_lds_raw) + threadIdx.x;
-    const int st = blockDim.x, t = blockIdx.x;
+    const int st = blockDim.x, t = tile0 + blockIdx.x;
     Xsc += (size_t)blockIdx.z * sX;
     hyp += (size_t)blockIdx.z * sHyp;
     A += (size_t)blockIdx.z * bstride;
@@ -141,6 +143,43 @@ __global__ void kprog_var_set_kernel(const PredSet* __restrict__ sets, const dou
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j < M) ps.var[j] = pvar[(size_t)blockIdx.y * spv + j] + ps.var[j] + PREDICT_JITTER;
 }
+
+// The new column of a rank-one append on resident inverse factors (boss_kgp_set_sequential, append_locked): column 0 of the 32-wide
+// tile kstar_rows_kernel writes there for the built-in kernels, out[row·32] = (α+1e-8)² f(u_row, u_new) for row < N0 and 0 for
+// N0 <= row < Np (winv_gemv_kernel<1> reads nothing else of the tile) — the entry kprog_kstar_body evaluates, row point first — and
+// kself[0] = (α+1e-8)² f(u_new, u_new), the prior variance the new diagonal entry starts from.  u_new is candidate 0 of Csc [d][Mp].
+// One row per thread: kprog_kstar_kernel<32> on a one-candidate block keeps 2 lanes of every wave busy (measured: 0.96 ms per
+// append at N = 4096, d = 8, 31 instructions, against 0.14 ms with this kernel).
+__global__ __launch_bounds__(64 * KPROG_MAX_WAVES) void kprog_col_kernel(FitProg g, const double* __restrict__ Xsc, int d, int N0, int Np,
+                                                                         const double* __restrict__ Csc, int Mp, double amp2,
+                                                                         double* __restrict__ out, double* __restrict__ kself) {
+    extern __shared__ __attribute__((aligned(16))) char kprog_lds_raw[];
+    double* col = reinterpret_cast<double*>(kprog_lds_raw) + threadIdx.x;
+    const int st = blockDim.x, row = blockIdx.x * st + threadIdx.x;
+    if (row < Np) out[(size_t)row * 32] = row < N0 ? amp2 * kprog_pair(g, d, Xsc, Np, row, Csc, Mp, 0, col, st) : 0.0;
+    if (row == 0) kself[0] = amp2 * kprog_pair(g, d, Csc, Mp, 0, Csc, Mp, 0, col, st);
+}
+
+// Tracked candidates of a program-kernel posterior (boss_kgp_set_sequential): the right-hand sides of up to TRACK_ROWS appended rows,
+// rhs[tile][q][32] = (α+1e-8)² f(u_{N0+q}, u*_j) for q < n — row point first, the entry kprog_kstar_body puts into a fresh K* — and
+// 0 for q >= n and for candidates >= M, as there.  Grid = candidate tiles, workgroup and LDS from kprog_block, every thread walks its
+// (row, candidate) entries in a stride loop.  track_append_kernel<true> (grad_kernels.hpp) reads the buffer where the built-in
+// instantiation evaluates kappa_r2: the interpreter's LDS column per thread does not fit beside that kernel's 256 threads
+// (96 slots × 256 threads × 8 B > a CU's 160 KiB), so the pair is two launches.
+__global__ __launch_bounds__(64 * KPROG_MAX_WAVES) void kprog_track_rhs_kernel(FitProg g, const double* __restrict__ Xsc, int d, int Np, int N0, int n,
+                                                                               const double* __restrict__ Csc, int Mp, int M, double amp2,
+                                                                               double* __restrict__ rhs) {
+    constexpr int BN = 32;
+    extern __shared__ __attribute__((aligned(16))) char kprog_lds_raw[];
+    double* col = reinterpret_cast<double*>(kprog_lds_raw) + threadIdx.x;
+    const int st = blockDim.x, c0 = blockIdx.x * BN;
+    double* out = rhs + (size_t)blockIdx.x * TRACK_ROWS * BN;
+    for (int e = threadIdx.x; e < TRACK_ROWS * BN; e += st) {
+        const int q = e / BN, c = e % BN;
+        out[e] = (q < n && c0 + c < M) ? amp2 * kprog_pair(g, d, Xsc, Np, N0 + q, Csc, Mp, c0 + c, col, st) : 0.0;
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // Gradients of a program-kernel posterior (boss_kgp_set_grad): the reverse sweep kern_grad behind fit_eval gives all 2d partials
 // f_u = ∂f/∂u, f_v = ∂f/∂v of a pair.  A column then holds 2·(2d + nI) doubles, values | adjoints (kprog_grad_slots): the longest

@@ -936,11 +936,13 @@ __global__ __launch_bounds__(256) void linv_col_gemv_kernel(const double* __rest
 }
 
 // Σ of the gemv partials (fixed-order tree), then d, z_new; scal = {logdet, zᵀz} is advanced, dz = {d, z_new};
-// a non-positive d² is reported like a failed pivot (info = N0 + 1).
+// a non-positive d² is reported like a failed pivot (info = N0 + 1).  kself: k(x_new, x_new) of a program kernel, evaluated on the
+// device (kprog_append_col_launch) — null for the built-in kernels, whose prior variance is hyp[0] = (α+1e-8)².
 __global__ __launch_bounds__(256) void append_scalars_kernel(const double* __restrict__ part, int nwg, const double* __restrict__ hyp,
                                                              const double* __restrict__ y, const double* __restrict__ mean, int N0,
                                                              double* __restrict__ scal, double* __restrict__ dz, int* __restrict__ info,
-                                                             double* __restrict__ host_out = nullptr, unsigned long long res_seq = 0) {
+                                                             double* __restrict__ host_out = nullptr, unsigned long long res_seq = 0,
+                                                             const double* __restrict__ kself = nullptr) {
     __shared__ double red[2][256];
     const int tid = threadIdx.x;
     double s = 0.0, z = 0.0;
@@ -959,7 +961,7 @@ __global__ __launch_bounds__(256) void append_scalars_kernel(const double* __res
         __syncthreads();
     }
     if (tid == 0) {
-        const double d2 = hyp[0] + hyp[1] - red[0][0];
+        const double d2 = (kself ? kself[0] : hyp[0]) + hyp[1] - red[0][0];
         if (!(d2 > 0.0)) *info = N0 + 1;
         const double dd = sqrt(d2), zn = (y[N0] - mean[N0] - red[1][0]) / dd;
         dz[0] = dd;

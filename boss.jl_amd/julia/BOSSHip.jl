@@ -1380,6 +1380,7 @@ end
 # not bound: boss_kgp_create — a posterior handle over a kernel program; needs boss_kern_create
 # not bound: boss_kern_grad_host — see boss_kern_create (the host run of a kernel program's reverse sweep, used by tests)
 # not bound: boss_kgp_set_grad — switches gradients on for a boss_kgp_create handle; needs boss_kern_create
+# not bound: boss_kgp_set_sequential — switches appends and tracked candidates on for a boss_kgp_create handle; needs boss_kern_create
 # not bound: boss_kgp_loglike_batch — S parameter sets of a kernel-program posterior in one call; needs boss_kern_create
 # not bound: boss_kgp_fit_batch — S kernel-program posteriors out of one batched factorisation; needs boss_kern_create
 # not bound: boss_acq_ei_warp — acquisition of a warped model in one call; needs boss_warp_create

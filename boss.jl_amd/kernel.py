@@ -18,6 +18,10 @@ program (api.KernelProgram.grad, the reverse sweep the gradient kernels run): at
 finite and agree with central differences of the closure (h = 1e-5) within 1e-6·max(1, |∂f|) — truncation is of order h², rounding of
 order ε/h, both far below that —, and at 8 coincident pairs (u, u) every partial must be finite (a one-sided cusp has no central
 difference to agree with; the sweep passes a local partial of exactly 0 on as 0, which is what makes exp(-sqrt(r2)) finite there).
+
+DeviceKernel(f, x_dim, sequential=True) switches appends and tracked candidates on (boss_kgp_set_sequential), independently of grad:
+slice.append, post.append, model_posterior(..., reserve=…) and HipSequentialBatchAM (tracked candidates or the untracked loop) then
+work as for a built-in kernel.  Covariances, devices=[…], warps and the gradient-observation / nonstationary models stay refused.
 """
 from __future__ import annotations
 
@@ -118,12 +122,14 @@ def trace_kernel(closure: Callable, x_dim: int, grad: bool = False) -> api.Kerne
 
 class DeviceKernel:
     """The covariance closure with its traced program: HipGaussianProcess(kernel=DeviceKernel(f, x_dim)).  Calling it calls the
-    original closure.  `program` is the api.KernelProgram.  grad=True: the model's handles carry gradients (module docstring)."""
+    original closure.  `program` is the api.KernelProgram.  grad=True: the model's handles carry gradients; sequential=True: they take
+    appends and tracked candidates (module docstring)."""
 
-    def __init__(self, closure: Callable, x_dim: int, grad: bool = False):
+    def __init__(self, closure: Callable, x_dim: int, grad: bool = False, sequential: bool = False):
         self.closure = closure
         self.x_dim = int(x_dim)
         self.grad = bool(grad)
+        self.sequential = bool(sequential)
         self.program = trace_kernel(closure, x_dim, self.grad)
 
     def __call__(self, u, v):
@@ -136,14 +142,18 @@ def device_kernel_of(model) -> Optional[DeviceKernel]:
     return k if isinstance(k, DeviceKernel) else None
 
 
-def refuse_device_kernel(model, what: str, grad_ok: bool = False):
+def refuse_device_kernel(model, what: str, grad_ok: bool = False, seq_ok: bool = False):
     """NotImplementedError for the parts of the plugin surface a DeviceKernel model does not reach.  grad_ok: the part needs only
-    gradients, which DeviceKernel(..., grad=True) provides."""
+    gradients, which DeviceKernel(..., grad=True) provides; seq_ok: it needs only appends / tracked candidates, which
+    DeviceKernel(..., sequential=True) provides."""
     dk = device_kernel_of(model)
-    if dk is None or (grad_ok and dk.grad):
+    if dk is None or (grad_ok and dk.grad) or (seq_ok and dk.sequential):
         return
     if grad_ok:
         raise NotImplementedError(f"{what} is not available for a model whose kernel is a DeviceKernel traced without gradients: "
                                   "DeviceKernel(f, x_dim, grad=True) switches candidate / likelihood gradients on")
+    if seq_ok:
+        raise NotImplementedError(f"{what} is not available for a model whose kernel is a plain DeviceKernel: "
+                                  "DeviceKernel(f, x_dim, sequential=True) switches appends and tracked candidates on")
     raise NotImplementedError(f"{what} is not available for a model whose kernel is a DeviceKernel (a traced program kernel has no "
-                              "covariances, appends, tracks, warps or in-library multi-device path yet)")
+                              "covariances, warps or in-library multi-device path yet)")

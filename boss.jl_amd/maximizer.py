@@ -427,14 +427,17 @@ class HipSequentialBatchAM:
     point; here the posteriors stay resident and each speculative observation is a block Cholesky
     append (boss_gp_append, O(N^2)) under the unchanged hyper-parameters — same posterior.  When the
     inner maximiser's candidate set is fixed (`points`, or a seeded sample) the candidates' predictive
-    state stays resident too (boss_track_*) and is extended in O(N·M) per selection."""
+    state stays resident too (boss_track_*) and is extended in O(N·M) per selection.  A model under a DeviceKernel takes both
+    routes when the kernel was traced with sequential=True (boss_kgp_set_sequential), and raises NotImplementedError otherwise."""
     am: HipBatchAM
     batch_size: int
 
     def maximize_acquisition(self, problem: BossProblem, options: BossOptions = BossOptions()):
         import copy
+        if int(self.batch_size) < 1:
+            raise ValueError(f"HipSequentialBatchAM: batch_size = {self.batch_size}, at least one point is selected")
         _no_warp(problem, "HipSequentialBatchAM (appending observations, tracked candidates)")
-        refuse_device_kernel(problem.model, "HipSequentialBatchAM (appending observations, tracked candidates)")
+        refuse_device_kernel(problem.model, "HipSequentialBatchAM (appending observations, tracked candidates)", seq_ok=True)
         prob = copy.copy(problem)                                        # problem_ = deepcopy(problem) (batch.jl:27)
         prob.data = type(problem.data)(problem.data.X.copy(), problem.data.Y.copy())
         posts = posteriors_of(prob, reserve=self.batch_size)             # no re-allocation when the appends arrive

@@ -63,9 +63,10 @@ class HipGaussianProcess:
     `parametric` (or `mean`, with theta_dim = 0) may be a DeviceMean: values and exact Jacobians then come from its traced program on
     the device, and `parametric_jac` is ignored.
     `kernel`: "matern32" | "matern52" | "sqexp", or a DeviceKernel (kernel.py) — a user-defined covariance function traced into a
-    device program (boss_kgp_create).  Such a model fits, predicts and drives HipBatchedMAP / HipBatchAM / bo; what needs covariances,
-    appends or tracks raises NotImplementedError, and so does what needs gradients (mean_and_var_grad, data_loglike_grad_batch,
-    HipGradientMAP, HipSampleOptMAP, HipGradientAM) unless the kernel was traced with DeviceKernel(f, x_dim, grad=True)."""
+    device program (boss_kgp_create).  Such a model fits, predicts and drives HipBatchedMAP / HipBatchAM / bo; what needs covariances
+    raises NotImplementedError, and so does what needs gradients (mean_and_var_grad, data_loglike_grad_batch, HipGradientMAP,
+    HipSampleOptMAP, HipGradientAM) unless the kernel was traced with DeviceKernel(f, x_dim, grad=True), and what needs appends or
+    tracked candidates (append, model_posterior(..., reserve=…), HipSequentialBatchAM) unless it was traced with sequential=True."""
     lengthscale_priors: Sequence
     amplitude_priors: Sequence
     noise_std_priors: Sequence
@@ -93,7 +94,7 @@ class HipGaussianProcess:
         """An unfitted resident handle for one output: boss_gp_create, or boss_kgp_create under a DeviceKernel."""
         dk = device_kernel_of(self)
         if dk is not None:
-            return api.KernelGP(X, y, dk.program, self.discrete, self.device, grad=dk.grad)
+            return api.KernelGP(X, y, dk.program, self.discrete, self.device, grad=dk.grad, sequential=dk.sequential)
         return api.GP(X, y, self.kernel, self.discrete, self.device)
 
     # ------------------------------------------------------------------ prior mean on the device (DeviceMean)
@@ -322,9 +323,11 @@ class HipGaussianProcess:
         mX = self.mean_values(data.X, params, i) if mean_X is None else mean_X
         if device_kernel_of(self) is not None:
             if reserve:
-                refuse_device_kernel(self, "model_posterior with room for appends (HipSequentialBatchAM)")
+                refuse_device_kernel(self, "model_posterior with room for appends (HipSequentialBatchAM)", seq_ok=True)
             g = self._new_gp(data.X, data.Y[i])
             try:
+                if reserve:
+                    g.reserve(g.N + reserve)
                 g.update(params.lengthscales[:, i], params.amplitudes[i], params.noise_std[i], mX)
             except Exception:
                 g.close()
@@ -355,7 +358,8 @@ class HipGaussianProcess:
                     lam = np.stack([p.lengthscales[:, i] for p in params], axis=1)
                     amp, sig = [p.amplitudes[i] for p in params], [p.noise_std[i] for p in params]
                     if dk is not None:
-                        gps, _, st = api.kgp_fit_batch(data.X, data.Y[i], dk.program, lam, amp, sig, mX, self.discrete, self.device, grad=dk.grad)
+                        gps, _, st = api.kgp_fit_batch(data.X, data.Y[i], dk.program, lam, amp, sig, mX, self.discrete, self.device, grad=dk.grad,
+                                                       sequential=dk.sequential)
                     else:
                         gps, _, st = api.fit_batch(data.X, data.Y[i], self.kernel, lam, amp, sig, mX, self.discrete, self.device)
                     if np.any(st != 0):
@@ -438,7 +442,7 @@ class HipGaussianProcessPosteriorSlice:
         """Posterior of the data augmented by (x, y_i) under the same hyper-parameters — what
         model_posterior returns after augment_dataset! (problem.jl:191-198) — as a block Cholesky
         append on the resident factor (boss_gp_append).  x: length-d vector or d×n matrix."""
-        refuse_device_kernel(self.model, "append")
+        refuse_device_kernel(self.model, "append", seq_ok=True)
         x = np.asarray(x, float)
         return self.gp.append(x, y_i, self._mean_s(x))
 

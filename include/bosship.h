@@ -785,7 +785,19 @@ int boss_acq_ei_grad_warp(const boss_warp_t* warp, int P, int S, boss_gp_t* cons
  * ∂K_ij/∂λ_m = −α² (f_u,m u_i,m + f_v,m u_j,m)/(λ_m+1e-8), and at a candidate
  *   ∇μ_m = ∇m_m + Σ_i a_i α² f_v,m(u_i, u*)/(λ_m+1e-8),
  *   ∇σ²_m = [α² (f_u,m + f_v,m)(u*, u*) − 2 Σ_i w_i α² f_v,m(u_i, u*)]/(λ_m+1e-8),   w = K⁻¹ k*,
- * 0 in discrete dims.  A call that holds an unflagged program handle is refused as before.  Every other refusal stands. */
+ * 0 in discrete dims.  A call that holds an unflagged program handle is refused as before.  Every other refusal stands.
+ *
+ * Appends and tracked candidates are opt-in as well.  boss_kgp_set_sequential(g, on) sets or clears a second flag, independent of
+ * the gradient flag, on a boss_kgp_create handle or a member of boss_kgp_fit_batch (BOSS_E_INVALID for NULL and for any other
+ * handle, "was not created by boss_kgp_create"), before or after boss_gp_update; nothing resident changes.  While it is set,
+ * boss_gp_append (block rows, re-factorisation, or — from the second single observation on — the rank-one append on the resident
+ * inverse factors, through device buffers), boss_gp_reserve and boss_track_create take the handle, and boss_track_sync /
+ * boss_track_moments / boss_track_free and boss_acq_ei_tracks follow: the new Gram rows, the new column K(X, x_new), the new
+ * diagonal entry k(x_new, x_new) + (σ+1e-8)² and the right-hand side k(x_r, x*) of a tracked row are the program's, evaluated on the
+ * device; the tracked σ² is the unclipped k(x*, x*) − Σv² + 1e-18.  A member of a set is detached from its slab by its first append.
+ * Without the flag these calls are refused as before ("program-kernel posteriors ... without boss_kgp_set_sequential"), and every
+ * other refusal (boss_gp_update_acq, boss_gp_predict_cov, boss_multi_*, the warp, Monte-Carlo EI and latent-model calls,
+ * boss_debug_rider_replay) holds for a flagged handle too. */
 typedef struct boss_kern boss_kern_t;
 int boss_kern_create(int d, int n_const, const double* consts, int n_instr, const int* code, int out_id, boss_kern_t** out);
 void boss_kern_free(boss_kern_t* kern);
@@ -794,6 +806,7 @@ int boss_kgp_create(int device, int d, int N, const double* X, const double* y, 
                     const boss_kern_t* kern, boss_gp_t** out);
 int boss_kern_grad_host(const boss_kern_t* kern, int n, const double* U, const double* V, double* k_out, double* dU, double* dV);
 int boss_kgp_set_grad(boss_gp_t* g, int on);
+int boss_kgp_set_sequential(boss_gp_t* g, int on);
 
 /* S hyper-parameter sets of one output slice under ONE kernel program: `loglike.(samples)` of SamplingMAP
  * (src/model_fitters/sampling.jl:59-78) and the S posteriors of a Bayesian-inference fit (src/posterior.jl:15-19).
